@@ -13,8 +13,12 @@ the sweeps themselves (--exchange rccl: one RCCL all-gather instead), every rank
 runs of the default config also time configs[3] (the 10000x5x10000 cube over the same ranks) into the extra key
 "sharded_10000x5x10000".
 
-Prints ONE JSON line (rank 0).  Extra keys: roofline (dominant kernel, live HIP-event timing on the engine's stream),
-cpu_baseline (the AVX2+threads CPU port of the reference path, timed on this host; N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline keys (metric,
+value, unit, ms_per_step, ...).  --full adds everything else, each in runs of its own after the timed steps: roofline (dominant
+kernel, live HIP-event timing on the engine's stream), cpu_baseline (the AVX2+threads CPU port of the reference path, timed on
+this host; N=1 only) and parity against it, the latency distribution, the resident sweep, the sharded extras and the M / L1
+points.  --dump-outputs DIR writes the question ids the last timed step returned (DIR/selected_question.npy; batched configs:
+DIR/selected_questions.npy, one per quiz) for comparing two builds on the same seeded cube.
 """
 from __future__ import annotations
 
@@ -57,9 +61,15 @@ SEED = 20260928
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=5000,
-                    help="untimed steps first (the default is long enough for the GPU's clocks to settle: +2-4 %% at S)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 2000; batched configs: 20, or 3 for cubes over 1e8 elements)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps first (default 5000, long enough for the GPU's clocks to settle: +2-4 %% at S; batched configs: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside `value`: latency distribution, resident sweep, native caller, "
+                         "rooflines, pipelined / graph / batched rates, quiz loops, sharded extras, the M and L1 points, CPU baseline "
+                         "and parity against the CPU port (a plain run sets up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (float64)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="S")
     ap.add_argument("--variant", type=int, default=0, help="force an eval kernel shape (0 = auto)")
     ap.add_argument("--batch", type=int, default=-1,
@@ -119,6 +129,12 @@ def main():
 
     cfg = CONFIGS[args.config]
     Q, K, T = cfg["Q"], cfg["K"], cfg["T"]
+    if args.steps is None:
+        args.steps = (3 if Q * T > 1e8 else 20) if "quizzes" in cfg else 2000
+    if args.warmup is None:
+        args.warmup = 1 if "quizzes" in cfg else 5000
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if "quizzes" in cfg:
         if args.batch > 0 and args.batch != cfg["quizzes"]:
             cfg = dict(cfg, quizzes=args.batch, traffic_key="%s_b%d" % (args.config, args.batch))   # (--config L1 --batch 32: the small-batch point)
@@ -268,21 +284,25 @@ def main():
             barrier()
     elapsed, sel = timed(step, args.warmup, args.steps)
     value = args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, selected_question=[sel])   # what PqaEngine_NextQuestion returns: the question id
 
     # ---- per-step latency distribution of the same synchronous call (median and p10 / p90)
-    lat = []
-    for _ in range(min(args.steps, 2000)):
-        t1 = time.perf_counter()
-        step()
-        lat.append(time.perf_counter() - t1)
-    lat.sort()
-    latency_us = {"p10": 1e6 * lat[len(lat) // 10], "p50": 1e6 * lat[len(lat) // 2], "p90": 1e6 * lat[(9 * len(lat)) // 10],
-                  "n": len(lat)}
+    latency_us = None
+    if args.full:
+        lat = []
+        for _ in range(min(args.steps, 2000)):
+            t1 = time.perf_counter()
+            step()
+            lat.append(time.perf_counter() - t1)
+        lat.sort()
+        latency_us = {"p10": 1e6 * lat[len(lat) // 10], "p50": 1e6 * lat[len(lat) // 2], "p90": 1e6 * lat[(9 * len(lat)) // 10],
+                      "n": len(lat)}
 
     # ---- the dominant kernel ON THE `value` PATH.  Resident sweep: eval_server_f64's own 100 MHz clock, request in hand to answer
     # published, per step (engine option server_last_step_ns); a launch per selection: eval_questions_f64, HIP events below.
     server_step_us = None
-    if resident:
+    if args.full and resident:
         ticks = []
         for _ in range(max(50, min(args.steps, 500))):
             step()
@@ -297,7 +317,7 @@ def main():
     # ---- the same synchronous call made by native code (libPqaClient.so: n x PqaEngine_NextQuestion, no Python between the calls):
     # what of a step is the wrapper's
     native = None
-    if selector is None:
+    if args.full and selector is None:
         n_nat = max(500, min(args.steps, 5000))
         dt_n, sel_n = interop.time_selections_native(eng, quiz, 200, n_nat)
         native = {"resident" if resident else "launched": {"selections_per_sec": n_nat / dt_n, "us_per_step": 1e6 * dt_n / n_nat,
@@ -305,7 +325,7 @@ def main():
         if server_step_us:
             native["resident"]["host_overhead_us"] = 1e6 * dt_n / n_nat - server_step_us["mean"]
     launch_rate = None
-    if resident:
+    if args.full and resident:
         eng.set_option("server", 0)   # everything below launches kernels that would wait for the resident one to leave
         dt_l, sel_l = timed(step, min(args.warmup, 500), max(200, args.steps // 2))
         launch_rate = {"selections_per_sec": max(200, args.steps // 2) / dt_l, "agrees_with_resident": int(sel_l) == int(sel)}
@@ -316,7 +336,7 @@ def main():
     # ---- extra (not `value`): the same synchronous call through the resident sweep kernel (engine option server = 1: opt-in -- it keeps
     # every CU polling for up to server_idle_us after a selection), where the engine has one for the cube's shape
     resident_extra = None
-    if not resident and selector is None and not args.no_server and not uses_collective:
+    if args.full and not resident and selector is None and not args.no_server and not uses_collective:
         eng.set_option("server", 1)
         if eng.get_option("server_active") == 1:
             n_r = max(200, args.steps)
@@ -337,12 +357,12 @@ def main():
                                       "the selections, request and answer through pinned / BAR-mapped memory; resident_step_us is the kernel's own 100 MHz "
                                       "clock per step, request in hand to answer published"}
         eng.set_option("server", 0)
-    kernel_ms = kernel_ms_of(eng, quiz, max(20, min(args.steps, 200)))
+    kernel_ms = kernel_ms_of(eng, quiz, max(20, min(args.steps, 200))) if args.full else None
     # ... and the sweep's launch INSIDE the synchronous call `value` times: HIP events recorded by the engine on its stream right
     # around the launch (option time_sweeps), dispatch to retirement -- what a kernel trace of this command shows per launch
     # (profiles/): a launch onto an idle device does not overlap its ramp with the previous one's tail as back-to-back launches do
     sync_kernel_us = None
-    if selector is None and not resident:
+    if args.full and selector is None and not resident:
         eng.set_option("time_sweeps", 1)
         ts = []
         for _ in range(max(50, min(args.steps, 500))):
@@ -356,13 +376,9 @@ def main():
             sync_kernel_us = {"mean": sum(ts) / len(ts), "p10": ts[len(ts) // 10], "p50": ts[len(ts) // 2], "p90": ts[(9 * len(ts)) // 10], "n": len(ts)}
     alg_bytes = q_local * (K + 1) * T * 8  # one read of every sA row and the mD row, fp64
     alg_flops = q_local * K * T * FLOPS_PER_ELEMENT   # ~45 fp64 operations per (question, answer, target)
-    launched_us = kernel_ms * 1e3
-    # the contract's kernel = the one `value` was measured through
-    path_us = server_step_us["mean"] if server_step_us else launched_us
-    achieved = alg_bytes / (path_us * 1e-6) / 1e9
 
     # ---- stream-ordered (pipelined) throughput: selections enqueued back to back, results left on the device
-    if selector is None:
+    if args.full and selector is None:
         for _ in range(5):
             eng.enqueue_select_argmax(quiz)
         torch.cuda.synchronize()
@@ -376,7 +392,7 @@ def main():
 
     # ---- extra (not `value`): the same synchronous selection replayed from a HIP graph (SURVEY 8(d) asks for the variant)
     graph_rate = None
-    if selector is None:
+    if args.full and selector is None:
         eng.set_option("use_graph", 1)
         for _ in range(50):
             eng.next_question_argmax(quiz)
@@ -390,7 +406,7 @@ def main():
 
     # ---- extra (not `value`): many quizzes in flight, one launch per batch (PqaEngine_NextQuestionArgmaxBatch)
     batched = None
-    if selector is None and args.batch > 0:
+    if args.full and selector is None and args.batch > 0:
         quizzes = [quiz] + [eng.start_quiz() for _ in range(args.batch - 1)]
         reps = max(3, min(200, args.steps // args.batch))
         for _ in range(2):
@@ -407,7 +423,7 @@ def main():
     # sampled selector, RecordAnswer by the binary-search rule, ListTopTargets(1), until the guess is on top or 30 questions
     # were asked, then RecordQuizTarget.  On the synthetic trained cube of this run, not from a fresh KB.
     quiz_loop = None
-    if selector is None and args.config == "S" and not args.no_quiz_loop:
+    if args.full and selector is None and args.config == "S" and not args.no_quiz_loop:
         from probqa_amd import synth
 
         eng.set_option("select", 0)
@@ -469,7 +485,7 @@ def main():
     exchanges_s, sharded_m, sharded_l1 = None, None, None
     ranks_seen = ctl.rccl_ranks_seen()          # (every rank takes part)
     want = set(x for x in args.sharded_configs.split(",") if x)
-    if sharded and args.config == "S":
+    if args.full and sharded and args.config == "S":
         if "S" in want:
             exchanges_s = both_exchanges(eng, quiz, "s", 200, max(500, min(args.steps, 2000)),
                                          None if resident else (args.exchange, {"selections_per_sec": value, "us_per_step": 1e6 / value, "selected_question": int(sel)}))
@@ -496,7 +512,7 @@ def main():
     # device and PqaEngine_NextQuestion fans out over them -- what the reference's unchanged wrappers get).  Rank 0 drives all
     # `world` GPUs while the other ranks wait at a barrier.
     one_process = None
-    if sharded and world > 1:
+    if args.full and sharded and world > 1:
         if rank == 0:
             one_process = {}
             os.environ["PQA_DEVICES"] = ",".join(str(d % n_dev) for d in range(world))
@@ -576,7 +592,7 @@ def main():
     # the HBM-bound point M (BASELINE configs[2]: 10000x5x10000 fp64, one quiz) and the VALU-bound point L1 (configs[4]'s
     # per-GPU shard: 12500x5x100000 fp32, 256 quizzes per batched sweep), each with a bounded parity sample against the CPU port.
     hbm_point_m, valu_point_l1, late_state = None, None, None
-    if not sharded and args.config == "S" and not args.no_points:
+    if args.full and not sharded and args.config == "S" and not args.no_points:
         free_b = torch.cuda.mem_get_info(device)[0]
         if free_b > 12e9:
             hbm_point_m = point_m(args, np, torch, interop, factory, stream, kernel_ms_of)
@@ -593,7 +609,7 @@ def main():
     # the end of every quiz; the engine combines the concurrent NextQuestion calls into batched sweeps and the RecordAnswers
     # into batched launches (engine option "combine").
     quiz_loop_threads, learners_hung = None, False
-    if selector is None and args.config == "S" and not args.no_quiz_loop:
+    if args.full and selector is None and args.config == "S" and not args.no_quiz_loop:
         eng.set_option("select", 0)
         eng.set_option("seed", SEED)
         quiz_loop_threads = {}
@@ -654,17 +670,6 @@ def main():
             "selected_question": int(sel),
         },
         "question_evals_per_sec": value * Q,
-        "step_latency_us": latency_us,
-        # what a synchronous step spends outside the sweep: the request's way to the kernel, the answer's way back, the wrapper
-        "host_overhead_us": (1e6 * elapsed / args.steps - server_step_us["mean"]) if server_step_us else (1e6 * elapsed / args.steps - launched_us),
-        "launch_per_selection": launch_rate if launch_rate is not None else ({"selections_per_sec": value, "note": "this is `value`"} if selector is None else None),
-        "resident_sweep": resident_extra,
-        "native_caller": native,
-        "pipelined_selections_per_sec": pipelined,
-        "batched": batched,
-        "hip_graph_replay": graph_rate,
-        "quiz_loop": quiz_loop,
-        "quiz_loop_threads": quiz_loop_threads,
         # what a scaling run is read by: which exchange `value` used, how many ranks an RCCL collective reached, the node's peer
         # access, and the rate of BOTH exchanges where the run is sharded (one launch per selection on both)
         "multi_gpu": {
@@ -673,60 +678,78 @@ def main():
             "rccl_ranks_seen": ranks_seen,
             "peer_access_matrix": ctl.peer_access_matrix(),
             "selections_per_sec": {k: v.get("selections_per_sec") for k, v in exchanges_s.items() if isinstance(v, dict)} if exchanges_s else
-            {"single_gpu_no_exchange": value},
-        },
-        "exchange_1000x5x1000": exchanges_s,
-        "sharded_10000x5x10000": sharded_m,
-        "sharded_12500x5x100000_per_gpu": sharded_l1,
-        "one_process_sharded_engine": one_process,
-        "hbm_point_M": hbm_point_m,
-        "late_state_S": late_state,
-        "valu_point_L1": valu_point_l1,
-        "roofline": {
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "traffic": pmc_traffic(args.config, world),
-            "traffic_from_other_sources_than_the_tree": pmc_is_stale(args.config),
-            "kernel": ("eval_server_f64 (wg256_np2, resident: one launch serves the selections; the kernel `value` went through)"
-                       if server_step_us else "eval_questions_f64 (%s)" % eng.eval_kernel_name()),
-            "kernel_us": path_us,
-            "kernel_us_source": ("the resident kernel's own 100 MHz clock per step, request in hand to answer published "
-                                 "(mean of %d steps; p10/p50/p90 in resident_step_us)" % server_step_us["n"]) if server_step_us
-            else "HIP events on the engine's stream around back-to-back launches (mean)",
-            # the same kernel launched onto an IDLE device, as every synchronous call of the timed region launches it: the engine's own
-            # HIP events right around the launch (option time_sweeps; the two event markers included), dispatch to retirement.  A launch
-            # by itself does not overlap its ramp with the previous kernel's tail: rocprofv3's per-launch average over the profiled
-            # command (profiles/r06_S_*: mostly such launches) lies between this and kernel_us
-            "synchronous_launch_us": sync_kernel_us,
-            "resident_step_us": server_step_us,
-            "launched_kernel": {"kernel": "eval_questions_f64 (%s)" % eng.eval_kernel_name(), "kernel_us": launched_us,
-                                "achieved": alg_bytes / (launched_us * 1e-6) / 1e9,
-                                "frac": alg_bytes / (launched_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                                "source": "HIP events on the engine's stream around back-to-back launches (mean); the "
-                                          "rocprofv3 --kernel-trace --stats summary of this kernel is under profiles/"},
-            "algorithmic_bytes_per_launch": alg_bytes,
-            "note": "48 MB cube fits the 256 MiB Infinity Cache: achieved GB/s is not an HBM measurement at this size; "
-                    "use --config M for the HBM-bound point" if args.config == "S" else "cube exceeds the Infinity Cache",
-        },
-        # the other roofline ("report both"): the sweep's arithmetic against the fp64 vector peak
-        "roofline_valu": {
-            "bound": "valu_fp64",
-            "achieved": alg_flops / (path_us * 1e-6) / 1e12,
-            "peak": FP64_VECTOR_PEAK_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": alg_flops / (path_us * 1e-6) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
-            "algorithmic_flops_per_launch": alg_flops,
-            "flops_per_element": FLOPS_PER_ELEMENT,
-            "pmc": pmc_valu(args.config, world),
-            "note": "algorithmic flops = Q K T x 45 (the reference's operation count, SURVEY 8(d)); pmc = VALU instructions and "
-                    "VALU-busy cycles per launch of the launched kernel from the committed counter pass (profiles/)",
+            ({"single_gpu_no_exchange": value} if selector is None else {args.exchange: value}),
         },
     }
+    if args.full:
+        launched_us = kernel_ms * 1e3
+        # the contract's kernel = the one `value` was measured through
+        path_us = server_step_us["mean"] if server_step_us else launched_us
+        achieved = alg_bytes / (path_us * 1e-6) / 1e9
+        out.update({
+            "step_latency_us": latency_us,
+            # what a synchronous step spends outside the sweep: the request's way to the kernel, the answer's way back, the wrapper
+            "host_overhead_us": (1e6 * elapsed / args.steps - server_step_us["mean"]) if server_step_us else (1e6 * elapsed / args.steps - launched_us),
+            "launch_per_selection": launch_rate if launch_rate is not None else ({"selections_per_sec": value, "note": "this is `value`"} if selector is None else None),
+            "resident_sweep": resident_extra,
+            "native_caller": native,
+            "pipelined_selections_per_sec": pipelined,
+            "batched": batched,
+            "hip_graph_replay": graph_rate,
+            "quiz_loop": quiz_loop,
+            "quiz_loop_threads": quiz_loop_threads,
+            "exchange_1000x5x1000": exchanges_s,
+            "sharded_10000x5x10000": sharded_m,
+            "sharded_12500x5x100000_per_gpu": sharded_l1,
+            "one_process_sharded_engine": one_process,
+            "hbm_point_M": hbm_point_m,
+            "late_state_S": late_state,
+            "valu_point_L1": valu_point_l1,
+            "roofline": {
+                "bound": "hbm",
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "traffic": pmc_traffic(args.config, world),
+                "traffic_from_other_sources_than_the_tree": pmc_is_stale(args.config),
+                "kernel": ("eval_server_f64 (wg256_np2, resident: one launch serves the selections; the kernel `value` went through)"
+                           if server_step_us else "eval_questions_f64 (%s)" % eng.eval_kernel_name()),
+                "kernel_us": path_us,
+                "kernel_us_source": ("the resident kernel's own 100 MHz clock per step, request in hand to answer published "
+                                     "(mean of %d steps; p10/p50/p90 in resident_step_us)" % server_step_us["n"]) if server_step_us
+                else "HIP events on the engine's stream around back-to-back launches (mean)",
+                # the same kernel launched onto an IDLE device, as every synchronous call of the timed region launches it: the engine's own
+                # HIP events right around the launch (option time_sweeps; the two event markers included), dispatch to retirement.  A launch
+                # by itself does not overlap its ramp with the previous kernel's tail: rocprofv3's per-launch average over the profiled
+                # command (profiles/r06_S_*: mostly such launches) lies between this and kernel_us
+                "synchronous_launch_us": sync_kernel_us,
+                "resident_step_us": server_step_us,
+                "launched_kernel": {"kernel": "eval_questions_f64 (%s)" % eng.eval_kernel_name(), "kernel_us": launched_us,
+                                    "achieved": alg_bytes / (launched_us * 1e-6) / 1e9,
+                                    "frac": alg_bytes / (launched_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                                    "source": "HIP events on the engine's stream around back-to-back launches (mean); the "
+                                              "rocprofv3 --kernel-trace --stats summary of this kernel is under profiles/"},
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "note": "48 MB cube fits the 256 MiB Infinity Cache: achieved GB/s is not an HBM measurement at this size; "
+                        "use --config M for the HBM-bound point" if args.config == "S" else "cube exceeds the Infinity Cache",
+            },
+            # the other roofline ("report both"): the sweep's arithmetic against the fp64 vector peak
+            "roofline_valu": {
+                "bound": "valu_fp64",
+                "achieved": alg_flops / (path_us * 1e-6) / 1e12,
+                "peak": FP64_VECTOR_PEAK_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": alg_flops / (path_us * 1e-6) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
+                "algorithmic_flops_per_launch": alg_flops,
+                "flops_per_element": FLOPS_PER_ELEMENT,
+                "pmc": pmc_valu(args.config, world),
+                "note": "algorithmic flops = Q K T x 45 (the reference's operation count, SURVEY 8(d)); pmc = VALU instructions and "
+                        "VALU-busy cycles per launch of the launched kernel from the committed counter pass (profiles/)",
+            },
+        })
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], cpu_argmax, cpu_margin = cpu_baseline(np, cfg, args.cpu_seconds)
         # north_star: "with the argmax matching CpuEngine" -- the CPU port's priorities of the same cube and quiz state
         # (after StartQuiz), its argmax (lowest index on ties) against the question the timed steps selected
@@ -745,6 +768,13 @@ def main():
         selector.close()
     eng.close()
     ctl.close()
+
+
+def dump_outputs(d, np, **arrays):
+    """--dump-outputs: each array as d/<name>.npy in float64 (question ids are exact in it), so that two builds can be compared."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def self_spawn(n):
@@ -1015,8 +1045,7 @@ def run_batched(args, cfg, np, torch, interop, pdist, ctl, rank, dev_index, devi
     if compact:
         steps, warmup = (2, 1) if Q * T > 1e8 else (10, 2)
     else:
-        steps = args.steps if args.steps != 2000 else (3 if Q * T > 1e8 else 20)       # the defaults are sized for the S config
-        warmup = args.warmup if args.warmup != 5000 else 1
+        steps, warmup = args.steps, args.warmup
     factory = interop.PqaEngineFactory()
     stream = torch.cuda.Stream(device=device)
     torch.cuda.set_stream(stream)
@@ -1081,13 +1110,17 @@ def run_batched(args, cfg, np, torch, interop, pdist, ctl, rank, dev_index, devi
         return dt, ev0.elapsed_time(ev1) / steps, picks
 
     dt, kernel_ms, picks = timed_steps(step_shm)
+    if args.dump_outputs and rank == 0 and not compact:
+        dump_outputs(args.dump_outputs, np, selected_questions=picks)   # one question id per quiz of the batch
     exchange = None
     if world > 1:
         exchange = {"shm": {"selections_per_sec": B * steps / dt, "ms_per_step": 1e3 * dt / steps, "selected_question_of_quiz_0": int(picks[0])}}
-        if ctl.rccl:
+        if ctl.rccl and args.full:
             dt_r, _, picks_r = timed_steps(step_rccl)
             exchange["rccl"] = {"selections_per_sec": B * steps / dt_r, "ms_per_step": 1e3 * dt_r / steps, "selected_question_of_quiz_0": int(picks_r[0]),
                                 "same_picks_as_shm": [int(x) for x in picks_r] == [int(x) for x in picks]}
+        elif ctl.rccl:
+            exchange["rccl"] = {"skipped": "measured with --full"}
         else:
             exchange["rccl"] = {"skipped": "the ranks share a device: RCCL refuses that"}
     value = B * steps / dt
@@ -1169,7 +1202,7 @@ def run_batched(args, cfg, np, torch, interop, pdist, ctl, rank, dev_index, devi
                     "side idles (SURVEY 8(d)) -- `traffic` above is the measured fetch per batch, priors included",
         },
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], out["sample_parity"] = cpu_baseline_batched(np, cfg, eng, quizzes, args.cpu_seconds, f32)
         out["argmax_vs_cpu"] = argmax_share(np, cfg, eng, quizzes, picks, f32)
     if shm is not None:

@@ -18,7 +18,7 @@ for i in 1 2; do
     (cd $c && python tools/sweep_timing.py 500x5x500 1000x5x1000 2000x5x2000 4000x5x4000 8000x5x8000 10000x5x10000 2>/dev/null | sed "s|^|$c |")
     (cd $c && python tools/f32_single_bench.py 2000 5 100000 10 2>/dev/null | sed "s|^|$c |")
     (cd $c && python tools/f32_single_bench.py 10000 5 10000 20 2>/dev/null | sed "s|^|$c |")
-    (cd $c && python bench.py --no-points 2>/dev/null | python -c "
+    (cd $c && python bench.py $(grep -q -e "\"--full\"" bench.py && echo --full) --no-points 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r = d['roofline']
 print('$c', 'S: value', round(d['value']), 'resident step', round(r['resident_step_us']['mean'], 2), 'launched kernel', round(r['launched_kernel']['kernel_us'], 2),

@@ -15,7 +15,7 @@ case $CFG in
   custom:*) KERNEL=${CFG#custom:}; shift 2; CMD="$*"; CFG=$KERNEL ;;
   L1_b*) CMD="python $PWD/bench.py --config L1 --batch ${CFG#L1_b} --steps $STEPS --warmup 1 --no-cpu-baseline"; KERNEL=eval_batch_kernel ;;
   L1|LS|SB) CMD="python $PWD/bench.py --config $CFG --steps $STEPS --warmup 1 --no-cpu-baseline"; KERNEL=eval_batch_kernel ;;
-  *) CMD="python $PWD/bench.py --config $CFG --variant $VAR --steps $STEPS --warmup 5 --no-cpu-baseline --batch 0 --no-server --no-quiz-loop --no-points"; KERNEL=eval_questions ;;
+  *) CMD="python $PWD/bench.py --config $CFG --variant $VAR --steps $STEPS --warmup 5 --full --no-cpu-baseline --batch 0 --no-server --no-quiz-loop --no-points"; KERNEL=eval_questions ;;   # (--full: the launches the profiles of earlier rounds counted)
 esac
 cd /tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD > $OUT/bench_trace.json 2> $OUT/trace.err

@@ -1,3 +1,5 @@
+# OUT: the folder this run's outputs are collected in, the one tools/promote_profiles.py copies into profiles/ (the bench lines go there)
+: "${OUT:?set OUT to the output folder of the run}"
 set -x
 cd $GRAFT_REPO_ROOT
 bash tools/prof.sh r6_S S 0 300 > gpurun_out/prof_r6_S.log 2>&1
@@ -10,11 +12,11 @@ bash tools/prof.sh r6_cluster custom:eval_cluster python $GRAFT_REPO_ROOT/tools/
 # the counter passes go into profiles/traffic.json HERE, on the box, before the bench lines are taken: they report whether the
 # counters they quote belong to the kernel sources in the tree (the copy that is committed is made by the same script at home)
 python tools/promote_profiles.py > gpurun_out/promote_on_box.log 2>&1
-python bench.py > gpurun_out/r6_bench_S.json 2> gpurun_out/r6_bench_S.err
+python bench.py --full > $OUT/r6_bench_S.json 2> $OUT/r6_bench_S.err
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r6_bench_S_driver_command_steps20_warmup5.json 2> gpurun_out/r6_bench_Sd.err
-python bench.py --config M > gpurun_out/r6_bench_M.json 2> gpurun_out/r6_bench_M.err
-python bench.py --config L1 > gpurun_out/r6_bench_L1.json 2> gpurun_out/r6_bench_L1.err
-python bench.py --config L1 --batch 32 > gpurun_out/r6_bench_L1_b32.json 2> gpurun_out/r6_bench_L1_b32.err
+python bench.py --config M --full > $OUT/r6_bench_M.json 2> $OUT/r6_bench_M.err
+python bench.py --config L1 --full > $OUT/r6_bench_L1.json 2> $OUT/r6_bench_L1.err
+python bench.py --config L1 --batch 32 --full > $OUT/r6_bench_L1_b32.json 2> $OUT/r6_bench_L1_b32.err
 cd /tmp && export TMPDIR=/tmp
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pq -o t -- python $GRAFT_REPO_ROOT/tools/quiz_loop_breakdown.py > $GRAFT_REPO_ROOT/gpurun_out/r6_quiz_loop.log 2>&1
 f=$(find /tmp/pq -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && { echo "command: rocprofv3 --kernel-trace --stats -- python tools/quiz_loop_breakdown.py   (bench.py's quiz loop, 600 quizzes)"; grep -v "^W2026\|^E2026" $GRAFT_REPO_ROOT/gpurun_out/r6_quiz_loop.log | tail -12; cat "$f"; } > $GRAFT_REPO_ROOT/gpurun_out/r6_quiz_loop_stats.txt
