@@ -56,11 +56,12 @@ PQACORE_API void *PqaEngineFactory_CreateHipEngineSharded(void *pvFactory, void 
  * "fuse_update" (RecordAnswer's posterior update runs inside the launch of that speculative sweep where its shape allows it -- rows
  * of up to 1024 targets -- instead of in a kernel of its own ahead of it; same bits; default 1; read-only "fused_updates"),
  * "combine" (concurrent client threads: their NextQuestion calls share batched sweeps, their RecordAnswer / StartQuiz /
- * RecordQuizTarget calls share launches, and a call that finds the engine taken posts its operation to the thread inside instead
+ * ResumeQuiz / RecordQuizTarget calls share launches, and a call that finds the engine taken posts its operation to the thread inside instead
  * of queueing on the lock; default 1, also PQA_COMBINE; "combine_linger_us": how long a leader / a ListTopTargets waits for the
  * other clients' requests, default 20; read-only "combined_batches", "combined_requests", "combined_max_batch", "update_flushes",
- * "updates_flushed", "update_max_flush", "posted_ops", "posted_drains", "train_batches", "train_batch_calls"),
- * "long_row_form" (StartQuiz / RecordAnswer over rows beyond 16384 targets as one workgroup per subtask of the reference's sum
+ * "updates_flushed", "update_max_flush", "posted_ops", "posted_drains", "train_batches", "train_batch_calls",
+ * "resume_batches", "resumes_batched"),
+ * "long_row_form" (StartQuiz / RecordAnswer / ResumeQuiz over rows beyond 16384 targets as one workgroup per subtask of the reference's sum
  * plus a division launch; default 1), "post_always" (test hook: the posted form of the quiz-level calls even when the engine is free),
  * "eval_max_grid" (test hook: cap the workgroups of a sweep so that each streams many questions; 0 = no cap).
  * "batch_min" (PqaEngine_NextQuestionArgmaxBatch: batches of at least this many quizzes take the row-sharing sweep, which
@@ -123,6 +124,15 @@ PQACORE_API void *PqaEngine_NextQuestionArgmaxBatch(void *pvEngine, const int64_
  * same batched launch by the engine itself (option "combine"). */
 PQACORE_API void *PqaEngine_RecordAnswerBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pAnswers);
 PQACORE_API void *PqaEngine_StartQuizBatch(void *pvEngine, const int64_t nQuizzes, int64_t *pQuizzes);
+/* ResumeQuiz for nQuizzes quizzes in one call and one launch per chunk.  Quiz i resumes from the pCounts[i] answered
+ * questions starting at pAQs[sum(pCounts[0..i))]; pCounts[i] == 0 is a StartQuiz (BaseEngine.cpp:393-395).  Every posterior is
+ * bit-identical to PqaEngine_ResumeQuiz's for the same list (CEUpdatePriorsSubtaskMul + NormalizePriors + CEDivTargPriors).
+ * All or none: on any error (index out of range, I64Underflow of any quiz, out of memory) no quiz is created and the error
+ * names the batch entry.  pQuizzes receives the ids, in the order consecutive PqaEngine_ResumeQuiz calls would assign them.
+ * No speculative sweep is launched behind the batch.  Concurrent PqaEngine_ResumeQuiz calls of different client threads are
+ * gathered into such a batch by the engine itself (option "combine"; counters "resume_batches", "resumes_batched"). */
+PQACORE_API void *PqaEngine_ResumeQuizBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts,
+                                            const CiAnsweredQuestion *pAQs, int64_t *pQuizzes);
 /* ListTopTargets for nQuizzes quizzes (any number; 256 per launch sequence) without copying a posterior to the host: pDest[i * maxCount + j],
  * j < pCounts[i], is the listing PqaEngine_ListTopTargets(pQuizzes[i], maxCount) returns -- descending probability, gaps and
  * probabilities <= 0 dropped (reference PqaCore/CEHeapifyPriorsSubtaskMake.cpp:42-52), equal probabilities in the order the reference's

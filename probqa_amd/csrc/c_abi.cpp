@@ -432,6 +432,12 @@ PQACORE_API void *PqaEngine_StartQuizBatch(void *pvEngine, const int64_t nQuizze
   ENGINE_OR_RETURN_ERROR;
   return ReturnErr(pEng->StartQuizBatch(nQuizzes, pQuizzes));
 }
+PQACORE_API void *PqaEngine_ResumeQuizBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts, const CiAnsweredQuestion *pAQs,
+                                            int64_t *pQuizzes) {
+  ENGINE_OR_RETURN_ERROR;
+  static_assert(sizeof(CiAnsweredQuestion) == sizeof(AQ), "the answered questions are passed through as they are");
+  return ReturnErr(pEng->ResumeQuizBatch(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pQuizzes));
+}
 PQACORE_API void *PqaEngine_ListTopTargetsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
                                                 CiRatedTarget *pDest, int64_t *pCounts) {
   ENGINE_OR_RETURN_ERROR;

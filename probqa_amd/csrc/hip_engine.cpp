@@ -281,7 +281,7 @@ HipEngine::~HipEngine() {
   for (auto &g : _graphs) hipGraphExecDestroy(g.second.exec);
   hipFree(_dGraphScratch); hipFree(_dTagCell);
   for (QuizPinned *slab : _pinSlabs) hipHostFree(slab);
-  hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
+  hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   if (_hTopBatch) hipHostFree(_hTopBatch);
   hipFree(_dTopExact);
   if (_evSweep[0]) { hipEventDestroy(_evSweep[0]); hipEventDestroy(_evSweep[1]); }
@@ -412,6 +412,8 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "posted_drains") return (int64_t)_postedDrains;
   if (n == "train_batches") return (int64_t)_trainBatches;           // launches that ran posted RecordQuizTarget calls together ...
   if (n == "train_batch_calls") return (int64_t)_trainBatchCalls;    // ... this many of them           // ... in this many rounds
+  if (n == "resume_batches") return (int64_t)_resumeBatches;         // launch sequences that ran posted ResumeQuiz calls together ...
+  if (n == "resumes_batched") return (int64_t)_resumesBatched;       // ... this many of them
   if (n == "update_flushes") return (int64_t)_flushes;              // launches that ran deferred RecordAnswers ...
   if (n == "updates_flushed") return (int64_t)_flushedUpdates;      // ... the updates they ran ...
   if (n == "update_max_flush") return (int64_t)_maxFlush;           // ... and the most in one launch
@@ -544,6 +546,27 @@ void HipEngine::DestroyQuiz(Quiz *q) {
   delete q;
 }
 
+// A quiz's prior and bitmap buffers (q->hAsked sized already): a released quiz's of the same dimensions, or new ones
+hipError_t HipEngine::TakeQuizBuffers(Quiz *q) {
+  while (!_quizBufferPool.empty() && q->dPrior == nullptr) {
+    const QuizBuffers b = _quizBufferPool.back();
+    _quizBufferPool.pop_back();
+    if (b.ldT == _ldT && b.askedWords == q->hAsked.size()) {
+      q->dPrior = b.dPrior;
+      q->dAsked = b.dAsked;
+    } else {  // the knowledge base changed shape since that quiz was released
+      hipFree(b.dPrior);
+      hipFree(b.dAsked);
+    }
+  }
+  hipError_t he = hipSuccess;
+  if (q->dPrior == nullptr) {
+    he = hipMalloc(&q->dPrior, (size_t)_ldT * sizeof(double));
+    if (he == hipSuccess) he = hipMalloc(&q->dAsked, q->hAsked.size() * sizeof(uint32_t));
+  }
+  return he;
+}
+
 void HipEngine::DropQuizBufferPool() {
   for (const QuizBuffers &b : _quizBufferPool) {
     hipFree(b.dPrior);
@@ -586,22 +609,7 @@ int64_t HipEngine::CreateQuiz(Error &err, int64_t nAnswered, const AQ *pAQs, con
     return fail(Error::MakeP(ErrCode::NotImplemented, "Feature=ResumeQuiz across separately driven shards",
                              "An answered question belongs to another shard: its rows are not reachable from this engine alone "
                              "(PQA_DEVICES / the sharded engine of one process resolves them)."));
-  hipError_t he = hipSuccess;
-  while (!_quizBufferPool.empty() && quiz->dPrior == nullptr) {
-    const QuizBuffers b = _quizBufferPool.back();
-    _quizBufferPool.pop_back();
-    if (b.ldT == _ldT && b.askedWords == quiz->hAsked.size()) {
-      quiz->dPrior = b.dPrior;
-      quiz->dAsked = b.dAsked;
-    } else {  // the knowledge base changed shape since that quiz was released
-      hipFree(b.dPrior);
-      hipFree(b.dAsked);
-    }
-  }
-  if (quiz->dPrior == nullptr) {
-    he = hipMalloc(&quiz->dPrior, (size_t)_ldT * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc(&quiz->dAsked, quiz->hAsked.size() * sizeof(uint32_t));
-  }
+  hipError_t he = TakeQuizBuffers(quiz.get());
   const bool startClears = nAnswered == 0 && srcPrior == nullptr;   // StartQuiz: its kernel clears the bitmap itself
   if (he == hipSuccess && !startClears)   // (ResumeQuiz synchronises further down: the host source stays valid)
     he = nAnswered == 0 ? hipMemsetAsync(quiz->dAsked, 0, quiz->hAsked.size() * sizeof(uint32_t), _stream)
@@ -694,7 +702,24 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
     return -1;
   }
   CallScope scope(_activeCallers);
-  std::lock_guard<EngineMutex> lk(_mu);
+  if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // (the engine is taken: the resumes posted meanwhile share ONE launch)
+    PostedOp op;
+    op.kind = 7; op.arg = nAnswered; op.aqs = pAQs;   // (this thread waits for the result: the list stays valid)
+    RunPosted(op);
+    err = op.err;
+    return op.result;
+  }
+  std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
+  if (_optCombine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  else lk.lock();
+  if (nAnswered > 0 && ResumeTakesLongRow(View())) {   // long rows: the multi-workgroup form (hip_engine_resume.cpp), as a batch of one
+    std::vector<ResumeEntry> e(1);
+    e[0].nAnswered = nAnswered;
+    e[0].pAQs = pAQs;
+    err = ResumeEntriesLocked(e, true);
+    if (!e[0].err.ok()) err = e[0].err;
+    return SpeculateFor(err.ok() ? e[0].id : -1);
+  }
   return SpeculateFor(CreateQuiz(err, nAnswered, pAQs, nullptr, nullptr, 0, nullptr));  // nAnswered == 0 -> StartQuiz (BaseEngine.cpp:393-395)
 }
 

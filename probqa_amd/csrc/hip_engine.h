@@ -195,6 +195,7 @@ class IEngine {
   virtual Error RecordAnswerRemote(int64_t iQuiz, int64_t iAnswer) = 0;
   virtual Error RecordAnswerBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers) = 0;
   virtual Error StartQuizBatch(int64_t n, int64_t *pQuizzes) = 0;
+  virtual Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) = 0;
   virtual Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) = 0;
 };
 
@@ -260,6 +261,7 @@ class HipEngine : public IEngine {
   Error RecordAnswerRemote(int64_t iQuiz, int64_t iAnswer) override;
   Error RecordAnswerBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers) override;
   Error StartQuizBatch(int64_t n, int64_t *pQuizzes) override;
+  Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) override;
   Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
@@ -292,6 +294,10 @@ class HipEngine : public IEngine {
   // rowDevices / stageRow (optional): the device each row lives on, and whether it is copied to this device first (no peer access)
   int64_t ResumeQuizRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *const *rows, const int *rowDevices = nullptr,
                          const char *stageRow = nullptr);
+  // ResumeQuizBatch with the row pointers resolved by the sharded engine (2 sum(pCounts) of them, in entry order), staged as
+  // ResumeQuizRows stages them
+  Error ResumeQuizBatchRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *const *rows, const int *rowDevices,
+                            const char *stageRow, int64_t *pQuizzes);
   // .kb arrays of this engine's questions at the file's current position (hip_engine_kb.cpp); the engine's lock is not taken
   Error IoRows(FILE *f, const char *filePath, bool mD, bool write);
   Error IoVB(FILE *f, const char *filePath, bool write);
@@ -342,6 +348,18 @@ class HipEngine : public IEngine {
   bool QuestionUnavailable(const Quiz *q, int64_t qGlobal) const;
   Error RecordAnswerImpl(int64_t iQuiz, int64_t iAnswer, bool remote);
   Error RecordAnswerLocked(int64_t iQuiz, int64_t iAnswer, bool remote, bool flushNow);
+  // ---- batched ResumeQuiz (hip_engine_resume.cpp): the entries of a ResumeQuizBatch, of a drain's posted ResumeQuiz calls, or one
+  // long-row ResumeQuiz.  rows (optional): the entry's 2 nAnswered row pointers, resolved by the sharded engine.
+  struct ResumeEntry { int64_t nAnswered = 0; const AQ *pAQs = nullptr; const void *const *rows = nullptr; Error err; int64_t id = -1; Quiz *quiz = nullptr; };
+  // allOrNone: any failing entry fails the call and no quiz is created (the entry's own error is in e[i].err); otherwise every
+  // entry succeeds or fails on its own.  The ids are assigned in entry order once every launch has been checked.
+  Error ResumeEntriesLocked(std::vector<ResumeEntry> &e, bool allOrNone);
+  hipError_t TakeQuizBuffers(Quiz *q);
+  // the batch's device tables -- slots, statuses, asked bitmaps, row pointers, long-row sums, exponent scratch -- and their
+  // pinned host mirror: grown to the largest chunk so far, reused by every batch after it
+  char *_dResume = nullptr, *_hResume = nullptr;
+  size_t _dResumeBytes = 0, _hResumeBytes = 0;
+  uint64_t _resumeBatches = 0, _resumesBatched = 0;   // options "resume_batches", "resumes_batched": drains that ran posted ResumeQuiz calls, and those calls
   StartBatchInline *_startBatch = nullptr;   // StartQuizBatch: CreateQuiz queues the new quizzes' buffers here instead of launching
   void BuildTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &steps, std::vector<int64_t> &chainStart) const;
   Error TrainLocked(int64_t nQuestions, const AQ *pAQs, int64_t iTarget, double amount, bool fromQuiz);
@@ -487,7 +505,9 @@ class HipEngine : public IEngine {
   struct PostedOp {
     int kind = 0;                      // 1: RecordAnswer(iQuiz, arg = iAnswer, remote); 2: ListTopTargets' launch (arg = maxCount);
                                        // 3: a leader's LaunchBatch(ctx, batch, flight); 4: StartQuiz (result = the quiz);
-                                       // 5: ReleaseQuiz(iQuiz); 6: RecordQuizTarget(iQuiz, arg = iTarget, amount)
+                                       // 5: ReleaseQuiz(iQuiz); 6: RecordQuizTarget(iQuiz, arg = iTarget, amount);
+                                       // 7: ResumeQuiz(arg = nAnswered, aqs) (result = the quiz)
+    const AQ *aqs = nullptr;
     double amount = 0;
     int64_t iQuiz = -1, arg = 0;
     bool remote = false;

@@ -85,13 +85,14 @@ void HipEngine::DrainPosted() {
   while (list != nullptr) { PostedOp *n = list->next; list->next = ordered; ordered = list; list = n; }
   _postedDrains++;
   bool needFlush = false;
-  int64_t nStarts = 0, nTrains = 0;
+  int64_t nStarts = 0, nTrains = 0, nResumes = 0;
   for (PostedOp *op = ordered; op != nullptr; op = op->next) {
     _postedOps++;
     if (op->kind == 1) { op->err = RecordAnswerLocked(op->iQuiz, op->arg, op->remote, false); continue; }
     if (op->kind == 5) { op->err = ReleaseQuizLocked(op->iQuiz, false); continue; }
     if (op->kind == 6) { nTrains++; continue; }
     if (op->kind == 4) { nStarts++; continue; }
+    if (op->kind == 7) { nResumes++; continue; }
     if (op->kind == 3) continue;
     op->result = -1;
     op->err = CheckRegular("list top targets");
@@ -136,6 +137,21 @@ void HipEngine::DrainPosted() {
       if (batch.n == kStartInline) launch();
     }
     launch();
+  }
+  if (nResumes > 0) {
+    // the ResumeQuiz calls of this drain: one launch sequence and one synchronisation per chunk for all of them (as ResumeQuizBatch),
+    // each call failing or succeeding on its own
+    MarkStreamBusy();
+    std::vector<ResumeEntry> es;
+    es.reserve((size_t)nResumes);
+    for (PostedOp *op = ordered; op != nullptr; op = op->next)
+      if (op->kind == 7) { es.emplace_back(); es.back().nAnswered = op->arg; es.back().pAQs = op->aqs; }
+    (void)ResumeEntriesLocked(es, false);
+    size_t i = 0;
+    for (PostedOp *op = ordered; op != nullptr; op = op->next)
+      if (op->kind == 7) { op->err = es[i].err; op->result = es[i].err.ok() ? es[i].id : -1; i++; }
+    _resumeBatches++;
+    _resumesBatched += (uint64_t)nResumes;
   }
   for (PostedOp *op = ordered; op != nullptr; op = op->next)
     if (op->kind == 3) LaunchBatchLocked(*op->ctx, *op->batch, *op->flight);   // (behind the updates, ahead of the listings: the sweep is what the most clients wait for)

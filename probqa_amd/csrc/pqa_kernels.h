@@ -351,6 +351,26 @@ hipError_t LaunchStartQuizBatch(const KbView &kb, const StartBatchInline &batch,
 // {error code (0 / 16 = I64Underflow), fullMax}.  bugCompat reproduces PqaCore/CEUpdatePriorsSubtaskMul.cpp:53.
 hipError_t LaunchResumeQuiz(const KbView &kb, double *prior, int64_t *exps, const void *const *rows, int64_t nAnswered,
                             int64_t nWorkers, int bugCompat, int64_t *status, hipStream_t stream);
+// Several quizzes' ResumeQuiz in one launch sequence: slot i (device memory) is quiz i's LaunchResumeQuiz, every posterior
+// bit-identical to it.  The kernels also copy askedSrc (askedWords words) into asked.  Rows of up to 16384 targets: one workgroup
+// per quiz (grid.x = quiz).  Longer rows with kb.priorScratch set (option long_row_form): three launches over (part of the row,
+// quiz) -- products and the exponent maximum, normalisation and the reference's subtask sums, division -- with longScratch:
+// n * ResumeLongStride(nWorkers) words, zeroed by the caller before the launch.  n <= kResumeChunk.
+constexpr int kResumeChunk = 256;
+struct ResumeSlot {
+  double *prior;
+  uint32_t *asked;
+  const uint32_t *askedSrc;
+  const void *const *rows;        // 2 nAnswered row pointers, as LaunchResumeQuiz's
+  int64_t *exps;                  // ldT int64 of scratch
+  int64_t *status;                // int64[2], as LaunchResumeQuiz's
+  int64_t nAnswered;              // >= 1
+  int64_t pad;
+};
+inline int64_t ResumeLongStride(int64_t nWorkers) { return 8 + 8 * nWorkers; }
+inline bool ResumeTakesLongRow(const KbView &kb) { return kb.ldT > 16384 && kb.priorScratch != nullptr; }
+hipError_t LaunchResumeQuizBatch(const KbView &kb, const ResumeSlot *slots, int64_t n, int64_t askedWords, int64_t nWorkers,
+                                 int bugCompat, uint64_t *longScratch, hipStream_t stream);
 
 // ---- KB construction / mutation
 hipError_t LaunchFillFresh(void *cube, int elem, double *vB, int64_t K, int64_t Q, int64_t T, int64_t ldT, double initAmount,

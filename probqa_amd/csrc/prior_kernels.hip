@@ -87,13 +87,11 @@ __device__ __forceinline__ int ceil_log2_u64(uint64_t val) {  // SRPlatform/Inte
 // rows: for answered question i the rows sA[q_i][a_i][.] (rows[2i]) and mD[q_i][.] (rows[2i + 1]) -- pointers instead of
 // indices, so that the rows of a question held by ANOTHER device of the process (a shard of the question axis,
 // sharded_engine.cpp) are read in place over xGMI peer access.
-__global__ __launch_bounds__(kThreads) void resume_quiz_kernel(PriorArgs a, int64_t *__restrict__ exps,
-                                                               const void *const *__restrict__ rows, int64_t nAnswered,
-                                                               int bugCompat, int64_t *status) {
-  extern __shared__ double lds[];
-  __shared__ long long sMax[kThreads / kWave];
+// sMax: one slot per wave; sCorr: one.  Shared by resume_quiz_kernel and resume_quiz_batch_kernel.
+__device__ __forceinline__ void resume_quiz_body(PriorArgs a, int64_t *__restrict__ exps, const void *const *__restrict__ rows,
+                                                 int64_t nAnswered, int bugCompat, int64_t *status, double *lds, long long *sMax,
+                                                 long long &sCorr) {
   const int nWaves = (int)(blockDim.x / kWave);
-  __shared__ long long sCorr;
   const int64_t nVects = (a.T + 3) >> 2;
   // a8: every target runs its own chain of products over the answered questions, mantissa and exponent kept apart.
   long long myMax = INT64_MIN;
@@ -153,6 +151,199 @@ __global__ __launch_bounds__(kThreads) void resume_quiz_kernel(PriorArgs a, int6
   }
   const double total = reference_order_sum(a.prior, nVects, a.nWorkers, lds);
   for (int64_t t = threadIdx.x; t < 4 * nVects; t += blockDim.x) a.prior[t] = a.prior[t] / total;
+}
+
+__global__ __launch_bounds__(kThreads) void resume_quiz_kernel(PriorArgs a, int64_t *__restrict__ exps,
+                                                               const void *const *__restrict__ rows, int64_t nAnswered,
+                                                               int bugCompat, int64_t *status) {
+  extern __shared__ double lds[];
+  __shared__ long long sMax[kThreads / kWave];
+  __shared__ long long sCorr;
+  resume_quiz_body(a, exps, rows, nAnswered, bugCompat, status, lds, sMax, sCorr);
+}
+
+// grid.x = quiz: workgroup i runs slot i's ResumeQuiz exactly as resume_quiz_kernel would, after copying the quiz's asked bitmap
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? kSmallThreads : kThreads) void resume_quiz_batch_kernel(PriorArgs a, const ResumeSlot *__restrict__ slots,
+                                                                                             int64_t askedWords, int bugCompat) {
+  extern __shared__ double lds[];
+  __shared__ long long sMax[(SMALL ? kSmallThreads : kThreads) / kWave];
+  __shared__ long long sCorr;
+  const ResumeSlot s = slots[blockIdx.x];
+  for (int64_t i = threadIdx.x; i < askedWords; i += blockDim.x) s.asked[i] = s.askedSrc[i];
+  a.prior = s.prior;
+  resume_quiz_body(a, s.exps, s.rows, s.nAnswered, bugCompat, s.status, lds, sMax, sCorr);
+}
+
+// ---- ResumeQuiz on long rows (ldT > 16384), several quizzes at once: grid.y = quiz.  The one-workgroup kernel above walks the
+// whole row's product chains on one CU; here they are spread over the device, and the two device-wide steps -- the exponent
+// maximum and the total -- are each the last arriving workgroup's (the agent-scope release / acquire counter of
+// long_row_stage_kernel), with a launch boundary in front of the steps that need them.  Same operations on the same values in the
+// same order: bit-identical to resume_quiz_kernel.
+// Per quiz, ResumeLongStride(nWorkers) words of longScratch (zeroed by the host before the first launch):
+//   [0] the maximum exponent, biased (x ^ 2^63: unsigned order, 0 = INT64_MIN)  [1] phase 1's arrival counter
+//   [2] the exponent correction (INT64_MIN: I64Underflow)  [3] the total  [4] phase 2's arrival counter  [8 + 8 s ..] subtask s's sums
+constexpr int kLongTile = 4 * kSmallThreads;   // targets per workgroup of phases 1 and 3
+
+// Phase 1 (a8 + a9 part 1): the product chains of a tile of 1024 targets, four per thread -- their loads for an answered question
+// requested together -- and the tile's maximum into the quiz's; the last tile of a quiz forms the correction or flags I64Underflow.
+__global__ __launch_bounds__(kSmallThreads) void resume_long_products_kernel(PriorArgs a, const ResumeSlot *__restrict__ slots, int64_t askedWords,
+                                                                              int bugCompat, uint64_t *__restrict__ longScratch, int64_t stride) {
+  __shared__ long long sMax[kSmallThreads / kWave];
+  const ResumeSlot s = slots[blockIdx.y];
+  uint64_t *sc = longScratch + blockIdx.y * stride;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < askedWords; i += (int64_t)gridDim.x * blockDim.x) s.asked[i] = s.askedSrc[i];
+  const int64_t nVects = (a.T + 3) >> 2;
+  const int64_t t0 = (int64_t)blockIdx.x * kLongTile + threadIdx.x;
+  int64_t tt[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) tt[e] = t0 + e * kSmallThreads < a.ldT ? t0 + e * kSmallThreads : a.ldT - 1;   // (past the row: a repeat of its last element, not stored)
+  double mant[4];
+  int64_t ex[4];
+  {
+    double av[4], dv[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) { av[e] = cube_ld(s.rows[0], a.elem, tt[e]); dv[e] = cube_ld(s.rows[1], a.elem, tt[e]); }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const double pQaGivenT = av[e] / dv[e];
+      const double oldMant = bugCompat ? a.vB[tt[e] & 3] : a.vB[tt[e]];   // CEUpdatePriorsSubtaskMul.cpp:53
+      const uint64_t up = d2u(oldMant * pQaGivenT);                        // :54
+      mant[e] = u2d(kExp0Up | (up & ~kExpMaskUp));                         // :56
+      ex[e] = (int64_t)((up & kExpMaskUp) >> 52);                          // :59
+    }
+  }
+  for (int64_t i = 1; i < s.nAnswered; i++) {
+    const void *ra = s.rows[2 * i], *rd = s.rows[2 * i + 1];
+    double av[4], dv[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) { av[e] = cube_ld(ra, a.elem, tt[e]); dv[e] = cube_ld(rd, a.elem, tt[e]); }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const uint64_t up = d2u(mant[e] * (av[e] / dv[e]));                  // :75
+      mant[e] = u2d(kExp0Up | (up & ~kExpMaskUp));                         // :77
+      ex[e] += (int64_t)((up & kExpMaskUp) >> 52);                         // :80-82
+    }
+  }
+  long long myMax = INT64_MIN;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int64_t t = t0 + e * kSmallThreads;
+    if (t >= a.ldT) continue;
+    s.prior[t] = mant[e];
+    s.exps[t] = ex[e];
+    const long long totExp = ex[e] + (long long)((d2u(mant[e]) & kExpMaskUp) >> 52);   // CENormPriorsSubtaskMax
+    if (t < 4 * nVects && !bit_test(a.tgap, t) && totExp > myMax) myMax = totExp;
+  }
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) {
+    const long long o = __shfl_xor(myMax, m, kWave);
+    myMax = o > myMax ? o : myMax;
+  }
+  if (threadIdx.x % kWave == 0) sMax[threadIdx.x / kWave] = myMax;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  long long tileMax = sMax[0];
+  for (int w = 1; w < kSmallThreads / kWave; w++) tileMax = sMax[w] > tileMax ? sMax[w] : tileMax;
+  __hip_atomic_fetch_max(sc + 0, (uint64_t)tileMax ^ (1ull << 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  if (__hip_atomic_fetch_add(sc + 1, (uint64_t)1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) != (uint64_t)(gridDim.x - 1)) return;
+  const long long fullMax = (long long)(__hip_atomic_load(sc + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ (1ull << 63));
+  const long long highBound = 1023 + 1023 - ceil_log2_u64((uint64_t)a.T) - 2;   // CpuEngine.cpp:316
+  const long long minAllowed = INT64_MIN + highBound + 1;                       // :317
+  s.status[1] = fullMax;
+  s.status[0] = fullMax <= minAllowed ? 16 : 0;                                 // :318-321 I64Underflow
+  sc[2] = (uint64_t)(fullMax <= minAllowed ? INT64_MIN : highBound - fullMax);  // :322
+}
+
+// Phase 2 (a9 part 2 + the sum): grid.x = subtask of the reference's split, one workgroup as in long_row_stage_kernel -- the subtask's
+// values normalised (into LDS as well when they fit), its four Kahan chains, and the last subtask of a quiz adds them up.
+__global__ __launch_bounds__(kThreads) void resume_long_norm_kernel(PriorArgs a, const ResumeSlot *__restrict__ slots, uint64_t *__restrict__ longScratch,
+                                                                    int64_t stride, int valuesInLds) {
+  extern __shared__ double lds[];   // 8 * nSubtasks + 1 doubles for the last workgroup's sum, then this subtask's values
+  __shared__ int isLast;
+  const ResumeSlot sl = slots[blockIdx.y];
+  uint64_t *sc = longScratch + blockIdx.y * stride;
+  double *part = reinterpret_cast<double *>(sc + 8);
+  const long long corrExp = (long long)sc[2];
+  if (corrExp == INT64_MIN) return;   // I64Underflow: the host destroys the quiz
+  const int64_t nVects = (a.T + 3) >> 2;
+  const int64_t quot = nVects / a.nWorkers, rem = nVects % a.nWorkers;
+  const int64_t nSubtasks = gridDim.x, s = blockIdx.x;
+  const int64_t first = (s == 0) ? 0 : prior_split_bound(s - 1, quot, rem), limit = prior_split_bound(s, quot, rem);
+  const int64_t e0 = 4 * first, e1 = (s == nSubtasks - 1) ? a.ldT : 4 * limit;
+  double *vals = lds + 8 * nSubtasks + 1;
+  for (int64_t t = e0 + threadIdx.x; t < e1; t += blockDim.x) {   // CENormPriorsSubtaskCorrSum.cpp:25-40
+    const uint64_t um = d2u(sl.prior[t]);
+    const long long normExp = sl.exps[t] + (long long)((um & kExpMaskUp) >> 52) + corrExp;
+    const bool assume0 = (1 > normExp) || bit_test(a.tgap, t);
+    const double v = assume0 ? 0.0 : u2d(((uint64_t)normExp << 52) | (um & ~kExpMaskUp));   // ReplaceExponents
+    sl.prior[t] = v;
+    if (valuesInLds) vals[t - e0] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {   // one chain per lane, as long_row_stage_kernel
+    const int c = (int)threadIdx.x;
+    const double *v = valuesInLds ? vals : sl.prior;
+    const int64_t off = valuesInLds ? e0 : 0;
+    double sum = 0, corr = 0;
+    int64_t j = first;
+    for (; j + 16 <= limit; j += 16) {
+      double x[16];
+#pragma unroll
+      for (int e = 0; e < 16; e++) x[e] = v[4 * (j + e) + c - off];
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const double y = x[e] - corr;
+        const double u = sum + y;
+        corr = (u - sum) - y;
+        sum = u;
+      }
+    }
+    for (; j < limit; j++) {
+      const double y = v[4 * j + c - off] - corr;
+      const double u = sum + y;
+      corr = (u - sum) - y;
+      sum = u;
+    }
+    __hip_atomic_store(part + 8 * s + c, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(part + 8 * s + 4 + c, corr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (threadIdx.x < kWave) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (threadIdx.x == 0) isLast = __hip_atomic_fetch_add(sc + 4, (uint64_t)1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint64_t)(nSubtasks - 1);
+  }
+  __syncthreads();
+  if (!isLast) return;
+  for (int64_t i = threadIdx.x; i < 8 * nSubtasks; i += blockDim.x) lds[i] = __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  for (int64_t s2 = threadIdx.x; s2 < nSubtasks; s2 += blockDim.x) {
+    const double ps = precise_sum4(lds + 8 * s2, lds + 8 * s2 + 4);
+    lds[8 * s2] = ps;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Kahan1 acc;  // Summator::ForPriors, PqaCore/Summator.h:14-19
+    acc.init(0.0);
+    for (int64_t s2 = 0; s2 < nSubtasks; s2++) acc.add(lds[8 * s2]);
+    const double total = acc.get();
+    sc[3] = d2u(total);
+  }
+}
+
+// Phase 3: the division (CEDivTargPriors :19), tiles of 1024 targets
+__global__ __launch_bounds__(kSmallThreads) void resume_long_divide_kernel(const ResumeSlot *__restrict__ slots, const uint64_t *__restrict__ longScratch,
+                                                                            int64_t stride, int64_t n4) {
+  const uint64_t *sc = longScratch + blockIdx.y * stride;
+  if ((long long)sc[2] == INT64_MIN) return;
+  double *prior = slots[blockIdx.y].prior;
+  const double total = u2d(sc[3]);
+  const int64_t t0 = (int64_t)blockIdx.x * kLongTile + threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int64_t t = t0 + e * kSmallThreads;
+    if (t < n4) prior[t] = prior[t] / total;
+  }
 }
 
 // ---- long rows (ldT > 16384: BASELINE configs[4]'s 100000 targets).  One workgroup per SUBTASK of the reference's sum instead of
@@ -377,6 +568,35 @@ hipError_t LaunchResumeQuiz(const KbView &kb, double *prior, int64_t *exps, cons
   if (nWorkers < 1 || nWorkers > kMaxWorkers || nAnswered < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(resume_quiz_kernel, dim3(1), dim3(small_launch(kb) ? kSmallThreads : kThreads), sum_lds_bytes(nWorkers), stream,
                      make_args(kb, prior, nWorkers), exps, rows, nAnswered, bugCompat, status);
+  return hipGetLastError();
+}
+
+hipError_t LaunchResumeQuizBatch(const KbView &kb, const ResumeSlot *slots, int64_t n, int64_t askedWords, int64_t nWorkers,
+                                 int bugCompat, uint64_t *longScratch, hipStream_t stream) {
+  if (nWorkers < 1 || nWorkers > kMaxWorkers || n < 1 || n > kResumeChunk) return hipErrorInvalidValue;
+  if (ResumeTakesLongRow(kb)) {
+    if (longScratch == nullptr) return hipErrorInvalidValue;
+    const int64_t nVects = (kb.T + 3) >> 2, quot = nVects / nWorkers, rem = nVects % nWorkers;
+    const int64_t nSubtasks = quot == 0 ? rem : nWorkers;
+    const int64_t stride = ResumeLongStride(nWorkers), tiles = (kb.ldT + kLongTile - 1) / kLongTile;
+    const PriorArgs a = make_args(kb, nullptr, nWorkers);
+    hipLaunchKernelGGL(resume_long_products_kernel, dim3((unsigned)tiles, (unsigned)n), dim3(kSmallThreads), 0, stream, a, slots, askedWords,
+                       bugCompat, longScratch, stride);
+    const size_t values = (size_t)(4 * (quot + 1) + (kb.ldT - 4 * nVects)) * sizeof(double);
+    const bool inLds = sum_lds_bytes(nSubtasks) + values <= 65536;
+    hipLaunchKernelGGL(resume_long_norm_kernel, dim3((unsigned)nSubtasks, (unsigned)n), dim3(kThreads), sum_lds_bytes(nSubtasks) + (inLds ? values : 0),
+                       stream, a, slots, longScratch, stride, inLds ? 1 : 0);
+    hipLaunchKernelGGL(resume_long_divide_kernel, dim3((unsigned)((4 * nVects + kLongTile - 1) / kLongTile), (unsigned)n), dim3(kSmallThreads), 0,
+                       stream, slots, longScratch, stride, 4 * nVects);
+    return hipGetLastError();
+  }
+  // 256-thread workgroups whenever the rows are short: several quizzes' resumes share a CU
+  if (kb.T <= 4 * kSmallThreads)
+    hipLaunchKernelGGL(resume_quiz_batch_kernel<true>, dim3((unsigned)n), dim3(kSmallThreads), sum_lds_bytes(nWorkers), stream,
+                       make_args(kb, nullptr, nWorkers), slots, askedWords, bugCompat);
+  else
+    hipLaunchKernelGGL(resume_quiz_batch_kernel<false>, dim3((unsigned)n), dim3(kThreads), sum_lds_bytes(nWorkers), stream,
+                       make_args(kb, nullptr, nWorkers), slots, askedWords, bugCompat);
   return hipGetLastError();
 }
 

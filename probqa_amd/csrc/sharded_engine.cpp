@@ -59,6 +59,7 @@ class ShardedEngine final : public IEngine {
   void CopyDims(CiEngineDimensions *pDims) const override { _sh[0]->CopyDims(pDims); }
   int64_t StartQuiz(Error &err) override;
   int64_t ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) override;
+  Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) override;
   int64_t NextQuestion(Error &err, int64_t iQuiz) override;
   Error RecordAnswer(int64_t iQuiz, int64_t iAnswer) override;
   int64_t GetActiveQuestionId(Error &err, int64_t iQuiz) override;
@@ -828,6 +829,67 @@ int64_t ShardedEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs)
   }
   NewQuiz(id);
   return id;
+}
+
+// ResumeQuizBatch: the row pointers resolved as ResumeQuiz resolves them, then every shard one batch (HipEngine::ResumeQuizBatchRows:
+// a launch sequence per chunk).  The shards assign the same ids; all or none across the shards.
+Error ShardedEngine::ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "|nQuizzes| must be non-negative.");
+  if (n > 0 && (!pCounts || !pQuizzes)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (pCounts[i] < 0)
+      return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(pCounts[i]),
+                          "Batch entry " + std::to_string(i) + ": |nAnswered| must be non-negative.");
+    total += pCounts[i];
+  }
+  if (total > 0 && pAQs == nullptr) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of answered questions.");
+  for (int64_t i = 0; i < n; i++) pQuizzes[i] = -1;
+  if (n == 0) return Error();
+  CallScope scope(_activeCallers);
+  std::lock_guard<OpMutex> lk(_opMu);
+  Error err = FlushAnswers();
+  if (!err.ok()) return err;
+  std::vector<const void *> rows(2 * (size_t)total);
+  std::vector<int> rowDev(2 * (size_t)total), owners((size_t)total);
+  for (int64_t i = 0, j = 0; i < n; i++)
+    for (int64_t k = 0; k < pCounts[i]; k++, j++) {
+      const int owner = OwnerOf(pAQs[j].iQuestion);
+      if (owner < 0) err = Error::MakeP(ErrCode::IndexOutOfRange, "subjIndex=" + std::to_string(pAQs[j].iQuestion), "Question index is not in KB range.");
+      else err = _sh[(size_t)owner]->GetRowPointers(pAQs[j].iQuestion, pAQs[j].iAnswer, &rows[2 * (size_t)j], &rows[2 * (size_t)j + 1]);
+      if (!err.ok()) { err.message = "Batch entry " + std::to_string(i) + ": " + err.message; return err; }
+      owners[(size_t)j] = owner;
+      rowDev[2 * (size_t)j] = rowDev[2 * (size_t)j + 1] = _sh[(size_t)owner]->Device();
+    }
+  std::vector<int64_t> ids((size_t)n);
+  auto releaseAll = [&](size_t nShards) { for (int64_t i = 0; i < n; i++) if (pQuizzes[i] >= 0) ReleaseEverywhere(pQuizzes[i], nShards); };
+  for (size_t s = 0; s < _sh.size(); s++) {
+    bool allInPlace = true;
+    std::vector<char> stage(2 * (size_t)total, 0);
+    for (int64_t j = 0; j < total; j++) {
+      const size_t o = (size_t)owners[(size_t)j];
+      if (o == s) continue;
+      err = WaitForTraining(s, o);
+      if (!err.ok()) { releaseAll(s); return err; }
+      if (!InPlace(s, o)) {
+        allInPlace = false;
+        stage[2 * (size_t)j] = stage[2 * (size_t)j + 1] = 1;
+        _stagedRows.fetch_add(2, std::memory_order_relaxed);
+      }
+    }
+    err = _sh[s]->ResumeQuizBatchRows(n, pCounts, pAQs, rows.data(), allInPlace ? nullptr : rowDev.data(), allInPlace ? nullptr : stage.data(),
+                                      s == 0 ? pQuizzes : ids.data());
+    if (!err.ok()) { releaseAll(s); for (int64_t i = 0; i < n; i++) pQuizzes[i] = -1; return err; }
+    if (s > 0 && !std::equal(ids.begin(), ids.end(), pQuizzes)) {
+      for (int64_t i = 0; i < n; i++) (void)_sh[s]->ReleaseQuiz(ids[(size_t)i]);
+      releaseAll(s);
+      for (int64_t i = 0; i < n; i++) pQuizzes[i] = -1;
+      return Error::Make(ErrCode::Internal, "The shards' quiz registries have diverged.");
+    }
+    // (every chunk of the batch synchronised the shard's stream: its reads of the other shards' rows are done)
+  }
+  for (int64_t i = 0; i < n; i++) NewQuiz(pQuizzes[i]);
+  return Error();
 }
 
 // ClearOldQuizzes (behaviour: BaseEngine.cpp:814-873), decided once for all shards by the rule the one-device engine uses

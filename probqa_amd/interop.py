@@ -147,6 +147,7 @@ HIP_EXPORTS = {
     "PqaHip_RecordAnswerRemote": (_vp, [_vp, _i64, _i64]),
     "PqaEngine_RecordAnswerBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_StartQuizBatch": (_vp, [_vp, _i64, _pi64]),
+    "PqaEngine_ResumeQuizBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
 }
@@ -681,6 +682,16 @@ class PqaEngine:
         """n new quizzes, one launch for their priors."""
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_StartQuizBatch(self.c_engine, n, out))
+        return list(out[:n])
+
+    def resume_quiz_batch(self, lists) -> List[int]:
+        """ResumeQuiz for every list of answered questions in `lists`, one launch per chunk; all or none."""
+        n = len(lists)
+        counts = (ctypes.c_int64 * max(n, 1))(*[len(l) for l in lists])
+        flat = [aq for l in lists for aq in l]
+        arr, _ = self.to_c_answered_questions(flat)
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_ResumeQuizBatch(self.c_engine, n, counts, arr, out))
         return list(out[:n])
 
     def list_top_targets_batch(self, quizzes, max_count: int) -> List[List[RatedTarget]]:
