@@ -105,7 +105,6 @@ HipEngine *HipEngine::Create(Error &err, const CiEngineDefinition &def, const Ci
 }
 
 Error HipEngine::Init(const CiEngineDefinition &def, const CiHipShard *shard) {
-  _mu.owner = this;
   // reference PqaCore/PqaEngineBaseFactory.cpp:29-42: minimum dimensions
   const int64_t minA = 2, minQ = 1, minT = 2;
   if (def._nAnswers < minA || def._nQuestions < minQ || def._nTargets < minT) {
@@ -676,7 +675,7 @@ int64_t HipEngine::StartQuiz(Error &err) {
   if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // (the engine is taken: the quizzes started meanwhile share ONE launch)
     PostedOp op;
     op.kind = 4;
-    RunPosted(op);
+    PostAndWait(_mu, op);
     err = op.err;
     return op.result;
   }
@@ -705,7 +704,7 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
   if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // (the engine is taken: the resumes posted meanwhile share ONE launch)
     PostedOp op;
     op.kind = 7; op.arg = nAnswered; op.aqs = pAQs;   // (this thread waits for the result: the list stays valid)
-    RunPosted(op);
+    PostAndWait(_mu, op);
     err = op.err;
     return op.result;
   }
@@ -728,7 +727,7 @@ Error HipEngine::ReleaseQuiz(int64_t iQuiz) {
   if (_optCombine && (_optPostAlways || !_mu.try_lock())) {
     PostedOp op;
     op.kind = 5; op.iQuiz = iQuiz;
-    RunPosted(op);
+    PostAndWait(_mu, op);
     return op.err;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);

@@ -24,6 +24,7 @@
 
 #include "../../include/PqaHipExt.h"
 #include "pqa_kernels.h"
+#include "combining.h"
 
 namespace pqa {
 
@@ -447,11 +448,6 @@ class HipEngine : public IEngine {
   void MarkStreamBusy();
   uint64_t _flushes = 0, _flushedUpdates = 0, _maxFlush = 0;
   std::atomic<int> _activeCallers{0};         // client threads inside quiz-level calls right now
-  struct CallScope {
-    std::atomic<int> &n;
-    explicit CallScope(std::atomic<int> &c) : n(c) { n.fetch_add(1, std::memory_order_relaxed); }
-    ~CallScope() { n.fetch_sub(1, std::memory_order_relaxed); }
-  };
   const std::atomic<int> *_extCallers = nullptr;   // a shard: the client threads inside the sharded engine that drives it
   int Callers() const {
     const int own = _activeCallers.load(std::memory_order_relaxed);
@@ -491,15 +487,12 @@ class HipEngine : public IEngine {
   std::atomic<int64_t> _sweepNsEwma{0};            // how long a follower of a combined sweep waits for its result (moving average): it sleeps most of that, then spins
   std::atomic<int64_t> _lastCombined{0};           // requests of the newest combined sweep: as many RecordAnswers are about to arrive
   int64_t _optLingerUs = 20;                       // option "combine_linger_us": how long a ListTopTargets waits for them before it launches the updates
-  std::mutex _combMu;
-  std::vector<SelRequest *> _combQueue;
-  bool _leaderActive = false;
   int64_t Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd);
   // ---- posted operations.  With dozens of client threads the engine's lock is not held long but changes hands through the
   // kernel every time: each RecordAnswer and ListTopTargets slept on it and was woken by the thread before it, one wake-up
   // latency per call, serially (64 threads: 200 us inside a RecordAnswer that works for 1).  So a call that finds the lock
   // taken does not queue on it: it posts its operation and sleeps on the operation's own word; whoever holds the lock runs
-  // everything posted so far right before it lets go (EngineMutex::unlock) -- the RecordAnswers of a drain into the list of
+  // everything posted so far right before it lets go (combining.h: PostingLock) -- the RecordAnswers of a drain into the list of
   // deferred updates, ONE launch for all the posteriors its ListTopTargets ask for -- and wakes the posters, all at once.
   struct Flight;
   struct PostedOp {
@@ -523,16 +516,12 @@ class HipEngine : public IEngine {
     std::atomic<int> state{0};         // 0 posted, 2 posted and its thread asleep on this word, 1 done
     PostedOp *next = nullptr;
   };
-  std::atomic<PostedOp *> _posted{nullptr};
-  std::vector<std::atomic<int> *> _postedWake;     // the drain's sleepers, woken once the lock is released
   uint64_t _postedOps = 0, _postedDrains = 0;
-  void DrainPosted();                              // (the engine's lock held)
+  void DrainPosted(PostedOp *ordered);             // (the engine's lock held: everything posted so far, in post order)
   void TrainPosted(PostedOp *ordered);             // the drain's RecordQuizTarget calls
   uint64_t _trainBatches = 0, _trainBatchCalls = 0;
   Error ReleaseQuizLocked(int64_t iQuiz, bool mayWait);
   Error RecordQuizTargetLocked(int64_t iQuiz, int64_t iTarget, double amount);
-  void RunPosted(PostedOp &op);                    // post, and return when somebody has run it
-  void ServeQueue(SelRequest *own);
   int64_t PreferredCombinedBatch(int64_t m) const;
   struct Flight {                      // a combined sweep between its launch and its collection
     std::vector<SelRequest *> live;
@@ -573,8 +562,7 @@ class HipEngine : public IEngine {
   // row-sharing sweep (batch_kernels.hip; sized by its plan, grown on demand), the host copy of the priority vectors.  Two of
   // them: the batch calls of the ABI and the shards' halves use the first; the leaders of combined sweeps alternate, so that
   // the next sweep is launched while the previous one runs.
-  struct BatchCtx {
-    std::mutex mu;                       // one batch at a time in this context (taken before the engine's lock)
+  struct BatchCtx : CombineCtx {         // (mu: taken before the engine's lock)
     BatchPinned *h = nullptr;
     QuizSlot *dSlots = nullptr;
     SelectResult *dScratch = nullptr;
@@ -589,12 +577,10 @@ class HipEngine : public IEngine {
     double *hPri = nullptr;              // pinned: the batch's priority vectors for the host-side selector -- copied there behind the
     size_t hPriDoubles = 0;              // row-sharing sweep, or written there by the grid.y = quiz sweep itself as {priority, launch tag} records
     bool hPriCoherent = false;           // hPri is host-coherent mapped memory (the kernels write it) rather than a copy's destination
-    std::atomic<int> readers{0};         // clients still selecting out of hPri
     hipEvent_t event = nullptr;
-    std::atomic<bool> inFlight{false};   // a leader's sweep launched and not yet collected
   };
   BatchCtx _ctx[2];
-  int _ctxNext = 0;                      // (the leader's)
+  Combiner<SelRequest, BatchCtx> _comb{_ctx};
   // wantPriorities: the row-sharing sweep with its priority matrix kept (EvalPrioritiesBatch).  hostPriorities: whichever form
   // suits the batch, and the quizzes' priority vectors copied into _hBatchPri (layout: *pQuizMinor) for the host's selector.
   Error BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std::vector<Quiz *> &quizzes, bool wantPriorities, uint64_t tag,
@@ -631,32 +617,31 @@ class HipEngine : public IEngine {
   // The engine's lock.  Taking it also marks the engine's stream as possibly busy: the resident sweep runs on its own
   // stream, so a request is posted only after whatever the other operations enqueued on `_stream` has finished
   // (ServerPost); the selection paths, which leave nothing running, restore the mark they found.
-  struct EngineMutex {
+  // Releasing it runs the posted operations first (DrainPosted).
+  struct EngineMutex : PostingLock<PostedOp, HipEngine> {
     // (a sleeping lock on purpose: the client threads of a server may outnumber the cores it is allowed -- the GPU boxes of
     //  this project give a container 16 of 256 hardware threads -- and spinning waiters, tried in round 3 as a test-and-set and
     //  as a ticket lock, burn that allowance: 64 client threads fell from 45 k to 13 k questions/s, 256 to 0.3 k)
-    std::mutex m;
+    using PostingLock::PostingLock;
     bool busy = false, wasBusy = false;
     // (spinFirst -- set while the client threads are fewer than the CPUs the process may use: a bounded spin before sleeping; the
     //  holder is usually a microsecond of bookkeeping or one kernel launch away from releasing, and being woken through the kernel
     //  costs tens of microseconds.  With more clients than CPUs every spinning waiter takes time from a thread that has work.)
     std::atomic<bool> spinFirst{false};
-    HipEngine *owner = nullptr;
     bool try_lock() {
-      if (!m.try_lock()) return false;
+      if (!PostingLock::try_lock()) return false;
       wasBusy = busy; busy = true;
       return true;
     }
     void lock() {
       if (spinFirst.load(std::memory_order_relaxed))
         for (int i = 0; i < 400; i++) {
-          if (m.try_lock()) { wasBusy = busy; busy = true; return; }
+          if (PostingLock::try_lock()) { wasBusy = busy; busy = true; return; }
           for (int j = 0; j < 4; j++) __builtin_ia32_pause();
         }
-      m.lock(); wasBusy = busy; busy = true;
+      PostingLock::lock(); wasBusy = busy; busy = true;
     }
     void lock_urgent() { lock(); }
-    void unlock();   // (runs the posted operations first: hip_engine_combine.cpp)
   };
   struct UrgentLock {   // (RAII for lock_urgent, re-lockable like std::unique_lock)
     EngineMutex &mu;
@@ -666,7 +651,7 @@ class HipEngine : public IEngine {
     void lock() { mu.lock_urgent(); held = true; }
     void unlock() { mu.unlock(); held = false; }
   };
-  mutable EngineMutex _mu;
+  mutable EngineMutex _mu{this, &HipEngine::DrainPosted};
   std::atomic<uint64_t> _nQuestionsAsked{0};
   Mode _mode = Mode::Regular;
   // options

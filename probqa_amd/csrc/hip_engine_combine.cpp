@@ -33,56 +33,10 @@ int HipEngine::AllowedCpus() {
   return n;
 }
 
-// ---- posted operations (hip_engine.h)
-void HipEngine::EngineMutex::unlock() {
-  for (;;) {
-    std::atomic<int> *wake[64];
-    size_t nWake = 0;
-    std::vector<std::atomic<int> *> more;
-    if (owner != nullptr && owner->_posted.load(std::memory_order_acquire) != nullptr) {
-      owner->DrainPosted();
-      std::vector<std::atomic<int> *> &w = owner->_postedWake;
-      if (w.size() <= 64) { nWake = w.size(); std::copy(w.begin(), w.end(), wake); }
-      else more.swap(w);
-      w.clear();
-    }
-    m.unlock();
-    for (size_t i = 0; i < nWake; i++) FutexWakeOne(wake[i]);
-    for (std::atomic<int> *word : more) FutexWakeOne(word);
-    // Posted between the drain and the release: its thread saw the lock taken and sleeps.  (Both sides are a locked
-    // read-modify-write followed by a load -- the post then try_lock there, the release then this load here: one of the two sees
-    // the other.)  If somebody else has the lock by now, the operation is theirs to run.
-    if (owner == nullptr || owner->_posted.load(std::memory_order_seq_cst) == nullptr || !m.try_lock()) return;
-  }
-}
-
-void HipEngine::RunPosted(PostedOp &op) {
-  PostedOp *head = _posted.load(std::memory_order_relaxed);
-  do op.next = head; while (!_posted.compare_exchange_weak(head, &op, std::memory_order_seq_cst, std::memory_order_relaxed));
-  for (;;) {
-    if (_mu.try_lock()) { _mu.unlock(); }   // (free after all: run it -- and the others' -- here)
-    for (int spins = 0; spins < 300; spins++) {
-      if (op.state.load(std::memory_order_acquire) == 1) return;
-      _mm_pause();
-    }
-    int expected = 0;
-    if (op.state.compare_exchange_strong(expected, 2, std::memory_order_seq_cst) || expected == 2) {
-      // (the timeout is a belt to the braces above: a millisecond, then the lock is tried again)
-      struct timespec ts{0, 1000000};
-      syscall(SYS_futex, reinterpret_cast<int *>(&op.state), FUTEX_WAIT_PRIVATE, 2, &ts, nullptr, 0);
-    }
-    if (op.state.load(std::memory_order_acquire) == 1) return;
-  }
-}
-
 // Everything posted so far, in the order it was posted.  The RecordAnswers first go where RecordAnswer puts them (the list of
 // deferred updates), ReleaseQuiz and RecordQuizTarget run as they come; the StartQuiz calls then share one launch; then ONE launch runs every deferred update if a ListTopTargets of this drain needs its quiz's posterior;
 // then the combined sweeps leaders have posted; then the listings that the update kernel has not made already.
-void HipEngine::DrainPosted() {
-  PostedOp *list = _posted.exchange(nullptr, std::memory_order_acq_rel);
-  if (list == nullptr) return;
-  PostedOp *ordered = nullptr;
-  while (list != nullptr) { PostedOp *n = list->next; list->next = ordered; ordered = list; list = n; }
+void HipEngine::DrainPosted(PostedOp *ordered) {
   _postedDrains++;
   bool needFlush = false;
   int64_t nStarts = 0, nTrains = 0, nResumes = 0;
@@ -156,7 +110,7 @@ void HipEngine::DrainPosted() {
   for (PostedOp *op = ordered; op != nullptr; op = op->next)
     if (op->kind == 3) LaunchBatchLocked(*op->ctx, *op->batch, *op->flight);   // (behind the updates, ahead of the listings: the sweep is what the most clients wait for)
   for (PostedOp *op = ordered; op != nullptr;) {
-    PostedOp *const next = op->next;   // (the operation is its thread's again the moment its state says so)
+    PostedOp *const next = op->next;   // (the operation is its thread's again the moment it is done)
     if (op->kind == 2 && op->quiz != nullptr) {
       Quiz *q = op->quiz;
       const int64_t want = std::min<int64_t>(op->arg, _T);
@@ -179,8 +133,7 @@ void HipEngine::DrainPosted() {
         else { op->pin = q->pin; op->flagOp = q->topOp; op->result = want; }
       }
     }
-    std::atomic<int> *word = &op->state;
-    if (word->exchange(1, std::memory_order_acq_rel) == 2) _postedWake.push_back(word);
+    _mu.Done(op);
     op = next;
   }
   // The drain runs on the holder's way out -- possibly after a selection path declared the stream idle -- and may have launched
@@ -263,56 +216,23 @@ int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
   }
   SelRequest r;
   r.iQuiz = iQuiz; r.kind = kind; r.rnd = rnd;
-  bool lead;
-  {
-    std::lock_guard<std::mutex> lk(_combMu);
-    _combQueue.push_back(&r);
-    lead = !_leaderActive;
-    if (lead) _leaderActive = true;
+  int st = _comb.Wait(r, &_sweepNsEwma, ClientsFitCpus());
+  if (st == 2) {   // (the lead: nobody else led, or the leader before served its own batch and handed the lead to this, the oldest request)
+    if (_optLingerUs > 0 && Concurrent())   // (alone in the engine: nobody to wait for)
+      _comb.Linger(_optLingerUs, _flushedSinceSweep.load(std::memory_order_relaxed), _activeCallers);
+    Flight f;
+    st = _comb.Lead(
+        r, kMaxBatch, [this](int64_t m) { return PreferredCombinedBatch(m); },
+        [&](BatchCtx &c, std::vector<SelRequest *> &batch, std::chrono::steady_clock::time_point tA) {
+          f.tA = tA;
+          LaunchBatch(c, batch, f);   // (under the engine's lock; what could not be launched has its error -- or its result, for a batch of one)
+        },
+        [&](BatchCtx &c, std::vector<SelRequest *> &batch) { return !f.live.empty() && CollectBatch(c, batch, f, &r); });
   }
-  if (!lead) {
-    // (a combined sweep takes a fraction of a millisecond, and a thread woken through the kernel arrives tens of
-    //  microseconds after its neighbours; but dozens of spinning client threads eat the cores the process is allowed:
-    //  a short spin, then sleep)
-    int st = 0;
-    const auto tw0 = std::chrono::steady_clock::now();
-    for (int spins = 0; spins < 1500 && (st = r.state.load(std::memory_order_acquire)) == 0; spins++) _mm_pause();
-    if (st == 0 && ClientsFitCpus()) {
-      // Fewer clients than CPUs: sleep most of the expected wait (about as long as the last combined sweeps took), spin the rest --
-      // woken through the kernel the clients of one sweep arrive tens of microseconds apart.  More clients than CPUs: the
-      // condition variable only (spinning waiters would take the CPUs from the threads that have work).
-      const int64_t expect = _sweepNsEwma.load(std::memory_order_relaxed);
-      if (expect > 90000) {
-        static thread_local bool slackSet = false;
-        if (!slackSet) { prctl(PR_SET_TIMERSLACK, 2000UL, 0, 0, 0); slackSet = true; }
-        const auto until = tw0 + std::chrono::nanoseconds(std::min<int64_t>(expect - 50000, 2000000));
-        // (in naps of 40 us: the lead may be handed to this request meanwhile, and the next sweep waits for its leader)
-        while ((st = r.state.load(std::memory_order_acquire)) == 0 && std::chrono::steady_clock::now() < until) {
-          struct timespec ts{0, 40000};
-          nanosleep(&ts, nullptr);
-        }
-      }
-      for (int spins = 0; spins < 12000 && (st = r.state.load(std::memory_order_acquire)) == 0; spins++) _mm_pause();
-    }
-    while (st == 0) {
-      FutexWait(&r.state, 0);   // (returns at once if the state is no longer 0)
-      st = r.state.load(std::memory_order_acquire);
-    }
-    {
-      const int64_t waited = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw0).count();
-      const int64_t old = _sweepNsEwma.load(std::memory_order_relaxed);
-      _sweepNsEwma.store(old == 0 ? waited : old + (waited - old) / 8, std::memory_order_relaxed);
-    }
-    if (st == 1) { err = r.err; return r.result; }
-    if (st == 3) {   // the sweep has run: this quiz's priorities are on the host, the selection is this thread's own work
-      const int64_t sel = SelectFromPriorities(&r);
-      r.ctx->readers.fetch_sub(1, std::memory_order_release);
-      err = r.err;
-      return sel;
-    }
-    // (2: the leader before served its own batch and handed the lead to this, the oldest waiting request)
+  if (st == 3) {   // the sweep has run: this quiz's priorities are on the host, the selection is this thread's own work
+    SelectFromPriorities(&r);
+    r.ctx->readers.fetch_sub(1, std::memory_order_release);
   }
-  ServeQueue(&r);
   err = r.err;
   return r.result;
 }
@@ -389,81 +309,13 @@ int64_t HipEngine::PreferredCombinedBatch(int64_t m) const {
   return rem == 0 || rem >= 52 ? m : std::max<int64_t>(full, 32);
 }
 
-// The leader's turn: ONE batch -- everything posted so far, distinct quizzes, `own` among them (it is the oldest request).  The
-// lead goes on to the oldest request still waiting (or is given up) as soon as the batch's sweep is LAUNCHED: the next leader
-// gathers and launches the next sweep -- into the other of the two batch contexts -- while this one's runs, so that the device
-// finds the next sweep queued when it finishes this one.
-void HipEngine::ServeQueue(SelRequest *own) {
-  // The clients whose RecordAnswers ran since the last combined sweep are on their way here (their ListTopTargets have just
-  // returned): a leader that starts at once sweeps for the two or three that were quickest and makes the rest wait for a
-  // second sweep.  So it waits -- microseconds -- until most of them have posted, or nobody new comes.
-  // While the previous leader's sweep still runs there is no hurry at all: a sweep launched now only queues behind it, so the
-  // requests that arrive until it is (nearly) done ride along for free.
-  if (_optLingerUs > 0 && Concurrent()) {   // (alone in the engine: nobody to wait for)
-    const int64_t expect = std::min<int64_t>(_flushedSinceSweep.load(std::memory_order_relaxed), _activeCallers.load(std::memory_order_relaxed) - 1);
-    const BatchCtx &other = _ctx[_ctxNext ^ 1];
-    const auto t0 = std::chrono::steady_clock::now();
-    const auto limit = std::chrono::microseconds(_optLingerUs), limitBusy = std::chrono::microseconds(8 * _optLingerUs);
-    for (;;) {
-      size_t have;
-      { std::lock_guard<std::mutex> lk(_combMu); have = _combQueue.size(); }
-      const bool busy = other.inFlight.load(std::memory_order_relaxed);
-      if (!busy && (expect <= 1 || (int64_t)have * 5 >= expect * 4)) break;
-      if (busy && (int64_t)have >= _activeCallers.load(std::memory_order_relaxed) - 1) break;   // (everybody is here)
-      for (int i = 0; i < 32; i++) _mm_pause();
-      if (std::chrono::steady_clock::now() - t0 > (busy ? limitBusy : limit)) break;
-    }
-  }
-  // this batch's context: its previous sweep has been collected, and the clients that were selecting out of its priority
-  // buffer -- they need no lock for that -- are done (normally long ago)
-  BatchCtx &c = _ctx[_ctxNext];
-  _ctxNext ^= 1;
-  const auto tA = std::chrono::steady_clock::now();
-  std::unique_lock<std::mutex> ctxLock(c.mu);
-  while (c.readers.load(std::memory_order_acquire) != 0) _mm_pause();
-  std::vector<SelRequest *> batch;
-  {
-    std::lock_guard<std::mutex> lk(_combMu);
-    std::vector<SelRequest *> rest;
-    for (SelRequest *r : _combQueue) {
-      bool take = (int64_t)batch.size() < kMaxBatch;
-      for (size_t i = 0; take && i < batch.size(); i++) take = batch[i]->iQuiz != r->iQuiz;   // a quiz once per sweep
-      (take ? batch : rest).push_back(r);
-    }
-    // (the sweep's lanes come in groups: the newest requests beyond the last well-filled group wait for the next sweep -- it is
-    //  launched right behind this one)
-    const size_t keep = (size_t)PreferredCombinedBatch((int64_t)batch.size());
-    if (keep < batch.size()) {
-      rest.insert(rest.begin(), batch.begin() + (std::ptrdiff_t)keep, batch.end());
-      batch.resize(keep);
-    }
-    _combQueue.swap(rest);
-  }
-  Flight f;
-  f.tA = tA;
-  LaunchBatch(c, batch, f);   // (under the engine's lock; what could not be launched has its error -- or its result, for a batch of one)
-  {
-    std::lock_guard<std::mutex> lk(_combMu);
-    if (_combQueue.empty()) _leaderActive = false;
-    else PublishState(&_combQueue.front()->state, 2);
-  }
-  const bool ownSelects = f.live.empty() ? false : CollectBatch(c, batch, f, own);
-  ctxLock.unlock();
-  for (SelRequest *r : batch)
-    if (r != nullptr && r != own) PublishState(&r->state, 1);   // (r is its caller's again from here on)
-  if (ownSelects) {
-    SelectFromPriorities(own);
-    c.readers.fetch_sub(1, std::memory_order_release);
-  }
-}
-
 // Validate and launch (the caller holds the context; the engine's lock is taken and released here).  f.live: the requests whose
 // sweep is in flight; every other request of `batch` has its result or error.
 void HipEngine::LaunchBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flight &f) {
   if (batch.size() > 1 && !_mu.try_lock()) {   // (the engine is taken: its holder launches this sweep on its way out)
     PostedOp op;
     op.kind = 3; op.ctx = &c; op.batch = &batch; op.flight = &f;
-    RunPosted(op);
+    PostAndWait(_mu, op);
     return;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
@@ -567,10 +419,9 @@ bool HipEngine::CollectBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flig
       r->priTag = f.tagged ? f.tag : 0;
       r->ctx = &c;
       if (r == own) { ownLive = true; continue; }
-      for (SelRequest *&slot : batch) if (slot == r) slot = nullptr;   // (published here: not the caller's to publish again)
-      PublishState(&r->state, 3);
+      Combiner<SelRequest, BatchCtx>::LetSelect(batch, r);
     }
-        _combNs[3] += ns(tD, std::chrono::steady_clock::now());
+    _combNs[3] += ns(tD, std::chrono::steady_clock::now());
     return ownLive;
   }
   // The kernel's choices: finished here for every request, and without the engine's lock -- the quizzes are held (inSelection:

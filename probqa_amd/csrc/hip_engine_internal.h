@@ -3,11 +3,7 @@
 // posterior updates, listings, training; hip_engine_shard.cpp: what a sharded engine asks of its shards).
 #pragma once
 
-#include <immintrin.h>
-#include <linux/futex.h>
 #include <sched.h>
-#include <sys/prctl.h>
-#include <sys/syscall.h>
 #include <time.h>
 #include <unistd.h>
 
@@ -22,6 +18,7 @@
 #include <random>
 #include <sstream>
 
+#include "combining.h"   // FutexWait, PublishState, PostingLock, Combiner
 #include "hip_engine.h"
 
 namespace pqa {
@@ -57,20 +54,6 @@ inline uint64_t SplitMix64(uint64_t &x) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
   return z ^ (z >> 31);
 }
-
-// A waiting client sleeps on ITS OWN request's state word and is woken alone (futex): with one condition variable for all
-// requests every published batch woke every sleeper, most of them only to find their own request unserved and sleep again.
-inline void FutexWait(std::atomic<int> *word, int expected) {
-  syscall(SYS_futex, reinterpret_cast<int *>(word), FUTEX_WAIT_PRIVATE, expected, nullptr, nullptr, 0);
-}
-inline void FutexWakeOne(std::atomic<int> *word) { syscall(SYS_futex, reinterpret_cast<int *>(word), FUTEX_WAKE_PRIVATE, 1, nullptr, nullptr, 0); }
-// The new state, then the wake -- always: whether the owner sleeps cannot be asked once the state is stored (it may have seen it,
-// returned and gone with its request), and a wake on a word nobody sleeps on only costs the call.
-inline void PublishState(std::atomic<int> *word, int state) {
-  word->store(state, std::memory_order_release);
-  FutexWakeOne(word);
-}
-static_assert(sizeof(std::atomic<int>) == sizeof(int), "the state word is slept on as a futex");
 
 // A wait for a word the GPU writes: a pure spin while the answer is a kernel's time away (the first ~50 us), then the core is
 // offered to whoever else wants it between looks (sched_yield) -- a process whose clients outnumber its CPUs otherwise burns its

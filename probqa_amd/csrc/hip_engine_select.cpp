@@ -419,7 +419,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
     if (!c.event) HIP_TRY(hipEventCreateWithFlags(&c.event, hipEventDisableTiming));
   }
   auto copyToHost = [&](const double *src, size_t doubles) -> Error {
-    if (c.readers.load(std::memory_order_acquire) != 0)   // (ServeQueue has waited for them before it took the lock they need)
+    if (c.readers.load(std::memory_order_acquire) != 0)   // (Combiner::Lead has waited for them before it took the lock they need)
       return Error::Make(ErrCode::Internal, "A priority buffer is still being read.");
     if (doubles > c.hPriDoubles) {
       HIP_TRY(hipStreamSynchronize(_stream));   // (nothing of an earlier batch is on its way into the old buffer)

@@ -11,7 +11,7 @@ Error HipEngine::RecordAnswerImpl(int64_t iQuiz, int64_t iAnswer, bool remote) {
   if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // somebody is inside the engine: it runs this call's bookkeeping on its way out
     PostedOp op;
     op.kind = 1; op.iQuiz = iQuiz; op.arg = iAnswer; op.remote = remote;
-    RunPosted(op);
+    PostAndWait(_mu, op);
     return op.err;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
@@ -420,7 +420,7 @@ int64_t HipEngine::ListTopTargetsFast(Error &err, int64_t iQuiz, int64_t maxCoun
     // have gathered, the listing if the update kernel has not made it); the wait for the quiz's own lines is this thread's
     PostedOp op;
     op.kind = 2; op.iQuiz = iQuiz; op.arg = maxCount;
-    RunPosted(op);
+    PostAndWait(_mu, op);
     if (op.result != -2) {
       err = op.err;
       if (!err.ok() || op.result < 0) return -1;
@@ -832,7 +832,7 @@ Error HipEngine::RecordQuizTarget(int64_t iQuiz, int64_t iTarget, double amount)
   if (_optCombine && (_optPostAlways || !_mu.try_lock())) {
     PostedOp op;
     op.kind = 6; op.iQuiz = iQuiz; op.arg = iTarget; op.amount = amount;
-    RunPosted(op);
+    PostAndWait(_mu, op);
     return op.err;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);

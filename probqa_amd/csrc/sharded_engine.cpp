@@ -28,7 +28,7 @@
 //                          engine's file: a KB saved sharded loads unsharded and vice versa).
 // One lock (_opMu) orders what must happen in the same order on every shard -- quiz registry changes, trainings, the launch of a
 // combined sweep; it is never held while the GPU is waited for, and calls that find it taken post their operation and are served
-// by its holder on the way out (as hip_engine_combine.cpp's posted operations).  Maintenance-mode edits of the dimensions rebuild the
+// by its holder on the way out (combining.h: PostingLock).  Maintenance-mode edits of the dimensions rebuild the
 // shards (Rebuild below).  Not sharded (NotImplemented on this engine): SetStream and the stream-ordered single-shard entry points.
 #include "hip_engine_internal.h"
 
@@ -69,7 +69,7 @@ class ShardedEngine final : public IEngine {
   Error ReleaseQuiz(int64_t iQuiz) override;
   // A forced switch destroys the shards' quizzes (BaseEngine.cpp:650-668), a shutdown likewise: what this engine keeps per quiz goes too
   Error StartMaintenance(bool force) override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     e = AllLocked([&](HipEngine &sh) { return sh.StartMaintenance(force); });
@@ -79,7 +79,7 @@ class ShardedEngine final : public IEngine {
   Error FinishMaintenance() override { return All([&](HipEngine &e) { return e.FinishMaintenance(); }); }
   Error Shutdown(const char *saveFilePath) override {
     if (saveFilePath && *saveFilePath) { Error e = SaveKB(saveFilePath, false); if (!e.ok()) return e; }   // BaseEngine.cpp:270-300
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     (void)FlushAnswers();
     Error e = AllLocked([&](HipEngine &sh) { return sh.Shutdown(nullptr); });
     if (e.ok()) ForgetQuizzes();
@@ -87,7 +87,7 @@ class ShardedEngine final : public IEngine {
   }
   bool MapIds(int which, bool toPerm, int64_t count, int64_t *pIds) override {
     if (which == 0) {   // questions: the global compact <-> permanent map lives here (the shards' own maps are over local ids)
-      std::lock_guard<OpMutex> lk(_opMu);
+      std::lock_guard<OpLock> lk(_opMu);
       bool ok = true;
       for (int64_t i = 0; i < count; i++) {
         pIds[i] = toPerm ? _questionIds.PermanentOf(pIds[i]) : _questionIds.SlotOf(pIds[i]);
@@ -97,8 +97,8 @@ class ShardedEngine final : public IEngine {
     }
     return _sh[0]->MapIds(which, toPerm, count, pIds);
   }
-  bool EnsurePermQuizGreater(int64_t bound) override { std::lock_guard<OpMutex> lk(_opMu); bool ok = true; for (auto &s : _sh) ok = s->EnsurePermQuizGreater(bound) && ok; return ok; }
-  bool RemapQuizPermId(int64_t a, int64_t b) override { std::lock_guard<OpMutex> lk(_opMu); bool ok = true; for (auto &s : _sh) ok = s->RemapQuizPermId(a, b) && ok; return ok; }
+  bool EnsurePermQuizGreater(int64_t bound) override { std::lock_guard<OpLock> lk(_opMu); bool ok = true; for (auto &s : _sh) ok = s->EnsurePermQuizGreater(bound) && ok; return ok; }
+  bool RemapQuizPermId(int64_t a, int64_t b) override { std::lock_guard<OpLock> lk(_opMu); bool ok = true; for (auto &s : _sh) ok = s->RemapQuizPermId(a, b) && ok; return ok; }
   Error SaveKB(const char *filePath, bool doubleBuffer) override;
   static ShardedEngine *Load(Error &err, const char *filePath, const std::vector<int> &devices);
   Error AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) override;
@@ -109,7 +109,7 @@ class ShardedEngine final : public IEngine {
 
   Error SetOption(const char *name, int64_t value) override {
     const std::string n(name ? name : "");
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     if (n == "combine") { _optCombine = value ? 1 : 0; return Error(); }          // (this engine's own combining; the shards are driven one call at a time)
@@ -142,7 +142,7 @@ class ShardedEngine final : public IEngine {
   }
   const char *EvalKernelName() const override { return _sh[0]->EvalKernelName(); }
   Error SetKB(const double *pA, const double *pD, const double *pB) override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     { Error fe = FlushAnswers(); if (!fe.ok()) return fe; }   // (the gathered answers read the cube as it was when they were given)
     for (auto &s : _sh) {
       const size_t q0 = (size_t)s->FirstQuestion();
@@ -152,7 +152,7 @@ class ShardedEngine final : public IEngine {
     return Error();
   }
   Error GetKB(double *pA, double *pD, double *pB) override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     { Error fe = FlushAnswers(); if (!fe.ok()) return fe; }
     for (auto &s : _sh) {
       const size_t q0 = (size_t)s->FirstQuestion();
@@ -164,7 +164,7 @@ class ShardedEngine final : public IEngine {
   Error FillSynthetic(double nTrain, double noiseAmp, uint64_t seed) override { return All([&](HipEngine &e) { return e.FillSynthetic(nTrain, noiseAmp, seed); }); }
   Error SetTargetGaps(int64_t n, const int64_t *ids) override { return All([&](HipEngine &e) { return e.SetTargetGaps(n, ids); }); }
   Error SetQuestionGaps(int64_t n, const int64_t *ids) override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     { Error fe = FlushAnswers(); if (!fe.ok()) return fe; }
     Error e = AllLocked([&](HipEngine &eng) { return eng.SetQuestionGaps(n, ids); });
     if (e.ok())
@@ -175,7 +175,7 @@ class ShardedEngine final : public IEngine {
   }
   Error EvalPriorities(int64_t iQuiz, double *pOut, int64_t n) override {
     if (n != _Q) return Error::MakeP(ErrCode::IndexOutOfRange, "n=" + std::to_string(n), "Priority buffer length must equal the question count.");
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     for (auto &s : _sh) { e = s->EvalPriorities(iQuiz, pOut + s->FirstQuestion(), s->LocalQuestions()); if (!e.ok()) return e; }
@@ -196,13 +196,13 @@ class ShardedEngine final : public IEngine {
   hipStream_t GetStream() const override { return _sh[0]->GetStream(); }
   Error SetStream(hipStream_t) override { return NotSharded("SetStream"); }
   Error Synchronize() override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     return AllLocked([&](HipEngine &sh) { return sh.Synchronize(); });
   }
   Error Quiesce() override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     return AllLocked([&](HipEngine &sh) { return sh.Quiesce(); });
@@ -210,7 +210,7 @@ class ShardedEngine final : public IEngine {
   Error EnqueueSelectArgmax(int64_t, void *) override { return NotSharded("EnqueueSelectArgmax"); }
   Error EnqueueSelectArgmaxFlag(int64_t, void *, void *, uint64_t) override { return NotSharded("EnqueueSelectArgmaxFlag"); }
   Error EnqueueEval(int64_t iQuiz) override {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     return AllLocked([&](HipEngine &sh) { return sh.EnqueueEval(iQuiz); });
@@ -243,12 +243,11 @@ class ShardedEngine final : public IEngine {
   }
 
  private:
-  ShardedEngine() { _opMu.owner = this; }
+  ShardedEngine() = default;
 
   // ---- the engine's lock and its posted operations ---------------------------------------------------------------------------
   struct SelRequest;
   struct Flight;
-  struct BatchCtx;
   struct Op {
     int kind = 0;                      // 1 StartQuiz (result = the quiz), 2 ReleaseQuiz(iQuiz), 3 RecordQuizTarget(iQuiz, iTarget, amount),
                                        // 4 hand the gathered answers to the shards, 5 a leader's LaunchBatch(ctx, batch, flight)
@@ -262,23 +261,13 @@ class ShardedEngine final : public IEngine {
     std::atomic<int> state{0};         // 0 posted, 2 posted and its thread asleep on this word, 1 done
     Op *next = nullptr;
   };
-  struct OpMutex {                     // (a sleeping lock; releasing it runs whatever was posted meanwhile)
-    std::mutex m;
-    ShardedEngine *owner = nullptr;
-    bool try_lock() { return m.try_lock(); }
-    void lock() { m.lock(); }
-    void unlock();
-  };
-  mutable OpMutex _opMu;
-  std::atomic<Op *> _posted{nullptr};
-  std::vector<std::atomic<int> *> _wake;   // the drain's sleepers, woken once the lock is released
-  void RunOp(Op &op);                  // runs it under the lock -- here, or by the lock's holder on its way out
-  void Drain();                        // (the lock held)
-  void Execute(Op *ordered);
+  using OpLock = PostingLock<Op, ShardedEngine>;   // (a sleeping lock; releasing it runs whatever was posted meanwhile: Execute)
+  mutable OpLock _opMu{this, &ShardedEngine::Execute};
+  void Execute(Op *ordered);           // (the lock held)
 
   template <typename F>
   Error All(F &&f) {   // (the gathered answers first: what follows reads or changes what they read)
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error fe = FlushAnswers();
     return fe.ok() ? AllLocked(f) : fe;
   }
@@ -334,7 +323,7 @@ class ShardedEngine final : public IEngine {
   Error FlushNow() {                    // through the lock: when it returns, every hand-over begun before it has reached all shards
     Op op;
     op.kind = 4;
-    RunOp(op);
+    if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
     return op.err;
   }
   // Before anything reads quiz `iQuiz`'s posterior on a shard: its answer -- if one is among the gathered ones, or in a hand-over
@@ -379,7 +368,7 @@ class ShardedEngine final : public IEngine {
     return _rng[1] + s0;
   }
 
-  // ---- concurrent NextQuestion calls: combined (as hip_engine_combine.cpp's Combine / ServeQueue / LaunchBatch / CollectBatch) --------
+  // ---- concurrent NextQuestion calls: combined (combining.h; as hip_engine_combine.cpp's Combine / LaunchBatch / CollectBatch) -------
   struct SelRequest {
     int64_t iQuiz = -1;
     int kind = 0;                      // 0 argmax, 1 sampled (rnd)
@@ -389,12 +378,7 @@ class ShardedEngine final : public IEngine {
     std::atomic<int> state{0};         // 0 waiting, 1 served, 2 lead handed over: serve the queue yourself, 3 select for yourself from `views`
     std::vector<HipEngine::PriorityView> views;   // state 3: per shard, this quiz's priority vector on the host
     std::vector<uint64_t> skip;        // state 3: asked questions and gaps in GLOBAL numbering as the sweeps saw them (64-bit packs)
-    BatchCtx *ctx = nullptr;
-  };
-  struct BatchCtx {
-    std::mutex mu;                     // one combined sweep at a time in this context (and the batch calls of the ABI in context 0)
-    std::atomic<int> readers{0};       // clients still selecting out of the shards' host buffers of this context
-    std::atomic<bool> inFlight{false};
+    CombineCtx *ctx = nullptr;
   };
   struct Flight {
     std::vector<SelRequest *> live;    // the requests whose sweep is in flight
@@ -402,22 +386,13 @@ class ShardedEngine final : public IEngine {
     std::vector<std::vector<uint32_t>> unavailable;   // per shard: live.size() x words
     bool anySampled = false;
   };
-  BatchCtx _bctx[2];
-  int _ctxNext = 0;
-  std::mutex _combMu;
-  std::vector<SelRequest *> _combQueue;
-  bool _leaderActive = false;
+  CombineCtx _bctx[2];                 // (mu: one combined sweep at a time in a context, and the batch calls of the ABI in context 0)
+  Combiner<SelRequest, CombineCtx> _comb{_bctx};
   std::mutex _rngMu;
   int64_t _optCombine = 1, _optLingerUs = 20;
   std::atomic<int> _activeCallers{0};
-  struct CallScope {
-    std::atomic<int> &n;
-    explicit CallScope(std::atomic<int> &c) : n(c) { n.fetch_add(1, std::memory_order_relaxed); }
-    ~CallScope() { n.fetch_sub(1, std::memory_order_relaxed); }
-  };
   bool Concurrent() const { return _optCombine && _activeCallers.load(std::memory_order_relaxed) > 1; }
   int64_t Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd);
-  void ServeQueue(SelRequest *own);
   void LaunchBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f);
   void LaunchBatchLocked(int ctx, std::vector<SelRequest *> &batch, Flight &f);
   bool CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f, SelRequest *own);
@@ -480,61 +455,6 @@ ShardedEngine::~ShardedEngine() {
   _sh.clear();
   if (_slots) hipHostFree(_slots);
   for (auto &c : _rows) delete[] c.load();
-}
-
-// ---- the lock ---------------------------------------------------------------------------------------------------------------------
-void ShardedEngine::OpMutex::unlock() {
-  for (;;) {
-    std::vector<std::atomic<int> *> wake;
-    if (owner != nullptr && owner->_posted.load(std::memory_order_acquire) != nullptr) {
-      owner->Drain();
-      wake.swap(owner->_wake);
-    }
-    m.unlock();
-    for (std::atomic<int> *w : wake) FutexWakeOne(w);
-    // posted between the drain and the release: its thread saw the lock taken and waits.  (Post then try_lock there, release then
-    // this load here: one of the two sees the other.)  If somebody else has the lock by now, the operation is theirs to run.
-    if (owner == nullptr || owner->_posted.load(std::memory_order_seq_cst) == nullptr || !m.try_lock()) return;
-  }
-}
-
-void ShardedEngine::RunOp(Op &op) {
-  if (_opMu.try_lock()) {            // free: run it here (and whatever else has been posted, on the way out)
-    op.next = nullptr;
-    Execute(&op);
-    _opMu.unlock();
-    return;
-  }
-  _postedOps.fetch_add(1, std::memory_order_relaxed);
-  Op *head = _posted.load(std::memory_order_relaxed);
-  do op.next = head; while (!_posted.compare_exchange_weak(head, &op, std::memory_order_seq_cst, std::memory_order_relaxed));
-  for (;;) {
-    if (_opMu.try_lock()) _opMu.unlock();   // (free after all: the release runs it)
-    for (int spins = 0; spins < 300; spins++) {
-      if (op.state.load(std::memory_order_acquire) == 1) return;
-      _mm_pause();
-    }
-    int expected = 0;
-    if (op.state.compare_exchange_strong(expected, 2, std::memory_order_seq_cst) || expected == 2) {
-      struct timespec ts{0, 1000000};   // (a millisecond, then the lock is tried again: a belt to the braces above)
-      syscall(SYS_futex, reinterpret_cast<int *>(&op.state), FUTEX_WAIT_PRIVATE, 2, &ts, nullptr, 0);
-    }
-    if (op.state.load(std::memory_order_acquire) == 1) return;
-  }
-}
-
-void ShardedEngine::Drain() {
-  Op *list = _posted.exchange(nullptr, std::memory_order_acq_rel);
-  if (list == nullptr) return;
-  Op *ordered = nullptr;
-  while (list != nullptr) { Op *n = list->next; list->next = ordered; ordered = list; list = n; }   // the order they were posted in
-  Execute(ordered);
-  for (Op *op = ordered; op != nullptr;) {
-    Op *const next = op->next;   // (the operation is its thread's again the moment its state says so)
-    std::atomic<int> *word = &op->state;
-    if (word->exchange(1, std::memory_order_acq_rel) == 2) _wake.push_back(word);
-    op = next;
-  }
 }
 
 // A list of operations under the lock (one, from a caller that found the lock free; or everything posted so far).  All of them are
@@ -769,7 +689,7 @@ int64_t ShardedEngine::StartQuiz(Error &err) {
   CallScope scope(_activeCallers);
   Op op;
   op.kind = 1;
-  RunOp(op);
+  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
   err = op.err;
   return op.result;
 }
@@ -778,7 +698,7 @@ Error ShardedEngine::ReleaseQuiz(int64_t iQuiz) {
   CallScope scope(_activeCallers);
   Op op;
   op.kind = 2; op.iQuiz = iQuiz;
-  RunOp(op);
+  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
   return op.err;
 }
 
@@ -787,7 +707,7 @@ int64_t ShardedEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs)
   if (nAnswered == 0) return StartQuiz(err);   // BaseEngine.cpp:393-395
   if (pAQs == nullptr) { err = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of answered questions."); return -1; }
   CallScope scope(_activeCallers);
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   err = FlushAnswers();
   if (!err.ok()) return -1;
   // every shard computes the posterior itself from row POINTERS: the rows of other shards' questions in place, or staged
@@ -847,7 +767,7 @@ Error ShardedEngine::ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ
   for (int64_t i = 0; i < n; i++) pQuizzes[i] = -1;
   if (n == 0) return Error();
   CallScope scope(_activeCallers);
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   Error err = FlushAnswers();
   if (!err.ok()) return err;
   std::vector<const void *> rows(2 * (size_t)total);
@@ -897,7 +817,7 @@ Error ShardedEngine::ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ
 Error ShardedEngine::ClearOldQuizzes(int64_t maxCount, double maxAgeSec) {
   if (maxCount < 0)
     return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(maxCount), "The number of quizzes to keep cannot be less than 0.");
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   if (!_sh[0]->IsRegularMode()) return Error();   // quizzes are not expected to exist in maintenance / shutdown mode
   Error first = FlushAnswers();
   std::vector<QuizUsage> inUse;
@@ -1053,7 +973,7 @@ int64_t ShardedEngine::ListTopTargets(Error &err, int64_t iQuiz, int64_t maxCoun
 // The reference validates every answered question before any Add subtask runs (CETrainSubtaskDistrib.h:26-45): a gap question
 // owned by shard k must not leave shards 0..k-1 trained and their vB replicas ahead -- every shard validates, then every shard trains.
 Error ShardedEngine::Train(int64_t n, const AQ *pAQs, int64_t iTarget, double amount) {
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   Error e = FlushAnswers();
   if (!e.ok()) return e;
   if (n >= 0 && amount > 0 && (n == 0 || pAQs != nullptr))   // (else: shard 0 produces the reference's argument error, before any kernel)
@@ -1069,7 +989,7 @@ Error ShardedEngine::RecordQuizTarget(int64_t iQuiz, int64_t iTarget, double amo
   CallScope scope(_activeCallers);
   Op op;
   op.kind = 3; op.iQuiz = iQuiz; op.iTarget = iTarget; op.amount = amount;
-  RunOp(op);
+  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
   return op.err;
 }
 
@@ -1163,103 +1083,36 @@ int64_t ShardedEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd
   SelRequest r;
   r.iQuiz = iQuiz; r.kind = kind; r.rnd = rnd;
   if (!_optCombine) {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     err = FlushAnswers();
     if (!err.ok()) return -1;
     ServeAlone(&r);
     err = r.err;
     return r.result;
   }
-  bool lead;
-  {
-    std::lock_guard<std::mutex> lk(_combMu);
-    _combQueue.push_back(&r);
-    lead = !_leaderActive;
-    if (lead) _leaderActive = true;
+  int st = _comb.Wait(r);
+  if (st == 2) {   // (the lead: nobody else led, or the leader before launched its batch and handed the lead to this, the oldest request)
+    if (_optLingerUs > 0 && Concurrent()) _comb.Linger(_optLingerUs, _answersSinceSweep.load(std::memory_order_relaxed), _activeCallers);
+    Flight f;
+    st = _comb.Lead(
+        r, 256, [this](int64_t m) { return _sh[0]->CombinedBatchFor(m); },
+        [&](CombineCtx &c, std::vector<SelRequest *> &batch, std::chrono::steady_clock::time_point) {
+          LaunchBatch((int)(&c - _bctx), batch, f);   // (under _opMu; what could not be launched has its error -- or its result, for a batch of one)
+        },
+        [&](CombineCtx &c, std::vector<SelRequest *> &batch) { return !f.live.empty() && CollectBatch((int)(&c - _bctx), batch, f, &r); });
   }
-  if (!lead) {
-    int st = 0;
-    for (int spins = 0; spins < 1500 && (st = r.state.load(std::memory_order_acquire)) == 0; spins++) _mm_pause();
-    while (st == 0) {
-      FutexWait(&r.state, 0);   // (returns at once if the state is no longer 0)
-      st = r.state.load(std::memory_order_acquire);
-    }
-    if (st == 1) { err = r.err; return r.result; }
-    if (st == 3) {   // the sweeps have run: this quiz's priorities are on the host, the selection is this thread's own work
-      const int64_t sel = SelectFromViews(&r);
-      r.ctx->readers.fetch_sub(1, std::memory_order_release);
-      err = r.err;
-      return sel;
-    }
-    // (2: the leader before has launched its batch and handed the lead to this, the oldest waiting request)
+  if (st == 3) {   // the sweeps have run: this quiz's priorities are on the host, the selection is this thread's own work
+    SelectFromViews(&r);
+    r.ctx->readers.fetch_sub(1, std::memory_order_release);
   }
-  ServeQueue(&r);
   err = r.err;
   return r.result;
-}
-
-void ShardedEngine::ServeQueue(SelRequest *own) {
-  // The clients whose answers were handed over since the last combined sweep are on their way here: a leader that starts at once
-  // sweeps for the two or three that were quickest and makes the rest wait for a second sweep.  So it waits -- microseconds --
-  // until most of them have posted, or nobody new comes; while the previous leader's sweeps still run there is no hurry at all.
-  if (_optLingerUs > 0 && Concurrent()) {
-    const int64_t expect = std::min<int64_t>(_answersSinceSweep.load(std::memory_order_relaxed), _activeCallers.load(std::memory_order_relaxed) - 1);
-    const BatchCtx &other = _bctx[_ctxNext ^ 1];
-    const auto t0 = std::chrono::steady_clock::now();
-    const auto limit = std::chrono::microseconds(_optLingerUs), limitBusy = std::chrono::microseconds(8 * _optLingerUs);
-    for (;;) {
-      size_t have;
-      { std::lock_guard<std::mutex> lk(_combMu); have = _combQueue.size(); }
-      const bool busy = other.inFlight.load(std::memory_order_relaxed);
-      if (!busy && (expect <= 1 || (int64_t)have * 5 >= expect * 4)) break;
-      if (busy && (int64_t)have >= _activeCallers.load(std::memory_order_relaxed) - 1) break;   // (everybody is here)
-      for (int i = 0; i < 32; i++) _mm_pause();
-      if (std::chrono::steady_clock::now() - t0 > (busy ? limitBusy : limit)) break;
-    }
-  }
-  const int ctx = _ctxNext;
-  _ctxNext ^= 1;
-  BatchCtx &c = _bctx[ctx];
-  std::unique_lock<std::mutex> ctxLock(c.mu);
-  while (c.readers.load(std::memory_order_acquire) != 0) _mm_pause();
-  std::vector<SelRequest *> batch;
-  {
-    std::lock_guard<std::mutex> lk(_combMu);
-    std::vector<SelRequest *> rest;
-    for (SelRequest *r : _combQueue) {
-      bool take = (int64_t)batch.size() < 256;
-      for (size_t i = 0; take && i < batch.size(); i++) take = batch[i]->iQuiz != r->iQuiz;   // a quiz once per sweep
-      (take ? batch : rest).push_back(r);
-    }
-    // (the sweeps' lanes come in groups: the newest requests beyond the last well-filled group wait for the next sweep)
-    const size_t keep = (size_t)_sh[0]->CombinedBatchFor((int64_t)batch.size());
-    if (keep < batch.size()) {
-      rest.insert(rest.begin(), batch.begin() + (std::ptrdiff_t)keep, batch.end());
-      batch.resize(keep);
-    }
-    _combQueue.swap(rest);
-  }
-  Flight f;
-  LaunchBatch(ctx, batch, f);   // (under _opMu; what could not be launched has its error -- or its result, for a batch of one)
-  {
-    std::lock_guard<std::mutex> lk(_combMu);
-    if (_combQueue.empty()) _leaderActive = false;
-    else PublishState(&_combQueue.front()->state, 2);
-  }
-  const bool ownSelects = f.live.empty() ? false : CollectBatch(ctx, batch, f, own);
-  ctxLock.unlock();
-  for (SelRequest *r : batch)
-    if (r != nullptr && r != own) PublishState(&r->state, 1);   // (r is its caller's again from here on)
-  if (ownSelects) {
-    SelectFromViews(own);
-    c.readers.fetch_sub(1, std::memory_order_release);
-  }
 }
 
 void ShardedEngine::LaunchBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f) {
   Op op;
   op.kind = 5; op.ctx = ctx; op.batch = &batch; op.flight = &f;
-  RunOp(op);
+  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
 }
 
 void ShardedEngine::LaunchBatchLocked(int ctx, std::vector<SelRequest *> &batch, Flight &f) {
@@ -1307,7 +1160,7 @@ void ShardedEngine::LaunchBatchLocked(int ctx, std::vector<SelRequest *> &batch,
 bool ShardedEngine::CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f, SelRequest *own) {
   const int64_t n = (int64_t)f.live.size();
   const size_t N = _sh.size();
-  BatchCtx &c = _bctx[ctx];
+  CombineCtx &c = _bctx[ctx];
   std::vector<std::vector<CiHipSelection>> winners(N);
   std::vector<std::vector<HipEngine::PriorityView>> views(N);
   Error err;
@@ -1343,8 +1196,7 @@ bool ShardedEngine::CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flig
       for (int64_t q = _Q; q < packs * 64; q++) r->skip[(size_t)(q >> 6)] |= 1ULL << (q & 63);
       r->ctx = &c;
       if (r == own) { ownLive = true; continue; }
-      for (SelRequest *&slot : batch) if (slot == r) slot = nullptr;   // (published here: not the caller's to publish again)
-      PublishState(&r->state, 3);
+      Combiner<SelRequest, CombineCtx>::LetSelect(batch, r);
     }
     return ownLive;
   }
@@ -1420,7 +1272,7 @@ Error ShardedEngine::SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHip
   while (_bctx[0].readers.load(std::memory_order_acquire) != 0) _mm_pause();
   std::vector<uint64_t> tags(_sh.size(), 0);
   {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     _shardsInFlightMax = 0;
@@ -1464,7 +1316,7 @@ Error ShardedEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, dou
   std::lock_guard<std::mutex> ctxLock(_bctx[0].mu);
   while (_bctx[0].readers.load(std::memory_order_acquire) != 0) _mm_pause();
   {
-    std::lock_guard<OpMutex> lk(_opMu);
+    std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
     // every shard's sweep is in flight (its own device and stream) before the first one is waited for
@@ -1491,7 +1343,7 @@ Error ShardedEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, dou
 
 // ---- maintenance ------------------------------------------------------------------------------------------------------------
 Error ShardedEngine::RemoveQuestions(int64_t n, const int64_t *pQIds) {   // BaseEngine.cpp:722-743; all ids validated before the first is removed
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   Error e = MaintenanceOnly("remove questions");
   if (!e.ok()) return e;
   if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "Counts must be non-negative.");
@@ -1509,7 +1361,7 @@ Error ShardedEngine::RemoveQuestions(int64_t n, const int64_t *pQIds) {   // Bas
 }
 
 Error ShardedEngine::RemoveTargets(int64_t n, const int64_t *pTIds) {   // BaseEngine.cpp:745-765
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   Error e = MaintenanceOnly("remove targets");
   if (!e.ok()) return e;
   // (the target axis is replicated: every shard validates and removes the same ids; shard 0 refuses a bad call before any other is asked)
@@ -1598,7 +1450,7 @@ Error ShardedEngine::Rebuild(int64_t newQ, int64_t newT, const std::vector<int64
 }
 
 Error ShardedEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) {
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   Error e = MaintenanceOnly("add questions/targets");
   if (!e.ok()) return e;
   if (nQuestions < 0 || nTargets < 0)
@@ -1640,7 +1492,7 @@ Error ShardedEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t 
 }
 
 Error ShardedEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets) {
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   Error e = MaintenanceOnly("compact the KB");
   if (!e.ok()) return e;
   if (!pnQuestions || !ppOldQuestions || !pnTargets || !ppOldTargets) return Error::Make(ErrCode::NullArgument, "Nullptr output.");
@@ -1704,7 +1556,7 @@ struct FileGuard {
 Error ShardedEngine::SaveKB(const char *filePath, bool doubleBuffer) {
   (void)doubleBuffer;
   if (!filePath) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name.");
-  std::lock_guard<OpMutex> lk(_opMu);
+  std::lock_guard<OpLock> lk(_opMu);
   { Error e = FlushAnswers(); if (!e.ok()) return e; }
   for (auto &s : _sh) { Error e = s->Synchronize(); if (!e.ok()) return e; }   // (also parks resident sweeps)
   FileGuard fg{std::fopen(filePath, "wb")};
