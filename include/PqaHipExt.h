@@ -133,6 +133,20 @@ PQACORE_API void *PqaEngine_StartQuizBatch(void *pvEngine, const int64_t nQuizze
  * gathered into such a batch by the engine itself (option "combine"; counters "resume_batches", "resumes_batched"). */
 PQACORE_API void *PqaEngine_ResumeQuizBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts,
                                             const CiAnsweredQuestion *pAQs, int64_t *pQuizzes);
+/* Train for nRecords records in one call: record i = the pCounts[i] answered questions starting at pAQs[sum(pCounts[0..i))],
+ * its target pTargets[i] and amount pAmounts[i].  A, D and vB end bit-identical to nRecords consecutive PqaEngine_Train calls
+ * in this order (reference PqaCore/CpuEngine.cpp:102-183, CETrainOperation.cpp:15-83); the asked-questions counter grows by
+ * sum(pCounts).  All or none: every record is validated before any cell changes; the error names the batch entry.  pAQs may be
+ * null when every count is 0.  One launch per chunk of at most "train_chunk_steps" steps (default 2^22); read-only counters
+ * "train_bulk_calls", "train_bulk_records", "train_bulk_launches", "train_bulk_host_ns" (host preparation and launching) and
+ * "train_bulk_device_ns" (the kernels, between events), summed over the engine's batches. */
+PQACORE_API void *PqaEngine_TrainBatch(void *pvEngine, const int64_t nRecords, const int64_t *pCounts,
+                                       const CiAnsweredQuestion *pAQs, const int64_t *pTargets, const double *pAmounts);
+/* RecordQuizTarget for nQuizzes quizzes (ids may repeat) in one call: the same KB as consecutive PqaEngine_RecordQuizTarget
+ * calls (BaseEngine.cpp:529-566, CpuEngine.cpp:442-466); the counter is not touched.  All or none likewise; same launches and
+ * counters as PqaEngine_TrainBatch. */
+PQACORE_API void *PqaEngine_RecordQuizTargetBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes,
+                                                  const int64_t *pTargets, const double *pAmounts);
 /* ListTopTargets for nQuizzes quizzes (any number; 256 per launch sequence) without copying a posterior to the host: pDest[i * maxCount + j],
  * j < pCounts[i], is the listing PqaEngine_ListTopTargets(pQuizzes[i], maxCount) returns -- descending probability, gaps and
  * probabilities <= 0 dropped (reference PqaCore/CEHeapifyPriorsSubtaskMake.cpp:42-52), equal probabilities in the order the reference's

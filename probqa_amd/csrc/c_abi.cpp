@@ -438,6 +438,16 @@ PQACORE_API void *PqaEngine_ResumeQuizBatch(void *pvEngine, const int64_t nQuizz
   static_assert(sizeof(CiAnsweredQuestion) == sizeof(AQ), "the answered questions are passed through as they are");
   return ReturnErr(pEng->ResumeQuizBatch(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pQuizzes));
 }
+PQACORE_API void *PqaEngine_TrainBatch(void *pvEngine, const int64_t nRecords, const int64_t *pCounts, const CiAnsweredQuestion *pAQs,
+                                       const int64_t *pTargets, const double *pAmounts) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(pEng->TrainBatch(nRecords, pCounts, reinterpret_cast<const AQ *>(pAQs), pTargets, pAmounts));
+}
+PQACORE_API void *PqaEngine_RecordQuizTargetBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pTargets,
+                                                  const double *pAmounts) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(pEng->RecordQuizTargetBatch(nQuizzes, pQuizzes, pTargets, pAmounts));
+}
 PQACORE_API void *PqaEngine_ListTopTargetsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
                                                 CiRatedTarget *pDest, int64_t *pCounts) {
   ENGINE_OR_RETURN_ERROR;

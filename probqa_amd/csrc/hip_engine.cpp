@@ -280,6 +280,7 @@ HipEngine::~HipEngine() {
   for (auto &g : _graphs) hipGraphExecDestroy(g.second.exec);
   hipFree(_dGraphScratch); hipFree(_dTagCell);
   for (QuizPinned *slab : _pinSlabs) hipHostFree(slab);
+  FreeTrainBulk();
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   if (_hTopBatch) hipHostFree(_hTopBatch);
   hipFree(_dTopExact);
@@ -338,6 +339,7 @@ Error HipEngine::SetOption(const char *name, int64_t value) {
   else if (n == "fuse_update") { _optFuseUpdate = value ? 1 : 0; }   // RecordAnswer's posterior update inside the speculative sweep's launch
   else if (n == "post_always") { _optPostAlways = value ? 1 : 0; }   // test hook: RecordAnswer / ListTopTargets always as posted operations
   else if (n == "combine_linger_us") { if (value < 0 || value > 10000) goto bad; _optLingerUs = value; }
+  else if (n == "train_chunk_steps") { if (value < 1 || value > (int64_t(1) << 28)) goto bad; _optTrainChunkSteps = value; }   // test hook: the most steps per launch of a training batch
   else if (n == "workers") { if (value < 1 || value > kMaxWorkers) goto bad; _optWorkers = value; }
   else if (n == "eval_subtasks") { if (value < 0 || value > 8192) goto bad; _optEvalSubtasks = value; }
   else if (n == "eval_variant") { if (value < 0) goto bad; _optEvalVariant = value; }
@@ -413,6 +415,12 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "train_batch_calls") return (int64_t)_trainBatchCalls;    // ... this many of them           // ... in this many rounds
   if (n == "resume_batches") return (int64_t)_resumeBatches;         // launch sequences that ran posted ResumeQuiz calls together ...
   if (n == "resumes_batched") return (int64_t)_resumesBatched;       // ... this many of them
+  if (n == "train_chunk_steps") return _optTrainChunkSteps;
+  if (n == "train_bulk_calls") return (int64_t)_trainBulkCalls;       // TrainBatch / RecordQuizTargetBatch calls that trained ...
+  if (n == "train_bulk_records") return (int64_t)_trainBulkRecords;   // ... their records ...
+  if (n == "train_bulk_launches") return (int64_t)_trainBulkLaunches; // ... and their launches (one per chunk)
+  if (n == "train_bulk_host_ns") return (int64_t)_trainBulkHostNs;    // their host time, waits for the device left out ...
+  if (n == "train_bulk_device_ns") return (int64_t)_trainBulkDeviceNs;   // ... and their kernels' time between events
   if (n == "update_flushes") return (int64_t)_flushes;              // launches that ran deferred RecordAnswers ...
   if (n == "updates_flushed") return (int64_t)_flushedUpdates;      // ... the updates they ran ...
   if (n == "update_max_flush") return (int64_t)_maxFlush;           // ... and the most in one launch

@@ -197,6 +197,8 @@ class IEngine {
   virtual Error RecordAnswerBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers) = 0;
   virtual Error StartQuizBatch(int64_t n, int64_t *pQuizzes) = 0;
   virtual Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) = 0;
+  virtual Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) = 0;
+  virtual Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) = 0;
   virtual Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) = 0;
 };
 
@@ -263,6 +265,8 @@ class HipEngine : public IEngine {
   Error RecordAnswerBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers) override;
   Error StartQuizBatch(int64_t n, int64_t *pQuizzes) override;
   Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) override;
+  Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) override;
+  Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) override;
   Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
@@ -320,6 +324,11 @@ class HipEngine : public IEngine {
   Error CollectBatchSelections(int64_t n, uint64_t tag, CiHipSelection *pOut);
   Error CollectBatchPriorities(int64_t n, double *pOut);
   Error ValidateTrain(int64_t nQuestions, const AQ *pAQs, int64_t iTarget, int64_t iQuiz);
+  // The same for a whole TrainBatch (pQuizzes == nullptr) or RecordQuizTargetBatch (pCounts, pAQs unused); an error names its entry.
+  // The argument checks that come before the lock are the static ones below, shared with the sharded engine.
+  Error ValidateTrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const int64_t *pQuizzes);
+  static Error CheckTrainBatchArgs(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts);
+  static Error CheckQuizTargetBatchArgs(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts);
   bool IsRegularMode() const { return _mode == Mode::Regular; }
   bool IsMaintenanceMode() const { return _mode == Mode::Maintenance; }
   double InitAmount() const { return _initAmount; }
@@ -362,7 +371,18 @@ class HipEngine : public IEngine {
   size_t _dResumeBytes = 0, _hResumeBytes = 0;
   uint64_t _resumeBatches = 0, _resumesBatched = 0;   // options "resume_batches", "resumes_batched": drains that ran posted ResumeQuiz calls, and those calls
   StartBatchInline *_startBatch = nullptr;   // StartQuizBatch: CreateQuiz queues the new quizzes' buffers here instead of launching
+  // the steps of one training call in execution order, appended to `out`; scratch: the caller's, reused from call to call
+  void AppendTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &out, std::vector<int64_t> &scratch) const;
   void BuildTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &steps, std::vector<int64_t> &chainStart) const;
+  // ---- many trainings in one call (hip_engine_train.cpp)
+  struct TrainRecord { const AQ *pAQs; int64_t n, iTarget; double amount; };
+  struct TrainBulk;                    // host scratch, pinned and device staging, events: kept from call to call
+  TrainBulk *_tb = nullptr;
+  void FreeTrainBulk();
+  Error ValidateTrainBatchLocked(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const int64_t *pQuizzes);
+  Error TrainRecordsLocked(const std::vector<TrainRecord> &recs, bool fromQuiz);
+  int64_t _optTrainChunkSteps = int64_t(1) << 22;   // option "train_chunk_steps": the most steps one launch of a batch carries
+  uint64_t _trainBulkCalls = 0, _trainBulkRecords = 0, _trainBulkLaunches = 0, _trainBulkHostNs = 0, _trainBulkDeviceNs = 0;
   Error TrainLocked(int64_t nQuestions, const AQ *pAQs, int64_t iTarget, double amount, bool fromQuiz);
   Error ValidateTrainLocked(int64_t nQuestions, const AQ *pAQs, int64_t iTarget) const;
   uint64_t NextRandom();

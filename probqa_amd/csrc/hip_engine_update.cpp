@@ -693,19 +693,17 @@ Error HipEngine::ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t
 //     entries at a time through Perform2, a last odd one through Perform1 (CETrainSubtaskAdd.cpp:17-38);
 //   fromQuiz = true: CpuEngine::RecordQuizTargetSpec (CpuEngine.cpp:442-466) -- the quiz's answers in order, pairs (0,1), (2,3) ...
 // Perform2 over two different questions is two independent Perform1 steps (CETrainOperation.cpp:56-82); over one question it
-// is a step of kind 2 (same answer) or 3 (different answers), see kb_kernels.hip.  The steps come out grouped by question
-// (chains), each chain in execution order; steps on other shards' questions are dropped.
-void HipEngine::BuildTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &steps, std::vector<int64_t> &chainStart) const {
-  std::vector<std::pair<int64_t, TrainStep>> ordered;   // (execution rank, step)
-  int64_t rank = 0;
+// is a step of kind 2 (same answer) or 3 (different answers), see kb_kernels.hip.  Steps on other shards' questions are dropped.
+// BuildTrainSteps groups them by question (chains), each chain in execution order.
+void HipEngine::AppendTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &out, std::vector<int64_t> &scratch) const {
   auto local = [&](int64_t q) { return q >= _qFirst && q < _qFirst + _Q; };
   auto perform1 = [&](const AQ &aq) {
-    if (local(aq.iQuestion)) ordered.push_back({rank++, TrainStep{1, aq.iQuestion - _qFirst, aq.iAnswer, aq.iAnswer}});
+    if (local(aq.iQuestion)) out.push_back(TrainStep{1, aq.iQuestion - _qFirst, aq.iAnswer, aq.iAnswer});
   };
   auto perform2 = [&](const AQ &first, const AQ &second) {
     if (first.iQuestion != second.iQuestion) { perform1(first); perform1(second); return; }
     if (!local(first.iQuestion)) return;
-    ordered.push_back({rank++, TrainStep{first.iAnswer == second.iAnswer ? 2 : 3, first.iQuestion - _qFirst, first.iAnswer, second.iAnswer}});
+    out.push_back(TrainStep{first.iAnswer == second.iAnswer ? 2 : 3, first.iQuestion - _qFirst, first.iAnswer, second.iAnswer});
   };
   if (fromQuiz) {
     int64_t i = 0;
@@ -713,7 +711,8 @@ void HipEngine::BuildTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::v
     if (i == n - 1) perform1(pAQs[i]);
   } else {
     const int64_t nWorkers = _optWorkers;
-    std::vector<int64_t> last((size_t)nWorkers, -1), prev((size_t)std::max<int64_t>(n, 1), -1);
+    scratch.assign((size_t)(nWorkers + n), -1);   // [last per bucket | prev per entry]
+    int64_t *last = scratch.data(), *prev = last + nWorkers;
     for (int64_t i = 0; i < n; i++) {
       const int64_t bucket = pAQs[i].iQuestion % nWorkers;
       prev[i] = last[bucket];
@@ -730,14 +729,17 @@ void HipEngine::BuildTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::v
       }
     }
   }
-  std::stable_sort(ordered.begin(), ordered.end(), [](const auto &x, const auto &y) { return x.second.q < y.second.q; });
+}
+
+void HipEngine::BuildTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &steps, std::vector<int64_t> &chainStart) const {
+  std::vector<int64_t> scratch;
   steps.clear();
+  AppendTrainSteps(n, pAQs, fromQuiz, steps, scratch);   // (execution order)
+  std::stable_sort(steps.begin(), steps.end(), [](const TrainStep &x, const TrainStep &y) { return x.q < y.q; });
   chainStart.clear();
-  for (size_t i = 0; i < ordered.size(); i++) {
-    if (i == 0 || ordered[i].second.q != ordered[i - 1].second.q) chainStart.push_back((int64_t)i);
-    steps.push_back(ordered[i].second);
-  }
-  chainStart.push_back((int64_t)ordered.size());
+  for (size_t i = 0; i < steps.size(); i++)
+    if (i == 0 || steps[i].q != steps[i - 1].q) chainStart.push_back((int64_t)i);
+  chainStart.push_back((int64_t)steps.size());
 }
 
 // Validation of a training call (CETrainSubtaskDistrib.h:26-45, CpuEngine.cpp:138-155): ranges over the GLOBAL question range, gaps

@@ -154,6 +154,57 @@ __global__ void train_batch_inline_kernel(void *__restrict__ cube, int elem, dou
   }
 }
 
+// Many records in one launch (hip_engine_train.cpp: why the result is bit-identical to consecutive training calls).  One lane per
+// chain -- the steps on one (target, question) in record order -- with the step arithmetic of train_steps_body operation for
+// operation, but each step with its own record's amount.  D[q][t] belongs to the chain alone: it stays in a register and is
+// rounded where cube_st would round it, once per step on a Float cube.  The A cells are read and written in memory (a chain may
+// come back to one).  The lanes after the chains add each target's amounts to vB[t] in record order with the rounding of
+// train_steps_body.  No barriers: the kernel is latency-bound and its speed is the number of chains in flight.
+__global__ __launch_bounds__(64) void train_chains_kernel(void *__restrict__ cube, int elem, double *__restrict__ vB, int64_t K,
+                                                          int64_t ldT, const TrainChain *__restrict__ chains, int64_t nChains,
+                                                          int64_t nTargets, const TrainChainStep *__restrict__ steps,
+                                                          const double *__restrict__ amounts) {
+  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < nChains + nTargets; c += (int64_t)gridDim.x * blockDim.x) {
+    const TrainChain ch = chains[c];
+    if (c >= nChains) {
+      double b = vB[ch.t];
+      for (int32_t i = ch.first; i < ch.end; i++) {
+        b = b + amounts[i];                                  // PqaCore/CpuEngine.cpp:172, :462
+        if (elem == 4) b = (double)(float)b;
+      }
+      vB[ch.t] = b;
+      continue;
+    }
+    const int64_t q = steps[ch.first].q;
+    const int64_t colQ = q * (K + 1) * ldT + ch.t, iD = colQ + K * ldT;
+    double d = cube_ld(cube, elem, iD);
+    for (int32_t i = ch.first; i < ch.end; i++) {
+      const TrainChainStep st = steps[i];
+      const uint32_t kind = st.kindRec & 3u;
+      const double amount = amounts[st.kindRec >> 2];
+      const double twoB = 2 * amount, bSquare = amount * amount;   // CETrainTaskNumSpec.h:24-32
+      const double fourB = 4 * amount, square2B = 4 * bSquare;
+      const int64_t iA = colQ + (int64_t)st.a1 * ldT;
+      const double oldA = cube_ld(cube, elem, iA);
+      const double a = sqrt(oldA);                                 // CETrainOperation.cpp:18
+      if (kind == 3) {
+        const int64_t iA2 = colQ + (int64_t)st.a2 * ldT;
+        const double oldA2 = cube_ld(cube, elem, iA2);
+        const double add1 = a * twoB + bSquare, add2 = sqrt(oldA2) * twoB + bSquare;   // :42-44
+        cube_st(cube, elem, iA, oldA + add1);                      // :47-53
+        cube_st(cube, elem, iA2, oldA2 + add2);
+        d = d + (add1 + add1);
+      } else {
+        const double addend = kind == 2 ? a * fourB + square2B : a * twoB + bSquare;   // :19
+        cube_st(cube, elem, iA, oldA + addend);                    // :23-24
+        d = d + addend;                                            // :25
+      }
+      if (elem == 4) d = (double)(float)d;                         // (what cube_st and the next cube_ld would make of it)
+    }
+    cube_st(cube, elem, iD, d);
+  }
+}
+
 // ListTopTargets on the device (top_targets_publish in pqa_device.h); T <= 16384.
 static_assert(sizeof(TopOut) == sizeof(RatedTargetDev), "same record");
 template <bool SMALL>
@@ -294,6 +345,14 @@ hipError_t LaunchTrainSteps(void *cube, int elem, double *vB, int64_t K, int64_t
 hipError_t LaunchTrainStepsInline(void *cube, int elem, double *vB, int64_t K, int64_t ldT, const TrainStepsInline &in,
                                   int64_t iTarget, double amount, hipStream_t stream) {
   hipLaunchKernelGGL(train_steps_inline_kernel, dim3(1), dim3(64), 0, stream, cube, elem, vB, K, ldT, in, iTarget, amount);
+  return hipGetLastError();
+}
+
+hipError_t LaunchTrainChains(void *cube, int elem, double *vB, int64_t K, int64_t ldT, const TrainChain *chains, int64_t nChains,
+                             int64_t nTargets, const TrainChainStep *steps, const double *amounts, hipStream_t stream) {
+  if (nChains + nTargets <= 0) return hipSuccess;
+  hipLaunchKernelGGL(train_chains_kernel, dim3(grid_for(nChains + nTargets, 64)), dim3(64), 0, stream, cube, elem, vB, K, ldT, chains,
+                     nChains, nTargets, steps, amounts);
   return hipGetLastError();
 }
 

@@ -407,6 +407,18 @@ struct TrainBatchInline {
   TrainBatchStep steps[kTrainBatchSteps];
 };
 hipError_t LaunchTrainBatchInline(void *cube, int elem, double *vB, int64_t K, int64_t ldT, const TrainBatchInline &in, hipStream_t stream);
+// Many training records -- any targets, repeated ones too -- in one launch (TrainBatch / RecordQuizTargetBatch,
+// hip_engine_train.cpp).  Lane c < nChains runs chain c: the steps on one (target t, question) cell column, in record order;
+// lane nChains + j adds amounts[first .. end) to vB[t] of target slot j, in that order.  Every step names the amount of its
+// record: amounts[rec].  No two lanes touch the same cell.
+struct TrainChain { int64_t t; int32_t first, end; };   // chain: steps [first, end); target slot: amounts [first, end)
+struct TrainChainStep {                                 // kind 1 | 2 | 3 as TrainStep; q local
+  int32_t q;
+  uint32_t kindRec;                                     // rec << 2 | kind
+  int32_t a1, a2;
+};
+hipError_t LaunchTrainChains(void *cube, int elem, double *vB, int64_t K, int64_t ldT, const TrainChain *chains, int64_t nChains,
+                             int64_t nTargets, const TrainChainStep *steps, const double *amounts, hipStream_t stream);
 // Maintenance (PqaCore/CpuEngine.cpp:468-658): (re)initialise whole questions / whole target columns; compact the target
 // axis with (src,dst) column moves.  qs/ts/inits/moves are device arrays.
 hipError_t LaunchFillQuestions(void *cube, int elem, int64_t K, int64_t T, int64_t ldT, const int64_t *qs, const double *inits,

@@ -60,6 +60,8 @@ class ShardedEngine final : public IEngine {
   int64_t StartQuiz(Error &err) override;
   int64_t ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) override;
   Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) override;
+  Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) override;
+  Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) override;
   int64_t NextQuestion(Error &err, int64_t iQuiz) override;
   Error RecordAnswer(int64_t iQuiz, int64_t iAnswer) override;
   int64_t GetActiveQuestionId(Error &err, int64_t iQuiz) override;
@@ -981,6 +983,39 @@ Error ShardedEngine::Train(int64_t n, const AQ *pAQs, int64_t iTarget, double am
   e = BeforeTraining();
   if (!e.ok()) return e;
   for (auto &s : _sh) { e = s->Train(n, pAQs, iTarget, amount); if (!e.ok()) break; }
+  Error ae = AfterTraining();
+  return e.ok() ? ae : e;
+}
+
+// TrainBatch / RecordQuizTargetBatch: what Train does, once for the whole batch -- every shard validates every entry, then every
+// shard runs the batch on its own questions and its vB replica between the two barriers.
+Error ShardedEngine::TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) {
+  Error e = HipEngine::CheckTrainBatchArgs(n, pCounts, pAQs, pTargets, pAmounts);
+  if (!e.ok() || n == 0) return e;
+  CallScope scope(_activeCallers);
+  std::lock_guard<OpLock> lk(_opMu);
+  e = FlushAnswers();
+  if (!e.ok()) return e;
+  for (auto &s : _sh) { e = s->ValidateTrainBatch(n, pCounts, pAQs, pTargets, nullptr); if (!e.ok()) return e; }
+  e = BeforeTraining();
+  if (!e.ok()) return e;
+  for (auto &s : _sh) { e = s->TrainBatch(n, pCounts, pAQs, pTargets, pAmounts); if (!e.ok()) break; }
+  Error ae = AfterTraining();
+  return e.ok() ? ae : e;
+}
+
+Error ShardedEngine::RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) {
+  Error e = HipEngine::CheckQuizTargetBatchArgs(n, pQuizzes, pTargets, pAmounts);
+  if (!e.ok() || n == 0) return e;
+  CallScope scope(_activeCallers);
+  std::lock_guard<OpLock> lk(_opMu);
+  e = FlushAnswers();
+  if (!e.ok()) return e;
+  for (auto &s : _sh) { e = s->ValidateTrainBatch(n, nullptr, nullptr, pTargets, pQuizzes); if (!e.ok()) return e; }
+  e = BeforeTraining();
+  if (!e.ok()) return e;
+  for (int64_t i = 0; i < n; i++) Touch(pQuizzes[i]);
+  for (auto &s : _sh) { e = s->RecordQuizTargetBatch(n, pQuizzes, pTargets, pAmounts); if (!e.ok()) break; }
   Error ae = AfterTraining();
   return e.ok() ? ae : e;
 }

@@ -148,6 +148,8 @@ HIP_EXPORTS = {
     "PqaEngine_RecordAnswerBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_StartQuizBatch": (_vp, [_vp, _i64, _pi64]),
     "PqaEngine_ResumeQuizBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64]),
+    "PqaEngine_TrainBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64, _pdbl]),
+    "PqaEngine_RecordQuizTargetBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
 }
@@ -693,6 +695,40 @@ class PqaEngine:
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_ResumeQuizBatch(self.c_engine, n, counts, arr, out))
         return list(out[:n])
+
+    def train_batch(self, records, throw: bool = True) -> Optional[PqaError]:
+        """Train for every (answered_questions, i_target, amount) of `records` in one call: the KB consecutive `train` calls
+        would leave; all or none."""
+        counts = np.array([len(r[0]) for r in records], dtype=np.int64)
+        aqs = np.array([(aq.i_question, aq.i_answer) for r in records for aq in r[0]], dtype=np.int64).reshape(-1, 2)
+        targets = np.array([r[1] for r in records], dtype=np.int64)
+        amounts = np.array([r[2] for r in records], dtype=np.float64)
+        return self.train_batch_arrays(counts, aqs, targets, amounts, throw)
+
+    def train_batch_arrays(self, counts, aqs, targets, amounts, throw: bool = True) -> Optional[PqaError]:
+        """train_batch over numpy arrays: counts, targets int64 [n], amounts float64 [n], aqs int64 [sum(counts), 2] of
+        (question, answer) -- no Python object per record."""
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        targets = np.ascontiguousarray(targets, dtype=np.int64)
+        amounts = np.ascontiguousarray(amounts, dtype=np.float64)
+        aqs = np.ascontiguousarray(aqs, dtype=np.int64).reshape(-1, 2)
+        n = len(counts)
+        if len(targets) != n or len(amounts) != n:
+            raise ValueError("counts, targets and amounts must have the same length")
+        p_aqs = aqs.ctypes.data_as(_pAQ) if aqs.shape[0] > 0 else None
+        return _check(_lib.PqaEngine_TrainBatch(self.c_engine, n, counts.ctypes.data_as(_pi64), p_aqs, targets.ctypes.data_as(_pi64),
+                                                amounts.ctypes.data_as(_pdbl)), throw)
+
+    def record_quiz_target_batch(self, quizzes, targets, amounts, throw: bool = True) -> Optional[PqaError]:
+        """RecordQuizTarget for every (quizzes[i], targets[i], amounts[i]) in one call; all or none."""
+        quizzes = np.ascontiguousarray(quizzes, dtype=np.int64)
+        targets = np.ascontiguousarray(targets, dtype=np.int64)
+        amounts = np.ascontiguousarray(amounts, dtype=np.float64)
+        n = len(quizzes)
+        if len(targets) != n or len(amounts) != n:
+            raise ValueError("quizzes, targets and amounts must have the same length")
+        return _check(_lib.PqaEngine_RecordQuizTargetBatch(self.c_engine, n, quizzes.ctypes.data_as(_pi64), targets.ctypes.data_as(_pi64),
+                                                           amounts.ctypes.data_as(_pdbl)), throw)
 
     def list_top_targets_batch(self, quizzes, max_count: int) -> List[List[RatedTarget]]:
         """ListTopTargets of several quizzes with one launch sequence; no posterior leaves the device."""
