@@ -117,6 +117,21 @@ PQACORE_API int64_t PqaEngine_NextQuestionSampled(void *pvEngine, void **ppError
  * of nQuizzes x PqaEngine_NextQuestion (reference PqaCore/CpuEngine.cpp:337-415 serves them one sweep at a time). */
 PQACORE_API void *PqaEngine_NextQuestionArgmaxBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes,
                                                     int64_t *pQuestions);
+/* The reference's own selector (PqaCore/CpuEngine.cpp:362-400: a question drawn with probability proportional to its priority) for
+ * nQuizzes <= 256 distinct quizzes with ONE batched sweep and one selector launch behind it: pQuestions[i] is the question
+ * PqaEngine_NextQuestionSampled(pQuizzes[i], pRnd[i]) selects, and it becomes that quiz's active question; -1 (and no error) for a
+ * quiz with no question left.  A repeated or unknown quiz id is an error that names the entry and changes nothing.  The selector
+ * reads the priorities on the device, where the sweep left them; option "sampled_batch_host" = 1 serves the same call with the
+ * host's selector over the copied priorities instead (for comparison; default 0).  Read-only options: "sampled_batches" (calls that
+ * selected), "sampled_batch_device_ns" (with "time_sweeps": the selector launches' time between events), "priority_host_bytes"
+ * (bytes of priorities the batched sweeps have delivered to the host). */
+PQACORE_API void *PqaEngine_NextQuestionSampledBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const uint64_t *pRnd,
+                                                     int64_t *pQuestions);
+/* What a server with many quizzes in flight calls instead of nQuizzes x PqaEngine_NextQuestion: the engine's "select" option
+ * decides.  select = 1: PqaEngine_NextQuestionArgmaxBatch.  select = 0: one random number per quiz from the engine's generator, in
+ * batch order, exactly as nQuizzes consecutive PqaEngine_NextQuestion calls would draw them (a refused call draws none), then
+ * PqaEngine_NextQuestionSampledBatch. */
+PQACORE_API void *PqaEngine_NextQuestionBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, int64_t *pQuestions);
 /* RecordAnswer for nQuizzes quizzes (each with an active question) in one call and ONE launch -- every posterior bit-identical to
  * PqaEngine_RecordAnswer's (reference PqaCore/CERecordAnswerSubtaskMul.cpp:15-42 per quiz) -- and StartQuiz for nQuizzes new
  * quizzes likewise (pQuizzes receives their ids; all or none).  What a server with many quizzes in flight calls beside

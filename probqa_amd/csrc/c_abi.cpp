@@ -424,6 +424,15 @@ PQACORE_API void *PqaEngine_NextQuestionArgmaxBatch(void *pvEngine, const int64_
   ENGINE_OR_RETURN_ERROR;
   return ReturnErr(pEng->NextQuestionArgmaxBatch(nQuizzes, pQuizzes, pQuestions));
 }
+PQACORE_API void *PqaEngine_NextQuestionSampledBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const uint64_t *pRnd,
+                                                     int64_t *pQuestions) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(pEng->NextQuestionSampledBatch(nQuizzes, pQuizzes, pRnd, pQuestions));
+}
+PQACORE_API void *PqaEngine_NextQuestionBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, int64_t *pQuestions) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(pEng->NextQuestionBatch(nQuizzes, pQuizzes, pQuestions));
+}
 PQACORE_API void *PqaEngine_RecordAnswerBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pAnswers) {
   ENGINE_OR_RETURN_ERROR;
   return ReturnErr(pEng->RecordAnswerBatch(nQuizzes, pQuizzes, pAnswers));

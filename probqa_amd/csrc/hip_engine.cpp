@@ -271,7 +271,8 @@ HipEngine::~HipEngine() {
   hipFree(_dCube); hipFree(_dVB); hipFree(_dPriority); hipFree(_dRunLength); hipFree(_dPoleScratch); hipFree(_dExps); hipFree(_dStatus);
   hipFree(_dNOut); hipFree(_dSel); hipFree(_dSelScratch); hipFree(_dPriorScratch); hipFree(_dClusterScratch);
   for (BatchCtx &c : _ctx) {
-    hipFree(c.dSlots); hipFree(c.dScratch); hipFree(c.dPriority); hipFree(c.dPT); hipFree(c.dAcc); hipFree(c.dRecs); hipFree(c.dPriT); hipFree(c.dRerank); hipFree(c.dPole);
+    hipFree(c.dSlots); hipFree(c.dScratch); hipFree(c.dPriority); hipFree(c.dPT); hipFree(c.dAcc); hipFree(c.dRecs); hipFree(c.dPriT); hipFree(c.dRerank); hipFree(c.dPole); hipFree(c.dSelGrand); hipFree(c.dSelRun);
+    if (c.evSel[0]) { hipEventDestroy(c.evSel[0]); hipEventDestroy(c.evSel[1]); }
     if (c.hPri) hipHostFree(c.hPri);
     if (c.event) hipEventDestroy(c.event);
     if (c.h) hipHostFree(c.h);
@@ -351,6 +352,7 @@ Error HipEngine::SetOption(const char *name, int64_t value) {
   else if (n == "eval_max_grid") { if (value < 0 || value > 65535) goto bad; StopServer(); _optEvalMaxGrid = value; _kbVersion++; }
   else if (n == "fused_sampled") { _optFusedSampled = value ? 1 : 0; }
   else if (n == "host_sampled") { _optHostSampled = value ? 1 : 0; }
+  else if (n == "sampled_batch_host") { _optSampledBatchHost = value ? 1 : 0; }
   else if (n == "batch_min") { if (value < 0 || value > 257) goto bad; _optBatchMin = value; }
   else if (n == "rerank") { _optRerank = value ? 1 : 0; }
   else if (n == "batch_form") { if (value < 0 || value > 3) goto bad; _optBatchForm = value; }
@@ -383,6 +385,10 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "server_idle_us") return _optServerIdleUs;
   if (n == "fused_sampled") return _optFusedSampled;
   if (n == "host_sampled") return _optHostSampled;
+  if (n == "sampled_batch_host") return _optSampledBatchHost;
+  if (n == "sampled_batches") return (int64_t)_sampledBatches;                  // NextQuestionSampledBatch calls that selected ...
+  if (n == "sampled_batch_device_ns") return (int64_t)_sampledBatchDeviceNs;    // ... and their selector launches' time between events
+  if (n == "priority_host_bytes") return (int64_t)_priorityHostBytes;           // priorities the batched sweeps delivered to the host
   if (n == "speculate") return _optSpeculate;
   if (n == "combine") return _optCombine;
   if (n == "combine_linger_us") return _optLingerUs;

@@ -182,6 +182,8 @@ class IEngine {
   virtual int64_t NextQuestionSampled(Error &err, int64_t iQuiz, uint64_t rnd) = 0;
   virtual Error GetPriors(int64_t iQuiz, double *pOut, int64_t n) = 0;
   virtual Error NextQuestionArgmaxBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) = 0;
+  virtual Error NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) = 0;
+  virtual Error NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) = 0;
   virtual Error EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) = 0;
   virtual Error SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHipSelection *pOut) = 0;
   virtual Error Log2HotArray(const double *pIn, double *pOut, int64_t n) = 0;
@@ -250,6 +252,9 @@ class HipEngine : public IEngine {
   Error GetPriors(int64_t iQuiz, double *pOut, int64_t n) override;
   int64_t NextQuestionArgmaxGraph(Error &err, Quiz *q);
   Error NextQuestionArgmaxBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) override;
+  // the reference's selector (NextQuestionSampled) for many quizzes: one batched sweep, one selector launch behind it
+  Error NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) override;
+  Error NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) override;   // by option "select", random numbers drawn in batch order
   Error EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) override;
   Error SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHipSelection *pOut) override;   // pOut[i][q], q < local question count
   Error Log2HotArray(const double *pIn, double *pOut, int64_t n) override;  // device log2hot over an array (tests)
@@ -323,6 +328,7 @@ class HipEngine : public IEngine {
   Error EnqueueBatch(int64_t n, const int64_t *pQuizzes, bool wantPriorities, uint64_t *pTag);
   Error CollectBatchSelections(int64_t n, uint64_t tag, CiHipSelection *pOut);
   Error CollectBatchPriorities(int64_t n, double *pOut);
+  Error ValidateBatch(int64_t n, const int64_t *pQuizzes) { std::lock_guard<EngineMutex> lk(_mu); return ValidateBatchLocked(n, pQuizzes); }   // what EnqueueBatch would refuse; changes nothing
   Error ValidateTrain(int64_t nQuestions, const AQ *pAQs, int64_t iTarget, int64_t iQuiz);
   // The same for a whole TrainBatch (pQuizzes == nullptr) or RecordQuizTargetBatch (pCounts, pAQs unused); an error names its entry.
   // The argument checks that come before the lock are the static ones below, shared with the sharded engine.
@@ -577,7 +583,12 @@ class HipEngine : public IEngine {
   int64_t _optLongRowForm = 1;           // option "long_row_form": StartQuiz / RecordAnswer over rows beyond 16384 targets as one workgroup per subtask of the sum
   // batched selections (NextQuestionArgmaxBatch); allocated on first use
   static constexpr int64_t kMaxBatch = 256, kBatchGrid = 1024;
-  struct BatchPinned { QuizSlot slots[kMaxBatch]; SelectResult out[kMaxBatch]; uint64_t seq[kMaxBatch]; };
+  // (sweepOut / sweepSeq: where the sweep of a sampled batch publishes its own winners, so that out / seq are the selector's
+  //  behind it; rnd: that batch's random numbers, read by the selector where they are)
+  struct BatchPinned {
+    QuizSlot slots[kMaxBatch]; SelectResult out[kMaxBatch]; uint64_t seq[kMaxBatch];
+    SelectResult sweepOut[kMaxBatch]; uint64_t sweepSeq[kMaxBatch]; uint64_t rnd[kMaxBatch];
+  };
   // Everything ONE batched sweep in flight needs of its own: the staged slots and winner records, the scratch of the
   // row-sharing sweep (batch_kernels.hip; sized by its plan, grown on demand), the host copy of the priority vectors.  Two of
   // them: the batch calls of the ABI and the shards' halves use the first; the leaders of combined sweeps alternate, so that
@@ -593,6 +604,9 @@ class HipEngine : public IEngine {
     void *dRerank = nullptr;             // Float engines: the candidates of the fp64 re-rank and their priorities
     void *dPole = nullptr;               // Double engines: the batched sweeps' pole scratch (BatchPlan::pole)
     size_t poleBytes = 0;
+    double *dSelGrand = nullptr, *dSelRun = nullptr;   // the batched sampled selector's totals and run lengths (select_kernels.hip)
+    size_t selGrandBytes = 0, selRunBytes = 0;
+    hipEvent_t evSel[2] = {nullptr, nullptr};          // around that selector's launch
     int lastBp = 0;
     double *hPri = nullptr;              // pinned: the batch's priority vectors for the host-side selector -- copied there behind the
     size_t hPriDoubles = 0;              // row-sharing sweep, or written there by the grid.y = quiz sweep itself as {priority, launch tag} records
@@ -604,7 +618,15 @@ class HipEngine : public IEngine {
   // wantPriorities: the row-sharing sweep with its priority matrix kept (EvalPrioritiesBatch).  hostPriorities: whichever form
   // suits the batch, and the quizzes' priority vectors copied into _hBatchPri (layout: *pQuizMinor) for the host's selector.
   Error BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std::vector<Quiz *> &quizzes, bool wantPriorities, uint64_t tag,
-                   bool hostPriorities = false, bool *pQuizMinor = nullptr, bool *pTagged = nullptr);
+                   bool hostPriorities = false, bool *pQuizMinor = nullptr, bool *pTagged = nullptr, bool devicePriorities = false);
+  // devicePriorities: the batch's form as for an argmax batch, every quiz's priorities left on the device (its own vector or the
+  // quiz-minor matrix: lastBp), the sweep's own winners published to sweepOut / sweepSeq -- for the selector launched behind it
+  Error ValidateBatchLocked(int64_t n, const int64_t *pQuizzes);
+  Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
+  Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
+  int64_t _optSampledBatchHost = 0;    // option "sampled_batch_host": 1 = NextQuestionSampledBatch by the host's selector over the copied priorities (the A/B leg)
+  uint64_t _sampledBatches = 0, _sampledBatchDeviceNs = 0;   // read-only "sampled_batches", "sampled_batch_device_ns" (the selector's launches between events)
+  uint64_t _priorityHostBytes = 0;     // read-only "priority_host_bytes": priorities the batched sweeps delivered to the host
   Error WaitBatchFlags(BatchCtx &c, int64_t n, uint64_t tag);
   Error EnqueueBatchLocked(int64_t n, const int64_t *pQuizzes, bool wantPriorities, uint64_t *pTag);
   Error CollectBatchSelectionsLocked(int64_t n, uint64_t tag, CiHipSelection *pOut);

@@ -383,7 +383,7 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
 
 
 Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std::vector<Quiz *> &quizzes, bool wantPriorities, uint64_t tag,
-                            bool hostPriorities, bool *pQuizMinor, bool *pTagged) {
+                            bool hostPriorities, bool *pQuizMinor, bool *pTagged, bool devicePriorities) {
   if (!c.h) {  // first batch: staging in host-coherent pinned memory, winner records
     HIP_TRY(hipHostMalloc(&c.h, sizeof(BatchPinned), hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(c.h, 0, sizeof(BatchPinned));
@@ -431,6 +431,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
       c.hPriCoherent = false;
     }
     HIP_TRY(hipMemcpyAsync(c.hPri, src, doubles * sizeof(double), hipMemcpyDeviceToHost, _stream));
+    _priorityHostBytes += doubles * sizeof(double);
     return Error();
   };
   if (!rowSharing && c.priorityQ != _Q) {  // per-quiz priority vectors of the grid.y form, (re)sized with the knowledge base
@@ -449,7 +450,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
       if (pQuizzes[j] == pQuizzes[i])
         return Error::MakeP(ErrCode::IndexOutOfRange, "quizId=" + std::to_string(pQuizzes[i]), "A quiz appears twice in one batch.");
     c.h->slots[i] = QuizSlot{quizzes[i]->dPrior, quizzes[i]->dAsked, rowSharing ? nullptr : c.dPriority + (size_t)i * (size_t)_Q,
-                                 &c.h->out[i], &c.h->seq[i], nullptr};
+                                 devicePriorities ? &c.h->sweepOut[i] : &c.h->out[i], devicePriorities ? &c.h->sweepSeq[i] : &c.h->seq[i], nullptr};
   }
   // grid.y = quiz and the priorities wanted on the host: every workgroup stores the priorities of its questions there itself, one
   // {priority, launch tag} record each (as the single-quiz sweep's hand-over, FusedSelect::hostPriority) -- no copy behind the
@@ -471,6 +472,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
       c.hPriCoherent = true;
     }
     for (int64_t i = 0; i < n; i++) c.h->slots[i].hostPriority = reinterpret_cast<TaggedPriority *>(c.hPri) + (size_t)i * (size_t)_Q;
+    _priorityHostBytes += doubles * sizeof(double);
   }
   HIP_TRY(hipMemcpyAsync(c.dSlots, c.h->slots, (size_t)n * sizeof(QuizSlot), hipMemcpyHostToDevice, _stream));
   StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
@@ -504,7 +506,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
     HIP_TRY(grow(&c.dPT, c.ptBytes, plan.ptBytes));
     HIP_TRY(grow((void **)&c.dRecs, c.recBytes, plan.recBytes));
     HIP_TRY(growPole(plan));
-    const bool matrix = wantPriorities || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
+    const bool matrix = wantPriorities || devicePriorities || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
     if (matrix) HIP_TRY(grow((void **)&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
     HIP_TRY(LaunchEvalMidBatch(kb, c.dSlots, (int)n, &plan, c.dPT, c.dRecs, matrix ? c.dPriT : nullptr, 0, tag, false, _stream));
     c.lastBp = plan.Bp;
@@ -534,9 +536,9 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
   HIP_TRY(grow((void **)&c.dAcc, c.accBytes, plan.accBytes));
   HIP_TRY(grow((void **)&c.dRecs, c.recBytes, plan.recBytes));
   // Float engines: the fp32 sweep nominates every quiz's best questions, fp64 decides among them (option "rerank", default on)
-  const bool rerank = _elem == 4 && _optRerank != 0;
+  const bool rerank = _elem == 4 && _optRerank != 0 && !devicePriorities;   // (an argmax device: the sampled selector reads the matrix itself)
   HIP_TRY(growPole(plan));
-  const bool matrix = wantPriorities || rerank || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
+  const bool matrix = wantPriorities || devicePriorities || rerank || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
   if (matrix) HIP_TRY(grow((void **)&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
   if (rerank) HIP_TRY(grow(&c.dRerank, c.rerankBytes, BatchRerankScratchBytes()));
   HIP_TRY(LaunchEvalBatch(kb, c.dSlots, (int)n, &plan, c.dPT, c.dAcc, c.dRecs, matrix ? c.dPriT : nullptr, 0, tag,
@@ -606,11 +608,13 @@ Error HipEngine::CollectBatchPrioritiesLocked(int64_t n, double *pOut) {
   hipSetDevice(_device);
   BatchCtx &c = _ctx[0];
   if (c.lastBp == 0) {   // grid.y = quiz: every quiz's own vector
+    _priorityHostBytes += (size_t)n * (size_t)_Q * sizeof(double);
     HIP_TRY(hipMemcpyAsync(pOut, c.dPriority, (size_t)n * (size_t)_Q * sizeof(double), hipMemcpyDeviceToHost, _stream));
     HIP_TRY(hipStreamSynchronize(_stream));
     return Error();
   }
   std::vector<double> host((size_t)_Q * (size_t)c.lastBp);
+  _priorityHostBytes += host.size() * sizeof(double);
   HIP_TRY(hipMemcpyAsync(host.data(), c.dPriT, host.size() * sizeof(double), hipMemcpyDeviceToHost, _stream));
   HIP_TRY(hipStreamSynchronize(_stream));
   for (int64_t i = 0; i < n; i++)
@@ -674,6 +678,149 @@ Error HipEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double 
   Error err = EnqueueBatchLocked(n, pQuizzes, true, &tag);
   if (!err.ok() || n == 0) return err;
   return CollectBatchPrioritiesLocked(n, pOut);
+}
+
+// ---- NextQuestionSampledBatch: the reference's selector (PqaCore/CpuEngine.cpp:362-400) for many quizzes ------------------------------
+// One batched sweep, chosen as NextQuestionArgmaxBatch chooses it, with the pole fix behind it, and ONE selector launch behind that
+// on the same stream (select_kernels.hip: LaunchSelectSampledBatch).  The selector reads the priorities where the sweep left them --
+// the quizzes' own vectors or the quiz-minor matrix -- so nothing of size Q crosses to the host.  In this mode the sweep publishes
+// its own winners to BatchPinned::sweepOut / sweepSeq; out[i] / seq[i] are the selector's, and WaitBatchFlags collects them.
+Error HipEngine::ValidateBatchLocked(int64_t n, const int64_t *pQuizzes) {   // what EnqueueBatchLocked and BatchSweep refuse, before anything changes
+  Error err = CheckRegular("compute next questions");
+  if (!err.ok()) return err;
+  if (n < 0 || n > kMaxBatch)
+    return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(n, 0, kMaxBatch), "Batch size is out of range.");
+  if (n == 0) return Error();
+  if (!pQuizzes) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  for (int64_t i = 0; i < n; i++) {
+    if (!UseQuiz(err, pQuizzes[i])) return err;
+    for (int64_t j = 0; j < i; j++)
+      if (pQuizzes[j] == pQuizzes[i])
+        return Error::MakeP(ErrCode::IndexOutOfRange, "quizId=" + std::to_string(pQuizzes[i]), "A quiz appears twice in one batch.");
+  }
+  return Error();
+}
+
+Error HipEngine::LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag) {
+  const int64_t nSub = _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;  // reference PqaCore/CpuEngine.cpp:339
+  std::memcpy(c.h->rnd, pRnd, (size_t)n * sizeof(uint64_t));   // (host-coherent: the selector reads them there)
+  size_t grandDoubles = 0, runDoubles = 0;
+  SelectSampledBatchScratch(_Q, nSub, (int)n, c.lastBp, &grandDoubles, &runDoubles);
+  auto grow = [&](double **p, size_t &have, size_t need) -> hipError_t {
+    if (need <= have) return hipSuccess;
+    hipStreamSynchronize(_stream);
+    hipFree(*p);
+    *p = nullptr;
+    have = 0;
+    const hipError_t e = hipMalloc((void **)p, need);
+    if (e == hipSuccess) have = need;
+    return e;
+  };
+  HIP_TRY(grow(&c.dSelGrand, c.selGrandBytes, grandDoubles * sizeof(double)));
+  HIP_TRY(grow(&c.dSelRun, c.selRunBytes, runDoubles * sizeof(double)));
+  SampledBatch a{};
+  a.slots = c.dSlots; a.nSlots = (int)n; a.Bp = c.lastBp;
+  a.priorityT = c.lastBp > 0 ? c.dPriT : nullptr;
+  a.qgap = _dQGap; a.n = _Q; a.nWorkers = nSub;
+  a.rnd = c.h->rnd; a.grand = c.dSelGrand; a.run = c.dSelRun;
+  a.out = c.h->out; a.seq = c.h->seq; a.flagValue = tag; a.outBase = 0;
+  if (_optTimeSweeps) {
+    if (!c.evSel[0]) { HIP_TRY(hipEventCreate(&c.evSel[0])); HIP_TRY(hipEventCreate(&c.evSel[1])); }
+    HIP_TRY(hipEventRecord(c.evSel[0], _stream));
+  }
+  HIP_TRY(LaunchSelectSampledBatch(a, _stream));
+  if (_optTimeSweeps) HIP_TRY(hipEventRecord(c.evSel[1], _stream));
+  return Error();
+}
+
+Error HipEngine::NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) {
+  Error err = ValidateBatchLocked(n, pQuizzes);
+  if (!err.ok() || n == 0) return err;
+  if (!pRnd || !pOut) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  hipSetDevice(_device);
+  err = FlushUpdates();
+  if (!err.ok()) return err;
+  BatchCtx &c = _ctx[0];
+  const uint64_t tag = NextLaunchTag();
+  const int64_t nSub = _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;
+  std::vector<int64_t> picks((size_t)n, -1);
+  if (_optSampledBatchHost) {
+    // the A/B leg: the priorities to the host as a combined sweep delivers them, the host's selector per quiz (SelectFromPriorities)
+    while (c.readers.load(std::memory_order_acquire) != 0) _mm_pause();   // (clients of an earlier combined sweep still read hPri)
+    bool quizMinor = false, tagged = false;
+    err = BatchSweep(c, n, pQuizzes, _batchQuizzes, false, tag, true, &quizMinor, &tagged);
+    if (!err.ok()) return err;
+    HIP_TRY(hipStreamSynchronize(_stream));
+    err = WaitBatchFlags(c, n, tag);
+    if (!err.ok()) return err;
+    _hostRun.resize((size_t)_Q);
+    for (int64_t i = 0; i < n; i++) {
+      if (c.h->out[i].index == -3) return HipErr(hipErrorLaunchFailure, "sampled batch (incomplete sweep)");
+      const Quiz *q = _batchQuizzes[(size_t)i];
+      if (tagged) {
+        const volatile TaggedPriority *rec = reinterpret_cast<const TaggedPriority *>(c.hPri) + (size_t)i * (size_t)_Q;
+        SpinWait w;
+        for (int64_t k = 0; k < _Q; k++) {
+          if (BitTest(_hQGap, k) || BitTest(q->hAsked, k)) { _hostRun[(size_t)k] = 0.0; continue; }
+          while (rec[k].tag != tag)
+            if (!w.Tick(std::chrono::seconds(30))) return HipErr(hipErrorNotReady, "priority vector hand-over (sampled batch)");
+          std::atomic_thread_fence(std::memory_order_acquire);
+          _hostRun[(size_t)k] = rec[k].priority;
+        }
+      } else {
+        const double *pri = quizMinor ? c.hPri + i : c.hPri + (size_t)i * (size_t)_Q;
+        const size_t stride = quizMinor ? (size_t)c.lastBp : 1;
+        for (int64_t k = 0; k < _Q; k++) _hostRun[(size_t)k] = BitTest(_hQGap, k) || BitTest(q->hAsked, k) ? 0.0 : pri[(size_t)k * stride];
+      }
+      picks[(size_t)i] = SelectSampledHostBits(_hostRun.data(), _Q, nSub, pRnd[i], _hQGap.data(), q->hAsked.data());
+    }
+  } else {
+    err = BatchSweep(c, n, pQuizzes, _batchQuizzes, false, tag, false, nullptr, nullptr, true);
+    if (!err.ok()) return err;
+    err = LaunchSampledBatch(c, n, pRnd, tag);
+    if (!err.ok()) return err;
+    err = WaitBatchFlags(c, n, tag);
+    if (!err.ok()) return err;
+    for (int64_t i = 0; i < n; i++) {   // (the sweep published before the selector did)
+      if (c.h->sweepSeq[i] == tag && c.h->sweepOut[i].index == -3) return HipErr(hipErrorLaunchFailure, "sampled batch (incomplete sweep)");
+      CheckPriority(c.h->out[i].priority, c.h->out[i].index);
+      picks[(size_t)i] = c.h->out[i].index;
+    }
+    if (_optTimeSweeps && c.evSel[1]) {
+      float ms = 0;
+      if (hipEventSynchronize(c.evSel[1]) == hipSuccess && hipEventElapsedTime(&ms, c.evSel[0], c.evSel[1]) == hipSuccess) _sampledBatchDeviceNs += (uint64_t)(ms * 1e6);
+      else (void)hipGetLastError();
+    }
+  }
+  _sampledBatches++;
+  for (int64_t i = 0; i < n; i++) {
+    Error e;   // -1 + QuestionsExhausted: reported as -1 only
+    pOut[i] = FinishSelection(e, _batchQuizzes[(size_t)i], picks[(size_t)i]);
+  }
+  return Error();
+}
+
+Error HipEngine::NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) {
+  std::lock_guard<std::mutex> selLk(_ctx[0].mu);   // (this context's staging buffers: not while a leader's combined sweep uses them)
+  std::lock_guard<EngineMutex> lk(_mu);
+  return NextQuestionSampledBatchLocked(n, pQuizzes, pRnd, pOut);
+}
+
+// What a server calls: by option "select".  select = 0: one number per quiz from the engine's generator, in batch order, as
+// nQuizzes consecutive NextQuestion calls would draw them -- after the batch has been validated, so that a refused call draws nothing.
+Error HipEngine::NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) {
+  if (_optSelect == 1) return NextQuestionArgmaxBatch(n, pQuizzes, pOut);
+  std::lock_guard<std::mutex> selLk(_ctx[0].mu);
+  std::lock_guard<EngineMutex> lk(_mu);
+  Error err = ValidateBatchLocked(n, pQuizzes);
+  if (!err.ok() || n == 0) return err;
+  if (!pOut) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  std::vector<uint64_t> rnd((size_t)n);
+  {
+    std::lock_guard<std::mutex> rk(_rngMu);
+    for (int64_t i = 0; i < n; i++) rnd[(size_t)i] = NextRandom();
+  }
+  return NextQuestionSampledBatchLocked(n, pQuizzes, rnd.data(), pOut);
 }
 
 // The same selection replayed from a HIP graph (option "use_graph"; SURVEY 8(d) asks for the variant).  One graph per quiz:

@@ -308,6 +308,15 @@ __device__ __forceinline__ int64_t upper_bound_d(const double *a, int64_t n, dou
   }
   return lo;
 }
+// ... the same over a[0], a[stride], a[2 stride], ...: a quiz's column of a quiz-minor matrix (select_kernels.hip: the batched selector)
+__device__ __forceinline__ int64_t upper_bound_strided(const double *a, int64_t n, int64_t stride, double v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (!(v < a[mid * stride])) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
 // SRPoolRunner::CalcSplit bound i (reference: SRPlatform/Interface/SRPoolRunner.h:96-110) in closed form:
 // the first `rem` subtasks get quot+1 items.
 __device__ __forceinline__ int64_t calc_split_bound(int64_t i, int64_t quot, int64_t rem) {  // end of subtask i

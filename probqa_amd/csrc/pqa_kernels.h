@@ -306,6 +306,27 @@ hipError_t LaunchSelectArgmax(const double *priority, const uint32_t *qgap, cons
 hipError_t LaunchSelectSampled(const double *priority, const uint32_t *qgap, const uint32_t *asked, int64_t qFirst,
                                int64_t n, int64_t nSubtasks, uint64_t rnd, double *runLength, SelectResult *out,
                                uint64_t *flag, uint64_t flagValue, hipStream_t stream);
+// The same selection for every quiz of a batched sweep, behind it on its stream (NextQuestionSampledBatch): quiz b's priorities
+// are its own vector slots[b].priority (priorityT == nullptr; grid.y = quiz) or column b of the quiz-minor matrix
+// priorityT[q * Bp + b] (row-sharing and mid-batch sweeps; Bp a multiple of 64), its asked bits slots[b].asked, its random number
+// rnd[b].  Quiz b's {grand total, position + outBase} goes to out[b] and then flagValue to seq[b] (host-coherent, as rnd).
+// grand / run: device scratch of SelectSampledBatchScratch's sizes (a size of 0: not needed).
+constexpr size_t kSampledBatchLdsBytes = 160 * 1024;   // per-quiz vectors are staged in LDS up to this much (gfx950: 160 KiB per CU)
+struct SampledBatch {
+  const QuizSlot *slots;          // device array
+  int nSlots, Bp;
+  const double *priorityT;
+  const uint32_t *qgap;
+  int64_t n, nWorkers;            // questions; eval_subtasks
+  const uint64_t *rnd;
+  double *grand, *run;
+  SelectResult *out;
+  uint64_t *seq;
+  uint64_t flagValue;
+  int64_t outBase;
+};
+void SelectSampledBatchScratch(int64_t n, int64_t nSubtasks, int nSlots, int Bp, size_t *grandDoubles, size_t *runDoubles);
+hipError_t LaunchSelectSampledBatch(const SampledBatch &a, hipStream_t stream);
 
 // ---- prior updates (single workgroup, O(T)); nWorkers = emulated CPU worker count that fixes the summation order.
 // The subtasks' partial sums live in (8 nWorkers + 1) doubles of LDS, within the 64 KiB a launch gets without opting in.

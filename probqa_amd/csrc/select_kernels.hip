@@ -104,6 +104,115 @@ __global__ __launch_bounds__(256) void select_sampled_lds_kernel(const double *_
   }
 }
 
+// ---- the reference's selector for every quiz of a batched sweep (NextQuestionSampledBatch) --------------------------------------
+// The priorities are read where the batched sweep (and the pole fix behind it) left them.  Per-quiz vectors (grid.y = quiz): one
+// workgroup per quiz runs the single-quiz selector's own workgroup code, staged in LDS while it fits, with run lengths in global
+// scratch beyond that.
+template <bool LDS>
+__global__ __launch_bounds__(256) void select_sampled_batch_vec_kernel(SampledBatch a) {
+  extern __shared__ double lds[];   // LDS: the whole staging; else the subtasks' totals
+  const int b = blockIdx.x;
+  const QuizSlot s = a.slots[b];
+  const uint64_t rnd = a.rnd[b];
+  SampledPick r;
+  if constexpr (LDS) r = select_sampled_wg_lds<false>(s.priority, a.qgap, s.asked, 0, a.n, a.nWorkers, rnd, lds);
+  else r = select_sampled_wg_impl<false>(s.priority, a.qgap, s.asked, 0, a.n, a.nWorkers, rnd, a.run + (size_t)b * (size_t)a.n, lds);
+  if (threadIdx.x == 0) {
+    a.out[b].priority = r.priority;
+    a.out[b].index = r.index + a.outBase;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __hip_atomic_store(a.seq + b, a.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// The quiz-minor matrix priorityT[q * Bp + b] (row-sharing and mid-batch sweeps): the lane is the quiz.  A thread runs ONE subtask's
+// Kahan chain (PqaCore/CEEvalQsSubtaskConsider.cpp:52-58, :212-214) of ONE quiz over consecutive questions; the 64 lanes of a wave
+// are 64 adjacent quizzes on the same subtask, so every load instruction covers 64 adjacent doubles of a matrix row.  The eight
+// loads of a round are issued before the chain consumes them.  STORE: the running sums go to run[(i - first) * stride + b].
+template <bool STORE>
+__device__ __forceinline__ double sampled_lane_chain(const double *__restrict__ col, int64_t stride, const uint32_t *__restrict__ qgap,
+                                                     const uint32_t *__restrict__ asked, int64_t first, int64_t limit, double *run) {
+  Kahan1 acc;
+  acc.init(0.0);
+  int64_t word = -1;
+  uint32_t bits = 0;
+  for (int64_t i0 = first; i0 < limit; i0 += 8) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = i0 + u < limit ? col[(i0 + u) * stride] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const int64_t i = i0 + u;
+      if (i < limit) {
+        if ((i >> 5) != word) { word = i >> 5; bits = qgap[word] | asked[word]; }
+        if (!((bits >> (i & 31)) & 1u)) acc.add(v[u]);   // gap / asked questions only copy the running sum (:54-58)
+        if constexpr (STORE) run[(i - first) * stride] = acc.get();
+      }
+    }
+  }
+  return acc.get();
+}
+
+// grand[s * Bp + b] = total of subtask s for quiz b
+__global__ __launch_bounds__(256) void select_sampled_lanes_kernel(SampledBatch a) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = (int)(g % a.Bp);
+  const int64_t s = g / a.Bp;
+  const int64_t quot = a.n / a.nWorkers, rem = a.n % a.nWorkers;
+  const int64_t nSubtasks = (quot == 0) ? rem : a.nWorkers;  // CalcSplit stops once the items run out
+  if (s >= nSubtasks || b >= a.nSlots) return;
+  const int64_t first = (s == 0) ? 0 : calc_split_bound(s - 1, quot, rem), limit = calc_split_bound(s, quot, rem);
+  a.grand[s * a.Bp + b] = sampled_lane_chain<false>(a.priorityT + b, a.Bp, a.qgap, a.slots[b].asked, first, limit, nullptr);
+}
+
+// ... and the finish, a lane per quiz: Kahan grand totals in subtask order (PqaCore/CpuEngine.cpp:362-368), the uniform number, the
+// upper_bound over the totals, then the chosen subtask's chain once more -- the same operations on the same values, so the same
+// bits -- with its running sums STORED (run[j * Bp + b]) and the second upper_bound over them as stored values.
+__global__ __launch_bounds__(64) void select_sampled_lanes_finish_kernel(SampledBatch a) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b >= a.nSlots) return;
+  const int64_t Bp = a.Bp, n = a.n;
+  const int64_t quot = n / a.nWorkers, rem = n % a.nWorkers;
+  const int64_t nSubtasks = (quot == 0) ? rem : a.nWorkers;
+  double *grand = a.grand + b;
+  Kahan1 accTotG;
+  accTotG.init(0.0);                                           // :362
+  for (int64_t s0 = 0; s0 < nSubtasks; s0 += 16) {             // (16 loads together, as select_sampled_wg_impl)
+    double g[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) g[u] = s0 + u < nSubtasks ? grand[(s0 + u) * Bp] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 16; u++) {
+      if (s0 + u < nSubtasks) {
+        accTotG.add(g[u]);                                     // :366-367
+        g[u] = accTotG.get();                                  // :368
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 16; u++)
+      if (s0 + u < nSubtasks) grand[(s0 + u) * Bp] = g[u];
+  }
+  const double totG = grand[(nSubtasks - 1) * Bp];             // :375
+  const double selRunLen = totG * (double)a.rnd[b] / 18446744073709551615.0;  // :379, SRDoubleNumber::MakeRandom
+  int64_t sel;
+  const int64_t iWorker = upper_bound_strided(grand, nSubtasks, Bp, selRunLen);   // :380-381
+  if (iWorker >= nSubtasks) {
+    sel = n - 1;                                               // :384
+  } else {
+    const double inWorkerRunLen = selRunLen - ((iWorker == 0) ? 0.0 : grand[(iWorker - 1) * Bp]);  // :388
+    const int64_t first = (iWorker == 0) ? 0 : calc_split_bound(iWorker - 1, quot, rem);           // :389
+    const int64_t limit = calc_split_bound(iWorker, quot, rem);                                     // :390
+    double *run = a.run + b;
+    sampled_lane_chain<true>(a.priorityT + b, Bp, a.qgap, a.slots[b].asked, first, limit, run);
+    sel = first + upper_bound_strided(run, limit - first, Bp, inWorkerRunLen);                      // :391
+    if (sel >= limit) sel = limit - 1;                         // :392-400
+  }
+  a.out[b].priority = totG;
+  a.out[b].index = sel + a.outBase;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __hip_atomic_store(a.seq + b, a.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 }  // namespace
 
 hipError_t LaunchSelectArgmax(const double *priority, const uint32_t *qgap, const uint32_t *asked, int64_t qFirst,
@@ -129,6 +238,49 @@ hipError_t LaunchSelectSampled(const double *priority, const uint32_t *qgap, con
   if (shmem > 64 * 1024) return hipErrorInvalidValue;
   hipLaunchKernelGGL(select_sampled_kernel, dim3(1), dim3(1024), shmem, stream, priority, qgap, asked, qFirst, n, nSubtasks,
                      rnd, runLength, out, flag, flagValue);
+  return hipGetLastError();
+}
+
+void SelectSampledBatchScratch(int64_t n, int64_t nSubtasks, int nSlots, int Bp, size_t *grandDoubles, size_t *runDoubles) {
+  const int64_t quot = n / nSubtasks, rem = n % nSubtasks, subtasks = quot == 0 ? rem : nSubtasks;
+  if (Bp > 0) {   // the matrix: the subtasks' totals and one subtask's running sums, quiz-minor both
+    *grandDoubles = (size_t)subtasks * (size_t)Bp;
+    *runDoubles = (size_t)(quot + 1) * (size_t)Bp;
+    return;
+  }
+  *grandDoubles = 0;   // (LDS)
+  *runDoubles = (size_t)select_sampled_lds_doubles(n, nSubtasks) * sizeof(double) <= kSampledBatchLdsBytes ? 0 : (size_t)nSlots * (size_t)n;
+}
+
+hipError_t LaunchSelectSampledBatch(const SampledBatch &a, hipStream_t stream) {
+  if (a.n <= 0 || a.nWorkers <= 0 || a.nSlots <= 0 || a.nSlots > 256 || !a.slots || !a.rnd || !a.out || !a.seq) return hipErrorInvalidValue;
+  if (a.priorityT != nullptr) {
+    if (a.Bp < a.nSlots || a.Bp % kWave != 0 || !a.grand || !a.run) return hipErrorInvalidValue;
+    const int64_t quot = a.n / a.nWorkers, rem = a.n % a.nWorkers, nSubtasks = quot == 0 ? rem : a.nWorkers;
+    const int64_t threads = nSubtasks * a.Bp;
+    hipLaunchKernelGGL(select_sampled_lanes_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(select_sampled_lanes_finish_kernel, dim3((unsigned)((a.nSlots + kWave - 1) / kWave)), dim3(kWave), 0, stream, a);
+    return hipGetLastError();
+  }
+  const size_t staged = (size_t)select_sampled_lds_doubles(a.n, a.nWorkers) * sizeof(double);
+  if (staged <= kSampledBatchLdsBytes) {
+    static LaunchCache cache;   // (per device)
+    const int devSlot = LaunchCache::Device();
+    int attrSet = 0;
+    if (staged > 64 * 1024 && !cache.Get(devSlot, 1, &attrSet)) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(select_sampled_batch_vec_kernel<true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSampledBatchLdsBytes);
+      if (e != hipSuccess) return e;
+      cache.Put(devSlot, 1, 1);
+    }
+    hipLaunchKernelGGL(select_sampled_batch_vec_kernel<true>, dim3((unsigned)a.nSlots), dim3(256), staged, stream, a);
+    return hipGetLastError();
+  }
+  const size_t shmem = (size_t)a.nWorkers * sizeof(double);
+  if (shmem > 64 * 1024 || !a.run) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(select_sampled_batch_vec_kernel<false>, dim3((unsigned)a.nSlots), dim3(256), shmem, stream, a);
   return hipGetLastError();
 }
 

@@ -192,6 +192,9 @@ class ShardedEngine final : public IEngine {
     return _sh[0]->GetPriors(iQuiz, pOut, n);
   }
   Error NextQuestionArgmaxBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) override;
+  Error NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) override;
+  Error NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) override;
+  Error ValidateSelectionBatch(int64_t n, const int64_t *pQuizzes);
   Error EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) override;
   Error SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHipSelection *pOut) override;
   Error Log2HotArray(const double *pIn, double *pOut, int64_t n) override { return _sh[0]->Log2HotArray(pIn, pOut, n); }
@@ -1345,6 +1348,66 @@ Error ShardedEngine::NextQuestionArgmaxBatch(int64_t n, const int64_t *pQuizzes,
     pOut[i] = Commit(ce, pQuizzes[i], best[(size_t)i]._iQuestion);   // -1 + QuestionsExhausted: reported as -1 only
   }
   return Error();
+}
+
+// NextQuestionSampledBatch: the subtask split of the reference's selector runs over the GLOBAL question axis, so no shard can select
+// by itself.  One batched sweep per shard (all in flight together), the priority vectors gathered on the host, then per quiz what
+// SelectSampledLocked does: SelectSampledHost over the global vector, the nearest free question for a pick that is asked or a gap,
+// the active question set.  Every shard validates the batch before anything is launched or changed.
+Error ShardedEngine::ValidateSelectionBatch(int64_t n, const int64_t *pQuizzes) {
+  if (n < 0 || n > 256) return Error::MakeP(ErrCode::IndexOutOfRange, "n=" + std::to_string(n), "Batch size is out of range.");
+  if (n == 0) return Error();
+  if (!pQuizzes) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  for (auto &s : _sh) { Error e = s->ValidateBatch(n, pQuizzes); if (!e.ok()) return e; }
+  for (int64_t i = 0; i < n; i++) { Error e = FailedQuiz(pQuizzes[i]); if (!e.ok()) return e; }
+  return Error();
+}
+
+Error ShardedEngine::NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) {
+  Error e = ValidateSelectionBatch(n, pQuizzes);
+  if (!e.ok() || n == 0) return e;
+  if (!pRnd || !pOut) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  std::vector<double> pri((size_t)n * (size_t)_Q);
+  e = EvalPrioritiesBatch(n, pQuizzes, pri.data());   // (flushes the gathered answers, touches the quizzes)
+  if (!e.ok()) return e;
+  std::lock_guard<OpLock> lk(_opMu);
+  const int64_t nSub = _sh[0]->GetOption("eval_subtasks");
+  std::vector<uint64_t> skip((size_t)((_Q + 63) / 64) + 1);
+  std::vector<uint32_t> words;
+  std::vector<int64_t> picks((size_t)n, -1);
+  for (int64_t i = 0; i < n; i++) {
+    // which questions are asked or gaps, in global numbering (the shards' ranges are not multiples of 32)
+    std::fill(skip.begin(), skip.end(), 0);
+    for (auto &s : _sh) {
+      e = s->UnavailableWords(pQuizzes[i], words);
+      if (!e.ok()) return e;   // (nothing has changed yet)
+      for (int64_t k = 0; k < s->LocalQuestions(); k++)
+        if ((words[(size_t)(k >> 5)] >> (k & 31)) & 1u) skip[(size_t)((s->FirstQuestion() + k) >> 6)] |= 1ULL << ((s->FirstQuestion() + k) & 63);
+    }
+    for (int64_t q = _Q; q < (int64_t)skip.size() * 64; q++) skip[(size_t)(q >> 6)] |= 1ULL << (q & 63);
+    auto skipped = [&](int64_t q) { return ((skip[(size_t)(q >> 6)] >> (q & 63)) & 1ULL) != 0; };
+    int64_t sel = SelectSampledHost(pri.data() + (size_t)i * (size_t)_Q, _Q, nSub, pRnd[i], skipped);
+    if (skipped(sel)) sel = FindNearestInPacks(sel, _Q, [&](int64_t p) { return ~skip[(size_t)p]; });   // :403-407
+    picks[(size_t)i] = sel;
+  }
+  for (int64_t i = 0; i < n; i++) {
+    Error ce;
+    pOut[i] = Commit(ce, pQuizzes[i], picks[(size_t)i]);   // -1 + QuestionsExhausted: reported as -1 only
+  }
+  return Error();
+}
+
+Error ShardedEngine::NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) {
+  if (_select == 1) return NextQuestionArgmaxBatch(n, pQuizzes, pOut);
+  Error e = ValidateSelectionBatch(n, pQuizzes);   // (a refused call draws nothing)
+  if (!e.ok() || n == 0) return e;
+  if (!pOut) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  std::vector<uint64_t> rnd((size_t)n);
+  {
+    std::lock_guard<std::mutex> lk(_rngMu);   // one number per quiz in batch order, as consecutive NextQuestion calls draw them
+    for (int64_t i = 0; i < n; i++) rnd[(size_t)i] = NextRandom();
+  }
+  return NextQuestionSampledBatch(n, pQuizzes, rnd.data(), pOut);
 }
 
 Error ShardedEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) {

@@ -63,6 +63,7 @@ class CiHipSelection(ctypes.Structure):
 _vp, _i64, _u64, _u8, _dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_double
 _pvp = ctypes.POINTER(ctypes.c_void_p)
 _pi64 = ctypes.POINTER(ctypes.c_int64)
+_pu64 = ctypes.POINTER(ctypes.c_uint64)
 _pdbl = ctypes.POINTER(ctypes.c_double)
 _pAQ = ctypes.POINTER(CiAnsweredQuestion)
 
@@ -129,6 +130,8 @@ HIP_EXPORTS = {
     "PqaEngine_EvalPrioritiesBatch": (_vp, [_vp, _i64, _pi64, _pdbl]),
     "PqaHip_SelectArgmaxBatch": (_vp, [_vp, _i64, _pi64, ctypes.POINTER(CiHipSelection)]),
     "PqaEngine_NextQuestionArgmaxBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
+    "PqaEngine_NextQuestionSampledBatch": (_vp, [_vp, _i64, _pi64, _pu64, _pi64]),
+    "PqaEngine_NextQuestionBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_NextQuestionSampled": (_i64, [_vp, _pvp, _i64, _u64]),
     "PqaHip_GetPriors": (_vp, [_vp, _i64, _pdbl, _i64]),
     "PqaHip_GetStream": (_vp, [_vp]),
@@ -593,6 +596,27 @@ class PqaEngine:
         qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_NextQuestionArgmaxBatch(self.c_engine, n, qs, out))
+        return list(out[:n])
+
+    def next_question_sampled_batch(self, quizzes, rnds) -> List[int]:
+        """The reference's selector for several distinct quizzes with one sweep and one selector launch: entry i is what
+        next_question_sampled(quizzes[i], rnds[i]) selects; -1 for a quiz that has run out of questions."""
+        n = len(quizzes)
+        if len(rnds) != n:
+            raise ValueError("one random number per quiz")
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        rs = (ctypes.c_uint64 * max(n, 1))(*[int(r) for r in rnds])
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_NextQuestionSampledBatch(self.c_engine, n, qs, rs, out))
+        return list(out[:n])
+
+    def next_question_batch(self, quizzes) -> List[int]:
+        """NextQuestion of several distinct quizzes in one call, by the engine's `select` option: the argmax batch, or the sampled
+        batch with random numbers drawn from the engine's generator in batch order."""
+        n = len(quizzes)
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_NextQuestionBatch(self.c_engine, n, qs, out))
         return list(out[:n])
 
     def select_argmax_batch(self, quizzes) -> np.ndarray:

@@ -1,0 +1,67 @@
+"""No-GPU checks that PqaEngine_NextQuestionSampledBatch and PqaEngine_NextQuestionBatch are part of the boundary: declared in
+include/PqaHipExt.h, bound in probqa_amd/interop.py with their Python methods, and exported by the built libPqaCore.so.  Also
+without a GPU: the plain-Python selector of the GPU tests agrees with the oracle, and every seeded draw of those tests keeps its
+distance from the run-length boundaries (from the oracle's run lengths alone)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+import sampled_batch_common as sb
+from probqa_amd import interop
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"PqaEngine_NextQuestionSampledBatch": 5, "PqaEngine_NextQuestionBatch": 4}
+
+
+@pytest.mark.parametrize("name", sorted(NAMES))
+def test_header_declares_sampled_batch(name):
+    text = open(os.path.join(ROOT, "include", "PqaHipExt.h")).read()
+    m = re.search(r"PQACORE_API\s+void\s*\*\s*" + name + r"\s*\(([^)]*)\)", text)
+    assert m, "PqaHipExt.h does not declare " + name
+    args = [a.strip() for a in m.group(1).split(",")]
+    assert len(args) == NAMES[name], args
+    assert "int64_t *pQuestions" in args[-1] and "const" not in args[-1], args
+    if name == "PqaEngine_NextQuestionSampledBatch":
+        assert "const uint64_t" in args[3], args
+
+
+@pytest.mark.parametrize("name", sorted(NAMES))
+def test_binding_carries_sampled_batch(name):
+    assert name in interop.HIP_EXPORTS
+    _, argtypes = interop.HIP_EXPORTS[name]
+    assert len(argtypes) == NAMES[name]
+
+
+def test_python_methods_present():
+    for m in ("next_question_sampled_batch", "next_question_batch"):
+        assert callable(getattr(interop.PqaEngine, m, None)), m
+
+
+def test_library_exports_sampled_batch(factory):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
+    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    for name in NAMES:
+        assert name in exported
+        assert getattr(interop.load_library(), name) is not None
+
+
+@pytest.mark.parametrize("case", sb.scenarios(), ids=lambda c: c.name)
+def test_seeded_draws_clear_the_boundaries_and_python_selector_is_the_oracles(case, oracle_lib):
+    steps = sb.oracle_steps(case)
+    orc = case.make_oracle()
+    orc.start_quiz(16)
+    for i, (run, picks) in enumerate(steps):
+        _, pri = orc.eval(sb.SUBTASKS)
+        skip = [False] * case.Q
+        for q in case.qgaps + [q for q, _ in case.answers[:i]]:
+            skip[q] = True
+        for rnds, guarded in sb.batches(case):
+            if guarded:
+                assert sb.boundary_distance(run, sb.SUBTASKS, rnds[i]) > sb.GUARD, (case.name, i, rnds[i])
+            pick = sb.select_py(pri, skip, sb.SUBTASKS, rnds[i])
+            if not skip[pick]:   # (else the reference falls to the nearest free question: the oracle's find_nearest)
+                assert pick == picks[rnds[i]], (case.name, i, rnds[i])
+        if i < len(case.answers):
+            orc.record_answer(*case.answers[i], 15)
