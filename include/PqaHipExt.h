@@ -237,6 +237,15 @@ PQACORE_API void *PqaHip_RecordAnswerRemote(void *pvEngine, const int64_t iQuiz,
    operation into pOut (ids, or 0 / 1 for the boolean ones).
    what = "let_go": pIn = {now, maxCount, maxAgeSec, n, then n x {quiz id, last usage}}; pOut receives the count and then the ids
    ClearOldQuizzes would release, in release order (reference behaviour: PqaCore/BaseEngine.cpp:814-873).
+   The maintenance plans and the shards' pick both engines share (lists travel as {n, then n words}, doubles as their bit patterns):
+   what = "add_plan": pIn = {Q, T, question gaps, target gaps, the questions' init amounts, the targets'}; pOut = {gaps reused for
+   questions, for targets, new Q, new T, question ids, target ids, question amounts, target amounts} (PqaCore/CpuEngine.cpp:468-575).
+   what = "compact_plan": pIn = {Q, T, question gaps, target gaps}; pOut = {old question of every new one, old target of every new
+   one, the question moves as dst, src pairs in the order they are made} (PqaCore/CpuEngine.cpp:577-658).
+   what = "check_removal": pIn = {limit, gaps, ids to remove}; pOut = {position of the first id that is out of range, a gap or
+   repeated, or -1; the error code the call returns}.
+   what = "better_pick": pIn = {priority, index} per shard; pOut = {priority, index} of the winner (maximum priority, lowest index
+   on ties, a NaN counts as -infinity, a negative index is no candidate; {0, -1} if there is none).
    Returns the number of results written, or -1 for a malformed script / too small an output. */
 PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut);
 

@@ -507,6 +507,19 @@ PQACORE_API void *PqaHip_HostUnregister(void *pHost) {
   if (pHost) hipHostUnregister(pHost);
   return nullptr;
 }
+// The winner (kb_plan.h: BestPick) among `world` records {double priority; int64 index} that lie strideBytes apart.
+static void PickOfRecords(const char *base, int64_t world, int64_t strideBytes, double *pPriority, int64_t *pIndex) {
+  pqa::BestPick best;
+  for (int64_t r = 0; r < world; r++) {
+    double p;
+    int64_t i;
+    std::memcpy(&p, base + r * strideBytes, 8);
+    std::memcpy(&i, base + r * strideBytes + 8, 8);
+    best.Offer(p, i);
+  }
+  *pPriority = best.priority;
+  *pIndex = best.index;
+}
 // Host-side half of the shared-memory exchange: spin until the flags of all `world` slots equal flagValue, then pick the
 // winner (maximum priority, lowest index on ties, NaN never wins, -1 if no slot has an eligible question).  A slot is
 // strideBytes long and starts with {double priority; int64 index; uint64 flag}.  Returns an error after timeoutSec.
@@ -533,19 +546,7 @@ PQACORE_API void *PqaHip_PickWhenAll(const void *pSlots, const int64_t world, co
     }
   }
   std::atomic_thread_fence(std::memory_order_acquire);
-  double bestP = 0;
-  int64_t bestI = -1;
-  for (int64_t r = 0; r < world; r++) {
-    double p;
-    int64_t i;
-    std::memcpy(&p, base + r * strideBytes, 8);
-    std::memcpy(&i, base + r * strideBytes + 8, 8);
-    if (i < 0) continue;
-    if (p != p) p = -HUGE_VAL;
-    if (bestI < 0 || p > bestP || (p == bestP && i < bestI)) { bestP = p; bestI = i; }
-  }
-  *pPriority = bestP;
-  *pIndex = bestI;
+  PickOfRecords(base, world, strideBytes, pPriority, pIndex);
   return nullptr;
 }
 // One step of the shared-memory exchange in one call: enqueue this shard's selection with its record and flag in slot `rank`
@@ -644,19 +645,7 @@ PQACORE_API void *PqaHip_SelectArgmaxRccl(void *pvEngine, const int64_t iQuiz, v
   hipError_t he = hipMemcpyAsync(b.hRecv, b.dRecv, (size_t)world * 16, hipMemcpyDeviceToHost, stream);
   if (he == hipSuccess) he = hipStreamSynchronize(stream);
   if (he != hipSuccess) return ReturnErr(Error::MakeP(ErrCode::StdException, hipGetErrorString(he), "PqaHip_SelectArgmaxRccl: the gathered winners did not arrive."));
-  double bestP = 0;
-  int64_t bestI = -1;
-  for (int64_t r = 0; r < world; r++) {   // (as PqaHip_PickWhenAll: max priority, lowest index on ties, NaN never wins, -1 if none)
-    double p;
-    int64_t i;
-    std::memcpy(&p, static_cast<const char *>(b.hRecv) + r * 16, 8);
-    std::memcpy(&i, static_cast<const char *>(b.hRecv) + r * 16 + 8, 8);
-    if (i < 0) continue;
-    if (p != p) p = -HUGE_VAL;
-    if (bestI < 0 || p > bestP || (p == bestP && i < bestI)) { bestP = p; bestI = i; }
-  }
-  *pPriority = bestP;
-  *pIndex = bestI;
+  PickOfRecords(static_cast<const char *>(b.hRecv), world, 16, pPriority, pIndex);
   return nullptr;
 }
 static void ReleaseEngineSideTables(void *pvEngine) { ReleaseRcclBufs(pvEngine); }
@@ -726,6 +715,61 @@ PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, 
     pOut[0] = (int64_t)ids.size();
     for (size_t k = 0; k < ids.size(); k++) pOut[1 + k] = ids[k];
     return (int64_t)ids.size() + 1;
+  }
+  // The maintenance plans and the shards' pick (kb_plan.h).  Lists travel as {n, then n words}; doubles as their bit patterns.
+  int64_t at = 0, nRes = 0;
+  auto list = [&](std::vector<int64_t> &v) {
+    if (at >= nIn || pIn[at] < 0 || at + 1 + pIn[at] > nIn) return false;
+    v.assign(pIn + at + 1, pIn + at + 1 + pIn[at]);
+    at += 1 + pIn[at];
+    return true;
+  };
+  auto gapList = [&](std::vector<int64_t> &v, int64_t limit) {   // ... within the dimension, each id once: what an engine's list is
+    if (!list(v)) return false;
+    std::vector<char> seen((size_t)std::max<int64_t>(limit, 0), 0);
+    for (int64_t g : v) { if (g < 0 || g >= limit || seen[(size_t)g]) return false; seen[(size_t)g] = 1; }
+    return true;
+  };
+  auto put = [&](const std::vector<int64_t> &v) {
+    if (nRes + 1 + (int64_t)v.size() > nOut) return false;
+    pOut[nRes++] = (int64_t)v.size();
+    nRes = std::copy(v.begin(), v.end(), pOut + nRes) - pOut;
+    return true;
+  };
+  std::vector<int64_t> qGaps, tGaps, qWords, tWords;
+  if (w == "add_plan" || w == "compact_plan") {
+    at = 2;
+    if (nIn < 2 || !gapList(qGaps, pIn[0]) || !gapList(tGaps, pIn[1])) return -1;
+    if (w == "compact_plan") {
+      const pqa::CompactPlan plan = pqa::PlanCompact(qGaps, tGaps, pIn[0], pIn[1]);
+      for (const auto &mv : plan.qMoves) { qWords.push_back(mv.first); qWords.push_back(mv.second); }
+      return at == nIn && put(plan.oldQ) && put(plan.oldT) && put(qWords) ? nRes : -1;
+    }
+    if (!list(qWords) || !list(tWords) || at != nIn || nOut < 4) return -1;
+    std::vector<CiAddQorTParam> aq(qWords.size()), atp(tWords.size());
+    for (size_t i = 0; i < aq.size(); i++) std::memcpy(&aq[i]._initAmount, &qWords[i], 8);
+    for (size_t i = 0; i < atp.size(); i++) std::memcpy(&atp[i]._initAmount, &tWords[i], 8);
+    const pqa::AddPlan plan = pqa::PlanAdd(qGaps, tGaps, pIn[0], pIn[1], (int64_t)aq.size(), aq.data(), (int64_t)atp.size(), atp.data());
+    if (!qWords.empty()) std::memcpy(qWords.data(), plan.qInit.data(), 8 * qWords.size());
+    if (!tWords.empty()) std::memcpy(tWords.data(), plan.tInit.data(), 8 * tWords.size());
+    pOut[0] = plan.nQReuse; pOut[1] = plan.nTReuse; pOut[2] = plan.newQ; pOut[3] = plan.newT;
+    nRes = 4;
+    return put(plan.qIds) && put(plan.tIds) && put(qWords) && put(tWords) ? nRes : -1;
+  }
+  if (w == "check_removal") {
+    at = 1;
+    if (nIn < 1 || !gapList(qGaps, pIn[0]) || !list(qWords) || at != nIn || nOut < 2) return -1;
+    auto isGap = [&](int64_t id) { return std::find(qGaps.begin(), qGaps.end(), id) != qGaps.end(); };
+    pOut[0] = pqa::FirstBadRemoval((int64_t)qWords.size(), qWords.data(), pIn[0], isGap);
+    pOut[1] = (int64_t)pqa::CheckRemoval((int64_t)qWords.size(), qWords.data(), pIn[0], isGap, "").code;
+    return 2;
+  }
+  if (w == "better_pick") {
+    if (nIn % 2 != 0 || nOut < 2) return -1;
+    double p;   // (the script is what the exchanges hold: records {priority, index})
+    PickOfRecords(reinterpret_cast<const char *>(pIn), nIn / 2, 16, &p, &pOut[1]);
+    std::memcpy(&pOut[0], &p, 8);
+    return 2;
   }
   return -1;
 }

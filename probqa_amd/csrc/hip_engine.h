@@ -25,6 +25,7 @@
 #include "../../include/PqaHipExt.h"
 #include "pqa_kernels.h"
 #include "combining.h"
+#include "kb_plan.h"
 
 namespace pqa {
 
@@ -102,6 +103,44 @@ class IdLedger {
 // ones in registry order, then by age, the longest-unused first, equal ages by registry order.
 struct QuizUsage { int64_t id; time_t lastUsage; };
 std::vector<int64_t> QuizzesToLetGo(const std::vector<QuizUsage> &quizzes, time_t now, int64_t maxCount, double maxAgeSec);
+
+// The frame of a .kb file around the arrays (layout: hip_engine_kb.cpp), one copy for the one-device and the sharded engine:
+// KbHeader in front of them -- the file's first 40 bytes as they are -- and behind them the gap lists (i64 n, n ids: questions,
+// targets) and PermanentIdManager x3 (questions, targets, quizzes saved empty).  KbFile closes what is still open when it goes.
+uint64_t PackPrecision(uint64_t type, uint64_t mantissa, uint64_t exponent);   // PrecisionDefinition (8 B)
+struct KbHeader {
+  uint64_t precision;
+  int64_t K, Q, T;             // EngineDimensions {nAnswers, nQuestions, nTargets}
+  uint64_t nAsked;
+  CiEngineDefinition Definition() const;   // (precision unpacked; _initAmount = 1: not stored, every count is read from the file)
+};
+Error FileErr(const char *path, const char *msg);   // FileOp, with the path
+struct KbFile {
+  FILE *f = nullptr;
+  const char *path;
+  Error opened;                // why there is no file: no name, or it cannot be opened -- what the header calls answer then
+  KbFile(const char *filePath, bool write);
+  ~KbFile() { if (f) std::fclose(f); }
+  Error WriteHeader(const KbHeader &h);
+  Error ReadHeader(KbHeader &h);
+  Error WriteTrailer(const std::vector<int64_t> &qGaps, const std::vector<int64_t> &tGaps, const IdLedger &questionIds,
+                     const IdLedger &targetIds, const IdLedger &quizIds);
+  Error ReadTrailer(int64_t Q, int64_t T, std::vector<int64_t> &qGaps, std::vector<int64_t> &tGaps, IdLedger &questionIds,
+                    IdLedger &targetIds, IdLedger &quizIds);   // every gap id checked against its dimension
+  Error FlushAndClose();
+};
+
+// What every maintenance-mode operation answers in another mode, and what a removal answers to bad arguments or to an id that is
+// out of range, a gap already, or repeated within the call (kb_plan.h: FirstBadRemoval) -- nothing has changed then.
+Error WrongModeErr(const char *what);
+Error CheckAddArgs(int64_t nQuestions, const CiAddQorTParam *pAqps, int64_t nTargets, const CiAddQorTParam *pAtps);   // AddQsTs: counts, arrays
+template <typename IsGap>
+Error CheckRemoval(int64_t n, const int64_t *ids, int64_t limit, IsGap isGap, const char *msg) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "Counts must be non-negative.");
+  if (n > 0 && !ids) return Error::Make(ErrCode::NullArgument, "Nullptr ids array.");
+  const int64_t bad = FirstBadRemoval(n, ids, limit, isGap);
+  return bad < 0 ? Error() : Error::MakeP(ErrCode::AbsentId, "id=" + std::to_string(ids[bad]), msg);
+}
 
 // A quiz's own lines of host-coherent pinned memory: what the kernels working for ONE quiz hand to the host without a copy --
 // the posterior's best targets (listed by RecordAnswer's kernel ahead of the ListTopTargets that follows it) and their flag.
@@ -393,6 +432,8 @@ class HipEngine : public IEngine {
   Error ValidateTrainLocked(int64_t nQuestions, const AQ *pAQs, int64_t iTarget) const;
   uint64_t NextRandom();
   Error UploadGaps();
+  Error RemoveIds(int64_t n, const int64_t *ids, int64_t limit, std::vector<uint32_t> &gapBits, std::vector<int64_t> &gapList, IdLedger &ledger,
+                  const char *absentMsg);   // RemoveQuestions / RemoveTargets: all ids validated, then flagged, listed and retired
   Error ReallocKB(int64_t newQ, int64_t newT);               // grow the device cube / vB / per-question buffers
   int64_t AssignQuiz(Quiz *q);                               // reference BaseEngine::AssignQuiz, BaseEngine.cpp:780-793
   void UnassignQuiz(int64_t iQuiz);

@@ -1,6 +1,6 @@
 // hip_engine_internal.h -- small helpers shared by the files that implement HipEngine (hip_engine.cpp: construction, options,
 // registry; hip_engine_select.cpp: the selection paths; hip_engine_combine.cpp: concurrent clients; hip_engine_update.cpp:
-// posterior updates, listings, training; hip_engine_shard.cpp: what a sharded engine asks of its shards).
+// posterior updates, listings, training; hip_engine_shard.cpp: what a sharded engine asks of its shards; hip_engine_kb.cpp: id maps, .kb files, maintenance).
 #pragma once
 
 #include <sched.h>
@@ -46,6 +46,13 @@ inline void BitSet(std::vector<uint32_t> &bits, int64_t i, bool v) {
 inline size_t BitWords(int64_t nBits) { return (size_t)((nBits + 63) / 64) * 2 + 2; }  // whole 64-bit packs + slack
 inline uint64_t Pack64(const std::vector<uint32_t> &bits, int64_t iPack) {
   return (uint64_t)bits[2 * iPack] | ((uint64_t)bits[2 * iPack + 1] << 32);
+}
+
+// An id table of Compact as the C ABI hands it out: the caller frees it (never of size zero)
+inline int64_t *MallocCopy(const std::vector<int64_t> &v) {
+  int64_t *p = (int64_t *)std::malloc(sizeof(int64_t) * std::max<size_t>(v.size(), 1));
+  std::copy(v.begin(), v.end(), p);
+  return p;
 }
 
 inline uint64_t SplitMix64(uint64_t &x) {

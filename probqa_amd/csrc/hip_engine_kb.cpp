@@ -3,50 +3,11 @@
 // Reference: PqaCore/PermanentIdManager.cpp, PqaCore/BaseEngine.cpp:124-215,323-385,704-873,
 // PqaCore/CpuEngine.cpp:468-658,664-688, PqaCore/PqaEngineBaseFactory.cpp:44-83.  Host bookkeeping is the reference's;
 // the cube itself stays on the device and is edited there (kb_kernels.hip).
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-
-#include "hip_engine.h"
+#include "hip_engine_internal.h"
 
 namespace pqa {
 
 namespace {
-
-Error HipErr(hipError_t e, const char *what) {
-  std::string msg = std::string("HIP failure in ") + what + ": " + hipGetErrorString(e);
-  return Error::MakeP(ErrCode::Internal, std::string("Internal error at hip_engine_kb.cpp(") + what + ")", msg);
-}
-#define HIP_TRY(expr)                                   \
-  do {                                                  \
-    const hipError_t e_ = (expr);                       \
-    if (e_ != hipSuccess) return HipErr(e_, #expr);     \
-  } while (0)
-
-inline bool BitTest(const std::vector<uint32_t> &bits, int64_t i) { return (bits[i >> 5] >> (i & 31)) & 1u; }
-inline void BitSet(std::vector<uint32_t> &bits, int64_t i, bool v) {
-  if (v) bits[i >> 5] |= 1u << (i & 31); else bits[i >> 5] &= ~(1u << (i & 31));
-}
-inline size_t BitWords(int64_t nBits) { return (size_t)((nBits + 63) / 64) * 2 + 2; }
-
-Error FileErr(const char *path, const char *msg) {
-  return Error::MakeP(ErrCode::FileOp, std::string("filePath=[") + path + "]", msg);
-}
-
-struct FileCloser {
-  FILE *f;
-  ~FileCloser() { if (f) std::fclose(f); }
-};
-
-Error WrongModeErr(const char *what) {
-  return Error::Make(ErrCode::WrongMode, std::string("Can't perform maintenance-only mode operation - ") + what +
-                                             " - because current mode is not maintenance (but regular/shutdown?).");
-}
-
-// PrecisionDefinition bitfield of reference PqaCore/Interface/PqaCommon.h:26-32 (type:4, mantissa:28, exponent:16, reserved:16)
-uint64_t PackPrecision(uint64_t type, uint64_t mantissa, uint64_t exponent) {
-  return (type & 0xF) | ((mantissa & 0xFFFFFFF) << 4) | ((exponent & 0xFFFF) << 32);
-}
 
 template <typename T>
 hipError_t Upload(T **dst, const std::vector<T> &src, hipStream_t stream) {
@@ -58,6 +19,10 @@ hipError_t Upload(T **dst, const std::vector<T> &src, hipStream_t stream) {
 }
 
 }  // namespace
+
+Error FileErr(const char *path, const char *msg) {
+  return Error::MakeP(ErrCode::FileOp, std::string("filePath=[") + path + "]", msg);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // IdLedger: compact slot <-> permanent id (hip_engine.h).  What callers and files observe follows the reference's
@@ -381,91 +346,128 @@ Error HipEngine::SetVBFromHost(const double *vb) {
 //   sA rows [q][a] of nTargets doubles | mD rows [q] | vB | question gaps (i64 n, n ids) | target gaps |
 //   PermanentIdManager x3 (questions, targets, quizzes saved empty)
 // ------------------------------------------------------------------------------------------------------------------
-Error HipEngine::SaveKB(const char *filePath, bool doubleBuffer) {
-  (void)doubleBuffer;  // the device copy already is the "second buffer": the file is written from a host snapshot
-  if (!filePath) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name.");
-  std::lock_guard<EngineMutex> lk(_mu);
-  StopServer();
-  if (_qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=SaveKB of a sharded engine", "Save the shards' owner instead.");
-  FileCloser fc{std::fopen(filePath, "wb")};
-  if (!fc.f)
-    return Error::MakeP(ErrCode::CantOpenFile, std::string("filePath=[") + filePath + "]", "Can't open the file to write KB to.");
-  hipSetDevice(_device);
-  const uint64_t prec = PackPrecision(_precType, _precMantissa, _precExponent);   // Double | Float: the element type of the arrays below
-  const int64_t dims[3] = {_K, _Q, _T};
-  const uint64_t nAsked = _nQuestionsAsked.load(std::memory_order_acquire);
-  if (std::fwrite(&prec, 8, 1, fc.f) != 1) return FileErr(filePath, "Can't write precision definition header.");
-  if (std::fwrite(dims, sizeof(dims), 1, fc.f) != 1) return FileErr(filePath, "Can't write engine dimensions header.");
-  if (std::fwrite(&nAsked, 8, 1, fc.f) != 1) return FileErr(filePath, "Can't write the number of questions asked.");
-  Error e = IoRows(fc.f, filePath, false, true);      // sA rows [q][a]
-  if (e.ok()) e = IoRows(fc.f, filePath, true, true);  // mD rows [q]
-  if (e.ok()) e = IoVB(fc.f, filePath, true);
-  if (!e.ok()) return e;
-  auto writeGaps = [&](const std::vector<int64_t> &gaps) {
-    const int64_t n = (int64_t)gaps.size();
-    return std::fwrite(&n, 8, 1, fc.f) == 1 && std::fwrite(gaps.data(), 8, (size_t)n, fc.f) == (size_t)n;
-  };
-  if (!writeGaps(_questionGapList)) return FileErr(filePath, "Can't write the question gaps.");
-  if (!writeGaps(_targetGapList)) return FileErr(filePath, "Can't write the target gaps.");
-  if (!_questionIds.Write(fc.f)) return FileErr(filePath, "Can't write the question permanent-compact ID mappings.");
-  if (!_targetIds.Write(fc.f)) return FileErr(filePath, "Can't write the target permanent-compact ID mappings.");
-  if (!_quizIds.Write(fc.f, true)) return FileErr(filePath, "Can't write the quiz permanent-compact ID mappings.");
-  if (std::fflush(fc.f) != 0) return FileErr(filePath, "Failed in hard flushing the KB.");
-  FILE *f = fc.f;
-  fc.f = nullptr;
-  if (std::fclose(f) != 0) return FileErr(filePath, "Failed in closing the file.");
+// PrecisionDefinition bitfield of reference PqaCore/Interface/PqaCommon.h:26-32 (type:4, mantissa:28, exponent:16, reserved:16)
+uint64_t PackPrecision(uint64_t type, uint64_t mantissa, uint64_t exponent) {
+  return (type & 0xF) | ((mantissa & 0xFFFFFFF) << 4) | ((exponent & 0xFFFF) << 32);
+}
+CiEngineDefinition KbHeader::Definition() const {
+  CiEngineDefinition def;
+  std::memset(&def, 0, sizeof(def));
+  def._nAnswers = K; def._nQuestions = Q; def._nTargets = T;
+  def._precType = (uint8_t)(precision & 0xF);
+  def._precMantissa = (uint32_t)((precision >> 4) & 0xFFFFFFF);
+  def._precExponent = (uint16_t)((precision >> 32) & 0xFFFF);
+  def._initAmount = 1.0;
+  return def;
+}
+
+KbFile::KbFile(const char *filePath, bool write) : path(filePath) {
+  if (!path) opened = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name.");
+  else if (!(f = std::fopen(path, write ? "wb" : "rb")))
+    opened = Error::MakeP(ErrCode::CantOpenFile, std::string("filePath=[") + path + "]", write ? "Can't open the file to write KB to." : "Can't open the KB file to read.");
+}
+Error KbFile::WriteHeader(const KbHeader &h) {
+  if (!f) return opened;
+  if (std::fwrite(&h.precision, 8, 1, f) != 1) return FileErr(path, "Can't write precision definition header.");   // Double | Float: the element type of the arrays
+  if (std::fwrite(&h.K, 8, 3, f) != 3) return FileErr(path, "Can't write engine dimensions header.");
+  if (std::fwrite(&h.nAsked, 8, 1, f) != 1) return FileErr(path, "Can't write the number of questions asked.");
+  return Error();
+}
+Error KbFile::ReadHeader(KbHeader &h) {
+  if (!f) return opened;
+  if (std::fread(&h.precision, 8, 1, f) != 1) return FileErr(path, "Can't read precision definition header.");
+  if (std::fread(&h.K, 8, 3, f) != 3) return FileErr(path, "Can't read engine dimensions header.");
+  if (std::fread(&h.nAsked, 8, 1, f) != 1) return FileErr(path, "Can't read the number of questions asked.");
   return Error();
 }
 
+static bool WriteGaps(FILE *f, const std::vector<int64_t> &gaps) {   // (LIFO order, as the reference's GapTracker saves it)
+  const int64_t n = (int64_t)gaps.size();
+  return std::fwrite(&n, 8, 1, f) == 1 && std::fwrite(gaps.data(), 8, (size_t)n, f) == (size_t)n;
+}
+static bool ReadGaps(FILE *f, std::vector<int64_t> &gaps, int64_t limit) {
+  int64_t n;
+  if (std::fread(&n, 8, 1, f) != 1 || n < 0 || n > limit) return false;
+  gaps.resize((size_t)n);
+  if (std::fread(gaps.data(), 8, (size_t)n, f) != (size_t)n) return false;
+  for (int64_t g : gaps) if (g < 0 || g >= limit) return false;
+  return true;
+}
+
+// (the live quiz map is written without its slots and keeps its next permanent id, as BaseEngine.cpp:379 writes it)
+Error KbFile::WriteTrailer(const std::vector<int64_t> &qGaps, const std::vector<int64_t> &tGaps, const IdLedger &questionIds,
+                           const IdLedger &targetIds, const IdLedger &quizIds) {
+  if (!WriteGaps(f, qGaps)) return FileErr(path, "Can't write the question gaps.");
+  if (!WriteGaps(f, tGaps)) return FileErr(path, "Can't write the target gaps.");
+  if (!questionIds.Write(f)) return FileErr(path, "Can't write the question permanent-compact ID mappings.");
+  if (!targetIds.Write(f)) return FileErr(path, "Can't write the target permanent-compact ID mappings.");
+  if (!quizIds.Write(f, true)) return FileErr(path, "Can't write the quiz permanent-compact ID mappings.");
+  return Error();
+}
+Error KbFile::ReadTrailer(int64_t Q, int64_t T, std::vector<int64_t> &qGaps, std::vector<int64_t> &tGaps, IdLedger &questionIds,
+                          IdLedger &targetIds, IdLedger &quizIds) {
+  if (!ReadGaps(f, qGaps, Q)) return FileErr(path, "Can't read the question gaps.");
+  if (!ReadGaps(f, tGaps, T)) return FileErr(path, "Can't read the target gaps.");
+  if (!questionIds.Read(f)) return FileErr(path, "Can't read the question permanent-compact ID mapping.");
+  if (!targetIds.Read(f)) return FileErr(path, "Can't read the target permanent-compact ID mapping.");
+  if (!quizIds.Read(f)) return FileErr(path, "Can't read the quizzes permanent-compact ID mapping.");
+  return Error();
+}
+Error KbFile::FlushAndClose() {
+  if (std::fflush(f) != 0) return FileErr(path, "Failed in hard flushing the KB.");
+  FILE *open = f;
+  f = nullptr;
+  if (std::fclose(open) != 0) return FileErr(path, "Failed in closing the file.");
+  return Error();
+}
+
+Error HipEngine::SaveKB(const char *filePath, bool doubleBuffer) {
+  (void)doubleBuffer;  // the device copy already is the "second buffer": the file is written from a host snapshot
+  std::lock_guard<EngineMutex> lk(_mu);
+  StopServer();
+  if (_qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=SaveKB of a sharded engine", "Save the shards' owner instead.");
+  KbFile file(filePath, true);
+  hipSetDevice(_device);
+  Error e = file.WriteHeader(KbHeader{PackPrecision(_precType, _precMantissa, _precExponent), _K, _Q, _T, _nQuestionsAsked.load(std::memory_order_acquire)});
+  if (e.ok()) e = IoRows(file.f, filePath, false, true);   // sA rows [q][a]
+  if (e.ok()) e = IoRows(file.f, filePath, true, true);    // mD rows [q]
+  if (e.ok()) e = IoVB(file.f, filePath, true);
+  if (e.ok()) e = file.WriteTrailer(_questionGapList, _targetGapList, _questionIds, _targetIds, _quizIds);
+  return e.ok() ? file.FlushAndClose() : e;
+}
+
 HipEngine *HipEngine::Load(Error &err, const char *filePath) {  // PqaEngineBaseFactory.cpp:44-83, CpuEngine.cpp:41-92
-  if (!filePath) { err = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name."); return nullptr; }
-  FileCloser fc{std::fopen(filePath, "rb")};
-  if (!fc.f) {
-    err = Error::MakeP(ErrCode::CantOpenFile, std::string("filePath=[") + filePath + "]", "Can't open the KB file to read.");
-    return nullptr;
-  }
-  uint64_t prec = 0, nAsked = 0;
-  int64_t dims[3];
-  if (std::fread(&prec, 8, 1, fc.f) != 1) { err = FileErr(filePath, "Can't read precision definition header."); return nullptr; }
-  if (std::fread(dims, sizeof(dims), 1, fc.f) != 1) { err = FileErr(filePath, "Can't read engine dimensions header."); return nullptr; }
-  if (std::fread(&nAsked, 8, 1, fc.f) != 1) { err = FileErr(filePath, "Can't read the number of questions asked."); return nullptr; }
-  CiEngineDefinition def;
-  std::memset(&def, 0, sizeof(def));
-  def._nAnswers = dims[0]; def._nQuestions = dims[1]; def._nTargets = dims[2];
-  def._precType = (uint8_t)(prec & 0xF);
-  def._precMantissa = (uint32_t)((prec >> 4) & 0xFFFFFFF);
-  def._precExponent = (uint16_t)((prec >> 32) & 0xFFFF);
-  def._initAmount = 1.0;  // not stored in the file; every count is overwritten below
-  std::unique_ptr<HipEngine> eng(HipEngine::Create(err, def, nullptr));
+  KbFile file(filePath, false);
+  KbHeader h;
+  err = file.ReadHeader(h);
+  if (!err.ok()) return nullptr;
+  std::unique_ptr<HipEngine> eng(HipEngine::Create(err, h.Definition(), nullptr));
   if (!eng) return nullptr;
   HipEngine &e = *eng;
-  auto fail = [&](Error x) { err = std::move(x); return (HipEngine *)nullptr; };
   hipSetDevice(e._device);
-  Error ioErr = e.IoRows(fc.f, filePath, false, false);
-  if (ioErr.ok()) ioErr = e.IoRows(fc.f, filePath, true, false);
-  if (ioErr.ok()) ioErr = e.IoVB(fc.f, filePath, false);
-  if (!ioErr.ok()) return fail(std::move(ioErr));
-  e._nQuestionsAsked.store(nAsked);
-  auto readGaps = [&](std::vector<int64_t> &gaps, int64_t limit) {
-    int64_t n;
-    if (std::fread(&n, 8, 1, fc.f) != 1 || n < 0 || n > limit) return false;
-    gaps.resize((size_t)n);
-    if (std::fread(gaps.data(), 8, (size_t)n, fc.f) != (size_t)n) return false;
-    for (int64_t g : gaps) if (g < 0 || g >= limit) return false;
-    return true;
-  };
-  if (!readGaps(e._questionGapList, e._Q)) return fail(FileErr(filePath, "Can't read the question gaps."));
-  if (!readGaps(e._targetGapList, e._T)) return fail(FileErr(filePath, "Can't read the target gaps."));
+  err = e.IoRows(file.f, filePath, false, false);
+  if (err.ok()) err = e.IoRows(file.f, filePath, true, false);
+  if (err.ok()) err = e.IoVB(file.f, filePath, false);
+  if (!err.ok()) return nullptr;
+  e._nQuestionsAsked.store(h.nAsked);
+  err = file.ReadTrailer(e._Q, e._T, e._questionGapList, e._targetGapList, e._questionIds, e._targetIds, e._quizIds);
+  if (!err.ok()) return nullptr;
   for (int64_t g : e._questionGapList) BitSet(e._hQGap, g, true);
   for (int64_t g : e._targetGapList) BitSet(e._hTGap, g, true);
   e._nTargetGaps = (int64_t)e._targetGapList.size();
-  if (!e._questionIds.Read(fc.f)) return fail(FileErr(filePath, "Can't read the question permanent-compact ID mapping."));
-  if (!e._targetIds.Read(fc.f)) return fail(FileErr(filePath, "Can't read the target permanent-compact ID mapping."));
-  if (!e._quizIds.Read(fc.f)) return fail(FileErr(filePath, "Can't read the quizzes permanent-compact ID mapping."));
-  Error ue = e.UploadGaps();
-  if (!ue.ok()) return fail(std::move(ue));
-  err = Error();
-  return eng.release();
+  err = e.UploadGaps();
+  return err.ok() ? eng.release() : nullptr;
+}
+
+Error CheckAddArgs(int64_t nQuestions, const CiAddQorTParam *pAqps, int64_t nTargets, const CiAddQorTParam *pAtps) {
+  if (nQuestions < 0 || nTargets < 0)
+    return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(std::min(nQuestions, nTargets)), "Counts must be non-negative.");
+  if ((nQuestions > 0 && !pAqps) || (nTargets > 0 && !pAtps)) return Error::Make(ErrCode::NullArgument, "Nullptr parameters array.");
+  return Error();
+}
+Error WrongModeErr(const char *what) {
+  return Error::Make(ErrCode::WrongMode, std::string("Can't perform maintenance-only mode operation - ") + what +
+                                             " - because current mode is not maintenance (but regular/shutdown?).");
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -545,37 +547,27 @@ Error HipEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTar
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_mode != Mode::Maintenance) return WrongModeErr("add questions/targets");
-  if (nQuestions < 0 || nTargets < 0)
-    return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(std::min(nQuestions, nTargets)), "Counts must be non-negative.");
-  if ((nQuestions > 0 && !pAqps) || (nTargets > 0 && !pAtps)) return Error::Make(ErrCode::NullArgument, "Nullptr parameters array.");
+  Error ae = CheckAddArgs(nQuestions, pAqps, nTargets, pAtps);
+  if (!ae.ok()) return ae;
   if (_qFirst != 0 || _qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=AddQsTs on a shard", "Not on a sharded engine.");
   hipSetDevice(_device);
-  // CpuEngine::AddQsTsSpec, reference PqaCore/CpuEngine.cpp:468-575.  The ids are worked out first and committed -- gap
-  // lists, permanent ids, bitmaps, the caller's _index fields -- only after the resize and the fills have succeeded.
-  const int64_t nQReuse = std::min<int64_t>(nQuestions, (int64_t)_questionGapList.size()), nQNew = nQuestions - nQReuse;
-  const int64_t nTReuse = std::min<int64_t>(nTargets, (int64_t)_targetGapList.size()), nTNew = nTargets - nTReuse;
-  const int64_t nQOld = _Q, nTOld = _T;
-  std::vector<int64_t> qIds, tIds;
-  std::vector<double> qInit, tInit;
-  for (int64_t i = 0; i < nQReuse; i++) qIds.push_back(_questionGapList[_questionGapList.size() - 1 - (size_t)i]);   // :476-482 gaps are reused LIFO
-  for (int64_t i = 0; i < nTReuse; i++) tIds.push_back(_targetGapList[_targetGapList.size() - 1 - (size_t)i]);       // :488-493
-  for (int64_t i = 0; i < nQNew; i++) qIds.push_back(nQOld + i);   // :500
-  // NOTE reference :516,:523,:529 index the target parameters with nQReuse + j; the evident intent nTReuse + j is used
-  for (int64_t j = 0; j < nTNew; j++) tIds.push_back(nTOld + j);    // :531
-  for (int64_t i = 0; i < nQuestions; i++) qInit.push_back(pAqps[i]._initAmount);
-  for (int64_t j = 0; j < nTargets; j++) tInit.push_back(pAtps[j]._initAmount);
+  // CpuEngine::AddQsTsSpec, reference PqaCore/CpuEngine.cpp:468-575.  The ids are worked out first (kb_plan.h) and committed
+  // -- gap lists, permanent ids, bitmaps, the caller's _index fields -- only after the resize and the fills have succeeded.
+  const AddPlan plan = PlanAdd(_questionGapList, _targetGapList, _Q, _T, nQuestions, pAqps, nTargets, pAtps);
+  const std::vector<int64_t> &qIds = plan.qIds, &tIds = plan.tIds;
+  const int64_t nQReuse = plan.nQReuse, nTReuse = plan.nTReuse, nTNew = nTargets - nTReuse, nQOld = _Q;
   // whole questions first, then target columns over the questions not (re)initialised just now
-  std::vector<uint32_t> skip(BitWords(nQOld + nQNew), 0);
+  std::vector<uint32_t> skip(BitWords(plan.newQ), 0);
   for (int64_t i = 0; i < nQReuse; i++) BitSet(skip, qIds[(size_t)i], true);    // :558-560 only reused questions are skipped
   DevBuf<int64_t> dQ, dT;
   DevBuf<double> dQi, dTi;
   DevBuf<uint32_t> dSkip;
   HIP_TRY(Upload(&dQ.p, qIds, _stream));
-  HIP_TRY(Upload(&dQi.p, qInit, _stream));
+  HIP_TRY(Upload(&dQi.p, plan.qInit, _stream));
   HIP_TRY(Upload(&dT.p, tIds, _stream));
-  HIP_TRY(Upload(&dTi.p, tInit, _stream));
+  HIP_TRY(Upload(&dTi.p, plan.tInit, _stream));
   HIP_TRY(Upload(&dSkip.p, skip, _stream));
-  Error e = ReallocKB(nQOld + nQNew, nTOld + nTNew);   // all-or-nothing; the reused ids are still flagged as gaps
+  Error e = ReallocKB(plan.newQ, plan.newT);   // all-or-nothing; the reused ids are still flagged as gaps
   if (!e.ok()) return e;
   // new target columns apply to every old question (:512-527); reused target columns skip reused questions (:553-567).
   // New questions are filled over ALL columns with their own amount (:497-510), so they are filled last.
@@ -590,19 +582,11 @@ Error HipEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTar
     return HipErr(he, "AddQsTs");
   }
   // ---- commit
-  for (int64_t i = 0; i < nQReuse; i++) {
-    const int64_t curQ = qIds[(size_t)i];
-    _questionGapList.pop_back();
-    BitSet(_hQGap, curQ, false);
-    _questionIds.Reissue(curQ);
-  }
-  for (int64_t i = 0; i < nTReuse; i++) {
-    const int64_t curT = tIds[(size_t)i];
-    _targetGapList.pop_back();
-    BitSet(_hTGap, curT, false);
-    _nTargetGaps--;
-    _targetIds.Reissue(curT);
-  }
+  for (int64_t i = 0; i < nQReuse; i++) { BitSet(_hQGap, qIds[(size_t)i], false); _questionIds.Reissue(qIds[(size_t)i]); }
+  for (int64_t i = 0; i < nTReuse; i++) { BitSet(_hTGap, tIds[(size_t)i], false); _targetIds.Reissue(tIds[(size_t)i]); }
+  _questionGapList.resize(_questionGapList.size() - (size_t)nQReuse);   // (the reused ids were its last entries)
+  _targetGapList.resize(_targetGapList.size() - (size_t)nTReuse);
+  _nTargetGaps = (int64_t)_targetGapList.size();
   _questionIds.Extend(_Q);                           // :541-542
   _targetIds.Extend(_T);
   for (int64_t i = 0; i < nQuestions; i++) pAqps[i]._index = qIds[(size_t)i];
@@ -655,45 +639,27 @@ Error HipEngine::RemoveQuestions(int64_t n, const int64_t *pQIds) {  // BaseEngi
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_mode != Mode::Maintenance) return WrongModeErr("remove questions");
-  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "Counts must be non-negative.");
-  if (n > 0 && !pQIds) return Error::Make(ErrCode::NullArgument, "Nullptr ids array.");
   if (_qFirst != 0 || _qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=RemoveQuestions on a shard", "Not on a sharded engine.");
-  std::vector<uint32_t> seen(BitWords(_Q), 0);
-  for (int64_t i = 0; i < n; i++) {
-    const int64_t iq = pQIds[i];
-    if (iq < 0 || iq >= _Q || BitTest(_hQGap, iq) || BitTest(seen, iq))
-      return Error::MakeP(ErrCode::AbsentId, "id=" + std::to_string(iq), "Question index is not in KB.");
-    BitSet(seen, iq, true);
-  }
-  for (int64_t i = 0; i < n; i++) {
-    const int64_t iq = pQIds[i];
-    BitSet(_hQGap, iq, true);
-    _questionGapList.push_back(iq);
-    _questionIds.Vacate(iq);
-  }
-  hipSetDevice(_device);
-  return UploadGaps();
+  return RemoveIds(n, pQIds, _Q, _hQGap, _questionGapList, _questionIds, "Question index is not in KB.");
 }
 
 Error HipEngine::RemoveTargets(int64_t n, const int64_t *pTIds) {  // BaseEngine.cpp:745-765
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_mode != Mode::Maintenance) return WrongModeErr("remove targets");
-  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "Counts must be non-negative.");
-  if (n > 0 && !pTIds) return Error::Make(ErrCode::NullArgument, "Nullptr ids array.");
-  std::vector<uint32_t> seen(BitWords(_T), 0);
+  Error e = RemoveIds(n, pTIds, _T, _hTGap, _targetGapList, _targetIds, "Target index is not in KB (but rather at a gap).");
+  _nTargetGaps = (int64_t)_targetGapList.size();
+  return e;
+}
+
+Error HipEngine::RemoveIds(int64_t n, const int64_t *ids, int64_t limit, std::vector<uint32_t> &gapBits, std::vector<int64_t> &gapList,
+                           IdLedger &ledger, const char *absentMsg) {
+  Error e = CheckRemoval(n, ids, limit, [&](int64_t id) { return BitTest(gapBits, id); }, absentMsg);
+  if (!e.ok()) return e;
   for (int64_t i = 0; i < n; i++) {
-    const int64_t it = pTIds[i];
-    if (it < 0 || it >= _T || BitTest(_hTGap, it) || BitTest(seen, it))
-      return Error::MakeP(ErrCode::AbsentId, "id=" + std::to_string(it), "Target index is not in KB (but rather at a gap).");
-    BitSet(seen, it, true);
-  }
-  for (int64_t i = 0; i < n; i++) {
-    const int64_t it = pTIds[i];
-    BitSet(_hTGap, it, true);
-    _targetGapList.push_back(it);
-    _nTargetGaps++;
-    _targetIds.Vacate(it);
+    BitSet(gapBits, ids[i], true);
+    gapList.push_back(ids[i]);
+    ledger.Vacate(ids[i]);
   }
   hipSetDevice(_device);
   return UploadGaps();
@@ -706,41 +672,20 @@ Error HipEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, i
   if (_mode != Mode::Maintenance) return WrongModeErr("compact the KB");
   if (!pnQuestions || !ppOldQuestions || !pnTargets || !ppOldTargets) return Error::Make(ErrCode::NullArgument, "Nullptr output.");
   hipSetDevice(_device);
-  const int64_t nQ = _Q - (int64_t)_questionGapList.size(), nT = _T - (int64_t)_targetGapList.size();
-  int64_t *oldQ = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nQ, 1));
-  int64_t *oldT = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nT, 1));
-  // questions: a gap in the kept prefix takes the LAST surviving question (:586-601)
-  {
-    int64_t iFirst = 0, iLast = _Q - 1;
-    for (; iFirst <= iLast; iFirst++) {
-      if (!BitTest(_hQGap, iFirst)) { oldQ[iFirst] = iFirst; continue; }
-      while (BitTest(_hQGap, iLast) && iLast > iFirst) iLast--;
-      if (iFirst == iLast) break;
-      oldQ[iFirst] = iLast;
-      const hipError_t ce = hipMemcpyAsync(CubeAt(iFirst), CubeAt(iLast), (size_t)(_K + 1) * (size_t)_ldT * (size_t)_elem,
-                                           hipMemcpyDeviceToDevice, _stream);
-      if (ce != hipSuccess) { std::free(oldQ); std::free(oldT); return HipErr(ce, "Compact (question move)"); }
-      iLast--;
-    }
-  }
-  // targets: gaps of the kept prefix (ascending) take the survivors of the dropped tail (ascending) -- the pairing the
-  // reference produces when no gap lies in the tail (:604-618); with tail gaps the reference's move table is
-  // under-filled, here the pairing simply continues.
-  std::vector<int64_t> moves;
-  {
-    std::vector<int64_t> dst, src;
-    for (int64_t t = 0; t < nT; t++) if (BitTest(_hTGap, t)) dst.push_back(t); else oldT[t] = t;
-    for (int64_t t = nT; t < _T; t++) if (!BitTest(_hTGap, t)) src.push_back(t);
-    for (size_t i = 0; i < dst.size(); i++) { oldT[dst[i]] = src[i]; moves.push_back(src[i]); moves.push_back(dst[i]); }
-  }
+  const CompactPlan plan = PlanCompact(_questionGapList, _targetGapList, _Q, _T);   // the pairing: kb_plan.h
+  const int64_t nQ = (int64_t)plan.oldQ.size(), nT = (int64_t)plan.oldT.size();
+  for (const auto &mv : plan.qMoves)   // (in the plan's order: a question that moves is read before anything lands on it)
+    HIP_TRY(hipMemcpyAsync(CubeAt(mv.first), CubeAt(mv.second), (size_t)(_K + 1) * (size_t)_ldT * (size_t)_elem, hipMemcpyDeviceToDevice, _stream));
+  std::vector<int64_t> moves;   // {src, dst} per target column that moves
+  for (int64_t t = 0; t < nT; t++) if (plan.oldT[(size_t)t] != t) { moves.push_back(plan.oldT[(size_t)t]); moves.push_back(t); }
   int64_t *dMoves = nullptr;
   hipError_t he = Upload(&dMoves, moves, _stream);
   if (he == hipSuccess) he = LaunchMoveTargets(_dCube, _elem, _dVB, _K, _ldT, nQ, dMoves, (int64_t)moves.size() / 2, _stream);
   if (he == hipSuccess) he = hipStreamSynchronize(_stream);
   hipFree(dMoves);
-  if (he != hipSuccess) { std::free(oldQ); std::free(oldT); return HipErr(he, "Compact"); }
-  _questionIds.Repack(nQ, oldQ);
-  _targetIds.Repack(nT, oldT);
+  if (he != hipSuccess) return HipErr(he, "Compact");
+  _questionIds.Repack(nQ, plan.oldQ.data());
+  _targetIds.Repack(nT, plan.oldT.data());
   _questionGapList.clear();
   _targetGapList.clear();
   _nTargetGaps = 0;
@@ -753,7 +698,7 @@ Error HipEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, i
   HIP_TRY(hipMalloc(&_dQGap, _hQGap.size() * sizeof(uint32_t)));
   _Q = nQ; _qTotal = nQ; _T = nT;
   *pnQuestions = nQ; *pnTargets = nT;
-  *ppOldQuestions = oldQ; *ppOldTargets = oldT;
+  *ppOldQuestions = MallocCopy(plan.oldQ); *ppOldTargets = MallocCopy(plan.oldT);
   return UploadGaps();
 }
 

@@ -1,0 +1,107 @@
+// kb_plan.h -- the decisions both engines must take alike, over plain vectors and no engine state: which ids an AddQsTs call
+// hands out, what a Compact moves where, whether a removal is valid, and which of several shards' winners is the selection.
+// HipEngine (hip_engine_kb.cpp) then moves the data on its device, ShardedEngine (sharded_engine.cpp) rebuilds its shards; the
+// C ABI's multi-process exchanges (c_abi.cpp) use the pick.  Host C++17 only -- no HIP -- like combining.h, so that the CPU
+// suite drives it (tests/test_host_logic.py through PqaHip_HostLogicProbe).
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "../../include/PqaCInterop.h"
+
+namespace pqa {
+
+// CpuEngine::AddQsTsSpec, reference PqaCore/CpuEngine.cpp:468-575: gaps are reused LIFO (:476-482 questions, :488-493 targets),
+// the rest is appended (:500, :531); entry i of the caller's parameters belongs to id i of the plan.
+// NOTE reference :516,:523,:529 index the target parameters with nQReuse + j; the evident intent nTReuse + j is used.
+struct AddPlan {
+  std::vector<int64_t> qIds, tIds;     // in the caller's order: the reused gaps first, then the appended ids
+  std::vector<double> qInit, tInit;    // their init amounts
+  int64_t nQReuse = 0, nTReuse = 0;    // how many leading ids are reused gaps (the last entries of the gap lists)
+  int64_t newQ = 0, newT = 0;          // the dimensions afterwards
+};
+inline AddPlan PlanAdd(const std::vector<int64_t> &qGapList, const std::vector<int64_t> &tGapList, int64_t Q, int64_t T,
+                       int64_t nQuestions, const CiAddQorTParam *pAqps, int64_t nTargets, const CiAddQorTParam *pAtps) {
+  AddPlan p;
+  auto axis = [](const std::vector<int64_t> &gaps, int64_t size, int64_t n, const CiAddQorTParam *params, std::vector<int64_t> &ids,
+                 std::vector<double> &init, int64_t &nReuse, int64_t &newSize) {
+    nReuse = std::min<int64_t>(n, (int64_t)gaps.size());
+    newSize = size + (n - nReuse);
+    for (int64_t i = 0; i < nReuse; i++) ids.push_back(gaps[gaps.size() - 1 - (size_t)i]);
+    for (int64_t i = nReuse; i < n; i++) ids.push_back(size + (i - nReuse));
+    for (int64_t i = 0; i < n; i++) init.push_back(params[i]._initAmount);
+  };
+  axis(qGapList, Q, nQuestions, pAqps, p.qIds, p.qInit, p.nQReuse, p.newQ);
+  axis(tGapList, T, nTargets, pAtps, p.tIds, p.tInit, p.nTReuse, p.newT);
+  return p;
+}
+
+// CpuEngine::CompactSpec, reference PqaCore/CpuEngine.cpp:577-658.  Questions: a gap in the kept prefix takes the LAST surviving
+// question (:586-601).  Targets: gaps of the kept prefix (ascending) take the survivors of the dropped tail (ascending) -- the
+// pairing the reference produces when no gap lies in the tail (:604-618); with tail gaps the reference's move table is
+// under-filled, here the pairing simply continues.
+struct CompactPlan {
+  std::vector<int64_t> oldQ, oldT;                    // new id -> the old id whose data it keeps
+  std::vector<std::pair<int64_t, int64_t>> qMoves;    // (dst, src) whole-question moves, in the order they must be made
+};
+inline CompactPlan PlanCompact(const std::vector<int64_t> &qGapList, const std::vector<int64_t> &tGapList, int64_t Q, int64_t T) {
+  std::vector<char> qGap((size_t)Q, 0), tGap((size_t)T, 0);
+  for (int64_t g : qGapList) qGap[(size_t)g] = 1;
+  for (int64_t g : tGapList) tGap[(size_t)g] = 1;
+  const int64_t nQ = Q - (int64_t)qGapList.size(), nT = T - (int64_t)tGapList.size();
+  CompactPlan p;
+  p.oldQ.resize((size_t)nQ);
+  p.oldT.resize((size_t)nT);
+  int64_t iFirst = 0, iLast = Q - 1;
+  for (; iFirst <= iLast; iFirst++) {
+    if (!qGap[(size_t)iFirst]) { p.oldQ[(size_t)iFirst] = iFirst; continue; }
+    while (qGap[(size_t)iLast] && iLast > iFirst) iLast--;
+    if (iFirst == iLast) break;
+    p.oldQ[(size_t)iFirst] = iLast;
+    p.qMoves.emplace_back(iFirst, iLast);
+    iLast--;
+  }
+  int64_t src = nT;
+  for (int64_t t = 0; t < nT; t++) {
+    if (!tGap[(size_t)t]) { p.oldT[(size_t)t] = t; continue; }
+    while (tGap[(size_t)src]) src++;
+    p.oldT[(size_t)t] = src++;
+  }
+  return p;
+}
+
+// RemoveQuestions / RemoveTargets: every id is validated -- range, gaps, repeats within the call -- before the first one is
+// removed.  The position of the first id that cannot be removed, -1 if the call is valid.
+template <typename IsGap>
+inline int64_t FirstBadRemoval(int64_t n, const int64_t *ids, int64_t limit, IsGap isGap) {
+  std::vector<bool> seen((size_t)std::max<int64_t>(limit, 0), false);
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t id = ids[i];
+    if (id < 0 || id >= limit || isGap(id) || seen[(size_t)id]) return i;
+    seen[(size_t)id] = true;
+  }
+  return -1;
+}
+
+// The winner among several shards' winners: maximum priority, lowest index on ties, a NaN counts as -infinity (it never beats
+// a number), a negative index is no candidate.  True if {p, i} is to replace {bestP, bestI}.
+inline bool BetterPick(double bestP, int64_t bestI, double p, int64_t i) {
+  if (i < 0) return false;
+  if (bestI < 0) return true;
+  if (p != p) p = -HUGE_VAL;
+  if (bestP != bestP) bestP = -HUGE_VAL;
+  return p > bestP || (p == bestP && i < bestI);
+}
+struct BestPick {   // {0, -1} while nothing was offered that is a candidate
+  double priority = 0;
+  int64_t index = -1;
+  void Offer(double p, int64_t i) {
+    if (BetterPick(priority, index, p, i)) { priority = p != p ? -HUGE_VAL : p; index = i; }
+  }
+};
+
+}  // namespace pqa

@@ -143,25 +143,17 @@ class ShardedEngine final : public IEngine {
     return _sh[0]->GetOption(name);
   }
   const char *EvalKernelName() const override { return _sh[0]->EvalKernelName(); }
-  Error SetKB(const double *pA, const double *pD, const double *pB) override {
-    std::lock_guard<OpLock> lk(_opMu);
-    { Error fe = FlushAnswers(); if (!fe.ok()) return fe; }   // (the gathered answers read the cube as it was when they were given)
-    for (auto &s : _sh) {
-      const size_t q0 = (size_t)s->FirstQuestion();
-      Error e = s->SetKB(pA + q0 * (size_t)_K * (size_t)_T, pD + q0 * (size_t)_T, pB);
-      if (!e.ok()) return e;
-    }
-    return Error();
+  Error SetKB(const double *pA, const double *pD, const double *pB) override {   // (the gathered answers read the cube as it was when they were given)
+    return All([&](HipEngine &sh) {
+      const size_t q0 = (size_t)sh.FirstQuestion();
+      return sh.SetKB(pA + q0 * (size_t)_K * (size_t)_T, pD + q0 * (size_t)_T, pB);
+    });
   }
   Error GetKB(double *pA, double *pD, double *pB) override {
-    std::lock_guard<OpLock> lk(_opMu);
-    { Error fe = FlushAnswers(); if (!fe.ok()) return fe; }
-    for (auto &s : _sh) {
-      const size_t q0 = (size_t)s->FirstQuestion();
-      Error e = s->GetKB(pA ? pA + q0 * (size_t)_K * (size_t)_T : nullptr, pD ? pD + q0 * (size_t)_T : nullptr, s == _sh[0] ? pB : nullptr);
-      if (!e.ok()) return e;
-    }
-    return Error();
+    return All([&](HipEngine &sh) {
+      const size_t q0 = (size_t)sh.FirstQuestion();
+      return sh.GetKB(pA ? pA + q0 * (size_t)_K * (size_t)_T : nullptr, pD ? pD + q0 * (size_t)_T : nullptr, &sh == _sh[0].get() ? pB : nullptr);
+    });
   }
   Error FillSynthetic(double nTrain, double noiseAmp, uint64_t seed) override { return All([&](HipEngine &e) { return e.FillSynthetic(nTrain, noiseAmp, seed); }); }
   Error SetTargetGaps(int64_t n, const int64_t *ids) override { return All([&](HipEngine &e) { return e.SetTargetGaps(n, ids); }); }
@@ -177,14 +169,10 @@ class ShardedEngine final : public IEngine {
   }
   Error EvalPriorities(int64_t iQuiz, double *pOut, int64_t n) override {
     if (n != _Q) return Error::MakeP(ErrCode::IndexOutOfRange, "n=" + std::to_string(n), "Priority buffer length must equal the question count.");
-    std::lock_guard<OpLock> lk(_opMu);
-    Error e = FlushAnswers();
-    if (!e.ok()) return e;
-    for (auto &s : _sh) { e = s->EvalPriorities(iQuiz, pOut + s->FirstQuestion(), s->LocalQuestions()); if (!e.ok()) return e; }
-    return Error();
+    return All([&](HipEngine &sh) { return sh.EvalPriorities(iQuiz, pOut + sh.FirstQuestion(), sh.LocalQuestions()); });
   }
-  int64_t NextQuestionArgmax(Error &err, int64_t iQuiz) override { return Combine(err, iQuiz, 0, 0); }
-  int64_t NextQuestionSampled(Error &err, int64_t iQuiz, uint64_t rnd) override { return Combine(err, iQuiz, 1, rnd); }
+  int64_t NextQuestionArgmax(Error &err, int64_t iQuiz) override { return Combine(err, iQuiz, SelKind::Argmax, 0); }
+  int64_t NextQuestionSampled(Error &err, int64_t iQuiz, uint64_t rnd) override { return Combine(err, iQuiz, SelKind::Sampled, rnd); }
   Error GetPriors(int64_t iQuiz, double *pOut, int64_t n) override {
     Error e = EnsureApplied(iQuiz);
     if (!e.ok()) return e;
@@ -195,31 +183,17 @@ class ShardedEngine final : public IEngine {
   Error NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) override;
   Error NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) override;
   Error ValidateSelectionBatch(int64_t n, const int64_t *pQuizzes);
+  Error EnqueueBatchOnShards(int64_t n, const int64_t *pQuizzes, bool wantPriorities, std::vector<uint64_t> &tags);   // (under _opMu, the gathered answers first)
   Error EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) override;
   Error SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHipSelection *pOut) override;
   Error Log2HotArray(const double *pIn, double *pOut, int64_t n) override { return _sh[0]->Log2HotArray(pIn, pOut, n); }
   hipStream_t GetStream() const override { return _sh[0]->GetStream(); }
   Error SetStream(hipStream_t) override { return NotSharded("SetStream"); }
-  Error Synchronize() override {
-    std::lock_guard<OpLock> lk(_opMu);
-    Error e = FlushAnswers();
-    if (!e.ok()) return e;
-    return AllLocked([&](HipEngine &sh) { return sh.Synchronize(); });
-  }
-  Error Quiesce() override {
-    std::lock_guard<OpLock> lk(_opMu);
-    Error e = FlushAnswers();
-    if (!e.ok()) return e;
-    return AllLocked([&](HipEngine &sh) { return sh.Quiesce(); });
-  }
+  Error Synchronize() override { return All([&](HipEngine &sh) { return sh.Synchronize(); }); }
+  Error Quiesce() override { return All([&](HipEngine &sh) { return sh.Quiesce(); }); }
   Error EnqueueSelectArgmax(int64_t, void *) override { return NotSharded("EnqueueSelectArgmax"); }
   Error EnqueueSelectArgmaxFlag(int64_t, void *, void *, uint64_t) override { return NotSharded("EnqueueSelectArgmaxFlag"); }
-  Error EnqueueEval(int64_t iQuiz) override {
-    std::lock_guard<OpLock> lk(_opMu);
-    Error e = FlushAnswers();
-    if (!e.ok()) return e;
-    return AllLocked([&](HipEngine &sh) { return sh.EnqueueEval(iQuiz); });
-  }
+  Error EnqueueEval(int64_t iQuiz) override { return All([&](HipEngine &sh) { return sh.EnqueueEval(iQuiz); }); }
   Error GetPriorDevicePtr(int64_t iQuiz, void **ppDev, int64_t *pLdT) override {
     Error e = EnsureApplied(iQuiz);
     if (!e.ok()) return e;
@@ -253,9 +227,17 @@ class ShardedEngine final : public IEngine {
   // ---- the engine's lock and its posted operations ---------------------------------------------------------------------------
   struct SelRequest;
   struct Flight;
+  enum class SelKind { Argmax, Sampled };
+  enum class OpKind {
+    StartQuiz,          // result = the quiz
+    ReleaseQuiz,        // (iQuiz)
+    RecordQuizTarget,   // (iQuiz, iTarget, amount)
+    Flush,              // hand the gathered answers to the shards
+    LaunchBatch         // a leader's LaunchBatch(ctx, batch, flight)
+  };
   struct Op {
-    int kind = 0;                      // 1 StartQuiz (result = the quiz), 2 ReleaseQuiz(iQuiz), 3 RecordQuizTarget(iQuiz, iTarget, amount),
-                                       // 4 hand the gathered answers to the shards, 5 a leader's LaunchBatch(ctx, batch, flight)
+    OpKind kind;
+    explicit Op(OpKind k) : kind(k) {}
     int64_t iQuiz = -1, iTarget = -1;
     double amount = 0;
     Error err;
@@ -269,6 +251,7 @@ class ShardedEngine final : public IEngine {
   using OpLock = PostingLock<Op, ShardedEngine>;   // (a sleeping lock; releasing it runs whatever was posted meanwhile: Execute)
   mutable OpLock _opMu{this, &ShardedEngine::Execute};
   void Execute(Op *ordered);           // (the lock held)
+  void RunOrPost(Op &op) { if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed); }
 
   template <typename F>
   Error All(F &&f) {   // (the gathered answers first: what follows reads or changes what they read)
@@ -289,7 +272,11 @@ class ShardedEngine final : public IEngine {
   // (no concurrent calls on one quiz, IPqaEngine.h:44): a table of chunks that only grows, under _opMu.
   // failed: a hand-over of this quiz's answer did not reach every shard (FlushAnswers): the posterior replicas may differ, and every
   // later call on the quiz says so instead of selecting from one of them; released like any other quiz
-  struct QuizRow { std::atomic<int64_t> lastUse{0}, active{-1}; std::atomic<int> pending{0}, failed{0}; };
+  struct QuizRow {
+    std::atomic<int64_t> lastUse{0}, active{-1};
+    std::atomic<int> pending{0}, failed{0};
+    void Clear() { lastUse.store(0); active.store(-1); pending.store(0); failed.store(0); }   // the quiz is not there (any more)
+  };
   static constexpr int64_t kRowsPerChunk = 4096, kRowChunks = 8192;
   std::atomic<QuizRow *> _rows[kRowChunks] = {};
   std::atomic<int64_t> _registrySize{0};       // ids below this have been handed out at some time
@@ -308,14 +295,15 @@ class ShardedEngine final : public IEngine {
   }
   void Touch(int64_t iQuiz) { if (QuizRow *r = LiveRow(iQuiz)) r->lastUse.store((int64_t)NowStamp(), std::memory_order_relaxed); }
   static int64_t NowStamp() { const time_t t = time(nullptr); return t == 0 ? 1 : (int64_t)t; }
-  void NewQuiz(int64_t id) { QuizRow *r = EnsureRow(id); if (r) { r->active.store(-1); r->pending.store(0); r->failed.store(0); r->lastUse.store(NowStamp()); } }
+  void NewQuiz(int64_t id) { QuizRow *r = EnsureRow(id); if (r) { r->Clear(); r->lastUse.store(NowStamp()); } }
   void ForgetQuizzes() {
     { std::lock_guard<std::mutex> lk(_pendMu); _pending.clear(); _pendingCount.store(0); }
-    for (int64_t id = 0; id < _registrySize.load(); id++) if (QuizRow *r = Row(id)) { r->lastUse.store(0); r->active.store(-1); r->pending.store(0); r->failed.store(0); }
+    for (int64_t id = 0; id < _registrySize.load(); id++) if (QuizRow *r = Row(id)) r->Clear();
   }
   // The error a call on quiz `iQuiz` gets when the quiz is not there or the mode is wrong: the shards' own (BaseEngine::UseQuiz,
   // BaseEngine.cpp:399-419; the MaintenanceSwitch gate), asked of shard 0 by a call that changes nothing.
   Error QuizError(int64_t iQuiz) { Error e; (void)_sh[0]->GetActiveQuestionId(e, iQuiz); return e; }
+  QuizRow *UseQuiz(Error &err, int64_t iQuiz);
 
   // ---- the gathered answers ---------------------------------------------------------------------------------------------------
   struct PendingAnswer { int64_t iQuiz, qGlobal, iAnswer; };
@@ -326,9 +314,8 @@ class ShardedEngine final : public IEngine {
   Error RecordAnswerDeferred(int64_t iQuiz, int64_t iAnswer);
   Error FlushAnswers();                 // (_opMu held) everything gathered so far: one ApplyAnswers per shard
   Error FlushNow() {                    // through the lock: when it returns, every hand-over begun before it has reached all shards
-    Op op;
-    op.kind = 4;
-    if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
+    Op op(OpKind::Flush);
+    RunOrPost(op);
     return op.err;
   }
   // Before anything reads quiz `iQuiz`'s posterior on a shard: its answer -- if one is among the gathered ones, or in a hand-over
@@ -358,6 +345,28 @@ class ShardedEngine final : public IEngine {
   Error WaitForTraining(size_t s, size_t o);     // before shard s reads shard o's rows
   Error BeforeTraining();               // every shard's reads of other shards' rows so far are ordered before every shard's training
   Error AfterTraining();
+  // A training on every shard (_opMu held).  The reference validates every answered question before any Add subtask runs
+  // (CETrainSubtaskDistrib.h:26-45): a gap question owned by shard k must not leave shards 0..k-1 trained and their vB replicas
+  // ahead -- so the gathered answers go out, EVERY shard validates, and only then every shard applies the steps that fall on its
+  // own questions (and its vB replica), between the two barriers that order the other shards' reads of those rows around it.
+  template <typename Validate, typename Apply>
+  Error TrainOnAllShards(Validate &&validate, Apply &&apply) {
+    Error e = FlushAnswers();
+    if (!e.ok()) return e;
+    for (auto &s : _sh) { e = validate(*s); if (!e.ok()) return e; }
+    e = BeforeTraining();
+    if (!e.ok()) return e;
+    for (auto &s : _sh) { e = apply(*s); if (!e.ok()) break; }
+    Error ae = AfterTraining();
+    return e.ok() ? ae : e;
+  }
+  // The rows a resumed quiz (or a batch of them) reads, `total` answered questions in all: every shard computes the posterior itself
+  // from row POINTERS, the rows of other shards' questions in place or staged.  ResolveRows: per answered question its owner and
+  // its two rows (*iBad: the entry that was refused).  StageFor: before shard s reads them -- the owners' trainings are waited for,
+  // and the rows it cannot read in place are marked for staging.
+  struct ResumeRows { std::vector<const void *> rows; std::vector<int> rowDev, owners; std::vector<char> stage; };
+  Error ResolveRows(int64_t total, const AQ *pAQs, ResumeRows &r, int64_t *iBad);
+  Error StageFor(size_t s, ResumeRows &r, bool *allInPlace);
   std::atomic<uint64_t> _stagedRows{0}, _trainBarriers{0};
 
   // ---- one NextQuestion by itself ------------------------------------------------------------------------------------------------
@@ -373,10 +382,31 @@ class ShardedEngine final : public IEngine {
     return _rng[1] + s0;
   }
 
+  // A quiz's asked-or-gap bitmap in GLOBAL numbering (64-bit packs, the bits past the last question set) out of the shards' 32-bit words
+  // in local bit order (their ranges are not multiples of 32).  wordsOf(s): shard s's words, nullptr -> false.  `skip` is the caller's.
+  template <typename WordsOf>
+  bool GlobalSkip(WordsOf &&wordsOf, std::vector<uint64_t> &skip) const {
+    skip.assign((size_t)((_Q + 63) / 64) + 1, 0);
+    for (size_t s = 0; s < _sh.size(); s++) {
+      const uint32_t *w = wordsOf(s);
+      if (!w) return false;
+      const int64_t q0 = _sh[s]->FirstQuestion(), nLocal = _sh[s]->LocalQuestions();
+      for (int64_t k = 0; k < nLocal; k++)
+        if ((w[(size_t)(k >> 5)] >> (k & 31)) & 1u) skip[(size_t)((q0 + k) >> 6)] |= 1ULL << ((q0 + k) & 63);
+    }
+    for (int64_t q = _Q; q < (int64_t)skip.size() * 64; q++) skip[(size_t)(q >> 6)] |= 1ULL << (q & 63);
+    return true;
+  }
+  static bool Skipped(const std::vector<uint64_t> &skip, int64_t q) { return ((skip[(size_t)(q >> 6)] >> (q & 63)) & 1ULL) != 0; }
+  // CpuEngine.cpp:403-407: a pick that is asked or a gap falls to BaseEngine::FindNearestQuestion, over the global bitmap
+  static int64_t NearestFree(const std::vector<uint64_t> &skip, int64_t pick, int64_t nQ) {
+    return pick >= 0 && Skipped(skip, pick) ? FindNearestInPacks(pick, nQ, [&](int64_t p) { return ~skip[(size_t)p]; }) : pick;
+  }
+
   // ---- concurrent NextQuestion calls: combined (combining.h; as hip_engine_combine.cpp's Combine / LaunchBatch / CollectBatch) -------
   struct SelRequest {
     int64_t iQuiz = -1;
-    int kind = 0;                      // 0 argmax, 1 sampled (rnd)
+    SelKind kind = SelKind::Argmax;    // (Sampled: with rnd)
     uint64_t rnd = 0;
     int64_t result = -1;
     Error err;
@@ -397,7 +427,7 @@ class ShardedEngine final : public IEngine {
   int64_t _optCombine = 1, _optLingerUs = 20;
   std::atomic<int> _activeCallers{0};
   bool Concurrent() const { return _optCombine && _activeCallers.load(std::memory_order_relaxed) > 1; }
-  int64_t Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd);
+  int64_t Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t rnd);
   void LaunchBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f);
   void LaunchBatchLocked(int ctx, std::vector<SelRequest *> &batch, Flight &f);
   bool CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f, SelRequest *own);
@@ -405,7 +435,7 @@ class ShardedEngine final : public IEngine {
   void ServeAlone(SelRequest *r) {     // (_opMu held)
     r->err = FailedQuiz(r->iQuiz);
     if (!r->err.ok()) { r->result = -1; return; }
-    r->result = r->kind == 0 ? SelectArgmaxAlone(r->err, r->iQuiz) : SelectSampledLocked(r->err, r->iQuiz, r->rnd);
+    r->result = r->kind == SelKind::Argmax ? SelectArgmaxAlone(r->err, r->iQuiz) : SelectSampledLocked(r->err, r->iQuiz, r->rnd);
   }
   int64_t SelectArgmaxAlone(Error &err, int64_t iQuiz) {
     const int64_t q = SelectArgmaxLocked(err, iQuiz, nullptr);
@@ -439,10 +469,13 @@ class ShardedEngine final : public IEngine {
                 const std::vector<int64_t> &qGaps, const std::vector<int64_t> &tGaps, const IdLedger &targetIds,
                 const std::vector<int64_t> &fillT, const std::vector<double> &fillTInit, const std::vector<int64_t> &fillQ,
                 const std::vector<double> &fillQInit);
-  Error MaintenanceOnly(const char *what) const {
-    if (_sh[0]->IsMaintenanceMode()) return Error();
-    return Error::Make(ErrCode::WrongMode, std::string("Can't perform maintenance-only mode operation - ") + what +
-                                               " - because current mode is not maintenance (but regular/shutdown?).");
+  // Shard s of N over qTotal questions in all, from *first on (SRPoolRunner::CalcSplit, SRPlatform/Interface/SRPoolRunner.h:96-110:
+  // the first qTotal % N shards hold one question more); *first moves to the next shard's.
+  static HipEngine *NewShard(Error &err, CiEngineDefinition def, int64_t s, int64_t N, int64_t qTotal, int device, int64_t *first) {
+    def._nQuestions = qTotal / N + (s < qTotal % N ? 1 : 0);
+    const CiHipShard sh{*first, qTotal, device, 0};
+    *first += def._nQuestions;
+    return HipEngine::Create(err, def, &sh);
   }
   Error InitCrossShard();               // peer access between the devices, the ordering events
   void AdoptShards();                   // what every (re)built set of shards is told
@@ -468,12 +501,12 @@ ShardedEngine::~ShardedEngine() {
 // trainings between their two barriers, and last the combined sweeps -- they are what the most clients wait for.
 void ShardedEngine::Execute(Op *ordered) {
   Error flushErr = FlushAnswers();
-  int64_t nStarts = 0, nTrains = 0;
+  std::vector<Op *> starts, trains;
   for (Op *op = ordered; op != nullptr; op = op->next) {
-    if (op->kind == 4) { op->err = flushErr; continue; }
-    if (op->kind == 1) { nStarts++; continue; }
-    if (op->kind == 3) { nTrains++; continue; }
-    if (op->kind == 2) {   // ReleaseQuiz: every shard releases (a shard that has not got the quiz says so): the registries stay in step
+    if (op->kind == OpKind::Flush) { op->err = flushErr; continue; }
+    if (op->kind == OpKind::StartQuiz) { starts.push_back(op); continue; }
+    if (op->kind == OpKind::RecordQuizTarget) { op->err = flushErr; trains.push_back(op); continue; }
+    if (op->kind == OpKind::ReleaseQuiz) {   // every shard releases (a shard that has not got the quiz says so): the registries stay in step
       Error first;
       size_t released = 0;
       for (auto &s : _sh) { Error e = s->ReleaseQuiz(op->iQuiz); if (e.ok()) released++; else if (first.ok()) first = e; }
@@ -491,14 +524,12 @@ void ShardedEngine::Execute(Op *ordered) {
         }
         if (!first.ok()) { struct timespec ts{0, 50000}; nanosleep(&ts, nullptr); }
       }
-      if (first.ok()) if (QuizRow *r = Row(op->iQuiz)) { r->lastUse.store(0); r->active.store(-1); r->pending.store(0); r->failed.store(0); }
+      if (first.ok()) if (QuizRow *r = Row(op->iQuiz)) r->Clear();
       op->err = first;
     }
   }
-  if (nStarts > 0) {
+  if (!starts.empty()) {
     // the StartQuiz calls that arrived together: ONE launch per shard sets all their priors (prior_kernels.hip: start_quiz_batch_kernel)
-    std::vector<Op *> starts;
-    for (Op *op = ordered; op != nullptr; op = op->next) if (op->kind == 1) starts.push_back(op);
     const int64_t k = (int64_t)starts.size();
     std::vector<int64_t> ids((size_t)k), got((size_t)k);
     Error err;
@@ -520,32 +551,30 @@ void ShardedEngine::Execute(Op *ordered) {
       if (k > 1) _startBatches.fetch_add(1, std::memory_order_relaxed);
     }
   }
-  if (nTrains > 0) {
-    // RecordQuizTarget (BaseEngine.cpp:529-566, CpuEngine.cpp:442-466): every shard validates before any trains -- a gap question
-    // owned by shard k must not leave shards 0..k-1 trained and their vB replicas ahead -- then every shard applies the steps on
-    // its own questions; the other shards' reads of those rows are ordered around the trainings by events
-    std::vector<Op *> valid;
-    for (Op *op = ordered; op != nullptr; op = op->next) {
-      if (op->kind != 3) continue;
-      op->err = flushErr;
-      if (op->err.ok() && op->amount > 0)
-        for (auto &s : _sh) { op->err = s->ValidateTrain(0, nullptr, op->iTarget, op->iQuiz); if (!op->err.ok()) break; }
-      if (op->err.ok()) valid.push_back(op);
-    }
-    if (!valid.empty()) {
-      Error be = BeforeTraining();
-      for (Op *op : valid) {
-        op->err = be;
-        if (!op->err.ok()) continue;
-        Touch(op->iQuiz);
-        for (auto &s : _sh) { op->err = s->RecordQuizTarget(op->iQuiz, op->iTarget, op->amount); if (!op->err.ok()) break; }
-      }
-      Error ae = AfterTraining();
-      if (!ae.ok()) for (Op *op : valid) if (op->err.ok()) op->err = ae;
-    }
+  if (!trains.empty()) {
+    // RecordQuizTarget (BaseEngine.cpp:529-566, CpuEngine.cpp:442-466), every call with its own error: one that a shard refuses
+    // is left out, the others train (no barriers when none is left)
+    Error te = !flushErr.ok() ? flushErr : TrainOnAllShards(
+        [&](HipEngine &sh) {
+          bool any = false;
+          for (Op *op : trains) {
+            if (op->err.ok() && op->amount > 0) op->err = sh.ValidateTrain(0, nullptr, op->iTarget, op->iQuiz);
+            any = any || op->err.ok();
+          }
+          return any ? Error() : trains[0]->err;
+        },
+        [&](HipEngine &sh) {
+          for (Op *op : trains) {
+            if (!op->err.ok()) continue;
+            if (&sh == _sh[0].get()) Touch(op->iQuiz);
+            op->err = sh.RecordQuizTarget(op->iQuiz, op->iTarget, op->amount);
+          }
+          return Error();
+        });
+    if (!te.ok()) for (Op *op : trains) if (op->err.ok()) op->err = te;
   }
   for (Op *op = ordered; op != nullptr; op = op->next)
-    if (op->kind == 5) LaunchBatchLocked(op->ctx, *op->batch, *op->flight);
+    if (op->kind == OpKind::LaunchBatch) LaunchBatchLocked(op->ctx, *op->batch, *op->flight);
 }
 
 // ---- creation -------------------------------------------------------------------------------------------------------------------
@@ -559,18 +588,10 @@ ShardedEngine *ShardedEngine::Create(Error &err, const CiEngineDefinition &def, 
   }
   eng->_K = def._nAnswers; eng->_Q = def._nQuestions; eng->_T = def._nTargets;
   eng->_devices = devices;
-  // SRPoolRunner::CalcSplit (SRPlatform/Interface/SRPoolRunner.h:96-110): the first Q % N shards hold one question more
-  const int64_t quot = def._nQuestions / N, rem = def._nQuestions % N;
-  int64_t first = 0;
-  for (int64_t s = 0; s < N; s++) {
-    CiEngineDefinition d = def;
-    d._nQuestions = quot + (s < rem ? 1 : 0);
-    CiHipShard sh;
-    sh._qFirst = first; sh._qTotal = def._nQuestions; sh._device = devices[(size_t)s]; sh._reserved = 0;
-    HipEngine *e = HipEngine::Create(err, d, &sh);
+  for (int64_t s = 0, first = 0; s < N; s++) {
+    HipEngine *e = NewShard(err, def, s, N, def._nQuestions, devices[(size_t)s], &first);
     if (!e) return nullptr;
     eng->_sh.emplace_back(e);
-    first += d._nQuestions;
   }
   err = eng->InitCrossShard();
   if (!err.ok()) return nullptr;
@@ -692,18 +713,17 @@ Error ShardedEngine::AfterTraining() {
 // ---- quiz registry ----------------------------------------------------------------------------------------------------------------
 int64_t ShardedEngine::StartQuiz(Error &err) {
   CallScope scope(_activeCallers);
-  Op op;
-  op.kind = 1;
-  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
+  Op op(OpKind::StartQuiz);
+  RunOrPost(op);
   err = op.err;
   return op.result;
 }
 
 Error ShardedEngine::ReleaseQuiz(int64_t iQuiz) {
   CallScope scope(_activeCallers);
-  Op op;
-  op.kind = 2; op.iQuiz = iQuiz;
-  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
+  Op op(OpKind::ReleaseQuiz);
+  op.iQuiz = iQuiz;
+  RunOrPost(op);
   return op.err;
 }
 
@@ -715,33 +735,15 @@ int64_t ShardedEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs)
   std::lock_guard<OpLock> lk(_opMu);
   err = FlushAnswers();
   if (!err.ok()) return -1;
-  // every shard computes the posterior itself from row POINTERS: the rows of other shards' questions in place, or staged
-  std::vector<const void *> rows(2 * (size_t)nAnswered);
-  std::vector<int> rowDev(2 * (size_t)nAnswered), owners((size_t)nAnswered);
-  for (int64_t i = 0; i < nAnswered; i++) {
-    const int owner = OwnerOf(pAQs[i].iQuestion);
-    if (owner < 0) { err = Error::MakeP(ErrCode::IndexOutOfRange, "subjIndex=" + std::to_string(pAQs[i].iQuestion), "Question index is not in KB range."); return -1; }
-    err = _sh[(size_t)owner]->GetRowPointers(pAQs[i].iQuestion, pAQs[i].iAnswer, &rows[2 * (size_t)i], &rows[2 * (size_t)i + 1]);
-    if (!err.ok()) return -1;
-    owners[(size_t)i] = owner;
-    rowDev[2 * (size_t)i] = rowDev[2 * (size_t)i + 1] = _sh[(size_t)owner]->Device();
-  }
+  ResumeRows r;
+  err = ResolveRows(nAnswered, pAQs, r, nullptr);
+  if (!err.ok()) return -1;
   int64_t id = -1;
   for (size_t s = 0; s < _sh.size(); s++) {
     bool allInPlace = true;
-    std::vector<char> stage(2 * (size_t)nAnswered, 0);
-    for (int64_t i = 0; i < nAnswered; i++) {
-      const size_t o = (size_t)owners[(size_t)i];
-      if (o == s) continue;
-      err = WaitForTraining(s, o);
-      if (!err.ok()) { ReleaseEverywhere(id, s); return -1; }
-      if (!InPlace(s, o)) {
-        allInPlace = false;
-        stage[2 * (size_t)i] = stage[2 * (size_t)i + 1] = 1;
-        _stagedRows.fetch_add(2, std::memory_order_relaxed);
-      }
-    }
-    const int64_t got = _sh[s]->ResumeQuizRows(err, nAnswered, pAQs, rows.data(), allInPlace ? nullptr : rowDev.data(), allInPlace ? nullptr : stage.data());
+    err = StageFor(s, r, &allInPlace);
+    if (!err.ok()) { ReleaseEverywhere(id, s); return -1; }
+    const int64_t got = _sh[s]->ResumeQuizRows(err, nAnswered, pAQs, r.rows.data(), allInPlace ? nullptr : r.rowDev.data(), allInPlace ? nullptr : r.stage.data());
     if (got < 0) { ReleaseEverywhere(id, s); return -1; }   // (e.g. out of memory on shard s: the earlier shards' quiz goes again)
     if (s == 0) id = got;
     else if (got != id) {
@@ -754,6 +756,39 @@ int64_t ShardedEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs)
   }
   NewQuiz(id);
   return id;
+}
+
+Error ShardedEngine::ResolveRows(int64_t total, const AQ *pAQs, ResumeRows &r, int64_t *iBad) {
+  r.rows.resize(2 * (size_t)total);
+  r.rowDev.resize(2 * (size_t)total);
+  r.owners.resize((size_t)total);
+  for (int64_t i = 0; i < total; i++) {
+    if (iBad) *iBad = i;
+    const int owner = OwnerOf(pAQs[i].iQuestion);
+    if (owner < 0) return Error::MakeP(ErrCode::IndexOutOfRange, "subjIndex=" + std::to_string(pAQs[i].iQuestion), "Question index is not in KB range.");
+    Error e = _sh[(size_t)owner]->GetRowPointers(pAQs[i].iQuestion, pAQs[i].iAnswer, &r.rows[2 * (size_t)i], &r.rows[2 * (size_t)i + 1]);
+    if (!e.ok()) return e;
+    r.owners[(size_t)i] = owner;
+    r.rowDev[2 * (size_t)i] = r.rowDev[2 * (size_t)i + 1] = _sh[(size_t)owner]->Device();
+  }
+  return Error();
+}
+
+Error ShardedEngine::StageFor(size_t s, ResumeRows &r, bool *allInPlace) {
+  r.stage.assign(2 * r.owners.size(), 0);
+  *allInPlace = true;
+  for (size_t i = 0; i < r.owners.size(); i++) {
+    const size_t o = (size_t)r.owners[i];
+    if (o == s) continue;
+    Error e = WaitForTraining(s, o);
+    if (!e.ok()) return e;
+    if (!InPlace(s, o)) {
+      *allInPlace = false;
+      r.stage[2 * i] = r.stage[2 * i + 1] = 1;
+      _stagedRows.fetch_add(2, std::memory_order_relaxed);
+    }
+  }
+  return Error();
 }
 
 // ResumeQuizBatch: the row pointers resolved as ResumeQuiz resolves them, then every shard one batch (HipEngine::ResumeQuizBatchRows:
@@ -775,34 +810,22 @@ Error ShardedEngine::ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ
   std::lock_guard<OpLock> lk(_opMu);
   Error err = FlushAnswers();
   if (!err.ok()) return err;
-  std::vector<const void *> rows(2 * (size_t)total);
-  std::vector<int> rowDev(2 * (size_t)total), owners((size_t)total);
-  for (int64_t i = 0, j = 0; i < n; i++)
-    for (int64_t k = 0; k < pCounts[i]; k++, j++) {
-      const int owner = OwnerOf(pAQs[j].iQuestion);
-      if (owner < 0) err = Error::MakeP(ErrCode::IndexOutOfRange, "subjIndex=" + std::to_string(pAQs[j].iQuestion), "Question index is not in KB range.");
-      else err = _sh[(size_t)owner]->GetRowPointers(pAQs[j].iQuestion, pAQs[j].iAnswer, &rows[2 * (size_t)j], &rows[2 * (size_t)j + 1]);
-      if (!err.ok()) { err.message = "Batch entry " + std::to_string(i) + ": " + err.message; return err; }
-      owners[(size_t)j] = owner;
-      rowDev[2 * (size_t)j] = rowDev[2 * (size_t)j + 1] = _sh[(size_t)owner]->Device();
-    }
+  ResumeRows r;
+  int64_t iBad = 0;
+  err = ResolveRows(total, pAQs, r, &iBad);
+  if (!err.ok()) {
+    int64_t entry = 0;   // (the quiz whose answered question was refused)
+    for (int64_t end = pCounts[0]; end <= iBad; end += pCounts[entry]) entry++;
+    err.message = "Batch entry " + std::to_string(entry) + ": " + err.message;
+    return err;
+  }
   std::vector<int64_t> ids((size_t)n);
   auto releaseAll = [&](size_t nShards) { for (int64_t i = 0; i < n; i++) if (pQuizzes[i] >= 0) ReleaseEverywhere(pQuizzes[i], nShards); };
   for (size_t s = 0; s < _sh.size(); s++) {
     bool allInPlace = true;
-    std::vector<char> stage(2 * (size_t)total, 0);
-    for (int64_t j = 0; j < total; j++) {
-      const size_t o = (size_t)owners[(size_t)j];
-      if (o == s) continue;
-      err = WaitForTraining(s, o);
-      if (!err.ok()) { releaseAll(s); return err; }
-      if (!InPlace(s, o)) {
-        allInPlace = false;
-        stage[2 * (size_t)j] = stage[2 * (size_t)j + 1] = 1;
-        _stagedRows.fetch_add(2, std::memory_order_relaxed);
-      }
-    }
-    err = _sh[s]->ResumeQuizBatchRows(n, pCounts, pAQs, rows.data(), allInPlace ? nullptr : rowDev.data(), allInPlace ? nullptr : stage.data(),
+    err = StageFor(s, r, &allInPlace);
+    if (!err.ok()) { releaseAll(s); return err; }
+    err = _sh[s]->ResumeQuizBatchRows(n, pCounts, pAQs, r.rows.data(), allInPlace ? nullptr : r.rowDev.data(), allInPlace ? nullptr : r.stage.data(),
                                       s == 0 ? pQuizzes : ids.data());
     if (!err.ok()) { releaseAll(s); for (int64_t i = 0; i < n; i++) pQuizzes[i] = -1; return err; }
     if (s > 0 && !std::equal(ids.begin(), ids.end(), pQuizzes)) {
@@ -829,27 +852,30 @@ Error ShardedEngine::ClearOldQuizzes(int64_t maxCount, double maxAgeSec) {
   for (int64_t id = 0; id < _registrySize.load(); id++)
     if (QuizRow *r = LiveRow(id)) inUse.push_back(QuizUsage{id, (time_t)r->lastUse.load()});   // (registry order)
   for (int64_t id : QuizzesToLetGo(inUse, time(nullptr), maxCount, maxAgeSec)) {
-    if (QuizRow *r = Row(id)) { r->lastUse.store(0); r->active.store(-1); r->pending.store(0); }
+    if (QuizRow *r = Row(id)) r->Clear();
     for (auto &s : _sh) { Error e = s->ReleaseQuiz(id); if (!e.ok() && first.ok()) first = e; }
   }
   return first;
 }
 
 // ---- active question, answers, listings -----------------------------------------------------------------------------------------
-int64_t ShardedEngine::GetActiveQuestionId(Error &err, int64_t iQuiz) {
+ShardedEngine::QuizRow *ShardedEngine::UseQuiz(Error &err, int64_t iQuiz) {   // BaseEngine::UseQuiz: the quiz's row, its last use now
   QuizRow *r = _sh[0]->IsRegularMode() ? LiveRow(iQuiz) : nullptr;
-  if (!r) { err = QuizError(iQuiz); if (!err.ok()) return -1; r = LiveRow(iQuiz); if (!r) { err = Error::Make(ErrCode::Internal, "The quiz tables have diverged."); return -1; } }
-  err = Error();
-  r->lastUse.store(NowStamp(), std::memory_order_relaxed);
-  return r->active.load(std::memory_order_relaxed);
+  err = r ? Error() : QuizError(iQuiz);
+  if (!r && err.ok() && !(r = LiveRow(iQuiz))) err = Error::Make(ErrCode::Internal, "The quiz tables have diverged.");
+  if (r) r->lastUse.store(NowStamp(), std::memory_order_relaxed);
+  return r;
+}
+
+int64_t ShardedEngine::GetActiveQuestionId(Error &err, int64_t iQuiz) {
+  QuizRow *r = UseQuiz(err, iQuiz);
+  return r ? r->active.load(std::memory_order_relaxed) : -1;
 }
 
 Error ShardedEngine::SetActiveQuestion(int64_t iQuiz, int64_t iQuestion) {
-  QuizRow *r = _sh[0]->IsRegularMode() ? LiveRow(iQuiz) : nullptr;
-  if (!r) { Error e = QuizError(iQuiz); if (!e.ok()) return e; r = LiveRow(iQuiz); if (!r) return Error::Make(ErrCode::Internal, "The quiz tables have diverged."); }
-  r->lastUse.store(NowStamp(), std::memory_order_relaxed);
-  r->active.store(iQuestion, std::memory_order_relaxed);   // unchecked, as reference PqaCore/BaseEngine.cpp:507-508
-  return Error();
+  Error err;
+  if (QuizRow *r = UseQuiz(err, iQuiz)) r->active.store(iQuestion, std::memory_order_relaxed);   // unchecked, as reference PqaCore/BaseEngine.cpp:507-508
+  return err;
 }
 
 // Everything NextQuestion does after the pick (CpuEngine.cpp:403-413): the question becomes the quiz's active question, the
@@ -975,36 +1001,21 @@ int64_t ShardedEngine::ListTopTargets(Error &err, int64_t iQuiz, int64_t maxCoun
 }
 
 // ---- training -------------------------------------------------------------------------------------------------------------------
-// The reference validates every answered question before any Add subtask runs (CETrainSubtaskDistrib.h:26-45): a gap question
-// owned by shard k must not leave shards 0..k-1 trained and their vB replicas ahead -- every shard validates, then every shard trains.
 Error ShardedEngine::Train(int64_t n, const AQ *pAQs, int64_t iTarget, double amount) {
   std::lock_guard<OpLock> lk(_opMu);
-  Error e = FlushAnswers();
-  if (!e.ok()) return e;
-  if (n >= 0 && amount > 0 && (n == 0 || pAQs != nullptr))   // (else: shard 0 produces the reference's argument error, before any kernel)
-    for (auto &s : _sh) { e = s->ValidateTrain(n, pAQs, iTarget, -1); if (!e.ok()) return e; }
-  e = BeforeTraining();
-  if (!e.ok()) return e;
-  for (auto &s : _sh) { e = s->Train(n, pAQs, iTarget, amount); if (!e.ok()) break; }
-  Error ae = AfterTraining();
-  return e.ok() ? ae : e;
+  const bool checkable = n >= 0 && amount > 0 && (n == 0 || pAQs != nullptr);   // (else: shard 0 produces the reference's argument error, before any kernel)
+  return TrainOnAllShards([&](HipEngine &sh) { return checkable ? sh.ValidateTrain(n, pAQs, iTarget, -1) : Error(); },
+                          [&](HipEngine &sh) { return sh.Train(n, pAQs, iTarget, amount); });
 }
 
-// TrainBatch / RecordQuizTargetBatch: what Train does, once for the whole batch -- every shard validates every entry, then every
-// shard runs the batch on its own questions and its vB replica between the two barriers.
+// TrainBatch / RecordQuizTargetBatch: what Train does, once for the whole batch.
 Error ShardedEngine::TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) {
   Error e = HipEngine::CheckTrainBatchArgs(n, pCounts, pAQs, pTargets, pAmounts);
   if (!e.ok() || n == 0) return e;
   CallScope scope(_activeCallers);
   std::lock_guard<OpLock> lk(_opMu);
-  e = FlushAnswers();
-  if (!e.ok()) return e;
-  for (auto &s : _sh) { e = s->ValidateTrainBatch(n, pCounts, pAQs, pTargets, nullptr); if (!e.ok()) return e; }
-  e = BeforeTraining();
-  if (!e.ok()) return e;
-  for (auto &s : _sh) { e = s->TrainBatch(n, pCounts, pAQs, pTargets, pAmounts); if (!e.ok()) break; }
-  Error ae = AfterTraining();
-  return e.ok() ? ae : e;
+  return TrainOnAllShards([&](HipEngine &sh) { return sh.ValidateTrainBatch(n, pCounts, pAQs, pTargets, nullptr); },
+                          [&](HipEngine &sh) { return sh.TrainBatch(n, pCounts, pAQs, pTargets, pAmounts); });
 }
 
 Error ShardedEngine::RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) {
@@ -1012,22 +1023,18 @@ Error ShardedEngine::RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, c
   if (!e.ok() || n == 0) return e;
   CallScope scope(_activeCallers);
   std::lock_guard<OpLock> lk(_opMu);
-  e = FlushAnswers();
-  if (!e.ok()) return e;
-  for (auto &s : _sh) { e = s->ValidateTrainBatch(n, nullptr, nullptr, pTargets, pQuizzes); if (!e.ok()) return e; }
-  e = BeforeTraining();
-  if (!e.ok()) return e;
-  for (int64_t i = 0; i < n; i++) Touch(pQuizzes[i]);
-  for (auto &s : _sh) { e = s->RecordQuizTargetBatch(n, pQuizzes, pTargets, pAmounts); if (!e.ok()) break; }
-  Error ae = AfterTraining();
-  return e.ok() ? ae : e;
+  return TrainOnAllShards([&](HipEngine &sh) { return sh.ValidateTrainBatch(n, nullptr, nullptr, pTargets, pQuizzes); },
+                          [&](HipEngine &sh) {
+                            if (&sh == _sh[0].get()) for (int64_t i = 0; i < n; i++) Touch(pQuizzes[i]);
+                            return sh.RecordQuizTargetBatch(n, pQuizzes, pTargets, pAmounts);
+                          });
 }
 
 Error ShardedEngine::RecordQuizTarget(int64_t iQuiz, int64_t iTarget, double amount) {
   CallScope scope(_activeCallers);
-  Op op;
-  op.kind = 3; op.iQuiz = iQuiz; op.iTarget = iTarget; op.amount = amount;
-  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
+  Op op(OpKind::RecordQuizTarget);
+  op.iQuiz = iQuiz; op.iTarget = iTarget; op.amount = amount;
+  RunOrPost(op);
   return op.err;
 }
 
@@ -1051,20 +1058,15 @@ int64_t ShardedEngine::SelectArgmaxLocked(Error &err, int64_t iQuiz, double *pPr
       }
   }
   std::atomic_thread_fence(std::memory_order_acquire);
-  double bestP = 0;
-  int64_t bestI = -1;
+  BestPick best;   // (kb_plan.h: maximum priority, lowest index on ties)
   for (size_t s = 0; s < _sh.size(); s++) {
-    double p = _slots[s].priority;
-    const int64_t i = _slots[s].index;
-    if (i == -3) { err = Error::Make(ErrCode::Internal, "A shard's sweep did not complete."); return -1; }
-    if (i < 0) continue;
-    if (p != p) p = -HUGE_VAL;
-    if (bestI < 0 || p > bestP || (p == bestP && i < bestI)) { bestP = p; bestI = i; }
+    if (_slots[s].index == -3) { err = Error::Make(ErrCode::Internal, "A shard's sweep did not complete."); return -1; }
+    best.Offer(_slots[s].priority, _slots[s].index);
   }
-  CheckPriority(bestP, bestI);   // (the reference's "Got priority=" warning, for the question that was selected)
-  if (pPriority) *pPriority = bestP;
+  CheckPriority(best.priority, best.index);   // (the reference's "Got priority=" warning, for the question that was selected)
+  if (pPriority) *pPriority = best.priority;
   err = Error();
-  return bestI;
+  return best.index;
 }
 
 // The reference's selector (PqaCore/CpuEngine.cpp:362-400) over the GLOBAL question range: the same per-subtask Kahan run
@@ -1083,31 +1085,18 @@ int64_t ShardedEngine::SelectSampledLocked(Error &err, int64_t iQuiz, uint64_t r
     hipSetDevice(s->Device());
     if (hipStreamSynchronize(s->GetStream()) != hipSuccess) { err = Error::Make(ErrCode::Internal, "A shard's sweep failed."); return -1; }
   }
-  // which questions are asked or gaps, in global numbering (the shards' ranges are not multiples of 32)
-  std::vector<uint64_t> skip((size_t)((_Q + 63) / 64) + 1, 0);
-  {
-    std::vector<uint32_t> words;
-    for (auto &s : _sh) {
-      err = s->UnavailableWords(iQuiz, words);
-      if (!err.ok()) return -1;
-      for (int64_t i = 0; i < s->LocalQuestions(); i++)
-        if ((words[(size_t)(i >> 5)] >> (i & 31)) & 1u) skip[(size_t)((s->FirstQuestion() + i) >> 6)] |= 1ULL << ((s->FirstQuestion() + i) & 63);
-    }
-    for (int64_t q = _Q; q < (int64_t)skip.size() * 64; q++) skip[(size_t)(q >> 6)] |= 1ULL << (q & 63);
-  }
-  auto skipped = [&](int64_t q) { return (skip[(size_t)(q >> 6)] >> (q & 63)) & 1ULL; };
-  const int64_t n = _Q;
-  int64_t sel = SelectSampledHost(_hostPriority.data(), n, _sh[0]->GetOption("eval_subtasks"), rnd, [&](int64_t q) { return skipped(q) != 0; });
-  // :403-407 a gap / asked pick falls to BaseEngine::FindNearestQuestion, over the global bitmap
-  if (skipped(sel)) sel = FindNearestInPacks(sel, n, [&](int64_t p) { return ~skip[(size_t)p]; });
-  return Commit(err, iQuiz, sel);
+  std::vector<uint64_t> skip;
+  std::vector<uint32_t> words;
+  if (!GlobalSkip([&](size_t s) { err = _sh[s]->UnavailableWords(iQuiz, words); return err.ok() ? words.data() : nullptr; }, skip)) return -1;
+  const int64_t sel = SelectSampledHost(_hostPriority.data(), _Q, _sh[0]->GetOption("eval_subtasks"), rnd, [&](int64_t q) { return Skipped(skip, q); });
+  return Commit(err, iQuiz, NearestFree(skip, sel, _Q));
 }
 
 int64_t ShardedEngine::NextQuestion(Error &err, int64_t iQuiz) {
-  if (_select == 1) return Combine(err, iQuiz, 0, 0);
+  if (_select == 1) return Combine(err, iQuiz, SelKind::Argmax, 0);
   uint64_t rnd;
   { std::lock_guard<std::mutex> lk(_rngMu); rnd = NextRandom(); }   // (drawn when the call arrives, whatever sweep serves it)
-  return Combine(err, iQuiz, 1, rnd);
+  return Combine(err, iQuiz, SelKind::Sampled, rnd);
 }
 
 // ---- concurrent NextQuestion calls ------------------------------------------------------------------------------------------------
@@ -1116,7 +1105,7 @@ int64_t ShardedEngine::NextQuestion(Error &err, int64_t iQuiz) {
 // in flight before the first is waited for), hands the lead to the oldest request still waiting as soon as the sweeps are
 // launched, and then waits for its own.  Two batch contexts alternate, so that the next leader launches while this one's sweeps
 // run.  One request alone takes the single-quiz path (the shards' fused argmax through the pinned slots).
-int64_t ShardedEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
+int64_t ShardedEngine::Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t rnd) {
   CallScope scope(_activeCallers);
   SelRequest r;
   r.iQuiz = iQuiz; r.kind = kind; r.rnd = rnd;
@@ -1148,9 +1137,9 @@ int64_t ShardedEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd
 }
 
 void ShardedEngine::LaunchBatch(int ctx, std::vector<SelRequest *> &batch, Flight &f) {
-  Op op;
-  op.kind = 5; op.ctx = ctx; op.batch = &batch; op.flight = &f;
-  if (_opMu.RunOrPost(op)) _postedOps.fetch_add(1, std::memory_order_relaxed);
+  Op op(OpKind::LaunchBatch);
+  op.ctx = ctx; op.batch = &batch; op.flight = &f;
+  RunOrPost(op);
 }
 
 void ShardedEngine::LaunchBatchLocked(int ctx, std::vector<SelRequest *> &batch, Flight &f) {
@@ -1163,7 +1152,7 @@ void ShardedEngine::LaunchBatchLocked(int ctx, std::vector<SelRequest *> &batch,
     { Error fe = FailedQuiz(r->iQuiz); if (!fe.ok()) { r->err = fe; r->result = -1; continue; } }
     live.push_back(r);
     ids.push_back(r->iQuiz);
-    f.anySampled = f.anySampled || r->kind == 1;
+    f.anySampled = f.anySampled || r->kind == SelKind::Sampled;
   }
   if (live.empty()) return;
   if (live.size() == 1) { ServeAlone(live[0]); return; }
@@ -1217,40 +1206,24 @@ bool ShardedEngine::CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flig
     // The priority vectors are on the host: every client selects for ITSELF (the O(Q) scalar Kahan steps of the reference's
     // selector run on as many cores as there are clients), the leader only for its own request.
     c.readers.fetch_add((int)n, std::memory_order_acq_rel);
-    const int64_t packs = (_Q + 63) / 64 + 1;
     bool ownLive = false;
     for (int64_t i = 0; i < n; i++) {
       SelRequest *r = f.live[(size_t)i];
       r->views.resize(N);
-      r->skip.assign((size_t)packs, 0);
-      for (size_t s = 0; s < N; s++) {
-        r->views[s] = views[s][(size_t)i];
-        const size_t words = _sh[s]->UnavailableWordCount();
-        const uint32_t *w = f.unavailable[s].data() + (size_t)i * words;
-        const int64_t q0 = _sh[s]->FirstQuestion();
-        for (int64_t k = 0; k < _sh[s]->LocalQuestions(); k++)
-          if ((w[(size_t)(k >> 5)] >> (k & 31)) & 1u) r->skip[(size_t)((q0 + k) >> 6)] |= 1ULL << ((q0 + k) & 63);
-      }
-      for (int64_t q = _Q; q < packs * 64; q++) r->skip[(size_t)(q >> 6)] |= 1ULL << (q & 63);
+      for (size_t s = 0; s < N; s++) r->views[s] = views[s][(size_t)i];
+      GlobalSkip([&](size_t s) { return f.unavailable[s].data() + (size_t)i * _sh[s]->UnavailableWordCount(); }, r->skip);
       r->ctx = &c;
       if (r == own) { ownLive = true; continue; }
       Combiner<SelRequest, CombineCtx>::LetSelect(batch, r);
     }
     return ownLive;
   }
-  // the kernels' choices: per quiz the best of the shards' winners (maximum priority, lowest index on ties, NaN never wins)
+  // the kernels' choices: per quiz the best of the shards' winners
   for (int64_t i = 0; i < n; i++) {
     SelRequest *r = f.live[(size_t)i];
-    double bestP = 0;
-    int64_t bestI = -1;
-    for (size_t s = 0; s < N; s++) {
-      double p = winners[s][(size_t)i]._priority;
-      const int64_t q = winners[s][(size_t)i]._iQuestion;
-      if (q < 0) continue;
-      if (p != p) p = -HUGE_VAL;
-      if (bestI < 0 || p > bestP || (p == bestP && q < bestI)) { bestP = p; bestI = q; }
-    }
-    r->result = Commit(r->err, r->iQuiz, bestI);
+    BestPick best;
+    for (size_t s = 0; s < N; s++) best.Offer(winners[s][(size_t)i]._priority, winners[s][(size_t)i]._iQuestion);
+    r->result = Commit(r->err, r->iQuiz, best.index);
   }
   return false;
 }
@@ -1260,7 +1233,7 @@ bool ShardedEngine::CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flig
 // client's own thread, no lock.
 int64_t ShardedEngine::SelectFromViews(SelRequest *r) {
   const int64_t nQ = _Q;
-  auto skipped = [&](int64_t q) { return ((r->skip[(size_t)(q >> 6)] >> (q & 63)) & 1ULL) != 0; };
+  auto skipped = [&](int64_t q) { return Skipped(r->skip, q); };
   std::vector<double> run((size_t)nQ);
   SpinWait w;
   for (size_t s = 0; s < _sh.size(); s++) {
@@ -1284,45 +1257,41 @@ int64_t ShardedEngine::SelectFromViews(SelRequest *r) {
     }
   }
   int64_t pick = -1;
-  if (r->kind == 1) {
+  if (r->kind == SelKind::Sampled) {
     pick = SelectSampledHost(run.data(), nQ, _sh[0]->GetOption("eval_subtasks"), r->rnd, [&](int64_t q) { return skipped(q); });
   } else {
-    double best = 0;
-    for (int64_t q = 0; q < nQ; q++) {
-      if (skipped(q)) continue;
-      double p = run[(size_t)q];
-      if (p != p) p = -HUGE_VAL;
-      if (pick < 0 || p > best) { best = p; pick = q; }
-    }
+    BestPick best;
+    for (int64_t q = 0; q < nQ; q++) if (!skipped(q)) best.Offer(run[(size_t)q], q);
+    pick = best.index;
     if (pick >= 0) CheckPriority(run[(size_t)pick], pick);
   }
-  // :403-407 a gap / asked pick falls to BaseEngine::FindNearestQuestion, over the global bitmap
-  if (pick >= 0 && skipped(pick)) pick = FindNearestInPacks(pick, nQ, [&](int64_t p) { return ~r->skip[(size_t)p]; });
-  return r->result = Commit(r->err, r->iQuiz, pick);
+  return r->result = Commit(r->err, r->iQuiz, NearestFree(r->skip, pick, nQ));
 }
 
 // ---- the batch calls of the ABI -------------------------------------------------------------------------------------------------
 // Every shard's batched sweep is enqueued -- on its own device and stream -- before the first one is waited for: on N devices a
 // batch takes one shard's time, not N shards' (SRPoolRunner's subtasks run side by side too, SRPlatform/Interface/SRPoolRunner.h:96-110).
+Error ShardedEngine::EnqueueBatchOnShards(int64_t n, const int64_t *pQuizzes, bool wantPriorities, std::vector<uint64_t> &tags) {
+  tags.assign(_sh.size(), 0);
+  std::lock_guard<OpLock> lk(_opMu);
+  Error e = FlushAnswers();
+  _shardsInFlightMax = 0;
+  for (size_t s = 0; e.ok() && s < _sh.size(); s++) {
+    e = _sh[s]->EnqueueBatch(n, pQuizzes, wantPriorities, &tags[s]);   // (validation fails on shard 0, before anything was launched)
+    if (e.ok()) _shardsInFlightMax++;
+  }
+  for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) Touch(pQuizzes[i]);
+  return e;
+}
+
 Error ShardedEngine::SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHipSelection *pOut) {
   if (n > 0 && !pOut) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
   std::lock_guard<std::mutex> ctxLock(_bctx[0].mu);   // (the shards' batch context 0: not while a combined sweep uses it)
   while (_bctx[0].readers.load(std::memory_order_acquire) != 0) _mm_pause();
-  std::vector<uint64_t> tags(_sh.size(), 0);
-  {
-    std::lock_guard<OpLock> lk(_opMu);
-    Error e = FlushAnswers();
-    if (!e.ok()) return e;
-    _shardsInFlightMax = 0;
-    for (size_t s = 0; s < _sh.size(); s++) {
-      e = _sh[s]->EnqueueBatch(n, pQuizzes, false, &tags[s]);
-      if (!e.ok()) return e;   // (validation fails on shard 0, before anything was launched)
-      _shardsInFlightMax++;
-    }
-    for (int64_t i = 0; i < n; i++) Touch(pQuizzes[i]);
-  }
+  std::vector<uint64_t> tags;
+  Error first = EnqueueBatchOnShards(n, pQuizzes, false, tags);
+  if (!first.ok()) return first;
   std::vector<CiHipSelection> part((size_t)n);
-  Error first;
   for (size_t s = 0; s < _sh.size(); s++) {
     Error e = _sh[s]->CollectBatchSelections(n, tags[s], part.data());
     if (!e.ok()) { if (first.ok()) first = e; continue; }   // (the other shards' launches are still waited for)
@@ -1330,7 +1299,7 @@ Error ShardedEngine::SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHip
       const CiHipSelection &c = part[(size_t)i];
       CiHipSelection &b = pOut[i];
       if (s == 0) { b = c; continue; }
-      if (c._iQuestion >= 0 && (b._iQuestion < 0 || c._priority > b._priority || (c._priority == b._priority && c._iQuestion < b._iQuestion))) b = c;
+      if (BetterPick(b._priority, b._iQuestion, c._priority, c._iQuestion)) b = c;
     }
   }
   return first;
@@ -1372,23 +1341,14 @@ Error ShardedEngine::NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes
   if (!e.ok()) return e;
   std::lock_guard<OpLock> lk(_opMu);
   const int64_t nSub = _sh[0]->GetOption("eval_subtasks");
-  std::vector<uint64_t> skip((size_t)((_Q + 63) / 64) + 1);
+  std::vector<uint64_t> skip;
   std::vector<uint32_t> words;
   std::vector<int64_t> picks((size_t)n, -1);
   for (int64_t i = 0; i < n; i++) {
-    // which questions are asked or gaps, in global numbering (the shards' ranges are not multiples of 32)
-    std::fill(skip.begin(), skip.end(), 0);
-    for (auto &s : _sh) {
-      e = s->UnavailableWords(pQuizzes[i], words);
-      if (!e.ok()) return e;   // (nothing has changed yet)
-      for (int64_t k = 0; k < s->LocalQuestions(); k++)
-        if ((words[(size_t)(k >> 5)] >> (k & 31)) & 1u) skip[(size_t)((s->FirstQuestion() + k) >> 6)] |= 1ULL << ((s->FirstQuestion() + k) & 63);
-    }
-    for (int64_t q = _Q; q < (int64_t)skip.size() * 64; q++) skip[(size_t)(q >> 6)] |= 1ULL << (q & 63);
-    auto skipped = [&](int64_t q) { return ((skip[(size_t)(q >> 6)] >> (q & 63)) & 1ULL) != 0; };
-    int64_t sel = SelectSampledHost(pri.data() + (size_t)i * (size_t)_Q, _Q, nSub, pRnd[i], skipped);
-    if (skipped(sel)) sel = FindNearestInPacks(sel, _Q, [&](int64_t p) { return ~skip[(size_t)p]; });   // :403-407
-    picks[(size_t)i] = sel;
+    if (!GlobalSkip([&](size_t s) { e = _sh[s]->UnavailableWords(pQuizzes[i], words); return e.ok() ? words.data() : nullptr; }, skip))
+      return e;   // (nothing has changed yet)
+    const int64_t sel = SelectSampledHost(pri.data() + (size_t)i * (size_t)_Q, _Q, nSub, pRnd[i], [&](int64_t q) { return Skipped(skip, q); });
+    picks[(size_t)i] = NearestFree(skip, sel, _Q);
   }
   for (int64_t i = 0; i < n; i++) {
     Error ce;
@@ -1413,20 +1373,9 @@ Error ShardedEngine::NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64
 Error ShardedEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) {
   std::lock_guard<std::mutex> ctxLock(_bctx[0].mu);
   while (_bctx[0].readers.load(std::memory_order_acquire) != 0) _mm_pause();
-  {
-    std::lock_guard<OpLock> lk(_opMu);
-    Error e = FlushAnswers();
-    if (!e.ok()) return e;
-    // every shard's sweep is in flight (its own device and stream) before the first one is waited for
-    _shardsInFlightMax = 0;
-    for (auto &s : _sh) {
-      uint64_t tag = 0;
-      e = s->EnqueueBatch(n, pQuizzes, true, &tag);
-      if (!e.ok()) return e;
-      _shardsInFlightMax++;
-    }
-    for (int64_t i = 0; i < n && pQuizzes; i++) Touch(pQuizzes[i]);
-  }
+  std::vector<uint64_t> tags;
+  Error first = EnqueueBatchOnShards(n, pQuizzes, true, tags);
+  if (!first.ok()) return first;
   std::vector<double> part;
   for (auto &s : _sh) {
     part.resize((size_t)n * (size_t)s->LocalQuestions());
@@ -1442,16 +1391,10 @@ Error ShardedEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, dou
 // ---- maintenance ------------------------------------------------------------------------------------------------------------
 Error ShardedEngine::RemoveQuestions(int64_t n, const int64_t *pQIds) {   // BaseEngine.cpp:722-743; all ids validated before the first is removed
   std::lock_guard<OpLock> lk(_opMu);
-  Error e = MaintenanceOnly("remove questions");
+  Error e = _sh[0]->IsMaintenanceMode() ? Error() : WrongModeErr("remove questions");
   if (!e.ok()) return e;
-  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "Counts must be non-negative.");
-  if (n > 0 && !pQIds) return Error::Make(ErrCode::NullArgument, "Nullptr ids array.");
-  for (int64_t i = 0; i < n; i++) {
-    const int64_t iq = pQIds[i];
-    bool bad = iq < 0 || iq >= _Q || std::find(_qGapList.begin(), _qGapList.end(), iq) != _qGapList.end();
-    for (int64_t j = 0; j < i && !bad; j++) bad = pQIds[j] == iq;
-    if (bad) return Error::MakeP(ErrCode::AbsentId, "id=" + std::to_string(iq), "Question index is not in KB.");
-  }
+  e = CheckRemoval(n, pQIds, _Q, [&](int64_t iq) { return _qGapBit[(size_t)iq] != 0; }, "Question index is not in KB.");
+  if (!e.ok()) return e;
   for (auto &s : _sh) { e = s->SetQuestionGaps(n, pQIds); if (!e.ok()) return e; }
   for (int64_t i = 0; i < n; i++) { _qGapList.push_back(pQIds[i]); _questionIds.Vacate(pQIds[i]); }
   RefreshGapBits();
@@ -1460,7 +1403,7 @@ Error ShardedEngine::RemoveQuestions(int64_t n, const int64_t *pQIds) {   // Bas
 
 Error ShardedEngine::RemoveTargets(int64_t n, const int64_t *pTIds) {   // BaseEngine.cpp:745-765
   std::lock_guard<OpLock> lk(_opMu);
-  Error e = MaintenanceOnly("remove targets");
+  Error e = _sh[0]->IsMaintenanceMode() ? Error() : WrongModeErr("remove targets");
   if (!e.ok()) return e;
   // (the target axis is replicated: every shard validates and removes the same ids; shard 0 refuses a bad call before any other is asked)
   for (auto &s : _sh) { e = s->RemoveTargets(n, pTIds); if (!e.ok()) return e; }
@@ -1489,19 +1432,14 @@ Error ShardedEngine::Rebuild(int64_t newQ, int64_t newT, const std::vector<int64
   Error err;
   for (auto &s : _sh) { err = s->Synchronize(); if (!err.ok()) return err; }
   std::vector<std::unique_ptr<HipEngine>> fresh;
-  const int64_t quot = newQ / N, rem = newQ % N;   // SRPoolRunner::CalcSplit
-  int64_t first = 0;
-  for (int64_t s = 0; s < N; s++) {
-    CiEngineDefinition d = def;
-    d._nQuestions = quot + (s < rem ? 1 : 0);
-    CiHipShard sh;
-    sh._qFirst = first; sh._qTotal = newQ; sh._device = _devices[(size_t)s]; sh._reserved = 0;
-    HipEngine *e = HipEngine::Create(err, d, &sh);
+  for (int64_t s = 0, next = 0; s < N; s++) {
+    HipEngine *e = NewShard(err, def, s, N, newQ, _devices[(size_t)s], &next);
     if (!e) return err;
     fresh.emplace_back(e);
+    const int64_t first = e->FirstQuestion(), nLocal = e->LocalQuestions();
     // its questions' rows, from wherever the old shards hold them
-    std::vector<const void *> blocks((size_t)d._nQuestions, nullptr);
-    for (int64_t q = 0; q < d._nQuestions; q++) {
+    std::vector<const void *> blocks((size_t)nLocal, nullptr);
+    for (int64_t q = 0; q < nLocal; q++) {
       const int64_t old = srcQ[(size_t)(first + q)];
       if (old < 0) continue;
       const int owner = OwnerOf(old);
@@ -1512,7 +1450,7 @@ Error ShardedEngine::Rebuild(int64_t newQ, int64_t newT, const std::vector<int64
     std::vector<int64_t> localQ;
     std::vector<double> localInit;
     for (size_t i = 0; i < fillQ.size(); i++)
-      if (fillQ[i] >= first && fillQ[i] < first + d._nQuestions) { localQ.push_back(fillQ[i] - first); localInit.push_back(fillQInit[i]); }
+      if (fillQ[i] >= first && fillQ[i] < first + nLocal) { localQ.push_back(fillQ[i] - first); localInit.push_back(fillQInit[i]); }
     err = e->ApplyFills(fillT, fillTInit, localQ, localInit);
     if (!err.ok()) return err;
     err = e->SetQuestionGaps((int64_t)qGaps.size(), qGaps.data());
@@ -1530,7 +1468,6 @@ Error ShardedEngine::Rebuild(int64_t newQ, int64_t newT, const std::vector<int64
     }
     err = e->StartMaintenance(false);
     if (!err.ok()) return err;
-    first += d._nQuestions;
   }
   // ---- commit
   _sh.swap(fresh);
@@ -1549,26 +1486,15 @@ Error ShardedEngine::Rebuild(int64_t newQ, int64_t newT, const std::vector<int64
 
 Error ShardedEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) {
   std::lock_guard<OpLock> lk(_opMu);
-  Error e = MaintenanceOnly("add questions/targets");
+  Error e = _sh[0]->IsMaintenanceMode() ? Error() : WrongModeErr("add questions/targets");
+  if (e.ok()) e = CheckAddArgs(nQuestions, pAqps, nTargets, pAtps);
   if (!e.ok()) return e;
-  if (nQuestions < 0 || nTargets < 0)
-    return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(std::min(nQuestions, nTargets)), "Counts must be non-negative.");
-  if ((nQuestions > 0 && !pAqps) || (nTargets > 0 && !pAtps)) return Error::Make(ErrCode::NullArgument, "Nullptr parameters array.");
-  // CpuEngine::AddQsTsSpec, reference PqaCore/CpuEngine.cpp:468-575, over the GLOBAL ids (as HipEngine::AddQsTs over its own):
-  // gaps are reused LIFO, the rest is appended
+  // CpuEngine::AddQsTsSpec, reference PqaCore/CpuEngine.cpp:468-575, over the GLOBAL ids (kb_plan.h)
   std::vector<int64_t> tGapList, tmp;
   _sh[0]->GetGapLists(tmp, tGapList);
-  const int64_t nQReuse = std::min<int64_t>(nQuestions, (int64_t)_qGapList.size()), nQNew = nQuestions - nQReuse;
-  const int64_t nTReuse = std::min<int64_t>(nTargets, (int64_t)tGapList.size()), nTNew = nTargets - nTReuse;
-  std::vector<int64_t> qIds, tIds;
-  std::vector<double> qInit, tInit;
-  for (int64_t i = 0; i < nQReuse; i++) qIds.push_back(_qGapList[_qGapList.size() - 1 - (size_t)i]);   // :476-482
-  for (int64_t i = 0; i < nTReuse; i++) tIds.push_back(tGapList[tGapList.size() - 1 - (size_t)i]);      // :488-493
-  for (int64_t i = 0; i < nQNew; i++) qIds.push_back(_Q + i);                                           // :500
-  for (int64_t j = 0; j < nTNew; j++) tIds.push_back(_T + j);                                           // :531
-  for (int64_t i = 0; i < nQuestions; i++) qInit.push_back(pAqps[i]._initAmount);
-  for (int64_t j = 0; j < nTargets; j++) tInit.push_back(pAtps[j]._initAmount);
-  const int64_t newQ = _Q + nQNew, newT = _T + nTNew;
+  const AddPlan plan = PlanAdd(_qGapList, tGapList, _Q, _T, nQuestions, pAqps, nTargets, pAtps);
+  const std::vector<int64_t> &qIds = plan.qIds, &tIds = plan.tIds;
+  const int64_t nQReuse = plan.nQReuse, nTReuse = plan.nTReuse, newQ = plan.newQ, newT = plan.newT;
   std::vector<int64_t> srcQ((size_t)newQ, -1), srcT((size_t)newT, -1);
   for (int64_t q = 0; q < _Q; q++) srcQ[(size_t)q] = q;      // (a gap's rows travel too: they are nobody's)
   for (int64_t t = 0; t < _T; t++) srcT[(size_t)t] = t;
@@ -1581,7 +1507,7 @@ Error ShardedEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t 
   for (int64_t i = 0; i < nQReuse; i++) questionIds.Reissue(qIds[(size_t)i]);
   questionIds.Extend(newQ);
   // (the rebuilt shards mark their remaining gaps themselves: their own id maps are over local ids and are not consulted)
-  e = Rebuild(newQ, newT, srcQ, srcT, qGaps, tGaps, targetIds, tIds, tInit, qIds, qInit);
+  e = Rebuild(newQ, newT, srcQ, srcT, qGaps, tGaps, targetIds, tIds, plan.tInit, qIds, plan.qInit);
   if (!e.ok()) return e;
   _questionIds = questionIds;
   for (int64_t i = 0; i < nQuestions; i++) pAqps[i]._index = qIds[(size_t)i];
@@ -1591,153 +1517,77 @@ Error ShardedEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t 
 
 Error ShardedEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets) {
   std::lock_guard<OpLock> lk(_opMu);
-  Error e = MaintenanceOnly("compact the KB");
+  Error e = _sh[0]->IsMaintenanceMode() ? Error() : WrongModeErr("compact the KB");
   if (!e.ok()) return e;
   if (!pnQuestions || !ppOldQuestions || !pnTargets || !ppOldTargets) return Error::Make(ErrCode::NullArgument, "Nullptr output.");
-  // CpuEngine::CompactSpec, CpuEngine.cpp:577-658, over the global axes (the pairing of HipEngine::Compact)
+  // CpuEngine::CompactSpec, CpuEngine.cpp:577-658, over the global axes (kb_plan.h); the data moves by rebuilding the shards
   std::vector<int64_t> tGapList, tmp;
   _sh[0]->GetGapLists(tmp, tGapList);
-  std::vector<char> qGap((size_t)_Q, 0), tGap((size_t)_T, 0);
-  for (int64_t g : _qGapList) qGap[(size_t)g] = 1;
-  for (int64_t g : tGapList) tGap[(size_t)g] = 1;
-  const int64_t nQ = _Q - (int64_t)_qGapList.size(), nT = _T - (int64_t)tGapList.size();
+  const CompactPlan plan = PlanCompact(_qGapList, tGapList, _Q, _T);
+  const int64_t nQ = (int64_t)plan.oldQ.size(), nT = (int64_t)plan.oldT.size();
   if (nQ < (int64_t)_sh.size())
     return Error::MakeP(ErrCode::InsufficientEngineDimensions, "[nQuestions=" + std::to_string(nQ) + " of " + std::to_string(_sh.size()) + "]",
                         "Fewer questions than devices in PQA_DEVICES would remain.");
-  std::vector<int64_t> oldQ((size_t)std::max<int64_t>(nQ, 1)), oldT((size_t)std::max<int64_t>(nT, 1));
-  {   // questions: a gap in the kept prefix takes the LAST surviving question (:586-601)
-    int64_t iFirst = 0, iLast = _Q - 1;
-    for (; iFirst <= iLast; iFirst++) {
-      if (!qGap[(size_t)iFirst]) { oldQ[(size_t)iFirst] = iFirst; continue; }
-      while (qGap[(size_t)iLast] && iLast > iFirst) iLast--;
-      if (iFirst == iLast) break;
-      oldQ[(size_t)iFirst] = iLast;
-      iLast--;
-    }
-  }
-  {   // targets: gaps of the kept prefix (ascending) take the survivors of the dropped tail (ascending) (:604-618)
-    std::vector<int64_t> dst, src;
-    for (int64_t t = 0; t < nT; t++) if (tGap[(size_t)t]) dst.push_back(t); else oldT[(size_t)t] = t;
-    for (int64_t t = nT; t < _T; t++) if (!tGap[(size_t)t]) src.push_back(t);
-    for (size_t i = 0; i < dst.size(); i++) oldT[dst[i]] = src[i];
-  }
-  oldQ.resize((size_t)nQ);
-  oldT.resize((size_t)nT);
   IdLedger targetIds = _sh[0]->TargetIds(), questionIds = _questionIds;
-  targetIds.Repack(nT, oldT.data());
-  questionIds.Repack(nQ, oldQ.data());
-  e = Rebuild(nQ, nT, oldQ, oldT, {}, {}, targetIds, {}, {}, {}, {});
+  targetIds.Repack(nT, plan.oldT.data());
+  questionIds.Repack(nQ, plan.oldQ.data());
+  e = Rebuild(nQ, nT, plan.oldQ, plan.oldT, {}, {}, targetIds, {}, {}, {}, {});
   if (!e.ok()) return e;
   _questionIds = questionIds;
-  int64_t *outQ = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nQ, 1));
-  int64_t *outT = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nT, 1));
-  std::copy(oldQ.begin(), oldQ.end(), outQ);
-  std::copy(oldT.begin(), oldT.end(), outT);
   *pnQuestions = nQ; *pnTargets = nT;
-  *ppOldQuestions = outQ; *ppOldTargets = outT;
+  *ppOldQuestions = MallocCopy(plan.oldQ); *ppOldTargets = MallocCopy(plan.oldT);
   return Error();
 }
 
 // ---- .kb file (layout of reference PqaCore/BaseEngine.cpp:323-385 + PqaCore/CpuEngine.cpp:664-688, see hip_engine_kb.cpp): the
 // file orders its rows by question, so the shards' blocks follow each other -- every shard streams its own rows through its
 // own staging buffer; vB, the target gaps and the target / quiz id maps are replicas (shard 0's are written).
-namespace {
-Error KbFileErr(const char *path, const char *msg) {
-  return Error::MakeP(ErrCode::FileOp, std::string("filePath=[") + (path ? path : "") + "]", msg);
-}
-struct FileGuard {
-  FILE *f;
-  ~FileGuard() { if (f) std::fclose(f); }
-};
-}  // namespace
-
 Error ShardedEngine::SaveKB(const char *filePath, bool doubleBuffer) {
   (void)doubleBuffer;
-  if (!filePath) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name.");
   std::lock_guard<OpLock> lk(_opMu);
-  { Error e = FlushAnswers(); if (!e.ok()) return e; }
-  for (auto &s : _sh) { Error e = s->Synchronize(); if (!e.ok()) return e; }   // (also parks resident sweeps)
-  FileGuard fg{std::fopen(filePath, "wb")};
-  if (!fg.f) return Error::MakeP(ErrCode::CantOpenFile, std::string("filePath=[") + filePath + "]", "Can't open the file to write KB to.");
+  Error e = FlushAnswers();
+  if (!e.ok()) return e;
+  for (auto &s : _sh) { e = s->Synchronize(); if (!e.ok()) return e; }   // (also parks resident sweeps)
+  KbFile file(filePath, true);
   HipEngine &s0 = *_sh[0];
-  const uint64_t prec = (uint64_t)(s0.PrecisionType() & 0xF) | ((uint64_t)(s0.PrecMantissa() & 0xFFFFFFF) << 4) | ((uint64_t)s0.PrecExponent() << 32);
-  const int64_t dims[3] = {_K, _Q, _T};
-  Error ae;
-  const uint64_t nAsked = s0.GetTotalQuestionsAsked(ae);
-  if (std::fwrite(&prec, 8, 1, fg.f) != 1 || std::fwrite(dims, sizeof(dims), 1, fg.f) != 1 || std::fwrite(&nAsked, 8, 1, fg.f) != 1)
-    return KbFileErr(filePath, "Can't write the KB file header.");
-  for (auto &s : _sh) { Error e = s->IoRows(fg.f, filePath, false, true); if (!e.ok()) return e; }
-  for (auto &s : _sh) { Error e = s->IoRows(fg.f, filePath, true, true); if (!e.ok()) return e; }
-  { Error e = s0.IoVB(fg.f, filePath, true); if (!e.ok()) return e; }
-  std::vector<int64_t> qGaps = _qGapList, tGaps, tmp;   // (LIFO order, as the reference's GapTracker saves it)
+  const uint64_t nAsked = s0.GetTotalQuestionsAsked(e);
+  e = file.WriteHeader(KbHeader{PackPrecision(s0.PrecisionType(), s0.PrecMantissa(), s0.PrecExponent()), _K, _Q, _T, nAsked});
+  for (size_t s = 0; e.ok() && s < _sh.size(); s++) e = _sh[s]->IoRows(file.f, filePath, false, true);
+  for (size_t s = 0; e.ok() && s < _sh.size(); s++) e = _sh[s]->IoRows(file.f, filePath, true, true);
+  if (e.ok()) e = s0.IoVB(file.f, filePath, true);
+  std::vector<int64_t> tGaps, tmp;
   s0.GetGapLists(tmp, tGaps);
-  auto writeGaps = [&](const std::vector<int64_t> &gaps) {
-    const int64_t n = (int64_t)gaps.size();
-    return std::fwrite(&n, 8, 1, fg.f) == 1 && std::fwrite(gaps.data(), 8, (size_t)n, fg.f) == (size_t)n;
-  };
-  if (!writeGaps(qGaps) || !writeGaps(tGaps)) return KbFileErr(filePath, "Can't write the gaps.");
-  // (the live quiz map with empty = true keeps its next permanent id, as BaseEngine.cpp:379 and HipEngine::SaveKB write it)
-  if (!_questionIds.Write(fg.f) || !s0.TargetIds().Write(fg.f) || !s0.QuizIds().Write(fg.f, true))
-    return KbFileErr(filePath, "Can't write the permanent-compact ID mappings.");
-  if (std::fflush(fg.f) != 0) return KbFileErr(filePath, "Failed in hard flushing the KB.");
-  FILE *f = fg.f;
-  fg.f = nullptr;
-  if (std::fclose(f) != 0) return KbFileErr(filePath, "Failed in closing the file.");
-  return Error();
+  if (e.ok()) e = file.WriteTrailer(_qGapList, tGaps, _questionIds, s0.TargetIds(), s0.QuizIds());
+  return e.ok() ? file.FlushAndClose() : e;
 }
 
 ShardedEngine *ShardedEngine::Load(Error &err, const char *filePath, const std::vector<int> &devices) {
-  if (!filePath) { err = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name."); return nullptr; }
-  FileGuard fg{std::fopen(filePath, "rb")};
-  if (!fg.f) { err = Error::MakeP(ErrCode::CantOpenFile, std::string("filePath=[") + filePath + "]", "Can't open the KB file to read."); return nullptr; }
-  uint64_t prec = 0, nAsked = 0;
-  int64_t dims[3];
-  if (std::fread(&prec, 8, 1, fg.f) != 1 || std::fread(dims, sizeof(dims), 1, fg.f) != 1 || std::fread(&nAsked, 8, 1, fg.f) != 1) {
-    err = KbFileErr(filePath, "Can't read the KB file header.");
-    return nullptr;
-  }
-  CiEngineDefinition def;
-  std::memset(&def, 0, sizeof(def));
-  def._nAnswers = dims[0]; def._nQuestions = dims[1]; def._nTargets = dims[2];
-  def._precType = (uint8_t)(prec & 0xF);
-  def._precMantissa = (uint32_t)((prec >> 4) & 0xFFFFFFF);
-  def._precExponent = (uint16_t)((prec >> 32) & 0xFFFF);
-  def._initAmount = 1.0;   // not stored in the file; every count is overwritten below
-  std::unique_ptr<ShardedEngine> eng(Create(err, def, devices));
+  KbFile file(filePath, false);
+  KbHeader h;
+  err = file.ReadHeader(h);
+  if (!err.ok()) return nullptr;
+  std::unique_ptr<ShardedEngine> eng(Create(err, h.Definition(), devices));
   if (!eng) return nullptr;
-  auto fail = [&](Error e) { err = std::move(e); return (ShardedEngine *)nullptr; };
-  for (auto &s : eng->_sh) { Error e = s->IoRows(fg.f, filePath, false, false); if (!e.ok()) return fail(std::move(e)); }
-  for (auto &s : eng->_sh) { Error e = s->IoRows(fg.f, filePath, true, false); if (!e.ok()) return fail(std::move(e)); }
-  {
-    Error e = eng->_sh[0]->IoVB(fg.f, filePath, false);
-    if (!e.ok()) return fail(std::move(e));
-    std::vector<double> vb((size_t)dims[2]);   // shard 0's vB (already in the engine's number type) to the other replicas
-    e = eng->_sh[0]->GetKB(nullptr, nullptr, vb.data());
-    for (size_t i = 1; e.ok() && i < eng->_sh.size(); i++) e = eng->_sh[i]->SetVBFromHost(vb.data());
-    if (!e.ok()) return fail(std::move(e));
-  }
-  eng->_sh[0]->SetQuestionsAsked(nAsked);
-  auto readGaps = [&](std::vector<int64_t> &gaps, int64_t limit) {
-    int64_t n;
-    if (std::fread(&n, 8, 1, fg.f) != 1 || n < 0 || n > limit) return false;
-    gaps.resize((size_t)n);
-    if (std::fread(gaps.data(), 8, (size_t)n, fg.f) != (size_t)n) return false;
-    for (int64_t g : gaps) if (g < 0 || g >= limit) return false;
-    return true;
-  };
-  std::vector<int64_t> qGaps, tGaps;
-  if (!readGaps(qGaps, dims[1]) || !readGaps(tGaps, dims[2])) return fail(KbFileErr(filePath, "Can't read the gaps."));
-  eng->_qGapList = qGaps;
+  for (size_t s = 0; err.ok() && s < eng->_sh.size(); s++) err = eng->_sh[s]->IoRows(file.f, filePath, false, false);
+  for (size_t s = 0; err.ok() && s < eng->_sh.size(); s++) err = eng->_sh[s]->IoRows(file.f, filePath, true, false);
+  if (err.ok()) err = eng->_sh[0]->IoVB(file.f, filePath, false);
+  std::vector<double> vb((size_t)h.T);   // shard 0's vB (already in the engine's number type) to the other replicas
+  if (err.ok()) err = eng->_sh[0]->GetKB(nullptr, nullptr, vb.data());
+  for (size_t i = 1; err.ok() && i < eng->_sh.size(); i++) err = eng->_sh[i]->SetVBFromHost(vb.data());
+  if (!err.ok()) return nullptr;
+  eng->_sh[0]->SetQuestionsAsked(h.nAsked);
+  std::vector<int64_t> tGaps;
+  IdLedger targetIds, quizIds;
+  err = file.ReadTrailer(h.Q, h.T, eng->_qGapList, tGaps, eng->_questionIds, targetIds, quizIds);
+  if (!err.ok()) return nullptr;
   eng->RefreshGapBits();
   for (auto &s : eng->_sh) {
-    Error e = s->SetQuestionGaps((int64_t)qGaps.size(), qGaps.data());
-    if (e.ok()) e = s->SetTargetGaps((int64_t)tGaps.size(), tGaps.data());
-    if (!e.ok()) return fail(std::move(e));
+    err = s->SetQuestionGaps((int64_t)eng->_qGapList.size(), eng->_qGapList.data());
+    if (err.ok()) err = s->SetTargetGaps((int64_t)tGaps.size(), tGaps.data());
+    if (!err.ok()) return nullptr;
+    s->SetTargetIds(targetIds);
+    s->SetQuizIds(quizIds);
   }
-  IdLedger targetIds, quizIds;
-  if (!eng->_questionIds.Read(fg.f) || !targetIds.Read(fg.f) || !quizIds.Read(fg.f)) return fail(KbFileErr(filePath, "Can't read the permanent-compact ID mappings."));
-  for (auto &s : eng->_sh) { s->SetTargetIds(targetIds); s->SetQuizIds(quizIds); }
-  err = Error();
   return eng.release();
 }
 

@@ -1,8 +1,12 @@
-"""Host bookkeeping of the engine that needs no device (runs in the CPU suite): the compact <-> permanent id map and the
-eviction rule of ClearOldQuizzes, driven through PqaHip_HostLogicProbe and held to a Python model of the reference's
-observable behaviour (PqaCore/PermanentIdManager.cpp, PqaCore/BaseEngine.cpp:814-873)."""
+"""Host bookkeeping of the engine that needs no device (runs in the CPU suite): the compact <-> permanent id map, the
+eviction rule of ClearOldQuizzes, and what the one-device and the sharded engine decide through the same code (kb_plan.h) -- the
+ids AddQsTs hands out, what Compact moves where, which removals are refused, which shard's winner is the selection -- driven
+through PqaHip_HostLogicProbe and held to a Python model of the reference's observable behaviour
+(PqaCore/PermanentIdManager.cpp, PqaCore/BaseEngine.cpp:722-765,814-873, PqaCore/CpuEngine.cpp:468-658)."""
 import ctypes
+import math
 import random
+import struct
 
 import numpy as np
 import pytest
@@ -199,3 +203,246 @@ def test_clear_old_quizzes_rule_random(seed):
     if extra and kept:
         assert max(age[q] for q in extra) <= min(t for _, t in kept)      # nobody kept is older than somebody released
     assert [age[q] for q in extra] == sorted(age[q] for q in extra)       # longest-unused first
+
+
+# ---- the plans both engines share (kb_plan.h) -------------------------------------------------------------------------------------
+def words_of(values):
+    return [len(values), *values]
+
+
+def bits(x):
+    return struct.unpack("<q", struct.pack("<d", x))[0]
+
+
+def from_bits(w):
+    return struct.unpack("<d", struct.pack("<q", w))[0]
+
+
+def take_list(out, at):
+    n = out[at]
+    return out[at + 1:at + 1 + n], at + 1 + n
+
+
+def add_plan(Q, T, q_gaps, t_gaps, q_amounts, t_amounts):
+    words = [Q, T, *words_of(q_gaps), *words_of(t_gaps), *words_of([bits(a) for a in q_amounts]), *words_of([bits(a) for a in t_amounts])]
+    n_out = 8 + 2 * (len(q_amounts) + len(t_amounts))
+    n, out = probe("add_plan", words, n_out)
+    assert n == n_out
+    q_ids, at = take_list(out, 4)
+    t_ids, at = take_list(out, at)
+    q_init, at = take_list(out, at)
+    t_init, at = take_list(out, at)
+    assert at == n
+    return dict(n_q_reuse=out[0], n_t_reuse=out[1], new_q=out[2], new_t=out[3], q_ids=q_ids, t_ids=t_ids,
+                q_init=[from_bits(w) for w in q_init], t_init=[from_bits(w) for w in t_init])
+
+
+def add_model(Q, T, q_gaps, t_gaps, q_amounts, t_amounts):
+    """GapTracker.Acquire pops the back of the gap list; when it is empty the axis grows by one."""
+    def axis(gaps, size, amounts):
+        gaps, ids = list(gaps), []
+        for _ in amounts:
+            if gaps:
+                ids.append(gaps.pop())
+            else:
+                ids.append(size)
+                size += 1
+        return ids, size
+    q_ids, new_q = axis(q_gaps, Q, q_amounts)
+    t_ids, new_t = axis(t_gaps, T, t_amounts)
+    return dict(n_q_reuse=min(len(q_gaps), len(q_amounts)), n_t_reuse=min(len(t_gaps), len(t_amounts)), new_q=new_q, new_t=new_t,
+                q_ids=q_ids, t_ids=t_ids, q_init=list(q_amounts), t_init=list(t_amounts))
+
+
+def compact_plan(Q, T, q_gaps, t_gaps):
+    n_out = 3 + 3 * Q + T
+    n, out = probe("compact_plan", [Q, T, *words_of(q_gaps), *words_of(t_gaps)], n_out)
+    assert n > 0
+    old_q, at = take_list(out, 0)
+    old_t, at = take_list(out, at)
+    moves, at = take_list(out, at)
+    assert at == n
+    return old_q, old_t, list(zip(moves[0::2], moves[1::2]))
+
+
+def compact_model(Q, T, q_gaps, t_gaps):
+    """CompactSpec as a caller sees it: the survivors fill 0 .. n-1; a question gap below n takes the LAST question not yet
+    taken, a target gap below n (ascending) takes the survivors from n on (ascending)."""
+    n_q, n_t = Q - len(q_gaps), T - len(t_gaps)
+    tail_q = [q for q in range(Q - 1, n_q - 1, -1) if q not in q_gaps]
+    old_q, moves = [], []
+    for q in range(n_q):
+        if q in q_gaps:
+            old_q.append(tail_q.pop(0))
+            moves.append((q, old_q[-1]))
+        else:
+            old_q.append(q)
+    tail_t = [t for t in range(n_t, T) if t not in t_gaps]
+    old_t = [tail_t.pop(0) if t in t_gaps else t for t in range(n_t)]
+    assert not tail_q and not tail_t
+    return old_q, old_t, moves
+
+
+def test_add_plan_fixed_case():
+    """the sequence of tests/test_gpu_kb.py::test_add_remove_compact_against_numpy_model"""
+    got = add_plan(12, 19, [2, 9], [0, 5, 18], [0.5, 0.25, 2.0], [0.3, 0.7])
+    assert got["q_ids"] == [9, 2, 12] and got["t_ids"] == [18, 5]
+    assert (got["n_q_reuse"], got["n_t_reuse"], got["new_q"], got["new_t"]) == (2, 2, 13, 19)
+    assert got["q_init"] == [0.5, 0.25, 2.0] and got["t_init"] == [0.3, 0.7]
+    assert got == add_model(12, 19, [2, 9], [0, 5, 18], [0.5, 0.25, 2.0], [0.3, 0.7])
+
+
+def test_add_plan_named_cases():
+    # no gaps: everything is appended
+    assert add_plan(5, 4, [], [], [1.0, 2.0], [3.0]) == add_model(5, 4, [], [], [1.0, 2.0], [3.0])
+    assert add_plan(5, 4, [], [], [1.0, 2.0], [3.0])["q_ids"] == [5, 6]
+    # more additions than gaps: the gaps from the back of the list, then new ids
+    assert add_plan(6, 6, [4, 1], [3], [1.0] * 4, [1.0] * 3)["q_ids"] == [1, 4, 6, 7]
+    assert add_plan(6, 6, [4, 1], [3], [1.0] * 4, [1.0] * 3)["t_ids"] == [3, 6, 7]
+    # fewer additions than gaps: the dimensions stay
+    got = add_plan(6, 6, [4, 1, 0], [3, 2], [0.5], [0.25])
+    assert got["q_ids"] == [0] and got["t_ids"] == [2] and (got["new_q"], got["new_t"]) == (6, 6)
+    # every question a gap
+    got = add_plan(3, 2, [0, 1, 2], [], [1.0, 1.0, 1.0, 1.0], [])
+    assert got["q_ids"] == [2, 1, 0, 3] and got["new_q"] == 4 and got["t_ids"] == []
+    # nothing added
+    assert add_plan(3, 2, [1], [0], [], []) == add_model(3, 2, [1], [0], [], [])
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_add_plan_against_model(seed):
+    rng = random.Random(300 + seed)
+    Q, T = rng.randrange(1, 60), rng.randrange(1, 60)
+    q_gaps = rng.sample(range(Q), rng.randrange(0, Q + 1))
+    t_gaps = rng.sample(range(T), rng.randrange(0, T + 1))
+    q_amounts = [rng.choice([0.1, 0.5, 1.0, 2.5]) for _ in range(rng.randrange(0, 2 * len(q_gaps) + 3))]
+    t_amounts = [rng.choice([0.1, 0.5, 1.0, 2.5]) for _ in range(rng.randrange(0, 2 * len(t_gaps) + 3))]
+    assert add_plan(Q, T, q_gaps, t_gaps, q_amounts, t_amounts) == add_model(Q, T, q_gaps, t_gaps, q_amounts, t_amounts)
+
+
+def test_compact_plan_fixed_case():
+    """tests/test_gpu_kb.py::test_add_remove_compact_against_numpy_model after its additions: 13 questions, 19 targets"""
+    old_q, old_t, moves = compact_plan(13, 19, [3, 11], [0])
+    assert len(old_q) == 11 and old_q[3] == 12 and old_q[:3] == [0, 1, 2] and sorted(old_q) == [q for q in range(13) if q not in (3, 11)]
+    assert len(old_t) == 18 and old_t[0] == 18 and old_t[1:] == list(range(1, 18))
+    assert moves == [(3, 12)]
+    assert (old_q, old_t, moves) == compact_model(13, 19, [3, 11], [0])
+
+
+def test_compact_plan_named_cases():
+    # no gaps: nothing moves
+    assert compact_plan(4, 3, [], []) == ([0, 1, 2, 3], [0, 1, 2], [])
+    # every question a gap (and every target)
+    assert compact_plan(3, 2, [2, 0, 1], [1, 0]) == ([], [], [])
+    # gaps only in the dropped tail: the prefix stays where it is
+    assert compact_plan(6, 5, [5, 4], [3, 4]) == ([0, 1, 2, 3], [0, 1, 2], [])
+    # gaps in the prefix AND in the tail: the last survivors come down, the tail's gaps are passed over
+    assert compact_plan(7, 7, [1, 5, 0], [6, 0, 4, 1]) == ([6, 4, 2, 3], [3, 5, 2], [(0, 6), (1, 4)])
+    assert compact_model(7, 7, [1, 5, 0], [6, 0, 4, 1]) == ([6, 4, 2, 3], [3, 5, 2], [(0, 6), (1, 4)])
+    # one survivor, at the very end
+    assert compact_plan(4, 1, [0, 1, 2], []) == ([3], [0], [(0, 3)])
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_compact_plan_against_model(seed):
+    rng = random.Random(400 + seed)
+    Q, T = rng.randrange(1, 80), rng.randrange(1, 80)
+    q_gaps = rng.sample(range(Q), rng.randrange(0, Q + 1))
+    t_gaps = rng.sample(range(T), rng.randrange(0, T + 1))
+    old_q, old_t, moves = compact_plan(Q, T, q_gaps, t_gaps)
+    assert (old_q, old_t, moves) == compact_model(Q, T, q_gaps, t_gaps)
+    # what the moves are for: made in their order on an array that holds its own indices, they leave old_q in the kept prefix
+    rows = list(range(Q))
+    for dst, src in moves:
+        rows[dst] = rows[src]
+    assert rows[:len(old_q)] == old_q
+    assert sorted(old_q) == [q for q in range(Q) if q not in q_gaps] and sorted(old_t) == [t for t in range(T) if t not in t_gaps]
+
+
+def check_removal(limit, gaps, ids):
+    n, out = probe("check_removal", [limit, *words_of(gaps), *words_of(ids)], 2)
+    assert n == 2
+    return out
+
+
+ABSENT_ID = 13      # PqaErrors.h: the id is absent from the KB
+
+
+def removal_model(limit, gaps, ids):
+    for i, x in enumerate(ids):
+        if x < 0 or x >= limit or x in gaps or x in ids[:i]:
+            return [i, ABSENT_ID]
+    return [-1, 0]
+
+
+def test_check_removal_named_cases():
+    assert check_removal(10, [], [3, 1, 9, 0]) == [-1, 0]
+    assert check_removal(10, [], []) == [-1, 0]
+    assert check_removal(10, [4], [3, 1, 3]) == [2, ABSENT_ID]        # a repeated id
+    assert check_removal(10, [4, 7], [3, 7, 1]) == [1, ABSENT_ID]     # a gap id
+    assert check_removal(10, [], [10]) == [0, ABSENT_ID]
+    assert check_removal(10, [], [0, -1]) == [1, ABSENT_ID]
+    assert check_removal(0, [], [0]) == [0, ABSENT_ID]
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_check_removal_against_model(seed):
+    rng = random.Random(500 + seed)
+    limit = rng.randrange(1, 50)
+    gaps = rng.sample(range(limit), rng.randrange(0, limit))
+    for _ in range(40):
+        ids = [rng.randrange(-1, limit + 1) if rng.random() < 0.1 else rng.randrange(limit) for _ in range(rng.randrange(0, 6))]
+        assert check_removal(limit, gaps, ids) == removal_model(limit, gaps, ids), (limit, gaps, ids)
+
+
+def better_pick(records):
+    words = []
+    for p, i in records:
+        words += [bits(p), i]
+    n, out = probe("better_pick", words, 2)
+    assert n == 2
+    return from_bits(out[0]), out[1]
+
+
+def pick_model(records):
+    """maximum priority, lowest index on ties, a NaN counts as -infinity, a negative index is no candidate"""
+    best = None
+    for p, i in records:
+        if i < 0:
+            continue
+        p = -math.inf if math.isnan(p) else p
+        if best is None or p > best[0] or (p == best[0] and i < best[1]):
+            best = (p, i)
+    return best or (0.0, -1)
+
+
+def test_better_pick_named_cases():
+    assert better_pick([]) == (0.0, -1)
+    assert better_pick([(5.0, -1), (7.0, -3), (1.0, -1)]) == (0.0, -1)             # all indices negative
+    assert better_pick([(math.nan, 4), (-1e300, 9)]) == (-1e300, 9)                # a NaN against a number, either order
+    assert better_pick([(-1e300, 9), (math.nan, 4)]) == (-1e300, 9)
+    assert better_pick([(math.nan, 4), (-math.inf, 9)]) == (-math.inf, 4)          # ... and against -infinity: the lower index
+    assert better_pick([(5.0, -1), (math.nan, 6)]) == (-math.inf, 6)               # a NaN alone still is the selection
+    assert better_pick([(math.nan, 6), (math.nan, 2)]) == (-math.inf, 2)
+    assert better_pick([(2.0, 8), (2.0, 3), (2.0, 5)]) == (2.0, 3)                 # equal priorities: the lowest index
+    assert better_pick([(1.0, 0), (3.0, 7), (2.0, 1), (9.0, -1)]) == (3.0, 7)
+    assert better_pick([(-0.0, 5), (0.0, 2)]) == (0.0, 2)
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_better_pick_against_model(seed):
+    rng = random.Random(600 + seed)
+    for _ in range(200):
+        records = [(rng.choice([math.nan, -math.inf, math.inf, 0.0, 1.5, 1.5, -2.0, rng.random()]), rng.randrange(-2, 12))
+                   for _ in range(rng.randrange(0, 9))]
+        assert better_pick(records) == pick_model(records), records
+
+
+def test_malformed_plan_scripts_are_refused():
+    assert probe("add_plan", [5, 5, 1, 9, 0, 0, 0], 32)[0] == -1            # a gap beyond the dimension
+    assert probe("add_plan", [5, 5, 2, 1, 1, 0, 0, 0], 32)[0] == -1         # a gap listed twice
+    assert probe("add_plan", [5, 5, 0, 0, 1, bits(1.0), 0], 4)[0] == -1     # output too small
+    assert probe("compact_plan", [5, 5, 0, 0, 0], 32)[0] == -1              # words left over
+    assert probe("compact_plan", [5, 5, 3, 1], 32)[0] == -1                 # the list is cut short
+    assert probe("check_removal", [5, 0, 1, 2], 1)[0] == -1
+    assert probe("better_pick", [bits(1.0)], 2)[0] == -1
