@@ -228,6 +228,32 @@ PQACORE_API void *PqaHip_GetPriorDevicePtr(void *pvEngine, const int64_t iQuiz, 
 /* RecordAnswer on a shard that does not own the active question: bookkeeping only; the owner's prior is expected to be
  * broadcast into PqaHip_GetPriorDevicePtr's buffer by the caller. */
 PQACORE_API void *PqaHip_RecordAnswerRemote(void *pvEngine, const int64_t iQuiz, const int64_t iAnswer);
+/* ---- ResumeQuiz on shards that separate processes drive (PqaEngineFactory_CreateHipEngineSharded, one per GPU): the two rows
+ * of every answered question reach the ranks that do not hold it as a ROW PACKAGE.  A package for n answered questions is n
+ * slots of PqaHip_AnswerRowSlotBytes bytes (2 * ldT elements of the engine's own type, 8 bytes for Double engines and 4 for
+ * Float; a multiple of 16): slot i = sA[q_i][k_i][0..ldT) followed by mD[q_i][0..ldT), exactly as they lie in the owner's cube,
+ * padding included.  A package is a snapshot: it is valid while no rank trains between packing and resuming. */
+PQACORE_API int64_t PqaHip_AnswerRowSlotBytes(void *pvEngine);
+/* Stream-ordered on the engine's stream, no host synchronisation: for every i < nAnswered whose question THIS engine holds,
+ * its two rows are copied into slot i of pDst -- any device-visible address, 16-byte aligned: device memory, or registered host
+ * memory (PqaHip_HostRegister), as for PqaHip_EnqueueSelectArgmaxFlag.  Other slots are not touched, so several shards fill one
+ * (zero-initialised) buffer.  Question ids are GLOBAL; an id out of [0, nQuestions of the whole KB) or an answer out of
+ * [0, nAnswers) is IndexOutOfRange, and nothing is launched.  pFlag != NULL: flagValue is stored there once every row is visible
+ * system-wide (also when this engine holds none of the questions); a reader in another process may poll it.  One launch for
+ * all rows, a workgroup per 16 KB of a row; a training enqueued before the call is ordered in front of it by the stream. */
+PQACORE_API void *PqaHip_PackAnswerRows(void *pvEngine, const int64_t nAnswered, const CiAnsweredQuestion *pAQs, void *pDst,
+                                        void *pFlag, const uint64_t flagValue);
+/* PqaEngine_ResumeQuiz / PqaEngine_ResumeQuizBatch in everything -- validation, the asked bits of the LOCAL questions,
+ * I64Underflow, all or none for the batch, the ids, no speculative sweep behind the batch -- except where the rows come from:
+ * those of answered question i are read from slot i of pRows when this engine does not hold the question, from its own cube when
+ * it does (such slots may be left unfilled).  For the batch the slots count through all its answered questions, in entry order.
+ * pRows: device-visible memory, valid until the call returns; both calls synchronise.  A package in registered host memory is
+ * copied to the device first (option "rows_stage", default 1; 0 = read in place).  Concurrent calls take the engine one after the
+ * other.  PqaEngine_ResumeQuiz itself keeps answering NotImplemented for a question another process's shard holds. */
+PQACORE_API int64_t PqaEngine_ResumeQuizFromRows(void *pvEngine, void **ppError, const int64_t nAnswered,
+                                                 const CiAnsweredQuestion *pAQs, const void *pRows);
+PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts,
+                                                    const CiAnsweredQuestion *pAQs, const void *pRows, int64_t *pQuizzes);
 
 /* Host bookkeeping of the engine that needs no device, driven by a small script so that it is testable where there is no GPU.
    what = "id_ledger": pIn is a sequence of operations on one fresh compact<->permanent id map (reference behaviour:

@@ -495,6 +495,30 @@ PQACORE_API void *PqaHip_EnqueueSelectArgmaxFlag(void *pvEngine, const int64_t i
   ENGINE_OR_RETURN_ERROR;
   return ReturnErr(pEng->EnqueueSelectArgmaxFlag(iQuiz, pOut, pFlag, flagValue));
 }
+// ---- ResumeQuiz on shards driven by processes of their own: the owners pack the answered questions' rows, every rank resumes
+// from the exchanged package (hip_engine_resume.cpp)
+PQACORE_API int64_t PqaHip_AnswerRowSlotBytes(void *pvEngine) {
+  ENGINE_OR_LOG(-1);
+  return pEng->AnswerRowSlotBytes();
+}
+PQACORE_API void *PqaHip_PackAnswerRows(void *pvEngine, const int64_t nAnswered, const CiAnsweredQuestion *pAQs, void *pDst, void *pFlag,
+                                        const uint64_t flagValue) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(pEng->PackAnswerRows(nAnswered, reinterpret_cast<const AQ *>(pAQs), pDst, pFlag, flagValue));
+}
+PQACORE_API int64_t PqaEngine_ResumeQuizFromRows(void *pvEngine, void **ppError, const int64_t nAnswered, const CiAnsweredQuestion *pAQs,
+                                                 const void *pRows) {
+  ENGINE_OR_SET_ERROR(-1);
+  Error err;
+  const int64_t id = pEng->ResumeQuizFromRows(err, nAnswered, reinterpret_cast<const AQ *>(pAQs), pRows);
+  AssignErr(ppError, err);
+  return id;
+}
+PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts, const CiAnsweredQuestion *pAQs,
+                                                    const void *pRows, int64_t *pQuizzes) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(pEng->ResumeQuizBatchFromRows(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pRows, pQuizzes));
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   if (!pHost || !ppDevice || nBytes <= 0) return ReturnErr(Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_HostRegister."));

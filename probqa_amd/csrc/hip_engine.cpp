@@ -285,6 +285,9 @@ HipEngine::~HipEngine() {
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   if (_hTopBatch) hipHostFree(_hTopBatch);
   hipFree(_dTopExact);
+  hipFree(_dRowStage);
+  if (_hPack) hipHostFree(_hPack);
+  if (_evPack) hipEventDestroy(_evPack);
   if (_evSweep[0]) { hipEventDestroy(_evSweep[0]); hipEventDestroy(_evSweep[1]); }
   if (_hPinned) hipHostFree(_hPinned);
   if (_hHostPriority) hipHostFree(_hHostPriority);
@@ -337,6 +340,7 @@ Error HipEngine::SetOption(const char *name, int64_t value) {
   else if (n == "pole_lazy") { StopServer(); (void)SettlePoleList(); _optPoleLazy = value ? 1 : 0; }
   else if (n == "pole_follow") { StopServer(); (void)SettlePoleList(); _optPoleFollow = value ? 1 : 0; }   // measurement hook: 0 = the watching sweeps without the fix launched behind them (KbView::poleNoFollow)
   else if (n == "long_row_form") { _optLongRowForm = value ? 1 : 0; }   // 0: the one-workgroup posterior kernels for rows beyond 16384 targets too
+  else if (n == "rows_stage") { _optRowsStage = value ? 1 : 0; }   // ResumeQuizFromRows: a package in host memory copied to the device first (1) or read in place (0)
   else if (n == "fuse_update") { _optFuseUpdate = value ? 1 : 0; }   // RecordAnswer's posterior update inside the speculative sweep's launch
   else if (n == "post_always") { _optPostAlways = value ? 1 : 0; }   // test hook: RecordAnswer / ListTopTargets always as posted operations
   else if (n == "combine_linger_us") { if (value < 0 || value > 10000) goto bad; _optLingerUs = value; }
@@ -419,7 +423,11 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "posted_drains") return (int64_t)_postedDrains;
   if (n == "train_batches") return (int64_t)_trainBatches;           // launches that ran posted RecordQuizTarget calls together ...
   if (n == "train_batch_calls") return (int64_t)_trainBatchCalls;    // ... this many of them           // ... in this many rounds
-  if (n == "resume_batches") return (int64_t)_resumeBatches;         // launch sequences that ran posted ResumeQuiz calls together ...
+  if (n == "rows_stage") return _optRowsStage;
+  if (n == "pack_calls") return (int64_t)_packCalls;                 // PackAnswerRows launches ...
+  if (n == "pack_bytes") return (int64_t)_packBytes;                 // ... and the bytes they were asked to move
+  if (n == "rows_staged") return (int64_t)_rowsStaged;               // host packages copied to the device before they were read
+  if (n == "resume_batches") return (int64_t)_resumeBatches;        // launch sequences that ran posted ResumeQuiz calls together ...
   if (n == "resumes_batched") return (int64_t)_resumesBatched;       // ... this many of them
   if (n == "train_chunk_steps") return _optTrainChunkSteps;
   if (n == "train_bulk_calls") return (int64_t)_trainBulkCalls;       // TrainBatch / RecordQuizTargetBatch calls that trained ...

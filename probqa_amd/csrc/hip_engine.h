@@ -241,6 +241,10 @@ class IEngine {
   virtual Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) = 0;
   virtual Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) = 0;
   virtual Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) = 0;
+  virtual int64_t AnswerRowSlotBytes() const = 0;
+  virtual Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) = 0;
+  virtual int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) = 0;
+  virtual Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) = 0;
 };
 
 class HipEngine : public IEngine {
@@ -312,6 +316,12 @@ class HipEngine : public IEngine {
   Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) override;
   Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) override;
   Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
+  // ---- a shard driven by a process of its own (hip_engine_resume.cpp): the rows of answered questions as a package -- slot i
+  // = sA[q_i][k_i][0..ldT) then mD[q_i][0..ldT), in the cube's element type -- filled by the owners, consumed by every rank
+  int64_t AnswerRowSlotBytes() const override { return 2 * _ldT * (int64_t)_elem; }
+  Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) override;
+  int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) override;
+  Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
   // An answer of a quiz as the sharded engine hands it to EVERY shard: the answered question in global numbering; for the shards
@@ -409,6 +419,16 @@ class HipEngine : public IEngine {
   // allOrNone: any failing entry fails the call and no quiz is created (the entry's own error is in e[i].err); otherwise every
   // entry succeeds or fails on its own.  The ids are assigned in entry order once every launch has been checked.
   Error ResumeEntriesLocked(std::vector<ResumeEntry> &e, bool allOrNone);
+  Error ResumeBatchEntriesLocked(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *const *rows, int64_t *pQuizzes);
+  // a package's slots as row pointers (this engine's own questions: its cube); a package in host memory staged by option "rows_stage"
+  Error PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pRows, std::vector<const void *> &rows);
+  int64_t *_hPack = nullptr;           // PackAnswerRows: the pinned source of its pointer list, and the event behind the list's copy
+  int64_t _hPackWords = 0;
+  hipEvent_t _evPack = nullptr;
+  char *_dRowStage = nullptr;          // ResumeQuizFromRows: where a host package is copied first
+  size_t _rowStageBytes = 0;
+  int64_t _optRowsStage = 1;           // option "rows_stage": 1 = a package in host memory is copied to the device before it is read, 0 = read in place
+  uint64_t _packCalls = 0, _packBytes = 0, _rowsStaged = 0;   // read-only "pack_calls", "pack_bytes", "rows_staged"
   hipError_t TakeQuizBuffers(Quiz *q);
   // the batch's device tables -- slots, statuses, asked bitmaps, row pointers, long-row sums, exponent scratch -- and their
   // pinned host mirror: grown to the largest chunk so far, reused by every batch after it

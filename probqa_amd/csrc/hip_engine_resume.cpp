@@ -241,14 +241,20 @@ Error HipEngine::ResumeQuizBatchRows(int64_t n, const int64_t *pCounts, const AQ
       if (he != hipSuccess) { hipStreamSynchronize(_stream); hipFree(stage); return HipErr(he, "staging another device's rows for ResumeQuizBatch"); }
     }
   }
+  const Error err = ResumeBatchEntriesLocked(n, pCounts, pAQs, local.data(), pQuizzes);
+  if (stage) { hipStreamSynchronize(_stream); hipFree(stage); }
+  return err;
+}
+
+// A batch whose row pointers are resolved (2 sum(pCounts) of them, in entry order): all or none, the error names its entry
+Error HipEngine::ResumeBatchEntriesLocked(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *const *rows, int64_t *pQuizzes) {
   std::vector<ResumeEntry> e((size_t)n);
   for (int64_t i = 0, at = 0; i < n; at += pCounts[i], i++) {
     e[(size_t)i].nAnswered = pCounts[i];
     e[(size_t)i].pAQs = pAQs + at;
-    e[(size_t)i].rows = local.data() + 2 * at;
+    e[(size_t)i].rows = rows + 2 * at;
   }
   Error err = ResumeEntriesLocked(e, true);
-  if (stage) { hipStreamSynchronize(_stream); hipFree(stage); }
   for (int64_t i = 0; i < n; i++)
     if (!e[(size_t)i].err.ok()) {
       err = e[(size_t)i].err;
@@ -258,6 +264,163 @@ Error HipEngine::ResumeQuizBatchRows(int64_t n, const int64_t *pCounts, const AQ
   if (!err.ok()) return err;
   for (int64_t i = 0; i < n; i++) pQuizzes[i] = e[(size_t)i].id;
   return Error();
+}
+
+// ---- ResumeQuiz on a shard that is driven by a process of its own (probqa_amd/dist.py): the rows of answered questions other
+// ranks hold arrive as a package -- slot i = the two rows of answered question i as they lie in the owner's cube -- that the
+// owners fill with PackAnswerRows and the ranks exchange.  Resuming from it is the row-pointer path of the sharded engine
+// (CreateQuiz / ResumeEntriesLocked with `rows`), its pointers aimed at the package's slots.
+
+// One launch (kb_kernels.hip: pack_answer_rows_kernel) behind one copy of the pointer list; nothing here waits for the device,
+// except that the pinned list is not rewritten while an earlier call's copy of it is still under way.
+Error HipEngine::PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "|nAnswered| must be non-negative.");
+  if (n > 0 && (!pAQs || !pDst)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of answered questions or the package.");
+  std::lock_guard<EngineMutex> lk(_mu);
+  Error err = CheckRegular("pack answer rows");
+  if (!err.ok()) return err;
+  for (int64_t i = 0; i < n; i++) {   // (everything is checked before anything is launched)
+    const int64_t iq = pAQs[i].iQuestion, ia = pAQs[i].iAnswer;
+    if (iq < 0 || iq >= _qTotal) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(iq, 0, _qTotal - 1), "Question index is not in KB range.");
+    if (ia < 0 || ia >= _K) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(ia, 0, _K - 1), "Answer index is not in KB range.");
+  }
+  int64_t m = 0;
+  for (int64_t i = 0; i < n; i++) m += OwnsQuestion(pAQs[i].iQuestion) ? 1 : 0;
+  if (m == 0 && pFlag == nullptr) return Error();
+  hipSetDevice(_device);
+  if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
+  // the list: {arrival counter, pad} and then a PackPair per row pair of this engine's questions
+  static_assert(sizeof(PackPair) == 3 * sizeof(int64_t), "the pairs travel in the answered-question buffer");
+  const int64_t words = 2 + 3 * m;
+  if (words > 2 * _aqCapacity) {
+    hipFree(_dAqs);   // (waits for whatever still reads it)
+    _dAqs = nullptr;
+    _aqCapacity = 0;
+    const int64_t cap = std::max<int64_t>((words + 1) / 2, 64);
+    HIP_TRY(hipMalloc(&_dAqs, (size_t)cap * 2 * sizeof(int64_t)));
+    _aqCapacity = cap;
+  }
+  if (_evPack == nullptr) HIP_TRY(hipEventCreateWithFlags(&_evPack, hipEventDisableTiming));
+  else HIP_TRY(hipEventSynchronize(_evPack));
+  if (words > _hPackWords) {
+    hipHostFree(_hPack);
+    _hPack = nullptr;
+    _hPackWords = 0;
+    const int64_t cap = std::max<int64_t>(words, 128);
+    HIP_TRY(hipHostMalloc((void **)&_hPack, (size_t)cap * sizeof(int64_t), hipHostMallocDefault));
+    _hPackWords = cap;
+  }
+  _hPack[0] = _hPack[1] = 0;
+  PackPair *pairs = reinterpret_cast<PackPair *>(_hPack + 2);
+  const size_t slotBytes = (size_t)AnswerRowSlotBytes();
+  for (int64_t i = 0, at = 0; i < n; i++) {
+    if (!OwnsQuestion(pAQs[i].iQuestion)) continue;
+    pairs[at++] = PackPair{CubeAt(pAQs[i].iQuestion - _qFirst, pAQs[i].iAnswer), CubeAt(pAQs[i].iQuestion - _qFirst, _K),
+                           static_cast<char *>(pDst) + (size_t)i * slotBytes};
+  }
+  MarkStreamBusy();
+  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
+  HIP_TRY(hipEventRecord(_evPack, _stream));
+  HIP_TRY(LaunchPackAnswerRows(reinterpret_cast<const PackPair *>(_dAqs + 2), m, (int64_t)(slotBytes / 2), reinterpret_cast<unsigned *>(_dAqs),
+                               static_cast<uint64_t *>(pFlag), flagValue, _stream));
+  _packCalls++;
+  _packBytes += (uint64_t)m * slotBytes;
+  return Error();
+}
+
+// The 2 `total` row pointers of a package's slots; a package in host memory (registered, as PqaHip_HostRegister leaves it) is
+// first copied into the engine's own device scratch when option "rows_stage" says so: `base` then points there.
+Error HipEngine::PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pRows, std::vector<const void *> &rows) {
+  rows.assign(2 * (size_t)total, nullptr);
+  bool anyForeign = false;
+  for (int64_t i = 0; i < total; i++) anyForeign = anyForeign || !OwnsQuestion(pAQs[i].iQuestion);
+  if (anyForeign && pRows == nullptr) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the row package.");
+  const size_t slotBytes = (size_t)AnswerRowSlotBytes();
+  const char *base = static_cast<const char *>(pRows);
+  if (anyForeign && _optRowsStage) {
+    hipSetDevice(_device);
+    hipPointerAttribute_t at;
+    const hipError_t q = hipPointerGetAttributes(&at, pRows);
+    if (q != hipSuccess) (void)hipGetLastError();
+    if (q == hipSuccess && at.type == hipMemoryTypeHost) {
+      const size_t bytes = (size_t)total * slotBytes;
+      if (bytes > _rowStageBytes) {
+        hipFree(_dRowStage);   // (every call that used it has synchronised)
+        _dRowStage = nullptr;
+        _rowStageBytes = 0;
+        HIP_TRY(hipMalloc((void **)&_dRowStage, bytes));
+        _rowStageBytes = bytes;
+      }
+      // one copy per run of slots of other engines' questions: this engine's own slots may be unfilled and are not read
+      for (int64_t i = 0; i < total;) {
+        if (OwnsQuestion(pAQs[i].iQuestion)) { i++; continue; }
+        int64_t j = i + 1;
+        while (j < total && !OwnsQuestion(pAQs[j].iQuestion)) j++;
+        HIP_TRY(hipMemcpyAsync(_dRowStage + (size_t)i * slotBytes, base + (size_t)i * slotBytes, (size_t)(j - i) * slotBytes, hipMemcpyDefault, _stream));
+        i = j;
+      }
+      base = _dRowStage;
+      _rowsStaged++;
+    }
+  }
+  for (int64_t i = 0; i < total; i++) {
+    if (OwnsQuestion(pAQs[i].iQuestion)) {
+      const bool valid = pAQs[i].iAnswer >= 0 && pAQs[i].iAnswer < _K;   // (an answer out of range is refused further down, before any row is read)
+      rows[2 * (size_t)i] = CubeAt(pAQs[i].iQuestion - _qFirst, valid ? pAQs[i].iAnswer : 0);
+      rows[2 * (size_t)i + 1] = CubeAt(pAQs[i].iQuestion - _qFirst, _K);
+    } else {
+      rows[2 * (size_t)i] = base + (size_t)i * slotBytes;
+      rows[2 * (size_t)i + 1] = base + (size_t)i * slotBytes + slotBytes / 2;
+    }
+  }
+  return Error();
+}
+
+int64_t HipEngine::ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) {
+  if (nAnswered < 0) {  // reference PqaCore/BaseEngine.cpp:388-392
+    err = Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(nAnswered), "|nAnswered| must be non-negative.");
+    return -1;
+  }
+  if (nAnswered > 0 && pAQs == nullptr) {
+    err = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of answered questions.");
+    return -1;
+  }
+  CallScope scope(_activeCallers);
+  std::lock_guard<EngineMutex> lk(_mu);   // (not a posted operation: concurrent calls take the engine one after the other)
+  std::vector<const void *> rows;
+  err = PackageRowsLocked(nAnswered, pAQs, pRows, rows);
+  if (!err.ok()) return -1;
+  if (nAnswered > 0 && ResumeTakesLongRow(View())) {   // long rows: the multi-workgroup form, as a batch of one
+    std::vector<ResumeEntry> e(1);
+    e[0].nAnswered = nAnswered;
+    e[0].pAQs = pAQs;
+    e[0].rows = rows.data();
+    err = ResumeEntriesLocked(e, true);
+    if (!e[0].err.ok()) err = e[0].err;
+    return SpeculateFor(err.ok() ? e[0].id : -1);
+  }
+  return SpeculateFor(CreateQuiz(err, nAnswered, pAQs, nAnswered > 0 ? rows.data() : nullptr, nullptr, 0, nullptr));
+}
+
+Error HipEngine::ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "|nQuizzes| must be non-negative.");
+  if (n > 0 && (!pCounts || !pQuizzes)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (pCounts[i] < 0)   // reference PqaCore/BaseEngine.cpp:388-392
+      return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(pCounts[i]),
+                          "Batch entry " + std::to_string(i) + ": |nAnswered| must be non-negative.");
+    total += pCounts[i];
+  }
+  if (total > 0 && pAQs == nullptr) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of answered questions.");
+  for (int64_t i = 0; i < n; i++) pQuizzes[i] = -1;
+  CallScope scope(_activeCallers);
+  std::lock_guard<EngineMutex> lk(_mu);
+  std::vector<const void *> rows;
+  const Error err = PackageRowsLocked(total, pAQs, pRows, rows);
+  if (!err.ok()) return err;
+  if (total == 0) rows.assign(1, nullptr);   // (a batch of StartQuiz entries: the pointer list is never read)
+  return ResumeBatchEntriesLocked(n, pCounts, pAQs, rows.data(), pQuizzes);
 }
 
 }  // namespace pqa

@@ -286,7 +286,50 @@ __global__ __launch_bounds__(256) void adopt_vb_kernel(double *__restrict__ dst,
     if (colMap[t] >= 0) dst[t] = src[colMap[t]];
 }
 
+// PqaHip_PackAnswerRows: workgroup (row, chunk) copies kPackChunkBytes of one row -- row 2 i the sA row of pair i, row 2 i + 1 its mD
+// row, which lands rowUnits 16-byte units behind it -- as 16-byte loads, all of a thread's requested before its first store.  The
+// bytes travel as they are: no element is looked at, so Float and Double cubes take the same kernel.  With a flag, every workgroup
+// makes its stores visible system-wide and counts itself in; the last one to arrive publishes flagValue (the finisher of the sweeps).
+// Workgroups past `nWork` (a package without a row of this engine: one workgroup) only do that.
+__global__ __launch_bounds__(256) void pack_answer_rows_kernel(const PackPair *__restrict__ pairs, int64_t nWork, int64_t rowUnits, int64_t chunksPerRow,
+                                                               unsigned *counter, uint64_t *flag, uint64_t flagValue) {
+  constexpr int kPer = (int)(kPackChunkBytes / 16 / 256);
+  if ((int64_t)blockIdx.x < nWork) {
+    const int64_t row = blockIdx.x / chunksPerRow, chunk = blockIdx.x % chunksPerRow;
+    const PackPair p = pairs[row >> 1];
+    const uint4 *src = static_cast<const uint4 *>((row & 1) ? p.rowD : p.rowA);
+    uint4 *dst = static_cast<uint4 *>(p.dst) + (row & 1) * rowUnits;
+    const int64_t u0 = chunk * (kPer * 256) + threadIdx.x;
+    uint4 v[kPer];
+#pragma unroll
+    for (int e = 0; e < kPer; e++)
+      if (u0 + e * 256 < rowUnits) v[e] = src[u0 + e * 256];
+#pragma unroll
+    for (int e = 0; e < kPer; e++)
+      if (u0 + e * 256 < rowUnits) dst[u0 + e * 256] = v[e];
+  }
+  if (flag == nullptr) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: this thread's part of the rows before the count
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) != gridDim.x - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 }  // namespace
+
+hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowBytes, unsigned *counter, uint64_t *flag, uint64_t flagValue,
+                                hipStream_t stream) {
+  if (n < 0 || rowBytes <= 0 || rowBytes % 16 != 0 || (flag != nullptr && counter == nullptr)) return hipErrorInvalidValue;
+  if (n == 0 && flag == nullptr) return hipSuccess;
+  const int64_t rowUnits = rowBytes / 16, chunksPerRow = (rowBytes + kPackChunkBytes - 1) / kPackChunkBytes;   // (a short row: one workgroup)
+  const int64_t nWork = 2 * n * chunksPerRow;
+  if (nWork > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pack_answer_rows_kernel, dim3((unsigned)std::max<int64_t>(nWork, 1)), dim3(256), 0, stream, pairs, nWork, rowUnits, chunksPerRow,
+                     counter, flag, flagValue);
+  return hipGetLastError();
+}
 
 hipError_t LaunchAdoptRows(void *dst, int elem, double *dstVB, int64_t K, int64_t nQ, int64_t Tn, int64_t ldTn, const void *const *src,
                            int64_t ldTs, const double *srcVB, const int64_t *colMap, hipStream_t stream) {

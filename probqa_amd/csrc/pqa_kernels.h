@@ -452,6 +452,15 @@ hipError_t LaunchAdoptRows(void *dst, int elem, double *dstVB, int64_t K, int64_
                            int64_t ldTs, const double *srcVB, const int64_t *colMap, hipStream_t stream);
 hipError_t LaunchMoveTargets(void *cube, int elem, double *vB, int64_t K, int64_t ldT, int64_t nQ, const int64_t *moves,
                              int64_t n, hipStream_t stream);
+// The rows of answered questions packed for another engine (PqaHip_PackAnswerRows): pair i of `pairs` (device memory) is copied as
+// it lies -- rowBytes of sA[q][k][.] and then rowBytes of mD[q][.], padding included -- to pair i's dst, which may be any
+// device-visible address.  rowBytes: a multiple of 16, every address 16-byte aligned.  One launch: a workgroup per (row, chunk of
+// kPackChunkBytes).  flag != nullptr: `counter` (device memory, zero at launch) counts the workgroups in, and the last one stores
+// flagValue to flag once every row is visible system-wide; n == 0 then launches that store alone.
+struct PackPair { const void *rowA, *rowD; void *dst; };
+constexpr int64_t kPackChunkBytes = 16384;
+hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowBytes, unsigned *counter, uint64_t *flag, uint64_t flagValue,
+                                hipStream_t stream);
 // ListTopTargets (PqaCore/CEListTopTargetsAlgorithm.cpp): top maxCount (prob,target) pairs, descending, gaps skipped.
 // (flag != nullptr: out / nOut / flag are host-coherent; the kernel stores flagValue to *flag after its results)
 hipError_t LaunchTopTargets(const KbView &kb, const double *prior, int64_t maxCount, RatedTargetDev *out,

@@ -200,6 +200,13 @@ class ShardedEngine final : public IEngine {
     return _sh[0]->GetPriorDevicePtr(iQuiz, ppDev, pLdT);
   }
   Error RecordAnswerRemote(int64_t, int64_t) override { return NotSharded("RecordAnswerRemote"); }
+  // (row packages serve shards driven by processes of their own; this engine holds every question, so a package has nothing to add)
+  int64_t AnswerRowSlotBytes() const override { return _sh[0]->AnswerRowSlotBytes(); }
+  Error PackAnswerRows(int64_t, const AQ *, void *, void *, uint64_t) override { return NotSharded("PackAnswerRows"); }
+  int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *) override { return ResumeQuiz(err, nAnswered, pAQs); }
+  Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *, int64_t *pQuizzes) override {
+    return ResumeQuizBatch(n, pCounts, pAQs, pQuizzes);
+  }
   Error RecordAnswerBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers) override {   // (gathered like any other answers: one hand-over to the shards)
     if (n > 0 && (!pQuizzes || !pAnswers)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
     for (int64_t i = 0; i < n; i++) { Error e = RecordAnswerDeferred(pQuizzes[i], pAnswers[i]); if (!e.ok()) return e; }

@@ -278,6 +278,251 @@ def owner_of(question: int, n_questions: int, world_size: int) -> int:
     raise IndexError(question)
 
 
+def _question_of(answered) -> int:
+    q = getattr(answered, "i_question", None)
+    return int(answered[0]) if q is None else int(q)
+
+
+def row_owners(answered, n_questions: int, world: int) -> List[int]:
+    """The rank that holds the two rows of each answered question (AnsweredQuestion objects or (question, answer) pairs, GLOBAL
+    ids): `owner_of` over `shard_bounds`.  IndexError for an id outside [0, n_questions)."""
+    import bisect
+
+    bounds = shard_bounds(n_questions, world)
+    owners = []
+    for a in answered:
+        q = _question_of(a)
+        if q < 0 or q >= n_questions:
+            raise IndexError(q)
+        owners.append(bisect.bisect_right(bounds, q))
+    return owners
+
+
+# ---- ResumeQuiz in the process-per-GPU form ------------------------------------------------------------------------------
+# A quiz is resumed from the rows of its answered questions (PqaCore/CECreateQuizOperation.cpp:55-83), and those lie on whichever
+# rank holds the question.  The owners copy them into a ROW PACKAGE (PqaHip_PackAnswerRows: slot i = the sA and the mD row of
+# answered question i, as they lie in the owner's cube), the ranks combine their packages, and every rank resumes from the
+# combined one (PqaEngine_ResumeQuizFromRows).  A package is a snapshot of the cube: it is valid only while no rank trains
+# between pack and resume.  The helpers below run both back to back and promise nothing beyond that.
+
+
+def _package(engine, n_slots: int, device: torch.device) -> torch.Tensor:
+    """A zero-filled package of n_slots slots in the engine's element type: [n_slots, 2 * ldT]."""
+    slot = engine.answer_row_slot_bytes()
+    ld = engine.get_option("ldT")
+    elem = slot // (2 * ld)
+    if elem not in (4, 8) or 2 * ld * elem != slot:
+        raise ValueError("unexpected slot size %d for rows of %d elements" % (slot, ld))
+    return torch.zeros(max(n_slots, 1), 2 * ld, dtype=torch.float64 if elem == 8 else torch.float32, device=device)
+
+
+def _combined_package(engine, flat, device: torch.device, group):
+    """-> (the combined package, this rank's error text or None).  A rank whose pack is refused still takes part in the
+    collective, so that the ranks stay in step; the status word that follows fails the call everywhere."""
+    from . import interop
+
+    pkg = _package(engine, len(flat), device)
+    on_gpu = device.type == "cuda"
+    if on_gpu:
+        torch.cuda.current_stream(device).synchronize()   # the zeros are there before the engine's stream writes among them
+    error = None
+    try:
+        engine.pack_answer_rows(flat, pkg.data_ptr())
+    except interop.PqaException as e:
+        error = str(e)
+    engine.synchronize()                                  # ... and the rows before the collective's stream (or the host) reads them
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        if on_gpu and dist.get_backend(group) != "nccl":   # gloo: through the host
+            host = pkg.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+            pkg.copy_(host)
+        else:
+            dist.all_reduce(pkg, op=dist.ReduceOp.SUM, group=group)
+        if on_gpu:
+            torch.cuda.current_stream(device).synchronize()
+    return pkg, error
+
+
+def _settle(engine, quizzes: List[int], error: Optional[str], rank: int, world: int, device: torch.device, group) -> None:
+    """One status word between the ranks: all succeeded, or the quizzes of those that did are released again and every rank
+    raises the same PqaException (the first failing rank's)."""
+    from . import interop
+
+    if not (dist.is_initialized() and dist.get_world_size(group) > 1):
+        if error is not None:
+            raise interop.PqaException(error)
+        return
+    on_dev = device.type == "cuda" and dist.get_backend(group) == "nccl"
+    word = torch.tensor([rank if error is not None else world], dtype=torch.int64, device=device if on_dev else "cpu")
+    dist.all_reduce(word, op=dist.ReduceOp.MIN, group=group)
+    first = int(word.item())
+    if first >= world:
+        return
+    if error is None:
+        for q in quizzes:
+            engine.release_quiz(q)
+    text = [error if rank == first else None]
+    dist.broadcast_object_list(text, src=dist.get_global_rank(group, first) if group is not None else first, group=group,
+                               device=device if on_dev else None)
+    raise interop.PqaException("rank %d: %s" % (first, text[0]))
+
+
+def resume_quiz(engine, answered, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                device: Optional[torch.device] = None) -> int:
+    """ResumeQuiz on the shards of `world` ranks: a collective every rank calls with the same list of AnsweredQuestion (GLOBAL
+    question ids).  Returns the quiz id, the same on every rank whose engines have created and released the same quizzes.
+
+    Each rank packs the rows it holds into a zero-filled torch tensor on its device, the packages are combined by ONE
+    all_reduce(SUM) in the engine's element type -- exact, and a move of bits: every slot is written by exactly one rank, every
+    count and every padding element of the cube is finite (0 behind the sA rows, 1 behind the mD rows), and x + 0 == x -- and
+    every rank resumes from the combined package.  Under an NCCL (RCCL) group the tensors stay on the device, under gloo they go
+    through the host.  All or none: if any rank fails, the others release their quiz and all raise the first failure.
+    The package is a snapshot of the cube: no rank may train between the pack and the resume inside this call."""
+    from . import interop
+
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    answered = list(answered)
+    quiz = -1
+    pkg, error = _combined_package(engine, answered, device, group)
+    if error is None:
+        try:
+            quiz = engine.resume_quiz_from_rows(answered, pkg.data_ptr())
+        except interop.PqaException as e:
+            error = str(e)
+    _settle(engine, [quiz], error, rank, world, device, group)
+    return quiz
+
+
+def resume_quiz_batch(engine, lists, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                      device: Optional[torch.device] = None) -> List[int]:
+    """resume_quiz for many lists at once (PqaEngine_ResumeQuizBatchFromRows): one package whose slots count through all the
+    lists' answered questions, one all_reduce, one batched resume per rank; all or none over the ranks as over the entries."""
+    from . import interop
+
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    lists = [list(l) for l in lists]
+    flat = [aq for l in lists for aq in l]
+    quizzes = []
+    pkg, error = _combined_package(engine, flat, device, group)
+    if error is None:
+        try:
+            quizzes = engine.resume_quiz_batch_from_rows(lists, pkg.data_ptr())
+        except interop.PqaException as e:
+            error = str(e)
+    _settle(engine, quizzes, error, rank, world, device, group)
+    return quizzes
+
+
+class ShmRowExchange:
+    """resume_quiz / resume_quiz_batch without a process group, for the shared-memory deployments that use ShmSelector: the
+    package lives in ONE /dev/shm segment every rank has mapped and registered with its GPU.  The owners pack straight into it
+    with the flag form of PqaHip_PackAnswerRows, every rank waits (bounded) for all `world` flags to carry the step number and
+    resumes from the segment's device-visible address; a status word per rank, written by the host, then makes the call all or
+    none as the collective is.  Two halves alternate by step parity, as ShmSelector's slot sets do.  The segment (`size_for`
+    bytes, zero-filled) is created by the caller before the ranks open it.  No rank may train between pack and resume."""
+
+    LINE = 64
+
+    @classmethod
+    def size_for(cls, world: int, slot_bytes: int, max_slots: int) -> int:
+        return 2 * (2 * world * cls.LINE + max_slots * slot_bytes)
+
+    def __init__(self, rank: int, world: int, name: str, slot_bytes: int, max_slots: int):
+        import ctypes
+        import mmap
+        import os
+
+        import numpy as np
+
+        from . import interop
+
+        self.rank, self.world, self.slot_bytes, self.max_slots = rank, world, slot_bytes, max_slots
+        self.path = "/dev/shm/pqa_rows_%s" % name
+        self._half = 2 * world * self.LINE + max_slots * slot_bytes
+        size = self.size_for(world, slot_bytes, max_slots)
+        fd = os.open(self.path, os.O_RDWR)
+        try:
+            if os.fstat(fd).st_size < size:
+                raise ValueError("%s is smaller than the %d bytes the exchange needs" % (self.path, size))
+            self._map = mmap.mmap(fd, size)
+        finally:
+            os.close(fd)
+        self._host = ctypes.addressof(ctypes.c_char.from_buffer(self._map))
+        self._dev = interop.host_register(self._host, size)
+        self._words = np.frombuffer(self._map, dtype=np.uint64)
+        self._interop = interop
+        self.step = 0
+
+    def _word(self, half: int, kind: int, r: int) -> int:
+        """Index (in 8-byte words) of rank r's flag (kind 0) or status (kind 1) of a half."""
+        return (half * self._half + (kind * self.world + r) * self.LINE) // 8
+
+    def _wait(self, half: int, kind: int, timeout_s: float):
+        import time
+
+        t0 = time.perf_counter()
+        seen = []
+        for r in range(self.world):
+            i = self._word(half, kind, r)
+            while (int(self._words[i]) >> kind) != self.step:
+                if time.perf_counter() - t0 > timeout_s:
+                    raise TimeoutError("rank %d never published %s %d" % (r, "status" if kind else "rows of step", self.step))
+            seen.append(int(self._words[i]))
+        return seen
+
+    def _run(self, engine, flat, resume, release, timeout_s: float):
+        if len(flat) > self.max_slots:
+            raise ValueError("%d answered questions, the segment holds %d" % (len(flat), self.max_slots))
+        self.step += 1
+        half = self.step & 1
+        rows = half * self._half + 2 * self.world * self.LINE
+        result, error = None, None
+        try:
+            engine.pack_answer_rows(flat, self._dev + rows, self._dev + 8 * self._word(half, 0, self.rank), self.step)
+        except self._interop.PqaException as e:   # (the others must not wait for rows that never come: the status fails the call)
+            error = str(e)
+            self._words[self._word(half, 0, self.rank)] = self.step
+        self._wait(half, 0, timeout_s)
+        if error is None:
+            try:
+                result = resume(self._dev + rows)
+            except self._interop.PqaException as e:
+                error = str(e)
+        self._words[self._word(half, 1, self.rank)] = 2 * self.step + (1 if error is not None else 0)
+        status = self._wait(half, 1, timeout_s)
+        failed = [r for r in range(self.world) if status[r] & 1]
+        if failed:
+            if error is None:
+                release(result)
+            raise self._interop.PqaException("ResumeQuiz failed on rank%s %s%s" % ("s" if len(failed) > 1 else "", ", ".join(map(str, failed)),
+                                                                              "" if error is None else ": " + error))
+        return result
+
+    def resume_quiz(self, engine, answered, timeout_s: float = 30.0) -> int:
+        answered = list(answered)
+        return self._run(engine, answered, lambda rows: engine.resume_quiz_from_rows(answered, rows), engine.release_quiz, timeout_s)
+
+    def resume_quiz_batch(self, engine, lists, timeout_s: float = 30.0) -> List[int]:
+        lists = [list(l) for l in lists]
+
+        def release(quizzes):
+            for q in quizzes:
+                engine.release_quiz(q)
+
+        return self._run(engine, [aq for l in lists for aq in l], lambda rows: engine.resume_quiz_batch_from_rows(lists, rows), release,
+                         timeout_s)
+
+    def close(self) -> None:
+        if self._map is not None:
+            self._interop.host_unregister(self._host)
+            self._words = None
+            try:
+                self._map.close()
+            except BufferError:
+                pass
+            self._map = None
+
+
 def tensor_from_device_ptr(ptr: int, n_doubles: int, device: torch.device) -> torch.Tensor:
     """Wrap engine-owned device memory (e.g. a quiz's prior vector) as a torch tensor without copying."""
 

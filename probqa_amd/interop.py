@@ -148,6 +148,10 @@ HIP_EXPORTS = {
     "PqaHip_EnqueueEval": (_vp, [_vp, _i64]),
     "PqaHip_GetPriorDevicePtr": (_vp, [_vp, _i64, _pvp, _pi64]),
     "PqaHip_RecordAnswerRemote": (_vp, [_vp, _i64, _i64]),
+    "PqaHip_AnswerRowSlotBytes": (_i64, [_vp]),
+    "PqaHip_PackAnswerRows": (_vp, [_vp, _i64, _pAQ, _vp, _vp, ctypes.c_uint64]),
+    "PqaEngine_ResumeQuizFromRows": (_i64, [_vp, _pvp, _i64, _pAQ, _vp]),
+    "PqaEngine_ResumeQuizBatchFromRows": (_vp, [_vp, _i64, _pi64, _pAQ, _vp, _pi64]),
     "PqaEngine_RecordAnswerBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_StartQuizBatch": (_vp, [_vp, _i64, _pi64]),
     "PqaEngine_ResumeQuizBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64]),
@@ -718,6 +722,34 @@ class PqaEngine:
         arr, _ = self.to_c_answered_questions(flat)
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_ResumeQuizBatch(self.c_engine, n, counts, arr, out))
+        return list(out[:n])
+
+    # ---- row packages: ResumeQuiz on a shard that a process of its own drives (include/PqaHipExt.h) ----------------------
+    def answer_row_slot_bytes(self) -> int:
+        """Bytes of one slot of a row package: the sA row and the mD row of one answered question, in the cube's element type."""
+        return _lib.PqaHip_AnswerRowSlotBytes(self.c_engine)
+
+    def pack_answer_rows(self, answered_questions: List[AnsweredQuestion], dst: int, flag: int = 0, flag_value: int = 0) -> None:
+        """Enqueue (no synchronisation) the copy of the rows of those answered questions this engine holds into their slots of the
+        package at device-visible address `dst`; `flag` (an address, 0 = none) receives `flag_value` once they are visible."""
+        arr, n = self.to_c_answered_questions(answered_questions)
+        _check(_lib.PqaHip_PackAnswerRows(self.c_engine, n, arr, ctypes.c_void_p(dst), ctypes.c_void_p(flag or None), flag_value))
+
+    def resume_quiz_from_rows(self, answered_questions: List[AnsweredQuestion], rows: int) -> int:
+        """resume_quiz with the rows of the questions other shards hold read from the package at device-visible address `rows`."""
+        arr, n = self.to_c_answered_questions(answered_questions)
+        c_err = ctypes.c_void_p()
+        i_quiz = _lib.PqaEngine_ResumeQuizFromRows(self.c_engine, ctypes.byref(c_err), n, arr, ctypes.c_void_p(rows or None))
+        _check(c_err.value)
+        return i_quiz
+
+    def resume_quiz_batch_from_rows(self, lists, rows: int) -> List[int]:
+        """resume_quiz_batch likewise; the package's slots count through the answered questions of all lists, in order."""
+        n = len(lists)
+        counts = (ctypes.c_int64 * max(n, 1))(*[len(l) for l in lists])
+        arr, _ = self.to_c_answered_questions([aq for l in lists for aq in l])
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_ResumeQuizBatchFromRows(self.c_engine, n, counts, arr, ctypes.c_void_p(rows or None), out))
         return list(out[:n])
 
     def train_batch(self, records, throw: bool = True) -> Optional[PqaError]:
