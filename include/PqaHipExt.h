@@ -89,6 +89,17 @@ PQACORE_API void *PqaEngineFactory_CreateHipEngineSharded(void *pvFactory, void 
  * cluster sweep, a question over a cluster of workgroups), "cluster_form" (that sweep: 0 = default, 1 = question by question, 2 = pass 1 a question
  * ahead of the exchange), "cluster_shape" (threads x 16-byte units per thread of the form that runs ahead: 0 = default, 1 = 512 x 1, 2 = 256 x 2;
  * two workgroups per CU both; 256 x 2 is built for questions of two to five answers, other answer counts take 512 x 1),
+ * "combine_spin" (clients waiting for the engine spin first while they are fewer than the CPUs the process may use; default 1, 0 =
+ * they always sleep), "batch_form" (the batched sweep's form: 0 = by the batch's size and the cube's shape [default], 1 = grid.y = quiz,
+ * 2 = row-sharing, 3 = (quiz, chunk) lanes), "batch_qb" (questions per block of the row-sharing sweep, 0..4, 0 = default), "rerank"
+ * (Float engines' batched argmax: the fp32 sweep's best 8 questions per quiz re-ranked in fp64; default 1).
+ * Described with the calls they belong to: "sampled_batch_host", "time_sweeps", "train_chunk_steps", "rows_stage".
+ * The whole list -- name, accepted values, default, side effects, PQA_* variable -- is the table of probqa_amd/csrc/engine_options.h.
+ * An option named a flag there takes any integer and stores 0 or 1; every other one refuses a value outside its range with
+ * "Unknown option or value out of range: NAME" and keeps the value it had; an unknown name is refused the same way and reads -1.
+ * "seed" is write-only and "eval_max_grid" is not readable either: both read -1.  For unchanged wrappers the environment presets
+ * PQA_SELECT (sample | argmax), PQA_SERVER, PQA_BUG_COMPAT, PQA_SPECULATE, PQA_COMBINE, PQA_POLE_FIX, PQA_WORKERS and PQA_SEED when
+ * an engine is created; a value that is refused there (a flag wants 0 or 1) is reported on stderr and ignored.
  * Read-only: "server_last_step_ns" (device-side duration of the newest finished step of the resident sweep: request in hand
  * to answer published, from the kernel's own 100 MHz clock; -1 if there is none), "precision" (TPqaPrecisionType of the engine: 1 = Float, 3 = Double), "server_active",
  * "ldT", "device". */

@@ -693,6 +693,19 @@ PQACORE_API void *PqaHip_RecordAnswerRemote(void *pvEngine, const int64_t iQuiz,
 PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut) {
   const std::string w(what ? what : "");
   if (nIn < 0 || nOut < 0 || (nIn > 0 && !pIn) || (nOut > 0 && !pOut)) return -1;
+  if (w.compare(0, 12, "option_spec:") == 0) {   // a row of engine_options.h, by the option's name or as "#i" by its position
+    const std::string key = w.substr(12);
+    const pqa::OptionSpec *o = pqa::FindOption(key.c_str());
+    if (key.size() > 1 && key[0] == '#') {
+      char *end = nullptr;
+      const long long i = std::strtoll(key.c_str() + 1, &end, 10);
+      if (*end == 0 && i >= 0 && i < pqa::kOptionCount) o = &pqa::kOptions[i];
+    }
+    if (!o || nOut < 6) return -1;
+    const int64_t row[6] = {o->lo, o->hi, pqa::EngineOptions().*o->field, o->flag, o->effects, o->env != nullptr};
+    std::copy(row, row + 6, pOut);
+    return 6;
+  }
   if (w == "id_ledger") {
     pqa::IdLedger ledger;
     int64_t i = 0, nRes = 0;

@@ -213,9 +213,7 @@ Error HipEngine::Init(const CiEngineDefinition &def, const CiHipShard *shard) {
   _questionIds.Extend(_Q);  // reference PqaCore/BaseCpuEngine.cpp:24-25
   _targetIds.Extend(_T);
   std::random_device rd;  // the reference seeds from RDRAND (SRPlatform/Interface/SRFastRandom.h:31-40)
-  uint64_t seed = ((uint64_t)rd() << 32) ^ rd();
-  _rng[0] = SplitMix64(seed);
-  _rng[1] = SplitMix64(seed);
+  _rng.Seed(((uint64_t)rd() << 32) ^ rd());
   ApplyEnvironment();
   return Error();
 }
@@ -223,40 +221,22 @@ Error HipEngine::Init(const CiEngineDefinition &def, const CiHipShard *shard) {
 // The reference's wrappers can only call PqaEngineFactory_CreateCpuEngine / _LoadCpuEngine (ProbQA.py:131-145,
 // PqaEngineFactory.cs:24-33) and know nothing of PqaHip_SetOption: what they cannot say in a call they say in the environment.
 //   PQA_SELECT=sample|argmax   NextQuestion's selector (default sample: the reference's weighted draw, CpuEngine.cpp:362-400)
-//   PQA_SERVER=0|1             argmax selections through the resident sweep kernel
-//   PQA_BUG_COMPAT=0|1         ResumeQuiz as the reference binary (1, default) or as evidently intended (0)
-//   PQA_WORKERS=n              emulated thread-pool size (summation order of the posterior updates, training buckets)
+//   every row of kOptions (engine_options.h) that names a variable: an integer in the row's range, 0 or 1 for a flag --
+//     PQA_SERVER, PQA_BUG_COMPAT, PQA_SPECULATE, PQA_COMBINE, PQA_POLE_FIX, PQA_WORKERS
 //   PQA_SEED=n                 seed of the selector's generator (the reference's cannot be seeded)
-//   PQA_COMBINE=0|1            concurrent NextQuestion calls of different quizzes share one sweep, RecordAnswer's kernels are gathered (1, default)
-//   PQA_POLE_FIX=0|1           launched sweeps re-evaluate rows at the pole of the lack term in the reference's order (1, default; eval_kernels.hip: pole_fix)
 //   PQA_DEVICES=i[,j,...]      device ordinal(s): read by the factory (c_abi.cpp), which builds one shard per listed device
+// A value that is refused is reported on stderr and ignored.  The values go straight into the fields: nothing is running yet.
 void HipEngine::ApplyEnvironment() {
-  auto num = [](const char *name, int64_t lo, int64_t hi, int64_t &out) {
-    const char *v = std::getenv(name);
-    if (!v || !*v) return false;
-    char *end = nullptr;
-    const long long x = std::strtoll(v, &end, 10);
-    if (end == v || *end != 0 || x < lo || x > hi) {
-      std::fprintf(stderr, "PqaCore: ignoring %s=%s (expected an integer in %lld..%lld)\n", name, v, (long long)lo, (long long)hi);
-      return false;
-    }
-    out = x;
-    return true;
-  };
   if (const char *v = std::getenv("PQA_SELECT")) {
     const std::string sel(v);
-    if (sel == "argmax" || sel == "1") _optSelect = 1;
-    else if (sel == "sample" || sel == "sampled" || sel == "0") _optSelect = 0;
+    if (sel == "argmax" || sel == "1") _opt.select = 1;
+    else if (sel == "sample" || sel == "sampled" || sel == "0") _opt.select = 0;
     else if (!sel.empty()) std::fprintf(stderr, "PqaCore: ignoring PQA_SELECT=%s (expected sample or argmax)\n", v);
   }
   int64_t x = 0;
-  if (num("PQA_SERVER", 0, 1, x)) _optServer = x;
-  if (num("PQA_BUG_COMPAT", 0, 1, x)) _optBugCompat = x;
-  if (num("PQA_SPECULATE", 0, 1, x)) _optSpeculate = x;
-  if (num("PQA_COMBINE", 0, 1, x)) _optCombine = x;
-  if (num("PQA_POLE_FIX", 0, 1, x)) _optPoleFix = x;
-  if (num("PQA_WORKERS", 1, kMaxWorkers, x)) _optWorkers = x;
-  if (num("PQA_SEED", INT64_MIN, INT64_MAX, x)) { uint64_t s = (uint64_t)x; _rng[0] = SplitMix64(s); _rng[1] = SplitMix64(s); }
+  for (const OptionSpec &o : kOptions)
+    if (o.env && EnvInteger(o.env, o.lo, o.hi, x)) _opt.*o.field = x;
+  if (SeedFromEnvironment(x, true)) _rng.Seed((uint64_t)x);
 }
 
 HipEngine::~HipEngine() {
@@ -309,16 +289,16 @@ KbView HipEngine::View() const {
   v.cube = _dCube; v.elem = _elem; v.vB = _dVB; v.tgap = _dTGap; v.qgap = _dQGap;
   v.K = _K; v.Q = _Q; v.T = _T; v.ldT = _ldT;
   v.nValidTargets = _T - _nTargetGaps;
-  v.smallLaunches = _optServer ? 1 : 0;
-  v.priorScratch = _optLongRowForm ? _dPriorScratch : nullptr;
-  v.maxGrid = (int)_optEvalMaxGrid;
-  v.clusterForm = (int)_optClusterForm;
-  v.clusterShape = (int)_optClusterShape;
+  v.smallLaunches = _opt.server ? 1 : 0;
+  v.priorScratch = _opt.longRowForm ? _dPriorScratch : nullptr;
+  v.maxGrid = (int)_opt.evalMaxGrid;
+  v.clusterForm = (int)_opt.clusterForm;
+  v.clusterShape = (int)_opt.clusterShape;
   v.clusterFrom = ClusterFrom();
-  v.poleScratch = _optPoleFix ? _dPoleScratch : nullptr;
-  v.poleNoFollow = _optPoleFollow ? 0 : 1;
-  v.poleGate = _optPoleFix && _optPoleGate ? 1 : 0;
-  v.poleList = _optPoleFix ? reinterpret_cast<PoleHeader *>(_dPoleScratch + (size_t)_capQ * (size_t)(2 * _K + 2)) : nullptr;
+  v.poleScratch = _opt.poleFix ? _dPoleScratch : nullptr;
+  v.poleNoFollow = _opt.poleFollow ? 0 : 1;
+  v.poleGate = _opt.poleFix && _opt.poleGate ? 1 : 0;
+  v.poleList = _opt.poleFix ? reinterpret_cast<PoleHeader *>(_dPoleScratch + (size_t)_capQ * (size_t)(2 * _K + 2)) : nullptr;
   return v;
 }
 
@@ -329,139 +309,75 @@ Error HipEngine::SetOption(const char *name, int64_t value) {
   std::lock_guard<EngineMutex> lk(_mu);
   const std::string n(name ? name : "");
   (void)FlushUpdates();   // (deferred updates run under the options they were recorded under)
-  if (n == "select") { if (value != 0 && value != 1) goto bad; _optSelect = value; }
-  else if (n == "combine") { _optCombine = value ? 1 : 0; }
-  else if (n == "combine_spin") { _optCombineSpin = value ? 1 : 0; }
-  else if (n == "pole_fix") { StopServer(); (void)SettlePoleList(); _optPoleFix = value ? 1 : 0; _kbVersion++; }   // (settled while the list is still in view)   // 0: questions with a row at the pole of the lack term keep the sweep's own sums (pole_kernels.hip)
-  else if (n == "late_eager") { if (value < 0 || value > 1000000) goto bad; _optLateEager = value; }
-  else if (n == "top_exact") { _optTopExact = value ? 1 : 0; }   // 0: equal probabilities always by ascending target (the fast listing alone)
-  else if (n == "time_sweeps") { _optTimeSweeps = value ? 1 : 0; }   // measurement hook (hip_engine_select.cpp: LaunchSingleSweep)
-  else if (n == "pole_gate") { StopServer(); (void)SettlePoleList(); _optPoleGate = value ? 1 : 0; }   // 0: a fused argmax's fix redoes every listed question
-  else if (n == "pole_lazy") { StopServer(); (void)SettlePoleList(); _optPoleLazy = value ? 1 : 0; }
-  else if (n == "pole_follow") { StopServer(); (void)SettlePoleList(); _optPoleFollow = value ? 1 : 0; }   // measurement hook: 0 = the watching sweeps without the fix launched behind them (KbView::poleNoFollow)
-  else if (n == "long_row_form") { _optLongRowForm = value ? 1 : 0; }   // 0: the one-workgroup posterior kernels for rows beyond 16384 targets too
-  else if (n == "rows_stage") { _optRowsStage = value ? 1 : 0; }   // ResumeQuizFromRows: a package in host memory copied to the device first (1) or read in place (0)
-  else if (n == "fuse_update") { _optFuseUpdate = value ? 1 : 0; }   // RecordAnswer's posterior update inside the speculative sweep's launch
-  else if (n == "post_always") { _optPostAlways = value ? 1 : 0; }   // test hook: RecordAnswer / ListTopTargets always as posted operations
-  else if (n == "combine_linger_us") { if (value < 0 || value > 10000) goto bad; _optLingerUs = value; }
-  else if (n == "train_chunk_steps") { if (value < 1 || value > (int64_t(1) << 28)) goto bad; _optTrainChunkSteps = value; }   // test hook: the most steps per launch of a training batch
-  else if (n == "workers") { if (value < 1 || value > kMaxWorkers) goto bad; _optWorkers = value; }
-  else if (n == "eval_subtasks") { if (value < 0 || value > 8192) goto bad; _optEvalSubtasks = value; }
-  else if (n == "eval_variant") { if (value < 0) goto bad; _optEvalVariant = value; }
-  else if (n == "bug_compat") { _optBugCompat = value ? 1 : 0; }
-  else if (n == "use_graph") { _optUseGraph = value ? 1 : 0; }
-  else if (n == "top_cache") { if (value < 0 || value > 256) goto bad; _optTopCache = value; _topWantRecent = value; }
-  else if (n == "server") { StopServer(); _optServer = value ? 1 : 0; }
-  else if (n == "speculate") { DropSpeculation(); _optSpeculate = value ? 1 : 0; _specScore = 0; }
-  else if (n == "eval_max_grid") { if (value < 0 || value > 65535) goto bad; StopServer(); _optEvalMaxGrid = value; _kbVersion++; }
-  else if (n == "fused_sampled") { _optFusedSampled = value ? 1 : 0; }
-  else if (n == "host_sampled") { _optHostSampled = value ? 1 : 0; }
-  else if (n == "sampled_batch_host") { _optSampledBatchHost = value ? 1 : 0; }
-  else if (n == "batch_min") { if (value < 0 || value > 257) goto bad; _optBatchMin = value; }
-  else if (n == "rerank") { _optRerank = value ? 1 : 0; }
-  else if (n == "batch_form") { if (value < 0 || value > 3) goto bad; _optBatchForm = value; }
-  else if (n == "batch_qb") { if (value < 0 || value > 4) goto bad; _optBatchQb = value; }
-  else if (n == "batch_tile") { if (value < 0 || value > 8192) goto bad; _optBatchTile = value; }
-  else if (n == "cluster_shape") { if (value < 0 || value > 2) goto bad; _optClusterShape = value; }
-  else if (n == "cluster_form") { if (value < 0 || value > 2) goto bad; _optClusterForm = value; }
-  else if (n == "cluster_from") { if (value < 1024 || value > 16384) goto bad; StopServer(); _optClusterFrom = value; }   // rows longer than this take the cluster sweep
-  else if (n == "batch_tail") { _optBatchTail = value ? 1 : 0; }
-  else if (n == "batch_groups") { if (value < 0 || value > 8) goto bad; _optBatchGroups = value; }
-  else if (n == "server_vram_mailbox") { if (_serverStream) goto bad; _optServerVramMailbox = value ? 1 : 0; }
-  else if (n == "server_idle_us") { if (value < 10 || value > 1000000) goto bad; StopServer(); _optServerIdleUs = value; }
-  else if (n == "seed") { uint64_t s = (uint64_t)value; _rng[0] = SplitMix64(s); _rng[1] = SplitMix64(s); }
-  else goto bad;
+  if (n == "seed") { _rng.Seed((uint64_t)value); return Error(); }
+  const OptionSpec *o = FindOption(n.c_str());
+  const auto is = [o](int64_t EngineOptions::*field) { return o->field == field; };
+  if (!o || !AcceptOption(*o, value) || (is(&EngineOptions::serverVramMailbox) && _serverStream))
+    return Error::Make(ErrCode::UnhandledCase, "Unknown option or value out of range: " + n);
+  if (is(&EngineOptions::speculate)) DropSpeculation();
+  if (o->effects & kOptStopServer) StopServer();
+  if (o->effects & kOptSettlePoleList) (void)SettlePoleList();
+  _opt.*o->field = value;
+  if (o->effects & kOptBumpKbVersion) _kbVersion++;
+  if (is(&EngineOptions::speculate)) _specScore = 0;
+  if (is(&EngineOptions::topCache)) _topWantRecent = value;
   return Error();
-bad:
-  return Error::Make(ErrCode::UnhandledCase, "Unknown option or value out of range: " + n);
 }
 
 int64_t HipEngine::GetOption(const char *name) const {
   const std::string n(name ? name : "");
-  if (n == "select") return _optSelect;
-  if (n == "workers") return _optWorkers;
-  if (n == "eval_subtasks") return _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;
-  if (n == "eval_variant") return _optEvalVariant;
-  if (n == "bug_compat") return _optBugCompat;
-  if (n == "top_cache") return _optTopCache;
-  if (n == "use_graph") return _optUseGraph;
-  if (n == "server") return _optServer;
-  if (n == "server_idle_us") return _optServerIdleUs;
-  if (n == "fused_sampled") return _optFusedSampled;
-  if (n == "host_sampled") return _optHostSampled;
-  if (n == "sampled_batch_host") return _optSampledBatchHost;
-  if (n == "sampled_batches") return (int64_t)_sampledBatches;                  // NextQuestionSampledBatch calls that selected ...
-  if (n == "sampled_batch_device_ns") return (int64_t)_sampledBatchDeviceNs;    // ... and their selector launches' time between events
-  if (n == "priority_host_bytes") return (int64_t)_priorityHostBytes;           // priorities the batched sweeps delivered to the host
-  if (n == "speculate") return _optSpeculate;
-  if (n == "combine") return _optCombine;
-  if (n == "combine_linger_us") return _optLingerUs;
-  if (n == "combine_spin") return _optCombineSpin;
-  if (n == "post_always") return _optPostAlways;
-  if (n == "fuse_update") return _optFuseUpdate;
-  if (n == "fused_updates") return (int64_t)_fusedUpdates;           // RecordAnswers whose update ran inside the sweep's launch
-  if (n == "long_row_form") return _optLongRowForm;
-  if (n == "pole_fix") return _optPoleFix;
-  if (n == "late_eager") return _optLateEager;
-  if (n == "pole_lazy") return _optPoleLazy;
-  if (n == "pole_gate") return _optPoleGate;
-  if (n == "time_sweeps") return _optTimeSweeps;
+  if (const OptionSpec *o = FindOption(n.c_str())) {
+    const auto is = [o](int64_t EngineOptions::*field) { return o->field == field; };
+    if (is(&EngineOptions::evalSubtasks)) return _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;
+    if (is(&EngineOptions::serverVramMailbox) && _serverStream) return _serverRequestInVram ? 1 : 0;
+    if (is(&EngineOptions::evalMaxGrid)) return -1;   // (a test hook that was never made readable)
+    return _opt.*o->field;
+  }
+  // read-only: the plain counters ...
+  static constexpr struct { const char *name; uint64_t HipEngine::*counter; } kCounters[] = {
+      {"sampled_batches", &HipEngine::_sampledBatches},                   // NextQuestionSampledBatch calls that selected ...
+      {"sampled_batch_device_ns", &HipEngine::_sampledBatchDeviceNs},     // ... and their selector launches' time between events
+      {"priority_host_bytes", &HipEngine::_priorityHostBytes},            // priorities the batched sweeps delivered to the host
+      {"fused_updates", &HipEngine::_fusedUpdates},                       // RecordAnswers whose update ran inside the sweep's launch
+      {"top_exact_listings", &HipEngine::_topExactListings},
+      {"combined_batches", &HipEngine::_combBatches},                     // sweeps that served more than one NextQuestion call ...
+      {"combined_requests", &HipEngine::_combRequests},                   // ... the calls they served ...
+      {"combined_max_batch", &HipEngine::_combMaxBatch},                  // ... and the largest of them
+      {"posted_ops", &HipEngine::_postedOps},                             // RecordAnswer / ListTopTargets calls that found the engine taken and were run by its holder ...
+      {"posted_drains", &HipEngine::_postedDrains},                       // ... in this many rounds
+      {"train_batches", &HipEngine::_trainBatches},                       // launches that ran posted RecordQuizTarget calls together ...
+      {"train_batch_calls", &HipEngine::_trainBatchCalls},                // ... this many of them
+      {"pack_calls", &HipEngine::_packCalls},                             // PackAnswerRows launches ...
+      {"pack_bytes", &HipEngine::_packBytes},                             // ... and the bytes they were asked to move
+      {"rows_staged", &HipEngine::_rowsStaged},                           // host packages copied to the device before they were read
+      {"resume_batches", &HipEngine::_resumeBatches},                     // launch sequences that ran posted ResumeQuiz calls together ...
+      {"resumes_batched", &HipEngine::_resumesBatched},                   // ... this many of them
+      {"train_bulk_calls", &HipEngine::_trainBulkCalls},                  // TrainBatch / RecordQuizTargetBatch calls that trained ...
+      {"train_bulk_records", &HipEngine::_trainBulkRecords},              // ... their records ...
+      {"train_bulk_launches", &HipEngine::_trainBulkLaunches},            // ... and their launches (one per chunk)
+      {"train_bulk_host_ns", &HipEngine::_trainBulkHostNs},               // their host time, waits for the device left out ...
+      {"train_bulk_device_ns", &HipEngine::_trainBulkDeviceNs},           // ... and their kernels' time between events
+      {"update_flushes", &HipEngine::_flushes},                           // launches that ran deferred RecordAnswers ...
+      {"updates_flushed", &HipEngine::_flushedUpdates},                   // ... the updates they ran ...
+      {"update_max_flush", &HipEngine::_maxFlush},                        // ... and the most in one launch
+      {"spec_hits", &HipEngine::_specHits},                               // speculative sweeps a NextQuestion used ...
+      {"spec_dropped", &HipEngine::_specDropped},                         // ... and those nothing used
+  };
+  for (const auto &c : kCounters)
+    if (n == c.name) return (int64_t)(this->*c.counter);
+  // ... where the combined sweeps' time went (ns, summed): waiting for the engine, launching, waiting for the device, waiting for
+  // the engine again, selecting on the host ...
+  static constexpr const char *kCombinedNs[7] = {"lock", "launch", "device", "relock", "select", "selmu", "readers"};
+  if (n.compare(0, 12, "combined_ns_") == 0)
+    for (int i = 0; i < 7; i++)
+      if (n.compare(12, std::string::npos, kCombinedNs[i]) == 0) return (int64_t)_combNs[i];
+  // ... and what is computed
   if (n == "last_sweep_ns") {   // the newest timed sweep's launch, dispatch to retirement (-1: none)
     if (!_sweepTimed || !_evSweep[1]) return -1;
     float ms = 0;
     if (hipEventSynchronize(_evSweep[1]) != hipSuccess || hipEventElapsedTime(&ms, _evSweep[0], _evSweep[1]) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return (int64_t)(ms * 1e6);
   }
-  if (n == "top_exact") return _optTopExact;
-  if (n == "top_exact_listings") return _topExactListings;
-  if (n == "pole_follow") return _optPoleFollow;
-  if (n == "allowed_cpus") return AllowedCpus();
-  if (n == "combined_batches") return (int64_t)_combBatches;        // sweeps that served more than one NextQuestion call ...
-  if (n == "combined_requests") return (int64_t)_combRequests;      // ... the calls they served ...
-  if (n == "combined_max_batch") return (int64_t)_combMaxBatch;     // ... and the largest of them
-  if (n == "posted_ops") return (int64_t)_postedOps;                 // RecordAnswer / ListTopTargets calls that found the engine taken and were run by its holder ...
-  if (n == "posted_drains") return (int64_t)_postedDrains;
-  if (n == "train_batches") return (int64_t)_trainBatches;           // launches that ran posted RecordQuizTarget calls together ...
-  if (n == "train_batch_calls") return (int64_t)_trainBatchCalls;    // ... this many of them           // ... in this many rounds
-  if (n == "rows_stage") return _optRowsStage;
-  if (n == "pack_calls") return (int64_t)_packCalls;                 // PackAnswerRows launches ...
-  if (n == "pack_bytes") return (int64_t)_packBytes;                 // ... and the bytes they were asked to move
-  if (n == "rows_staged") return (int64_t)_rowsStaged;               // host packages copied to the device before they were read
-  if (n == "resume_batches") return (int64_t)_resumeBatches;        // launch sequences that ran posted ResumeQuiz calls together ...
-  if (n == "resumes_batched") return (int64_t)_resumesBatched;       // ... this many of them
-  if (n == "train_chunk_steps") return _optTrainChunkSteps;
-  if (n == "train_bulk_calls") return (int64_t)_trainBulkCalls;       // TrainBatch / RecordQuizTargetBatch calls that trained ...
-  if (n == "train_bulk_records") return (int64_t)_trainBulkRecords;   // ... their records ...
-  if (n == "train_bulk_launches") return (int64_t)_trainBulkLaunches; // ... and their launches (one per chunk)
-  if (n == "train_bulk_host_ns") return (int64_t)_trainBulkHostNs;    // their host time, waits for the device left out ...
-  if (n == "train_bulk_device_ns") return (int64_t)_trainBulkDeviceNs;   // ... and their kernels' time between events
-  if (n == "update_flushes") return (int64_t)_flushes;              // launches that ran deferred RecordAnswers ...
-  if (n == "updates_flushed") return (int64_t)_flushedUpdates;      // ... the updates they ran ...
-  if (n == "update_max_flush") return (int64_t)_maxFlush;           // ... and the most in one launch
-  // where the combined sweeps' time went (ns, summed): waiting for the engine, launching, waiting for the device, waiting for
-  // the engine again, selecting on the host
-  if (n == "combined_ns_lock") return (int64_t)_combNs[0];
-  if (n == "combined_ns_launch") return (int64_t)_combNs[1];
-  if (n == "combined_ns_device") return (int64_t)_combNs[2];
-  if (n == "combined_ns_relock") return (int64_t)_combNs[3];
-  if (n == "combined_ns_select") return (int64_t)_combNs[4];
-  if (n == "combined_ns_selmu") return (int64_t)_combNs[5];
-  if (n == "combined_ns_readers") return (int64_t)_combNs[6];
-  if (n == "spec_hits") return (int64_t)_specHits;         // speculative sweeps a NextQuestion used ...
-  if (n == "spec_dropped") return (int64_t)_specDropped;   // ... and those nothing used
-  if (n == "batch_min") return _optBatchMin;
-  if (n == "rerank") return _optRerank;
-  if (n == "batch_form") return _optBatchForm;
-  if (n == "batch_tile") return _optBatchTile;
-  if (n == "batch_groups") return _optBatchGroups;
-  if (n == "batch_tail") return _optBatchTail;
-  if (n == "cluster_form") return _optClusterForm;
-  if (n == "cluster_from") return _optClusterFrom;
-  if (n == "cluster_shape") return _optClusterShape;
-  if (n == "batch_qb") return _optBatchQb;
-  if (n == "precision") return _precType;
-  if (n == "server_vram_mailbox") return _serverStream ? (_serverRequestInVram ? 1 : 0) : _optServerVramMailbox;
-  if (n == "debug_mailbox") return (int64_t)(uintptr_t)_hMailbox;
   if (n == "server_last_step_ns") {   // device-side duration of the newest finished step of the resident sweep (-1: none)
     if (!_hMailbox || _serverPosted == 0) return -1;
     volatile ServerMailbox *mb = _hMailbox;
@@ -470,25 +386,19 @@ int64_t HipEngine::GetOption(const char *name) const {
       if (mb->state == kServerExited || std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) return -1;
     return (int64_t)mb->pad[0] * 10;      // 100 MHz ticks
   }
-  if (n == "server_active") return (_optServer && ServerUsable()) ? 1 : 0;
+  if (n == "server_active") return (_opt.server && ServerUsable()) ? 1 : 0;
+  if (n == "allowed_cpus") return AllowedCpus();
+  if (n == "debug_mailbox") return (int64_t)(uintptr_t)_hMailbox;
+  if (n == "precision") return _precType;
   if (n == "ldT") return _ldT;
   if (n == "device") return _device;
-  return -1;
+  return -1;   // (an unknown name, and the write-only "seed")
 }
 
 const char *HipEngine::EvalKernelName() const { 
   if (UseClusterSweep()) return EvalClusterKernelName(View());
-  if (_elem == 8) return EvalVariantName(View(), (int)_optEvalVariant);
-  return _optEvalVariant != 99 ? EvalF32KernelName(View(), (int)_optEvalVariant) : "f32_stream";
-}
-
-uint64_t HipEngine::NextRandom() {  // xorshift128+, the generator family of SRPlatform/Interface/SRFastRandom.h:60-72
-  uint64_t s1 = _rng[0];
-  const uint64_t s0 = _rng[1];
-  _rng[0] = s0;
-  s1 ^= s1 << 23;
-  _rng[1] = s1 ^ s0 ^ (s1 >> 18) ^ (s0 >> 5);
-  return _rng[1] + s0;
+  if (_elem == 8) return EvalVariantName(View(), (int)_opt.evalVariant);
+  return _opt.evalVariant != 99 ? EvalF32KernelName(View(), (int)_opt.evalVariant) : "f32_stream";
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -651,7 +561,7 @@ int64_t HipEngine::CreateQuiz(Error &err, int64_t nAnswered, const AQ *pAQs, con
       _startBatch->asked[_startBatch->n] = quiz->dAsked;
       _startBatch->n++;
     } else {
-      he = LaunchStartQuiz(kb, quiz->dPrior, quiz->dAsked, (int64_t)quiz->hAsked.size(), _optWorkers, _stream);
+      he = LaunchStartQuiz(kb, quiz->dPrior, quiz->dAsked, (int64_t)quiz->hAsked.size(), _opt.workers, _stream);
       if (he != hipSuccess) return fail(HipErr(he, "LaunchStartQuiz"));
     }
     // no synchronisation: every reader of the prior or the bitmap is ordered behind these on the engine's stream
@@ -673,8 +583,8 @@ int64_t HipEngine::CreateQuiz(Error &err, int64_t nAnswered, const AQ *pAQs, con
     static_assert(sizeof(void *) == sizeof(int64_t), "the pointer list travels in the answered-question buffer");
     he = hipMemcpyAsync(_dAqs, local.data(), local.size() * sizeof(void *), hipMemcpyHostToDevice, _stream);
     if (he == hipSuccess)
-      he = LaunchResumeQuiz(kb, quiz->dPrior, _dExps, reinterpret_cast<const void *const *>(_dAqs), nAnswered, _optWorkers,
-                            (int)_optBugCompat, _dStatus, _stream);
+      he = LaunchResumeQuiz(kb, quiz->dPrior, _dExps, reinterpret_cast<const void *const *>(_dAqs), nAnswered, _opt.workers,
+                            (int)_opt.bugCompat, _dStatus, _stream);
     if (he == hipSuccess)
       he = hipMemcpyAsync(_hPinned->status, _dStatus, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, _stream);
     if (he == hipSuccess) he = hipStreamSynchronize(_stream);
@@ -694,7 +604,7 @@ int64_t HipEngine::CreateQuiz(Error &err, int64_t nAnswered, const AQ *pAQs, con
 
 int64_t HipEngine::StartQuiz(Error &err) {
   CallScope scope(_activeCallers);
-  if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // (the engine is taken: the quizzes started meanwhile share ONE launch)
+  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {   // (the engine is taken: the quizzes started meanwhile share ONE launch)
     PostedOp op;
     op.kind = 4;
     PostAndWait(_mu, op);
@@ -702,7 +612,7 @@ int64_t HipEngine::StartQuiz(Error &err) {
     return op.result;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_optCombine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
   else lk.lock();
   return SpeculateFor(CreateQuiz(err, 0, nullptr, nullptr, nullptr, 0, nullptr));
 }
@@ -723,7 +633,7 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
     return -1;
   }
   CallScope scope(_activeCallers);
-  if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // (the engine is taken: the resumes posted meanwhile share ONE launch)
+  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {   // (the engine is taken: the resumes posted meanwhile share ONE launch)
     PostedOp op;
     op.kind = 7; op.arg = nAnswered; op.aqs = pAQs;   // (this thread waits for the result: the list stays valid)
     PostAndWait(_mu, op);
@@ -731,7 +641,7 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
     return op.result;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_optCombine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
   else lk.lock();
   if (nAnswered > 0 && ResumeTakesLongRow(View())) {   // long rows: the multi-workgroup form (hip_engine_resume.cpp), as a batch of one
     std::vector<ResumeEntry> e(1);
@@ -746,14 +656,14 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
 
 Error HipEngine::ReleaseQuiz(int64_t iQuiz) {
   CallScope scope(_activeCallers);
-  if (_optCombine && (_optPostAlways || !_mu.try_lock())) {
+  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {
     PostedOp op;
     op.kind = 5; op.iQuiz = iQuiz;
     PostAndWait(_mu, op);
     return op.err;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_optCombine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
   else lk.lock();
   return ReleaseQuizLocked(iQuiz, true);
 }

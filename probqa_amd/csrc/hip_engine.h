@@ -26,6 +26,7 @@
 #include "pqa_kernels.h"
 #include "combining.h"
 #include "kb_plan.h"
+#include "engine_options.h"
 
 namespace pqa {
 
@@ -427,7 +428,6 @@ class HipEngine : public IEngine {
   hipEvent_t _evPack = nullptr;
   char *_dRowStage = nullptr;          // ResumeQuizFromRows: where a host package is copied first
   size_t _rowStageBytes = 0;
-  int64_t _optRowsStage = 1;           // option "rows_stage": 1 = a package in host memory is copied to the device before it is read, 0 = read in place
   uint64_t _packCalls = 0, _packBytes = 0, _rowsStaged = 0;   // read-only "pack_calls", "pack_bytes", "rows_staged"
   hipError_t TakeQuizBuffers(Quiz *q);
   // the batch's device tables -- slots, statuses, asked bitmaps, row pointers, long-row sums, exponent scratch -- and their
@@ -446,11 +446,9 @@ class HipEngine : public IEngine {
   void FreeTrainBulk();
   Error ValidateTrainBatchLocked(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const int64_t *pQuizzes);
   Error TrainRecordsLocked(const std::vector<TrainRecord> &recs, bool fromQuiz);
-  int64_t _optTrainChunkSteps = int64_t(1) << 22;   // option "train_chunk_steps": the most steps one launch of a batch carries
   uint64_t _trainBulkCalls = 0, _trainBulkRecords = 0, _trainBulkLaunches = 0, _trainBulkHostNs = 0, _trainBulkDeviceNs = 0;
   Error TrainLocked(int64_t nQuestions, const AQ *pAQs, int64_t iTarget, double amount, bool fromQuiz);
   Error ValidateTrainLocked(int64_t nQuestions, const AQ *pAQs, int64_t iTarget) const;
-  uint64_t NextRandom();
   Error UploadGaps();
   Error RemoveIds(int64_t n, const int64_t *ids, int64_t limit, std::vector<uint32_t> &gapBits, std::vector<int64_t> &gapList, IdLedger &ledger,
                   const char *absentMsg);   // RemoveQuestions / RemoveTargets: all ids validated, then flagged, listed and retired
@@ -492,8 +490,7 @@ class HipEngine : public IEngine {
   Error EnsureTopExactScratch(int64_t nQuizzes, int64_t want);
   void *_dTopExact = nullptr;
   size_t _topExactBytes = 0;
-  int64_t _optTopExact = 1;
-  int64_t _topExactListings = 0;   // read-only option "top_exact_listings": listings that took the heaps' path
+  uint64_t _topExactListings = 0;  // read-only option "top_exact_listings": listings that took the heaps' path
   // Released quizzes' device buffers, reused by the next StartQuiz / ResumeQuiz of the same dimensions: hipMalloc / hipFree
   // cost tens of microseconds and hipFree synchronises the device.  Reuse is ordered by the engine's stream.
   struct QuizBuffers { double *dPrior; uint32_t *dAsked; int64_t ldT; size_t askedWords; };
@@ -540,12 +537,9 @@ class HipEngine : public IEngine {
     const int own = _activeCallers.load(std::memory_order_relaxed);
     return _extCallers ? std::max(own, _extCallers->load(std::memory_order_relaxed)) : own;
   }
-  bool Concurrent() const { return _optCombine && Callers() > 1; }
+  bool Concurrent() const { return _opt.combine && Callers() > 1; }
   static int AllowedCpus();                   // the CPUs this process may use: the cgroup's quota (cpu.max) or the affinity mask
-  int64_t _optCombineSpin = 1;                // option "combine_spin": 1 = waiting clients spin while they are fewer than the allowed CPUs, 0 = they always sleep
-  int64_t _optPostAlways = 0;                 // option "post_always" (test hook): the posted form of RecordAnswer / ListTopTargets even when the engine is free
-  bool ClientsFitCpus() const { return _optCombineSpin && Callers() + 2 <= AllowedCpus(); }
-  int64_t _optCombine = 1;                    // option "combine" / PQA_COMBINE: 0 = every call by itself, as before
+  bool ClientsFitCpus() const { return _opt.combineSpin && Callers() + 2 <= AllowedCpus(); }
   // ---- combining of concurrent NextQuestion calls (reference: every client's NextQuestion runs under a SHARED lock,
   // PqaCore/CpuEngine.cpp:357-361, Interface/IPqaEngine.h:44).  A caller posts its request; if a leader is at work it waits
   // for its result, otherwise it becomes the leader: it takes everything posted so far -- distinct quizzes -- and serves it
@@ -573,7 +567,6 @@ class HipEngine : public IEngine {
   std::atomic<int64_t> _flushedSinceSweep{0};      // RecordAnswers launched since the newest combined sweep: their clients' NextQuestions are on their way
   std::atomic<int64_t> _sweepNsEwma{0};            // how long a follower of a combined sweep waits for its result (moving average): it sleeps most of that, then spins
   std::atomic<int64_t> _lastCombined{0};           // requests of the newest combined sweep: as many RecordAnswers are about to arrive
-  int64_t _optLingerUs = 20;                       // option "combine_linger_us": how long a ListTopTargets waits for them before it launches the updates
   int64_t Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd);
   // ---- posted operations.  With dozens of client threads the engine's lock is not held long but changes hands through the
   // kernel every time: each RecordAnswer and ListTopTargets slept on it and was woken by the thread before it, one wake-up
@@ -633,15 +626,8 @@ class HipEngine : public IEngine {
   Error WaitFlagNapping(volatile uint64_t *flag, uint64_t value, const char *what);   // for many waiters at once: a short spin, then naps
   SelectResult *_dSelScratch = nullptr;  // its per-workgroup winner records
   double *_dPriorScratch = nullptr;      // the long-row posterior kernels' subtask sums (KbView::priorScratch)
-  int64_t _optPoleFix = 1;               // option "pole_fix"
-  int64_t _optPoleFollow = 1;            // option "pole_follow" (measurement hook)
-  int64_t _optLateEager = 3;             // option "late_eager": see Quiz::lateStreak (0: speculative sweeps always with the fix-up behind them)
-  int64_t _optTimeSweeps = 0;            // option "time_sweeps" (measurement hook): events around every launched fp64 sweep; read-only "last_sweep_ns"
-  hipEvent_t _evSweep[2] = {nullptr, nullptr};
+  hipEvent_t _evSweep[2] = {nullptr, nullptr};   // option "time_sweeps": around every launched fp64 sweep; read-only "last_sweep_ns"
   mutable bool _sweepTimed = false;
-  int64_t _optPoleGate = 1;              // option "pole_gate": a fused single-quiz ARGMAX has only the listed questions redone that can still win (pole_kernels.hip: pole_bounds_kernel)
-  int64_t _optPoleLazy = 1;              // option "pole_lazy": synchronous single-quiz selections launch the fix only when the sweep listed something (FusedSelect::lazyFix)
-  int64_t _optLongRowForm = 1;           // option "long_row_form": StartQuiz / RecordAnswer over rows beyond 16384 targets as one workgroup per subtask of the sum
   // batched selections (NextQuestionArgmaxBatch); allocated on first use
   static constexpr int64_t kMaxBatch = 256, kBatchGrid = 1024;
   // (sweepOut / sweepSeq: where the sweep of a sampled batch publishes its own winners, so that out / seq are the selector's
@@ -685,7 +671,6 @@ class HipEngine : public IEngine {
   Error ValidateBatchLocked(int64_t n, const int64_t *pQuizzes);
   Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
   Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
-  int64_t _optSampledBatchHost = 0;    // option "sampled_batch_host": 1 = NextQuestionSampledBatch by the host's selector over the copied priorities (the A/B leg)
   uint64_t _sampledBatches = 0, _sampledBatchDeviceNs = 0;   // read-only "sampled_batches", "sampled_batch_device_ns" (the selector's launches between events)
   uint64_t _priorityHostBytes = 0;     // read-only "priority_host_bytes": priorities the batched sweeps delivered to the host
   Error WaitBatchFlags(BatchCtx &c, int64_t n, uint64_t tag);
@@ -757,35 +742,14 @@ class HipEngine : public IEngine {
   mutable EngineMutex _mu{this, &HipEngine::DrainPosted};
   std::atomic<uint64_t> _nQuestionsAsked{0};
   Mode _mode = Mode::Regular;
-  // options
-  int64_t _optSelect = 0, _optWorkers = 16, _optEvalSubtasks = 0, _optEvalVariant = 0;
-  // ResumeQuiz seeds the first answered question's product from vector 0 of vB for every target vector, as the reference binary
-  // does (PqaCore/CEUpdatePriorsSubtaskMul.cpp:53 loads pvB, not pvB + j): the drop-in default.  0 = the evident intent.
-  int64_t _optBugCompat = 1;
-  void ApplyEnvironment();   // PQA_SELECT / PQA_SERVER / PQA_BUG_COMPAT / PQA_WORKERS / PQA_SEED: defaults for unchanged wrappers
-  int64_t _optHostSampled = 1;    // the sampled NextQuestion as ONE launch + the selector on the host (the finisher workgroup hands over the priority vector)
+  EngineOptions _opt;        // every option of SetOption / GetOption (engine_options.h)
+  void ApplyEnvironment();   // the PQA_* variables: defaults for unchanged wrappers
   TaggedPriority *_hHostPriority = nullptr;   // host-coherent, _hostPriorityCap records {priority, launch tag}
   std::vector<double> _hostRun;               // the vector the host-side selector works on
   Error CollectHostPriority(uint64_t tag, const Quiz *q);   // the launch's entries out of _hHostPriority into _hostRun
   int64_t _hostPriorityCap = 0;
   hipError_t EnsureHostPriority();
-  int64_t _optFusedSampled = 0;   // the sampled NextQuestion as ONE launch (the sweep's finisher workgroup runs the selector): correct,
-                                  // but 38.3 vs 36.4 us at 1000 x 5 x 1000 -- one workgroup's serial selection costs more than a launch
-  int64_t _optEvalMaxGrid = 0;    // test hook: KbView::maxGrid
-  int64_t _optBatchMin = 0;       // batches of at least this many quizzes take the row-sharing sweep (lane = quiz), smaller ones grid.y = quiz; 0 = by the number of waves the batch gives the row-sharing sweep
-  int64_t _optBatchForm = 0;      // 0: the batch's form by its size and the cube's shape; 1 grid.y = quiz, 2 row-sharing, 3 (quiz, chunk) lanes
-  int64_t _optRerank = 1;         // Float engines' batched argmax: the fp32 sweep's best 8 questions per quiz re-ranked in fp64
-  int64_t _optBatchQb = 0;        // questions per block of that sweep (0 = default)
-  int64_t _optBatchTile = 0;      // targets per LDS tile of that sweep (0 = default)
-  int64_t _optClusterShape = 0;   // ... the shape of the form that runs ahead (cluster_kernels.hip: kAheadVariants), 0 = default
-  // Rows longer than this many elements take the cluster sweep (option cluster_from, 1024..16384).  10240: what the register shapes hold
-  // without spilling -- the 16-wave shapes behind them (128 registers a lane) ran 10500^2 at 2552 us against the cluster's 1597, 12000^2
-  // at 3004 against 1974, 16000^2 at 4230 against 3430 (round 6, one box); they stay selectable (eval_variant 6, 7, 11).
-  int64_t _optClusterFrom = 10240;
-  int64_t ClusterFrom() const { return _elem == 8 ? _optClusterFrom : 16384; }   // (Float engines: their register shapes hold 16384 elements; not re-measured)
-  int64_t _optClusterForm = 0;    // long rows, one quiz (cluster_kernels.hip): 0 = default, 1 = question by question, 2 = pass 1 a question ahead
-  int64_t _optBatchTail = 1;      // that sweep's last, partial round as a launch of its own with fewer questions per group (LaunchEvalBatch)
-  int64_t _optBatchGroups = 0;    // question groups per workgroup of that sweep for batches under 129 quizzes (0 = automatic)
+  int64_t ClusterFrom() const { return _elem == 8 ? _opt.clusterFrom : 16384; }   // rows longer than this take the cluster sweep (Float engines: their register shapes hold 16384 elements; not re-measured)
   // ---- the next sweep ahead of its request (option "speculate"): RecordAnswer enqueues, right behind its posterior kernel, the
   // sweep the NextQuestion that normally follows would launch -- the client's time between the two calls (the wrapper's own
   // overhead, ListTopTargets, a person reading the question) overlaps with it, and that NextQuestion only waits for the flag.
@@ -804,22 +768,17 @@ class HipEngine : public IEngine {
   // launch that uses the list empties it first (and the speculation that left them is dropped: its fix-up would find nothing)
   bool _poleListPending = false;
   Error SettlePoleList();
-  int64_t _optSpeculate = 1;
   int _specScore = 0;        // +1 per speculation used, -1 per speculation dropped: below -4 only every 32nd RecordAnswer speculates
   uint64_t _specProbe = 0, _specHits = 0, _specDropped = 0;
   bool Speculate(Quiz *q, int64_t updQuestion = -1, int64_t updAnswer = -1);
-  int64_t _optFuseUpdate = 1;   // option "fuse_update"
-  uint64_t _fusedUpdates = 0;
+  uint64_t _fusedUpdates = 0;   // read-only "fused_updates": RecordAnswers whose update ran inside the sweep's launch (option "fuse_update")
   int64_t SpeculateFor(int64_t iQuiz);
   int TakeSpeculation(Quiz *q, int kindMask, uint64_t *pTag);
   void DropSpeculation() {
     if (_spec.quiz != nullptr) { _spec.quiz = nullptr; _specDropped++; if (_specScore > -8) _specScore--; }
   }
-  int64_t _optUseGraph = 0;   // NextQuestion (argmax) replays a per-quiz HIP graph instead of launching
-  int64_t _topWantRecent = 10;   // what ListTopTargets has been asked for lately
-  int64_t _optTopCache = 10;  // targets RecordAnswer's kernel lists ahead of the ListTopTargets that follows it (0: none)
+  int64_t _topWantRecent = 10;   // what ListTopTargets has been asked for lately (option "top_cache" resets it)
   // ---- resident sweep (option "server"; pqa_kernels.h: ServerMailbox)
-  int64_t _optServer = 0, _optServerIdleUs = 500, _optServerVramMailbox = 1;
   hipStream_t _serverStream = nullptr;
   ServerMailbox *_hMailbox = nullptr;     // pinned
   ServerCtl *_dServerCtl = nullptr;
@@ -835,7 +794,7 @@ class HipEngine : public IEngine {
   Error ServerWait(volatile uint64_t *flag, uint64_t value, const char *what);
   void StopServer();
   void ServerQuiesce();   // returns once the posted step (if any) has finished: before anything that writes what it reads
-  uint64_t _rng[2] = {0, 0};
+  SelectorRng _rng;         // NextQuestion's random numbers, drawn under _rngMu
 };
 
 void LogAnomaly(DefaultLogger::Severity sev, const char *what, double value);   // the reference's numeric-anomaly log entries (rate-limited)

@@ -68,7 +68,7 @@ void HipEngine::DrainPosted(PostedOp *ordered) {
     std::vector<PostedOp *> chunk;
     auto launch = [&]() {
       if (batch.n > 0) {
-        const hipError_t he = LaunchStartQuizBatch(View(), batch, _optWorkers, _stream);
+        const hipError_t he = LaunchStartQuizBatch(View(), batch, _opt.workers, _stream);
         if (he != hipSuccess)
           for (PostedOp *o : chunk)
             if (o->result >= 0) {
@@ -202,7 +202,7 @@ void HipEngine::TrainPosted(PostedOp *ordered) {
 int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
   CallScope scope(_activeCallers);
   _mu.spinFirst.store(ClientsFitCpus() && _activeCallers.load(std::memory_order_relaxed) > 1, std::memory_order_relaxed);
-  if (!_optCombine) {
+  if (!_opt.combine) {
     std::lock_guard<EngineMutex> lk(_mu);
     return kind == 0 ? NextQuestionArgmaxLocked(err, iQuiz) : NextQuestionSampledLocked(err, iQuiz, rnd);
   }
@@ -218,8 +218,8 @@ int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
   r.iQuiz = iQuiz; r.kind = kind; r.rnd = rnd;
   int st = _comb.Wait(r, &_sweepNsEwma, ClientsFitCpus());
   if (st == 2) {   // (the lead: nobody else led, or the leader before served its own batch and handed the lead to this, the oldest request)
-    if (_optLingerUs > 0 && Concurrent())   // (alone in the engine: nobody to wait for)
-      _comb.Linger(_optLingerUs, _flushedSinceSweep.load(std::memory_order_relaxed), _activeCallers);
+    if (_opt.lingerUs > 0 && Concurrent())   // (alone in the engine: nobody to wait for)
+      _comb.Linger(_opt.lingerUs, _flushedSinceSweep.load(std::memory_order_relaxed), _activeCallers);
     Flight f;
     st = _comb.Lead(
         r, kMaxBatch, [this](int64_t m) { return PreferredCombinedBatch(m); },
@@ -298,7 +298,7 @@ int64_t HipEngine::SelectFromPriorities(SelRequest *r) {
 // groups of 64 (tools/midbatch_bench.py at 1000 x 5 x 1000: 60 / 107 / 192 / 362 us of kernel) -- so 20 requests cost what 32 do; with
 // the device as the bottleneck of a busy server, a sweep of 16 now and the other 4 with the next one serve more clients per second.
 int64_t HipEngine::PreferredCombinedBatch(int64_t m) const {
-  if (_optBatchForm != 0 || _elem != 8 || !EvalMidBatchSupported(View())) return m;
+  if (_opt.batchForm != 0 || _elem != 8 || !EvalMidBatchSupported(View())) return m;
   if (m <= 8) return m;
   if (m <= 10) return 8;
   if (m <= 16) return m;
@@ -346,7 +346,7 @@ void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch,
     f.anySampled = f.anySampled || r->kind == 1;
   }
   if (live.empty()) return;
-  if (live.size() == 1 || (_optServer && ServerUsable()) || _optUseGraph) {   // (the resident sweep and graph replay serve one quiz at a time)
+  if (live.size() == 1 || (_opt.server && ServerUsable()) || _opt.useGraph) {   // (the resident sweep and graph replay serve one quiz at a time)
     for (SelRequest *r : live) single(r);
     return;
   }
@@ -355,7 +355,7 @@ void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch,
   std::vector<Quiz *> quizzes;
   err = BatchSweep(c, n, ids.data(), quizzes, false, f.tag, f.anySampled, &f.quizMinor, &f.tagged);
   if (!err.ok()) { for (SelRequest *r : live) { r->err = err; r->result = -1; } return; }
-  const int64_t nSubtasks = _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;  // reference PqaCore/CpuEngine.cpp:339
+  const int64_t nSubtasks = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
   for (int64_t i = 0; i < n; i++) {
     SelRequest *r = live[(size_t)i];
     Quiz *q = quizzes[(size_t)i];

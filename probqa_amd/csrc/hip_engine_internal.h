@@ -55,13 +55,6 @@ inline int64_t *MallocCopy(const std::vector<int64_t> &v) {
   return p;
 }
 
-inline uint64_t SplitMix64(uint64_t &x) {
-  uint64_t z = (x += 0x9E3779B97F4A7C15ULL);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
-
 // A wait for a word the GPU writes: a pure spin while the answer is a kernel's time away (the first ~50 us), then the core is
 // offered to whoever else wants it between looks (sched_yield) -- a process whose clients outnumber its CPUs otherwise burns its
 // allowance on waiting -- and the clock is read only every so often.  Tick() returns false once `limit` has passed.

@@ -76,7 +76,7 @@ Error HipEngine::ResumeEntriesLocked(std::vector<ResumeEntry> &e, bool allOrNone
     hipError_t he = hipSuccess;
     if (starts->n > 0) {
       MarkStreamBusy();
-      he = LaunchStartQuizBatch(kb, *starts, _optWorkers, _stream);
+      he = LaunchStartQuizBatch(kb, *starts, _opt.workers, _stream);
       if (he != hipSuccess)
         for (ResumeEntry *x : startChunk) { drop(*x); x->err = HipErr(he, "StartQuiz"); }
     }
@@ -98,7 +98,7 @@ Error HipEngine::ResumeEntriesLocked(std::vector<ResumeEntry> &e, bool allOrNone
   // ---- the resumes, in chunks: one copy of the chunk's tables, the launch sequence, one copy of the statuses back, one synchronisation
   const bool longRow = ResumeTakesLongRow(kb);
   const int64_t chunkCap = std::max<int64_t>(1, std::min<int64_t>(kResumeChunk, (int64_t)(kResumeExpsBudget / ((size_t)_ldT * sizeof(int64_t)))));
-  const int64_t stride = ResumeLongStride(_optWorkers);
+  const int64_t stride = ResumeLongStride(_opt.workers);
   std::vector<ResumeEntry *> chunk;
   size_t next = 0;
   for (;;) {
@@ -151,7 +151,7 @@ Error HipEngine::ResumeEntriesLocked(std::vector<ResumeEntry> &e, bool allOrNone
     }
     if (he == hipSuccess && longRow) he = hipMemsetAsync(_dResume + offLong, 0, m * (size_t)stride * sizeof(uint64_t), _stream);
     if (he == hipSuccess)
-      he = LaunchResumeQuizBatch(kb, reinterpret_cast<const ResumeSlot *>(_dResume), (int64_t)m, (int64_t)askedWords, _optWorkers, (int)_optBugCompat,
+      he = LaunchResumeQuizBatch(kb, reinterpret_cast<const ResumeSlot *>(_dResume), (int64_t)m, (int64_t)askedWords, _opt.workers, (int)_opt.bugCompat,
                                  longRow ? reinterpret_cast<uint64_t *>(_dResume + offLong) : nullptr, _stream);
     if (he == hipSuccess)
       he = hipMemcpyAsync(_hResume + offStatus, _dResume + offStatus, m * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, _stream);
@@ -337,7 +337,7 @@ Error HipEngine::PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pR
   if (anyForeign && pRows == nullptr) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the row package.");
   const size_t slotBytes = (size_t)AnswerRowSlotBytes();
   const char *base = static_cast<const char *>(pRows);
-  if (anyForeign && _optRowsStage) {
+  if (anyForeign && _opt.rowsStage) {
     hipSetDevice(_device);
     hipPointerAttribute_t at;
     const hipError_t q = hipPointerGetAttributes(&at, pRows);

@@ -149,7 +149,7 @@ Error HipEngine::EnqueueEval(int64_t iQuiz) {
 // The single-quiz sweep of this engine's precision on the engine's stream: the register-resident fp64 shapes with the fused
 // argmax (eval_kernels.hip) for Double engines; for Float engines the fp32 streaming sweep and, where a selection is asked
 // for, the argmax kernel behind it (batch_kernels.hip, select_kernels.hip).
-bool HipEngine::UseClusterSweep() const { return _optEvalVariant == 0 && _ldT > ClusterFrom() && EvalClusterSupported(View()); }
+bool HipEngine::UseClusterSweep() const { return _opt.evalVariant == 0 && _ldT > ClusterFrom() && EvalClusterSupported(View()); }
 
 Error HipEngine::LaunchSingleSweep(Quiz *q, const FusedSelect *fused) {
   { Error se = SettlePoleList(); if (!se.ok()) return se; }
@@ -175,16 +175,16 @@ Error HipEngine::LaunchSingleSweep(Quiz *q, const FusedSelect *fused) {
     // (measurement hook, option "time_sweeps": HIP events on the engine's stream right around this launch -- what the launch of a
     //  SYNCHRONOUS selection takes on the device, dispatch to retirement, as a profiler's kernel trace sees it; back-to-back launches,
     //  whose ramps overlap, are shorter)
-    if (_optTimeSweeps) {
+    if (_opt.timeSweeps) {
       if (!_evSweep[0]) { HIP_TRY(hipEventCreate(&_evSweep[0])); HIP_TRY(hipEventCreate(&_evSweep[1])); }
       HIP_TRY(hipEventRecord(_evSweep[0], _stream));
     }
-    HIP_TRY(LaunchEvalQuestions(View(), q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_optEvalVariant, fused, _stream));
-    if (_optTimeSweeps) { HIP_TRY(hipEventRecord(_evSweep[1], _stream)); _sweepTimed = true; }
+    HIP_TRY(LaunchEvalQuestions(View(), q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, fused, _stream));
+    if (_opt.timeSweeps) { HIP_TRY(hipEventRecord(_evSweep[1], _stream)); _sweepTimed = true; }
     return Error();
   }
-  if (_optEvalVariant != 99 && EvalF32RegisterShape(View(), (int)_optEvalVariant))   // (variant 99: the streaming form, as for Double engines)
-    HIP_TRY(LaunchEvalQuestionsF32Reg(View(), q->dPrior, q->dAsked, _dPriority, (int)_optEvalVariant, _stream));
+  if (_opt.evalVariant != 99 && EvalF32RegisterShape(View(), (int)_opt.evalVariant))   // (variant 99: the streaming form, as for Double engines)
+    HIP_TRY(LaunchEvalQuestionsF32Reg(View(), q->dPrior, q->dAsked, _dPriority, (int)_opt.evalVariant, _stream));
   else
     HIP_TRY(LaunchEvalQuestionsF32(View(), q->dPrior, q->dAsked, _dPriority, _stream));
   if (fused != nullptr)
@@ -219,7 +219,7 @@ Error HipEngine::EnqueueSelectArgmaxFlag(int64_t iQuiz, void *pOut, void *pFlag,
   // The resident sweep cannot hand a quiz over to the fix of pole_kernels.hip here -- its record goes to another process, where a "-4,
   // take the launched path" means nothing -- so while that fix is on (the default) this selection is always launched, with the fix
   // behind it: a late quiz state gets the reference-order sums on the sharded path as on the single-engine one.
-  if (_optServer && !_optPoleFix && ServerUsable()) return ServerPost(q, (SelectResult *)pOut, (uint64_t *)pFlag, flagValue, _qFirst | (int64_t)kServerNoWatch);
+  if (_opt.server && !_opt.poleFix && ServerUsable()) return ServerPost(q, (SelectResult *)pOut, (uint64_t *)pFlag, flagValue, _qFirst | (int64_t)kServerNoWatch);
   const FusedSelect fs{_dSelScratch, (SelectResult *)pOut, (uint64_t *)pFlag, NextLaunchTag(), _qFirst, 0, flagValue, nullptr, 0, 0, nullptr, nullptr};
   StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
   return LaunchSingleSweep(q, &fs);
@@ -300,7 +300,7 @@ int64_t HipEngine::NextQuestionArgmax(Error &err, int64_t iQuiz) { return Combin
 // Synchronous single-quiz selections of a Double engine through a register shape (whose finisher knows whether anything was listed):
 // the fix of pole_kernels.hip is launched only when the sweep says so (FusedSelect::lazyFix) -- one launch per selection of a fresh quiz.
 bool HipEngine::LazyFix() const {
-  return _optPoleFix && _optPoleLazy && _optPoleFollow && _elem == 8 && !UseClusterSweep() && EvalVariantHasFinisherWorkgroup(View(), (int)_optEvalVariant);
+  return _opt.poleFix && _opt.poleLazy && _opt.poleFollow && _elem == 8 && !UseClusterSweep() && EvalVariantHasFinisherWorkgroup(View(), (int)_opt.evalVariant);
 }
 Error HipEngine::SettlePoleList() {
   if (!_poleListPending) return Error();
@@ -330,8 +330,8 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   hipSetDevice(_device);
   err = FlushUpdates();
   if (!err.ok()) return -1;
-  if (_optUseGraph && _elem == 8) return NextQuestionArgmaxGraph(err, q);
-  if (_optServer && !q->noServer && ServerUsable()) {
+  if (_opt.useGraph && _elem == 8) return NextQuestionArgmaxGraph(err, q);
+  if (_opt.server && !q->noServer && ServerUsable()) {
     // resident sweep: post the request, poll the answer -- no launch on the critical path
     const uint64_t value = kServerFlagBase | ++_opSeq;   // (its own range: see kGraphFlagBase)
     err = ServerPost(q, &_hPinned->sel, &_hPinned->seq, value, 0);
@@ -354,7 +354,7 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   if (TakeSpeculation(q, 1 << 1, &seq) != 0) fs = _spec.fs;   // (RecordAnswer has launched this very sweep already)
   else {
     seq = NextLaunchTag();
-    fs = FusedSelect{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, 0, 0, nullptr, nullptr, LazyFix() && q->lateStreak < _optLateEager ? 1 : 0};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
+    fs = FusedSelect{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, 0, 0, nullptr, nullptr, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
     StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
     err = LaunchSingleSweep(q, &fs);
     if (!err.ok()) return -1;
@@ -400,18 +400,18 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
   //  0.61 / 0.41, 128: 0.77 / 0.76, 192: 1.29 / 1.15, 256: 1.21 / 1.47 -- as before; 2000 x 5 x 2000 32: 1.24 / 1.10, 48: 1.55 / 2.00,
   //  64: 1.53 / 1.99, 128: 2.35 / 3.84 -- the row-sharing sweep from 33 quizzes on where rows are longer than 1024 targets and it has a
   //  thousand such waves; 4000 x 5 x 4000 and 10000 x 5 x 10000: from 32 quizzes, as before)
-  const int64_t qb = _optBatchQb > 0 ? _optBatchQb : (_elem == 4 ? 4 : 2), wavesRowSharing = ((n + 63) / 64) * ((_Q + qb - 1) / qb);
+  const int64_t qb = _opt.batchQb > 0 ? _opt.batchQb : (_elem == 4 ? 4 : 2), wavesRowSharing = ((n + 63) / 64) * ((_Q + qb - 1) / qb);
   bool rowSharing = _elem == 4 || wantPriorities ||
-                    (_optBatchMin > 0 ? n >= _optBatchMin : (n >= 32 && (wavesRowSharing >= 1536 || (n > 32 && _ldT > 1024 && wavesRowSharing >= 1000))));
+                    (_opt.batchMin > 0 ? n >= _opt.batchMin : (n >= 32 && (wavesRowSharing >= 1536 || (n > 32 && _ldT > 1024 && wavesRowSharing >= 1000))));
   // ... and between the two, for a few dozen quizzes over short rows (a server's combined sweeps): a lane is a (quiz, chunk of the
   // row) -- batch_kernels.hip: eval_midbatch_kernel.  Option batch_form: 0 = by these rules, 1 grid.y = quiz, 2 row-sharing, 3 this one.
   // By the measured costs at 1000 x 5 x 1000 (tools/midbatch_bench.py): grid.y ~11.3 us per quiz + 25; this form 87 / 138 / 229 us for up
   // to 8 / 16 / 32 quizzes (its lanes come in 8, 16 or 32 quiz slots) and 6.2 us per slot of 64 beyond: it won at 7 and 8 quizzes and from
   // 11 on, except 17 and 18.  Round 6, measured again (grid.y / this form, us per batch): 6: 91 / 91, 7: 103 / 92, 9: 145 / 133, 10: 157 / 134,
   // 12: 182 / 131, 17: 248 / 213, 18: 260 / 211, 24: 339 / 214, 32: 443 / 221 -- from seven quizzes on.
-  bool mid = EvalMidBatchSupported(View()) && ((_optBatchForm == 0 && !rowSharing && n >= 7) || _optBatchForm == 3);
-  if (_optBatchForm == 1 && _elem == 8) { rowSharing = false; mid = false; }   // (with priorities wanted too: the quizzes' own vectors, CollectBatchPriorities)
-  if (_optBatchForm == 2) { rowSharing = true; mid = false; }
+  bool mid = EvalMidBatchSupported(View()) && ((_opt.batchForm == 0 && !rowSharing && n >= 7) || _opt.batchForm == 3);
+  if (_opt.batchForm == 1 && _elem == 8) { rowSharing = false; mid = false; }   // (with priorities wanted too: the quizzes' own vectors, CollectBatchPriorities)
+  if (_opt.batchForm == 2) { rowSharing = true; mid = false; }
   if (mid) rowSharing = false;
   if (hostPriorities) {
     wantPriorities = rowSharing;   // (the row-sharing sweep keeps its priority matrix; grid.y = quiz writes per-quiz vectors anyway)
@@ -455,7 +455,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
   // grid.y = quiz and the priorities wanted on the host: every workgroup stores the priorities of its questions there itself, one
   // {priority, launch tag} record each (as the single-quiz sweep's hand-over, FusedSelect::hostPriority) -- no copy behind the
   // sweep and no event: the quiz's flag says that every workgroup has reported, an entry is taken once it carries the tag
-  const bool tagged = hostPriorities && !rowSharing && (mid || EvalVariantHasFinisherWorkgroup(View(), (int)_optEvalVariant));
+  const bool tagged = hostPriorities && !rowSharing && (mid || EvalVariantHasFinisherWorkgroup(View(), (int)_opt.evalVariant));
   if (pTagged) *pTagged = tagged;
   if (tagged) {
     const size_t doubles = 2 * (size_t)n * (size_t)_Q;
@@ -521,22 +521,22 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
     BatchPlan pp{};
     pp.poleBytes = EvalBatchPoleBytes(kbv, (int)n);
     HIP_TRY(growPole(pp));
-    HIP_TRY(LaunchEvalQuestionsBatch(kbv, c.dSlots, (int)n, 0, _Q, (int)_optEvalVariant, fs, _stream, pp.pole));
+    HIP_TRY(LaunchEvalQuestionsBatch(kbv, c.dSlots, (int)n, 0, _Q, (int)_opt.evalVariant, fs, _stream, pp.pole));
     if (hostPriorities && !tagged) return copyToHost(c.dPriority, (size_t)n * (size_t)_Q);
     return Error();
   }
   const KbView kb = View();
   BatchPlan plan{};
-  plan.tileTargets = (int)_optBatchTile;
-  plan.questionsPerBlock = (int)_optBatchQb;
-  plan.questionGroups = (int)_optBatchGroups;
-  plan.splitTail = (int)_optBatchTail;
+  plan.tileTargets = (int)_opt.batchTile;
+  plan.questionsPerBlock = (int)_opt.batchQb;
+  plan.questionGroups = (int)_opt.batchGroups;
+  plan.splitTail = (int)_opt.batchTail;
   HIP_TRY(LaunchEvalBatch(kb, c.dSlots, (int)n, &plan, nullptr, nullptr, nullptr, nullptr, 0, tag, true, _stream));
   HIP_TRY(grow(&c.dPT, c.ptBytes, plan.ptBytes));
   HIP_TRY(grow((void **)&c.dAcc, c.accBytes, plan.accBytes));
   HIP_TRY(grow((void **)&c.dRecs, c.recBytes, plan.recBytes));
   // Float engines: the fp32 sweep nominates every quiz's best questions, fp64 decides among them (option "rerank", default on)
-  const bool rerank = _elem == 4 && _optRerank != 0 && !devicePriorities;   // (an argmax device: the sampled selector reads the matrix itself)
+  const bool rerank = _elem == 4 && _opt.rerank != 0 && !devicePriorities;   // (an argmax device: the sampled selector reads the matrix itself)
   HIP_TRY(growPole(plan));
   const bool matrix = wantPriorities || devicePriorities || rerank || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
   if (matrix) HIP_TRY(grow((void **)&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
@@ -702,7 +702,7 @@ Error HipEngine::ValidateBatchLocked(int64_t n, const int64_t *pQuizzes) {   // 
 }
 
 Error HipEngine::LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag) {
-  const int64_t nSub = _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;  // reference PqaCore/CpuEngine.cpp:339
+  const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
   std::memcpy(c.h->rnd, pRnd, (size_t)n * sizeof(uint64_t));   // (host-coherent: the selector reads them there)
   size_t grandDoubles = 0, runDoubles = 0;
   SelectSampledBatchScratch(_Q, nSub, (int)n, c.lastBp, &grandDoubles, &runDoubles);
@@ -724,12 +724,12 @@ Error HipEngine::LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd
   a.qgap = _dQGap; a.n = _Q; a.nWorkers = nSub;
   a.rnd = c.h->rnd; a.grand = c.dSelGrand; a.run = c.dSelRun;
   a.out = c.h->out; a.seq = c.h->seq; a.flagValue = tag; a.outBase = 0;
-  if (_optTimeSweeps) {
+  if (_opt.timeSweeps) {
     if (!c.evSel[0]) { HIP_TRY(hipEventCreate(&c.evSel[0])); HIP_TRY(hipEventCreate(&c.evSel[1])); }
     HIP_TRY(hipEventRecord(c.evSel[0], _stream));
   }
   HIP_TRY(LaunchSelectSampledBatch(a, _stream));
-  if (_optTimeSweeps) HIP_TRY(hipEventRecord(c.evSel[1], _stream));
+  if (_opt.timeSweeps) HIP_TRY(hipEventRecord(c.evSel[1], _stream));
   return Error();
 }
 
@@ -742,9 +742,9 @@ Error HipEngine::NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizz
   if (!err.ok()) return err;
   BatchCtx &c = _ctx[0];
   const uint64_t tag = NextLaunchTag();
-  const int64_t nSub = _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;
+  const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;
   std::vector<int64_t> picks((size_t)n, -1);
-  if (_optSampledBatchHost) {
+  if (_opt.sampledBatchHost) {
     // the A/B leg: the priorities to the host as a combined sweep delivers them, the host's selector per quiz (SelectFromPriorities)
     while (c.readers.load(std::memory_order_acquire) != 0) _mm_pause();   // (clients of an earlier combined sweep still read hPri)
     bool quizMinor = false, tagged = false;
@@ -786,7 +786,7 @@ Error HipEngine::NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizz
       CheckPriority(c.h->out[i].priority, c.h->out[i].index);
       picks[(size_t)i] = c.h->out[i].index;
     }
-    if (_optTimeSweeps && c.evSel[1]) {
+    if (_opt.timeSweeps && c.evSel[1]) {
       float ms = 0;
       if (hipEventSynchronize(c.evSel[1]) == hipSuccess && hipEventElapsedTime(&ms, c.evSel[0], c.evSel[1]) == hipSuccess) _sampledBatchDeviceNs += (uint64_t)(ms * 1e6);
       else (void)hipGetLastError();
@@ -809,7 +809,7 @@ Error HipEngine::NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, co
 // What a server calls: by option "select".  select = 0: one number per quiz from the engine's generator, in batch order, as
 // nQuizzes consecutive NextQuestion calls would draw them -- after the batch has been validated, so that a refused call draws nothing.
 Error HipEngine::NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) {
-  if (_optSelect == 1) return NextQuestionArgmaxBatch(n, pQuizzes, pOut);
+  if (_opt.select == 1) return NextQuestionArgmaxBatch(n, pQuizzes, pOut);
   std::lock_guard<std::mutex> selLk(_ctx[0].mu);
   std::lock_guard<EngineMutex> lk(_mu);
   Error err = ValidateBatchLocked(n, pQuizzes);
@@ -818,7 +818,7 @@ Error HipEngine::NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *
   std::vector<uint64_t> rnd((size_t)n);
   {
     std::lock_guard<std::mutex> rk(_rngMu);
-    for (int64_t i = 0; i < n; i++) rnd[(size_t)i] = NextRandom();
+    for (int64_t i = 0; i < n; i++) rnd[(size_t)i] = _rng.Next();
   }
   return NextQuestionSampledBatchLocked(n, pQuizzes, rnd.data(), pOut);
 }
@@ -839,7 +839,7 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
     _graphTag = one;
   }
   auto it = _graphs.find(q);
-  if (it == _graphs.end() || it->second.variant != _optEvalVariant || it->second.stream != _stream ||
+  if (it == _graphs.end() || it->second.variant != _opt.evalVariant || it->second.stream != _stream ||
       it->second.kbVersion != _kbVersion) {
     if (it != _graphs.end()) { hipGraphExecDestroy(it->second.exec); _graphs.erase(it); }
     const FusedSelect fs{_dGraphScratch, &_hPinned->sel, &_hPinned->seq, 0, 0, 0, 0, _dTagCell, 0, 0, nullptr, nullptr};
@@ -847,14 +847,14 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
     hipGraphExec_t exec = nullptr;
     hipError_t he = hipStreamBeginCapture(_stream, hipStreamCaptureModeThreadLocal);
     if (he == hipSuccess) {
-      const hipError_t le = LaunchEvalQuestions(View(), q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_optEvalVariant, &fs, _stream);
+      const hipError_t le = LaunchEvalQuestions(View(), q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
       he = hipStreamEndCapture(_stream, &graph);
       if (he == hipSuccess) he = le;
     }
     if (he == hipSuccess) he = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     if (graph) hipGraphDestroy(graph);
     if (he != hipSuccess) { err = HipErr(he, "graph capture of the selection"); return -1; }
-    it = _graphs.emplace(q, GraphEntry{exec, _optEvalVariant, _stream, _kbVersion}).first;
+    it = _graphs.emplace(q, GraphEntry{exec, _opt.evalVariant, _stream, _kbVersion}).first;
   }
   const uint64_t expect = _graphTag;
   StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
@@ -883,8 +883,8 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
   err = FlushUpdates();
   if (!err.ok()) return -1;
   const KbView kb = View();
-  const int64_t nSub = _optEvalSubtasks ? _optEvalSubtasks : 8 * _optWorkers;  // reference PqaCore/CpuEngine.cpp:339
-  if (_optServer && !q->noServer && _optHostSampled && !_optFusedSampled && ServerUsable()) {
+  const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
+  if (_opt.server && !q->noServer && _opt.hostSampled && !_opt.fusedSampled && ServerUsable()) {
     // resident sweep: post the request with the hand-over mark, poll the flag, select on the host -- no launch on the path
     const uint64_t value = kServerFlagBase | ++_opSeq;   // (its own range: see kGraphFlagBase)
     err = ServerPost(q, &_hPinned->sel, &_hPinned->seq, value, (int64_t)kServerHandOver);
@@ -903,7 +903,7 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
   const int took = TakeSpeculation(q, (1 << 2) | (1 << 3), &specTag);   // 2 / 3: RecordAnswer has launched the sweep already
   const bool speculated = took == 2;
   if (took == 0) StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
-  if (took != 3 && _optHostSampled && !_optFusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_optEvalVariant)) {
+  if (took != 3 && _opt.hostSampled && !_opt.fusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_opt.evalVariant)) {
     // ONE launch, and the selection on the host: the sweep's finisher workgroup copies the finished priority vector (8 bytes per
     // question) into host-coherent memory and sets the flag; the selector's O(Q) scalar Kahan steps take the host a few
     // microseconds -- less than the dispatch of the selector kernel they replace.
@@ -915,8 +915,8 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     else {
       { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
       seq = NextLaunchTag();
-      fs = FusedSelect{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, 1, 0, nullptr, _hHostPriority, LazyFix() && q->lateStreak < _optLateEager ? 1 : 0};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
-      const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_optEvalVariant, &fs, _stream);
+      fs = FusedSelect{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, 1, 0, nullptr, _hHostPriority, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
+      const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
       if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
       if (fs.lazyFix) _poleListPending = true;   // (as NextQuestionArgmaxLocked)
     }
@@ -938,12 +938,12 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     const int64_t sel = SelectSampledHostBits(_hostRun.data(), _Q, nSub, rnd, _hQGap.data(), q->hAsked.data());
     return FinishSelection(err, q, sel);
   }
-  if (took != 3 && _optFusedSampled && _elem == 8 && EvalVariantFusesSampled(kb, (int)_optEvalVariant, nSub)) {
+  if (took != 3 && _opt.fusedSampled && _elem == 8 && EvalVariantFusesSampled(kb, (int)_opt.evalVariant, nSub)) {
     // ONE launch: the sweep's finisher workgroup runs the reference's selector once every workgroup has reported
     { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
     const uint64_t seq = NextLaunchTag();
     const FusedSelect fs{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, nSub, rnd, _dRunLength, nullptr};
-    const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_optEvalVariant, &fs, _stream);
+    const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
     if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
     err = WaitFlag(&_hPinned->seq, seq, "NextQuestionSampled");
     if (!err.ok()) return -1;
@@ -968,9 +968,9 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
 }
 
 int64_t HipEngine::NextQuestion(Error &err, int64_t iQuiz) {
-  if (_optSelect == 1) return Combine(err, iQuiz, 0, 0);
+  if (_opt.select == 1) return Combine(err, iQuiz, 0, 0);
   uint64_t rnd;
-  { std::lock_guard<std::mutex> lk(_rngMu); rnd = NextRandom(); }   // (drawn when the call arrives, whatever sweep serves it)
+  { std::lock_guard<std::mutex> lk(_rngMu); rnd = _rng.Next(); }   // (drawn when the call arrives, whatever sweep serves it)
   return Combine(err, iQuiz, 1, rnd);
 }
 

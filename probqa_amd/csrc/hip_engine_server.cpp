@@ -6,7 +6,7 @@ namespace pqa {
 // ------------------------------------------------------------------------------------------------------------------
 // resident sweep (pqa_kernels.h: ServerMailbox; eval_kernels.hip: eval_server_f64)
 // ------------------------------------------------------------------------------------------------------------------
-bool HipEngine::ServerUsable() const { return _elem == 8 && EvalServerSupported(View(), (int)_optEvalVariant) && _Q > 0; }
+bool HipEngine::ServerUsable() const { return _elem == 8 && EvalServerSupported(View(), (int)_opt.evalVariant) && _Q > 0; }
 
 void HipEngine::StopServer() {
   (void)FlushUpdates();   // whoever stops the resident sweep is about to read or change what the deferred updates read or write
@@ -67,7 +67,7 @@ Error HipEngine::ServerPost(Quiz *q, SelectResult *out, uint64_t *flag, uint64_t
     // the kernel's polls become local reads.  Where the platform does not map it, the mailbox's own first line is used.
     void *vram = nullptr;
     int largeBar = 0;
-    if (_optServerVramMailbox && hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, _device) == hipSuccess && largeBar &&
+    if (_opt.serverVramMailbox && hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, _device) == hipSuccess && largeBar &&
         hipExtMallocWithFlags(&vram, 64, hipDeviceMallocFinegrained) == hipSuccess && vram != nullptr) {
       _serverRequest = (volatile uint64_t *)vram;   // large BAR: the device address is valid on the host as well
       _serverRequestInVram = true;
@@ -78,7 +78,7 @@ Error HipEngine::ServerPost(Quiz *q, SelectResult *out, uint64_t *flag, uint64_t
     }
     if (!_serverRequestInVram) _serverRequest = &_hMailbox->req;
   }
-  if (_serverLaunched && (_serverKb != _kbVersion || _serverVariant != _optEvalVariant)) StopServer();
+  if (_serverLaunched && (_serverKb != _kbVersion || _serverVariant != _opt.evalVariant)) StopServer();
   volatile ServerMailbox *mb = _hMailbox;
   // the previous request's fields must have been read before they are overwritten
   if (_serverLaunched && _serverPosted != 0) {
@@ -124,12 +124,12 @@ Error HipEngine::ServerPost(Quiz *q, SelectResult *out, uint64_t *flag, uint64_t
   mb->state = kServerRunning;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   HIP_TRY(EnsureHostPriority());   // (a launch argument of the resident kernel: requests may ask for the priority vector)
-  HIP_TRY(LaunchEvalServer(View(), 0, _Q, _dPriority, (int)_optEvalVariant, _dSelScratch, _hMailbox, (void *)_serverRequest, _serverRequestInVram, _dServerCtl, prev,
-                           (uint64_t)_optServerIdleUs * 100, _hHostPriority, _serverStream,
-                           _optPoleFix != 0));   // 100 MHz ticks
+  HIP_TRY(LaunchEvalServer(View(), 0, _Q, _dPriority, (int)_opt.evalVariant, _dSelScratch, _hMailbox, (void *)_serverRequest, _serverRequestInVram, _dServerCtl, prev,
+                           (uint64_t)_opt.serverIdleUs * 100, _hHostPriority, _serverStream,
+                           _opt.poleFix != 0));   // 100 MHz ticks
   _serverLaunched = true;
   _serverKb = _kbVersion;
-  _serverVariant = _optEvalVariant;
+  _serverVariant = _opt.evalVariant;
   return Error();
 }
 

@@ -159,7 +159,7 @@ Error HipEngine::TrainRecordsLocked(const std::vector<TrainRecord> &recs, bool f
   for (int s = 0; s < 2; s++)
     for (hipEvent_t &e : b.ev[s])
       if (!e) HIP_TRY(hipEventCreate(&e));
-  const int64_t cap = _optTrainChunkSteps;
+  const int64_t cap = _opt.trainChunkSteps;
   int slot = 0;
   uint64_t launches = 0;
 

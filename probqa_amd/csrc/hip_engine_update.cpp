@@ -8,14 +8,14 @@ namespace pqa {
 // ------------------------------------------------------------------------------------------------------------------
 Error HipEngine::RecordAnswerImpl(int64_t iQuiz, int64_t iAnswer, bool remote) {
   CallScope scope(_activeCallers);
-  if (_optCombine && (_optPostAlways || !_mu.try_lock())) {   // somebody is inside the engine: it runs this call's bookkeeping on its way out
+  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {   // somebody is inside the engine: it runs this call's bookkeeping on its way out
     PostedOp op;
     op.kind = 1; op.iQuiz = iQuiz; op.arg = iAnswer; op.remote = remote;
     PostAndWait(_mu, op);
     return op.err;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_optCombine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
   else lk.lock();
   return RecordAnswerLocked(iQuiz, iAnswer, remote, !Concurrent());
 }
@@ -47,7 +47,7 @@ Error HipEngine::StartQuizBatch(int64_t n, int64_t *pQuizzes) {
   Error err;
   auto launch = [&]() -> Error {
     if (batch.n == 0) return Error();
-    HIP_TRY(LaunchStartQuizBatch(View(), batch, _optWorkers, _stream));
+    HIP_TRY(LaunchStartQuizBatch(View(), batch, _opt.workers, _stream));
     batch.n = 0;
     return Error();
   };
@@ -151,8 +151,8 @@ Error HipEngine::FlushUpdates() {
   hipSetDevice(_device);
   ServerQuiesce();
   // NLooseWorkers = max(1, hw - 1): reference PqaCore/CEQuiz.h:98, PqaCore/BaseCpuEngine.cpp:22
-  const int64_t nLoose = std::max<int64_t>(1, _optWorkers - 1);
-  const int64_t topCount = _T <= 16384 ? std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(_optTopCache, _topWantRecent), kQuizTop), _T) : 0;
+  const int64_t nLoose = std::max<int64_t>(1, _opt.workers - 1);
+  const int64_t topCount = _T <= 16384 ? std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(_opt.topCache, _topWantRecent), kQuizTop), _T) : 0;
   auto listed = [&](Quiz *q, uint64_t op) { q->topOp = op; q->topVersion = q->priorVersion; q->topCount = topCount; };
   auto counted = [&](size_t n) {
     _flushes++;
@@ -213,29 +213,29 @@ Error HipEngine::FlushUpdates() {
 bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
   const bool withUpdate = updQuestion >= 0;
   if (!withUpdate) DropSpeculation();   // (one at a time: the hand-over buffers are the engine's)
-  if (!_optSpeculate || (_optServer && !q->noServer) || _optUseGraph || _qTotal != _Q || _Q <= 0) return false;   // (a quiz the resident sweep has handed over -- rows at the pole of the lack term -- is served as if there were none)
-  if (_optServer && _serverLaunched) return false;   // (a launched sweep has no room beside the resident one: this quiz's last selection has sent it away, unless another quiz called it back)
+  if (!_opt.speculate || (_opt.server && !q->noServer) || _opt.useGraph || _qTotal != _Q || _Q <= 0) return false;   // (a quiz the resident sweep has handed over -- rows at the pole of the lack term -- is served as if there were none)
+  if (_opt.server && _serverLaunched) return false;   // (a launched sweep has no room beside the resident one: this quiz's last selection has sent it away, unless another quiz called it back)
   if (Concurrent()) return false;   // (several clients: their NextQuestions are served together, by a batched sweep)
-  if (withUpdate && (!_optFuseUpdate || _specScore < -4)) return false;
+  if (withUpdate && (!_opt.fuseUpdate || _specScore < -4)) return false;
   if (_specScore < -4 && (++_specProbe & 31) != 0) return false;   // the client does not follow RecordAnswer with NextQuestion: probe now and then
   const KbView kb = View();
   int kind = 0;
-  if (_optSelect == 1) kind = 1;
-  else if (_optHostSampled && !_optFusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_optEvalVariant)) kind = 2;
-  else if (!(_optFusedSampled && _elem == 8)) kind = 3;   // Float engines, long rows: the sweep now, the selector kernel at NextQuestion
+  if (_opt.select == 1) kind = 1;
+  else if (_opt.hostSampled && !_opt.fusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_opt.evalVariant)) kind = 2;
+  else if (!(_opt.fusedSampled && _elem == 8)) kind = 3;   // Float engines, long rows: the sweep now, the selector kernel at NextQuestion
   if (kind == 0) return false;
-  const int64_t nLoose = std::max<int64_t>(1, _optWorkers - 1);   // reference PqaCore/CEQuiz.h:98, PqaCore/BaseCpuEngine.cpp:22
-  if (withUpdate && (kind == 3 || UseClusterSweep() || !EvalFusesUpdate(kb, (int)_optEvalVariant, nLoose))) return false;
+  const int64_t nLoose = std::max<int64_t>(1, _opt.workers - 1);   // reference PqaCore/CEQuiz.h:98, PqaCore/BaseCpuEngine.cpp:22
+  if (withUpdate && (kind == 3 || UseClusterSweep() || !EvalFusesUpdate(kb, (int)_opt.evalVariant, nLoose))) return false;
   if (kind == 2 && EnsureHostPriority() != hipSuccess) return false;
   if (withUpdate) DropSpeculation();
   const uint64_t seq = NextLaunchTag();
   if (!SettlePoleList().ok()) return false;
   const FusedSelect fs{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, kind == 2 ? 1 : 0, 0, nullptr,
-                       kind == 2 ? _hHostPriority : nullptr, (kind == 1 || kind == 2) && LazyFix() && q->lateStreak < _optLateEager ? 1 : 0};
+                       kind == 2 ? _hHostPriority : nullptr, (kind == 1 || kind == 2) && LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0};
   if (withUpdate) {
-    const int64_t topCount = std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(_optTopCache, _topWantRecent), kQuizTop), _T);
+    const int64_t topCount = std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(_opt.topCache, _topWantRecent), kQuizTop), _T);
     const uint64_t op = _opSeq + 1;
-    if (LaunchEvalQuestionsWithUpdate(kb, q->dPrior, q->dAsked, _dPriority, (int)_optEvalVariant, fs, updQuestion, updAnswer, nLoose, q->pin->top,
+    if (LaunchEvalQuestionsWithUpdate(kb, q->dPrior, q->dAsked, _dPriority, (int)_opt.evalVariant, fs, updQuestion, updAnswer, nLoose, q->pin->top,
                                       &q->pin->nOut, &q->pin->topFlag, op, topCount, _stream) != hipSuccess) {
       (void)hipGetLastError();   // the usual way: posterior kernel, then the sweep
       return false;
@@ -246,13 +246,13 @@ bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
     if (_maxFlush < 1) _maxFlush = 1;
   } else if (kind == 1   ? !LaunchSingleSweep(q, &fs).ok()
              : kind == 3 ? !LaunchSingleSweep(q, nullptr).ok()
-                         : LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_optEvalVariant, &fs, _stream) != hipSuccess) {
+                         : LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream) != hipSuccess) {
     (void)hipGetLastError();   // NextQuestion will launch for itself and report
     return false;
   }
   _spec.quiz = q; _spec.priorVersion = q->priorVersion; _spec.tag = seq; _spec.kind = kind; _spec.fs = fs;
   if (fs.lazyFix) _poleListPending = true;
-  _spec.variant = _optEvalVariant; _spec.stream = _stream;
+  _spec.variant = _opt.evalVariant; _spec.stream = _stream;
   _pendingRecordOp = 0;   // the posterior kernel's flag no longer says that the stream is idle
   _pendingRecordFlag = nullptr;
   _mu.busy = true;
@@ -265,7 +265,7 @@ bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
 int HipEngine::TakeSpeculation(Quiz *q, int kindMask, uint64_t *pTag) {
   if (_spec.quiz == nullptr) return 0;
   const bool match = _spec.quiz == q && ((kindMask >> _spec.kind) & 1) && _spec.priorVersion == q->priorVersion && _spec.tag == _selSeq &&
-                     _spec.variant == _optEvalVariant && _spec.stream == _stream && (!_optServer || q->noServer) && !_optUseGraph;
+                     _spec.variant == _opt.evalVariant && _spec.stream == _stream && (!_opt.server || q->noServer) && !_opt.useGraph;
   if (!match) { DropSpeculation(); return 0; }
   _spec.quiz = nullptr;
   _specHits++;
@@ -351,7 +351,7 @@ static bool ListingHasTies(const CiRatedTarget *got, int64_t nGot, int64_t maxCo
 }
 
 int64_t HipEngine::ListTopTargets(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedTarget *pDest) {
-  if (maxCount <= 0 || pDest == nullptr || !_optTopExact) return ListTopTargetsFast(err, iQuiz, maxCount, pDest);
+  if (maxCount <= 0 || pDest == nullptr || !_opt.topExact) return ListTopTargetsFast(err, iQuiz, maxCount, pDest);
   const int64_t probed = std::min<int64_t>(maxCount, _T) + 1;   // (one beyond the list: the boundary)
   CiRatedTarget small[kQuizTop + 1];
   std::vector<CiRatedTarget> large;
@@ -387,7 +387,7 @@ int64_t HipEngine::ListTopTargetsExact(Error &err, int64_t iQuiz, int64_t maxCou
   TopBatchPriors pr;
   pr.prior[0] = q->dPrior;
   const uint64_t op = ++_opSeq;
-  const hipError_t he = LaunchTopTargetsExact(View(), pr, 1, _optWorkers, want, _dTopExact, _hPinned->top, &_hPinned->nOut, &_hPinned->topFlag, op, _stream);
+  const hipError_t he = LaunchTopTargetsExact(View(), pr, 1, _opt.workers, want, _dTopExact, _hPinned->top, &_hPinned->nOut, &_hPinned->topFlag, op, _stream);
   if (he != hipSuccess) { err = HipErr(he, "ListTopTargets"); return -1; }
   err = WaitFlag(&_hPinned->topFlag, op, "ListTopTargets");
   if (!err.ok()) return -1;
@@ -400,7 +400,7 @@ int64_t HipEngine::ListTopTargetsExact(Error &err, int64_t iQuiz, int64_t maxCou
 }
 
 Error HipEngine::EnsureTopExactScratch(int64_t nQuizzes, int64_t want) {
-  const size_t need = TopExactScratchBytes(_T, _optWorkers, want, nQuizzes);
+  const size_t need = TopExactScratchBytes(_T, _opt.workers, want, nQuizzes);
   if (need <= _topExactBytes) return Error();
   HIP_TRY(hipStreamSynchronize(_stream));
   if (_dTopExact) hipFree(_dTopExact);
@@ -413,8 +413,8 @@ Error HipEngine::EnsureTopExactScratch(int64_t nQuizzes, int64_t want) {
 int64_t HipEngine::ListTopTargetsFast(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedTarget *pDest) {
   CallScope scope(_activeCallers);
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (!_optCombine || maxCount <= 0 || pDest == nullptr) lk.lock();
-  else if (!_optPostAlways && _mu.try_lock()) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  if (!_opt.combine || maxCount <= 0 || pDest == nullptr) lk.lock();
+  else if (!_opt.postAlways && _mu.try_lock()) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
   else {
     // somebody is inside the engine: it launches what this call needs on its way out (the quiz's deferred update among all that
     // have gathered, the listing if the update kernel has not made it); the wait for the quiz's own lines is this thread's
@@ -439,7 +439,7 @@ int64_t HipEngine::ListTopTargetsFast(Error &err, int64_t iQuiz, int64_t maxCoun
   if (maxCount <= 0) return 0;
   if (!pDest) { err = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the destination."); return -1; }
   hipSetDevice(_device);
-  if (q->updatePending && _optLingerUs > 0 && Concurrent()) {
+  if (q->updatePending && _opt.lingerUs > 0 && Concurrent()) {
     // Group commit.  This quiz's RecordAnswer is deferred, and the clients that got their questions from the same combined sweep
     // are recording their answers right now: give them a moment, so that ONE launch runs all of them.  Whoever comes out of the
     // wait first launches; the others find their update on its way.
@@ -447,7 +447,7 @@ int64_t HipEngine::ListTopTargetsFast(Error &err, int64_t iQuiz, int64_t maxCoun
     if (_pendingUpdates.size() < target) {
       lk.unlock();
       const auto t0 = std::chrono::steady_clock::now();
-      const auto limit = std::chrono::microseconds(_optLingerUs);
+      const auto limit = std::chrono::microseconds(_opt.lingerUs);
       for (;;) {
         const size_t have = _pendingCount.load(std::memory_order_relaxed);
         if (have == 0 || have >= target) break;   // (0: somebody has launched them)
@@ -537,7 +537,7 @@ int64_t HipEngine::ListTopTargetsOnHost(Error &err, Quiz *q, int64_t want, CiRat
     // CEListTopTargetsAlgorithm::RunHeapifyBased (CEListTopTargetsAlgorithm.cpp:30-95) as written, with the C++ library's own heap calls
     struct Rated { int64_t t; double p; bool operator<(const Rated &o) const { return p < o.p; } };
     struct Head { double p; int64_t piece; bool operator<(const Head &o) const { return p < o.p; } };
-    const int64_t W = _optWorkers, quot = _T / W, rem = _T % W, nSub = quot == 0 ? rem : W;
+    const int64_t W = _opt.workers, quot = _T / W, rem = _T % W, nSub = quot == 0 ? rem : W;
     std::vector<Rated> ratings((size_t)_T);
     std::vector<int64_t> start((size_t)nSub), lim((size_t)nSub);
     for (int64_t i = 0; i < nSub; i++) {
@@ -620,7 +620,7 @@ Error HipEngine::ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t
   err = FlushUpdates();
   if (!err.ok()) return err;
   const int64_t want = std::min<int64_t>(maxCount, _T);
-  const bool exact = _optTopExact != 0;
+  const bool exact = _opt.topExact != 0;
   if (want > 256) {
     for (int64_t i = 0; i < n; i++) {
       // (bulk exports: on the host, in the reference's order right away)
@@ -671,7 +671,7 @@ Error HipEngine::ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t
     const int64_t m = std::min<int64_t>(tgroup, (int64_t)(tied.size() - first));
     TopBatchPriors pr;
     for (int64_t i = 0; i < m; i++) pr.prior[i] = quizzes[(size_t)tied[first + (size_t)i]]->dPrior;
-    HIP_TRY(LaunchTopTargetsExact(View(), pr, m, _optWorkers, want, _dTopExact, _hTopBatch, hCounts, nullptr, 0, _stream));   // (want <= probe: the lines hold it)
+    HIP_TRY(LaunchTopTargetsExact(View(), pr, m, _opt.workers, want, _dTopExact, _hTopBatch, hCounts, nullptr, 0, _stream));   // (want <= probe: the lines hold it)
     HIP_TRY(hipStreamSynchronize(_stream));
     for (int64_t i = 0; i < m; i++) {
       const int64_t at = tied[first + (size_t)i], c = std::min<int64_t>(hCounts[i], want);
@@ -710,7 +710,7 @@ void HipEngine::AppendTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::
     for (; i < n - 1; i += 2) perform2(pAQs[i], pAQs[i + 1]);
     if (i == n - 1) perform1(pAQs[i]);
   } else {
-    const int64_t nWorkers = _optWorkers;
+    const int64_t nWorkers = _opt.workers;
     scratch.assign((size_t)(nWorkers + n), -1);   // [last per bucket | prev per entry]
     int64_t *last = scratch.data(), *prev = last + nWorkers;
     for (int64_t i = 0; i < n; i++) {
@@ -831,14 +831,14 @@ Error HipEngine::RecordQuizTarget(int64_t iQuiz, int64_t iTarget, double amount)
   if (amount <= 0)
     return Error::MakeP(ErrCode::NonPositiveAmount, "amount=" + std::to_string(amount), "|amount| must be positive.");
   CallScope scope(_activeCallers);
-  if (_optCombine && (_optPostAlways || !_mu.try_lock())) {
+  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {
     PostedOp op;
     op.kind = 6; op.iQuiz = iQuiz; op.arg = iTarget; op.amount = amount;
     PostAndWait(_mu, op);
     return op.err;
   }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_optCombine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
+  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
   else lk.lock();
   return RecordQuizTargetLocked(iQuiz, iTarget, amount);
 }

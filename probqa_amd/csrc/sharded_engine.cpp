@@ -114,12 +114,15 @@ class ShardedEngine final : public IEngine {
     std::lock_guard<OpLock> lk(_opMu);
     Error e = FlushAnswers();
     if (!e.ok()) return e;
-    if (n == "combine") { _optCombine = value ? 1 : 0; return Error(); }          // (this engine's own combining; the shards are driven one call at a time)
-    if (n == "combine_linger_us") { if (value < 0 || value > 10000) return Error::Make(ErrCode::UnhandledCase, "Unknown option or value out of range: " + n); _optLingerUs = value; return Error(); }
+    if (n == "combine" || n == "combine_linger_us") {   // this engine's own combining (the shards are driven one call at a time)
+      if (!AcceptOption(*FindOption(name), value)) return Error::Make(ErrCode::UnhandledCase, "Unknown option or value out of range: " + n);
+      (n == "combine" ? _optCombine : _optLingerUs) = value;
+      return Error();
+    }
     e = AllLocked([&](HipEngine &sh) { return sh.SetOption(name, value); });
     if (!e.ok()) return e;   // (a value the shards refuse changes nothing here either)
     if (n == "select") _select = value;   // (kept here too: NextQuestion dispatches on it)
-    if (n == "seed") Seed((uint64_t)value);
+    if (n == "seed") _rng.Seed((uint64_t)value);
     return Error();
   }
   int64_t GetOption(const char *name) const override {
@@ -380,14 +383,6 @@ class ShardedEngine final : public IEngine {
   int64_t SelectArgmaxLocked(Error &err, int64_t iQuiz, double *pPriority);
   int64_t SelectSampledLocked(Error &err, int64_t iQuiz, uint64_t rnd);
   int64_t Commit(Error &err, int64_t iQuiz, int64_t qGlobal);
-  uint64_t NextRandom() {   // xorshift128+, the generator family of SRPlatform/Interface/SRFastRandom.h:60-72
-    uint64_t s1 = _rng[0];
-    const uint64_t s0 = _rng[1];
-    _rng[0] = s0;
-    s1 ^= s1 << 23;
-    _rng[1] = s1 ^ s0 ^ (s1 >> 18) ^ (s0 >> 5);
-    return _rng[1] + s0;
-  }
 
   // A quiz's asked-or-gap bitmap in GLOBAL numbering (64-bit packs, the bits past the last question set) out of the shards' 32-bit words
   // in local bit order (their ranges are not multiples of 32).  wordsOf(s): shard s's words, nullptr -> false.  `skip` is the caller's.
@@ -431,7 +426,7 @@ class ShardedEngine final : public IEngine {
   CombineCtx _bctx[2];                 // (mu: one combined sweep at a time in a context, and the batch calls of the ABI in context 0)
   Combiner<SelRequest, CombineCtx> _comb{_bctx};
   std::mutex _rngMu;
-  int64_t _optCombine = 1, _optLingerUs = 20;
+  int64_t _optCombine = EngineOptions().combine, _optLingerUs = EngineOptions().lingerUs;   // "combine", "combine_linger_us": kept here, not in the shards
   std::atomic<int> _activeCallers{0};
   bool Concurrent() const { return _optCombine && _activeCallers.load(std::memory_order_relaxed) > 1; }
   int64_t Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t rnd);
@@ -459,11 +454,7 @@ class ShardedEngine final : public IEngine {
   uint64_t _step = 0;
   std::vector<double> _hostPriority;
   IdLedger _questionIds;                     // global question ids
-  uint64_t _rng[2] = {0x9E3779B97F4A7C15ULL, 0xBF58476D1CE4E5B9ULL};
-  void Seed(uint64_t x) {   // SplitMix64 into the two words of the generator, as HipEngine does
-    _rng[0] = SplitMix64(x);
-    _rng[1] = SplitMix64(x);
-  }
+  SelectorRng _rng;                          // seeded by Create
   int64_t _shardsInFlightMax = 0;
   // ---- maintenance-mode edits of the dimensions (CpuEngine.cpp:468-658, BaseEngine.cpp:721-873): the ids are worked out HERE,
   // over the global question axis, exactly as the unsharded engine works them out; the data moves by REBUILDING the shards --
@@ -610,13 +601,9 @@ ShardedEngine *ShardedEngine::Create(Error &err, const CiEngineDefinition &def, 
   eng->_select = eng->_sh[0]->GetOption("select");
   {   // the selector's generator: from the system's entropy like the reference's (SRFastRandom.h:31-40), or PQA_SEED
     std::random_device rd;
-    uint64_t seed = ((uint64_t)rd() << 32) ^ rd();
-    if (const char *v = std::getenv("PQA_SEED")) {
-      char *end = nullptr;
-      const long long x = std::strtoll(v, &end, 10);
-      if (end != v && *end == 0) seed = (uint64_t)x;
-    }
-    eng->Seed(seed);
+    int64_t seed = (int64_t)(((uint64_t)rd() << 32) ^ rd());
+    (void)SeedFromEnvironment(seed, false);   // (a value that is refused: every shard has said so already)
+    eng->_rng.Seed((uint64_t)seed);
   }
   eng->_hostPriority.resize((size_t)def._nQuestions);
   eng->_questionIds.Extend(def._nQuestions);
@@ -1102,7 +1089,7 @@ int64_t ShardedEngine::SelectSampledLocked(Error &err, int64_t iQuiz, uint64_t r
 int64_t ShardedEngine::NextQuestion(Error &err, int64_t iQuiz) {
   if (_select == 1) return Combine(err, iQuiz, SelKind::Argmax, 0);
   uint64_t rnd;
-  { std::lock_guard<std::mutex> lk(_rngMu); rnd = NextRandom(); }   // (drawn when the call arrives, whatever sweep serves it)
+  { std::lock_guard<std::mutex> lk(_rngMu); rnd = _rng.Next(); }   // (drawn when the call arrives, whatever sweep serves it)
   return Combine(err, iQuiz, SelKind::Sampled, rnd);
 }
 
@@ -1372,7 +1359,7 @@ Error ShardedEngine::NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64
   std::vector<uint64_t> rnd((size_t)n);
   {
     std::lock_guard<std::mutex> lk(_rngMu);   // one number per quiz in batch order, as consecutive NextQuestion calls draw them
-    for (int64_t i = 0; i < n; i++) rnd[(size_t)i] = NextRandom();
+    for (int64_t i = 0; i < n; i++) rnd[(size_t)i] = _rng.Next();
   }
   return NextQuestionSampledBatch(n, pQuizzes, rnd.data(), pOut);
 }

@@ -1,7 +1,7 @@
 """Host bookkeeping of the engine that needs no device (runs in the CPU suite): the compact <-> permanent id map, the
-eviction rule of ClearOldQuizzes, and what the one-device and the sharded engine decide through the same code (kb_plan.h) -- the
-ids AddQsTs hands out, what Compact moves where, which removals are refused, which shard's winner is the selection -- driven
-through PqaHip_HostLogicProbe and held to a Python model of the reference's observable behaviour
+eviction rule of ClearOldQuizzes, what the one-device and the sharded engine decide through the same code (kb_plan.h) -- the
+ids AddQsTs hands out, what Compact moves where, which removals are refused, which shard's winner is the selection -- and the
+table of the engine's options (engine_options.h), driven through PqaHip_HostLogicProbe and held to a Python model of the reference's observable behaviour
 (PqaCore/PermanentIdManager.cpp, PqaCore/BaseEngine.cpp:722-765,814-873, PqaCore/CpuEngine.cpp:468-658)."""
 import ctypes
 import math
@@ -446,3 +446,74 @@ def test_malformed_plan_scripts_are_refused():
     assert probe("compact_plan", [5, 5, 3, 1], 32)[0] == -1                 # the list is cut short
     assert probe("check_removal", [5, 0, 1, 2], 1)[0] == -1
     assert probe("better_pick", [bits(1.0)], 2)[0] == -1
+
+
+# ---- the options (engine_options.h) -----------------------------------------------------------------------------------------------
+# Every option PqaHip_SetOption accepts, as SetOption, GetOption and ApplyEnvironment treated it before there was a table (this
+# list was written from those three functions, not from the table): the accepted values lo..hi, the default, whether it is a flag
+# (any integer accepted, stored as 0 or 1), the side effects of setting it, and whether a PQA_* variable presets it as an integer.
+# ("select" has PQA_SELECT, but that takes words -- sample, argmax -- and is read by itself: no integer variable.)
+STOP_SERVER, SETTLE_POLE_LIST, BUMP_KB_VERSION = 1, 2, 4
+POLE = STOP_SERVER | SETTLE_POLE_LIST
+I64_MAX = 2**63 - 1
+MAX_WORKERS = 1000
+OPTIONS = [
+    # name, lo, hi, default, flag, effects, has_env
+    ("combine", 0, 1, 1, 1, 0, 1),
+    ("combine_spin", 0, 1, 1, 1, 0, 0),
+    ("top_exact", 0, 1, 1, 1, 0, 0),
+    ("time_sweeps", 0, 1, 0, 1, 0, 0),
+    ("long_row_form", 0, 1, 1, 1, 0, 0),
+    ("rows_stage", 0, 1, 1, 1, 0, 0),
+    ("fuse_update", 0, 1, 1, 1, 0, 0),
+    ("post_always", 0, 1, 0, 1, 0, 0),
+    ("bug_compat", 0, 1, 1, 1, 0, 1),
+    ("use_graph", 0, 1, 0, 1, 0, 0),
+    ("fused_sampled", 0, 1, 0, 1, 0, 0),
+    ("host_sampled", 0, 1, 1, 1, 0, 0),
+    ("sampled_batch_host", 0, 1, 0, 1, 0, 0),
+    ("rerank", 0, 1, 1, 1, 0, 0),
+    ("batch_tail", 0, 1, 1, 1, 0, 0),
+    ("server", 0, 1, 0, 1, STOP_SERVER, 1),
+    ("speculate", 0, 1, 1, 1, 0, 1),
+    ("server_vram_mailbox", 0, 1, 1, 1, 0, 0),
+    ("pole_fix", 0, 1, 1, 1, POLE | BUMP_KB_VERSION, 1),
+    ("pole_gate", 0, 1, 1, 1, POLE, 0),
+    ("pole_lazy", 0, 1, 1, 1, POLE, 0),
+    ("pole_follow", 0, 1, 1, 1, POLE, 0),
+    ("select", 0, 1, 0, 0, 0, 0),
+    ("late_eager", 0, 1000000, 3, 0, 0, 0),
+    ("combine_linger_us", 0, 10000, 20, 0, 0, 0),
+    ("train_chunk_steps", 1, 2**28, 2**22, 0, 0, 0),
+    ("workers", 1, MAX_WORKERS, 16, 0, 0, 1),
+    ("eval_subtasks", 0, 8192, 0, 0, 0, 0),
+    ("eval_variant", 0, I64_MAX, 0, 0, 0, 0),
+    ("top_cache", 0, 256, 10, 0, 0, 0),
+    ("eval_max_grid", 0, 65535, 0, 0, STOP_SERVER | BUMP_KB_VERSION, 0),
+    ("batch_min", 0, 257, 0, 0, 0, 0),
+    ("batch_form", 0, 3, 0, 0, 0, 0),
+    ("batch_qb", 0, 4, 0, 0, 0, 0),
+    ("batch_tile", 0, 8192, 0, 0, 0, 0),
+    ("batch_groups", 0, 8, 0, 0, 0, 0),
+    ("cluster_shape", 0, 2, 0, 0, 0, 0),
+    ("cluster_form", 0, 2, 0, 0, 0, 0),
+    ("cluster_from", 1024, 16384, 10240, 0, STOP_SERVER, 0),
+    ("server_idle_us", 10, 1000000, 500, 0, STOP_SERVER, 0),
+]
+
+
+def test_option_table_is_the_contract():
+    assert len(OPTIONS) == 40 and len({o[0] for o in OPTIONS}) == 40
+    for name, *spec in OPTIONS:
+        assert probe("option_spec:" + name, [], 6) == (6, spec), name
+    # what is no settable option: the write-only seed, a counter, a name nobody knows, no name
+    for name in ("seed", "posted_ops", "shards", "no_such_option", "", "#", "#x", "#-1", "Combine", "combine "):
+        assert probe("option_spec:" + name, [], 6)[0] == -1, name
+    assert probe("option_spec:combine", [], 5)[0] == -1          # output too small
+    # the table holds nothing beyond the list: as many rows as the list, each of them one of the list's
+    rows = []
+    while probe("option_spec:#%d" % len(rows), [], 6)[0] == 6:
+        rows.append(probe("option_spec:#%d" % len(rows), [], 6)[1])
+        assert len(rows) <= len(OPTIONS)
+    assert len(rows) == len(OPTIONS)
+    assert sorted(rows) == sorted(list(o[1:]) for o in OPTIONS)
