@@ -37,6 +37,37 @@ PQACORE_API void *PqaEngineFactory_LoadHipEngine(void *pvFactory, void **ppError
 PQACORE_API void *PqaEngineFactory_CreateHipEngineSharded(void *pvFactory, void **ppError,
                                                           const CiEngineDefinition *pEngDef, const CiHipShard *pShard);
 
+/* ---- .kb files per shard and in either precision.  The byte layout is the reference's; a file's number type (its
+ * PrecisionDefinition: Float or Double) and the engine's need not be the same: where they differ every row passes through a device
+ * kernel on its way -- fp64 -> fp32 rounds to nearest even, as (float)x does, fp32 -> fp64 is exact -- instead of through fp64 host
+ * arrays of the whole cube (PqaHip_GetKB / PqaHip_SetKB).
+ *
+ * precType: 0 = the file's, else TPqaPrecisionType Float (1) or Double (3); anything else is NotImplemented.
+ * pShard NULL = the whole file (with PQA_DEVICES naming several devices: the one-process sharded engine, in that precision).
+ * Otherwise the engine holds questions [_qFirst, _qFirst + nLocalQuestions) of the file on _device (-1: the current one); _qTotal must
+ * be 0 or the file's question count (InsufficientEngineDimensions otherwise); a range that is not within the file's questions is
+ * IndexOutOfRange, a negative count NegativeCount; pShard together with PQA_DEVICES is refused (WrongMode).  The shard reads its two
+ * blocks of rows by seeking to them, the whole vB, the target gaps and the target and quiz id maps; the question gaps of its range
+ * become its gap bits, and the file's question gap list and question id map are kept as read, for PqaHip_SaveKBShard.
+ * A header whose dimensions are no knowledge base's, or whose arrays the file is too short for, is FileOp before anything is
+ * allocated.  A finite value that does not fit Float fails the load (FileOp, naming the array: _sA, _mD or _vB); no engine is
+ * returned.  C++ exceptions do not cross these three calls: they come back as StdException / SRException. */
+PQACORE_API void *PqaEngineFactory_LoadHipEngineAs(void *pvFactory, void **ppError, const char *filePath, uint8_t precType,
+                                                   const CiHipShard *pShard, int64_t nLocalQuestions);
+/* PqaEngine_SaveKB in a chosen precision (0 = the engine's own: the bytes PqaEngine_SaveKB writes).  The header is the one an
+ * engine created in that precision writes (Float: mantissa 24, exponent 8; Double: 53, 11), the arrays are in that type.  One-device
+ * engines and the one-process sharded engine; on a shard NotImplemented, as PqaEngine_SaveKB is. */
+PQACORE_API void *PqaHip_SaveKBAs(void *pvEngine, const char *filePath, uint8_t precType);
+/* A shard's part of a save, in place: the file is opened without being emptied (created if missing) and the shard writes its sA
+ * block and its mD block at their offsets.  The shard that holds question 0 also writes the header -- with ITS count of questions
+ * asked; every rank sees every Train --, vB and the trailer, and cuts the file behind the trailer.  The file is complete once every
+ * shard's call has returned; the calls may run in any order or at once (they write disjoint ranges), ordering them against readers is the
+ * caller's business (probqa_amd/dist.py: save_kb).  Every shard must name the same precType.  A shard loaded from a file writes that
+ * file's question gap list and id map back; a created one writes the gaps PqaHip_SetQuestionGaps was given over fresh ids.
+ * On a whole one-device engine the call is an equivalent of PqaHip_SaveKBAs (the engine is the only shard of its file); on the
+ * one-process sharded engine it is NotImplemented. */
+PQACORE_API void *PqaHip_SaveKBShard(void *pvEngine, const char *filePath, uint8_t precType);
+
 /* ---- options: "select" (0 = sampled like the reference [default], 1 = argmax), "workers" (emulated CPU worker count
  * fixing the summation order of the prior updates, default 16), "eval_subtasks" (question subtasks of the sampled
  * selector, default 8*workers as PqaCore/CpuEngine.cpp:339), "eval_variant" (0 = auto), "bug_compat" (reproduce

@@ -94,6 +94,17 @@ std::vector<int> DevicesFromEnvironment() {
   return devices;
 }
 
+template <typename Fn>
+Error Guarded(Fn &&fn) {
+  try {
+    return fn();
+  } catch (const std::exception &ex) {
+    return Error::MakeP(ErrCode::StdException, std::string("what=[") + ex.what() + "]", "A C++ exception was caught at the C interface.");
+  } catch (...) {
+    return Error::Make(ErrCode::SRException, "An unknown exception was caught at the C interface.");
+  }
+}
+
 void *CreateEngine(void *pvFactory, void **ppError, const CiEngineDefinition *pEngDef, const CiHipShard *pShard) {
   if (pvFactory == nullptr) {  // PqaCInterop.cpp:93-98
     if (ppError) *ppError = new Error(Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of IPqaEngineFactory."));
@@ -179,6 +190,44 @@ PQACORE_API void *PqaEngineFactory_LoadCpuEngine(void *pvFactory, void **ppError
 
 PQACORE_API void *PqaEngineFactory_LoadHipEngine(void *pvFactory, void **ppError, const char *filePath, uint64_t memPoolMaxBytes) {
   return PqaEngineFactory_LoadCpuEngine(pvFactory, ppError, filePath, memPoolMaxBytes);
+}
+
+// ---- .kb files per shard and in either precision (PqaHipExt.h).  The reference's two exception codes (PqaCInterop.cpp's catch blocks,
+// PqaErrors.h: SRException, StdException) behind a barrier: nothing thrown below -- an allocation a file's header asks for, say --
+// crosses the C ABI.
+PQACORE_API void *PqaEngineFactory_LoadHipEngineAs(void *pvFactory, void **ppError, const char *filePath, uint8_t precType, const CiHipShard *pShard,
+                                                   int64_t nLocalQuestions) {
+  if (pvFactory == nullptr) {
+    if (ppError) *ppError = new Error(Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of IPqaEngineFactory."));
+    return nullptr;
+  }
+  pqa::IEngine *eng = nullptr;
+  Error err = Guarded([&]() -> Error {
+    Error e;
+    if (precType != 0 && precType != 1 && precType != 3)
+      return Error::MakeP(ErrCode::NotImplemented, "Feature=precType " + std::to_string((int)precType), "A .kb file is loaded as TPqaPrecisionType::Float or ::Double.");
+    const std::vector<int> devices = DevicesFromEnvironment();
+    if (pShard != nullptr && !devices.empty())
+      return Error::Make(ErrCode::WrongMode, "A shard names its own device: PqaEngineFactory_LoadHipEngineAs with pShard is not combined with PQA_DEVICES.");
+    if (devices.size() >= 2) { eng = pqa::LoadShardedEngine(e, filePath, devices, precType); return e; }
+    if (devices.size() == 1 && hipSetDevice(devices[0]) != hipSuccess) {
+      (void)hipGetLastError();
+      return Error::MakeP(ErrCode::IndexOutOfRange, "device=" + std::to_string(devices[0]), "No such HIP device (PQA_DEVICES).");
+    }
+    eng = HipEngine::LoadAs(e, filePath, precType, pShard, nLocalQuestions);
+    return e;
+  });
+  if (!err.ok()) eng = nullptr;
+  AssignErr(ppError, err);
+  return eng;
+}
+PQACORE_API void *PqaHip_SaveKBAs(void *pvEngine, const char *filePath, uint8_t precType) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(Guarded([&] { return pEng->SaveKBAs(filePath, precType); }));
+}
+PQACORE_API void *PqaHip_SaveKBShard(void *pvEngine, const char *filePath, uint8_t precType) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(Guarded([&] { return pEng->SaveKBShard(filePath, precType); }));
 }
 
 PQACORE_API void CiReleasePqaError(void *pvErr) { delete static_cast<Error *>(pvErr); }
@@ -742,6 +791,15 @@ PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, 
       pOut[nRes++] = r;
     }
     return nRes;
+  }
+  if (w == "kb_layout") {   // {K, Q, T, elem, qFirst, nLocal} -> {valid, window ok, sA offset, sA bytes, mD offset, mD bytes, vB offset, trailer offset}
+    if (nIn != 6 || nOut < 8) return -1;
+    const pqa::KbLayout lay(pIn[0], pIn[1], pIn[2], pIn[3]);
+    const bool window = lay.HasWindow(pIn[4], pIn[5]);
+    const int64_t row[8] = {lay.valid, window, window ? lay.SaOffset(pIn[4]) : -1, window ? pIn[5] * lay.K * lay.rowBytes : -1, window ? lay.MdOffset(pIn[4]) : -1,
+                            window ? pIn[5] * lay.rowBytes : -1, lay.valid ? lay.vbOff : -1, lay.valid ? lay.trailerOff : -1};
+    std::copy(row, row + 8, pOut);
+    return 8;
   }
   if (w == "let_go") {
     if (nIn < 4 || pIn[3] < 0 || nIn != 4 + 2 * pIn[3]) return -1;

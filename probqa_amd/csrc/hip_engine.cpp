@@ -392,6 +392,8 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "precision") return _precType;
   if (n == "ldT") return _ldT;
   if (n == "device") return _device;
+  if (n == "q_first") return _qFirst;
+  if (n == "local_questions") return _Q;
   return -1;   // (an unknown name, and the write-only "seed")
 }
 
@@ -861,6 +863,12 @@ Error HipEngine::SetQuestionGaps(int64_t n, const int64_t *ids) {
   std::lock_guard<EngineMutex> lk(_mu);
   for (int64_t i = 0; i < n; i++)
     if (ids[i] < 0 || ids[i] >= _qTotal) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(ids[i], 0, _qTotal - 1), "Question index is not in KB range.");
+  if (_qTotal != _Q)   // a shard: the whole axis' gaps, for the trailer of its part of a save
+    for (int64_t i = 0; i < n; i++)
+      if (std::find(_globalQuestionGaps.begin(), _globalQuestionGaps.end(), ids[i]) == _globalQuestionGaps.end()) {
+        _globalQuestionGaps.push_back(ids[i]);
+        if (_fileTrailer) { _fileTrailer->questionGaps.push_back(ids[i]); _fileTrailer->questionIds.Vacate(ids[i]); }
+      }
   for (int64_t i = 0; i < n; i++)
     if (ids[i] >= _qFirst && ids[i] < _qFirst + _Q && !BitTest(_hQGap, ids[i] - _qFirst)) {
       BitSet(_hQGap, ids[i] - _qFirst, true);

@@ -116,11 +116,20 @@ struct KbHeader {
   CiEngineDefinition Definition() const;   // (precision unpacked; _initAmount = 1: not stored, every count is read from the file)
 };
 Error FileErr(const char *path, const char *msg);   // FileOp, with the path
+Error KbOverflowErr(const char *filePath, const char *array, uint64_t count);   // finite values of an array do not fit fp32
+// precType of a save (0: own) -> the header's PrecisionDefinition and the bytes of the file's number type; of a load -> the definition
+Error KbSavePrecision(uint8_t precType, uint8_t ownType, uint32_t ownMantissa, uint16_t ownExponent, uint64_t &packed, int &fileElem);
+Error KbLoadDefinition(const KbHeader &h, uint8_t precType, CiEngineDefinition &def);
 struct KbFile {
   FILE *f = nullptr;
   const char *path;
   Error opened;                // why there is no file: no name, or it cannot be opened -- what the header calls answer then
+  struct InPlace {};
   KbFile(const char *filePath, bool write);
+  KbFile(const char *filePath, InPlace);   // for writing, created where missing, NOT emptied: a shard's part of a save
+  Error CheckHeader(const KbHeader &h, KbLayout &layout) const;   // the dimensions make sense and the arrays fit the file's size
+  int64_t Size() const;
+  Error Seek(int64_t offset);
   ~KbFile() { if (f) std::fclose(f); }
   Error WriteHeader(const KbHeader &h);
   Error ReadHeader(KbHeader &h);
@@ -203,6 +212,8 @@ class IEngine {
   virtual bool EnsurePermQuizGreater(int64_t bound) = 0;
   virtual bool RemapQuizPermId(int64_t srcPermId, int64_t destPermId) = 0;
   virtual Error SaveKB(const char *filePath, bool doubleBuffer) = 0;
+  virtual Error SaveKBAs(const char *filePath, uint8_t precType) = 0;      // (additive) in a chosen precision, whole engines
+  virtual Error SaveKBShard(const char *filePath, uint8_t precType) = 0;   // (additive) a shard's part, in place
   virtual Error AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) = 0;
   virtual Error RemoveQuestions(int64_t n, const int64_t *pQIds) = 0;
   virtual Error RemoveTargets(int64_t n, const int64_t *pTIds) = 0;
@@ -274,7 +285,11 @@ class HipEngine : public IEngine {
   bool EnsurePermQuizGreater(int64_t bound) override;
   bool RemapQuizPermId(int64_t srcPermId, int64_t destPermId) override;
   Error SaveKB(const char *filePath, bool doubleBuffer) override;
+  Error SaveKBAs(const char *filePath, uint8_t precType) override;
+  Error SaveKBShard(const char *filePath, uint8_t precType) override;
   static HipEngine *Load(Error &err, const char *filePath);
+  // precType 0: the file's; shard != nullptr: questions [shard->_qFirst, + nLocal) of the file on shard->_device
+  static HipEngine *LoadAs(Error &err, const char *filePath, uint8_t precType, const CiHipShard *shard, int64_t nLocal);
   Error AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) override;
   Error RemoveQuestions(int64_t n, const int64_t *pQIds) override;
   Error RemoveTargets(int64_t n, const int64_t *pTIds) override;
@@ -359,8 +374,9 @@ class HipEngine : public IEngine {
   Error ResumeQuizBatchRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *const *rows, const int *rowDevices,
                             const char *stageRow, int64_t *pQuizzes);
   // .kb arrays of this engine's questions at the file's current position (hip_engine_kb.cpp); the engine's lock is not taken
-  Error IoRows(FILE *f, const char *filePath, bool mD, bool write);
-  Error IoVB(FILE *f, const char *filePath, bool write);
+  // fileElem: bytes of the file's number type (0: the engine's); where it differs the rows pass through convert_rows_kernel
+  Error IoRows(FILE *f, const char *filePath, bool mD, bool write, int fileElem = 0);
+  Error IoVB(FILE *f, const char *filePath, bool write, int fileElem = 0);
   Error SetVBFromHost(const double *vb);
   void GetGapLists(std::vector<int64_t> &questionsGlobal, std::vector<int64_t> &targets) const {
     for (int64_t q : _questionGapList) questionsGlobal.push_back(q + _qFirst);
@@ -697,6 +713,12 @@ class HipEngine : public IEngine {
   int64_t _capQ = 0;                        // questions the device buffers are allocated for (>= _Q)
   std::vector<int64_t> _questionGapList, _targetGapList;  // LIFO, like reference PqaCore/GapTracker.h
   IdLedger _questionIds, _targetIds, _quizIds;
+  // A shard: the question axis of the WHOLE knowledge base as its file had it -- the gap list and the id ledger, global ids, read-only
+  // (a shard changes neither: AddQsTs / RemoveQuestions are refused) -- so that SaveKBShard writes the file's trailer back byte for
+  // byte.  A created shard has none: its trailer is built from the global gaps SetQuestionGaps was given.
+  struct FileTrailer { std::vector<int64_t> questionGaps; IdLedger questionIds; };
+  std::unique_ptr<FileTrailer> _fileTrailer;
+  std::vector<int64_t> _globalQuestionGaps;
   uint32_t _precMantissa = 0;
   uint16_t _precExponent = 0;
   std::vector<Quiz *> _quizzes;
@@ -804,6 +826,6 @@ int64_t SelectSampledHostBits(double *run, int64_t n, int64_t nWorkers, uint64_t
 int64_t FindNearestInPacks(int64_t iMiddle, int64_t nQuestions, const std::function<uint64_t(int64_t)> &avail);
 // One knowledge base over several devices of this process (sharded_engine.cpp); devices.size() >= 2.
 IEngine *CreateShardedEngine(Error &err, const CiEngineDefinition &def, const std::vector<int> &devices);
-IEngine *LoadShardedEngine(Error &err, const char *filePath, const std::vector<int> &devices);
+IEngine *LoadShardedEngine(Error &err, const char *filePath, const std::vector<int> &devices, uint8_t precType = 0);
 
 }  // namespace pqa

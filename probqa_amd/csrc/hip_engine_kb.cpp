@@ -5,6 +5,10 @@
 // the cube itself stays on the device and is edited there (kb_kernels.hip).
 #include "hip_engine_internal.h"
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 namespace pqa {
 
 namespace {
@@ -230,9 +234,15 @@ Error HipEngine::ClearOldQuizzes(int64_t maxCount, double maxAgeSec) {  // behav
 // at their sum (reference: PqaCore/BaseEngine.cpp:323-385 writes row by row; PqaCore/CudaPersistence.cpp:15-43 stages through one
 // pageable buffer).  The mD rows of a batch are ONE strided copy (a row per question, (K + 1) ldT elements apart); a question's K sA
 // rows are one.
-Error HipEngine::IoRows(FILE *f, const char *filePath, bool mD, bool write) {   // sA rows [q][a] of T elements, or mD rows [q]
+// fileElem (0: the engine's): bytes of the FILE's number type.  Where it is the engine's, a batch is copied straight between the pinned buffer
+// and the cube, as it always was.  Where it differs, the batch passes through a dense block on the device -- pinned buffer -> dense block ->
+// convert_rows_kernel -> cube, a save the other way round -- one dense block per pinned buffer, everything in the engine's stream, so the
+// overlap of file and bus is the same.  Values that do not fit fp32 are counted on the device and fail the call behind its last batch.
+Error HipEngine::IoRows(FILE *f, const char *filePath, bool mD, bool write, int fileElem) {   // sA rows [q][a] of T elements, or mD rows [q]
   hipSetDevice(_device);
-  const size_t rowB = (size_t)_T * (size_t)_elem, ldB = (size_t)_ldT * (size_t)_elem;
+  const int fe = fileElem ? fileElem : _elem;
+  const bool convert = fe != _elem;
+  const size_t rowB = (size_t)_T * (size_t)fe, ldB = (size_t)_ldT * (size_t)_elem;
   const int64_t rowsPerQ = mD ? 1 : _K;
   const int64_t batch = std::max<int64_t>(1, (int64_t)((64u << 20) / (rowB * (size_t)rowsPerQ)));
   const size_t bufBytes = (size_t)std::min(batch, _Q) * (size_t)rowsPerQ * rowB;
@@ -242,12 +252,16 @@ Error HipEngine::IoRows(FILE *f, const char *filePath, bool mD, bool write) {   
     bool pinned = false;
     std::vector<char> pageable[2];
     hipStream_t stream = nullptr;
+    char *dense[2] = {nullptr, nullptr};   // the file's rows on the device, where its number type is not the cube's
+    unsigned *overflow = nullptr;
     ~Staging() {
       (void)hipStreamSynchronize(stream);   // (an early return -- a failed read, a failed copy -- leaves copies in flight: not under buffers about to go)
       for (int i = 0; i < 2; i++) {
         if (pinned && buf[i]) hipHostFree(buf[i]);
         if (done[i]) hipEventDestroy(done[i]);
+        if (dense[i]) hipFree(dense[i]);
       }
+      if (overflow) hipFree(overflow);
     }
   } st;
   const int nBuf = _Q > batch ? 2 : 1;
@@ -260,8 +274,23 @@ Error HipEngine::IoRows(FILE *f, const char *filePath, bool mD, bool write) {   
     for (int i = 0; i < nBuf; i++) { st.pageable[i].resize(bufBytes); st.buf[i] = st.pageable[i].data(); }
   }
   for (int i = 0; i < nBuf; i++) HIP_TRY(hipEventCreateWithFlags(&st.done[i], hipEventDisableTiming));
+  if (convert) {
+    for (int i = 0; i < nBuf; i++) HIP_TRY(hipMalloc((void **)&st.dense[i], bufBytes));
+    HIP_TRY(hipMalloc((void **)&st.overflow, sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(st.overflow, 0, sizeof(unsigned), _stream));
+  }
   const char *what = mD ? "the target dimension of _mD weights." : "the target dimension of _sA weights.";
-  auto copyBatch = [&](char *host, int64_t q0, int64_t nq) -> hipError_t {
+  auto copyBatch = [&](char *host, int which, int64_t q0, int64_t nq) -> hipError_t {
+    if (convert) {
+      const size_t bytes = (size_t)(nq * rowsPerQ) * rowB;
+      ConvertRows c{st.dense[which], CubeAt(q0, 0), fe, _elem, _T, _ldT, nq * rowsPerQ, rowsPerQ, mD ? _K : 0, _K + 1, !write, false, st.overflow};
+      if (write) {
+        const hipError_t he = LaunchConvertRows(c, _stream);
+        return he != hipSuccess ? he : hipMemcpyAsync(host, st.dense[which], bytes, hipMemcpyDeviceToHost, _stream);
+      }
+      const hipError_t he = hipMemcpyAsync(st.dense[which], host, bytes, hipMemcpyHostToDevice, _stream);
+      return he != hipSuccess ? he : LaunchConvertRows(c, _stream);
+    }
     if (mD) {   // one row per question, (K + 1) ldT elements apart
       return write ? hipMemcpy2DAsync(host, rowB, CubeAt(q0, _K), ldB * (size_t)(_K + 1), rowB, (size_t)nq, hipMemcpyDeviceToHost, _stream)
                    : hipMemcpy2DAsync(CubeAt(q0, _K), ldB * (size_t)(_K + 1), host, rowB, rowB, (size_t)nq, hipMemcpyHostToDevice, _stream);
@@ -284,10 +313,10 @@ Error HipEngine::IoRows(FILE *f, const char *filePath, bool mD, bool write) {   
     HIP_TRY(hipEventSynchronize(st.done[turn]));   // (whatever used this buffer two batches ago has finished; a fresh event is complete)
     if (!write) {
       if (std::fread(host, rowB, nRows, f) != nRows) { (void)hipStreamSynchronize(_stream); return FileErr(filePath, (std::string("Can't read ") + what).c_str()); }
-      HIP_TRY(copyBatch(host, q0, nq));
+      HIP_TRY(copyBatch(host, turn, q0, nq));
       HIP_TRY(hipEventRecord(st.done[turn], _stream));
     } else {
-      HIP_TRY(copyBatch(host, q0, nq));
+      HIP_TRY(copyBatch(host, turn, q0, nq));
       HIP_TRY(hipEventRecord(st.done[turn], _stream));
       if (prevQ0 >= 0) {   // while this batch comes back, the previous one goes to the file
         const int other = turn ^ (nBuf - 1);
@@ -305,14 +334,55 @@ Error HipEngine::IoRows(FILE *f, const char *filePath, bool mD, bool write) {   
     const int last = turn ^ 1;
     if (std::fwrite(st.buf[last], rowB, (size_t)(prevNq * rowsPerQ), f) != (size_t)(prevNq * rowsPerQ)) return FileErr(filePath, (std::string("Can't write ") + what).c_str());
   }
+  if (convert) {
+    unsigned lost = 0;
+    HIP_TRY(hipMemcpy(&lost, st.overflow, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (lost != 0) return KbOverflowErr(filePath, mD ? "_mD" : "_sA", lost);
+  }
   return Error();
 }
 
-// vB: fp64 on the device in both precisions; the file holds the engine's number type
-Error HipEngine::IoVB(FILE *f, const char *filePath, bool write) {
+// ... of an array of a .kb file do not fit TPqaPrecisionType::Float: the load (or the save) that asked for it fails
+Error KbOverflowErr(const char *filePath, const char *array, uint64_t count) {
+  return Error::MakeP(ErrCode::FileOp, std::string("filePath=[") + filePath + "] array=" + array + " values=" + std::to_string(count),
+                      std::string("Finite values of the ") + array + " weights overflow TPqaPrecisionType::Float.");
+}
+
+// vB: fp64 on the device in both precisions, the words holding the engine's number type; the file holds ITS number type.  Where that
+// is the engine's, the conversion is the host's, as it was.  Where it differs, the vector passes through the kernel of the rows: a
+// Double file into a Float engine rounds every word through fp32 (and counts what does not fit), a Float file widens, a Double
+// engine's save as Float rounds; a Float engine's words ARE the doubles a Double file holds.
+Error HipEngine::IoVB(FILE *f, const char *filePath, bool write, int fileElem) {
   hipSetDevice(_device);
+  const int fe = fileElem ? fileElem : _elem;
   std::vector<double> vb((size_t)_T);
-  std::vector<float> vf(_elem == 4 ? (size_t)_T : 0);
+  std::vector<float> vf(fe == 4 ? (size_t)_T : 0);
+  if (fe != _elem) {
+    const size_t bytes = (size_t)_T * (size_t)fe;
+    void *host = fe == 8 ? (void *)vb.data() : (void *)vf.data();
+    struct Dev { char *dense = nullptr; unsigned *overflow = nullptr; ~Dev() { hipFree(dense); hipFree(overflow); } } d;
+    HIP_TRY(hipMalloc((void **)&d.dense, bytes));
+    HIP_TRY(hipMalloc((void **)&d.overflow, sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(d.overflow, 0, sizeof(unsigned), _stream));
+    ConvertRows c{d.dense, _dVB, fe, 8, _T, _ldT, 1, 1, 0, 0, !write, !write && fe == 8, d.overflow};
+    if (write) {
+      if (fe == 8) HIP_TRY(hipMemcpyAsync(host, _dVB, bytes, hipMemcpyDeviceToHost, _stream));
+      else {
+        HIP_TRY(LaunchConvertRows(c, _stream));
+        HIP_TRY(hipMemcpyAsync(host, d.dense, bytes, hipMemcpyDeviceToHost, _stream));
+      }
+    } else {
+      if (std::fread(host, (size_t)fe, (size_t)_T, f) != (size_t)_T) return FileErr(filePath, "Can't read the _vB weights.");
+      HIP_TRY(hipMemcpyAsync(d.dense, host, bytes, hipMemcpyHostToDevice, _stream));
+      HIP_TRY(LaunchConvertRows(c, _stream));
+    }
+    unsigned lost = 0;
+    HIP_TRY(hipMemcpyAsync(&lost, d.overflow, sizeof(unsigned), hipMemcpyDeviceToHost, _stream));
+    HIP_TRY(hipStreamSynchronize(_stream));
+    if (lost != 0) return KbOverflowErr(filePath, "_vB", lost);
+    if (write && std::fwrite(host, (size_t)fe, (size_t)_T, f) != (size_t)_T) return FileErr(filePath, "Can't write the _vB weights.");
+    return Error();
+  }
   if (write) {
     HIP_TRY(hipMemcpyAsync(vb.data(), _dVB, (size_t)_T * sizeof(double), hipMemcpyDeviceToHost, _stream));
     HIP_TRY(hipStreamSynchronize(_stream));
@@ -421,38 +491,194 @@ Error KbFile::FlushAndClose() {
   return Error();
 }
 
+// The header a file of `precType` (0: the engine's own) carries when this engine writes it: the engine's own definition where the
+// type is its own -- the bytes SaveKB writes --, otherwise what an engine created in that type writes (the IEEE widths).
+Error KbSavePrecision(uint8_t precType, uint8_t ownType, uint32_t ownMantissa, uint16_t ownExponent, uint64_t &packed, int &fileElem) {
+  if (precType == 0) precType = ownType;
+  if (precType != 1 && precType != 3)
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=precType " + std::to_string((int)precType), "A .kb file is written as TPqaPrecisionType::Float or ::Double.");
+  fileElem = precType == 1 ? 4 : 8;
+  packed = precType == ownType ? PackPrecision(ownType, ownMantissa, ownExponent) : precType == 1 ? PackPrecision(1, 24, 8) : PackPrecision(3, 53, 11);
+  return Error();
+}
+
+// What a header must say before anything is allocated for it: a number type the engines have, the reference's minimum dimensions
+// (PqaEngineBaseFactory.cpp:29-42), and arrays that fit the file -- a damaged header's dimensions come back as an error, not as an
+// allocation.
+Error KbFile::CheckHeader(const KbHeader &h, KbLayout &layout) const {
+  const uint64_t type = h.precision & 0xF;
+  if (type != 1 && type != 3)
+    return Error::MakeP(ErrCode::NotImplemented, std::string("filePath=[") + path + "] precType=" + std::to_string(type),
+                        "The KB file's precision is neither TPqaPrecisionType::Float nor ::Double.");
+  layout = KbLayout(h.K, h.Q, h.T, type == 1 ? 4 : 8);
+  if (h.K < 2 || h.Q < 1 || h.T < 2 || !layout.valid)
+    return Error::MakeP(ErrCode::FileOp, std::string("filePath=[") + path + "] nAnswers=" + std::to_string(h.K) + " nQuestions=" + std::to_string(h.Q) +
+                        " nTargets=" + std::to_string(h.T), "The KB file's header does not hold the dimensions of a knowledge base.");
+  const int64_t size = Size();
+  if (size < layout.ArraysEnd())
+    return Error::MakeP(ErrCode::FileOp, std::string("filePath=[") + path + "] size=" + std::to_string(size) + " arrays=" + std::to_string(layout.ArraysEnd()),
+                        "The KB file is shorter than the arrays its header announces.");
+  return Error();
+}
+int64_t KbFile::Size() const {
+  struct stat st;
+  return f && fstat(fileno(f), &st) == 0 ? (int64_t)st.st_size : -1;
+}
+Error KbFile::Seek(int64_t offset) {
+  return fseeko(f, (off_t)offset, SEEK_SET) == 0 ? Error() : FileErr(path, "Can't seek in the KB file.");
+}
+// in place: the file is opened for writing without being emptied (created where there is none) -- a shard's part of a save
+KbFile::KbFile(const char *filePath, InPlace) : path(filePath) {
+  if (!path) { opened = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of KB file name."); return; }
+  const int fd = ::open(path, O_RDWR | O_CREAT, 0666);
+  if (fd < 0 || !(f = fdopen(fd, "r+b"))) {
+    if (fd >= 0) ::close(fd);
+    opened = Error::MakeP(ErrCode::CantOpenFile, std::string("filePath=[") + path + "]", "Can't open the file to write KB to.");
+  }
+}
+
 Error HipEngine::SaveKB(const char *filePath, bool doubleBuffer) {
   (void)doubleBuffer;  // the device copy already is the "second buffer": the file is written from a host snapshot
+  return SaveKBAs(filePath, 0);
+}
+
+Error HipEngine::SaveKBAs(const char *filePath, uint8_t precType) {
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=SaveKB of a sharded engine", "Save the shards' owner instead.");
+  uint64_t precision = 0;
+  int fe = 0;
+  Error e = KbSavePrecision(precType, _precType, _precMantissa, _precExponent, precision, fe);
+  if (!e.ok()) return e;
   KbFile file(filePath, true);
   hipSetDevice(_device);
-  Error e = file.WriteHeader(KbHeader{PackPrecision(_precType, _precMantissa, _precExponent), _K, _Q, _T, _nQuestionsAsked.load(std::memory_order_acquire)});
-  if (e.ok()) e = IoRows(file.f, filePath, false, true);   // sA rows [q][a]
-  if (e.ok()) e = IoRows(file.f, filePath, true, true);    // mD rows [q]
-  if (e.ok()) e = IoVB(file.f, filePath, true);
+  e = file.WriteHeader(KbHeader{precision, _K, _Q, _T, _nQuestionsAsked.load(std::memory_order_acquire)});
+  if (e.ok()) e = IoRows(file.f, filePath, false, true, fe);   // sA rows [q][a]
+  if (e.ok()) e = IoRows(file.f, filePath, true, true, fe);    // mD rows [q]
+  if (e.ok()) e = IoVB(file.f, filePath, true, fe);
   if (e.ok()) e = file.WriteTrailer(_questionGapList, _targetGapList, _questionIds, _targetIds, _quizIds);
   return e.ok() ? file.FlushAndClose() : e;
 }
 
+// A shard's part of a save, in place: its sA block and its mD block at their offsets of a file that is not emptied first; the shard
+// that holds question 0 also writes the header (with its own count of questions asked: every rank sees every Train), vB and the
+// trailer, and cuts the file behind the trailer.  The file is complete once every shard's call has returned, in any order.  A whole
+// engine is the one shard of its file: the call then writes what SaveKBAs writes.
+Error HipEngine::SaveKBShard(const char *filePath, uint8_t precType) {
+  std::lock_guard<EngineMutex> lk(_mu);
+  StopServer();
+  uint64_t precision = 0;
+  int fe = 0;
+  Error e = KbSavePrecision(precType, _precType, _precMantissa, _precExponent, precision, fe);
+  if (!e.ok()) return e;
+  const KbLayout lay(_K, _qTotal, _T, fe);
+  if (!lay.HasWindow(_qFirst, _Q)) return Error::Make(ErrCode::Internal, "SaveKBShard: the shard's range does not fit its file.");
+  KbFile file(filePath, KbFile::InPlace{});
+  if (!file.f) return file.opened;
+  hipSetDevice(_device);
+  e = file.Seek(lay.SaOffset(_qFirst));
+  if (e.ok()) e = IoRows(file.f, filePath, false, true, fe);
+  if (e.ok()) e = file.Seek(lay.MdOffset(_qFirst));
+  if (e.ok()) e = IoRows(file.f, filePath, true, true, fe);
+  if (e.ok() && _qFirst == 0) {
+    e = file.Seek(0);
+    if (e.ok()) e = file.WriteHeader(KbHeader{precision, _K, _qTotal, _T, _nQuestionsAsked.load(std::memory_order_acquire)});
+    if (e.ok()) e = file.Seek(lay.vbOff);
+    if (e.ok()) e = IoVB(file.f, filePath, true, fe);
+    if (e.ok()) {
+      if (_qTotal == _Q) e = file.WriteTrailer(_questionGapList, _targetGapList, _questionIds, _targetIds, _quizIds);
+      else if (_fileTrailer) e = file.WriteTrailer(_fileTrailer->questionGaps, _targetGapList, _fileTrailer->questionIds, _targetIds, _quizIds);
+      else {   // a shard that was created, not loaded: the question axis as Create and SetQuestionGaps left it on every rank
+        IdLedger all;
+        all.Extend(_qTotal);
+        for (int64_t g : _globalQuestionGaps) all.Vacate(g);
+        e = file.WriteTrailer(_globalQuestionGaps, _targetGapList, all, _targetIds, _quizIds);
+      }
+    }
+    if (e.ok() && (std::fflush(file.f) != 0 || ftruncate(fileno(file.f), ftello(file.f)) != 0)) e = FileErr(filePath, "Can't cut the KB file behind its trailer.");
+  }
+  return e.ok() ? file.FlushAndClose() : e;
+}
+
 HipEngine *HipEngine::Load(Error &err, const char *filePath) {  // PqaEngineBaseFactory.cpp:44-83, CpuEngine.cpp:41-92
+  return LoadAs(err, filePath, 0, nullptr, 0);
+}
+
+// The engine definition a file is loaded under: the file's own, or -- precType given and not the file's -- that type with the widths
+// an engine created in it carries.
+Error KbLoadDefinition(const KbHeader &h, uint8_t precType, CiEngineDefinition &def) {
+  def = h.Definition();
+  if (precType == 0 || precType == def._precType) return Error();
+  if (precType != 1 && precType != 3)
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=precType " + std::to_string((int)precType), "A .kb file is loaded as TPqaPrecisionType::Float or ::Double.");
+  def._precType = precType;
+  def._precMantissa = precType == 1 ? 24 : 53;
+  def._precExponent = precType == 1 ? 8 : 11;
+  return Error();
+}
+
+// Load in the file's precision or another (precType), whole (shard == nullptr) or the window [shard->_qFirst, + nLocal) of the
+// file's questions as a shard on shard->_device.  A shard takes its rows -- a seek to each of its two blocks --, the whole vB, the
+// target gaps, the target and quiz ledgers, and the question gaps of its range as local gap bits; the file's question gap list and
+// question id ledger it keeps as they are (_fileTrailer), for the trailer of a later SaveKBShard.
+HipEngine *HipEngine::LoadAs(Error &err, const char *filePath, uint8_t precType, const CiHipShard *shard, int64_t nLocal) {
   KbFile file(filePath, false);
   KbHeader h;
   err = file.ReadHeader(h);
   if (!err.ok()) return nullptr;
-  std::unique_ptr<HipEngine> eng(HipEngine::Create(err, h.Definition(), nullptr));
+  KbLayout lay;
+  err = file.CheckHeader(h, lay);
+  if (!err.ok()) return nullptr;
+  CiEngineDefinition def;
+  err = KbLoadDefinition(h, precType, def);
+  if (!err.ok()) return nullptr;
+  CiHipShard window{0, h.Q, -1, 0};
+  if (shard) {
+    if (nLocal < 0) { err = Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(nLocal), "The number of local questions cannot be negative."); return nullptr; }
+    if (shard->_qTotal != 0 && shard->_qTotal != h.Q) {
+      err = Error::MakeP(ErrCode::InsufficientEngineDimensions, "[_qTotal=" + std::to_string(shard->_qTotal) + " of " + std::to_string(h.Q) + "]",
+                         "The shard's total question count is not the KB file's.");
+      return nullptr;
+    }
+    if (!lay.HasWindow(shard->_qFirst, nLocal)) {
+      err = Error::MakeP(ErrCode::IndexOutOfRange, "[" + std::to_string(shard->_qFirst) + ", " + std::to_string(shard->_qFirst) + " + " + std::to_string(nLocal) + ") of " +
+                         std::to_string(h.Q), "The shard's question range is not within the KB file's.");
+      return nullptr;
+    }
+    window._qFirst = shard->_qFirst;
+    window._device = shard->_device;
+    def._nQuestions = nLocal;
+  }
+  std::unique_ptr<HipEngine> eng(HipEngine::Create(err, def, shard ? &window : nullptr));
   if (!eng) return nullptr;
   HipEngine &e = *eng;
   hipSetDevice(e._device);
-  err = e.IoRows(file.f, filePath, false, false);
-  if (err.ok()) err = e.IoRows(file.f, filePath, true, false);
-  if (err.ok()) err = e.IoVB(file.f, filePath, false);
+  const int fe = (int)lay.elem;
+  err = file.Seek(lay.SaOffset(e._qFirst));
+  if (err.ok()) err = e.IoRows(file.f, filePath, false, false, fe);
+  if (err.ok()) err = file.Seek(lay.MdOffset(e._qFirst));
+  if (err.ok()) err = e.IoRows(file.f, filePath, true, false, fe);
+  if (err.ok()) err = file.Seek(lay.vbOff);
+  if (err.ok()) err = e.IoVB(file.f, filePath, false, fe);
   if (!err.ok()) return nullptr;
   e._nQuestionsAsked.store(h.nAsked);
-  err = file.ReadTrailer(e._Q, e._T, e._questionGapList, e._targetGapList, e._questionIds, e._targetIds, e._quizIds);
-  if (!err.ok()) return nullptr;
-  for (int64_t g : e._questionGapList) BitSet(e._hQGap, g, true);
+  if (e._qTotal == e._Q) {
+    err = file.ReadTrailer(e._Q, e._T, e._questionGapList, e._targetGapList, e._questionIds, e._targetIds, e._quizIds);
+    if (!err.ok()) return nullptr;
+    for (int64_t g : e._questionGapList) BitSet(e._hQGap, g, true);
+  } else {
+    std::unique_ptr<FileTrailer> kept(new FileTrailer());
+    err = file.ReadTrailer(h.Q, e._T, kept->questionGaps, e._targetGapList, kept->questionIds, e._targetIds, e._quizIds);
+    if (!err.ok()) return nullptr;
+    for (int64_t g : kept->questionGaps)
+      if (e.OwnsQuestion(g) && !BitTest(e._hQGap, g - e._qFirst)) {
+        BitSet(e._hQGap, g - e._qFirst, true);
+        e._questionGapList.push_back(g - e._qFirst);
+        e._questionIds.Vacate(g - e._qFirst);
+      }
+    e._globalQuestionGaps = kept->questionGaps;
+    e._fileTrailer = std::move(kept);
+  }
   for (int64_t g : e._targetGapList) BitSet(e._hTGap, g, true);
   e._nTargetGaps = (int64_t)e._targetGapList.size();
   err = e.UploadGaps();

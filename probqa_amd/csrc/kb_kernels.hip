@@ -3,6 +3,9 @@
 //   fill_synthetic  : deterministic benchmark / test cube, bit-identical to probqa_amd/synth.py (numpy)
 //   train           : CETrainOperation::Perform1 / Perform2 (PqaCore/CETrainOperation.cpp:15-83)
 //   top_targets     : ListTopTargets (PqaCore/CEListTopTargetsAlgorithm.cpp:30-95): descending probability
+#include <algorithm>
+#include <type_traits>
+
 #include "pqa_device.h"
 #include "pqa_kernels.h"
 
@@ -317,7 +320,114 @@ __global__ __launch_bounds__(256) void pack_answer_rows_kernel(const PackPair *_
   __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- .kb rows between the file's dense layout in one number type and the cube's padded layout in another -------------------------------
+// A thread moves four consecutive elements of one row, columns [4 g, 4 g + 4): on the cube's side that is a 16-byte aligned unit of a
+// Float row (two of a Double row), whatever the row -- rows start on 128-byte lines.  The dense side is only element-aligned: row r
+// starts r T elements into the block, so with an odd T every other row is 8 (fp64) or 4, 8, 12 (fp32) bytes off.  The quad is moved by
+// the widest access its address allows -- 16 bytes where both sides allow it, 8 or 4 on the dense side otherwise; consecutive lanes
+// stay on consecutive addresses either way.  A row's last 1..3 elements go one by one, so nothing outside [0, T) of a row is read
+// or written on either side: the cube's padding stays as Create left it, and the dense neighbours are other rows.
+// 256 threads = rowsPerBlock rows x lanesPerRow quads (a power of two: short rows share a workgroup); grid.x strides along the row,
+// grid.y over the rows.  No LDS, no barrier: a streaming copy whose speed is the loads in flight.
+template <typename E>
+__device__ __forceinline__ void quad_load(const E *p, E (&v)[4]) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  if constexpr (sizeof(E) == 8) {
+    if ((a & 15) == 0) {
+      const double2 x = reinterpret_cast<const double2 *>(p)[0], y = reinterpret_cast<const double2 *>(p)[1];
+      v[0] = x.x; v[1] = x.y; v[2] = y.x; v[3] = y.y;
+    } else { v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3]; }
+  } else {
+    if ((a & 15) == 0) {
+      const float4 x = reinterpret_cast<const float4 *>(p)[0];
+      v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    } else if ((a & 7) == 0) {
+      const float2 x = reinterpret_cast<const float2 *>(p)[0], y = reinterpret_cast<const float2 *>(p)[1];
+      v[0] = x.x; v[1] = x.y; v[2] = y.x; v[3] = y.y;
+    } else { v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3]; }
+  }
+}
+template <typename E>
+__device__ __forceinline__ void quad_store(E *p, const E (&v)[4]) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  if constexpr (sizeof(E) == 8) {
+    if ((a & 15) == 0) {
+      reinterpret_cast<double2 *>(p)[0] = make_double2(v[0], v[1]);
+      reinterpret_cast<double2 *>(p)[1] = make_double2(v[2], v[3]);
+    } else { p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3]; }
+  } else {
+    if ((a & 15) == 0) reinterpret_cast<float4 *>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    else if ((a & 7) == 0) {
+      reinterpret_cast<float2 *>(p)[0] = make_float2(v[0], v[1]);
+      reinterpret_cast<float2 *>(p)[1] = make_float2(v[2], v[3]);
+    } else { p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3]; }
+  }
+}
+// One element on its way: fp64 -> fp32 rounds to nearest even (the conversion instruction's default mode, what (float)x is on the host);
+// fp32 -> fp64 is exact; kRound: fp64 words that are to hold fp32 values.  A finite value that does not stay finite is counted.
+template <typename D, typename S, bool kRound>
+__device__ __forceinline__ D convert_element(S x, unsigned &bad) {
+  if constexpr (sizeof(S) == 8 && (sizeof(D) == 4 || kRound)) {
+    const float y = (float)x;
+    if (fabs(x) < HUGE_VAL && !(fabsf(y) < HUGE_VALF)) bad++;
+    return (D)y;
+  } else {
+    return (D)x;
+  }
+}
+template <typename DenseT, typename CubeT, bool kToCube, bool kRound>
+__global__ __launch_bounds__(256) void convert_rows_kernel(DenseT *__restrict__ dense, CubeT *__restrict__ cube, int64_t T, int64_t ldT, int64_t nRows,
+                                                           unsigned rowsPerQ, unsigned rowBase, unsigned qStride, int laneBits, unsigned *overflow) {
+  using Src = typename std::conditional<kToCube, DenseT, CubeT>::type;
+  using Dst = typename std::conditional<kToCube, CubeT, DenseT>::type;
+  const int lanesPerRow = 1 << laneBits, lane = threadIdx.x & (lanesPerRow - 1), rowInBlock = threadIdx.x >> laneBits, rowsPerBlock = 256 >> laneBits;
+  unsigned bad = 0;
+  for (int64_t r = (int64_t)blockIdx.y * rowsPerBlock + rowInBlock; r < nRows; r += (int64_t)gridDim.y * rowsPerBlock) {
+    const unsigned ru = (unsigned)r;   // (the launcher: nRows < 2^31)
+    const int64_t cubeRow = (int64_t)(ru / rowsPerQ) * qStride + (ru % rowsPerQ) + rowBase;
+    DenseT *d = dense + r * T;
+    CubeT *c = cube + cubeRow * ldT;
+    const Src *src;
+    Dst *dst;
+    if constexpr (kToCube) { src = d; dst = c; } else { src = c; dst = d; }
+    for (int64_t t = ((int64_t)blockIdx.x * lanesPerRow + lane) * 4; t < T; t += (int64_t)gridDim.x * lanesPerRow * 4) {
+      if (t + 4 <= T) {
+        Src s[4];
+        Dst o[4];
+        quad_load(src + t, s);
+#pragma unroll
+        for (int e = 0; e < 4; e++) o[e] = convert_element<Dst, Src, kRound>(s[e], bad);
+        quad_store(dst + t, o);
+      } else {
+        for (int64_t e = t; e < T; e++) dst[e] = convert_element<Dst, Src, kRound>(src[e], bad);
+      }
+    }
+  }
+  if (bad != 0) atomicAdd(overflow, bad);
+}
+
 }  // namespace
+
+hipError_t LaunchConvertRows(const ConvertRows &c, hipStream_t stream) {
+  if (c.dense == nullptr || c.cube == nullptr || c.overflow == nullptr || c.T < 1 || c.ldT < c.T || c.nRows < 0 || c.nRows > 0x7fffffff || c.rowsPerQ < 1 ||
+      c.rowsPerQ > 0x7fffffff || c.rowBase < 0 || c.rowBase > 0x7fffffff || c.qStride < 0 || c.qStride > 0x7fffffff)
+    return hipErrorInvalidValue;
+  if (c.nRows == 0) return hipSuccess;
+  const int64_t quads = (c.T + 3) / 4;
+  int laneBits = 0;
+  while (laneBits < 8 && ((int64_t)1 << laneBits) < quads) laneBits++;
+  const int64_t lanesPerRow = (int64_t)1 << laneBits, rowsPerBlock = 256 / lanesPerRow;
+  const dim3 grid((unsigned)std::min<int64_t>((quads + lanesPerRow - 1) / lanesPerRow, 64), (unsigned)std::min<int64_t>((c.nRows + rowsPerBlock - 1) / rowsPerBlock, 65535));
+#define PQA_CONVERT(DenseT, CubeT, TO_CUBE, ROUND)                                                                                                          \
+  hipLaunchKernelGGL((convert_rows_kernel<DenseT, CubeT, TO_CUBE, ROUND>), grid, dim3(256), 0, stream, static_cast<DenseT *>(c.dense), static_cast<CubeT *>(c.cube), \
+                     c.T, c.ldT, c.nRows, (unsigned)c.rowsPerQ, (unsigned)c.rowBase, (unsigned)c.qStride, laneBits, c.overflow)
+  if (c.denseElem == 8 && c.cubeElem == 4 && !c.roundF32) { if (c.toCube) PQA_CONVERT(double, float, true, false); else PQA_CONVERT(double, float, false, false); }
+  else if (c.denseElem == 4 && c.cubeElem == 8 && !c.roundF32) { if (c.toCube) PQA_CONVERT(float, double, true, false); else PQA_CONVERT(float, double, false, false); }
+  else if (c.denseElem == 8 && c.cubeElem == 8 && c.roundF32 && c.toCube) PQA_CONVERT(double, double, true, true);
+  else return hipErrorInvalidValue;   // (equal types move by plain copies: hip_engine_kb.cpp)
+#undef PQA_CONVERT
+  return hipGetLastError();
+}
 
 hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowBytes, unsigned *counter, uint64_t *flag, uint64_t flagValue,
                                 hipStream_t stream) {

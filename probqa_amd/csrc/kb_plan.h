@@ -104,4 +104,28 @@ struct BestPick {   // {0, -1} while nothing was offered that is a candidate
   }
 };
 
+// Where the arrays of a .kb file lie (layout: hip_engine_kb.cpp), in bytes from the file's start, and where the rows of a window of
+// questions [qFirst, qFirst + nLocal) lie within them: a shard seeks to its two blocks instead of reading through the others'.
+//   header 40 | sA [Q][K][T] | mD [Q][T] | vB [T] | trailer
+// `elem`: bytes of the file's number type (4 or 8).  Every product is checked: dimensions a damaged header may claim do not wrap.
+struct KbLayout {
+  static constexpr int64_t kHeaderBytes = 40;
+  int64_t K = 0, Q = 0, T = 0, elem = 0;
+  int64_t rowBytes = 0, saBytes = 0, mdBytes = 0, vbOff = 0, trailerOff = 0;   // (the sizes of the whole blocks)
+  bool valid = false;
+  static bool Mul(int64_t a, int64_t b, int64_t &out) { return !__builtin_mul_overflow(a, b, &out); }
+  static bool Add(int64_t a, int64_t b, int64_t &out) { return !__builtin_add_overflow(a, b, &out); }
+  KbLayout() {}
+  KbLayout(int64_t nAnswers, int64_t nQuestions, int64_t nTargets, int64_t elemBytes) : K(nAnswers), Q(nQuestions), T(nTargets), elem(elemBytes) {
+    if (K < 1 || Q < 1 || T < 1 || (elem != 4 && elem != 8)) return;
+    int64_t qk = 0, end = 0;
+    valid = Mul(T, elem, rowBytes) && Mul(Q, K, qk) && Mul(qk, rowBytes, saBytes) && Mul(Q, rowBytes, mdBytes) &&
+            Add(kHeaderBytes, saBytes, end) && Add(end, mdBytes, vbOff) && Add(vbOff, rowBytes, trailerOff);
+  }
+  bool HasWindow(int64_t qFirst, int64_t nLocal) const { return valid && qFirst >= 0 && nLocal >= 1 && qFirst <= Q && nLocal <= Q - qFirst; }
+  int64_t SaOffset(int64_t qFirst) const { return kHeaderBytes + qFirst * K * rowBytes; }          // the K rows of question qFirst, then the next question's
+  int64_t MdOffset(int64_t qFirst) const { return kHeaderBytes + saBytes + qFirst * rowBytes; }    // one row per question
+  int64_t ArraysEnd() const { return trailerOff; }                                                 // a file shorter than this is cut inside its arrays
+};
+
 }  // namespace pqa

@@ -461,6 +461,22 @@ struct PackPair { const void *rowA, *rowD; void *dst; };
 constexpr int64_t kPackChunkBytes = 16384;
 hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowBytes, unsigned *counter, uint64_t *flag, uint64_t flagValue,
                                 hipStream_t stream);
+// Rows between a .kb file's dense layout in one number type and the cube's padded layout in another (kb_kernels.hip:
+// convert_rows_kernel).  `dense`: nRows rows of T elements back to back, denseElem (4 | 8) bytes each, only element-aligned.
+// `cube`: the first row's question block; dense row r is the cube's row (r / rowsPerQ) * qStride + r % rowsPerQ + rowBase, rows ldT
+// elements of cubeElem bytes apart, 16-byte aligned -- rowsPerQ = K, rowBase = 0, qStride = K + 1: the sA rows of consecutive
+// questions; rowsPerQ = 1, rowBase = K: their mD rows; rowsPerQ = 1, qStride = 0: vB.  toCube: dense -> cube (a load), else a save.
+// roundF32 (denseElem == cubeElem == 8, vB into a Float engine): every value rounded through fp32 on its way.
+// fp64 -> fp32 rounds to nearest even; each finite value that does not stay finite adds one to *overflow (device memory).
+// Only [0, T) of a row is read or written on either side.
+struct ConvertRows {
+  void *dense; void *cube;
+  int denseElem, cubeElem;
+  int64_t T, ldT, nRows, rowsPerQ, rowBase, qStride;
+  bool toCube, roundF32;
+  unsigned *overflow;
+};
+hipError_t LaunchConvertRows(const ConvertRows &c, hipStream_t stream);
 // ListTopTargets (PqaCore/CEListTopTargetsAlgorithm.cpp): top maxCount (prob,target) pairs, descending, gaps skipped.
 // (flag != nullptr: out / nOut / flag are host-coherent; the kernel stores flagValue to *flag after its results)
 hipError_t LaunchTopTargets(const KbView &kb, const double *prior, int64_t maxCount, RatedTargetDev *out,

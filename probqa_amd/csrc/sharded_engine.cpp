@@ -102,7 +102,11 @@ class ShardedEngine final : public IEngine {
   bool EnsurePermQuizGreater(int64_t bound) override { std::lock_guard<OpLock> lk(_opMu); bool ok = true; for (auto &s : _sh) ok = s->EnsurePermQuizGreater(bound) && ok; return ok; }
   bool RemapQuizPermId(int64_t a, int64_t b) override { std::lock_guard<OpLock> lk(_opMu); bool ok = true; for (auto &s : _sh) ok = s->RemapQuizPermId(a, b) && ok; return ok; }
   Error SaveKB(const char *filePath, bool doubleBuffer) override;
-  static ShardedEngine *Load(Error &err, const char *filePath, const std::vector<int> &devices);
+  Error SaveKBAs(const char *filePath, uint8_t precType) override;
+  Error SaveKBShard(const char *, uint8_t) override {
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=SaveKBShard of a one-process sharded engine", "Its shards are saved together: SaveKB / SaveKBAs.");
+  }
+  static ShardedEngine *Load(Error &err, const char *filePath, const std::vector<int> &devices, uint8_t precType = 0);
   Error AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) override;
   Error RemoveQuestions(int64_t n, const int64_t *pQIds) override;
   Error RemoveTargets(int64_t n, const int64_t *pTIds) override;
@@ -1538,33 +1542,48 @@ Error ShardedEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestion
 // own staging buffer; vB, the target gaps and the target / quiz id maps are replicas (shard 0's are written).
 Error ShardedEngine::SaveKB(const char *filePath, bool doubleBuffer) {
   (void)doubleBuffer;
+  return SaveKBAs(filePath, 0);
+}
+// precType 0: the engine's own; another type: every shard's rows pass through the converting kernel on their way out
+Error ShardedEngine::SaveKBAs(const char *filePath, uint8_t precType) {
   std::lock_guard<OpLock> lk(_opMu);
   Error e = FlushAnswers();
   if (!e.ok()) return e;
   for (auto &s : _sh) { e = s->Synchronize(); if (!e.ok()) return e; }   // (also parks resident sweeps)
-  KbFile file(filePath, true);
   HipEngine &s0 = *_sh[0];
+  uint64_t precision = 0;
+  int fe = 0;
+  e = KbSavePrecision(precType, s0.PrecisionType(), s0.PrecMantissa(), s0.PrecExponent(), precision, fe);
+  if (!e.ok()) return e;
+  KbFile file(filePath, true);
   const uint64_t nAsked = s0.GetTotalQuestionsAsked(e);
-  e = file.WriteHeader(KbHeader{PackPrecision(s0.PrecisionType(), s0.PrecMantissa(), s0.PrecExponent()), _K, _Q, _T, nAsked});
-  for (size_t s = 0; e.ok() && s < _sh.size(); s++) e = _sh[s]->IoRows(file.f, filePath, false, true);
-  for (size_t s = 0; e.ok() && s < _sh.size(); s++) e = _sh[s]->IoRows(file.f, filePath, true, true);
-  if (e.ok()) e = s0.IoVB(file.f, filePath, true);
+  e = file.WriteHeader(KbHeader{precision, _K, _Q, _T, nAsked});
+  for (size_t s = 0; e.ok() && s < _sh.size(); s++) e = _sh[s]->IoRows(file.f, filePath, false, true, fe);
+  for (size_t s = 0; e.ok() && s < _sh.size(); s++) e = _sh[s]->IoRows(file.f, filePath, true, true, fe);
+  if (e.ok()) e = s0.IoVB(file.f, filePath, true, fe);
   std::vector<int64_t> tGaps, tmp;
   s0.GetGapLists(tmp, tGaps);
   if (e.ok()) e = file.WriteTrailer(_qGapList, tGaps, _questionIds, s0.TargetIds(), s0.QuizIds());
   return e.ok() ? file.FlushAndClose() : e;
 }
 
-ShardedEngine *ShardedEngine::Load(Error &err, const char *filePath, const std::vector<int> &devices) {
+ShardedEngine *ShardedEngine::Load(Error &err, const char *filePath, const std::vector<int> &devices, uint8_t precType) {
   KbFile file(filePath, false);
   KbHeader h;
   err = file.ReadHeader(h);
   if (!err.ok()) return nullptr;
-  std::unique_ptr<ShardedEngine> eng(Create(err, h.Definition(), devices));
+  KbLayout lay;
+  err = file.CheckHeader(h, lay);
+  if (!err.ok()) return nullptr;
+  CiEngineDefinition def;
+  err = KbLoadDefinition(h, precType, def);   // (precType 0: the file's own)
+  if (!err.ok()) return nullptr;
+  const int fe = (int)lay.elem;
+  std::unique_ptr<ShardedEngine> eng(Create(err, def, devices));
   if (!eng) return nullptr;
-  for (size_t s = 0; err.ok() && s < eng->_sh.size(); s++) err = eng->_sh[s]->IoRows(file.f, filePath, false, false);
-  for (size_t s = 0; err.ok() && s < eng->_sh.size(); s++) err = eng->_sh[s]->IoRows(file.f, filePath, true, false);
-  if (err.ok()) err = eng->_sh[0]->IoVB(file.f, filePath, false);
+  for (size_t s = 0; err.ok() && s < eng->_sh.size(); s++) err = eng->_sh[s]->IoRows(file.f, filePath, false, false, fe);
+  for (size_t s = 0; err.ok() && s < eng->_sh.size(); s++) err = eng->_sh[s]->IoRows(file.f, filePath, true, false, fe);
+  if (err.ok()) err = eng->_sh[0]->IoVB(file.f, filePath, false, fe);
   std::vector<double> vb((size_t)h.T);   // shard 0's vB (already in the engine's number type) to the other replicas
   if (err.ok()) err = eng->_sh[0]->GetKB(nullptr, nullptr, vb.data());
   for (size_t i = 1; err.ok() && i < eng->_sh.size(); i++) err = eng->_sh[i]->SetVBFromHost(vb.data());
@@ -1585,8 +1604,8 @@ ShardedEngine *ShardedEngine::Load(Error &err, const char *filePath, const std::
   return eng.release();
 }
 
-IEngine *LoadShardedEngine(Error &err, const char *filePath, const std::vector<int> &devices) {
-  return ShardedEngine::Load(err, filePath, devices);
+IEngine *LoadShardedEngine(Error &err, const char *filePath, const std::vector<int> &devices, uint8_t precType) {
+  return ShardedEngine::Load(err, filePath, devices, precType);
 }
 
 IEngine *CreateShardedEngine(Error &err, const CiEngineDefinition &def, const std::vector<int> &devices) {

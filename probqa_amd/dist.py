@@ -413,6 +413,69 @@ def resume_quiz_batch(engine, lists, rank: int, world: int, group: Optional[dist
     return quizzes
 
 
+# ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
+# Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
+# place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges
+# of one file, so the only ordering a save needs is: the file is emptied before the first part lands, and nobody reads it before the
+# last one has.  Deployments without a process group order the calls themselves: empty (or remove) the file, let every rank call
+# engine.save_kb_shard(path) in any order, and take the file once all have returned.
+
+
+def load_shard(factory, path: str, rank: int, world: int, precision=None, device: int = -1):
+    """This rank's shard of the .kb file `path`: questions shard_range(Q, world, rank) of the file's Q, in `precision` (None: the
+    file's).  No collective: every rank reads the 40-byte header and its own rows."""
+    from . import interop
+
+    _, dims, _ = interop.read_kb_header(path)
+    first, limit = shard_range(dims.n_questions, world, rank)
+    return factory.load_hip_engine(path, precision, q_first=first, n_local=limit - first, q_total=dims.n_questions, device=device)
+
+
+def save_kb(engine, path: str, rank: int, world: int, group: Optional[dist.ProcessGroup] = None, precision=None) -> None:
+    """SaveKB of the shards of `world` ranks into ONE file: a collective every rank calls with the same path and precision.  The
+    rank that holds question 0 creates or empties the file; a barrier; every rank writes its part; one status word.  All or none:
+    if any rank failed, the rank that holds question 0 removes the file and every rank raises the first failure."""
+    import os
+
+    from . import interop
+
+    multi = dist.is_initialized() and dist.get_world_size(group) > 1
+    creator = engine.get_option("q_first") == 0
+    error = None
+    if creator:
+        try:
+            open(path, "wb").close()
+        except OSError as e:
+            error = "cannot create %s: %s" % (path, e)
+    if multi:
+        dist.barrier(group=group)
+    if error is None:
+        try:
+            engine.save_kb_shard(path, precision)
+        except interop.PqaException as e:
+            error = str(e)
+    first = rank if error is not None else world
+    if multi:
+        word = torch.tensor([first], dtype=torch.int64)
+        on_dev = dist.get_backend(group) == "nccl"
+        if on_dev:
+            word = word.cuda()
+        dist.all_reduce(word, op=dist.ReduceOp.MIN, group=group)
+        first = int(word.item())
+    if first >= world:
+        return
+    if creator:
+        try:
+            os.remove(path)
+        except OSError:
+            pass
+    text = [error if rank == first else None]
+    if multi:
+        dist.broadcast_object_list(text, src=dist.get_global_rank(group, first) if group is not None else first, group=group,
+                                   device=torch.device("cuda", torch.cuda.current_device()) if on_dev else None)
+    raise interop.PqaException("rank %d: %s" % (first, text[0]))
+
+
 class ShmRowExchange:
     """resume_quiz / resume_quiz_batch without a process group, for the shared-memory deployments that use ShmSelector: the
     package lives in ONE /dev/shm segment every rank has mapped and registered with its GPU.  The owners pack straight into it

@@ -159,6 +159,9 @@ HIP_EXPORTS = {
     "PqaEngine_RecordQuizTargetBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
+    "PqaEngineFactory_LoadHipEngineAs": (_vp, [_vp, _pvp, ctypes.c_char_p, _u8, ctypes.POINTER(CiHipShard), _i64]),
+    "PqaHip_SaveKBAs": (_vp, [_vp, ctypes.c_char_p, _u8]),
+    "PqaHip_SaveKBShard": (_vp, [_vp, ctypes.c_char_p, _u8]),
 }
 
 _lib = None
@@ -292,6 +295,25 @@ class EngineDimensions:
 
 
 INVALID_PQA_ID = -1
+
+
+def _prec_value(precision) -> int:
+    """PrecisionType, its integer, or None (0: the file's / the engine's own) as the C ABI's precType."""
+    if precision is None:
+        return 0
+    return int(precision.value if isinstance(precision, PrecisionType) else precision)
+
+
+def read_kb_header(file_path: str):
+    """(PrecisionType, EngineDimensions, questions asked) of a .kb file: its first 40 bytes."""
+    import struct
+
+    with open(file_path, "rb") as f:
+        raw = f.read(40)
+    if len(raw) != 40:
+        raise PqaException("%s is too short for a .kb header" % file_path)
+    prec, k, q, t, asked = struct.unpack("<QqqqQ", raw)
+    return PrecisionType(prec & 0xF), EngineDimensions(k, q, t), asked
 
 
 class AddQuestionParam:  # reference ProbQA.py:381-387
@@ -499,6 +521,16 @@ class PqaEngine:
 
     def save_kb(self, file_path: str, b_double_buffer: bool, throw: bool = True):
         return _check(_lib.PqaEngine_SaveKB(self.c_engine, file_path.encode(), 1 if b_double_buffer else 0), throw)
+
+    def save_kb_as(self, file_path: str, precision: Optional["PrecisionType"], throw: bool = True):
+        """save_kb in a chosen precision (PrecisionType.FLOAT / .DOUBLE; None = the engine's own: the bytes save_kb writes).  The rows are
+        converted on the device on their way out.  Whole engines (one device, or the one-process sharded engine)."""
+        return _check(_lib.PqaHip_SaveKBAs(self.c_engine, file_path.encode(), _prec_value(precision)), throw)
+
+    def save_kb_shard(self, file_path: str, precision: Optional["PrecisionType"] = None, throw: bool = True):
+        """This shard's part of a save, in place: its two blocks of rows at their offsets of `file_path`, which is not emptied; the
+        shard that holds question 0 also writes header, vB and trailer.  Complete once every shard has returned (dist.save_kb)."""
+        return _check(_lib.PqaHip_SaveKBShard(self.c_engine, file_path.encode(), _prec_value(precision)), throw)
 
     def start_maintenance(self, force_quizzes: bool, throw: bool = True):
         return _check(_lib.PqaEngine_StartMaintenance(self.c_engine, force_quizzes), throw)
@@ -827,6 +859,22 @@ class PqaEngineFactory:
         c_engine = _lib.PqaEngineFactory_LoadCpuEngine(self.c_factory, ctypes.byref(c_err), file_path.encode(),
                                                        mem_pool_max_bytes)
         return (PqaEngine(c_engine) if c_engine else None), PqaError.factor(c_err.value)
+
+    def load_hip_engine(self, file_path: str, precision: Optional[PrecisionType] = None, q_first: int = 0, n_local: Optional[int] = None,
+                        q_total: Optional[int] = None, device: int = -1) -> PqaEngine:
+        """Load a .kb file into an engine of `precision` (None: the file's), whatever the file's own -- the rows are converted on the
+        device.  n_local given: a shard holding questions [q_first, q_first + n_local) of the file on `device` (q_total: None, or the
+        file's question count, checked).  Raises PqaException; no engine exists then."""
+        c_err = ctypes.c_void_p()
+        shard = None
+        if n_local is not None:
+            shard = ctypes.byref(CiHipShard(q_first, q_total if q_total is not None else 0, device, 0))
+        elif q_first != 0 or q_total is not None or device != -1:
+            raise ValueError("q_first, q_total and device describe a shard: give n_local")
+        c_engine = _lib.PqaEngineFactory_LoadHipEngineAs(self.c_factory, ctypes.byref(c_err), file_path.encode(), _prec_value(precision), shard,
+                                                         n_local if n_local is not None else 0)
+        _check(c_err.value)
+        return PqaEngine(c_engine)
 
 
 class MaintenanceLock:  # reference ProbQA.py:786-796
