@@ -18,6 +18,11 @@ typedef struct {
   int32_t _reserved;
 } CiHipShard;
 
+typedef struct {     /* an entry of PqaEngine_ListTopQuestions: CiRatedTarget's layout, 16 bytes */
+  int64_t _iQuestion; /* GLOBAL question index */
+  double _priority;
+} CiRatedQuestion;
+
 typedef struct {     /* result of a stream-ordered selection; lives in device or pinned host memory */
   double _priority;
   int64_t _iQuestion; /* GLOBAL question index, -1 if no eligible question in this shard */
@@ -212,6 +217,33 @@ PQACORE_API void *PqaEngine_RecordQuizTargetBatch(void *pvEngine, const int64_t 
  * nQuizzes x maxCount records (the reference's GPU engine copies all nTargets posteriors per quiz: PqaCore/CudaEngine.cpp:251-289). */
 PQACORE_API void *PqaEngine_ListTopTargetsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
                                                 CiRatedTarget *pDest, int64_t *pCounts);
+/* The best next questions of a quiz, listed on the device: the quiz's questions that are neither asked nor gaps and whose priority is
+ * > 0, by descending priority, ascending question index among equal priorities, at most maxCount of them.  Returns the number listed;
+ * -1 and *ppError on failure.  The priorities are the ones PqaEngine_EvalPriorities returns for that quiz at that moment, bit for bit
+ * (the same sweep, the pole fix behind it redoing every listed question): on a Double engine the first entry is the question
+ * PqaEngine_NextQuestionArgmax selects whenever any priority is positive; a Float engine lists by its fp32 sweep's priorities, as its
+ * single-quiz argmax selects by them (no fp64 re-rank).  Question ids are GLOBAL ids; an engine made by
+ * PqaEngineFactory_CreateHipEngineSharded lists its own questions (probqa_amd/dist.py merges the ranks' lists), the one-process
+ * sharded engine (PQA_DEVICES) lists on every shard at once and merges on the host.
+ * No quiz state changes: the active question stays what it was, no counter moves; a client that takes a listed question follows with
+ * PqaEngine_SetActiveQuestion and PqaEngine_RecordAnswer.  Towards the resident sweep (option "server"), the speculative sweep and the
+ * pole list the call does what PqaEngine_EvalPriorities does.
+ * maxCount <= 256: the listing kernels run on the engine's stream behind the sweep and write the records into host-coherent memory;
+ * nothing of size nQuestions crosses to the host.  Beyond 256 the call is a bulk export, as long listings of targets are: the priority
+ * vector is copied and its prefix taken on the host, in the same order.
+ * maxCount == 0 lists nothing and is no error.  Errors: an unknown quiz and maintenance mode as PqaEngine_ListTopTargets answers them,
+ * maxCount < 0 NegativeCount, pDest == NULL with maxCount > 0 NullArgument -- PqaEngine_ListTopTargetsBatch's codes.  C++ exceptions
+ * do not cross the two calls (StdException / SRException). */
+PQACORE_API int64_t PqaEngine_ListTopQuestions(void *pvEngine, void **ppError, const int64_t iQuiz, const int64_t maxCount,
+                                               CiRatedQuestion *pDest);
+/* The same for nQuizzes <= 256 distinct quizzes behind ONE batched sweep: pDest[i * maxCount + j], j < pCounts[i], is the listing of
+ * pQuizzes[i] by the priorities PqaEngine_EvalPrioritiesBatch returns for the same batch, whichever form option "batch_form" and the
+ * batch give that sweep (the listing reads the quizzes' own vectors or the quiz-minor matrix where the sweep left them; it forces no
+ * form).  What crosses to the host is nQuizzes x maxCount records.  nQuizzes > 256, a repeated or an unknown quiz id are refused as
+ * PqaEngine_EvalPrioritiesBatch refuses them, the error naming the entry, and nothing is written; negative counts and missing buffers
+ * as PqaEngine_ListTopTargetsBatch. */
+PQACORE_API void *PqaEngine_ListTopQuestionsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
+                                                  CiRatedQuestion *pDest, int64_t *pCounts);
 /* The priority vectors of nQuizzes <= 256 distinct quizzes from ONE sweep that reads the cube once for the whole batch
  * (batch_kernels.hip): pOut[i * nLocalQuestions + q] = priority of local question q for pQuizzes[i], 0 for gap / asked
  * questions.  The deterministic output behind PqaEngine_NextQuestionArgmaxBatch's row-sharing form. */
@@ -314,6 +346,9 @@ PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_
    repeated, or -1; the error code the call returns}.
    what = "better_pick": pIn = {priority, index} per shard; pOut = {priority, index} of the winner (maximum priority, lowest index
    on ties, a NaN counts as -infinity, a negative index is no candidate; {0, -1} if there is none).
+   what = "merge_top": pIn = {maxCount, nLists, then per list n and n x {priority bits, index}}; pOut = {n, then n x {priority bits,
+   index}}: the best maxCount of the shards' PqaEngine_ListTopQuestions lists under the listings' order (descending priority, ascending
+   index among equal priorities; a priority that is not > 0 -- a NaN among them -- or a negative index is no candidate).
    Returns the number of results written, or -1 for a malformed script / too small an output. */
 PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut);
 

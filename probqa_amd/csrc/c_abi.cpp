@@ -511,6 +511,20 @@ PQACORE_API void *PqaEngine_ListTopTargetsBatch(void *pvEngine, const int64_t nQ
   ENGINE_OR_RETURN_ERROR;
   return ReturnErr(pEng->ListTopTargetsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts));
 }
+// (both behind the exception barrier: the listings size host vectors by the caller's counts)
+PQACORE_API int64_t PqaEngine_ListTopQuestions(void *pvEngine, void **ppError, const int64_t iQuiz, const int64_t maxCount, CiRatedQuestion *pDest) {
+  ENGINE_OR_SET_ERROR(-1);
+  int64_t n = -1;
+  Error err = Guarded([&]() { Error e; n = pEng->ListTopQuestions(e, iQuiz, maxCount, pDest); return e; });
+  if (!err.ok()) n = -1;
+  AssignErr(ppError, err);
+  return n;
+}
+PQACORE_API void *PqaEngine_ListTopQuestionsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
+                                                  CiRatedQuestion *pDest, int64_t *pCounts) {
+  ENGINE_OR_RETURN_ERROR;
+  return ReturnErr(Guarded([&]() { return pEng->ListTopQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); }));
+}
 PQACORE_API void *PqaHip_SelectArgmaxBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, CiHipSelection *pOut) {
   ENGINE_OR_RETURN_ERROR;
   return ReturnErr(pEng->SelectArgmaxBatch(nQuizzes, pQuizzes, pOut));
@@ -858,6 +872,26 @@ PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, 
     pOut[0] = pqa::FirstBadRemoval((int64_t)qWords.size(), qWords.data(), pIn[0], isGap);
     pOut[1] = (int64_t)pqa::CheckRemoval((int64_t)qWords.size(), qWords.data(), pIn[0], isGap, "").code;
     return 2;
+  }
+  if (w == "merge_top") {   // {maxCount, nLists, then per list n and n x {priority bits, index}} -> {n, then n x {priority bits, index}}
+    if (nIn < 2 || pIn[1] < 0) return -1;
+    std::vector<std::vector<pqa::RatedIndex>> recs;
+    at = 2;
+    for (int64_t l = 0; l < pIn[1]; l++) {
+      if (at >= nIn || pIn[at] < 0 || pIn[at] > (nIn - at - 1) / 2) return -1;
+      std::vector<pqa::RatedIndex> v((size_t)pIn[at]);
+      for (size_t k = 0; k < v.size(); k++) { std::memcpy(&v[k].priority, &pIn[at + 1 + 2 * (int64_t)k], 8); v[k].index = pIn[at + 2 + 2 * (int64_t)k]; }
+      at += 1 + 2 * pIn[at];
+      recs.push_back(std::move(v));
+    }
+    if (at != nIn) return -1;
+    std::vector<std::pair<const pqa::RatedIndex *, int64_t>> lists;
+    for (const auto &v : recs) lists.emplace_back(v.data(), (int64_t)v.size());
+    const std::vector<pqa::RatedIndex> best = pqa::MergeTop(lists, pIn[0]);
+    if (1 + 2 * (int64_t)best.size() > nOut) return -1;
+    pOut[0] = (int64_t)best.size();
+    for (size_t k = 0; k < best.size(); k++) { std::memcpy(&pOut[1 + 2 * k], &best[k].priority, 8); pOut[2 + 2 * k] = best[k].index; }
+    return 1 + 2 * (int64_t)best.size();
   }
   if (w == "better_pick") {
     if (nIn % 2 != 0 || nOut < 2) return -1;

@@ -264,6 +264,7 @@ HipEngine::~HipEngine() {
   FreeTrainBulk();
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   if (_hTopBatch) hipHostFree(_hTopBatch);
+  if (_hTopQ) hipHostFree(_hTopQ);
   hipFree(_dTopExact);
   hipFree(_dRowStage);
   if (_hPack) hipHostFree(_hPack);

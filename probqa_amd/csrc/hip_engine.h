@@ -253,6 +253,8 @@ class IEngine {
   virtual Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) = 0;
   virtual Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) = 0;
   virtual Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) = 0;
+  virtual int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) = 0;
+  virtual Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) = 0;
   virtual int64_t AnswerRowSlotBytes() const = 0;
   virtual Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) = 0;
   virtual int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) = 0;
@@ -332,6 +334,9 @@ class HipEngine : public IEngine {
   Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) override;
   Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) override;
   Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
+  // the best next questions by priority (hip_engine_list.cpp): what EvalPriorities / EvalPrioritiesBatch return, listed on the device
+  int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
+  Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
   // ---- a shard driven by a process of its own (hip_engine_resume.cpp): the rows of answered questions as a package -- slot i
   // = sA[q_i][k_i][0..ldT) then mD[q_i][0..ldT), in the cube's element type -- filled by the owners, consumed by every rank
   int64_t AnswerRowSlotBytes() const override { return 2 * _ldT * (int64_t)_elem; }
@@ -390,6 +395,14 @@ class HipEngine : public IEngine {
   uint32_t PrecMantissa() const { return _precMantissa; }
   uint16_t PrecExponent() const { return _precExponent; }
   Error UnavailableWords(int64_t iQuiz, std::vector<uint32_t> &words);
+  // ListTopQuestions / ListTopQuestionsBatch in two halves likewise (the sharded engine has every shard's sweep and listing in flight
+  // before it waits for the first): Enqueue* validates and launches, Collect* waits and hands over this shard's best
+  // min(maxCount, local questions) per quiz, GLOBAL ids, pDest[i * stride + j], j < pCounts[i].  One listing at a time between the two.
+  Error EnqueueTopQuestions(int64_t iQuiz, int64_t maxCount, bool haveDest);
+  int64_t CollectTopQuestions(Error &err, CiRatedQuestion *pDest);
+  Error EnqueueTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount);
+  Error CollectTopQuestionsBatch(int64_t n, int64_t stride, CiRatedQuestion *pDest, int64_t *pCounts);
+  static Error CheckTopQuestionsBatchArgs(int64_t n, const int64_t *pQuizzes, int64_t maxCount, bool haveDest, bool haveCounts);   // what comes before the lock
   // a batched selection in two halves: every shard's sweep is in flight before the first one is waited for
   Error EnqueueBatch(int64_t n, const int64_t *pQuizzes, bool wantPriorities, uint64_t *pTag);
   Error CollectBatchSelections(int64_t n, uint64_t tag, CiHipSelection *pOut);
@@ -498,6 +511,21 @@ class HipEngine : public IEngine {
   RatedTargetDev *_hTopBatch = nullptr;
   int64_t _hTopBatchRecords = 0;
   Error EnsureTopScratch(int64_t nQuizzes, int64_t want);
+  Error EnsureTopScratchRecords(int64_t need);   // (both buffers; the question listing shares them)
+  // ListTopQuestions (hip_engine_list.cpp): what a listing in flight between its two halves is, and the host-coherent lines a batch's
+  // results arrive in -- records, then counts, then one flag per quiz.  Between the halves _mu is free (the sharded engine has every
+  // shard's listing in flight before it waits for the first), so the single and the batch listing keep a record each -- the single one
+  // under the sharded engine's operation lock, the batch one under its batch context 0, as _ctx[0] is -- and a record refers to no
+  // quiz: a list of more than 256 questions takes its copy of the priorities and of the asked bits in the first half.
+  struct TopQFlight { int64_t n = 0, want = 0; uint64_t op = 0; bool onHost = false; std::vector<double> pri; std::vector<std::vector<uint32_t>> asked; };
+  TopQFlight _topQ, _topQBatch;
+  RatedTargetDev *_hTopQ = nullptr;
+  int64_t _hTopQRecords = 0;
+  Error EnqueueTopQuestionsLocked(Quiz *q, int64_t maxCount);
+  int64_t CollectTopQuestionsLocked(Error &err, CiRatedQuestion *pDest);
+  Error EnqueueTopQuestionsBatchLocked(int64_t n, const int64_t *pQuizzes, int64_t maxCount);
+  Error CollectTopQuestionsBatchLocked(int64_t n, int64_t stride, CiRatedQuestion *pDest, int64_t *pCounts);
+  int64_t TopQuestionsOfVector(const double *pri, const std::vector<uint32_t> &asked, int64_t want, CiRatedQuestion *pDest) const;   // the host's prefix, same order
   int64_t ListTopTargetsOnHost(Error &err, Quiz *q, int64_t want, CiRatedTarget *pDest, bool referenceOrder = false);
   // ListTopTargets = the fast listing with one entry more than asked for; where it shows equal probabilities, the reference's own
   // order among them (its per-worker heaps, reproduced on the device: kb_kernels.hip LaunchTopTargetsExact) -- option "top_exact"
@@ -529,6 +557,9 @@ class HipEngine : public IEngine {
     uint64_t opFlag;               // completion flag of the sampled selection kernel
     uint64_t topFlag;              // completion flag of whatever listed into top[] last
     RatedTargetDev top[256];
+    int64_t nOutQ;                 // ListTopQuestions of one quiz: lines of its own, so that a ListTopTargets between its two halves
+    uint64_t topQFlag;             // (sharded engine) lists into top[] without touching them
+    RatedTargetDev topQ[256];
   };
   // (Pinned::top: listings of more than kQuizTop targets; up to kQuizTop the quiz's own lines are used, where RecordAnswer's
   //  kernel lists the new posterior's best targets ahead of the ListTopTargets for the same quiz and posterior)

@@ -586,8 +586,8 @@ int64_t HipEngine::ListTopTargetsOnHost(Error &err, Quiz *q, int64_t want, CiRat
 }
 
 // The device scratch of the chunked listing (two buffers of candidate lists) for nQuizzes quizzes at once.
-Error HipEngine::EnsureTopScratch(int64_t nQuizzes, int64_t want) {
-  const int64_t need = nQuizzes * TopBatchScratchRecords(_T, want);
+Error HipEngine::EnsureTopScratch(int64_t nQuizzes, int64_t want) { return EnsureTopScratchRecords(nQuizzes * TopBatchScratchRecords(_T, want)); }
+Error HipEngine::EnsureTopScratchRecords(int64_t need) {
   if (need <= _topScratchRecords) return Error();
   HIP_TRY(hipStreamSynchronize(_stream));   // (nothing in flight reads the buffers about to go)
   for (int i = 0; i < 2; i++) { if (_dTopScratch[i]) hipFree(_dTopScratch[i]); _dTopScratch[i] = nullptr; }

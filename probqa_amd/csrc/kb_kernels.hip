@@ -603,12 +603,92 @@ __global__ __launch_bounds__(1024) void top_merge_kernel(const TopOut *__restric
     __syncthreads();
     if (threadIdx.x == 0) {
       if (nOut != nullptr) nOut[quiz] = listed;
-      if (flag != nullptr) {
+      if (flag != nullptr) {   // (one flag per quiz: flag[0] where one quiz is listed)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(flag + quiz, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
+}
+// ---- ListTopQuestions: the best next questions of a quiz, by priority ------------------------------------------------------------------
+// The question-side twin of the listing above, over the priorities a sweep has left on the device: descending priority, ascending
+// question among equal priorities.  A question is a candidate if its bit is clear in the question-gap bitmap AND in the quiz's asked
+// bitmap and its priority is > 0 -- the sweeps write 0 for asked questions and gaps, but the bits are tested here all the same, so that
+// a stale word of the vector is never listed; a NaN is no candidate.  Level 0 leaves a list per wave of 1024 questions, the merge
+// levels above do the rest.  Indices are 32-bit and LOCAL (Q < 2^31); the host adds the shard's first question.
+// Level 0 over a priority VECTOR (one quiz: the engine's own; a grid.y = quiz batch: blockIdx.y's, from its slot): top_chunks_kernel's
+// shape -- every wave holds 1024 consecutive questions, 16 per lane, loaded coalesced, and lists its own best by itself.
+// Bytes per quiz: 8 Q of priorities and Q / 4 of the two bitmaps.
+__global__ __launch_bounds__(kTopChunkThreads) void top_questions_chunks_kernel(const QuizSlot *__restrict__ slots, const double *__restrict__ priority,
+                                                                                const uint32_t *__restrict__ asked, const uint32_t *__restrict__ qgap,
+                                                                                int64_t Q, int64_t maxCount, TopOut *lists) {
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int64_t quiz = blockIdx.y, nLists = (int64_t)gridDim.x * (kTopChunkThreads / kWave);
+  const int64_t list = (int64_t)blockIdx.x * (kTopChunkThreads / kWave) + wave;
+  const int64_t qFirst = list * kTopWaveTargets;
+  if (slots != nullptr) {
+    priority = slots[quiz].priority;
+    asked = slots[quiz].asked;
+  }
+  double p[16];
+  int t[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const int64_t qq = qFirst + lane + e * kWave;
+    const bool ok = qq < Q && !bit_test(qgap, qq) && !bit_test(asked, qq);
+    p[e] = ok ? priority[qq] : -1.0;
+    if (!(p[e] > 0.0)) p[e] = -1.0;
+    t[e] = (int)qq;
+  }
+  TopOut *mine = lists + (quiz * nLists + list) * maxCount;
+  const int64_t listed = top_rounds_wave<16>(p, t, maxCount, mine);
+  for (int64_t i = listed + lane; i < maxCount; i += kWave) mine[i] = TopOut{-1, -1.0};
+}
+
+// Level 0 over the quiz-minor priority MATRIX [Q][Bp] of the row-sharing and (quiz, chunk) sweeps.  A wave that walked its quiz's
+// column would touch a 64-byte line per question and use 8 bytes of it -- every line pulled through the caches by eight waves.  Here
+// a workgroup takes 1024 questions x 8 adjacent quiz columns: one 64-byte line per question, requested by this workgroup only, eight
+// lanes along the quiz axis per line and eight lines per wave load; the tile is turned in LDS (64 KB: two workgroups per CU) and wave w
+// then lists column w from LDS exactly as the vector form lists from registers.  The LDS index is swizzled (row ^ 8 * column) so that
+// the eight columns of a row fall into different banks on the way in and a column reads without conflicts on the way out.
+// Bytes per batch of n quizzes: 64 Q ceil(n / 8) of priorities -- grid.y has a column group per eight quizzes, so of a row's Bp columns
+// (the batch rounded up to 64) only the lines that hold a quiz of the batch are read, each once: 16 of 64 columns at 9 quizzes; the
+// last group's columns beyond the batch come with their line and are not listed -- and Q / 8 per quiz and bitmap.
+constexpr int kTopQTileQuizzes = 8, kTopQTileThreads = kTopQTileQuizzes * kWave;
+__global__ __launch_bounds__(kTopQTileThreads) void top_questions_tile_kernel(const double *__restrict__ priorityT, int64_t Bp, const QuizSlot *__restrict__ slots,
+                                                                              int nSlots, const uint32_t *__restrict__ qgap, int64_t Q, int64_t maxCount,
+                                                                              TopOut *lists) {
+  __shared__ double tile[kTopQTileQuizzes * kTopWaveTargets];
+  const int64_t chunk = blockIdx.x, nLists = gridDim.x, qFirst = chunk * kTopWaveTargets;
+  const int col0 = (int)blockIdx.y * kTopQTileQuizzes;
+  {
+    const int c = threadIdx.x % kTopQTileQuizzes, r0 = threadIdx.x / kTopQTileQuizzes;
+    constexpr int kRowsPerPass = kTopQTileThreads / kTopQTileQuizzes;
+#pragma unroll 4
+    for (int r = r0; r < kTopWaveTargets; r += kRowsPerPass) {
+      const int64_t qq = qFirst + r;
+      tile[c * kTopWaveTargets + (r ^ (c << 3))] = qq < Q ? priorityT[qq * Bp + col0 + c] : -1.0;
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int quiz = col0 + wave;
+  if (quiz >= nSlots) return;
+  const uint32_t *asked = slots[quiz].asked;
+  double p[16];
+  int t[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const int r = lane + e * kWave;
+    const int64_t qq = qFirst + r;
+    const bool ok = qq < Q && !bit_test(qgap, qq) && !bit_test(asked, qq);
+    p[e] = ok ? tile[wave * kTopWaveTargets + (r ^ (wave << 3))] : -1.0;
+    if (!(p[e] > 0.0)) p[e] = -1.0;
+    t[e] = (int)qq;
+  }
+  TopOut *mine = lists + ((int64_t)quiz * nLists + chunk) * maxCount;
+  const int64_t listed = top_rounds_wave<16>(p, t, maxCount, mine);
+  for (int64_t i = listed + lane; i < maxCount; i += kWave) mine[i] = TopOut{-1, -1.0};
 }
 }  // namespace
 
@@ -817,15 +897,10 @@ hipError_t LaunchTopTargetsExact(const KbView &kb, const TopBatchPriors &priors,
 
 static int64_t TopBatchLists(int64_t T) { return (T <= 0 ? 1 : (T + kTopChunkTargets - 1) / kTopChunkTargets) * (kTopChunkThreads / kWave); }
 static int64_t TopFanIn(int64_t maxCount) { const int64_t f = kTopMergeCapacity / maxCount; return f < 2 ? 2 : f; }
-// records per quiz each of the two scratch buffers must hold
-int64_t TopBatchScratchRecords(int64_t T, int64_t maxCount) { return TopBatchLists(T) * maxCount; }
-hipError_t LaunchTopTargetsBatch(const KbView &kb, const TopBatchPriors &priors, int64_t nQuizzes, int64_t maxCount, RatedTargetDev *scratchA,
-                                 RatedTargetDev *scratchB, RatedTargetDev *out, int64_t *nOut, uint64_t *flag, uint64_t flagValue,
-                                 hipStream_t stream) {
-  if (nQuizzes <= 0 || nQuizzes > kTopBatchQuizzes || maxCount <= 0 || maxCount > 256 || (flag != nullptr && nQuizzes != 1)) return hipErrorInvalidValue;
-  int64_t nLists = TopBatchLists(kb.T);
-  hipLaunchKernelGGL(top_chunks_kernel, dim3((unsigned)(nLists / (kTopChunkThreads / kWave)), (unsigned)nQuizzes), dim3(kTopChunkThreads), 0, stream, priors,
-                     kb.tgap, kb.T, maxCount, reinterpret_cast<TopOut *>(scratchA));
+// The merge levels over nLists lists of maxCount records per quiz in scratchA: 16384 / maxCount lists per workgroup and level, until one
+// list per quiz is left; that level writes out / nOut (and flag[quiz], where a flag is given).
+static hipError_t LaunchTopMerges(int64_t nLists, int64_t nQuizzes, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB,
+                                  RatedTargetDev *out, int64_t *nOut, uint64_t *flag, uint64_t flagValue, hipStream_t stream) {
   const int64_t fanIn = TopFanIn(maxCount);
   RatedTargetDev *src = scratchA, *dst = scratchB;
   for (;;) {
@@ -840,5 +915,36 @@ hipError_t LaunchTopTargetsBatch(const KbView &kb, const TopBatchPriors &priors,
   }
   return hipGetLastError();
 }
+// records per quiz each of the two scratch buffers must hold
+int64_t TopBatchScratchRecords(int64_t T, int64_t maxCount) { return TopBatchLists(T) * maxCount; }
+hipError_t LaunchTopTargetsBatch(const KbView &kb, const TopBatchPriors &priors, int64_t nQuizzes, int64_t maxCount, RatedTargetDev *scratchA,
+                                 RatedTargetDev *scratchB, RatedTargetDev *out, int64_t *nOut, uint64_t *flag, uint64_t flagValue,
+                                 hipStream_t stream) {
+  if (nQuizzes <= 0 || nQuizzes > kTopBatchQuizzes || maxCount <= 0 || maxCount > 256 || (flag != nullptr && nQuizzes != 1)) return hipErrorInvalidValue;
+  int64_t nLists = TopBatchLists(kb.T);
+  hipLaunchKernelGGL(top_chunks_kernel, dim3((unsigned)(nLists / (kTopChunkThreads / kWave)), (unsigned)nQuizzes), dim3(kTopChunkThreads), 0, stream, priors,
+                     kb.tgap, kb.T, maxCount, reinterpret_cast<TopOut *>(scratchA));
+  return LaunchTopMerges(nLists, nQuizzes, maxCount, scratchA, scratchB, out, nOut, flag, flagValue, stream);
+}
 
+// ListTopQuestions: level 0 in the form the priorities lie in, then the merges.  The scratch buffers hold what LaunchTopTargetsBatch's
+// would for rows of Q elements.
+int64_t TopQuestionsScratchRecords(int64_t Q, int64_t maxCount) { return TopBatchLists(Q) * maxCount; }
+hipError_t LaunchTopQuestions(const TopQuestions &a, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB, RatedTargetDev *out,
+                              int64_t *nOut, uint64_t *flags, uint64_t flagValue, hipStream_t stream) {
+  if (a.nQuizzes <= 0 || a.nQuizzes > kTopBatchQuizzes || maxCount <= 0 || maxCount > 256 || a.Q <= 0 || a.Q > 0x7FFFFFFF || a.qgap == nullptr) return hipErrorInvalidValue;
+  if (a.slots == nullptr ? (a.nQuizzes != 1 || a.priority == nullptr || a.asked == nullptr || a.Bp != 0) : (a.Bp != 0 && a.priority == nullptr)) return hipErrorInvalidValue;
+  int64_t nLists;
+  if (a.Bp == 0) {
+    nLists = TopBatchLists(a.Q);
+    hipLaunchKernelGGL(top_questions_chunks_kernel, dim3((unsigned)(nLists / (kTopChunkThreads / kWave)), (unsigned)a.nQuizzes), dim3(kTopChunkThreads), 0, stream,
+                       a.slots, a.priority, a.asked, a.qgap, a.Q, maxCount, reinterpret_cast<TopOut *>(scratchA));
+  } else {
+    if (a.Bp % kTopQTileQuizzes != 0 || a.nQuizzes > a.Bp) return hipErrorInvalidValue;
+    nLists = (a.Q + kTopWaveTargets - 1) / kTopWaveTargets;
+    hipLaunchKernelGGL(top_questions_tile_kernel, dim3((unsigned)nLists, (unsigned)((a.nQuizzes + kTopQTileQuizzes - 1) / kTopQTileQuizzes)), dim3(kTopQTileThreads), 0,
+                       stream, a.priority, (int64_t)a.Bp, a.slots, a.nQuizzes, a.qgap, a.Q, maxCount, reinterpret_cast<TopOut *>(scratchA));
+  }
+  return LaunchTopMerges(nLists, a.nQuizzes, maxCount, scratchA, scratchB, out, nOut, flags, flagValue, stream);
+}
 }  // namespace pqa

@@ -104,6 +104,22 @@ struct BestPick {   // {0, -1} while nothing was offered that is a candidate
   }
 };
 
+// The best maxCount of several shards' listings (ListTopQuestions) under the listings' own order: descending priority, ascending
+// index among equal priorities.  A record whose priority is not > 0 (a NaN among them) or whose index is negative is no candidate.
+// Every list is in that order already and the shards' indices are distinct; neither is relied upon.
+struct RatedIndex { int64_t index; double priority; };   // == CiRatedQuestion
+inline bool RatedBefore(const RatedIndex &a, const RatedIndex &b) { return a.priority > b.priority || (a.priority == b.priority && a.index < b.index); }
+inline std::vector<RatedIndex> MergeTop(const std::vector<std::pair<const RatedIndex *, int64_t>> &lists, int64_t maxCount) {
+  std::vector<RatedIndex> all;
+  for (const auto &l : lists)
+    for (int64_t i = 0; i < l.second; i++)
+      if (l.first[i].priority > 0 && l.first[i].index >= 0) all.push_back(l.first[i]);
+  const size_t n = (size_t)std::max<int64_t>(0, std::min<int64_t>(maxCount, (int64_t)all.size()));
+  std::partial_sort(all.begin(), all.begin() + n, all.end(), RatedBefore);
+  all.resize(n);
+  return all;
+}
+
 // Where the arrays of a .kb file lie (layout: hip_engine_kb.cpp), in bytes from the file's start, and where the rows of a window of
 // questions [qFirst, qFirst + nLocal) lie within them: a shard seeks to its two blocks instead of reading through the others'.
 //   header 40 | sA [Q][K][T] | mD [Q][T] | vB [T] | trailer

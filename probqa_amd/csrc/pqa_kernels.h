@@ -497,4 +497,23 @@ hipError_t LaunchTopTargetsBatch(const KbView &kb, const TopBatchPriors &priors,
                                  RatedTargetDev *scratchB, RatedTargetDev *out, int64_t *nOut, uint64_t *flag, uint64_t flagValue,
                                  hipStream_t stream);
 
+// ListTopQuestions: the best maxCount (<= 256) questions of nQuizzes (<= kTopBatchQuizzes) quizzes by the priorities a sweep has left on
+// the device -- descending priority, ascending LOCAL question among equal priorities; gaps, asked questions (both bitmaps are tested)
+// and priorities that are not > 0 are never listed.  Where the priorities lie:
+//   one quiz          slots == nullptr, Bp == 0: `priority` is its vector, `asked` its bitmap;
+//   grid.y = quiz     slots (device), Bp == 0: every slot's own priority vector and asked bitmap;
+//   quiz-minor matrix slots (device, for the asked bitmaps), Bp > 0: `priority` is [Q][Bp], quiz i in column i.
+// out[quiz][maxCount], nOut[quiz] and flags[quiz] (optional: flagValue once the quiz's records are visible) are device or host-coherent.
+// The two scratch buffers hold nQuizzes * TopQuestionsScratchRecords(Q, maxCount) records each.
+struct TopQuestions {
+  const QuizSlot *slots;
+  const double *priority;
+  const uint32_t *asked, *qgap;
+  int nQuizzes, Bp;
+  int64_t Q;
+};
+int64_t TopQuestionsScratchRecords(int64_t Q, int64_t maxCount);
+hipError_t LaunchTopQuestions(const TopQuestions &a, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB, RatedTargetDev *out,
+                              int64_t *nOut, uint64_t *flags, uint64_t flagValue, hipStream_t stream);
+
 }  // namespace pqa

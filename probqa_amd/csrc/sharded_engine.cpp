@@ -225,6 +225,8 @@ class ShardedEngine final : public IEngine {
     if (!e.ok()) return e;
     return _sh[0]->ListTopTargetsBatch(n, pQuizzes, maxCount, pDest, pCounts);
   }
+  int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
+  Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
   Error StartQuizBatch(int64_t n, int64_t *pQuizzes) override {
     if (n > 0 && !pQuizzes) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
     for (int64_t i = 0; i < n; i++) {
@@ -1382,6 +1384,74 @@ Error ShardedEngine::EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, dou
     for (int64_t i = 0; i < n; i++)
       std::memcpy(pOut + (size_t)i * (size_t)_Q + (size_t)s->FirstQuestion(), part.data() + (size_t)i * (size_t)s->LocalQuestions(),
                   (size_t)s->LocalQuestions() * sizeof(double));
+  }
+  return Error();
+}
+
+// ---- ListTopQuestions: every shard lists the best maxCount of ITS questions -- all shards' sweeps and listings in flight before the
+// first is waited for -- and the host merges the shards' lists under the listings' own order (kb_plan.h: MergeTop).  The best maxCount
+// of the whole question axis are among the shards' best maxCount each.
+int64_t ShardedEngine::ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) {
+  std::lock_guard<OpLock> lk(_opMu);
+  err = FlushAnswers();   // (the gathered answers first: the sweeps read the posteriors they change)
+  if (err.ok()) err = FailedQuiz(iQuiz);
+  if (!err.ok()) return -1;
+  size_t launched = 0;
+  _shardsInFlightMax = 0;
+  for (; err.ok() && launched < _sh.size(); launched++) {   // (validation fails on shard 0, before anything was launched)
+    err = _sh[launched]->EnqueueTopQuestions(iQuiz, maxCount, pDest != nullptr);
+    if (err.ok()) _shardsInFlightMax++;
+  }
+  if (err.ok()) Touch(iQuiz);
+  std::vector<std::vector<RatedIndex>> part(_sh.size());
+  std::vector<std::pair<const RatedIndex *, int64_t>> lists;
+  for (size_t s = 0; s < launched; s++) {   // (what was launched is waited for, whatever the others reported)
+    part[s].resize((size_t)std::max<int64_t>(0, std::min<int64_t>(maxCount, _sh[s]->LocalQuestions())));
+    Error e;
+    const int64_t c = _sh[s]->CollectTopQuestions(e, reinterpret_cast<CiRatedQuestion *>(part[s].data()));
+    if (!e.ok() && err.ok()) err = e;
+    lists.emplace_back(part[s].data(), std::max<int64_t>(c, 0));
+  }
+  if (!err.ok()) return -1;
+  const std::vector<RatedIndex> best = MergeTop(lists, maxCount);
+  if (!best.empty()) std::memcpy(pDest, best.data(), best.size() * sizeof(RatedIndex));
+  return (int64_t)best.size();
+}
+
+Error ShardedEngine::ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) {
+  Error first = HipEngine::CheckTopQuestionsBatchArgs(n, pQuizzes, maxCount, pDest != nullptr, pCounts != nullptr);
+  if (!first.ok()) return first;
+  std::lock_guard<std::mutex> ctxLock(_bctx[0].mu);   // (the shards' batch context 0: not while a combined sweep uses it)
+  while (_bctx[0].readers.load(std::memory_order_acquire) != 0) _mm_pause();
+  size_t launched = 0;
+  {
+    std::lock_guard<OpLock> lk(_opMu);
+    first = FlushAnswers();
+    for (auto &s : _sh) { if (first.ok()) first = s->ValidateBatch(n, pQuizzes); }   // (every shard, before anything is launched)
+    for (int64_t i = 0; first.ok() && i < n; i++) first = FailedQuiz(pQuizzes[i]);
+    _shardsInFlightMax = 0;
+    for (; first.ok() && launched < _sh.size(); launched++) {
+      first = _sh[launched]->EnqueueTopQuestionsBatch(n, pQuizzes, maxCount);
+      if (first.ok()) _shardsInFlightMax++;
+    }
+    for (int64_t i = 0; first.ok() && i < n; i++) Touch(pQuizzes[i]);
+  }
+  std::vector<std::vector<RatedIndex>> part(_sh.size());
+  std::vector<std::vector<int64_t>> counts(_sh.size(), std::vector<int64_t>((size_t)std::max<int64_t>(n, 0), 0));
+  std::vector<int64_t> stride(_sh.size(), 0);
+  for (size_t s = 0; s < launched; s++) {
+    stride[s] = std::max<int64_t>(0, std::min<int64_t>(maxCount, _sh[s]->LocalQuestions()));
+    part[s].resize((size_t)(n * stride[s]));
+    Error e = _sh[s]->CollectTopQuestionsBatch(n, stride[s], reinterpret_cast<CiRatedQuestion *>(part[s].data()), counts[s].data());
+    if (!e.ok() && first.ok()) first = e;
+  }
+  if (!first.ok()) return first;
+  for (int64_t i = 0; i < n; i++) {
+    std::vector<std::pair<const RatedIndex *, int64_t>> lists;
+    for (size_t s = 0; s < _sh.size(); s++) lists.emplace_back(part[s].data() + i * stride[s], counts[s][(size_t)i]);
+    const std::vector<RatedIndex> best = MergeTop(lists, maxCount);
+    if (!best.empty()) std::memcpy(pDest + i * maxCount, best.data(), best.size() * sizeof(RatedIndex));
+    pCounts[i] = (int64_t)best.size();
   }
   return Error();
 }

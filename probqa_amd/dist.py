@@ -85,6 +85,60 @@ def select_batch(local_winners: torch.Tensor, group: Optional[dist.ProcessGroup]
     return pick_batch(torch.stack(parts))
 
 
+# ---- ListTopQuestions over the shards ---------------------------------------------------------------------------------------
+# On a shard (PqaEngineFactory_CreateHipEngineSharded) PqaEngine_ListTopQuestions lists the shard's own questions with GLOBAL ids.  The
+# best max_count of the whole question axis are among the shards' best max_count each: the ranks all-gather their records -- 16 bytes
+# each, max_count per quiz -- and every rank merges them under the listing's own order.
+
+
+def merge_top_questions(lists, max_count: int) -> List[Tuple[int, float]]:
+    """The best max_count (question, priority) of several listings: descending priority, ascending question among equal priorities.
+    A priority that is not > 0 (a NaN among them) or a negative question is no candidate.  Plain Python, no torch."""
+    cand = [(int(q), float(p)) for lst in lists for q, p in lst if p > 0 and q >= 0]
+    cand.sort(key=lambda r: (-r[1], r[0]))
+    return cand[:max(int(max_count), 0)]
+
+
+def _gather_top(local: List[List[Tuple[int, float]]], max_count: int, group, device: Optional[torch.device]) -> List[List[Tuple[int, float]]]:
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if world == 1 or max_count <= 0:
+        return [merge_top_questions([lst], max_count) for lst in local]
+    # one [quizzes, max_count, 2] tensor of 8-byte words per rank: the question (-1: no record) and the priority's bits
+    words = torch.full((len(local), max_count, 2), -1, dtype=torch.int64)
+    for i, lst in enumerate(local):
+        if lst:
+            words[i, :len(lst), 0] = torch.tensor([q for q, _ in lst], dtype=torch.int64)
+            words[i, :len(lst), 1] = torch.tensor([p for _, p in lst], dtype=torch.float64).view(torch.int64)
+    on_dev = dist.get_backend(group) == "nccl"
+    if on_dev:
+        words = words.to(device or torch.device("cuda", torch.cuda.current_device()))
+    parts = [torch.empty_like(words) for _ in range(world)]
+    dist.all_gather(parts, words, group=group)
+    parts = [p.cpu() for p in parts]
+    merged = []
+    for i in range(len(local)):
+        lists = []
+        for p in parts:
+            qs = p[i, :, 0].tolist()
+            ps = p[i, :, 1].contiguous().view(torch.float64).tolist()
+            lists.append([(q, pr) for q, pr in zip(qs, ps) if q >= 0])
+        merged.append(merge_top_questions(lists, max_count))
+    return merged
+
+
+def list_top_questions(engine, quiz: int, max_count: int, group: Optional[dist.ProcessGroup] = None,
+                       device: Optional[torch.device] = None) -> List[Tuple[int, float]]:
+    """The quiz's best max_count questions over the shards of all ranks: a collective every rank calls alike; every rank returns the
+    same list of (GLOBAL question, priority).  Under an NCCL (RCCL) group the records travel on the device, under gloo through the host."""
+    return _gather_top([engine.list_top_questions(quiz, max_count)], max_count, group, device)[0]
+
+
+def list_top_questions_batch(engine, quizzes, max_count: int, group: Optional[dist.ProcessGroup] = None,
+                             device: Optional[torch.device] = None) -> List[List[Tuple[int, float]]]:
+    """list_top_questions for up to 256 quizzes behind one batched sweep per rank and ONE all-gather."""
+    return _gather_top(engine.list_top_questions_batch(list(quizzes), max_count), max_count, group, device)
+
+
 class ShardedSelector:
     """Global next-question selection over question shards.
 

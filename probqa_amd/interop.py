@@ -44,6 +44,11 @@ class CiRatedTarget(ctypes.Structure):
     _fields_ = [("iTarget", ctypes.c_int64), ("prob", ctypes.c_double)]
 
 
+class CiRatedQuestion(ctypes.Structure):  # include/PqaHipExt.h
+    _pack_ = 8
+    _fields_ = [("iQuestion", ctypes.c_int64), ("priority", ctypes.c_double)]
+
+
 class CiAddQorTParam(ctypes.Structure):
     _pack_ = 8
     _fields_ = [("index", ctypes.c_int64), ("initAmount", ctypes.c_double)]
@@ -158,6 +163,8 @@ HIP_EXPORTS = {
     "PqaEngine_TrainBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64, _pdbl]),
     "PqaEngine_RecordQuizTargetBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
+    "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
     "PqaEngineFactory_LoadHipEngineAs": (_vp, [_vp, _pvp, ctypes.c_char_p, _u8, ctypes.POINTER(CiHipShard), _i64]),
     "PqaHip_SaveKBAs": (_vp, [_vp, ctypes.c_char_p, _u8]),
@@ -826,6 +833,27 @@ class PqaEngine:
         arr = (CiRatedTarget * max(n * max_count, 1))()
         _check(_lib.PqaEngine_ListTopTargetsBatch(self.c_engine, n, qs, max_count, arr, counts))
         return [[RatedTarget(arr[i * max_count + j].iTarget, arr[i * max_count + j].prob) for j in range(counts[i])] for i in range(n)]
+
+    def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
+        """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
+        eval_priorities' values, listed on the device.  GLOBAL ids; changes no quiz state -- follow with set_active_question and
+        record_answer to take one."""
+        held = max(min(max_count, self.copy_dims().n_questions), 1)   # (an engine lists at most the questions there are)
+        arr = (CiRatedQuestion * held)()
+        c_err = ctypes.c_void_p()
+        n = _lib.PqaEngine_ListTopQuestions(self.c_engine, ctypes.byref(c_err), i_quiz, max_count, arr)
+        if c_err.value:
+            _check(c_err.value)
+        return [(arr[i].iQuestion, arr[i].priority) for i in range(n)]
+
+    def list_top_questions_batch(self, quizzes, max_count: int) -> List[List[Tuple[int, float]]]:
+        """list_top_questions of up to 256 distinct quizzes behind one batched sweep (eval_priorities_batch's values)."""
+        n = len(quizzes)
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        counts = (ctypes.c_int64 * max(n, 1))()
+        arr = (CiRatedQuestion * max(n * max_count, 1))()
+        _check(_lib.PqaEngine_ListTopQuestionsBatch(self.c_engine, n, qs, max_count, arr, counts))
+        return [[(arr[i * max_count + j].iQuestion, arr[i * max_count + j].priority) for j in range(counts[i])] for i in range(n)]
 
     def record_answer_remote(self, i_quiz: int, i_answer: int):
         _check(_lib.PqaHip_RecordAnswerRemote(self.c_engine, i_quiz, i_answer))
