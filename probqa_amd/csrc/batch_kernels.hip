@@ -84,10 +84,7 @@ template <> struct Num<double> {
 };
 template <> struct Num<float> {
   static constexpr bool kTable = false;
-  static __device__ __forceinline__ float log2p(float p, const double *) {
-    // v_log_f32: log2, 1 ulp; 0 -> -inf, clamped to the Float analogue of Log2Hot's range (see the file comment)
-    return __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(p), -127.0f, -4.2992253e-08f);
-  }
+  static __device__ __forceinline__ float log2p(float p, const double *) { return log2p_f32(p); }   // (clamped: see the file comment)
   static __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }   // 1 ulp
   static __device__ __forceinline__ float inv(float x) { return 1.0f / x; }
 };
@@ -702,10 +699,6 @@ __global__ __launch_bounds__(64) void batch_pick_kernel(const BatchRecord *__res
 // work went into is the batched one above (BASELINE configs[4]).
 constexpr int kF32LdsTargets = 16384;
 __device__ __forceinline__ float wave_sum_f(float v) { return wave_sum_f32(v); }
-__device__ __forceinline__ float rcp_f32_nr(float x) {
-  const float r = __builtin_amdgcn_rcpf(x);
-  return fmaf(r, fmaf(-x, r, 1.0f), r);
-}
 // NT threads per workgroup: 256 for short rows (several workgroups per CU), 1024 for long ones (the row's two LDS vectors allow one
 // workgroup per CU: sixteen waves instead of four keep its SIMDs busy).
 template <bool LDSROW, int NT>
@@ -728,8 +721,8 @@ __global__ __launch_bounds__(NT) void eval_questions_f32_stream(const float *__r
   auto invd4 = [&](const float4 *rowD, int64_t i) __attribute__((always_inline)) {   // masked 1/D (:74)
     const uint32_t g = tgap[i >> 3] >> ((4 * i) & 31);
     const float4 d = rowD[i];
-    return make_float4((g & 1) ? 0.f : rcp_f32_nr(d.x), (g & 2) ? 0.f : rcp_f32_nr(d.y), (g & 4) ? 0.f : rcp_f32_nr(d.z),
-                       (g & 8) ? 0.f : rcp_f32_nr(d.w));
+    return make_float4((g & 1) ? 0.f : rcp_nr_f32(d.x), (g & 2) ? 0.f : rcp_nr_f32(d.y), (g & 4) ? 0.f : rcp_nr_f32(d.z),
+                       (g & 8) ? 0.f : rcp_nr_f32(d.w));
   };
   if constexpr (LDSROW)
     for (int64_t i = tid; i < nQuads; i += NT) prL[i] = prior4(i);
@@ -814,20 +807,13 @@ hipError_t launch_batch(const BatchArgs &args0, int nThreads, size_t *accBytesNe
   const int G = nThreads / args.Bq;   // question groups side by side (eval_batch_kernel)
   const size_t tileBytes = (size_t)args.TC * G * QB * (KG + 1) * sizeof(R);
   const size_t shmem = (Num<R>::kTable ? kLog2TableDoubles * sizeof(double) : 0) + tileBytes;
-  if (shmem > 160 * 1024) return hipErrorInvalidValue;
+  if (shmem > kLdsPerCU) return hipErrorInvalidValue;
   static LaunchCache cache;   // (per instantiation and device; the occupancy also depends on the thread count: part of the key)
-  const int devSlot = LaunchCache::Device();
-  const size_t key = shmem * 2048 + (size_t)nThreads;
+  const int dev = DeviceSlot();
   int perCU = 0;
-  if (!cache.Get(devSlot, key, &perCU)) {
-    if (shmem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      if (e != hipSuccess) return e;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, nThreads, shmem) != hipSuccess || perCU < 1) perCU = 1;
-    cache.Put(devSlot, key, perCU);
-  }
-  const int nCU = cache.NumCUs(devSlot);
+  const hipError_t e = cache.Residency(dev, kern, nThreads, shmem, shmem * 2048 + (size_t)nThreads, &perCU);
+  if (e != hipSuccess) return e;
+  const int nCU = DeviceCUs(dev);
   const int64_t nBlocks = (args.qEnd - args.qBegin + G * QB - 1) / (G * QB);
   int64_t grid = (int64_t)nCU * perCU;
   if (grid > kBatchMaxGrid) grid = kBatchMaxGrid;
@@ -840,29 +826,14 @@ hipError_t launch_batch(const BatchArgs &args0, int nThreads, size_t *accBytesNe
   return hipGetLastError();
 }
 
-// The pole scratch of a batched sweep (BatchPlan::pole): marks of the quizzes the fix changed [256] | list header | entries [Q x Bp]
-// | the listed pairs' sums [Q x Bp][2 K + 2].  The caller clears the first kBatchPoleClear bytes once; every launch leaves them cleared.
-static_assert(kBatchPoleClear == 256 * sizeof(uint32_t) + sizeof(PoleHeader), "marks and list header");
-size_t batch_pole_bytes(const KbView &kb, int Bp) {
-  const size_t cap = (size_t)kb.Q * (size_t)Bp;
-  return kBatchPoleClear + cap * sizeof(PoleEntry) + cap * (size_t)(2 * kb.K + 2) * sizeof(double);
-}
-struct BatchPole { PoleHeader *list; uint32_t *dirty; double *sums; };
-BatchPole batch_pole(const KbView &kb, int Bp, void *pole) {
-  char *p = static_cast<char *>(pole);
-  const size_t cap = (size_t)kb.Q * (size_t)Bp;
-  return BatchPole{reinterpret_cast<PoleHeader *>(p + 256 * sizeof(uint32_t)), reinterpret_cast<uint32_t *>(p),
-                   reinterpret_cast<double *>(p + kBatchPoleClear + cap * sizeof(PoleEntry))};
-}
 // the fix between a batched sweep and its pick: the listed pairs, corrected in the priority matrix (and in the host's records)
 hipError_t launch_batch_fixup(const KbView &kb, const QuizSlot *slots, int nSlots, int Bp, const BatchPole &bp, double *priorityT,
                               uint64_t hostTag, double vCompTail, hipStream_t stream) {
-  PoleFix f{};
-  f.cube = static_cast<const double *>(kb.cube); f.tgap = kb.tgap; f.qgap = kb.qgap; f.slots = slots;
-  f.list = bp.list; f.dirty = bp.dirty; f.sums = bp.sums; f.sumsStride = 2 * kb.K + 2; f.bySlot = 1;
-  f.wOff = 0; f.vOff = (int)kb.K; f.hOff = (int)(2 * kb.K); f.lOff = (int)(2 * kb.K + 1); f.secondIsWV = 1;
+  PoleFix f = PoleFixWV(static_cast<const double *>(kb.cube), kb.tgap, kb.qgap, kb.K, kb.T, kb.ldT);
+  f.slots = slots;
+  f.list = bp.list; f.dirty = bp.dirty; f.sums = bp.sums; f.bySlot = 1;
   f.priorityT = priorityT; f.Bp = Bp; f.hostTag = hostTag;
-  f.K = kb.K; f.T = kb.T; f.ldT = kb.ldT; f.qFirst = 0; f.nQ = kb.Q; f.capacity = kb.Q * (int64_t)nSlots;
+  f.qFirst = 0; f.nQ = kb.Q; f.capacity = kb.Q * (int64_t)nSlots;
   f.vCompTail = vCompTail;
   return LaunchPoleFixup(f, stream);
 }
@@ -888,8 +859,7 @@ hipError_t LaunchEvalBatch(const KbView &kb, const QuizSlot *slots, int nSlots, 
   // and four beyond -- what rounds 3-5 had for every size was tuned at 256 quizzes of fp32
   const int qb = plan->questionsPerBlock > 0 ? plan->questionsPerBlock : !f32 ? 1 : nSlots <= 32 ? 1 : nSlots <= 128 ? 2 : 4;
   // groups: as many as the lanes allow while every CU still gets a workgroup (a small cube keeps its waves apart instead)
-  static LaunchCache devInfo;
-  const int nCUs = devInfo.NumCUs(LaunchCache::Device());
+  const int nCUs = DeviceCUs();
   int G = 256 % Bq == 0 ? 256 / Bq : 1;
   if (plan->questionGroups > 0) G = std::min(G, 1 << (31 - __builtin_clz((unsigned)plan->questionGroups)));
   else if (f32 && G >= 4) G >>= 1;   // (fp32, same tables: half the groups the lanes allow -- 32 quizzes 110.7 -> 102.7 ms with four instead of eight, 64: 161.4 -> 150.6 with two)
@@ -905,8 +875,7 @@ hipError_t LaunchEvalBatch(const KbView &kb, const QuizSlot *slots, int nSlots, 
   tc = std::max(64, ((tc / G + 63) / 64) * 64);
   if ((int64_t)tc > kb.ldT) tc = (int)kb.ldT;                  // (ldT is a multiple of 32)
   a.TC = tc;
-  const double nT = (double)(kb.nValidTargets + 1);            // PqaCore/CEEvalQsSubtaskConsider.cpp:191
-  a.vCompTail = 0.34657359027997265470861606072909 / (nT * nT);
+  a.vCompTail = VCompTail(kb);
   a.acc = acc; a.recs = recs; a.priorityT = priorityT;
   // the engine's option pole_fix (KbView::poleList), Double engines: the sweep lists the (question, quiz) pairs at the pole of the
   // lack term, pole_kernels.hip redoes them in the priority matrix -- which the caller then provides -- before the pick
@@ -1020,7 +989,7 @@ hipError_t LaunchEvalBatch(const KbView &kb, const QuizSlot *slots, int nSlots, 
 bool EvalMidBatchSupported(const KbView &kb) {
   const int64_t km = kb.K == 5 ? 5 : kMidMaxK;
   return kb.elem == 8 && kb.K >= 2 && kb.K <= kMidMaxK &&
-         (size_t)(kLog2TableDoubles + kb.ldT * (km + 1) + (kMidThreads / kWave) * (km + 2) * 64 + 64) * sizeof(double) <= 160 * 1024;
+         (size_t)(kLog2TableDoubles + kb.ldT * (km + 1) + (kMidThreads / kWave) * (km + 2) * 64 + 64) * sizeof(double) <= kLdsPerCU;
 }
 
 // plan: out grid / Bp / ptBytes / recBytes (queryOnly), as LaunchEvalBatch; PT and recs from the caller.  Every quiz's winner goes to
@@ -1032,13 +1001,12 @@ hipError_t LaunchEvalMidBatch(const KbView &kb, const QuizSlot *slots, int nSlot
   // quiz slots per wave: as few as hold the batch (more chunks per wave: shorter serial sums), 64 beyond 32 quizzes
   const int QS = nSlots <= 8 ? 8 : nSlots <= 16 ? 16 : nSlots <= 32 ? 32 : 64;
   const int groups = (nSlots + QS - 1) / QS;
-  static LaunchCache cache;
-  const int devSlot = LaunchCache::Device();
-  const int nCU = cache.NumCUs(devSlot);
+  const int dev = DeviceSlot();
+  const int nCU = DeviceCUs(dev);
   const int KM = kb.K == 5 ? 5 : kMidMaxK;
   const size_t shmem = (size_t)(kLog2TableDoubles + kb.ldT * (KM + 1) + (kMidThreads / kWave) * (KM + 2) * QS + 64) * sizeof(double);   // (+ the watch words)
-  if (shmem > 160 * 1024) return hipErrorInvalidValue;
-  const int perCU = (int)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / shmem));
+  if (shmem > kLdsPerCU) return hipErrorInvalidValue;
+  const int perCU = (int)std::max<size_t>(1, std::min<size_t>(3, kLdsPerCU / shmem));
   int64_t grid = std::min<int64_t>(kb.Q, std::max<int64_t>(1, (int64_t)nCU * perCU / groups));
   if (grid > kBatchMaxGrid) grid = kBatchMaxGrid;
   if (kb.maxGrid > 0 && grid > kb.maxGrid) grid = kb.maxGrid;
@@ -1057,20 +1025,17 @@ hipError_t LaunchEvalMidBatch(const KbView &kb, const QuizSlot *slots, int nSlot
   void (*kern)(MidArgs) = nullptr;
   if (KM == 5) kern = QS == 8 ? eval_midbatch_kernel<8, 5, true> : QS == 16 ? eval_midbatch_kernel<16, 5, true> : QS == 32 ? eval_midbatch_kernel<32, 5, true> : eval_midbatch_kernel<64, 5, true>;
   else kern = QS == 8 ? eval_midbatch_kernel<8, kMidMaxK, false> : QS == 16 ? eval_midbatch_kernel<16, kMidMaxK, false> : QS == 32 ? eval_midbatch_kernel<32, kMidMaxK, false> : eval_midbatch_kernel<64, kMidMaxK, false>;
-  int attr = 0;
-  const size_t key = shmem * 1024 + (size_t)QS * 16 + (size_t)KM;
-  if (shmem > 64 * 1024 && !cache.Get(devSlot, key, &attr)) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  if (shmem > kLdsNoOptIn) {
+    static LaunchCache cache;   // (one for the eight instantiations: which of them, and its LDS size, are the key)
+    const hipError_t e = cache.OptIn(dev, kern, shmem, shmem * 1024 + (size_t)QS * 16 + (size_t)KM);
     if (e != hipSuccess) return e;
-    cache.Put(devSlot, key, 1);
   }
   const dim3 pgrid((unsigned)((kb.ldT + 63) / 64), (unsigned)(Bp / 64));
   hipLaunchKernelGGL(batch_prep_kernel<double>, pgrid, dim3(kTileThreads), 0, stream, slots, nSlots, Bp, kb.tgap, kb.ldT, static_cast<double *>(PT));
   MidArgs a{};
   a.cube = static_cast<const double *>(kb.cube); a.PT = static_cast<const double *>(PT); a.tgap = kb.tgap; a.qgap = kb.qgap;
   a.slots = slots; a.nSlots = nSlots; a.Bp = Bp; a.Q = kb.Q; a.ldT = kb.ldT; a.K = kb.K;
-  const double nT = (double)(kb.nValidTargets + 1);            // PqaCore/CEEvalQsSubtaskConsider.cpp:191
-  a.vCompTail = 0.34657359027997265470861606072909 / (nT * nT);
+  a.vCompTail = VCompTail(kb);
   a.recs = recs; a.priorityT = priorityT; a.tag = flagValue;
   a.poleList = bpole.list; a.poleSums = bpole.sums;
   const dim3 g((unsigned)grid, (unsigned)groups);
@@ -1088,22 +1053,18 @@ hipError_t LaunchEvalMidBatch(const KbView &kb, const QuizSlot *slots, int nSlot
 
 hipError_t LaunchEvalQuestionsF32(const KbView &kb, const double *prior, const uint32_t *asked, double *priority, hipStream_t stream) {
   if (kb.elem != 4) return hipErrorInvalidValue;
-  const double nT = (double)(kb.nValidTargets + 1);
-  const double vCompTail = 0.34657359027997265470861606072909 / (nT * nT);
+  const double vCompTail = VCompTail(kb);
   const bool ldsRow = kb.ldT <= kF32LdsTargets, big = kb.ldT >= 4096;
   const size_t shmem = (size_t)(2 * kb.K + 32) * sizeof(double) + (ldsRow ? (size_t)kb.ldT * 8 : 0);
-  static LaunchCache cache;   // (per device)
-  const int devSlot = LaunchCache::Device();
-  int attrSet = 0;
-  if (ldsRow && shmem > 64 * 1024 && !cache.Get(devSlot, 1, &attrSet)) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(eval_questions_f32_stream<true, 1024>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
+  const int dev = DeviceSlot();
+  if (ldsRow && shmem > kLdsNoOptIn) {
+    static LaunchCache cache;   // (per device)
+    const hipError_t e = cache.OptIn(dev, eval_questions_f32_stream<true, 1024>, kLdsPerCU);
     if (e != hipSuccess) return e;
-    cache.Put(devSlot, 1, 1);
   }
-  const int nCU = cache.NumCUs(devSlot);
+  const int nCU = DeviceCUs(dev);
   const int nt = big ? 1024 : 256;
-  int perCU = (int)std::max<size_t>(1, std::min<size_t>((size_t)(2048 / nt), (160 * 1024) / std::max<size_t>(shmem, 1)));
+  int perCU = (int)std::max<size_t>(1, std::min<size_t>((size_t)(2048 / nt), kLdsPerCU / std::max<size_t>(shmem, 1)));
   int64_t grid = std::min<int64_t>(kb.Q, (int64_t)nCU * perCU);
   if (kb.maxGrid > 0 && grid > kb.maxGrid) grid = kb.maxGrid;
   const float *cube = static_cast<const float *>(kb.cube);

@@ -65,11 +65,9 @@ template <> struct NumC<double> {
 };
 template <> struct NumC<float> {
   static constexpr bool kTable = false;
-  static __device__ __forceinline__ float log2p(float p, const double *) {   // (batch_kernels.hip: Num<float>::log2p)
-    return __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(p), -127.0f, -4.2992253e-08f);
-  }
+  static __device__ __forceinline__ float log2p(float p, const double *) { return log2p_f32(p); }
   static __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-  static __device__ __forceinline__ float inv(float x) { const float r = __builtin_amdgcn_rcpf(x); return fmaf(r, fmaf(-x, r, 1.0f), r); }
+  static __device__ __forceinline__ float inv(float x) { return rcp_nr_f32(x); }
 };
 
 // a 16-byte unit of a cube row, with the hint that it will not be read again (the cube streams: pqa_device.h, row_load)
@@ -1239,13 +1237,11 @@ const void *ahead_kernel_of(int variant, int64_t K) {
 
 // does the device hold `perCU` workgroups of the kernel per CU with this much LDS?  (cached per kernel, device and LDS size)
 bool occupancy_reaches(LaunchCache &cache, const void *kern, int threads, size_t shmem, int perCU) {
-  const int dev = LaunchCache::Device();
+  const int dev = DeviceSlot();
   int got = 0;
   if (cache.Get(dev, shmem, &got)) return got >= perCU;
-  hipError_t e = hipSuccess;
-  if (shmem > 64 * 1024) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&got, kern, threads, shmem);
-  if (e != hipSuccess) { got = 0; (void)hipGetLastError(); }   // (not this launch's error: the caller falls back to another form)
+  // a failed opt-in or query is not this launch's error: it is remembered as "no workgroup", and the caller falls back to another form
+  if (LaunchCache::Ask(kern, threads, shmem, &got) != hipSuccess || got < 1) { got = 0; (void)hipGetLastError(); }
   cache.Put(dev, shmem, got);
   return got >= perCU;
 }
@@ -1318,25 +1314,19 @@ int cluster_variant(const KbView &kb, int nCU, ClusterShape *out) {   // -1: not
 template <typename R>
 bool cluster_shape(const KbView &kb, int nCU, ClusterShape *out) { return cluster_variant<R>(kb, nCU, out) >= 0; }
 
-int device_cus() {
-  int dev = 0, nCU = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&nCU, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nCU <= 0) nCU = 256;
-  return nCU;
-}
-
 }  // namespace
 
 // Rows longer than the register shapes take (ldT > 16384), up to 16 answers, two workgroups per CU resident.
 bool EvalClusterSupported(const KbView &kb) {
   if (kb.ldT <= kb.clusterFrom) return false;
   ClusterShape s;
-  return kb.elem == 4 ? cluster_shape<float>(kb, device_cus(), &s) : cluster_shape<double>(kb, device_cus(), &s);
+  return kb.elem == 4 ? cluster_shape<float>(kb, DeviceCUs(), &s) : cluster_shape<double>(kb, DeviceCUs(), &s);
 }
 
 const char *EvalClusterKernelName(const KbView &kb) {
   static thread_local char name[48];
   ClusterShape s{};
-  const bool ok = kb.elem == 4 ? cluster_shape<float>(kb, device_cus(), &s) : cluster_shape<double>(kb, device_cus(), &s);
+  const bool ok = kb.elem == 4 ? cluster_shape<float>(kb, DeviceCUs(), &s) : cluster_shape<double>(kb, DeviceCUs(), &s);
   if (!ok) return "stream";
   char shape[16] = "";
   if (s.ahead && !(s.tpb == 512 && s.nu == 1)) std::snprintf(shape, sizeof(shape), "_%dx%d", s.tpb, s.nu);
@@ -1347,7 +1337,7 @@ const char *EvalClusterKernelName(const KbView &kb) {
 // bytes of exchange scratch the launch needs (records + totals; cleared once by the caller); 0 if the shape is not supported
 size_t EvalClusterScratchBytes(const KbView &kb) {
   ClusterShape s{};
-  const bool ok = kb.elem == 4 ? cluster_shape<float>(kb, device_cus(), &s) : cluster_shape<double>(kb, device_cus(), &s);
+  const bool ok = kb.elem == 4 ? cluster_shape<float>(kb, DeviceCUs(), &s) : cluster_shape<double>(kb, DeviceCUs(), &s);
   if (!ok) return 0;
   const size_t perCluster = (size_t)4 * s.C * (2 * kMaxK + 2) * sizeof(ExRec);   // (four record slots: the form that runs ahead; the other uses two)
   return (size_t)s.nClusters * perCluster + (size_t)kb.Q * (2 * kMaxK + 2) * sizeof(double) + 256 + ((size_t)kb.Q + 2) * sizeof(uint32_t) + (size_t)kb.Q * kMaxK * sizeof(unsigned long long);
@@ -1356,7 +1346,7 @@ size_t EvalClusterScratchBytes(const KbView &kb) {
 hipError_t LaunchEvalCluster(const KbView &kb, const double *prior, const uint32_t *asked, double *priority, void *scratch, hipStream_t stream) {
   ClusterShape s{};
   const bool f32 = kb.elem == 4;
-  const int variant = f32 ? cluster_variant<float>(kb, device_cus(), &s) : cluster_variant<double>(kb, device_cus(), &s);
+  const int variant = f32 ? cluster_variant<float>(kb, DeviceCUs(), &s) : cluster_variant<double>(kb, DeviceCUs(), &s);
   if (variant < 0 || scratch == nullptr) return hipErrorInvalidValue;
   char *p = static_cast<char *>(scratch);
   ClusterArgs a{};
@@ -1401,9 +1391,8 @@ hipError_t LaunchEvalCluster(const KbView &kb, const double *prior, const uint32
     e = LaunchPoleFixup(f, stream);
     if (e != hipSuccess) return e;
   }
-  const double nT = (double)(kb.nValidTargets + 1);             // PqaCore/CEEvalQsSubtaskConsider.cpp:191
   hipLaunchKernelGGL(cluster_epilogue_kernel, dim3((unsigned)((kb.Q + 255) / 256)), dim3(256), 0, stream, a.totals, kb.qgap, asked,
-                     priority, kb.K, kb.Q, 0.34657359027997265470861606072909 / (nT * nT));
+                     priority, kb.K, kb.Q, VCompTail(kb));
   return hipGetLastError();
 }
 

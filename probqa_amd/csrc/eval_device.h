@@ -3,6 +3,7 @@
 // fp64: one lane runs it per (question, quiz), whatever the precision the elements were accumulated in.
 #pragma once
 #include "pqa_device.h"
+#include "pqa_kernels.h"
 
 namespace pqa {
 
@@ -71,7 +72,7 @@ __device__ __forceinline__ double eval_epilogue_strided(const double *mW, double
   const double avgH = div_fast(whSum, totW);                   // :175-177
   const double avgV = div_fast(precise_sum4(vS, vC), totW);
   const double nExpectedTargets = exp2(avgH);                  // :181
-  const double cLnMaxV = 0.34657359027997265470861606072909;   // SRMath::_cLnSqrt2
+  const double cLnMaxV = kLnSqrt2;
   const double lnV = (avgV == 0) ? -746.0 : log_pos(avgV);     // :29
   const double vComp = div_fast(1.0, cLnMaxV - lnV + vCompTail);   // :30-32
   const double lack = -lackSum;                                // :201

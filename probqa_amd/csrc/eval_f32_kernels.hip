@@ -31,34 +31,12 @@ namespace pqa {
 
 namespace {
 
-__device__ __forceinline__ float rcp_nr_f32(float x) {       // 2^-22.5 -> full fp32 precision
-  const float r = __builtin_amdgcn_rcpf(x);
-  return fmaf(r, fmaf(-x, r, 1.0f), r);
-}
-__device__ __forceinline__ float log2p_f32(float p) {        // (batch_kernels.hip: Num<float>::log2p)
-  return __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(p), -127.0f, -4.2992253e-08f);
-}
-
 // The fp64 epilogue (exp2, log, four divisions) as a real call: inlined, its ~90 registers come on top of the rows a thread holds
 // (the 1024-thread shape spilled); called, it saves what it clobbers to the stack -- once per question, one lane of one wave.
 __device__ __attribute__((noinline)) double epilogue_call(const double *rec, double whSum, int64_t K, double lackSum, double vCompTail) {
   return eval_epilogue(rec, whSum, rec + K, K, lackSum, vCompTail);
 }
 
-// LDS-DMA (eval_kernels.hip: dma16): 16 bytes per lane from global memory straight into LDS, no destination registers; M0 = the
-// wave-uniform LDS byte address, lane i lands at M0 + 16 i; counted by vmcnt, invisible to the compiler's bookkeeping.
-typedef unsigned int dma_rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dma_rsrc_t dma_rsrc(const void *row, int64_t bytes) {
-  const uint64_t base = (uint64_t)(uintptr_t)row;
-  return dma_rsrc_t{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)base),
-                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(base >> 32)) & 0xFFFFu,
-                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void dma16(dma_rsrc_t rsrc, unsigned byteOffset, unsigned ldsDst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(byteOffset), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(ldsDst)) : "memory");
-}
 // one word of a bitmap by a SCALAR load (a vector load here would be counted with the DMA loads in flight, and the compiler's wait
 // for it would wait for them all): the word's address is wave-uniform
 __device__ __forceinline__ uint32_t scalar_word(const uint32_t *p) {
@@ -408,17 +386,9 @@ hipError_t launch_dma(const F32Args &args, int nt, int nCU, int64_t maxGrid, hip
   auto kern = eval_questions_f32_dma<NQ, D>;
   const size_t shmem = (size_t)D * nt * NQ * 16;
   static LaunchCache cache;
-  const int dev = LaunchCache::Device();
   int perCU = 0;
-  const size_t key = shmem * 2048 + (size_t)nt;
-  if (!cache.Get(dev, key, &perCU)) {
-    if (shmem > 48 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      if (e != hipSuccess) return e;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, nt, shmem) != hipSuccess || perCU < 1) perCU = 1;
-    cache.Put(dev, key, perCU);
-  }
+  const hipError_t e = cache.Residency(DeviceSlot(), kern, nt, shmem, shmem * 2048 + (size_t)nt, &perCU);
+  if (e != hipSuccess) return e;
   int64_t grid = std::min<int64_t>(args.Q, (int64_t)nCU * perCU);
   if (maxGrid > 0 && grid > maxGrid) grid = maxGrid;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)nt), shmem, stream, args);
@@ -428,8 +398,10 @@ hipError_t launch_dma(const F32Args &args, int nt, int nCU, int64_t maxGrid, hip
 template <int NQ>
 hipError_t launch_reg(const F32Args &args, int nt, int nCU, int64_t maxGrid, hipStream_t stream) {
   auto kern = eval_questions_f32_reg<NQ>;
+  static LaunchCache cache;   // (no dynamic LDS: the thread count is the key)
   int perCU = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, nt, 0) != hipSuccess || perCU < 1) perCU = 1;
+  const hipError_t e = cache.Residency(DeviceSlot(), kern, nt, 0, (size_t)nt, &perCU);
+  if (e != hipSuccess) return e;
   int64_t grid = std::min<int64_t>(args.Q, (int64_t)nCU * perCU);
   if (maxGrid > 0 && grid > maxGrid) grid = maxGrid;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)nt), 0, stream, args);
@@ -475,11 +447,8 @@ hipError_t LaunchEvalQuestionsF32Reg(const KbView &kb, const double *prior, cons
                                      hipStream_t stream) {
   const F32Shape s = f32_shape(kb.ldT, kb.K, variant);
   if (kb.elem != 4 || s.nt == 0) return hipErrorInvalidValue;
-  const double nT = (double)(kb.nValidTargets + 1);             // PqaCore/CEEvalQsSubtaskConsider.cpp:191
-  F32Args a{static_cast<const float *>(kb.cube), prior, kb.tgap, kb.qgap, asked, priority, kb.K, kb.Q, kb.ldT,
-            0.34657359027997265470861606072909 / (nT * nT)};
-  int dev = 0, nCU = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&nCU, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nCU <= 0) nCU = 256;
+  F32Args a{static_cast<const float *>(kb.cube), prior, kb.tgap, kb.qgap, asked, priority, kb.K, kb.Q, kb.ldT, VCompTail(kb)};
+  const int nCU = DeviceCUs();
   // The rows by LDS-DMA where that puts more bytes in flight per CU than the register form's one row per workgroup: measured
   // (tools/f32_single_bench.py, one box, whole selections): 10000 x 5 x 10000 498 us as 640 x 4 in registers, 478 with the rows by
   // DMA, 444 as 512 x 5 by DMA two rows ahead (449 three ahead); NOT for shorter rows, whose register form has two to four
@@ -489,7 +458,7 @@ hipError_t LaunchEvalQuestionsF32Reg(const KbView &kb, const double *prior, cons
   static const int dmaDepth = [] { const char *e = std::getenv("PQA_F32_DEPTH"); return e ? atoi(e) : 2; }();
   if (useDma && s.nq >= 5) {
     const size_t slot = (size_t)s.nt * s.nq * 16;
-    const int d = dmaDepth >= 3 && 3 * slot + 12 * 1024 <= 160 * 1024 ? 3 : 2 * slot + 12 * 1024 <= 160 * 1024 ? 2 : 0;
+    const int d = dmaDepth >= 3 && 3 * slot + 12 * 1024 <= kLdsPerCU ? 3 : 2 * slot + 12 * 1024 <= kLdsPerCU ? 2 : 0;
     if (s.nq == 5 && d == 3) return launch_dma<5, 3>(a, s.nt, nCU, kb.maxGrid, stream);
     if (s.nq == 5 && d == 2) return launch_dma<5, 2>(a, s.nt, nCU, kb.maxGrid, stream);
     if (s.nq == 6 && d == 3) return launch_dma<6, 3>(a, s.nt, nCU, kb.maxGrid, stream);

@@ -251,22 +251,6 @@ constexpr double kNearOneShare = 1.0 - 0x1p-9;   // (of W_k, in the streaming ke
 constexpr double kQuarterShare = 0.2499;         // ... and the wider watch (a strict compare: a wave of padding lanes, all sums 0, does not pass) for rows with a vanishing velocity sum (pole_device.h: kSmallV)
 constexpr int kSusDoubles = 4;                 // LDS: words [0], [1] by question parity (the answer rows that passed the watch, a bit each), [4] the list slot -- an EVEN count of doubles: the LDS priors behind it are read as 16-byte pairs
 
-// LDS-DMA: 16 bytes per lane from global memory straight into LDS, no destination VGPRs (buffer_load_dwordx4 ... offen lds:
-// row base in an SGPR descriptor, the lane's 32-bit byte offset in a VGPR -- no 64-bit address pairs either); completion is
-// counted by vmcnt but invisible to hipcc's own bookkeeping (wait for it explicitly).  M0 = wave-uniform LDS byte address
-// of the destination (16-byte aligned); lane i lands at M0 + 16*i.  Checked beyond 64 KiB by tools/glds_test.hip.
-typedef unsigned int dma_rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dma_rsrc_t dma_rsrc(const void *row, int64_t bytes) {
-  const uint64_t base = (uint64_t)(uintptr_t)row;
-  return dma_rsrc_t{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)base),
-                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(base >> 32)) & 0xFFFFu, (unsigned)bytes, 0x00020000u};
-}
-__device__ __forceinline__ void dma16(dma_rsrc_t rsrc, unsigned byteOffset, unsigned ldsDst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(byteOffset), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(ldsDst)) : "memory");
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Register-resident sweep: WPQ waves per question, NP target pairs per lane.  Requires ldT <= 128*WPQ*NP.
 // PRLDS: keep the masked prior vector in LDS instead of registers (long rows: frees 4*NP VGPRs).
@@ -429,7 +413,7 @@ __device__ __forceinline__ void sweep_body(EvalArgs a, bool copyTable) {
   auto head_of_stream = [&](int64_t qq) __attribute__((always_inline)) {
     if constexpr (kMdLds) {   // mD to its LDS landing row, the first answer row to the ring
       const RowRsrc rowA = row_rsrc(a.cube + qq * qStride, rowBytes);
-      const dma_rsrc_t md = dma_rsrc(a.cube + qq * qStride + K * ldT, rowBytes);
+      const dma_rsrc_t md = dma_rsrc<true>(a.cube + qq * qStride + K * ldT, rowBytes);
 #pragma unroll
       for (int j = 0; j < NP; j++) {
         ring[j] = row_load<kStreamHint>(rowA, poff[j]);
@@ -630,7 +614,7 @@ __device__ __forceinline__ void sweep_body(EvalArgs a, bool copyTable) {
       if (kMdLds && lastRow && moreQuestions) {
         // after the loop, not inside it: hipcc does not count these, and a counted wait for a ring pair with fresh DMA
         // requests behind it would wait for them too
-        const dma_rsrc_t mdNext = dma_rsrc(a.cube + qn * qStride + K * ldT, rowBytes);
+        const dma_rsrc_t mdNext = dma_rsrc<true>(a.cube + qn * qStride + K * ldT, rowBytes);
 #pragma unroll
         for (int j = 0; j < NP; j++) dma16(mdNext, poff[j], mdRowWaveAddr + (unsigned)j * (kThreads * 16u));
       }
@@ -1308,8 +1292,7 @@ hipError_t LaunchBatchRerank(const KbView &kb, const QuizSlot *slots, int nSlots
   if (kb.elem != 4 || nSlots <= 0 || nSlots > 256 || scratch == nullptr || priorityT == nullptr) return hipErrorInvalidValue;
   int64_t *cand = static_cast<int64_t *>(scratch);
   double *candPri = reinterpret_cast<double *>(cand + 256 * kRerank);
-  const double nT = (double)(kb.nValidTargets + 1);            // PqaCore/CEEvalQsSubtaskConsider.cpp:191
-  const double vCompTail = 0.34657359027997265470861606072909 / (nT * nT);
+  const double vCompTail = VCompTail(kb);
   hipLaunchKernelGGL(batch_topk_kernel, dim3((unsigned)nSlots), dim3(256), 0, stream, priorityT, kb.Q, Bp, kb.qgap, slots, cand);
   const size_t shmem = (size_t)(kLog2TableDoubles + 2 * 4 + kb.K + (kb.K + 2) * 4) * sizeof(double);
   hipLaunchKernelGGL(batch_rerank_kernel<float>, dim3(kRerank, (unsigned)nSlots), dim3(256), shmem, stream, static_cast<const float *>(kb.cube),
@@ -1349,16 +1332,37 @@ struct Variant {
   bool prLds;
   const char *name;
 };
-// capacity in targets = 128 * wpq * np
+// The register shapes: (id, waves per question, pairs per lane, priors in LDS, name); capacity in targets = 128 * wpq * np.
+// The list makes both the table below and the cases of launch_variant.
+#define PQA_REG_SHAPES(X)                    \
+  X(1, 1, 8, false, "wave_per_question_np8") \
+  X(2, 4, 2, false, "wg256_np2")             \
+  X(3, 4, 4, false, "wg256_np4")             \
+  X(4, 4, 8, false, "wg256_np8")             \
+  X(5, 8, 8, true, "wg512_np8_prlds")        \
+  X(6, 16, 5, true, "wg1024_np5_prlds")      \
+  X(7, 16, 8, true, "wg1024_np8_prlds")      \
+  X(8, 2, 4, false, "wg128_np4")             \
+  X(9, 8, 5, false, "wg512_np5")             \
+  X(10, 8, 10, true, "wg512_np10_prlds")     \
+  X(11, 16, 5, false, "wg1024_np5")          \
+  X(12, 8, 10, false, "wg512_np10")          \
+  X(13, 4, 3, false, "wg256_np3")            \
+  X(14, 4, 5, false, "wg256_np5")            \
+  X(15, 4, 6, false, "wg256_np6")            \
+  X(16, 8, 6, false, "wg512_np6")            \
+  X(17, 8, 7, false, "wg512_np7")            \
+  X(18, 8, 8, false, "wg512_np8")            \
+  X(19, 8, 9, false, "wg512_np9")            \
+  X(20, 4, 10, true, "wg256_np10_prlds")     \
+  X(21, 4, 10, false, "wg256_np10")          \
+  X(22, 4, 6, true, "wg256_np6_prlds")       \
+  X(23, 4, 8, true, "wg256_np8_prlds")       \
+  X(24, 4, 9, true, "wg256_np9_prlds")
 const Variant kVariants[] = {
-    {1, 1, 8, false, "wave_per_question_np8"}, {2, 4, 2, false, "wg256_np2"},   {3, 4, 4, false, "wg256_np4"},
-    {4, 4, 8, false, "wg256_np8"},             {5, 8, 8, true, "wg512_np8_prlds"}, {6, 16, 5, true, "wg1024_np5_prlds"},
-    {7, 16, 8, true, "wg1024_np8_prlds"},      {8, 2, 4, false, "wg128_np4"},   {9, 8, 5, false, "wg512_np5"},
-    {10, 8, 10, true, "wg512_np10_prlds"},     {11, 16, 5, false, "wg1024_np5"}, {12, 8, 10, false, "wg512_np10"},
-    {13, 4, 3, false, "wg256_np3"},            {14, 4, 5, false, "wg256_np5"},  {15, 4, 6, false, "wg256_np6"},
-    {16, 8, 6, false, "wg512_np6"},            {17, 8, 7, false, "wg512_np7"},  {18, 8, 8, false, "wg512_np8"},
-    {19, 8, 9, false, "wg512_np9"},            {20, 4, 10, true, "wg256_np10_prlds"}, {21, 4, 10, false, "wg256_np10"},
-    {22, 4, 6, true, "wg256_np6_prlds"},       {23, 4, 8, true, "wg256_np8_prlds"}, {24, 4, 9, true, "wg256_np9_prlds"},
+#define PQA_SHAPE_ROW(id, wpq, np, prLds, name) {id, wpq, np, prLds, name},
+    PQA_REG_SHAPES(PQA_SHAPE_ROW)
+#undef PQA_SHAPE_ROW
     {99, 4, 0, false, "stream256"},
 };
 
@@ -1385,8 +1389,6 @@ int pick_variant(int64_t ldT, int variant) {
   return 99;
 }
 
-
-constexpr size_t kLdsPerCU = 160 * 1024;   // gfx950
 template <int WPQ, int NP, bool PRLDS>
 constexpr size_t eval_base_lds_bytes(int64_t K, int64_t ldT) {
   return PRLDS ? eval_lds_doubles(WPQ, K, true, ldT) * sizeof(double)
@@ -1405,12 +1407,11 @@ static bool eval_gates(const EvalArgs &args) {
          args.fs.hostPriority == nullptr && !args.poleNoFollow && args.ldT > 1024;
 }
 hipError_t launch_pole_fixup(const EvalArgs &args, hipStream_t stream, int nBatch = 1) {
-  PoleFix f{};
-  f.cube = args.cube; f.tgap = args.tgap; f.qgap = args.qgap; f.asked = args.asked; f.prior = args.prior;
-  f.list = args.poleList; f.sums = args.poleScratch; f.sumsStride = 2 * args.K + 2;
-  f.wOff = 0; f.vOff = (int)args.K; f.hOff = (int)(2 * args.K); f.lOff = (int)(2 * args.K + 1); f.secondIsWV = 1;
+  PoleFix f = PoleFixWV(args.cube, args.tgap, args.qgap, args.K, args.T, args.ldT);
+  f.asked = args.asked; f.prior = args.prior;
+  f.list = args.poleList; f.sums = args.poleScratch;
   f.priority = args.priority;
-  f.K = args.K; f.T = args.T; f.ldT = args.ldT; f.qFirst = args.qFirst; f.nQ = args.qLimit - args.qFirst;
+  f.qFirst = args.qFirst; f.nQ = args.qLimit - args.qFirst;
   f.capacity = f.nQ;
   f.vCompTail = args.vCompTail;
   f.fs = args.fs;
@@ -1443,24 +1444,15 @@ hipError_t launch_reg_form(const EvalArgs &args, int64_t nQ, int nBatch, hipStre
   }();
   // attribute and occupancy are properties of (kernel, LDS size, device): asked once per device, not on every launch
   static LaunchCache cache;
-  const int dev = LaunchCache::Device();
-  int cachedPerCU = 0;
-  if (!cache.Get(dev, shmem, &cachedPerCU)) {
-    if (shmem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      if (e != hipSuccess) return e;
-    }
-    int perCU = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, WPQ * 64, shmem) != hipSuccess || perCU < 1) perCU = 1;
-    // measured at 1000 x 5 x 1000 (wg256_np2): three resident workgroups per CU striding over the questions run the sweep in
-    // 14.9 us, four (every question its own workgroup) in 15.7, two in 17.5 -- do not rely on the register count to say 3
-    if (NP <= 2 && perCU > 3) perCU = 3;
-    cachedPerCU = perCU;
-    cache.Put(dev, shmem, perCU);
-  }
-  const int gNumCUs = cache.NumCUs(dev);
+  const int dev = DeviceSlot();
+  int perCU = 0;
+  const hipError_t e = cache.Residency(dev, kern, WPQ * 64, shmem, &perCU);
+  if (e != hipSuccess) return e;
+  // measured at 1000 x 5 x 1000 (wg256_np2): three resident workgroups per CU striding over the questions run the sweep in
+  // 14.9 us, four (every question its own workgroup) in 15.7, two in 17.5 -- do not rely on the register count to say 3
+  if (NP <= 2 && perCU > 3) perCU = 3;
   // one question per workgroup while they all fit on the chip at once; otherwise a resident grid that strides
-  const int64_t resident = (int64_t)gNumCUs * cachedPerCU;
+  const int64_t resident = (int64_t)DeviceCUs(dev) * perCU;
   int64_t resGrid = nQ < resident ? nQ : resident;
   const int64_t maxRecords = args.slots != nullptr ? args.fs.scratchStride : kFusedMaxGrid;
   if (args.fs.scratch != nullptr && resGrid > maxRecords) resGrid = maxRecords;  // one winner record per workgroup
@@ -1493,30 +1485,9 @@ hipError_t launch_variant(const EvalArgs &args, int64_t ldT, int variant, int nB
     if (x.id == v) { wpq = x.wpq; np = x.np; }
   if (v != 99 && (wpq == 0 || ldT > (int64_t)128 * wpq * np)) return hipErrorInvalidValue;
   switch (v) {
-    case 1: return launch_reg<1, 8, false>(args, nQ, nBatch, stream);
-    case 2: return launch_reg<4, 2, false>(args, nQ, nBatch, stream);
-    case 3: return launch_reg<4, 4, false>(args, nQ, nBatch, stream);
-    case 4: return launch_reg<4, 8, false>(args, nQ, nBatch, stream);
-    case 5: return launch_reg<8, 8, true>(args, nQ, nBatch, stream);
-    case 6: return launch_reg<16, 5, true>(args, nQ, nBatch, stream);
-    case 7: return launch_reg<16, 8, true>(args, nQ, nBatch, stream);
-    case 8: return launch_reg<2, 4, false>(args, nQ, nBatch, stream);
-    case 9: return launch_reg<8, 5, false>(args, nQ, nBatch, stream);
-    case 10: return launch_reg<8, 10, true>(args, nQ, nBatch, stream);
-    case 11: return launch_reg<16, 5, false>(args, nQ, nBatch, stream);
-    case 12: return launch_reg<8, 10, false>(args, nQ, nBatch, stream);
-    case 13: return launch_reg<4, 3, false>(args, nQ, nBatch, stream);
-    case 14: return launch_reg<4, 5, false>(args, nQ, nBatch, stream);
-    case 15: return launch_reg<4, 6, false>(args, nQ, nBatch, stream);
-    case 16: return launch_reg<8, 6, false>(args, nQ, nBatch, stream);
-    case 17: return launch_reg<8, 7, false>(args, nQ, nBatch, stream);
-    case 18: return launch_reg<8, 8, false>(args, nQ, nBatch, stream);
-    case 19: return launch_reg<8, 9, false>(args, nQ, nBatch, stream);
-    case 20: return launch_reg<4, 10, true>(args, nQ, nBatch, stream);
-    case 21: return launch_reg<4, 10, false>(args, nQ, nBatch, stream);
-    case 22: return launch_reg<4, 6, true>(args, nQ, nBatch, stream);
-    case 23: return launch_reg<4, 8, true>(args, nQ, nBatch, stream);
-    case 24: return launch_reg<4, 9, true>(args, nQ, nBatch, stream);
+#define PQA_SHAPE_CASE(id, wpq, np, prLds, name) case id: return launch_reg<wpq, np, prLds>(args, nQ, nBatch, stream);
+    PQA_REG_SHAPES(PQA_SHAPE_CASE)
+#undef PQA_SHAPE_CASE
     case 99: {
       const size_t shmem = eval_lds_doubles(4, args.K, false, 0) * sizeof(double);
       int64_t maxBlocks = 256 * 8;
@@ -1553,8 +1524,7 @@ static EvalArgs make_args(const KbView &kb, int64_t qFirst, int64_t qLimit) {
   args.poleList = kb.poleScratch != nullptr ? kb.poleList : nullptr;
   args.qFirst = qFirst;
   args.qLimit = qLimit;
-  const double nT = (double)(kb.nValidTargets + 1);  // PqaCore/CEEvalQsSubtaskConsider.cpp:191
-  args.vCompTail = 0.34657359027997265470861606072909 / (nT * nT);
+  args.vCompTail = VCompTail(kb);
   args.fs = FusedSelect{nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr};
   args.slots = nullptr;
   args.maxGrid = kb.maxGrid;
@@ -1623,20 +1593,12 @@ hipError_t LaunchEvalQuestionsWithUpdate(const KbView &kb, double *prior, uint32
   auto kern = args.K == 5 ? (pole ? eval_questions_f64_upd<WPQ, NP, true, true, 5> : eval_questions_f64_upd<WPQ, NP, true, false, 5>)
                           : (pole ? eval_questions_f64_upd<WPQ, NP, true, true> : eval_questions_f64_upd<WPQ, NP, true, false>);
   static LaunchCache cache;
-  const int dev = LaunchCache::Device();
-  int cachedPerCU = 0;
-  if (!cache.Get(dev, shmem, &cachedPerCU)) {
-    if (shmem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      if (e != hipSuccess) return e;
-    }
-    int perCU = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, WPQ * 64, shmem) != hipSuccess || perCU < 1) perCU = 1;
-    if (perCU > 3) perCU = 3;   // as launch_reg_form
-    cachedPerCU = perCU;
-    cache.Put(dev, shmem, perCU);
-  }
-  const int64_t resident = (int64_t)cache.NumCUs(dev) * cachedPerCU;
+  const int dev = DeviceSlot();
+  int perCU = 0;
+  const hipError_t e = cache.Residency(dev, kern, WPQ * 64, shmem, &perCU);
+  if (e != hipSuccess) return e;
+  if (perCU > 3) perCU = 3;   // as launch_reg_form
+  const int64_t resident = (int64_t)DeviceCUs(dev) * perCU;
   int64_t grid = kb.Q < resident ? kb.Q : resident;
   if (grid > kFusedMaxGrid) grid = kFusedMaxGrid;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WPQ * 64), shmem, stream, args);
@@ -1647,8 +1609,7 @@ hipError_t LaunchEvalQuestionsWithUpdate(const KbView &kb, double *prior, uint32
 
 size_t EvalBatchPoleBytes(const KbView &kb, int nSlots) {
   if (kb.elem != 8 || kb.poleList == nullptr) return 0;
-  const size_t cap = (size_t)kb.Q * (size_t)nSlots;
-  return kBatchPoleClear + cap * sizeof(PoleEntry) + cap * (size_t)(2 * kb.K + 2) * sizeof(double);
+  return batch_pole_bytes(kb, nSlots);
 }
 
 hipError_t LaunchEvalQuestionsBatch(const KbView &kb, const QuizSlot *slots, int nSlots, int64_t qFirst, int64_t qLimit,
@@ -1663,9 +1624,9 @@ hipError_t LaunchEvalQuestionsBatch(const KbView &kb, const QuizSlot *slots, int
   args.poleScratch = nullptr;
   args.poleList = nullptr;
   if (pole != nullptr && kb.poleList != nullptr && qFirst == 0 && qLimit == kb.Q) {
-    char *p = static_cast<char *>(pole);
-    args.poleList = reinterpret_cast<PoleHeader *>(p + 256 * sizeof(uint32_t));
-    args.poleScratch = reinterpret_cast<double *>(p + kBatchPoleClear + (size_t)kb.Q * (size_t)nSlots * sizeof(PoleEntry));
+    const BatchPole bp = batch_pole(kb, nSlots, pole);
+    args.poleList = bp.list;
+    args.poleScratch = bp.sums;
   }
   finish_args(args);   // (a grid.y = quiz launch: never gated)
   return launch_variant(args, kb.ldT, variant, nSlots, stream);
@@ -1678,22 +1639,13 @@ static hipError_t launch_server_form(const EvalArgs &args, ServerMailbox *mb, vo
   const size_t shmem = stepOffset + 64;
   auto kern = eval_server_f64<WPQ, NP, DEFER, KC>;
   static LaunchCache cache;
-  const int dev = LaunchCache::Device();
-  int cachedPerCU = 0;
-  if (!cache.Get(dev, shmem, &cachedPerCU)) {
-    if (shmem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      if (e != hipSuccess) return e;
-    }
-    int perCU = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, WPQ * 64, shmem) != hipSuccess || perCU < 1) perCU = 1;
-    if (NP <= 2 && perCU > 3) perCU = 3;   // as launch_reg (measured for the resident kernel too: 46.0 k selections/s at three per CU, 43.9 k at four)
-    cachedPerCU = perCU;
-    cache.Put(dev, shmem, perCU);
-  }
-  const int gNumCUs = cache.NumCUs(dev);
+  const int dev = DeviceSlot();
+  int perCU = 0;
+  const hipError_t e = cache.Residency(dev, kern, WPQ * 64, shmem, &perCU);
+  if (e != hipSuccess) return e;
+  if (NP <= 2 && perCU > 3) perCU = 3;   // as launch_reg (measured for the resident kernel too: 46.0 k selections/s at three per CU, 43.9 k at four)
   // every workgroup must be resident at once: the steps are collective
-  const int64_t nQ = args.qLimit - args.qFirst, resident = (int64_t)gNumCUs * cachedPerCU;
+  const int64_t nQ = args.qLimit - args.qFirst, resident = (int64_t)DeviceCUs(dev) * perCU;
   int64_t grid = nQ < resident ? nQ : resident;
   if (grid > kFusedMaxGrid) grid = kFusedMaxGrid;
   if (args.maxGrid > 0 && grid > args.maxGrid) grid = args.maxGrid;

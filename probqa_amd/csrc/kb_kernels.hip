@@ -881,13 +881,10 @@ hipError_t LaunchTopTargetsExact(const KbView &kb, const TopBatchPriors &priors,
   a.counts = reinterpret_cast<int32_t *>(p);
   a.out = reinterpret_cast<TopOut *>(out); a.nOut = nOut; a.flag = flag; a.flagValue = flagValue;
   const size_t shPieces = big ? 16 : (size_t)pieceMax * sizeof(HeapRec);
-  static LaunchCache cache;
-  const int dev = LaunchCache::Device();
-  int dummy = 0;
-  if (shPieces > 64 * 1024 && !cache.Get(dev, 1, &dummy)) {   // (the opt-in to more than 64 KiB of dynamic LDS: once per device, for the largest size)
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(top_pieces_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kTopPieceLds * sizeof(HeapRec)));
+  if (shPieces > kLdsNoOptIn) {   // (the opt-in to more than 64 KiB of dynamic LDS: once per device, for the largest size)
+    static LaunchCache cache;
+    const hipError_t e = cache.OptIn(DeviceSlot(), top_pieces_kernel, kTopPieceLds * sizeof(HeapRec));
     if (e != hipSuccess) return e;
-    cache.Put(dev, 1, 1);
   }
   hipLaunchKernelGGL(top_pieces_kernel, dim3((unsigned)a.nSub, (unsigned)nQuizzes), dim3(kTopPieceThreads), shPieces, stream, a);
   const size_t shHeads = (size_t)a.nSub * (sizeof(HeapRec) + sizeof(int32_t)) + 16;

@@ -60,39 +60,6 @@ constexpr int kFixRowStride = kFixChunk + 4;       // doubles between the rows o
 constexpr int kFixRed = 12;                        // doubles of scratch per row
 constexpr int kFixDepth = PQA_FIX_DEPTH;           // chunks whose operands are in flight (LDS-DMA) ahead of the one worked on
 
-// LDS-DMA (eval_kernels.hip: dma16): 16 (4) bytes per lane from global memory straight into LDS -- the row base in an SGPR descriptor,
-// the lane's byte offset in a VGPR, M0 = the wave-uniform LDS byte address; lane i lands at M0 + 16 i (4 i).  Counted by vmcnt,
-// invisible to the compiler's own bookkeeping: waited for explicitly (wait_vmcnt).  Reads beyond the descriptor's range return 0.
-typedef unsigned int dma_rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dma_rsrc_t dma_rsrc(const void *row, int64_t bytes) {
-  const uint64_t base = (uint64_t)(uintptr_t)row;
-  return dma_rsrc_t{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)base),
-                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(base >> 32)) & 0xFFFFu,
-                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void dma16(dma_rsrc_t rsrc, unsigned byteOffset, unsigned ldsDst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(byteOffset), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(ldsDst)) : "memory");
-}
-__device__ __forceinline__ void dma4(dma_rsrc_t rsrc, unsigned byteOffset, unsigned ldsDst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(byteOffset), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(ldsDst)) : "memory");
-}
-// s_waitcnt vmcnt(n) for a wave-uniform n (the instruction takes an immediate; fewer than asked for is always safe)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-#define PQA_VM(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-  switch (n) {
-    PQA_VM(0) PQA_VM(1) PQA_VM(2) PQA_VM(3) PQA_VM(4) PQA_VM(5) PQA_VM(6) PQA_VM(7) PQA_VM(8) PQA_VM(9) PQA_VM(10) PQA_VM(11) PQA_VM(12)
-    PQA_VM(13) PQA_VM(14) PQA_VM(15) PQA_VM(16) PQA_VM(17) PQA_VM(18) PQA_VM(19) PQA_VM(20) PQA_VM(21) PQA_VM(22) PQA_VM(23) PQA_VM(24)
-    PQA_VM(25) PQA_VM(26) PQA_VM(27) PQA_VM(28) PQA_VM(29) PQA_VM(30) PQA_VM(31) PQA_VM(32) PQA_VM(33) PQA_VM(34) PQA_VM(35) PQA_VM(36)
-    PQA_VM(37) PQA_VM(38) PQA_VM(39) PQA_VM(40) PQA_VM(41) PQA_VM(42) PQA_VM(43) PQA_VM(44) PQA_VM(45) PQA_VM(46) PQA_VM(47) PQA_VM(48)
-    default: asm volatile("s_waitcnt vmcnt(48)" ::: "memory"); break;
-  }
-#undef PQA_VM
-}
-
 // log2hot (pqa_device.h) with the table in global memory: the same operations on the same table entries, so the same bits -- what
 // pass 2 of the sweep took for an element.  (This kernel's LDS is the rows' chunks; one lane per row needs the function.)
 __device__ __forceinline__ double log2hot_global(double x, const double *__restrict__ tbl) {
@@ -163,7 +130,7 @@ __global__ __launch_bounds__(256) void pole_bounds_kernel(PoleFix a) {
       const double avgV = wv / totW;
       if (avgV > 1e-100 && totW > 0.0) {
         const double lnV = log_pos(avgV);
-        const double vComp = 1.0 / (0.34657359027997265470861606072909 - lnV + a.vCompTail);
+        const double vComp = 1.0 / (kLnSqrt2 - lnV + a.vCompTail);
         const int rows = en.rowMask != 0u ? __popc(en.rowMask) : (int)K;
         const double lack = rows * (1.1 * kGateD + 3e-17) / ((double)g - 2.0 * kGateD);
         const double vel = 38.0 * kGateD * vComp / avgV;
@@ -525,20 +492,13 @@ hipError_t LaunchPoleFixup(const PoleFix &fix, hipStream_t stream) {
     const size_t need = ((size_t)select_sampled_lds_doubles(a.nQ, a.fs.sampleSubtasks) + 8) * sizeof(double);
     if (need > shmem) shmem = need;
   }
-  if (shmem > 160 * 1024) return hipErrorInvalidValue;
+  if (shmem > kLdsPerCU) return hipErrorInvalidValue;
   static LaunchCache caches[4];   // (per kernel: the shape is a function of the LDS size, up to selections with very many subtasks)
-  LaunchCache &cache = caches[a.rows == 2 ? 0 : a.rows == 5 ? 1 : a.rows == 8 ? 2 : 3];
-  const int dev = LaunchCache::Device();
+  const int dev = DeviceSlot();
   int perCU = 0;
-  if (!cache.Get(dev, shmem, &perCU)) {
-    if (shmem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      if (e != hipSuccess) return e;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, wgWaves * kWave, shmem) != hipSuccess || perCU < 1) perCU = 1;
-    cache.Put(dev, shmem, perCU);
-  }
-  int64_t grid = (int64_t)cache.NumCUs(dev) * perCU;
+  const hipError_t e = caches[a.rows == 2 ? 0 : a.rows == 5 ? 1 : a.rows == 8 ? 2 : 3].Residency(dev, kern, wgWaves * kWave, shmem, &perCU);
+  if (e != hipSuccess) return e;
+  int64_t grid = (int64_t)DeviceCUs(dev) * perCU;
   const int64_t wgs = (fix.capacity + wgWaves - 1) / wgWaves;   // (a wave per suspect)
   if (fix.capacity > 0 && grid > wgs) grid = wgs;
   if (grid < 1) grid = 1;

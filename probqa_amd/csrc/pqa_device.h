@@ -84,6 +84,55 @@ __device__ __forceinline__ double2 row_load(RowRsrc rs, uint32_t byteOffset) {
   return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, byteOffset, 0, NT ? 2 : 0));
 }
 
+// ---- LDS-DMA -----------------------------------------------------------------------------------------------------------
+// 16 (4) bytes per lane from global memory straight into LDS, no destination VGPRs (buffer_load_dwordx4 / _dword ... offen lds: the
+// row base in an SGPR descriptor, the lane's 32-bit byte offset in a VGPR -- no 64-bit address pairs either).  M0 = the wave-uniform
+// LDS byte address of the destination (16-byte aligned); lane i lands at M0 + 16 i (4 i).  Completion is counted by vmcnt but
+// invisible to hipcc's own bookkeeping: waited for explicitly (wait_vmcnt, or an s_waitcnt written out).  Reads beyond the
+// descriptor's range return 0.  Checked beyond 64 KiB by tools/glds_test.hip.
+// The descriptor's fields are made wave-uniform here (row_rsrc's comment) -- `bytes` too unless the caller's is uniform on its face
+// (PLAIN_BYTES: the register-shape sweeps of eval_kernels.hip, whose register allocation the extra v_readfirstlane changes).
+typedef unsigned int dma_rsrc_t __attribute__((ext_vector_type(4)));
+template <bool PLAIN_BYTES = false>
+__device__ __forceinline__ dma_rsrc_t dma_rsrc(const void *row, int64_t bytes) {
+  const uint64_t base = (uint64_t)(uintptr_t)row;
+  return dma_rsrc_t{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)base),
+                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(base >> 32)) & 0xFFFFu,
+                    PLAIN_BYTES ? (unsigned)bytes : (unsigned)__builtin_amdgcn_readfirstlane((unsigned)bytes), 0x00020000u};
+}
+__device__ __forceinline__ void dma16(dma_rsrc_t rsrc, unsigned byteOffset, unsigned ldsDst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(byteOffset), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(ldsDst)) : "memory");
+}
+__device__ __forceinline__ void dma4(dma_rsrc_t rsrc, unsigned byteOffset, unsigned ldsDst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(byteOffset), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(ldsDst)) : "memory");
+}
+// s_waitcnt vmcnt(n) for a wave-uniform n (the instruction takes an immediate; fewer than asked for is always safe)
+__device__ __forceinline__ void wait_vmcnt(int n) {
+#define PQA_VM(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+  switch (n) {
+    PQA_VM(0) PQA_VM(1) PQA_VM(2) PQA_VM(3) PQA_VM(4) PQA_VM(5) PQA_VM(6) PQA_VM(7) PQA_VM(8) PQA_VM(9) PQA_VM(10) PQA_VM(11) PQA_VM(12)
+    PQA_VM(13) PQA_VM(14) PQA_VM(15) PQA_VM(16) PQA_VM(17) PQA_VM(18) PQA_VM(19) PQA_VM(20) PQA_VM(21) PQA_VM(22) PQA_VM(23) PQA_VM(24)
+    PQA_VM(25) PQA_VM(26) PQA_VM(27) PQA_VM(28) PQA_VM(29) PQA_VM(30) PQA_VM(31) PQA_VM(32) PQA_VM(33) PQA_VM(34) PQA_VM(35) PQA_VM(36)
+    PQA_VM(37) PQA_VM(38) PQA_VM(39) PQA_VM(40) PQA_VM(41) PQA_VM(42) PQA_VM(43) PQA_VM(44) PQA_VM(45) PQA_VM(46) PQA_VM(47) PQA_VM(48)
+    default: asm volatile("s_waitcnt vmcnt(48)" ::: "memory"); break;
+  }
+#undef PQA_VM
+}
+
+// ---- fp32 elements (Float engines' sweeps) -----------------------------------------------------------------------------
+__device__ __forceinline__ float rcp_nr_f32(float x) {       // v_rcp_f32 and one Newton step: 2^-22.5 -> full fp32 precision
+  const float r = __builtin_amdgcn_rcpf(x);
+  return fmaf(r, fmaf(-x, r, 1.0f), r);
+}
+// v_log_f32: log2, 1 ulp; 0 -> -inf, clamped to the Float analogue of Log2Hot's range (batch_kernels.hip's file comment)
+__device__ __forceinline__ float log2p_f32(float p) {
+  return __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(p), -127.0f, -4.2992253e-08f);
+}
+
 // ---- SRVectMath::Log2Hot ---------------------------------------------------------------------------------------------
 // Reference: SRPlatform/Interface/SRVectMath.h:87-135 with the 1024-entry table of SRPlatform/SRVectMath.cpp:30-44 (log2 of
 // the bucket midpoint m, entry 0 scaled by 9.9999999999999927e-01 so that log2(1) < 0).  The table is built on the host

@@ -18,30 +18,70 @@
 
 namespace pqa {
 
+constexpr size_t kLdsPerCU = 160 * 1024;     // LDS of a CU (gfx950)
+constexpr size_t kLdsNoOptIn = 64 * 1024;    // dynamic LDS a launch gets without opting in (hipFuncAttributeMaxDynamicSharedMemorySize)
+constexpr double kLnSqrt2 = 0.34657359027997265470861606072909;   // SRMath::_cLnSqrt2 (host and device)
+
+constexpr int kMaxDevices = 64;
+inline int DeviceSlot() { int d = 0; return hipGetDevice(&d) == hipSuccess ? (d & (kMaxDevices - 1)) : 0; }
+// CUs of the current device, whose slot is `dev` (256 where the runtime does not say); asked once per process and device
+inline int DeviceCUs(int dev) {
+  static std::atomic<int> numCUs[kMaxDevices];
+  int n = numCUs[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    int d = 0;
+    n = (hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
+    numCUs[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+inline int DeviceCUs() { return DeviceCUs(DeviceSlot()); }
+
 // What a launch wrapper has asked the runtime about one kernel instantiation, PER DEVICE: the opt-in to more than 64 KiB of
 // dynamic LDS (hipFuncSetAttribute) belongs to the device that was current when it was made, and one process drives
 // several devices (sharded_engine.cpp).  One function-local static per instantiation; engines on different threads may
 // race for a slot -- they would store the same value.
 struct LaunchCache {
-  static constexpr int kDevices = 64;
-  std::atomic<uint64_t> slot[kDevices];   // (LDS bytes << 16) | (workgroups per CU + 1); 0 = nothing asked yet
-  std::atomic<int> numCUs[kDevices];
-  static int Device() { int d = 0; return hipGetDevice(&d) == hipSuccess ? (d & (kDevices - 1)) : 0; }
-  bool Get(int dev, size_t shmem, int *perCU) const {
+  std::atomic<uint64_t> slot[kMaxDevices];   // (key << 16) | (workgroups per CU + 1); 0 = nothing asked yet
+  bool Get(int dev, size_t key, int *perCU) const {
     const uint64_t v = slot[dev].load(std::memory_order_acquire);
-    if (v == 0 || (v >> 16) != (uint64_t)shmem) return false;
+    if (v == 0 || (v >> 16) != (uint64_t)key) return false;
     *perCU = (int)(v & 0xFFFF) - 1;
     return true;
   }
-  void Put(int dev, size_t shmem, int perCU) { slot[dev].store(((uint64_t)shmem << 16) | (uint64_t)(perCU + 1), std::memory_order_release); }
-  int NumCUs(int dev) {
-    int n = numCUs[dev].load(std::memory_order_relaxed);
-    if (n == 0) {
-      int d = 0;
-      n = (hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
-      numCUs[dev].store(n, std::memory_order_relaxed);
+  void Put(int dev, size_t key, int perCU) { slot[dev].store(((uint64_t)key << 16) | (uint64_t)(perCU + 1), std::memory_order_release); }
+  // Uncached: the opt-in where shmem needs one -- its error is the result -- then the runtime's workgroups per CU (0: it did not say).
+  static hipError_t Ask(const void *kern, int threads, size_t shmem, int *perCU) {
+    *perCU = 0;
+    if (shmem > kLdsNoOptIn) {
+      const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+      if (e != hipSuccess) return e;
     }
-    return n;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, kern, threads, shmem) != hipSuccess) *perCU = 0;
+    return hipSuccess;
+  }
+  // Workgroups of `threads` threads and `shmem` bytes of dynamic LDS that a CU of the current device holds (at least 1).  Attribute
+  // and occupancy are properties of (kernel, LDS size, device): asked once per device and `key` -- the LDS size, or what else the
+  // caller's shape depends on -- not on every launch.  A failed opt-in is returned and not remembered.  dev: DeviceSlot().
+  template <typename Kern>
+  hipError_t Residency(int dev, Kern *kern, int threads, size_t shmem, size_t key, int *perCU) {
+    if (Get(dev, key, perCU)) return hipSuccess;
+    const hipError_t e = Ask(reinterpret_cast<const void *>(kern), threads, shmem, perCU);
+    if (e != hipSuccess) return e;
+    if (*perCU < 1) *perCU = 1;
+    Put(dev, key, *perCU);
+    return hipSuccess;
+  }
+  template <typename Kern>
+  hipError_t Residency(int dev, Kern *kern, int threads, size_t shmem, int *perCU) { return Residency(dev, kern, threads, shmem, shmem, perCU); }
+  // The opt-in alone, once per device (and key), for a kernel whose grid does not depend on the occupancy: up to maxShmem bytes.
+  template <typename Kern>
+  hipError_t OptIn(int dev, Kern *kern, size_t maxShmem, size_t key = 1) {
+    int done = 0;
+    if (Get(dev, key, &done)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxShmem);
+    if (e == hipSuccess) Put(dev, key, 1);
+    return e;
   }
 };
 
@@ -69,6 +109,13 @@ struct KbView {
                           // redoes only the listed questions that can still win (pole_kernels.hip: pole_bounds_kernel) -- the register-shape
                           // sweeps then track, per listed question, how close to 1 its largest posterior element can be
 };
+
+// vCompTail of the epilogue (eval_device.h): ln(sqrt 2) / (nValidTargets + 1)^2, PqaCore/CEEvalQsSubtaskConsider.cpp:191, with the
+// reference's two operations
+inline double VCompTail(const KbView &kb) {
+  const double nT = (double)(kb.nValidTargets + 1);
+  return kLnSqrt2 / (nT * nT);
+}
 
 // ---- questions with a row at the pole of the lack term: listed by the sweeps, redone in the reference's order behind them
 // (pole_kernels.hip).  A list is a header and `capacity` entries; a sweep appends at most one entry per question (and quiz).
@@ -179,6 +226,16 @@ struct PoleFix {
   int gate;
 };
 hipError_t LaunchPoleFixup(const PoleFix &fix, hipStream_t stream);
+// The fix behind a Double engine's sweep that leaves a record as W_k [K] | W_k sqrt(V_k) [K] | sum l log2 p | lack sum: the cube and what
+// describes the record; the caller adds where the records, the list and the priorities lie.
+inline PoleFix PoleFixWV(const double *cube, const uint32_t *tgap, const uint32_t *qgap, int64_t K, int64_t T, int64_t ldT) {
+  PoleFix f{};
+  f.cube = cube; f.tgap = tgap; f.qgap = qgap;
+  f.K = K; f.T = T; f.ldT = ldT;
+  f.sumsStride = 2 * K + 2;
+  f.wOff = 0; f.vOff = (int)K; f.hOff = (int)(2 * K); f.lOff = (int)(2 * K + 1); f.secondIsWV = 1;
+  return f;
+}
 // The same sweep for nSlots quizzes in one launch (grid.y = quiz): `slots` is a DEVICE array; fused->scratch holds
 // nSlots * fused->scratchStride records; fused->out / seq are ignored (each slot has its own).
 // pole (optional): EvalBatchPoleBytes(kb, nSlots) bytes of device memory, the first kBatchPoleClear cleared once after allocation -- the
@@ -202,6 +259,21 @@ struct BatchPlan {
                           //     caller then also provides priorityT (the fix corrects the priority matrix, the pick reads it)
 };
 constexpr size_t kBatchPoleClear = 1024 + 16;
+// The pole scratch of a batched sweep (BatchPlan::pole, LaunchEvalQuestionsBatch's `pole`): marks of the quizzes the fix changed [256] |
+// list header | entries [Q x quizzes] | the listed pairs' sums [Q x quizzes][2 K + 2].  The caller clears the first kBatchPoleClear
+// bytes once; every launch leaves them cleared.
+static_assert(kBatchPoleClear == 256 * sizeof(uint32_t) + sizeof(PoleHeader), "marks and list header");
+inline size_t batch_pole_bytes(const KbView &kb, int quizzes) {
+  const size_t cap = (size_t)kb.Q * (size_t)quizzes;
+  return kBatchPoleClear + cap * sizeof(PoleEntry) + cap * (size_t)(2 * kb.K + 2) * sizeof(double);
+}
+struct BatchPole { PoleHeader *list; uint32_t *dirty; double *sums; };
+inline BatchPole batch_pole(const KbView &kb, int quizzes, void *pole) {
+  char *p = static_cast<char *>(pole);
+  const size_t cap = (size_t)kb.Q * (size_t)quizzes;
+  return BatchPole{reinterpret_cast<PoleHeader *>(p + 256 * sizeof(uint32_t)), reinterpret_cast<uint32_t *>(p),
+                   reinterpret_cast<double *>(p + kBatchPoleClear + cap * sizeof(PoleEntry))};
+}
 // queryOnly: only fill `plan`.  Otherwise: transposed masked priors -> PT, the sweep, and every quiz's winner {priority,
 // local index + outBase} to its slot's `out`, then flagValue to its `seq` (host-coherent).  priorityT (optional):
 // [Q][plan->Bp] priorities, quiz-minor.
@@ -311,7 +383,7 @@ hipError_t LaunchSelectSampled(const double *priority, const uint32_t *qgap, con
 // priorityT[q * Bp + b] (row-sharing and mid-batch sweeps; Bp a multiple of 64), its asked bits slots[b].asked, its random number
 // rnd[b].  Quiz b's {grand total, position + outBase} goes to out[b] and then flagValue to seq[b] (host-coherent, as rnd).
 // grand / run: device scratch of SelectSampledBatchScratch's sizes (a size of 0: not needed).
-constexpr size_t kSampledBatchLdsBytes = 160 * 1024;   // per-quiz vectors are staged in LDS up to this much (gfx950: 160 KiB per CU)
+constexpr size_t kSampledBatchLdsBytes = kLdsPerCU;   // per-quiz vectors are staged in LDS up to this much
 struct SampledBatch {
   const QuizSlot *slots;          // device array
   int nSlots, Bp;

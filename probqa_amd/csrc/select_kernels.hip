@@ -229,13 +229,13 @@ hipError_t LaunchSelectSampled(const double *priority, const uint32_t *qgap, con
                                uint64_t *flag, uint64_t flagValue, hipStream_t stream) {
   if (n <= 0 || nSubtasks <= 0) return hipErrorInvalidValue;
   const size_t staged = (size_t)select_sampled_lds_doubles(n, nSubtasks) * sizeof(double);
-  if (staged <= 64 * 1024) {
+  if (staged <= kLdsNoOptIn) {
     hipLaunchKernelGGL(select_sampled_lds_kernel, dim3(1), dim3(256), staged, stream, priority, qgap, asked, qFirst, n, nSubtasks,
                        rnd, out, flag, flagValue);
     return hipGetLastError();
   }
   const size_t shmem = (size_t)nSubtasks * sizeof(double);
-  if (shmem > 64 * 1024) return hipErrorInvalidValue;
+  if (shmem > kLdsNoOptIn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(select_sampled_kernel, dim3(1), dim3(1024), shmem, stream, priority, qgap, asked, qFirst, n, nSubtasks,
                      rnd, runLength, out, flag, flagValue);
   return hipGetLastError();
@@ -266,20 +266,16 @@ hipError_t LaunchSelectSampledBatch(const SampledBatch &a, hipStream_t stream) {
   }
   const size_t staged = (size_t)select_sampled_lds_doubles(a.n, a.nWorkers) * sizeof(double);
   if (staged <= kSampledBatchLdsBytes) {
-    static LaunchCache cache;   // (per device)
-    const int devSlot = LaunchCache::Device();
-    int attrSet = 0;
-    if (staged > 64 * 1024 && !cache.Get(devSlot, 1, &attrSet)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(select_sampled_batch_vec_kernel<true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSampledBatchLdsBytes);
+    if (staged > kLdsNoOptIn) {
+      static LaunchCache cache;   // (per device)
+      const hipError_t e = cache.OptIn(DeviceSlot(), select_sampled_batch_vec_kernel<true>, kSampledBatchLdsBytes);
       if (e != hipSuccess) return e;
-      cache.Put(devSlot, 1, 1);
     }
     hipLaunchKernelGGL(select_sampled_batch_vec_kernel<true>, dim3((unsigned)a.nSlots), dim3(256), staged, stream, a);
     return hipGetLastError();
   }
   const size_t shmem = (size_t)a.nWorkers * sizeof(double);
-  if (shmem > 64 * 1024 || !a.run) return hipErrorInvalidValue;
+  if (shmem > kLdsNoOptIn || !a.run) return hipErrorInvalidValue;
   hipLaunchKernelGGL(select_sampled_batch_vec_kernel<false>, dim3((unsigned)a.nSlots), dim3(256), shmem, stream, a);
   return hipGetLastError();
 }
