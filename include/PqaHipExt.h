@@ -138,7 +138,8 @@ PQACORE_API void *PqaHip_SaveKBShard(void *pvEngine, const char *filePath, uint8
  * an engine is created; a value that is refused there (a flag wants 0 or 1) is reported on stderr and ignored.
  * Read-only: "server_last_step_ns" (device-side duration of the newest finished step of the resident sweep: request in hand
  * to answer published, from the kernel's own 100 MHz clock; -1 if there is none), "precision" (TPqaPrecisionType of the engine: 1 = Float, 3 = Double), "server_active",
- * "ldT", "device". */
+ * "ldT" and "capQ" (the allocation: elements between two rows of the cube, questions it has room for -- maintenance only ever grows
+ * them), "device". */
 PQACORE_API void *PqaHip_SetOption(void *pvEngine, const char *name, int64_t value);
 PQACORE_API int64_t PqaHip_GetOption(void *pvEngine, const char *name);
 PQACORE_API const char *PqaHip_EvalKernelName(void *pvEngine);

@@ -392,6 +392,7 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "debug_mailbox") return (int64_t)(uintptr_t)_hMailbox;
   if (n == "precision") return _precType;
   if (n == "ldT") return _ldT;
+  if (n == "capQ") return _capQ;   // questions the allocation holds: like ldT it only grows (ReallocKB)
   if (n == "device") return _device;
   if (n == "q_first") return _qFirst;
   if (n == "local_questions") return _Q;

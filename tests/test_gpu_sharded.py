@@ -411,6 +411,77 @@ def test_sharded_maintenance_equals_whole_engine(f32, factory, tmp_path):
     whole.close()
 
 
+@pytest.mark.parametrize("f32", [False, True], ids=["double", "float"])
+def test_sharded_maintenance_across_a_row_granule(f32, factory, tmp_path):
+    """The sibling of the test above for what it leaves out: the rebuilt shards get their rows (adopt_rows_kernel) from shards of ANOTHER
+    row pitch.  30 -> 35 targets crosses a granule upwards (16 fp64 / 32 fp32 elements), a compaction to 14 targets comes back down --
+    the rebuilt shards are created at the pitch of 14 targets while the whole engine keeps its allocation --, and a second addition
+    grows again; every addition has columns without a source (-1 in the column map: the new targets) and questions without a source
+    block (the re-used question gaps).  Both engines, the same calls."""
+    import test_gpu_kb as tk
+
+    K, Q, T = 4, 23, 30
+    with devices("0,0,0"):
+        sh, *_ = tk.make(factory, K, Q, T, seed=19, f32=f32)
+    whole, *_ = tk.make(factory, K, Q, T, seed=19, f32=f32)
+    assert sh.get_option("shards") == 3
+
+    def both(fn):
+        a, b = fn(sh), fn(whole)
+        assert a == b, (a, b)
+        return a
+
+    def same_kb(n_q, n_t):
+        d = sh.copy_dims()
+        assert (d.n_questions, d.n_targets) == (n_q, n_t)
+        for x, y in zip(sh.get_kb(n_q), whole.get_kb()):
+            assert x.shape == y.shape and x.tobytes() == y.tobytes()
+
+    def add(e, q_amounts, t_amounts):
+        aq = [interop.AddQuestionParam(a) for a in q_amounts]
+        at = [interop.AddTargetParam(a) for a in t_amounts]
+        e.add_qs_ts(aq, at)
+        return [p.i_question for p in aq], [p.i_target for p in at]
+
+    for e in (sh, whole):
+        e.start_maintenance(False)
+    pitch = whole.get_option("ldT")
+    both(lambda e: e.remove_questions([4, 17]))
+    both(lambda e: e.remove_targets([11]))
+    # two question gaps re-used and one question appended, one target gap re-used and five targets appended: 35 targets
+    assert both(lambda e: add(e, (0.5, 0.25, 2.0), (0.3, 0.7, 0.9, 1.1, 1.5, 0.1))) == ([17, 4, 23], [11, 30, 31, 32, 33, 34])
+    assert whole.get_option("ldT") > pitch
+    pitch = whole.get_option("ldT")
+    same_kb(24, 35)
+    both(lambda e: e.remove_targets([t for t in range(35) if t % 5 not in (0, 3)]))       # 21 of 35: 14 stay
+    both(lambda e: e.remove_questions([0, 8, 23]))
+    old_q, old_t = both(lambda e: e.compact())
+    assert len(old_q) == 21 and len(old_t) == 14
+    assert whole.get_option("ldT") == pitch                                               # (the whole engine's allocation stays)
+    same_kb(21, 14)
+    both(lambda e: e.question_perm_from_comp(list(range(21))))
+    both(lambda e: e.target_perm_from_comp(list(range(14))))
+    both(lambda e: e.remove_questions([5, 20]))
+    both(lambda e: e.remove_targets([2]))
+    assert both(lambda e: add(e, (1.5, 0.7, 0.3), (0.25, 2.0, 0.5, 1.0))) == ([20, 5, 21], [2, 14, 15, 16])
+    same_kb(22, 17)
+    for e in (sh, whole):
+        e.finish_maintenance()
+    assert sh.get_option("shards") == 3
+    p1, p2 = str(tmp_path / "sh.kb"), str(tmp_path / "whole.kb")
+    sh.save_kb(p1, False)
+    whole.save_kb(p2, False)
+    assert open(p1, "rb").read() == open(p2, "rb").read()
+    qs, qw = sh.start_quiz(), whole.start_quiz()
+    for step in range(4):
+        assert np.array_equal(sh.get_priors(qs), whole.get_priors(qw))
+        assert cases.rel_err(sh.eval_priorities(qs, sh.copy_dims().n_questions), whole.eval_priorities(qw)).max() < 1e-11
+        assert both(lambda e: e.next_question_argmax(qs if e is sh else qw)) >= 0
+        both(lambda e: e.record_answer(qs if e is sh else qw, step % K))
+    sh.close()
+    whole.close()
+
+
 def test_learner_threads_on_a_sharded_engine(factory):
     """Many client threads on ONE sharded engine (reference: every client's NextQuestion under a shared lock,
     PqaCore/CpuEngine.cpp:357-361, the published rate the sum over the learner threads, PqaClient/PqaClient.cpp:238-245): concurrent

@@ -11,6 +11,7 @@ import struct
 import numpy as np
 import pytest
 
+from kb_model import add_model, compact_model   # (the id planning the maintenance model of tests/kb_model.py is built on)
 from probqa_amd import interop
 
 
@@ -237,23 +238,6 @@ def add_plan(Q, T, q_gaps, t_gaps, q_amounts, t_amounts):
                 q_init=[from_bits(w) for w in q_init], t_init=[from_bits(w) for w in t_init])
 
 
-def add_model(Q, T, q_gaps, t_gaps, q_amounts, t_amounts):
-    """GapTracker.Acquire pops the back of the gap list; when it is empty the axis grows by one."""
-    def axis(gaps, size, amounts):
-        gaps, ids = list(gaps), []
-        for _ in amounts:
-            if gaps:
-                ids.append(gaps.pop())
-            else:
-                ids.append(size)
-                size += 1
-        return ids, size
-    q_ids, new_q = axis(q_gaps, Q, q_amounts)
-    t_ids, new_t = axis(t_gaps, T, t_amounts)
-    return dict(n_q_reuse=min(len(q_gaps), len(q_amounts)), n_t_reuse=min(len(t_gaps), len(t_amounts)), new_q=new_q, new_t=new_t,
-                q_ids=q_ids, t_ids=t_ids, q_init=list(q_amounts), t_init=list(t_amounts))
-
-
 def compact_plan(Q, T, q_gaps, t_gaps):
     n_out = 3 + 3 * Q + T
     n, out = probe("compact_plan", [Q, T, *words_of(q_gaps), *words_of(t_gaps)], n_out)
@@ -263,24 +247,6 @@ def compact_plan(Q, T, q_gaps, t_gaps):
     moves, at = take_list(out, at)
     assert at == n
     return old_q, old_t, list(zip(moves[0::2], moves[1::2]))
-
-
-def compact_model(Q, T, q_gaps, t_gaps):
-    """CompactSpec as a caller sees it: the survivors fill 0 .. n-1; a question gap below n takes the LAST question not yet
-    taken, a target gap below n (ascending) takes the survivors from n on (ascending)."""
-    n_q, n_t = Q - len(q_gaps), T - len(t_gaps)
-    tail_q = [q for q in range(Q - 1, n_q - 1, -1) if q not in q_gaps]
-    old_q, moves = [], []
-    for q in range(n_q):
-        if q in q_gaps:
-            old_q.append(tail_q.pop(0))
-            moves.append((q, old_q[-1]))
-        else:
-            old_q.append(q)
-    tail_t = [t for t in range(n_t, T) if t not in t_gaps]
-    old_t = [tail_t.pop(0) if t in t_gaps else t for t in range(n_t)]
-    assert not tail_q and not tail_t
-    return old_q, old_t, moves
 
 
 def test_add_plan_fixed_case():
