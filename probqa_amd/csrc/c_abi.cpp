@@ -1,7 +1,8 @@
 // c_abi.cpp -- the extern "C" surface of libPqaCore.so.
-// Shims follow reference ProbQA/PqaCore/PqaCInterop.cpp:45-408 (AssignPqaError / ReturnPqaError and its three null-handle
-// conventions: return an error object, set *ppError, or log and return 0); declarations are in include/PqaCInterop.h and
-// include/PqaHipExt.h.
+// Every entry that takes an engine is one call of a shim of c_abi_shims.h -- reference ProbQA/PqaCore/PqaCInterop.cpp:45-408
+// (AssignPqaError / ReturnPqaError and its three null-handle conventions: return an error object, set *ppError, or log and return a
+// value) with the exception barrier inside --, every factory entry one call of CreateEngine / LoadEngine (EngineOf); declarations are in include/PqaCInterop.h
+// and include/PqaHipExt.h.
 #include <dlfcn.h>
 #include <sched.h>
 #include <atomic>
@@ -17,12 +18,15 @@
 #include <unordered_map>
 #include <vector>
 
+#include "c_abi_shims.h"
 #include "hip_engine.h"
 
 using pqa::AQ;
 using pqa::ErrCode;
 using pqa::Error;
 using pqa::HipEngine;
+using pqa::IEngine;
+using namespace pqa::abi;
 
 static_assert(sizeof(CiEngineDefinition) == 48, "POD layout must match reference PqaCInterop.h:10-19");
 static_assert(offsetof(CiEngineDefinition, _precType) == 24 && offsetof(CiEngineDefinition, _precExponent) == 26 &&
@@ -37,15 +41,7 @@ namespace {
 struct Factory { int unused; };
 Factory gFactory;  // process-global singleton, never freed (reference PqaCore/PqaEngineFactorySelector.cpp:11-15)
 
-void AssignErr(void **ppError, Error &err) {  // PqaCInterop.cpp:45-54
-  if (!ppError) return;
-  *ppError = err.ok() ? nullptr : new Error(std::move(err));
-}
-void *ReturnErr(Error &&err) {  // PqaCInterop.cpp:56-61
-  if (err.ok()) return nullptr;
-  return new Error(std::move(err));
-}
-Error NullEngine() { return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of IPqaEngine."); }
+void ReleaseEngineSideTables(void *pvEngine);   // (what c_abi.cpp keeps per engine handle: the RCCL exchange buffers)
 Error NotImpl(const char *feature) {
   return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + feature,
                       std::string(feature) + " is not built in the MI355X engine yet.");
@@ -55,22 +51,6 @@ char *DupString(const std::string &s) {
   std::memcpy(p, s.c_str(), s.size() + 1);
   return p;
 }
-
-#define ENGINE_OR_RETURN_ERROR                                   \
-  pqa::IEngine *pEng = static_cast<pqa::IEngine *>(pvEngine);         \
-  if (pEng == nullptr) return new Error(NullEngine());
-#define ENGINE_OR_SET_ERROR(retVal)                        \
-  pqa::IEngine *pEng = static_cast<pqa::IEngine *>(pvEngine);         \
-  if (pEng == nullptr) {                                        \
-    if (ppError) *ppError = new Error(NullEngine());            \
-    return retVal;                                              \
-  }
-#define ENGINE_OR_LOG(retVal)                                               \
-  pqa::IEngine *pEng = static_cast<pqa::IEngine *>(pvEngine);                             \
-  if (pEng == nullptr) {                                                            \
-    std::fprintf(stderr, "PqaCore: Nullptr is passed in place of IPqaEngine.\n");   \
-    return retVal;                                                                  \
-  }
 
 // PQA_DEVICES=i[,j,...]: empty when unset or malformed (a malformed value is reported and ignored)
 std::vector<int> DevicesFromEnvironment() {
@@ -94,44 +74,48 @@ std::vector<int> DevicesFromEnvironment() {
   return devices;
 }
 
-template <typename Fn>
-Error Guarded(Fn &&fn) {
-  try {
-    return fn();
-  } catch (const std::exception &ex) {
-    return Error::MakeP(ErrCode::StdException, std::string("what=[") + ex.what() + "]", "A C++ exception was caught at the C interface.");
-  } catch (...) {
-    return Error::Make(ErrCode::SRException, "An unknown exception was caught at the C interface.");
-  }
-}
-
+// The factory's create entries, one call of EngineOf.
+// PQA_DEVICES=i[,j,...] (unchanged wrappers cannot name a device): one ordinal = that device; several = one shard of
+// the question axis per listed device (an ordinal may repeat: several shards on one device), behind this one engine handle
 void *CreateEngine(void *pvFactory, void **ppError, const CiEngineDefinition *pEngDef, const CiHipShard *pShard) {
-  if (pvFactory == nullptr) {  // PqaCInterop.cpp:93-98
-    if (ppError) *ppError = new Error(Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of IPqaEngineFactory."));
-    return nullptr;
-  }
-  if (pEngDef == nullptr) {
-    if (ppError) *ppError = new Error(Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the engine definition."));
-    return nullptr;
-  }
-  Error err;
-  // PQA_DEVICES=i[,j,...] (unchanged wrappers cannot name a device): one ordinal = that device; several = one shard of
-  // the question axis per listed device (an ordinal may repeat: several shards on one device), behind this one engine handle
-  std::vector<int> devices;
-  if (pShard == nullptr) devices = DevicesFromEnvironment();
-  pqa::IEngine *eng = nullptr;
-  if (devices.size() >= 2) {
-    eng = pqa::CreateShardedEngine(err, *pEngDef, devices);
-  } else {
+  return EngineOf(pvFactory, ppError, [&](Error &err) -> IEngine * {
+    if (pEngDef == nullptr) {
+      err = Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the engine definition.");
+      return nullptr;
+    }
+    std::vector<int> devices;
+    if (pShard == nullptr) devices = DevicesFromEnvironment();
+    if (devices.size() >= 2) return pqa::CreateShardedEngine(err, *pEngDef, devices);
     CiHipShard whole;
     if (devices.size() == 1) {
       whole._qFirst = 0; whole._qTotal = pEngDef->_nQuestions; whole._device = devices[0]; whole._reserved = 0;
       pShard = &whole;
     }
-    eng = HipEngine::Create(err, *pEngDef, pShard);
-  }
-  AssignErr(ppError, err);
-  return eng;
+    return HipEngine::Create(err, *pEngDef, pShard);
+  });
+}
+
+// The factory's load entries likewise: .kb files whole or per shard, in the file's precision (precType 0) or another.
+// PQA_DEVICES as above, here by hipSetDevice; a shard names its own device.
+void *LoadEngine(void *pvFactory, void **ppError, const char *filePath, uint8_t precType, const CiHipShard *pShard, int64_t nLocalQuestions) {
+  return EngineOf(pvFactory, ppError, [&](Error &err) -> IEngine * {
+    if (precType != 0 && precType != 1 && precType != 3) {
+      err = Error::MakeP(ErrCode::NotImplemented, "Feature=precType " + std::to_string((int)precType), "A .kb file is loaded as TPqaPrecisionType::Float or ::Double.");
+      return nullptr;
+    }
+    const std::vector<int> devices = DevicesFromEnvironment();
+    if (pShard != nullptr && !devices.empty()) {
+      err = Error::Make(ErrCode::WrongMode, "A shard names its own device: PqaEngineFactory_LoadHipEngineAs with pShard is not combined with PQA_DEVICES.");
+      return nullptr;
+    }
+    if (devices.size() >= 2) return pqa::LoadShardedEngine(err, filePath, devices, precType);
+    if (devices.size() == 1 && hipSetDevice(devices[0]) != hipSuccess) {
+      (void)hipGetLastError();
+      err = Error::MakeP(ErrCode::IndexOutOfRange, "device=" + std::to_string(devices[0]), "No such HIP device (PQA_DEVICES).");
+      return nullptr;
+    }
+    return HipEngine::LoadAs(err, filePath, precType, pShard, nLocalQuestions);
+  });
 }
 
 }  // namespace
@@ -141,11 +125,23 @@ extern "C" {
 PQACORE_API void CiDebugBreak(void) { /* reference requests a debugger; nothing to do here */ }
 
 // The process-wide default logger (reference SRPlatform/SRDefaultLogger.cpp:47-83): a file logger once Logger_Init has named
-// it, the debug stream (here: stderr) until then.  A second initialisation is an error, reported as an owned C string.
+// it, the debug stream (here: stderr) until then.  A second initialisation is an error, reported as an owned C string -- and so is
+// an exception, by its text.
 PQACORE_API uint8_t Logger_Init(void **ppStrErr, const char *baseName) {
-  const std::string err = pqa::DefaultLogger::Init(baseName);
-  if (ppStrErr) *ppStrErr = err.empty() ? nullptr : DupString(err);
-  return err.empty() ? 1 : 0;
+  char *text = nullptr;
+  bool done = false;
+  Error err = Guarded([&] {
+    const std::string failure = pqa::DefaultLogger::Init(baseName);
+    done = failure.empty();
+    if (!done) text = DupString(failure);
+    return Error();
+  });
+  if (!err.ok()) {
+    done = false;
+    (void)Guarded([&] { text = DupString(err.message + " " + err.params); return Error(); });
+  }
+  if (ppStrErr) *ppStrErr = text; else delete[] text;
+  return done ? 1 : 0;
 }
 
 PQACORE_API void CiReleaseString(void *pvString) { delete[] static_cast<char *>(pvString); }
@@ -163,432 +159,285 @@ PQACORE_API void *PqaEngineFactory_CreateHipEngineSharded(void *pvFactory, void 
   return CreateEngine(pvFactory, ppError, pEngDef, pShard);
 }
 
-PQACORE_API void *PqaEngineFactory_LoadCpuEngine(void *pvFactory, void **ppError, const char *filePath,
-                                                 uint64_t memPoolMaxBytes) {
-  (void)memPoolMaxBytes;  // the device engine has no host memory pool to size
-  if (pvFactory == nullptr) {
-    if (ppError) *ppError = new Error(Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of IPqaEngineFactory."));
-    return nullptr;
-  }
-  Error err;
-  const std::vector<int> devices = DevicesFromEnvironment();
-  if (devices.size() >= 2) {
-    pqa::IEngine *sharded = pqa::LoadShardedEngine(err, filePath, devices);
-    AssignErr(ppError, err);
-    return sharded;
-  }
-  if (devices.size() == 1 && hipSetDevice(devices[0]) != hipSuccess) {
-    (void)hipGetLastError();
-    err = Error::MakeP(ErrCode::IndexOutOfRange, "device=" + std::to_string(devices[0]), "No such HIP device (PQA_DEVICES).");
-    AssignErr(ppError, err);
-    return nullptr;
-  }
-  pqa::IEngine *eng = HipEngine::Load(err, filePath);
-  AssignErr(ppError, err);
-  return eng;
+// (memPoolMaxBytes: the device engine has no host memory pool to size)
+PQACORE_API void *PqaEngineFactory_LoadCpuEngine(void *pvFactory, void **ppError, const char *filePath, uint64_t /* memPoolMaxBytes */) {
+  return LoadEngine(pvFactory, ppError, filePath, 0, nullptr, 0);
 }
-
-PQACORE_API void *PqaEngineFactory_LoadHipEngine(void *pvFactory, void **ppError, const char *filePath, uint64_t memPoolMaxBytes) {
-  return PqaEngineFactory_LoadCpuEngine(pvFactory, ppError, filePath, memPoolMaxBytes);
+PQACORE_API void *PqaEngineFactory_LoadHipEngine(void *pvFactory, void **ppError, const char *filePath, uint64_t /* memPoolMaxBytes */) {
+  return LoadEngine(pvFactory, ppError, filePath, 0, nullptr, 0);
 }
-
-// ---- .kb files per shard and in either precision (PqaHipExt.h).  The reference's two exception codes (PqaCInterop.cpp's catch blocks,
-// PqaErrors.h: SRException, StdException) behind a barrier: nothing thrown below -- an allocation a file's header asks for, say --
-// crosses the C ABI.
+// ---- .kb files per shard and in either precision (PqaHipExt.h)
 PQACORE_API void *PqaEngineFactory_LoadHipEngineAs(void *pvFactory, void **ppError, const char *filePath, uint8_t precType, const CiHipShard *pShard,
                                                    int64_t nLocalQuestions) {
-  if (pvFactory == nullptr) {
-    if (ppError) *ppError = new Error(Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of IPqaEngineFactory."));
-    return nullptr;
-  }
-  pqa::IEngine *eng = nullptr;
-  Error err = Guarded([&]() -> Error {
-    Error e;
-    if (precType != 0 && precType != 1 && precType != 3)
-      return Error::MakeP(ErrCode::NotImplemented, "Feature=precType " + std::to_string((int)precType), "A .kb file is loaded as TPqaPrecisionType::Float or ::Double.");
-    const std::vector<int> devices = DevicesFromEnvironment();
-    if (pShard != nullptr && !devices.empty())
-      return Error::Make(ErrCode::WrongMode, "A shard names its own device: PqaEngineFactory_LoadHipEngineAs with pShard is not combined with PQA_DEVICES.");
-    if (devices.size() >= 2) { eng = pqa::LoadShardedEngine(e, filePath, devices, precType); return e; }
-    if (devices.size() == 1 && hipSetDevice(devices[0]) != hipSuccess) {
-      (void)hipGetLastError();
-      return Error::MakeP(ErrCode::IndexOutOfRange, "device=" + std::to_string(devices[0]), "No such HIP device (PQA_DEVICES).");
-    }
-    eng = HipEngine::LoadAs(e, filePath, precType, pShard, nLocalQuestions);
-    return e;
-  });
-  if (!err.ok()) eng = nullptr;
-  AssignErr(ppError, err);
-  return eng;
+  return LoadEngine(pvFactory, ppError, filePath, precType, pShard, nLocalQuestions);
 }
 PQACORE_API void *PqaHip_SaveKBAs(void *pvEngine, const char *filePath, uint8_t precType) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(Guarded([&] { return pEng->SaveKBAs(filePath, precType); }));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SaveKBAs(filePath, precType); });
 }
 PQACORE_API void *PqaHip_SaveKBShard(void *pvEngine, const char *filePath, uint8_t precType) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(Guarded([&] { return pEng->SaveKBShard(filePath, precType); }));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SaveKBShard(filePath, precType); });
 }
 
 PQACORE_API void CiReleasePqaError(void *pvErr) { delete static_cast<Error *>(pvErr); }
 
 PQACORE_API void *PqaError_ToString(void *pvError, const uint8_t withParams) {
-  Error *pErr = static_cast<Error *>(pvError);
-  if (!pErr) return DupString("[Success] message=[]");
-  return DupString(pErr->ToString(withParams != 0));
+  const Error *pErr = static_cast<Error *>(pvError);
+  return GuardedValue<char *>(nullptr, nullptr, [&](Error &) { return DupString(pErr ? pErr->ToString(withParams != 0) : "[Success] message=[]"); });
 }
 
-static void ReleaseEngineSideTables(void *pvEngine);   // (what c_abi.cpp keeps per engine handle: the RCCL exchange buffers)
 PQACORE_API void CiReleasePqaEngine(void *pvEngine) {
   if (pvEngine) ReleaseEngineSideTables(pvEngine);
-  delete static_cast<pqa::IEngine *>(pvEngine);
+  delete AsEngine(pvEngine);
 }
 
 PQACORE_API void *PqaEngine_Train(void *pvEngine, int64_t nQuestions, const CiAnsweredQuestion *const pAQs,
                                   const int64_t iTarget, const double amount) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->Train(nQuestions, reinterpret_cast<const AQ *>(pAQs), iTarget, amount));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.Train(nQuestions, reinterpret_cast<const AQ *>(pAQs), iTarget, amount); });
 }
 
 PQACORE_API uint8_t PqaEngine_QuestionPermFromComp(void *pvEngine, const int64_t count, int64_t *pIds) {
-  ENGINE_OR_LOG(0);
-  return pEng->MapIds(0, true, count, pIds) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.MapIds(0, true, count, pIds); });
 }
 PQACORE_API uint8_t PqaEngine_QuestionCompFromPerm(void *pvEngine, const int64_t count, int64_t *pIds) {
-  ENGINE_OR_LOG(0);
-  return pEng->MapIds(0, false, count, pIds) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.MapIds(0, false, count, pIds); });
 }
 PQACORE_API uint8_t PqaEngine_TargetPermFromComp(void *pvEngine, const int64_t count, int64_t *pIds) {
-  ENGINE_OR_LOG(0);
-  return pEng->MapIds(1, true, count, pIds) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.MapIds(1, true, count, pIds); });
 }
 PQACORE_API uint8_t PqaEngine_TargetCompFromPerm(void *pvEngine, const int64_t count, int64_t *pIds) {
-  ENGINE_OR_LOG(0);
-  return pEng->MapIds(1, false, count, pIds) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.MapIds(1, false, count, pIds); });
 }
 PQACORE_API uint8_t PqaEngine_QuizPermFromComp(void *pvEngine, const int64_t count, int64_t *pIds) {
-  ENGINE_OR_LOG(0);
-  return pEng->MapIds(2, true, count, pIds) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.MapIds(2, true, count, pIds); });
 }
 PQACORE_API uint8_t PqaEngine_QuizCompFromPerm(void *pvEngine, const int64_t count, int64_t *pIds) {
-  ENGINE_OR_LOG(0);
-  return pEng->MapIds(2, false, count, pIds) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.MapIds(2, false, count, pIds); });
 }
 PQACORE_API uint8_t PqaEngine_EnsurePermQuizGreater(void *pvEngine, const int64_t bound) {
-  ENGINE_OR_LOG(0);
-  return pEng->EnsurePermQuizGreater(bound) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.EnsurePermQuizGreater(bound); });
 }
 PQACORE_API uint8_t PqaEngine_RemapQuizPermId(void *pvEngine, const int64_t srcPermId, const int64_t destPermId) {
-  ENGINE_OR_LOG(0);
-  return pEng->RemapQuizPermId(srcPermId, destPermId) ? 1 : 0;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { return e.RemapQuizPermId(srcPermId, destPermId); });
 }
 
 PQACORE_API uint64_t PqaEngine_GetTotalQuestionsAsked(void *pvEngine, void **ppError) {
-  ENGINE_OR_SET_ERROR(0);
-  Error err;
-  const uint64_t n = pEng->GetTotalQuestionsAsked(err);
-  AssignErr(ppError, err);
-  return n;
+  return ValueOf<uint64_t>(pvEngine, ppError, 0, [&](IEngine &e, Error &err) { return e.GetTotalQuestionsAsked(err); });
 }
 
 PQACORE_API uint8_t PqaEngine_CopyDims(void *pvEngine, CiEngineDimensions *pDims) {
-  ENGINE_OR_LOG(0);
-  pEng->CopyDims(pDims);
-  return 1;
+  return LoggedOf<uint8_t>(pvEngine, 0, [&](IEngine &e) { e.CopyDims(pDims); return 1; });
 }
 
 PQACORE_API int64_t PqaEngine_StartQuiz(void *pvEngine, void **ppError) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t id = pEng->StartQuiz(err);
-  AssignErr(ppError, err);
-  return id;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.StartQuiz(err); });
 }
 
 PQACORE_API int64_t PqaEngine_ResumeQuiz(void *pvEngine, void **ppError, const int64_t nAnswered,
                                          const CiAnsweredQuestion *const pAQs) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t id = pEng->ResumeQuiz(err, nAnswered, reinterpret_cast<const AQ *>(pAQs));
-  AssignErr(ppError, err);
-  return id;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.ResumeQuiz(err, nAnswered, reinterpret_cast<const AQ *>(pAQs)); });
 }
 
 PQACORE_API int64_t PqaEngine_NextQuestion(void *pvEngine, void **ppError, const int64_t iQuiz) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t q = pEng->NextQuestion(err, iQuiz);
-  AssignErr(ppError, err);
-  return q;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.NextQuestion(err, iQuiz); });
 }
 
 PQACORE_API void *PqaEngine_RecordAnswer(void *pvEngine, const int64_t iQuiz, const int64_t iAnswer) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RecordAnswer(iQuiz, iAnswer));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswer(iQuiz, iAnswer); });
 }
 
 PQACORE_API void *PqaEngine_ClearOldQuizzes(void *pvEngine, const int64_t maxCount, const double maxAgeSec) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->ClearOldQuizzes(maxCount, maxAgeSec));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ClearOldQuizzes(maxCount, maxAgeSec); });
 }
 
 PQACORE_API int64_t PqaEngine_GetActiveQuestionId(void *pvEngine, void **ppError, const int64_t iQuiz) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t q = pEng->GetActiveQuestionId(err, iQuiz);
-  AssignErr(ppError, err);
-  return q;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.GetActiveQuestionId(err, iQuiz); });
 }
 
 PQACORE_API void *PqaEngine_SetActiveQuestion(void *pvEngine, const int64_t iQuiz, const int64_t iQuestion) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SetActiveQuestion(iQuiz, iQuestion));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SetActiveQuestion(iQuiz, iQuestion); });
 }
 
 PQACORE_API int64_t PqaEngine_ListTopTargets(void *pvEngine, void **ppError, const int64_t iQuiz,
                                              const int64_t maxCount, CiRatedTarget *pDest) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t n = pEng->ListTopTargets(err, iQuiz, maxCount, pDest);
-  AssignErr(ppError, err);
-  return n;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.ListTopTargets(err, iQuiz, maxCount, pDest); });
 }
 
 PQACORE_API void *PqaEngine_RecordQuizTarget(void *pvEngine, const int64_t iQuiz, const int64_t iTarget,
                                              const double amount) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RecordQuizTarget(iQuiz, iTarget, amount));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordQuizTarget(iQuiz, iTarget, amount); });
 }
 
 PQACORE_API void *PqaEngine_ReleaseQuiz(void *pvEngine, const int64_t iQuiz) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->ReleaseQuiz(iQuiz));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ReleaseQuiz(iQuiz); });
 }
 
 PQACORE_API void *PqaEngine_SaveKB(void *pvEngine, const char *const filePath, const uint8_t bDoubleBuffer) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SaveKB(filePath, bDoubleBuffer != 0));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SaveKB(filePath, bDoubleBuffer != 0); });
 }
 
 PQACORE_API void *PqaEngine_StartMaintenance(void *pvEngine, const bool forceQuizzes) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->StartMaintenance(forceQuizzes));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.StartMaintenance(forceQuizzes); });
 }
 PQACORE_API void *PqaEngine_FinishMaintenance(void *pvEngine) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->FinishMaintenance());
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.FinishMaintenance(); });
 }
 PQACORE_API void *PqaEngine_AddQsTs(void *pvEngine, const int64_t nQuestions, CiAddQorTParam *pAddQuestionParams,
                                     const int64_t nTargets, CiAddQorTParam *pAddTargetParams) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->AddQsTs(nQuestions, pAddQuestionParams, nTargets, pAddTargetParams));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.AddQsTs(nQuestions, pAddQuestionParams, nTargets, pAddTargetParams); });
 }
 PQACORE_API void *PqaEngine_RemoveQuestions(void *pvEngine, const int64_t nQuestions, const int64_t *pQIds) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RemoveQuestions(nQuestions, pQIds));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RemoveQuestions(nQuestions, pQIds); });
 }
 PQACORE_API void *PqaEngine_RemoveTargets(void *pvEngine, const int64_t nTargets, const int64_t *pTIds) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RemoveTargets(nTargets, pTIds));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RemoveTargets(nTargets, pTIds); });
 }
 PQACORE_API void *PqaEngine_Compact(void *pvEngine, int64_t *pnQuestions, int64_t const **const ppOldQuestions,
                                     int64_t *pnTargets, int64_t const **const ppOldTargets) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->Compact(pnQuestions, ppOldQuestions, pnTargets, ppOldTargets));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.Compact(pnQuestions, ppOldQuestions, pnTargets, ppOldTargets); });
 }
 PQACORE_API void CiReleaseCompaction(const int64_t *p) { std::free(const_cast<int64_t *>(p)); }
 
 PQACORE_API void *PqaEngine_Shutdown(void *pvEngine, const char *const saveFilePath) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->Shutdown(saveFilePath));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.Shutdown(saveFilePath); });
 }
 // BaseEngine::SetLogger (reference PqaCore/BaseEngine.cpp:252-258): nullptr selects the default logger -- that case is served.
 // Any other value is a pointer to an SRPlat::ISRLogger, a C++ object of the MSVC ABI (SRPlatform/Interface/ISRLogger.h:11-25,
 // virtual Log(Severity, const SRString&)): none of the C-ABI wrappers can make one (ProbQA.py and the .NET layer only call
 // Logger_Init), and this library cannot call through a foreign vtable.
 PQACORE_API void *PqaEngine_SetLogger(void *pvEngine, void *pSRLogger) {
-  ENGINE_OR_RETURN_ERROR;
-  if (pSRLogger == nullptr) return nullptr;
-  return ReturnErr(NotImpl("SetLogger with a caller-supplied ISRLogger object (MSVC C++ ABI)"));
+  return ErrorOf(pvEngine, [&](IEngine &) { return pSRLogger ? NotImpl("SetLogger with a caller-supplied ISRLogger object (MSVC C++ ABI)") : Error(); });
 }
 
 // ---------------------------------------------------------------------------------------------------- PqaHipExt.h
 PQACORE_API void *PqaHip_SetOption(void *pvEngine, const char *name, int64_t value) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SetOption(name, value));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SetOption(name, value); });
 }
 PQACORE_API int64_t PqaHip_GetOption(void *pvEngine, const char *name) {
-  ENGINE_OR_LOG(-1);
-  return pEng->GetOption(name);
+  return LoggedOf<int64_t>(pvEngine, -1, [&](IEngine &e) { return e.GetOption(name); });
 }
 PQACORE_API const char *PqaHip_EvalKernelName(void *pvEngine) {
-  ENGINE_OR_LOG("");
-  return pEng->EvalKernelName();
+  return LoggedOf<const char *>(pvEngine, "", [&](IEngine &e) { return e.EvalKernelName(); });
 }
 PQACORE_API void *PqaHip_SetKB(void *pvEngine, const double *pA, const double *pD, const double *pB) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SetKB(pA, pD, pB));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SetKB(pA, pD, pB); });
 }
 PQACORE_API void *PqaHip_GetKB(void *pvEngine, double *pA, double *pD, double *pB) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->GetKB(pA, pD, pB));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.GetKB(pA, pD, pB); });
 }
 PQACORE_API void *PqaHip_FillSynthetic(void *pvEngine, double nTrain, double noiseAmp, uint64_t seed) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->FillSynthetic(nTrain, noiseAmp, seed));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.FillSynthetic(nTrain, noiseAmp, seed); });
 }
 PQACORE_API void *PqaHip_SetTargetGaps(void *pvEngine, int64_t n, const int64_t *pTargets) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SetTargetGaps(n, pTargets));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SetTargetGaps(n, pTargets); });
 }
 PQACORE_API void *PqaHip_SetQuestionGaps(void *pvEngine, int64_t n, const int64_t *pQuestions) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SetQuestionGaps(n, pQuestions));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SetQuestionGaps(n, pQuestions); });
 }
 PQACORE_API void *PqaEngine_EvalPriorities(void *pvEngine, const int64_t iQuiz, double *pOut, const int64_t n) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->EvalPriorities(iQuiz, pOut, n));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalPriorities(iQuiz, pOut, n); });
 }
 PQACORE_API int64_t PqaEngine_NextQuestionArgmax(void *pvEngine, void **ppError, const int64_t iQuiz) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t q = pEng->NextQuestionArgmax(err, iQuiz);
-  AssignErr(ppError, err);
-  return q;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.NextQuestionArgmax(err, iQuiz); });
 }
 PQACORE_API int64_t PqaEngine_NextQuestionSampled(void *pvEngine, void **ppError, const int64_t iQuiz,
                                                   const uint64_t rnd) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t q = pEng->NextQuestionSampled(err, iQuiz, rnd);
-  AssignErr(ppError, err);
-  return q;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.NextQuestionSampled(err, iQuiz, rnd); });
 }
 PQACORE_API void *PqaHip_GetPriors(void *pvEngine, const int64_t iQuiz, double *pOut, const int64_t n) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->GetPriors(iQuiz, pOut, n));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.GetPriors(iQuiz, pOut, n); });
 }
 PQACORE_API void *PqaEngine_NextQuestionArgmaxBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes,
                                                     int64_t *pQuestions) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->NextQuestionArgmaxBatch(nQuizzes, pQuizzes, pQuestions));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.NextQuestionArgmaxBatch(nQuizzes, pQuizzes, pQuestions); });
 }
 PQACORE_API void *PqaEngine_NextQuestionSampledBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const uint64_t *pRnd,
                                                      int64_t *pQuestions) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->NextQuestionSampledBatch(nQuizzes, pQuizzes, pRnd, pQuestions));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.NextQuestionSampledBatch(nQuizzes, pQuizzes, pRnd, pQuestions); });
 }
 PQACORE_API void *PqaEngine_NextQuestionBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, int64_t *pQuestions) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->NextQuestionBatch(nQuizzes, pQuizzes, pQuestions));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.NextQuestionBatch(nQuizzes, pQuizzes, pQuestions); });
 }
 PQACORE_API void *PqaEngine_RecordAnswerBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pAnswers) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RecordAnswerBatch(nQuizzes, pQuizzes, pAnswers));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerBatch(nQuizzes, pQuizzes, pAnswers); });
 }
 PQACORE_API void *PqaEngine_StartQuizBatch(void *pvEngine, const int64_t nQuizzes, int64_t *pQuizzes) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->StartQuizBatch(nQuizzes, pQuizzes));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.StartQuizBatch(nQuizzes, pQuizzes); });
 }
 PQACORE_API void *PqaEngine_ResumeQuizBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts, const CiAnsweredQuestion *pAQs,
                                             int64_t *pQuizzes) {
-  ENGINE_OR_RETURN_ERROR;
   static_assert(sizeof(CiAnsweredQuestion) == sizeof(AQ), "the answered questions are passed through as they are");
-  return ReturnErr(pEng->ResumeQuizBatch(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pQuizzes));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ResumeQuizBatch(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pQuizzes); });
 }
 PQACORE_API void *PqaEngine_TrainBatch(void *pvEngine, const int64_t nRecords, const int64_t *pCounts, const CiAnsweredQuestion *pAQs,
                                        const int64_t *pTargets, const double *pAmounts) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->TrainBatch(nRecords, pCounts, reinterpret_cast<const AQ *>(pAQs), pTargets, pAmounts));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.TrainBatch(nRecords, pCounts, reinterpret_cast<const AQ *>(pAQs), pTargets, pAmounts); });
 }
 PQACORE_API void *PqaEngine_RecordQuizTargetBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pTargets,
                                                   const double *pAmounts) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RecordQuizTargetBatch(nQuizzes, pQuizzes, pTargets, pAmounts));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordQuizTargetBatch(nQuizzes, pQuizzes, pTargets, pAmounts); });
 }
 PQACORE_API void *PqaEngine_ListTopTargetsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
                                                 CiRatedTarget *pDest, int64_t *pCounts) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->ListTopTargetsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListTopTargetsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
 }
-// (both behind the exception barrier: the listings size host vectors by the caller's counts)
 PQACORE_API int64_t PqaEngine_ListTopQuestions(void *pvEngine, void **ppError, const int64_t iQuiz, const int64_t maxCount, CiRatedQuestion *pDest) {
-  ENGINE_OR_SET_ERROR(-1);
-  int64_t n = -1;
-  Error err = Guarded([&]() { Error e; n = pEng->ListTopQuestions(e, iQuiz, maxCount, pDest); return e; });
-  if (!err.ok()) n = -1;
-  AssignErr(ppError, err);
-  return n;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.ListTopQuestions(err, iQuiz, maxCount, pDest); });
 }
 PQACORE_API void *PqaEngine_ListTopQuestionsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
                                                   CiRatedQuestion *pDest, int64_t *pCounts) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(Guarded([&]() { return pEng->ListTopQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); }));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListTopQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
 }
 PQACORE_API void *PqaHip_SelectArgmaxBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, CiHipSelection *pOut) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SelectArgmaxBatch(nQuizzes, pQuizzes, pOut));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SelectArgmaxBatch(nQuizzes, pQuizzes, pOut); });
 }
 PQACORE_API void *PqaEngine_EvalPrioritiesBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, double *pOut) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->EvalPrioritiesBatch(nQuizzes, pQuizzes, pOut));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalPrioritiesBatch(nQuizzes, pQuizzes, pOut); });
 }
 PQACORE_API void *PqaHip_Log2Hot(void *pvEngine, const double *pIn, double *pOut, const int64_t n) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->Log2HotArray(pIn, pOut, n));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.Log2HotArray(pIn, pOut, n); });
 }
 PQACORE_API void *PqaHip_GetStream(void *pvEngine) {
-  ENGINE_OR_LOG(nullptr);
-  return pEng->GetStream();
+  return LoggedOf<void *>(pvEngine, nullptr, [&](IEngine &e) { return e.GetStream(); });
 }
 PQACORE_API void *PqaHip_SetStream(void *pvEngine, void *hipStream) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->SetStream(static_cast<hipStream_t>(hipStream)));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SetStream(static_cast<hipStream_t>(hipStream)); });
 }
 PQACORE_API void *PqaHip_Synchronize(void *pvEngine) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->Synchronize());
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.Synchronize(); });
 }
 PQACORE_API void *PqaHip_Quiesce(void *pvEngine) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->Quiesce());
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.Quiesce(); });
 }
 PQACORE_API void *PqaHip_EnqueueSelectArgmaxFlag(void *pvEngine, const int64_t iQuiz, void *pOut, void *pFlag,
                                                  const uint64_t flagValue) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->EnqueueSelectArgmaxFlag(iQuiz, pOut, pFlag, flagValue));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EnqueueSelectArgmaxFlag(iQuiz, pOut, pFlag, flagValue); });
 }
 // ---- ResumeQuiz on shards driven by processes of their own: the owners pack the answered questions' rows, every rank resumes
 // from the exchanged package (hip_engine_resume.cpp)
 PQACORE_API int64_t PqaHip_AnswerRowSlotBytes(void *pvEngine) {
-  ENGINE_OR_LOG(-1);
-  return pEng->AnswerRowSlotBytes();
+  return LoggedOf<int64_t>(pvEngine, -1, [&](IEngine &e) { return e.AnswerRowSlotBytes(); });
 }
 PQACORE_API void *PqaHip_PackAnswerRows(void *pvEngine, const int64_t nAnswered, const CiAnsweredQuestion *pAQs, void *pDst, void *pFlag,
                                         const uint64_t flagValue) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->PackAnswerRows(nAnswered, reinterpret_cast<const AQ *>(pAQs), pDst, pFlag, flagValue));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackAnswerRows(nAnswered, reinterpret_cast<const AQ *>(pAQs), pDst, pFlag, flagValue); });
 }
 PQACORE_API int64_t PqaEngine_ResumeQuizFromRows(void *pvEngine, void **ppError, const int64_t nAnswered, const CiAnsweredQuestion *pAQs,
                                                  const void *pRows) {
-  ENGINE_OR_SET_ERROR(-1);
-  Error err;
-  const int64_t id = pEng->ResumeQuizFromRows(err, nAnswered, reinterpret_cast<const AQ *>(pAQs), pRows);
-  AssignErr(ppError, err);
-  return id;
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.ResumeQuizFromRows(err, nAnswered, reinterpret_cast<const AQ *>(pAQs), pRows); });
 }
 PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts, const CiAnsweredQuestion *pAQs,
                                                     const void *pRows, int64_t *pQuizzes) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->ResumeQuizBatchFromRows(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pRows, pQuizzes));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ResumeQuizBatchFromRows(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pRows, pQuizzes); });
 }
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
-  if (!pHost || !ppDevice || nBytes <= 0) return ReturnErr(Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_HostRegister."));
-  hipError_t he = hipHostRegister(pHost, (size_t)nBytes, hipHostRegisterMapped | hipHostRegisterPortable);
-  if (he == hipSuccess) he = hipHostGetDevicePointer(ppDevice, pHost, 0);
-  if (he != hipSuccess) return ReturnErr(Error::MakeP(ErrCode::StdException, std::string("hip=") + hipGetErrorString(he), "hipHostRegister failed."));
-  return nullptr;
+  return ReturnErr(Guarded([&]() -> Error {
+    if (!pHost || !ppDevice || nBytes <= 0) return Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_HostRegister.");
+    hipError_t he = hipHostRegister(pHost, (size_t)nBytes, hipHostRegisterMapped | hipHostRegisterPortable);
+    if (he == hipSuccess) he = hipHostGetDevicePointer(ppDevice, pHost, 0);
+    if (he != hipSuccess) return Error::MakeP(ErrCode::StdException, std::string("hip=") + hipGetErrorString(he), "hipHostRegister failed.");
+    return Error();
+  }));
 }
 PQACORE_API void *PqaHip_HostUnregister(void *pHost) {
   if (pHost) hipHostUnregister(pHost);
@@ -610,10 +459,10 @@ static void PickOfRecords(const char *base, int64_t world, int64_t strideBytes, 
 // Host-side half of the shared-memory exchange: spin until the flags of all `world` slots equal flagValue, then pick the
 // winner (maximum priority, lowest index on ties, NaN never wins, -1 if no slot has an eligible question).  A slot is
 // strideBytes long and starts with {double priority; int64 index; uint64 flag}.  Returns an error after timeoutSec.
-PQACORE_API void *PqaHip_PickWhenAll(const void *pSlots, const int64_t world, const int64_t strideBytes,
-                                     const uint64_t flagValue, const double timeoutSec, double *pPriority, int64_t *pIndex) {
+static Error PickWhenAll(const void *pSlots, const int64_t world, const int64_t strideBytes, const uint64_t flagValue, const double timeoutSec,
+                         double *pPriority, int64_t *pIndex) {
   if (!pSlots || !pPriority || !pIndex || world <= 0 || strideBytes < 24)
-    return ReturnErr(Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_PickWhenAll."));
+    return Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_PickWhenAll.");
   const char *base = (const char *)pSlots;
   const auto t0 = std::chrono::steady_clock::now();
   for (int64_t r = 0; r < world; r++) {
@@ -628,13 +477,17 @@ PQACORE_API void *PqaHip_PickWhenAll(const void *pSlots, const int64_t world, co
         continue;
       }
       if ((spins & 0xFF) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeoutSec)
-        return ReturnErr(Error::MakeP(ErrCode::StdException, "rank=" + std::to_string(r), "Timed out waiting for a shard's selection."));
+        return Error::MakeP(ErrCode::StdException, "rank=" + std::to_string(r), "Timed out waiting for a shard's selection.");
       sched_yield();
     }
   }
   std::atomic_thread_fence(std::memory_order_acquire);
   PickOfRecords(base, world, strideBytes, pPriority, pIndex);
-  return nullptr;
+  return Error();
+}
+PQACORE_API void *PqaHip_PickWhenAll(const void *pSlots, const int64_t world, const int64_t strideBytes,
+                                     const uint64_t flagValue, const double timeoutSec, double *pPriority, int64_t *pIndex) {
+  return ReturnErr(Guarded([&] { return PickWhenAll(pSlots, world, strideBytes, flagValue, timeoutSec, pPriority, pIndex); }));
 }
 // One step of the shared-memory exchange in one call: enqueue this shard's selection with its record and flag in slot `rank`
 // of the host's slot array (pSlotsDev: the device-visible address of the same array), then wait for every rank and pick.
@@ -642,13 +495,14 @@ PQACORE_API void *PqaHip_SelectThroughSlots(void *pvEngine, const int64_t iQuiz,
                                             const int64_t rank, const int64_t world, const int64_t strideBytes,
                                             const uint64_t flagValue, const double timeoutSec, double *pPriority,
                                             int64_t *pIndex) {
-  ENGINE_OR_RETURN_ERROR;
-  if (!pSlots || !pSlotsDev || rank < 0 || rank >= world || strideBytes < 24)
-    return ReturnErr(Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_SelectThroughSlots."));
-  char *mine = (char *)pSlotsDev + rank * strideBytes;
-  Error e = pEng->EnqueueSelectArgmaxFlag(iQuiz, mine, mine + 16, flagValue);
-  if (!e.ok()) return ReturnErr(std::move(e));
-  return PqaHip_PickWhenAll(pSlots, world, strideBytes, flagValue, timeoutSec, pPriority, pIndex);
+  return ErrorOf(pvEngine, [&](IEngine &eng) -> Error {
+    if (!pSlots || !pSlotsDev || rank < 0 || rank >= world || strideBytes < 24)
+      return Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_SelectThroughSlots.");
+    char *mine = (char *)pSlotsDev + rank * strideBytes;
+    Error e = eng.EnqueueSelectArgmaxFlag(iQuiz, mine, mine + 16, flagValue);
+    if (!e.ok()) return e;
+    return PickWhenAll(pSlots, world, strideBytes, flagValue, timeoutSec, pPriority, pIndex);
+  });
 }
 // The shards' 16-byte winners gathered by ONE RCCL collective on the engine's stream, for a process-per-GPU host that owns an RCCL
 // communicator and is not Python (probqa_amd/dist.py does the same through torch.distributed; north_star: "a single RCCL
@@ -681,6 +535,7 @@ void ReleaseRcclBufs(void *pvEngine) {
     b = std::move(it->second);
     gRcclBufs.erase(it);
   }
+  if (!b) return;   // (a slot whose buffers were never made)
   std::lock_guard<std::mutex> lk(b->mu);   // (a call still inside finishes first)
   b->Free();
 }
@@ -693,67 +548,64 @@ NcclAllGatherFn RcclAllGather() {
   }();
   return fn;
 }
+void ReleaseEngineSideTables(void *pvEngine) { ReleaseRcclBufs(pvEngine); }
 }  // namespace
 PQACORE_API void *PqaHip_SelectArgmaxRccl(void *pvEngine, const int64_t iQuiz, void *pNcclComm, const int64_t world, double *pPriority,
                                           int64_t *pIndex) {
-  ENGINE_OR_RETURN_ERROR;
-  if (!pNcclComm || !pPriority || !pIndex || world < 1 || world > 4096)
-    return ReturnErr(Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_SelectArgmaxRccl."));
-  const NcclAllGatherFn allGather = RcclAllGather();
-  if (allGather == nullptr) return ReturnErr(Error::Make(ErrCode::StdException, "librccl.so (ncclAllGather) could not be loaded."));
-  std::shared_ptr<RcclBufs> bufs;
-  {
-    std::lock_guard<std::mutex> lk(gRcclMu);
-    std::shared_ptr<RcclBufs> &slot = gRcclBufs[pvEngine];
-    if (!slot) slot = std::make_shared<RcclBufs>();
-    bufs = slot;
-  }
-  RcclBufs &b = *bufs;
-  std::lock_guard<std::mutex> held(b.mu);
-  const int device = (int)pEng->GetOption("device");
-  if (device < 0 || pEng->GetOption("shards") > 0) return ReturnErr(Error::Make(ErrCode::StdException, "PqaHip_SelectArgmaxRccl is for an engine on ONE device (a shard of a process-per-GPU host)."));
-  if (hipSetDevice(device) != hipSuccess) return ReturnErr(Error::Make(ErrCode::StdException, "PqaHip_SelectArgmaxRccl: the engine's device cannot be selected."));
-  if (b.world != world || b.device != device) {   // (first call, or another communicator size: allocated on the engine's device, whatever the calling thread's was)
-    b.Free();
-    b.device = device;
-    void *d = nullptr, *h = nullptr;
-    if (hipMalloc(&d, (size_t)(world + 1) * 16) != hipSuccess || hipHostMalloc(&h, (size_t)world * 16, hipHostMallocDefault) != hipSuccess) {
-      if (d) hipFree(d);
-      (void)hipGetLastError();
-      return ReturnErr(Error::Make(ErrCode::StdException, "PqaHip_SelectArgmaxRccl: no memory for the exchange buffers."));
+  return ErrorOf(pvEngine, [&](IEngine &eng) -> Error {
+    if (!pNcclComm || !pPriority || !pIndex || world < 1 || world > 4096)
+      return Error::Make(ErrCode::NullArgument, "Bad arguments to PqaHip_SelectArgmaxRccl.");
+    const NcclAllGatherFn allGather = RcclAllGather();
+    if (allGather == nullptr) return Error::Make(ErrCode::StdException, "librccl.so (ncclAllGather) could not be loaded.");
+    std::shared_ptr<RcclBufs> bufs;
+    {
+      std::lock_guard<std::mutex> lk(gRcclMu);
+      std::shared_ptr<RcclBufs> &slot = gRcclBufs[pvEngine];
+      if (!slot) slot = std::make_shared<RcclBufs>();
+      bufs = slot;
     }
-    b.dSend = d; b.dRecv = static_cast<char *>(d) + 16; b.hRecv = h; b.world = world;
-  }
-  Error e = pEng->EnqueueSelectArgmax(iQuiz, b.dSend);   // {priority, GLOBAL index} of this shard's winner, in stream order
-  if (!e.ok()) return ReturnErr(std::move(e));
-  const hipStream_t stream = pEng->GetStream();
-  const int rc = allGather(b.dSend, b.dRecv, 16, /* ncclUint8 */ 1, pNcclComm, stream);
-  if (rc != 0) return ReturnErr(Error::MakeP(ErrCode::StdException, "ncclResult=" + std::to_string(rc), "ncclAllGather failed."));
-  hipError_t he = hipMemcpyAsync(b.hRecv, b.dRecv, (size_t)world * 16, hipMemcpyDeviceToHost, stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(stream);
-  if (he != hipSuccess) return ReturnErr(Error::MakeP(ErrCode::StdException, hipGetErrorString(he), "PqaHip_SelectArgmaxRccl: the gathered winners did not arrive."));
-  PickOfRecords(static_cast<const char *>(b.hRecv), world, 16, pPriority, pIndex);
-  return nullptr;
+    RcclBufs &b = *bufs;
+    std::lock_guard<std::mutex> held(b.mu);
+    const int device = (int)eng.GetOption("device");
+    if (device < 0 || eng.GetOption("shards") > 0) return Error::Make(ErrCode::StdException, "PqaHip_SelectArgmaxRccl is for an engine on ONE device (a shard of a process-per-GPU host).");
+    if (hipSetDevice(device) != hipSuccess) return Error::Make(ErrCode::StdException, "PqaHip_SelectArgmaxRccl: the engine's device cannot be selected.");
+    if (b.world != world || b.device != device) {   // (first call, or another communicator size: allocated on the engine's device, whatever the calling thread's was)
+      b.Free();
+      b.device = device;
+      void *d = nullptr, *h = nullptr;
+      if (hipMalloc(&d, (size_t)(world + 1) * 16) != hipSuccess || hipHostMalloc(&h, (size_t)world * 16, hipHostMallocDefault) != hipSuccess) {
+        if (d) hipFree(d);
+        (void)hipGetLastError();
+        return Error::Make(ErrCode::StdException, "PqaHip_SelectArgmaxRccl: no memory for the exchange buffers.");
+      }
+      b.dSend = d; b.dRecv = static_cast<char *>(d) + 16; b.hRecv = h; b.world = world;
+    }
+    Error e = eng.EnqueueSelectArgmax(iQuiz, b.dSend);   // {priority, GLOBAL index} of this shard's winner, in stream order
+    if (!e.ok()) return e;
+    const hipStream_t stream = eng.GetStream();
+    const int rc = allGather(b.dSend, b.dRecv, 16, /* ncclUint8 */ 1, pNcclComm, stream);
+    if (rc != 0) return Error::MakeP(ErrCode::StdException, "ncclResult=" + std::to_string(rc), "ncclAllGather failed.");
+    hipError_t he = hipMemcpyAsync(b.hRecv, b.dRecv, (size_t)world * 16, hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) return Error::MakeP(ErrCode::StdException, hipGetErrorString(he), "PqaHip_SelectArgmaxRccl: the gathered winners did not arrive.");
+    PickOfRecords(static_cast<const char *>(b.hRecv), world, 16, pPriority, pIndex);
+    return Error();
+  });
 }
-static void ReleaseEngineSideTables(void *pvEngine) { ReleaseRcclBufs(pvEngine); }
 PQACORE_API void *PqaHip_EnqueueSelectArgmax(void *pvEngine, const int64_t iQuiz, void *pOut) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->EnqueueSelectArgmax(iQuiz, pOut));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EnqueueSelectArgmax(iQuiz, pOut); });
 }
 PQACORE_API void *PqaHip_EnqueueEval(void *pvEngine, const int64_t iQuiz) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->EnqueueEval(iQuiz));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EnqueueEval(iQuiz); });
 }
 PQACORE_API void *PqaHip_GetPriorDevicePtr(void *pvEngine, const int64_t iQuiz, void **ppDev, int64_t *pLdT) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->GetPriorDevicePtr(iQuiz, ppDev, pLdT));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.GetPriorDevicePtr(iQuiz, ppDev, pLdT); });
 }
 PQACORE_API void *PqaHip_RecordAnswerRemote(void *pvEngine, const int64_t iQuiz, const int64_t iAnswer) {
-  ENGINE_OR_RETURN_ERROR;
-  return ReturnErr(pEng->RecordAnswerRemote(iQuiz, iAnswer));
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerRemote(iQuiz, iAnswer); });
 }
 
-PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut) {
+static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut) {
   const std::string w(what ? what : "");
   if (nIn < 0 || nOut < 0 || (nIn > 0 && !pIn) || (nOut > 0 && !pOut)) return -1;
   if (w.compare(0, 12, "option_spec:") == 0) {   // a row of engine_options.h, by the option's name or as "#i" by its position
@@ -901,6 +753,9 @@ PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, 
     return 2;
   }
   return -1;
+}
+PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut) {
+  return GuardedValue<int64_t>(nullptr, -1, [&](Error &) { return HostLogicProbe(what, pIn, nIn, pOut, nOut); });
 }
 
 }  // extern "C"

@@ -1,0 +1,116 @@
+// engine_interface.h -- the error object and the engine interface the C ABI is written against (c_abi.cpp, c_abi_shims.h), apart
+// from the engines themselves (hip_engine.h): only the two public C headers and the stream's handle type are needed, so the C
+// boundary compiles on a host without HIP.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <utility>
+
+#include "../../include/PqaHipExt.h"
+
+typedef struct ihipStream_t *hipStream_t;   // (the opaque handle as <hip/hip_runtime_api.h> declares it)
+
+namespace pqa {
+
+// Error codes of reference PqaCore/Interface/PqaErrors.h:12-40
+enum class ErrCode : int64_t {
+  None = 0, NotImplemented = 1, SRException = 2, StdException = 3, InsufficientEngineDimensions = 4,
+  MaintenanceModeChangeInProgress = 5, MaintenanceModeAlreadyThis = 6, ObjectShutDown = 7, IndexOutOfRange = 8,
+  Internal = 9, Aggregate = 10, NegativeCount = 11, NonPositiveAmount = 12, AbsentId = 13, WrongMode = 14,
+  UnhandledCase = 15, I64Underflow = 16, QuestionsExhausted = 17, NoQuizActiveQuestion = 18, CantOpenFile = 19,
+  FileOp = 20, QuizzesActive = 21, NullArgument = 22, WrongRuntimeType = 23, NotInitialized = 24
+};
+
+// PqaError (reference PqaCore/Interface/PqaErrors.h:56-91): code + message + stringified params
+struct Error {
+  ErrCode code = ErrCode::None;
+  std::string message;
+  std::string params;   // what IPqaErrorParams::ToString() would give; empty = nullptr params
+  bool hasParams = false;
+  bool ok() const { return code == ErrCode::None; }
+  std::string ToString(bool withParams) const;  // reference PqaCore/PqaErrors.cpp:128-143
+  static Error Make(ErrCode c, std::string msg) { Error e; e.code = c; e.message = std::move(msg); return e; }
+  static Error MakeP(ErrCode c, std::string params, std::string msg) {
+    Error e; e.code = c; e.message = std::move(msg); e.params = std::move(params); e.hasParams = true; return e;
+  }
+};
+const char *ErrCodeName(ErrCode c);  // reference PqaCore/PqaErrors.cpp:13-62
+
+struct AQ { int64_t iQuestion, iAnswer; };
+
+// What the C ABI (c_abi.cpp) drives: one engine on one device (HipEngine), or the question axis of one knowledge base split
+// over several devices of the process (ShardedEngine, sharded_engine.cpp) -- the reference's IPqaEngine surface
+// (PqaCore/Interface/IPqaEngine.h:14-113) plus the additive calls of include/PqaHipExt.h.
+class IEngine {
+ public:
+  virtual ~IEngine() {}
+  virtual Error Train(int64_t nQuestions, const AQ *pAQs, int64_t iTarget, double amount) = 0;
+  virtual uint64_t GetTotalQuestionsAsked(Error &err) = 0;
+  virtual void CopyDims(CiEngineDimensions *pDims) const = 0;
+  virtual int64_t StartQuiz(Error &err) = 0;
+  virtual int64_t ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) = 0;
+  virtual int64_t NextQuestion(Error &err, int64_t iQuiz) = 0;
+  virtual Error RecordAnswer(int64_t iQuiz, int64_t iAnswer) = 0;
+  virtual int64_t GetActiveQuestionId(Error &err, int64_t iQuiz) = 0;
+  virtual Error SetActiveQuestion(int64_t iQuiz, int64_t iQuestion) = 0;
+  virtual int64_t ListTopTargets(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedTarget *pDest) = 0;
+  virtual Error RecordQuizTarget(int64_t iQuiz, int64_t iTarget, double amount) = 0;
+  virtual Error ReleaseQuiz(int64_t iQuiz) = 0;
+  virtual Error StartMaintenance(bool forceQuizzes) = 0;
+  virtual Error FinishMaintenance() = 0;
+  virtual Error Shutdown(const char *saveFilePath) = 0;
+  virtual bool MapIds(int which, bool toPerm, int64_t count, int64_t *pIds) = 0;
+  virtual bool EnsurePermQuizGreater(int64_t bound) = 0;
+  virtual bool RemapQuizPermId(int64_t srcPermId, int64_t destPermId) = 0;
+  virtual Error SaveKB(const char *filePath, bool doubleBuffer) = 0;
+  virtual Error SaveKBAs(const char *filePath, uint8_t precType) = 0;      // (additive) in a chosen precision, whole engines
+  virtual Error SaveKBShard(const char *filePath, uint8_t precType) = 0;   // (additive) a shard's part, in place
+  virtual Error AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) = 0;
+  virtual Error RemoveQuestions(int64_t n, const int64_t *pQIds) = 0;
+  virtual Error RemoveTargets(int64_t n, const int64_t *pTIds) = 0;
+  virtual Error Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets) = 0;
+  virtual Error ClearOldQuizzes(int64_t maxCount, double maxAgeSec) = 0;
+  // ---- additive (PqaHipExt.h)
+  virtual Error SetOption(const char *name, int64_t value) = 0;
+  virtual int64_t GetOption(const char *name) const = 0;
+  virtual const char *EvalKernelName() const = 0;
+  virtual Error SetKB(const double *pA, const double *pD, const double *pB) = 0;
+  virtual Error GetKB(double *pA, double *pD, double *pB) = 0;
+  virtual Error FillSynthetic(double nTrain, double noiseAmp, uint64_t seed) = 0;
+  virtual Error SetTargetGaps(int64_t n, const int64_t *ids) = 0;
+  virtual Error SetQuestionGaps(int64_t n, const int64_t *ids) = 0;
+  virtual Error EvalPriorities(int64_t iQuiz, double *pOut, int64_t n) = 0;
+  virtual int64_t NextQuestionArgmax(Error &err, int64_t iQuiz) = 0;
+  virtual int64_t NextQuestionSampled(Error &err, int64_t iQuiz, uint64_t rnd) = 0;
+  virtual Error GetPriors(int64_t iQuiz, double *pOut, int64_t n) = 0;
+  virtual Error NextQuestionArgmaxBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) = 0;
+  virtual Error NextQuestionSampledBatch(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut) = 0;
+  virtual Error NextQuestionBatch(int64_t n, const int64_t *pQuizzes, int64_t *pOut) = 0;
+  virtual Error EvalPrioritiesBatch(int64_t n, const int64_t *pQuizzes, double *pOut) = 0;
+  virtual Error SelectArgmaxBatch(int64_t n, const int64_t *pQuizzes, CiHipSelection *pOut) = 0;
+  virtual Error Log2HotArray(const double *pIn, double *pOut, int64_t n) = 0;
+  virtual hipStream_t GetStream() const = 0;
+  virtual Error SetStream(hipStream_t s) = 0;
+  virtual Error Synchronize() = 0;
+  virtual Error Quiesce() = 0;
+  virtual Error EnqueueSelectArgmax(int64_t iQuiz, void *pOut) = 0;
+  virtual Error EnqueueSelectArgmaxFlag(int64_t iQuiz, void *pOut, void *pFlag, uint64_t flagValue) = 0;
+  virtual Error EnqueueEval(int64_t iQuiz) = 0;
+  virtual Error GetPriorDevicePtr(int64_t iQuiz, void **ppDev, int64_t *pLdT) = 0;
+  virtual Error RecordAnswerRemote(int64_t iQuiz, int64_t iAnswer) = 0;
+  virtual Error RecordAnswerBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers) = 0;
+  virtual Error StartQuizBatch(int64_t n, int64_t *pQuizzes) = 0;
+  virtual Error ResumeQuizBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, int64_t *pQuizzes) = 0;
+  virtual Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) = 0;
+  virtual Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) = 0;
+  virtual Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) = 0;
+  virtual int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) = 0;
+  virtual Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) = 0;
+  virtual int64_t AnswerRowSlotBytes() const = 0;
+  virtual Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) = 0;
+  virtual int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) = 0;
+  virtual Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) = 0;
+};
+
+}  // namespace pqa
