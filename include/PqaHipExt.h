@@ -53,7 +53,7 @@ PQACORE_API void *PqaEngineFactory_CreateHipEngineSharded(void *pvFactory, void 
  * be 0 or the file's question count (InsufficientEngineDimensions otherwise); a range that is not within the file's questions is
  * IndexOutOfRange, a negative count NegativeCount; pShard together with PQA_DEVICES is refused (WrongMode).  The shard reads its two
  * blocks of rows by seeking to them, the whole vB, the target gaps and the target and quiz id maps; the question gaps of its range
- * become its gap bits, and the file's question gap list and question id map are kept as read, for PqaHip_SaveKBShard.
+ * become its gap bits, and the file's question gap list and question id map become the shard's view of the whole question axis.
  * A header whose dimensions are no knowledge base's, or whose arrays the file is too short for, is FileOp before anything is
  * allocated.  A finite value that does not fit Float fails the load (FileOp, naming the array: _sA, _mD or _vB); no engine is
  * returned.  C++ exceptions do not cross these three calls: they come back as StdException / SRException. */
@@ -68,7 +68,8 @@ PQACORE_API void *PqaHip_SaveKBAs(void *pvEngine, const char *filePath, uint8_t 
  * asked; every rank sees every Train --, vB and the trailer, and cuts the file behind the trailer.  The file is complete once every
  * shard's call has returned; the calls may run in any order or at once (they write disjoint ranges), ordering them against readers is the
  * caller's business (probqa_amd/dist.py: save_kb).  Every shard must name the same precType.  A shard loaded from a file writes that
- * file's question gap list and id map back; a created one writes the gaps PqaHip_SetQuestionGaps was given over fresh ids.
+ * trailer is the shard's view of the whole question axis -- the gap list and the id map every rank keeps: the file's as loaded, or
+ * fresh ids for a created shard, with everything PqaHip_SetQuestionGaps and the maintenance calls have done to them since.
  * On a whole one-device engine the call is an equivalent of PqaHip_SaveKBAs (the engine is the only shard of its file); on the
  * one-process sharded engine it is NotImplemented. */
 PQACORE_API void *PqaHip_SaveKBShard(void *pvEngine, const char *filePath, uint8_t precType);
@@ -330,6 +331,47 @@ PQACORE_API int64_t PqaEngine_ResumeQuizFromRows(void *pvEngine, void **ppError,
 PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts,
                                                     const CiAnsweredQuestion *pAQs, const void *pRows, int64_t *pQuizzes);
 
+/* ---- Maintenance on shards that separate processes drive.  PqaEngine_AddQsTs, PqaEngine_RemoveQuestions and PqaEngine_RemoveTargets
+ * are COLLECTIVE AND REPLICATED on such shards: every rank makes the same call with the same arguments (as every rank sees every
+ * PqaEngine_Train), in maintenance mode.  Each shard keeps the bookkeeping of the whole question axis -- the gap list in the
+ * reference's order, the permanent ids, the question count (option "q_total", read-only, beside "q_first") -- and applies the data
+ * changes to the questions it holds: the ids a call returns are GLOBAL and the same on every rank.  A removed question is flagged by
+ * its holder; a reused question id is re-initialised by its holder; APPENDED questions go to the shard whose range ends at the
+ * question count (its local count and capacity grow, the others only raise q_total), so the ranges are no longer an even split
+ * afterwards; added target columns are filled by every shard over its own questions.  PqaEngine_QuestionPermFromComp / CompFromPerm
+ * answer over GLOBAL compact ids.  Nothing travels between the ranks, and a failing call changes nothing on the rank it fails on.
+ *
+ * PqaEngine_Compact moves data between ranks and is refused on a shard (NotImplemented); the collective form is:
+ *   PqaHip_CompactPlan          host only, changes nothing: the dimensions after the compaction and the whole-question moves of the
+ *                               plan as *pnMoves pairs {dst, src} of GLOBAL ids (released with CiReleaseCompaction) -- the same on
+ *                               every rank -- and whether THIS shard would be left without a question.  The ranks vote: if any would,
+ *                               nobody compacts (a shard keeps [q_first, min(q_first + its count, new question count)); there is no
+ *                               re-split -- rebalancing is a save followed by a load at another split).
+ *   PqaHip_QuestionBlockSlotBytes   (nAnswers + 1) * RoundLdT(nTargets) * element size, RoundLdT: up to a 128-byte line.  A function
+ *                               of the dimensions and the precision alone: every rank computes the same value, whatever the pitch
+ *                               of its allocation.
+ *   PqaHip_PackQuestionBlocks   stream-ordered, no host synchronisation, one launch: for every i whose (GLOBAL) question this engine
+ *                               holds, slot i of pDst receives the question's nAnswers sA rows and its mD row, nTargets elements each
+ *                               at the slot's pitch, zeros behind them.  Other slots are untouched, so the ranks fill one zero-filled
+ *                               buffer (or sum theirs).  pDst, pFlag, flagValue as PqaHip_PackAnswerRows; ids out of [0, q_total) are
+ *                               IndexOutOfRange and nothing is launched.  Maintenance mode.  The questions are the plan's sources.
+ *   PqaEngine_CompactFromBlocks PqaEngine_Compact in everything except where a moved question comes from: this engine's own cube
+ *                               where it holds src (such slots may be left unfilled), otherwise slot i of pBlocks for move i.  The
+ *                               outputs are the global maps, the same on every rank.  slotBytes must be
+ *                               PqaHip_QuestionBlockSlotBytes (IndexOutOfRange otherwise).  emptiedRank: the outcome of the ranks'
+ *                               vote, -1 = nobody; any other value refuses the call with InsufficientEngineDimensions naming that
+ *                               rank -- the same text on every rank -- as does a shard that would itself be left empty; nothing has
+ *                               changed then.  A whole engine accepts pBlocks == NULL and does what PqaEngine_Compact does.
+ * probqa_amd/dist.py (compact) runs the sequence over a process group.  Nothing of this has been timed on a GPU. */
+PQACORE_API void *PqaHip_CompactPlan(void *pvEngine, int64_t *pnQuestions, int64_t *pnTargets, int64_t *pnMoves, int64_t const **const ppMoves,
+                                     uint8_t *pWouldBeEmpty);
+PQACORE_API int64_t PqaHip_QuestionBlockSlotBytes(void *pvEngine);
+PQACORE_API void *PqaHip_PackQuestionBlocks(void *pvEngine, const int64_t nQuestions, const int64_t *pQuestions, void *pDst, void *pFlag,
+                                            const uint64_t flagValue);
+PQACORE_API void *PqaEngine_CompactFromBlocks(void *pvEngine, const void *pBlocks, const int64_t slotBytes, const int64_t emptiedRank,
+                                              int64_t *pnQuestions, int64_t const **const ppOldQuestions, int64_t *pnTargets,
+                                              int64_t const **const ppOldTargets);
+
 /* Host bookkeeping of the engine that needs no device, driven by a small script so that it is testable where there is no GPU.
    what = "id_ledger": pIn is a sequence of operations on one fresh compact<->permanent id map (reference behaviour:
    PqaCore/PermanentIdManager.cpp), each {op, a, b}: 0 permanent id of slot a; 1 slot of permanent id a; 2 raise the issue floor
@@ -343,6 +385,8 @@ PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_
    questions, for targets, new Q, new T, question ids, target ids, question amounts, target amounts} (PqaCore/CpuEngine.cpp:468-575).
    what = "compact_plan": pIn = {Q, T, question gaps, target gaps}; pOut = {old question of every new one, old target of every new
    one, the question moves as dst, src pairs in the order they are made} (PqaCore/CpuEngine.cpp:577-658).
+   what = "shard_compact": pIn = {the shards' upper bounds, Q, T, question gaps, target gaps}; pOut = {1 if a shard would be left without
+   a question, the bounds clipped to the new question count, the question moves as {dst, src, dst's shard, src's shard}}.
    what = "check_removal": pIn = {limit, gaps, ids to remove}; pOut = {position of the first id that is out of range, a gap or
    repeated, or -1; the error code the call returns}.
    what = "better_pick": pIn = {priority, index} per shard; pOut = {priority, index} of the winner (maximum priority, lowest index

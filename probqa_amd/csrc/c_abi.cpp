@@ -605,6 +605,22 @@ PQACORE_API void *PqaHip_RecordAnswerRemote(void *pvEngine, const int64_t iQuiz,
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerRemote(iQuiz, iAnswer); });
 }
 
+PQACORE_API void *PqaHip_CompactPlan(void *pvEngine, int64_t *pnQuestions, int64_t *pnTargets, int64_t *pnMoves, int64_t const **const ppMoves,
+                                     uint8_t *pWouldBeEmpty) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.CompactPlanOf(pnQuestions, pnTargets, pnMoves, ppMoves, pWouldBeEmpty); });
+}
+PQACORE_API int64_t PqaHip_QuestionBlockSlotBytes(void *pvEngine) {
+  return LoggedOf<int64_t>(pvEngine, -1, [&](IEngine &e) { return e.QuestionBlockSlotBytes(); });
+}
+PQACORE_API void *PqaHip_PackQuestionBlocks(void *pvEngine, const int64_t nQuestions, const int64_t *pQuestions, void *pDst, void *pFlag,
+                                            const uint64_t flagValue) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackQuestionBlocks(nQuestions, pQuestions, pDst, pFlag, flagValue); });
+}
+PQACORE_API void *PqaEngine_CompactFromBlocks(void *pvEngine, const void *pBlocks, const int64_t slotBytes, const int64_t emptiedRank, int64_t *pnQuestions,
+                                              int64_t const **const ppOldQuestions, int64_t *pnTargets, int64_t const **const ppOldTargets) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.CompactFromBlocks(pBlocks, slotBytes, emptiedRank, pnQuestions, ppOldQuestions, pnTargets, ppOldTargets); });
+}
+
 static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut) {
   const std::string w(what ? what : "");
   if (nIn < 0 || nOut < 0 || (nIn > 0 && !pIn) || (nOut > 0 && !pOut)) return -1;
@@ -716,6 +732,19 @@ static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_
     pOut[0] = plan.nQReuse; pOut[1] = plan.nTReuse; pOut[2] = plan.newQ; pOut[3] = plan.newT;
     nRes = 4;
     return put(plan.qIds) && put(plan.tIds) && put(qWords) && put(tWords) ? nRes : -1;
+  }
+  if (w == "shard_compact") {   // {bounds, Q, T, question gaps, target gaps} -> {refused, new bounds, moves as {dst, src, dst's shard, src's shard}}
+    std::vector<int64_t> bounds;
+    if (!list(bounds) || bounds.empty() || at + 2 > nIn) return -1;
+    const int64_t Q = pIn[at], T = pIn[at + 1];
+    at += 2;
+    for (size_t r = 0; r < bounds.size(); r++)
+      if (bounds[r] <= (r == 0 ? 0 : bounds[r - 1])) return -1;   // ascending, no shard without a question
+    if (bounds.back() != Q || !gapList(qGaps, Q) || !gapList(tGaps, T) || at != nIn || nOut < 1) return -1;
+    const pqa::ShardCompactPlan s = pqa::PlanShardCompact(bounds, pqa::PlanCompact(qGaps, tGaps, Q, T));
+    pOut[0] = s.refused;
+    nRes = 1;
+    return put(s.newBounds) && put(s.moves) ? nRes : -1;
   }
   if (w == "check_removal") {
     at = 1;

@@ -111,6 +111,20 @@ class IEngine {
   virtual Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) = 0;
   virtual int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) = 0;
   virtual Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) = 0;
+  // Compact on a shard that a process of its own drives: question blocks travel as a package.  The one-process sharded engine moves
+  // its blocks itself: it plans and packs nothing, and compacts from no package as Compact does.
+  virtual Error CompactPlanOf(int64_t *, int64_t *, int64_t *, const int64_t **, uint8_t *) { return NoBlocks("CompactPlan"); }
+  virtual int64_t QuestionBlockSlotBytes() const { return -1; }
+  virtual Error PackQuestionBlocks(int64_t, const int64_t *, void *, void *, uint64_t) { return NoBlocks("PackQuestionBlocks"); }
+  virtual Error CompactFromBlocks(const void *pBlocks, int64_t, int64_t, int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets,
+                                  const int64_t **ppOldTargets) {
+    return pBlocks ? NoBlocks("CompactFromBlocks with a package") : Compact(pnQuestions, ppOldQuestions, pnTargets, ppOldTargets);
+  }
+
+ private:
+  static Error NoBlocks(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine", "Question block packages are for shards that separate processes drive.");
+  }
 };
 
 }  // namespace pqa

@@ -211,6 +211,7 @@ Error HipEngine::Init(const CiEngineDefinition &def, const CiHipShard *shard) {
   HIP_TRY(LaunchFillFresh(_dCube, _elem, _dVB, _K, _Q, _T, _ldT, _initAmount, _stream));
   HIP_TRY(hipStreamSynchronize(_stream));
   _questionIds.Extend(_Q);  // reference PqaCore/BaseCpuEngine.cpp:24-25
+  if (IsShard()) _globalQuestionIds.Extend(_qTotal);   // the whole question axis, as every rank keeps it (hip_engine.h)
   _targetIds.Extend(_T);
   std::random_device rd;  // the reference seeds from RDRAND (SRPlatform/Interface/SRFastRandom.h:31-40)
   _rng.Seed(((uint64_t)rd() << 32) ^ rd());
@@ -395,6 +396,7 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "capQ") return _capQ;   // questions the allocation holds: like ldT it only grows (ReallocKB)
   if (n == "device") return _device;
   if (n == "q_first") return _qFirst;
+  if (n == "q_total") return _qTotal;   // questions of the whole knowledge base (a shard: kept current by the replicated maintenance calls)
   if (n == "local_questions") return _Q;
   return -1;   // (an unknown name, and the write-only "seed")
 }
@@ -865,11 +867,11 @@ Error HipEngine::SetQuestionGaps(int64_t n, const int64_t *ids) {
   std::lock_guard<EngineMutex> lk(_mu);
   for (int64_t i = 0; i < n; i++)
     if (ids[i] < 0 || ids[i] >= _qTotal) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(ids[i], 0, _qTotal - 1), "Question index is not in KB range.");
-  if (_qTotal != _Q)   // a shard: the whole axis' gaps, for the trailer of its part of a save
+  if (IsShard())   // the whole axis' gaps and ids, as every rank keeps them
     for (int64_t i = 0; i < n; i++)
       if (std::find(_globalQuestionGaps.begin(), _globalQuestionGaps.end(), ids[i]) == _globalQuestionGaps.end()) {
         _globalQuestionGaps.push_back(ids[i]);
-        if (_fileTrailer) { _fileTrailer->questionGaps.push_back(ids[i]); _fileTrailer->questionIds.Vacate(ids[i]); }
+        _globalQuestionIds.Vacate(ids[i]);
       }
   for (int64_t i = 0; i < n; i++)
     if (ids[i] >= _qFirst && ids[i] < _qFirst + _Q && !BitTest(_hQGap, ids[i] - _qFirst)) {

@@ -197,6 +197,14 @@ class HipEngine : public IEngine {
   Error RemoveQuestions(int64_t n, const int64_t *pQIds) override;
   Error RemoveTargets(int64_t n, const int64_t *pTIds) override;
   Error Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets) override;
+  // ---- maintenance on a shard that a process of its own drives (hip_engine_kb.cpp): AddQsTs / RemoveQuestions / RemoveTargets are
+  // collective and replicated -- every rank makes the same call --; Compact moves whole question blocks between the ranks as a
+  // BLOCK PACKAGE: slot i = the K + 1 rows of the source of question move i of the plan, T elements each at the pitch of the current T
+  Error CompactPlanOf(int64_t *pnQuestions, int64_t *pnTargets, int64_t *pnMoves, const int64_t **ppMoves, uint8_t *pWouldBeEmpty) override;
+  int64_t QuestionBlockSlotBytes() const override { return (_K + 1) * RoundLdT(_T, _elem) * (int64_t)_elem; }
+  Error PackQuestionBlocks(int64_t n, const int64_t *pQuestions, void *pDst, void *pFlag, uint64_t flagValue) override;
+  Error CompactFromBlocks(const void *pBlocks, int64_t slotBytes, int64_t emptiedRank, int64_t *pnQuestions, const int64_t **ppOldQuestions,
+                          int64_t *pnTargets, const int64_t **ppOldTargets) override;
   Error ClearOldQuizzes(int64_t maxCount, double maxAgeSec) override;
 
   // ---- additive (PqaHipExt.h)
@@ -353,7 +361,8 @@ class HipEngine : public IEngine {
   Error ResumeBatchEntriesLocked(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *const *rows, int64_t *pQuizzes);
   // a package's slots as row pointers (this engine's own questions: its cube); a package in host memory staged by option "rows_stage"
   Error PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pRows, std::vector<const void *> &rows);
-  int64_t *_hPack = nullptr;           // PackAnswerRows: the pinned source of its pointer list, and the event behind the list's copy
+  Error EnsurePackList(int64_t words); // room for `words` 8-byte words in _dAqs and _hPack, the previous list's copy finished, the header zeroed
+  int64_t *_hPack = nullptr;           // PackAnswerRows / PackQuestionBlocks: the pinned source of the pointer list, and the event behind the list's copy
   int64_t _hPackWords = 0;
   hipEvent_t _evPack = nullptr;
   char *_dRowStage = nullptr;          // ResumeQuizFromRows: where a host package is copied first
@@ -382,7 +391,10 @@ class HipEngine : public IEngine {
   Error UploadGaps();
   Error RemoveIds(int64_t n, const int64_t *ids, int64_t limit, std::vector<uint32_t> &gapBits, std::vector<int64_t> &gapList, IdLedger &ledger,
                   const char *absentMsg);   // RemoveQuestions / RemoveTargets: all ids validated, then flagged, listed and retired
-  Error ReallocKB(int64_t newQ, int64_t newT);               // grow the device cube / vB / per-question buffers
+  Error ReallocKB(int64_t newQ, int64_t newT, int64_t newQTotal);   // grow the device cube / vB / per-question buffers (newQ: this engine's questions)
+  Error CompactLocked(bool fromBlocks, const void *pBlocks, int64_t slotBytes, int64_t emptiedRank, int64_t *pnQuestions,
+                      const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets);
+  bool IsShard() const { return _qTotal != _Q; }             // holds a part of the question axis (_qFirst + _Q <= _qTotal always)
   int64_t AssignQuiz(Quiz *q);                               // reference BaseEngine::AssignQuiz, BaseEngine.cpp:780-793
   void UnassignQuiz(int64_t iQuiz);
 
@@ -645,12 +657,12 @@ class HipEngine : public IEngine {
   int64_t _capQ = 0;                        // questions the device buffers are allocated for (>= _Q)
   std::vector<int64_t> _questionGapList, _targetGapList;  // LIFO, like reference PqaCore/GapTracker.h
   IdLedger _questionIds, _targetIds, _quizIds;
-  // A shard: the question axis of the WHOLE knowledge base as its file had it -- the gap list and the id ledger, global ids, read-only
-  // (a shard changes neither: AddQsTs / RemoveQuestions are refused) -- so that SaveKBShard writes the file's trailer back byte for
-  // byte.  A created shard has none: its trailer is built from the global gaps SetQuestionGaps was given.
-  struct FileTrailer { std::vector<int64_t> questionGaps; IdLedger questionIds; };
-  std::unique_ptr<FileTrailer> _fileTrailer;
+  // A shard: the question axis of the WHOLE knowledge base, replicated on every rank -- the gap list in the reference's LIFO order and
+  // the permanent-id ledger, both over GLOBAL ids.  Fresh ids at Create, the file's trailer after a load; SetQuestionGaps,
+  // RemoveQuestions, AddQsTs and CompactFromBlocks keep them current, SaveKBShard writes its trailer from them, and the question id
+  // maps answer from the ledger.  (_questionGapList, _questionIds and _hQGap stay what they are on a whole engine: over LOCAL ids.)
   std::vector<int64_t> _globalQuestionGaps;
+  IdLedger _globalQuestionIds;
   uint32_t _precMantissa = 0;
   uint16_t _precExponent = 0;
   std::vector<Quiz *> _quizzes;

@@ -168,7 +168,8 @@ std::vector<int64_t> QuizzesToLetGo(const std::vector<QuizUsage> &quizzes, time_
 bool HipEngine::MapIds(int which, bool toPerm, int64_t count, int64_t *pIds) {
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
-  IdLedger &ids = which == 0 ? _questionIds : which == 1 ? _targetIds : _quizIds;
+  // (a shard's question map is the whole axis': GLOBAL compact ids, the same answers on every rank)
+  IdLedger &ids = which == 0 ? (IsShard() ? _globalQuestionIds : _questionIds) : which == 1 ? _targetIds : _quizIds;
   for (int64_t i = 0; i < count; i++) pIds[i] = toPerm ? ids.PermanentOf(pIds[i]) : ids.SlotOf(pIds[i]);
   return true;
 }
@@ -585,16 +586,9 @@ Error HipEngine::SaveKBShard(const char *filePath, uint8_t precType) {
     if (e.ok()) e = file.WriteHeader(KbHeader{precision, _K, _qTotal, _T, _nQuestionsAsked.load(std::memory_order_acquire)});
     if (e.ok()) e = file.Seek(lay.vbOff);
     if (e.ok()) e = IoVB(file.f, filePath, true, fe);
-    if (e.ok()) {
-      if (_qTotal == _Q) e = file.WriteTrailer(_questionGapList, _targetGapList, _questionIds, _targetIds, _quizIds);
-      else if (_fileTrailer) e = file.WriteTrailer(_fileTrailer->questionGaps, _targetGapList, _fileTrailer->questionIds, _targetIds, _quizIds);
-      else {   // a shard that was created, not loaded: the question axis as Create and SetQuestionGaps left it on every rank
-        IdLedger all;
-        all.Extend(_qTotal);
-        for (int64_t g : _globalQuestionGaps) all.Vacate(g);
-        e = file.WriteTrailer(_globalQuestionGaps, _targetGapList, all, _targetIds, _quizIds);
-      }
-    }
+    if (e.ok())   // (a shard: the whole question axis as every rank keeps it)
+      e = IsShard() ? file.WriteTrailer(_globalQuestionGaps, _targetGapList, _globalQuestionIds, _targetIds, _quizIds)
+                    : file.WriteTrailer(_questionGapList, _targetGapList, _questionIds, _targetIds, _quizIds);
     if (e.ok() && (std::fflush(file.f) != 0 || ftruncate(fileno(file.f), ftello(file.f)) != 0)) e = FileErr(filePath, "Can't cut the KB file behind its trailer.");
   }
   return e.ok() ? file.FlushAndClose() : e;
@@ -620,7 +614,7 @@ Error KbLoadDefinition(const KbHeader &h, uint8_t precType, CiEngineDefinition &
 // Load in the file's precision or another (precType), whole (shard == nullptr) or the window [shard->_qFirst, + nLocal) of the
 // file's questions as a shard on shard->_device.  A shard takes its rows -- a seek to each of its two blocks --, the whole vB, the
 // target gaps, the target and quiz ledgers, and the question gaps of its range as local gap bits; the file's question gap list and
-// question id ledger it keeps as they are (_fileTrailer), for the trailer of a later SaveKBShard.
+// question id ledger become its view of the whole question axis (_globalQuestionGaps, _globalQuestionIds).
 HipEngine *HipEngine::LoadAs(Error &err, const char *filePath, uint8_t precType, const CiHipShard *shard, int64_t nLocal) {
   KbFile file(filePath, false);
   KbHeader h;
@@ -667,17 +661,14 @@ HipEngine *HipEngine::LoadAs(Error &err, const char *filePath, uint8_t precType,
     if (!err.ok()) return nullptr;
     for (int64_t g : e._questionGapList) BitSet(e._hQGap, g, true);
   } else {
-    std::unique_ptr<FileTrailer> kept(new FileTrailer());
-    err = file.ReadTrailer(h.Q, e._T, kept->questionGaps, e._targetGapList, kept->questionIds, e._targetIds, e._quizIds);
+    err = file.ReadTrailer(h.Q, e._T, e._globalQuestionGaps, e._targetGapList, e._globalQuestionIds, e._targetIds, e._quizIds);
     if (!err.ok()) return nullptr;
-    for (int64_t g : kept->questionGaps)
+    for (int64_t g : e._globalQuestionGaps)
       if (e.OwnsQuestion(g) && !BitTest(e._hQGap, g - e._qFirst)) {
         BitSet(e._hQGap, g - e._qFirst, true);
         e._questionGapList.push_back(g - e._qFirst);
         e._questionIds.Vacate(g - e._qFirst);
       }
-    e._globalQuestionGaps = kept->questionGaps;
-    e._fileTrailer = std::move(kept);
   }
   for (int64_t g : e._targetGapList) BitSet(e._hTGap, g, true);
   e._nTargetGaps = (int64_t)e._targetGapList.size();
@@ -713,7 +704,7 @@ struct DevBuf {
 // Grow the knowledge base to newQ questions and newT targets.  All-or-nothing: every new buffer is allocated and filled
 // before the engine's members change, so a failure (out of memory while the old and the new cube coexist) leaves the engine
 // as it was.
-Error HipEngine::ReallocKB(int64_t newQ, int64_t newT) {
+Error HipEngine::ReallocKB(int64_t newQ, int64_t newT, int64_t newQTotal) {
   const int64_t newLdT = std::max(_ldT, RoundLdT(newT, _elem));
   const int64_t newCap = std::max(_capQ, newQ);
   const bool regrow = newLdT != _ldT || newCap != _capQ;
@@ -764,53 +755,80 @@ Error HipEngine::ReallocKB(int64_t newQ, int64_t newT) {
   hipFree(_dTGap); hipFree(_dQGap);
   _dTGap = tgapDev.Release(); _dQGap = qgapDev.Release();
   _Q = newQ;
-  _qTotal = newQ;
+  _qTotal = newQTotal;
   _T = newT;
   return UploadGaps();
 }
 
+// On a shard the call is collective and replicated: every rank plans over the same global gap list and dimensions, so the ids are
+// the same everywhere.  Target columns are filled by every shard over its own questions (and its vB replica); a reused question id is
+// re-initialised by the shard that holds it; appended ids go to the shard whose range ends at the question count -- its _Q and capacity
+// grow --, every other shard only raises _qTotal.  A whole engine is the one shard that holds everything.
 Error HipEngine::AddQsTs(int64_t nQuestions, CiAddQorTParam *pAqps, int64_t nTargets, CiAddQorTParam *pAtps) {
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_mode != Mode::Maintenance) return WrongModeErr("add questions/targets");
   Error ae = CheckAddArgs(nQuestions, pAqps, nTargets, pAtps);
   if (!ae.ok()) return ae;
-  if (_qFirst != 0 || _qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=AddQsTs on a shard", "Not on a sharded engine.");
   hipSetDevice(_device);
   // CpuEngine::AddQsTsSpec, reference PqaCore/CpuEngine.cpp:468-575.  The ids are worked out first (kb_plan.h) and committed
   // -- gap lists, permanent ids, bitmaps, the caller's _index fields -- only after the resize and the fills have succeeded.
-  const AddPlan plan = PlanAdd(_questionGapList, _targetGapList, _Q, _T, nQuestions, pAqps, nTargets, pAtps);
+  const bool shard = IsShard(), holdsEnd = _qFirst + _Q == _qTotal;
+  const AddPlan plan = PlanAdd(shard ? _globalQuestionGaps : _questionGapList, _targetGapList, _qTotal, _T, nQuestions, pAqps, nTargets, pAtps);
   const std::vector<int64_t> &qIds = plan.qIds, &tIds = plan.tIds;
   const int64_t nQReuse = plan.nQReuse, nTReuse = plan.nTReuse, nTNew = nTargets - nTReuse, nQOld = _Q;
+  const int64_t newLocalQ = _Q + (holdsEnd ? plan.newQ - _qTotal : 0);
+  // the call's questions this engine holds, LOCAL ids: the reused ones first
+  std::vector<int64_t> qLocal;
+  std::vector<double> qLocalInit;
+  int64_t nLocalReuse = 0;
+  for (int64_t i = 0; i < nQuestions; i++) {
+    const bool mine = i < nQReuse ? OwnsQuestion(qIds[(size_t)i]) : holdsEnd;
+    if (!mine) continue;
+    qLocal.push_back(qIds[(size_t)i] - _qFirst);
+    qLocalInit.push_back(plan.qInit[(size_t)i]);
+    if (i < nQReuse) nLocalReuse++;
+  }
   // whole questions first, then target columns over the questions not (re)initialised just now
-  std::vector<uint32_t> skip(BitWords(plan.newQ), 0);
-  for (int64_t i = 0; i < nQReuse; i++) BitSet(skip, qIds[(size_t)i], true);    // :558-560 only reused questions are skipped
+  std::vector<uint32_t> skip(BitWords(newLocalQ), 0);
+  for (int64_t i = 0; i < nLocalReuse; i++) BitSet(skip, qLocal[(size_t)i], true);    // :558-560 only reused questions are skipped
   DevBuf<int64_t> dQ, dT;
   DevBuf<double> dQi, dTi;
   DevBuf<uint32_t> dSkip;
-  HIP_TRY(Upload(&dQ.p, qIds, _stream));
-  HIP_TRY(Upload(&dQi.p, plan.qInit, _stream));
+  HIP_TRY(Upload(&dQ.p, qLocal, _stream));
+  HIP_TRY(Upload(&dQi.p, qLocalInit, _stream));
   HIP_TRY(Upload(&dT.p, tIds, _stream));
   HIP_TRY(Upload(&dTi.p, plan.tInit, _stream));
   HIP_TRY(Upload(&dSkip.p, skip, _stream));
-  Error e = ReallocKB(plan.newQ, plan.newT);   // all-or-nothing; the reused ids are still flagged as gaps
+  Error e = ReallocKB(newLocalQ, plan.newT, plan.newQ);   // all-or-nothing; the reused ids are still flagged as gaps
   if (!e.ok()) return e;
   // new target columns apply to every old question (:512-527); reused target columns skip reused questions (:553-567).
   // New questions are filled over ALL columns with their own amount (:497-510), so they are filled last.
   hipError_t he = hipSuccess;
   if (nTReuse > 0) he = LaunchFillTargets(_dCube, _elem, _dVB, _K, _ldT, nQOld, dSkip.p, dT.p, dTi.p, nTReuse, _stream);
   if (he == hipSuccess && nTNew > 0) he = LaunchFillTargets(_dCube, _elem, _dVB, _K, _ldT, nQOld, nullptr, dT.p + nTReuse, dTi.p + nTReuse, nTNew, _stream);
-  if (he == hipSuccess && nQuestions > 0) he = LaunchFillQuestions(_dCube, _elem, _K, _T, _ldT, dQ.p, dQi.p, nQuestions, _stream);
+  if (he == hipSuccess && !qLocal.empty()) he = LaunchFillQuestions(_dCube, _elem, _K, _T, _ldT, dQ.p, dQi.p, (int64_t)qLocal.size(), _stream);
   if (he == hipSuccess) he = hipStreamSynchronize(_stream);
   if (he != hipSuccess) {   // (a failed launch: the device is gone) keep the id maps the size of the grown KB
     _questionIds.Extend(_Q);
     _targetIds.Extend(_T);
+    if (shard) _globalQuestionIds.Extend(_qTotal);
     return HipErr(he, "AddQsTs");
   }
   // ---- commit
-  for (int64_t i = 0; i < nQReuse; i++) { BitSet(_hQGap, qIds[(size_t)i], false); _questionIds.Reissue(qIds[(size_t)i]); }
+  for (int64_t i = 0; i < nLocalReuse; i++) { BitSet(_hQGap, qLocal[(size_t)i], false); _questionIds.Reissue(qLocal[(size_t)i]); }
   for (int64_t i = 0; i < nTReuse; i++) { BitSet(_hTGap, tIds[(size_t)i], false); _targetIds.Reissue(tIds[(size_t)i]); }
-  _questionGapList.resize(_questionGapList.size() - (size_t)nQReuse);   // (the reused ids were its last entries)
+  if (shard) {   // the whole axis, and this shard's own list (its order is not the global one's: the reused ids are looked up)
+    for (int64_t i = 0; i < nQReuse; i++) _globalQuestionIds.Reissue(qIds[(size_t)i]);
+    _globalQuestionGaps.resize(_globalQuestionGaps.size() - (size_t)nQReuse);
+    _globalQuestionIds.Extend(_qTotal);
+    for (int64_t i = 0; i < nLocalReuse; i++) {
+      const auto at = std::find(_questionGapList.begin(), _questionGapList.end(), qLocal[(size_t)i]);
+      if (at != _questionGapList.end()) _questionGapList.erase(at);
+    }
+  } else {
+    _questionGapList.resize(_questionGapList.size() - (size_t)nQReuse);   // (the reused ids were its last entries)
+  }
   _targetGapList.resize(_targetGapList.size() - (size_t)nTReuse);
   _nTargetGaps = (int64_t)_targetGapList.size();
   _questionIds.Extend(_Q);                           // :541-542
@@ -865,8 +883,24 @@ Error HipEngine::RemoveQuestions(int64_t n, const int64_t *pQIds) {  // BaseEngi
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_mode != Mode::Maintenance) return WrongModeErr("remove questions");
-  if (_qFirst != 0 || _qTotal != _Q) return Error::MakeP(ErrCode::NotImplemented, "Feature=RemoveQuestions on a shard", "Not on a sharded engine.");
-  return RemoveIds(n, pQIds, _Q, _hQGap, _questionGapList, _questionIds, "Question index is not in KB.");
+  if (!IsShard()) return RemoveIds(n, pQIds, _Q, _hQGap, _questionGapList, _questionIds, "Question index is not in KB.");
+  // A shard: GLOBAL ids, validated against the whole axis' gaps -- the same verdict on every rank --; every rank lists and retires
+  // them, the rank that holds one also flags it.
+  std::vector<char> isGap((size_t)_qTotal, 0);
+  for (int64_t g : _globalQuestionGaps) isGap[(size_t)g] = 1;
+  Error e = CheckRemoval(n, pQIds, _qTotal, [&](int64_t id) { return isGap[(size_t)id] != 0; }, "Question index is not in KB.");
+  if (!e.ok()) return e;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t id = pQIds[i];
+    _globalQuestionGaps.push_back(id);
+    _globalQuestionIds.Vacate(id);
+    if (!OwnsQuestion(id)) continue;
+    BitSet(_hQGap, id - _qFirst, true);
+    _questionGapList.push_back(id - _qFirst);
+    _questionIds.Vacate(id - _qFirst);
+  }
+  hipSetDevice(_device);
+  return UploadGaps();
 }
 
 Error HipEngine::RemoveTargets(int64_t n, const int64_t *pTIds) {  // BaseEngine.cpp:745-765
@@ -891,38 +925,127 @@ Error HipEngine::RemoveIds(int64_t n, const int64_t *ids, int64_t limit, std::ve
   return UploadGaps();
 }
 
-Error HipEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets,
-                         const int64_t **ppOldTargets) {  // CpuEngine::CompactSpec, CpuEngine.cpp:577-658
+Error HipEngine::Compact(int64_t *pnQuestions, const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets) {
+  return CompactLocked(false, nullptr, 0, -1, pnQuestions, ppOldQuestions, pnTargets, ppOldTargets);
+}
+Error HipEngine::CompactFromBlocks(const void *pBlocks, int64_t slotBytes, int64_t emptiedRank, int64_t *pnQuestions, const int64_t **ppOldQuestions,
+                                   int64_t *pnTargets, const int64_t **ppOldTargets) {
+  return CompactLocked(true, pBlocks, slotBytes, emptiedRank, pnQuestions, ppOldQuestions, pnTargets, ppOldTargets);
+}
+
+// What a compaction would do, on the host alone: the new dimensions and the whole-question moves as (dst, src) pairs of GLOBAL ids --
+// the same on every rank --, and whether THIS engine's range would be left without a question.
+Error HipEngine::CompactPlanOf(int64_t *pnQuestions, int64_t *pnTargets, int64_t *pnMoves, const int64_t **ppMoves, uint8_t *pWouldBeEmpty) {
+  if (!pnQuestions || !pnTargets || !pnMoves || !ppMoves || !pWouldBeEmpty) return Error::Make(ErrCode::NullArgument, "Nullptr output.");
+  std::lock_guard<EngineMutex> lk(_mu);
+  const CompactPlan plan = PlanCompact(IsShard() ? _globalQuestionGaps : _questionGapList, _targetGapList, _qTotal, _T);
+  std::vector<int64_t> moves;
+  for (const auto &mv : plan.qMoves) { moves.push_back(mv.first); moves.push_back(mv.second); }
+  *pnQuestions = (int64_t)plan.oldQ.size();
+  *pnTargets = (int64_t)plan.oldT.size();
+  *pnMoves = (int64_t)plan.qMoves.size();
+  *ppMoves = MallocCopy(moves);
+  *pWouldBeEmpty = ClippedQuestions(_qFirst, _Q, *pnQuestions) == 0 ? 1 : 0;
+  return Error();
+}
+
+// One launch (kb_kernels.hip: copy_question_blocks_kernel) behind one copy of the pointer list, as PackAnswerRows; nothing waits
+// for the device.  Slot i takes question pQuestions[i] where this engine holds it: its K + 1 rows, T elements each, zeros behind.
+Error HipEngine::PackQuestionBlocks(int64_t n, const int64_t *pQuestions, void *pDst, void *pFlag, uint64_t flagValue) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "The number of question blocks must be non-negative.");
+  if (n > 0 && (!pQuestions || !pDst)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the questions or the package.");
+  std::lock_guard<EngineMutex> lk(_mu);
+  if (_mode != Mode::Maintenance) return WrongModeErr("pack question blocks");
+  int64_t m = 0;
+  for (int64_t i = 0; i < n; i++) {   // (everything is checked before anything is launched)
+    if (pQuestions[i] < 0 || pQuestions[i] >= _qTotal)
+      return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(pQuestions[i], 0, _qTotal - 1), "Question index is not in KB range.");
+    m += OwnsQuestion(pQuestions[i]) ? 1 : 0;
+  }
+  if (m == 0 && pFlag == nullptr) return Error();
+  hipSetDevice(_device);
+  StopServer();
+  static_assert(sizeof(BlockCopy) == 2 * sizeof(int64_t), "the blocks travel in the answered-question buffer");
+  const int64_t words = 2 + 2 * m;   // {arrival counter, pad}, then a BlockCopy per block of this engine's
+  Error e = EnsurePackList(words);
+  if (!e.ok()) return e;
+  BlockCopy *blocks = reinterpret_cast<BlockCopy *>(_hPack + 2);
+  const size_t slotBytes = (size_t)QuestionBlockSlotBytes();
+  for (int64_t i = 0, at = 0; i < n; i++)
+    if (OwnsQuestion(pQuestions[i])) blocks[at++] = BlockCopy{CubeAt(pQuestions[i] - _qFirst), static_cast<char *>(pDst) + (size_t)i * slotBytes};
+  MarkStreamBusy();
+  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
+  HIP_TRY(hipEventRecord(_evPack, _stream));
+  HIP_TRY(LaunchCopyQuestionBlocks(reinterpret_cast<const BlockCopy *>(_dAqs + 2), m, _K + 1, _T * _elem / 4, _ldT * _elem, (int64_t)slotBytes / (_K + 1), true,
+                                   reinterpret_cast<unsigned *>(_dAqs), static_cast<uint64_t *>(pFlag), flagValue, _stream));
+  _packCalls++;
+  _packBytes += (uint64_t)m * slotBytes;
+  return Error();
+}
+
+// CpuEngine::CompactSpec, CpuEngine.cpp:577-658.  On a shard the plan is the global axis' (kb_plan.h) and the shard keeps the part
+// of its range below the new question count; every move (dst, src) has src among the dropped ids and dst a gap among the kept ones,
+// so the moves are independent of each other: this engine makes those whose dst it holds, from its own cube where it holds src too,
+// otherwise from slot i of the package (move i of the plan).  Everything is checked before anything moves.
+Error HipEngine::CompactLocked(bool fromBlocks, const void *pBlocks, int64_t slotBytes, int64_t emptiedRank, int64_t *pnQuestions,
+                               const int64_t **ppOldQuestions, int64_t *pnTargets, const int64_t **ppOldTargets) {
   std::lock_guard<EngineMutex> lk(_mu);
   StopServer();
   if (_mode != Mode::Maintenance) return WrongModeErr("compact the KB");
   if (!pnQuestions || !ppOldQuestions || !pnTargets || !ppOldTargets) return Error::Make(ErrCode::NullArgument, "Nullptr output.");
+  const bool shard = IsShard();
+  if (shard && !fromBlocks) return Error::MakeP(ErrCode::NotImplemented, "Feature=Compact on a shard", "Compact on a shard: use PqaEngine_CompactFromBlocks");
+  if (pBlocks && slotBytes != QuestionBlockSlotBytes())
+    return Error::MakeP(ErrCode::IndexOutOfRange, "[slotBytes=" + std::to_string(slotBytes) + " of " + std::to_string(QuestionBlockSlotBytes()) + "]",
+                        "The block package's slot size is not this engine's (PqaHip_QuestionBlockSlotBytes).");
   hipSetDevice(_device);
-  const CompactPlan plan = PlanCompact(_questionGapList, _targetGapList, _Q, _T);   // the pairing: kb_plan.h
+  const CompactPlan plan = PlanCompact(shard ? _globalQuestionGaps : _questionGapList, _targetGapList, _qTotal, _T);   // the pairing: kb_plan.h
   const int64_t nQ = (int64_t)plan.oldQ.size(), nT = (int64_t)plan.oldT.size();
-  for (const auto &mv : plan.qMoves)   // (in the plan's order: a question that moves is read before anything lands on it)
-    HIP_TRY(hipMemcpyAsync(CubeAt(mv.first), CubeAt(mv.second), (size_t)(_K + 1) * (size_t)_ldT * (size_t)_elem, hipMemcpyDeviceToDevice, _stream));
+  const int64_t nLocal = shard ? ClippedQuestions(_qFirst, _Q, nQ) : nQ;
+  if (emptiedRank >= 0 || (shard && nLocal == 0))   // (the ranks' vote, or at least this shard's own part of it: the same text on every rank)
+    return Error::MakeP(ErrCode::InsufficientEngineDimensions, "[nQuestions=" + std::to_string(nQ) + "]" + (emptiedRank >= 0 ? " [rank=" + std::to_string(emptiedRank) + "]" : ""),
+                        "The compaction would leave a shard without a question.");
+  std::vector<BlockCopy> foreign;
+  for (size_t i = 0; i < plan.qMoves.size(); i++) {
+    const int64_t dst = plan.qMoves[i].first, src = plan.qMoves[i].second;
+    if (!OwnsQuestion(dst) || OwnsQuestion(src)) continue;
+    if (pBlocks == nullptr) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the block package.");
+    foreign.push_back(BlockCopy{static_cast<const char *>(pBlocks) + i * (size_t)slotBytes, CubeAt(dst - _qFirst)});
+  }
+  for (const auto &mv : plan.qMoves)
+    if (OwnsQuestion(mv.first) && OwnsQuestion(mv.second))
+      HIP_TRY(hipMemcpyAsync(CubeAt(mv.first - _qFirst), CubeAt(mv.second - _qFirst), (size_t)(_K + 1) * (size_t)_ldT * (size_t)_elem, hipMemcpyDeviceToDevice, _stream));
   std::vector<int64_t> moves;   // {src, dst} per target column that moves
   for (int64_t t = 0; t < nT; t++) if (plan.oldT[(size_t)t] != t) { moves.push_back(plan.oldT[(size_t)t]); moves.push_back(t); }
-  int64_t *dMoves = nullptr;
-  hipError_t he = Upload(&dMoves, moves, _stream);
-  if (he == hipSuccess) he = LaunchMoveTargets(_dCube, _elem, _dVB, _K, _ldT, nQ, dMoves, (int64_t)moves.size() / 2, _stream);
+  DevBuf<BlockCopy> dForeign;
+  DevBuf<int64_t> dMoves;
+  hipError_t he = Upload(&dForeign.p, foreign, _stream);
+  if (he == hipSuccess && !foreign.empty())
+    he = LaunchCopyQuestionBlocks(dForeign.p, (int64_t)foreign.size(), _K + 1, _T * _elem / 4, slotBytes / (_K + 1), _ldT * _elem, false, nullptr, nullptr, 0, _stream);
+  if (he == hipSuccess) he = Upload(&dMoves.p, moves, _stream);
+  if (he == hipSuccess) he = LaunchMoveTargets(_dCube, _elem, _dVB, _K, _ldT, nLocal, dMoves.p, (int64_t)moves.size() / 2, _stream);
   if (he == hipSuccess) he = hipStreamSynchronize(_stream);
-  hipFree(dMoves);
   if (he != hipSuccess) return HipErr(he, "Compact");
-  _questionIds.Repack(nQ, plan.oldQ.data());
+  if (shard) {   // the whole axis; the local map starts over (its permanent ids are nobody's: MapIds answers from the global one)
+    _globalQuestionIds.Repack(nQ, plan.oldQ.data());
+    _globalQuestionGaps.clear();
+    _questionIds.Clear();
+    _questionIds.Extend(nLocal);
+  } else {
+    _questionIds.Repack(nQ, plan.oldQ.data());
+  }
   _targetIds.Repack(nT, plan.oldT.data());
   _questionGapList.clear();
   _targetGapList.clear();
   _nTargetGaps = 0;
   // shrink the logical dimensions; the allocation (capacity, ldT) stays, padding is re-flagged as gap
   _hTGap.assign(BitWords(_ldT), 0);
-  _hQGap.assign(BitWords(nQ), 0);
+  _hQGap.assign(BitWords(nLocal), 0);
   for (int64_t t = nT; t < (int64_t)_hTGap.size() * 32; t++) BitSet(_hTGap, t, true);
-  for (int64_t q = nQ; q < (int64_t)_hQGap.size() * 32; q++) BitSet(_hQGap, q, true);
+  for (int64_t q = nLocal; q < (int64_t)_hQGap.size() * 32; q++) BitSet(_hQGap, q, true);
   hipFree(_dQGap); _dQGap = nullptr;
   HIP_TRY(hipMalloc(&_dQGap, _hQGap.size() * sizeof(uint32_t)));
-  _Q = nQ; _qTotal = nQ; _T = nT;
+  _Q = nLocal; _qTotal = nQ; _T = nT;
   *pnQuestions = nQ; *pnTargets = nT;
   *ppOldQuestions = MallocCopy(plan.oldQ); *ppOldTargets = MallocCopy(plan.oldT);
   return UploadGaps();

@@ -292,6 +292,28 @@ Error HipEngine::PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFl
   // the list: {arrival counter, pad} and then a PackPair per row pair of this engine's questions
   static_assert(sizeof(PackPair) == 3 * sizeof(int64_t), "the pairs travel in the answered-question buffer");
   const int64_t words = 2 + 3 * m;
+  err = EnsurePackList(words);
+  if (!err.ok()) return err;
+  PackPair *pairs = reinterpret_cast<PackPair *>(_hPack + 2);
+  const size_t slotBytes = (size_t)AnswerRowSlotBytes();
+  for (int64_t i = 0, at = 0; i < n; i++) {
+    if (!OwnsQuestion(pAQs[i].iQuestion)) continue;
+    pairs[at++] = PackPair{CubeAt(pAQs[i].iQuestion - _qFirst, pAQs[i].iAnswer), CubeAt(pAQs[i].iQuestion - _qFirst, _K),
+                           static_cast<char *>(pDst) + (size_t)i * slotBytes};
+  }
+  MarkStreamBusy();
+  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
+  HIP_TRY(hipEventRecord(_evPack, _stream));
+  HIP_TRY(LaunchPackAnswerRows(reinterpret_cast<const PackPair *>(_dAqs + 2), m, (int64_t)(slotBytes / 2), reinterpret_cast<unsigned *>(_dAqs),
+                               static_cast<uint64_t *>(pFlag), flagValue, _stream));
+  _packCalls++;
+  _packBytes += (uint64_t)m * slotBytes;
+  return Error();
+}
+
+// The pointer list of a pack call (PackAnswerRows, PackQuestionBlocks): `words` 8-byte words fit the device buffer and its pinned
+// source, the copy of the previous call's list has left the pinned one, and the header -- the arrival counter -- is zero.
+Error HipEngine::EnsurePackList(int64_t words) {
   if (words > 2 * _aqCapacity) {
     hipFree(_dAqs);   // (waits for whatever still reads it)
     _dAqs = nullptr;
@@ -311,20 +333,6 @@ Error HipEngine::PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFl
     _hPackWords = cap;
   }
   _hPack[0] = _hPack[1] = 0;
-  PackPair *pairs = reinterpret_cast<PackPair *>(_hPack + 2);
-  const size_t slotBytes = (size_t)AnswerRowSlotBytes();
-  for (int64_t i = 0, at = 0; i < n; i++) {
-    if (!OwnsQuestion(pAQs[i].iQuestion)) continue;
-    pairs[at++] = PackPair{CubeAt(pAQs[i].iQuestion - _qFirst, pAQs[i].iAnswer), CubeAt(pAQs[i].iQuestion - _qFirst, _K),
-                           static_cast<char *>(pDst) + (size_t)i * slotBytes};
-  }
-  MarkStreamBusy();
-  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
-  HIP_TRY(hipEventRecord(_evPack, _stream));
-  HIP_TRY(LaunchPackAnswerRows(reinterpret_cast<const PackPair *>(_dAqs + 2), m, (int64_t)(slotBytes / 2), reinterpret_cast<unsigned *>(_dAqs),
-                               static_cast<uint64_t *>(pFlag), flagValue, _stream));
-  _packCalls++;
-  _packBytes += (uint64_t)m * slotBytes;
   return Error();
 }
 

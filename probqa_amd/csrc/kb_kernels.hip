@@ -320,6 +320,58 @@ __global__ __launch_bounds__(256) void pack_answer_rows_kernel(const PackPair *_
   __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// PqaHip_PackQuestionBlocks / PqaEngine_CompactFromBlocks: whole question blocks between a cube and a block package, whose row pitches
+// differ (the cube's ldT only ever grows; a package's pitch is that of the current T).  Workgroup (block, row, chunk) moves
+// kPackChunkBytes of one row as 16-byte units, all of a thread's loads requested before its first store; rows start on 128-byte lines on
+// both sides, so every unit is aligned.  A row is rowWords 4-byte words (elements are 4 or 8 bytes): its last unit may be partial.
+// kZeroTail (packing): the partial unit's other words and every unit behind it up to the destination's pitch are stored as zeros, so a
+// slot is a function of the row's T elements alone.  Otherwise (unpacking into a cube) the partial unit goes word by word and nothing
+// behind it is written: the cube's columns from T on stay as they are.  The flag protocol is pack_answer_rows_kernel's.
+template <bool kZeroTail>
+__global__ __launch_bounds__(256) void copy_question_blocks_kernel(const BlockCopy *__restrict__ blocks, int64_t nWork, int64_t rows, int64_t rowWords,
+                                                                   int64_t srcPitchUnits, int64_t dstPitchUnits, int64_t chunksPerRow, unsigned *counter,
+                                                                   uint64_t *flag, uint64_t flagValue) {
+  constexpr int kPer = (int)(kPackChunkBytes / 16 / 256);
+  if ((int64_t)blockIdx.x < nWork) {
+    const int64_t rowIndex = blockIdx.x / chunksPerRow, chunk = blockIdx.x % chunksPerRow;
+    const BlockCopy b = blocks[rowIndex / rows];
+    const int64_t r = rowIndex % rows;
+    const uint4 *src = static_cast<const uint4 *>(b.src) + r * srcPitchUnits;
+    uint4 *dst = static_cast<uint4 *>(b.dst) + r * dstPitchUnits;
+    const int64_t fullUnits = rowWords >> 2;
+    const int tailWords = (int)(rowWords & 3);
+    const int64_t dataUnits = fullUnits + (tailWords != 0 ? 1 : 0), dstUnits = kZeroTail ? dstPitchUnits : dataUnits;
+    const int64_t u0 = chunk * (kPer * 256) + threadIdx.x;
+    uint4 v[kPer];
+#pragma unroll
+    for (int e = 0; e < kPer; e++) {
+      const int64_t u = u0 + e * 256;
+      v[e] = u < dataUnits ? src[u] : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < kPer; e++) {
+      const int64_t u = u0 + e * 256;
+      if (u >= dstUnits) continue;
+      if (u != fullUnits || tailWords == 0) { dst[u] = v[e]; continue; }
+      if constexpr (kZeroTail) {
+        dst[u] = make_uint4(v[e].x, tailWords > 1 ? v[e].y : 0u, tailWords > 2 ? v[e].z : 0u, 0u);
+      } else {
+        uint32_t *w = reinterpret_cast<uint32_t *>(dst + u);
+        w[0] = v[e].x;
+        if (tailWords > 1) w[1] = v[e].y;
+        if (tailWords > 2) w[2] = v[e].z;
+      }
+    }
+  }
+  if (flag == nullptr) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: this thread's part of the blocks before the count
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) != gridDim.x - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ---- .kb rows between the file's dense layout in one number type and the cube's padded layout in another -------------------------------
 // A thread moves four consecutive elements of one row, columns [4 g, 4 g + 4): on the cube's side that is a 16-byte aligned unit of a
 // Float row (two of a Double row), whatever the row -- rows start on 128-byte lines.  The dense side is only element-aligned: row r
@@ -438,6 +490,26 @@ hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowByt
   if (nWork > 0x7fffffff) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pack_answer_rows_kernel, dim3((unsigned)std::max<int64_t>(nWork, 1)), dim3(256), 0, stream, pairs, nWork, rowUnits, chunksPerRow,
                      counter, flag, flagValue);
+  return hipGetLastError();
+}
+
+hipError_t LaunchCopyQuestionBlocks(const BlockCopy *blocks, int64_t n, int64_t rows, int64_t rowWords, int64_t srcPitchBytes, int64_t dstPitchBytes,
+                                    bool zeroTail, unsigned *counter, uint64_t *flag, uint64_t flagValue, hipStream_t stream) {
+  const int64_t dataBytes = (rowWords + 3) / 4 * 16;   // the row, rounded up to the unit
+  if (n < 0 || rows < 1 || rowWords < 1 || srcPitchBytes % 16 != 0 || dstPitchBytes % 16 != 0 || srcPitchBytes < dataBytes || dstPitchBytes < dataBytes ||
+      (n > 0 && blocks == nullptr) || (flag != nullptr && counter == nullptr))
+    return hipErrorInvalidValue;
+  if (n == 0 && flag == nullptr) return hipSuccess;
+  const int64_t dstBytes = zeroTail ? dstPitchBytes : dataBytes, chunksPerRow = (dstBytes + kPackChunkBytes - 1) / kPackChunkBytes;
+  if (n > 0x7fffffff / (rows * chunksPerRow)) return hipErrorInvalidValue;
+  const int64_t nWork = n * rows * chunksPerRow;
+  const dim3 grid((unsigned)std::max<int64_t>(nWork, 1));
+  if (zeroTail)
+    hipLaunchKernelGGL(copy_question_blocks_kernel<true>, grid, dim3(256), 0, stream, blocks, nWork, rows, rowWords, srcPitchBytes / 16, dstPitchBytes / 16,
+                       chunksPerRow, counter, flag, flagValue);
+  else
+    hipLaunchKernelGGL(copy_question_blocks_kernel<false>, grid, dim3(256), 0, stream, blocks, nWork, rows, rowWords, srcPitchBytes / 16, dstPitchBytes / 16,
+                       chunksPerRow, counter, flag, flagValue);
   return hipGetLastError();
 }
 

@@ -74,6 +74,34 @@ inline CompactPlan PlanCompact(const std::vector<int64_t> &qGapList, const std::
   return p;
 }
 
+// Compact on shards that separate processes drive (hip_engine_kb.cpp: CompactFromBlocks): the plan is PlanCompact over the GLOBAL
+// axis; no question changes its shard's range by being kept, so a shard that held [qFirst, qFirst + nLocal) keeps the part of it below
+// the new question count nQ -- possibly nothing, which refuses the compaction.  bounds: the shards' upper bounds, ascending.
+inline int64_t ClippedQuestions(int64_t qFirst, int64_t nLocal, int64_t nQ) { return std::max<int64_t>(0, std::min(qFirst + nLocal, nQ) - qFirst); }
+inline int64_t OwnerIn(const std::vector<int64_t> &bounds, int64_t q) {   // the shard whose range holds q; bounds.size() if none does
+  return (int64_t)(std::upper_bound(bounds.begin(), bounds.end(), q) - bounds.begin());
+}
+struct ShardCompactPlan {
+  bool refused = false;                    // a shard would be left without a question
+  std::vector<int64_t> newBounds;          // every bound clipped to the new question count (also when refused)
+  std::vector<int64_t> moves;              // per question move of the plan: dst, src, the shard that holds dst, the shard that holds src
+};
+inline ShardCompactPlan PlanShardCompact(const std::vector<int64_t> &bounds, const CompactPlan &plan) {
+  ShardCompactPlan s;
+  const int64_t nQ = (int64_t)plan.oldQ.size();
+  for (size_t r = 0; r < bounds.size(); r++) {
+    const int64_t first = r == 0 ? 0 : bounds[r - 1];
+    const int64_t kept = ClippedQuestions(first, bounds[r] - first, nQ);
+    s.refused = s.refused || kept == 0;
+    s.newBounds.push_back(std::min(bounds[r], nQ));
+  }
+  for (const auto &mv : plan.qMoves) {
+    s.moves.push_back(mv.first); s.moves.push_back(mv.second);
+    s.moves.push_back(OwnerIn(bounds, mv.first)); s.moves.push_back(OwnerIn(bounds, mv.second));
+  }
+  return s;
+}
+
 // RemoveQuestions / RemoveTargets: every id is validated -- range, gaps, repeats within the call -- before the first one is
 // removed.  The position of the first id that cannot be removed, -1 if the call is valid.
 template <typename IsGap>

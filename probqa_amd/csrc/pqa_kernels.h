@@ -533,6 +533,15 @@ struct PackPair { const void *rowA, *rowD; void *dst; };
 constexpr int64_t kPackChunkBytes = 16384;
 hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowBytes, unsigned *counter, uint64_t *flag, uint64_t flagValue,
                                 hipStream_t stream);
+// Whole question blocks between a cube and a BLOCK PACKAGE (PqaHip_PackQuestionBlocks, PqaEngine_CompactFromBlocks): block i of
+// `blocks` (device memory) is `rows` (K + 1) rows of rowWords 4-byte words -- T elements -- that lie srcPitchBytes apart at src and
+// dstPitchBytes apart at dst; both pitches are multiples of 128, every block starts on a 128-byte line, and a pitch holds the row
+// rounded up to 16 bytes.  zeroTail (packing): the rest of every dst row, up to its pitch, is zero-filled; otherwise (unpacking into a
+// cube) nothing behind the row's last word is written.  One launch: a workgroup per (block, row, chunk of kPackChunkBytes), 16-byte
+// accesses except the words of a row's last, partial unit.  counter / flag / flagValue as LaunchPackAnswerRows.
+struct BlockCopy { const void *src; void *dst; };
+hipError_t LaunchCopyQuestionBlocks(const BlockCopy *blocks, int64_t n, int64_t rows, int64_t rowWords, int64_t srcPitchBytes, int64_t dstPitchBytes,
+                                    bool zeroTail, unsigned *counter, uint64_t *flag, uint64_t flagValue, hipStream_t stream);
 // Rows between a .kb file's dense layout in one number type and the cube's padded layout in another (kb_kernels.hip:
 // convert_rows_kernel).  `dense`: nRows rows of T elements back to back, denseElem (4 | 8) bytes each, only element-aligned.
 // `cube`: the first row's question block; dense row r is the cube's row (r / rowsPerQ) * qStride + r % rowsPerQ + rowBase, rows ldT

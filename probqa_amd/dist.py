@@ -530,6 +530,141 @@ def save_kb(engine, path: str, rank: int, world: int, group: Optional[dist.Proce
     raise interop.PqaException("rank %d: %s" % (first, text[0]))
 
 
+# ---- changing the KB in the process-per-GPU form -----------------------------------------------------------------------------------
+# Maintenance on shards that separate processes drive is COLLECTIVE AND REPLICATED (include/PqaHipExt.h): every rank makes the same
+# call with the same arguments, each shard keeps the bookkeeping of the whole question axis and changes the rows it holds.  Appended
+# questions go to the shard whose range ends at the question count, and a compaction clips the ranges to the new count -- so once
+# maintenance has run, the ranges are no longer shard_bounds' even split: a host loop asks gather_bounds once after every maintenance
+# call that changes the question count and uses owner_in, not shard_bounds / owner_of / row_owners.  (Rebalancing is save_kb followed by
+# load_shard.)  Only compact moves data between ranks.  Nothing here has been timed on a GPU.
+
+
+def gather_bounds(engine, group: Optional[dist.ProcessGroup] = None) -> List[int]:
+    """End bound of each rank's question range as the engines hold them now: an all_gather of (q_first, local question count)."""
+    mine = [engine.get_option("q_first"), engine.get_option("local_questions")]
+    if not (dist.is_initialized() and dist.get_world_size(group) > 1):
+        return [mine[0] + mine[1]]
+    word = torch.tensor(mine, dtype=torch.int64)
+    if dist.get_backend(group) == "nccl":
+        word = word.cuda()
+    parts = [torch.empty_like(word) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(parts, word, group=group)
+    return [int(p[0]) + int(p[1]) for p in (x.cpu() for x in parts)]
+
+
+def owner_in(bounds: List[int], question: int) -> int:
+    """The rank whose range holds the question, under bounds as gather_bounds returns them.  IndexError outside [0, bounds[-1])."""
+    import bisect
+
+    if question < 0 or question >= bounds[-1]:
+        raise IndexError(question)
+    return bisect.bisect_right(bounds, question)
+
+
+def _replicated(call, rank: int, world: int, group, device: Optional[torch.device]):
+    """One replicated maintenance call and a status word: if any rank failed, every rank raises the first failure.  (The calls
+    validate against state every rank holds alike, so they fail on all ranks or on none; what can fail on one rank alone is its
+    device's memory, and that rank's engine is unchanged then.)"""
+    from . import interop
+
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    result, error = None, None
+    try:
+        result = call()
+    except interop.PqaException as e:
+        error = str(e)
+    _settle(None, [], error, rank, world, device, group)
+    return result
+
+
+def remove_questions(engine, question_ids, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                     device: Optional[torch.device] = None) -> None:
+    """RemoveQuestions (GLOBAL ids) on the shards of `world` ranks: a collective every rank calls with the same ids."""
+    _replicated(lambda: engine.remove_questions(list(question_ids)), rank, world, group, device)
+
+
+def remove_targets(engine, target_ids, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                   device: Optional[torch.device] = None) -> None:
+    """RemoveTargets on the shards of `world` ranks: a collective every rank calls with the same ids."""
+    _replicated(lambda: engine.remove_targets(list(target_ids)), rank, world, group, device)
+
+
+def add_qs_ts(engine, add_questions, add_targets, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+              device: Optional[torch.device] = None) -> None:
+    """AddQsTs on the shards of `world` ranks: a collective every rank calls with the same parameters; their i_question / i_target
+    receive the GLOBAL ids, the same on every rank.  Appended questions land on the last rank: see gather_bounds."""
+    _replicated(lambda: engine.add_qs_ts(add_questions, add_targets), rank, world, group, device)
+
+
+def compact(engine, rank: int, world: int, group: Optional[dist.ProcessGroup] = None, device: Optional[torch.device] = None):
+    """Compact on the shards of `world` ranks: a collective every rank calls.  Returns (old_q, old_t), the global maps, the same on
+    every rank.
+
+    Every rank plans (host only); one all_reduce(MIN) votes on errors and on whether any shard would be left without a question --
+    then every rank raises the same InsufficientEngineDimensions and nothing has changed; the owners pack the questions that move
+    into a zero-filled tensor on the device; ONE all_reduce(SUM) in the engine's element type combines the packages -- exact, and a
+    move of bits, for the reason resume_quiz's is: every slot is written by exactly one rank and x + 0 == x --, under gloo through
+    the host; every rank compacts from the combined package; one status word.  A shard keeps the part of its range below the new
+    question count: see gather_bounds."""
+    from . import interop
+
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    multi = dist.is_initialized() and dist.get_world_size(group) > 1
+    on_gpu = device.type == "cuda"
+    on_dev = on_gpu and multi and dist.get_backend(group) == "nccl"
+    plan, error = None, None
+    try:
+        plan = engine.compact_plan()
+    except interop.PqaException as e:
+        error = str(e)
+    # the vote: 2 * rank for an error, 2 * rank + 1 for a shard that would be emptied, 2 * world for neither
+    mine = 2 * rank if error is not None else 2 * rank + 1 if plan[3] else 2 * world
+    if multi:
+        word = torch.tensor([mine], dtype=torch.int64, device=device if on_dev else "cpu")
+        dist.all_reduce(word, op=dist.ReduceOp.MIN, group=group)
+        mine = int(word.item())
+    if mine < 2 * world:
+        first = mine // 2
+        if mine % 2:
+            engine.compact_from_blocks(0, 0, first)      # (refused, with the text every rank gets: nothing has changed)
+            raise AssertionError("a compaction that empties rank %d was not refused" % first)
+        text = [error if rank == first else None]
+        if multi:
+            dist.broadcast_object_list(text, src=dist.get_global_rank(group, first) if group is not None else first, group=group,
+                                       device=device if on_dev else None)
+        raise interop.PqaException("rank %d: %s" % (first, text[0]))
+    moves = plan[2]
+    slot = engine.question_block_slot_bytes()
+    pkg = None
+    if moves:
+        elem = 4 if engine.get_option("precision") == 1 else 8
+        pkg = torch.zeros(len(moves), slot // elem, dtype=torch.float32 if elem == 4 else torch.float64, device=device)
+        if on_gpu:
+            torch.cuda.current_stream(device).synchronize()   # the zeros are there before the engine's stream writes among them
+        try:
+            engine.pack_question_blocks([src for _, src in moves], pkg.data_ptr())
+        except interop.PqaException as e:                     # (still takes part in the collective: the status word fails the call)
+            error = str(e)
+        engine.synchronize()
+        if multi:
+            if on_gpu and not on_dev:                         # gloo: through the host
+                host = pkg.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+                pkg.copy_(host)
+            else:
+                dist.all_reduce(pkg, op=dist.ReduceOp.SUM, group=group)
+            if on_gpu:
+                torch.cuda.current_stream(device).synchronize()
+    result = None
+    if error is None:
+        try:
+            result = engine.compact_from_blocks(pkg.data_ptr() if pkg is not None else 0, slot if pkg is not None else 0, -1)
+        except interop.PqaException as e:
+            error = str(e)
+    _settle(None, [], error, rank, world, device, group)
+    return result
+
+
 class ShmRowExchange:
     """resume_quiz / resume_quiz_batch without a process group, for the shared-memory deployments that use ShmSelector: the
     package lives in ONE /dev/shm segment every rank has mapped and registered with its GPU.  The owners pack straight into it

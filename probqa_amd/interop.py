@@ -169,6 +169,10 @@ HIP_EXPORTS = {
     "PqaEngineFactory_LoadHipEngineAs": (_vp, [_vp, _pvp, ctypes.c_char_p, _u8, ctypes.POINTER(CiHipShard), _i64]),
     "PqaHip_SaveKBAs": (_vp, [_vp, ctypes.c_char_p, _u8]),
     "PqaHip_SaveKBShard": (_vp, [_vp, ctypes.c_char_p, _u8]),
+    "PqaHip_CompactPlan": (_vp, [_vp, _pi64, _pi64, _pi64, ctypes.POINTER(_pi64), ctypes.POINTER(_u8)]),
+    "PqaHip_QuestionBlockSlotBytes": (_i64, [_vp]),
+    "PqaHip_PackQuestionBlocks": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
+    "PqaEngine_CompactFromBlocks": (_vp, [_vp, _vp, _i64, _i64, _pi64, ctypes.POINTER(_pi64), _pi64, ctypes.POINTER(_pi64)]),
 }
 
 _lib = None
@@ -573,6 +577,43 @@ class PqaEngine:
         p_q, p_t = _pi64(), _pi64()
         _check(_lib.PqaEngine_Compact(self.c_engine, ctypes.byref(n_q), ctypes.byref(p_q), ctypes.byref(n_t),
                                       ctypes.byref(p_t)))
+        try:
+            return [p_q[i] for i in range(n_q.value)], [p_t[i] for i in range(n_t.value)]
+        finally:
+            _lib.CiReleaseCompaction(p_q)
+            _lib.CiReleaseCompaction(p_t)
+
+    # ---- Compact on a shard that a process of its own drives (include/PqaHipExt.h; probqa_amd/dist.py: compact) ------------------------
+    def compact_plan(self) -> Tuple[int, int, List[Tuple[int, int]], bool]:
+        """What a compaction would do, on the host alone: (questions afterwards, targets afterwards, the whole-question moves as
+        (dst, src) pairs of GLOBAL ids, whether THIS shard would be left without a question)."""
+        n_q, n_t, n_m, empty = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_uint8()
+        p_m = _pi64()
+        _check(_lib.PqaHip_CompactPlan(self.c_engine, ctypes.byref(n_q), ctypes.byref(n_t), ctypes.byref(n_m), ctypes.byref(p_m),
+                                       ctypes.byref(empty)))
+        try:
+            return n_q.value, n_t.value, [(p_m[2 * i], p_m[2 * i + 1]) for i in range(n_m.value)], bool(empty.value)
+        finally:
+            _lib.CiReleaseCompaction(p_m)
+
+    def question_block_slot_bytes(self) -> int:
+        """Bytes of one slot of a block package: the K + 1 rows of a question at the pitch of the current number of targets."""
+        return _lib.PqaHip_QuestionBlockSlotBytes(self.c_engine)
+
+    def pack_question_blocks(self, questions: List[int], dst: int, flag: int = 0, flag_value: int = 0) -> None:
+        """Enqueue (no synchronisation) the copy of those of the questions (GLOBAL ids) this engine holds into their slots of the
+        package at device-visible address `dst`; `flag` (an address, 0 = none) receives `flag_value` once they are visible."""
+        arr = (ctypes.c_int64 * max(len(questions), 1))(*questions)
+        _check(_lib.PqaHip_PackQuestionBlocks(self.c_engine, len(questions), arr, ctypes.c_void_p(dst or None), ctypes.c_void_p(flag or None),
+                                              flag_value))
+
+    def compact_from_blocks(self, blocks: int = 0, slot_bytes: int = 0, emptied_rank: int = -1) -> Tuple[List[int], List[int]]:
+        """compact() with the questions that move in from other shards read from the package at device-visible address `blocks` (slot i:
+        the source of move i of compact_plan).  emptied_rank: the ranks' vote (-1: no shard would be left empty)."""
+        n_q, n_t = ctypes.c_int64(), ctypes.c_int64()
+        p_q, p_t = _pi64(), _pi64()
+        _check(_lib.PqaEngine_CompactFromBlocks(self.c_engine, ctypes.c_void_p(blocks or None), slot_bytes, emptied_rank, ctypes.byref(n_q),
+                                                ctypes.byref(p_q), ctypes.byref(n_t), ctypes.byref(p_t)))
         try:
             return [p_q[i] for i in range(n_q.value)], [p_t[i] for i in range(n_t.value)]
         finally:
