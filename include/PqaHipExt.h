@@ -331,6 +331,55 @@ PQACORE_API int64_t PqaEngine_ResumeQuizFromRows(void *pvEngine, void **ppError,
 PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts,
                                                     const CiAnsweredQuestion *pAQs, const void *pRows, int64_t *pQuizzes);
 
+/* ---- The sampled selector (PqaEngine_NextQuestionSampled, the reference's PqaCore/CpuEngine.cpp:362-400) on shards that separate
+ * processes drive.  The selector splits the GLOBAL question axis into eval_subtasks subtasks (CalcSplit) and runs one Kahan chain
+ * per subtask in question order; a shard's range does not end on subtask bounds, and a Kahan chain cannot be cut and re-joined bit
+ * for bit from two totals -- it can be continued by whoever sees the earlier questions' priorities and skip bits.  So every rank
+ * contributes, per quiz, a SELECTION PART (probqa_amd/csrc/sampled_part.h), with (quot, rem, nS) the CalcSplit of q_total over
+ * eval_subtasks (8 x workers if unset), L = quot + (rem > 0) and W = ceil(L / 64):
+ *   header    int64 qFirst, int64 nLocal (the shard's range), int64 nS, uint64 seq (the pack's sequence number on its engine)
+ *   total     nS doubles: the Kahan total of subtask s where s lies whole inside the shard, 0 elsewhere
+ *   2 pieces  each L doubles, then W 64-bit words: the priorities, in question order, and the gap | asked bits (bit j of the words:
+ *             question j of the piece) of the shard's questions of ONE subtask that its bounds cut -- the one cut at the lower bound
+ *             first, then the one cut at the upper bound; both bounds inside one subtask make one piece.  Which pieces a part holds
+ *             follows from its header.  Doubles behind a piece's questions, and an unused piece, are not written.
+ * rounded up to 16 bytes: a function of q_total and eval_subtasks alone, the same on every rank whatever its range.  Nothing of the
+ * size of the question axis crosses between ranks.  The sequence, run by probqa_amd/dist.py (next_question_sampled_batch); a whole
+ * engine is a world of one:
+ *   PqaHip_SampledPartBytes      the size of one part.
+ *   PqaHip_PackSampledParts      stream-ordered, no host synchronisation.  nQuizzes <= 256 distinct quizzes, refused as
+ *                                PqaEngine_EvalPrioritiesBatch refuses them.  Runs the batched sweep that call would run (whichever
+ *                                form option batch_form gives, the pole fix behind it) and ONE launch that writes part i to
+ *                                pDst + i * partBytes.  pDst, pFlag, flagValue as PqaHip_PackAnswerRows.  The run lengths of the
+ *                                shard's whole subtasks stay in engine scratch, stamped with the header's sequence number.
+ *   (all-gather the parts: world x nQuizzes of them, rank-major)
+ *   PqaHip_SampledPickFromParts  pParts: the gathered parts, device-visible.  ONE launch: per quiz every whole subtask's total from
+ *                                the rank whose range contains it, every cut subtask's by continuing one Kahan chain through the
+ *                                ranks' pieces in rank order, then the selector's own finish -- the Kahan grand totals in subtask
+ *                                order, selRunLen = total * (double)rnd / 18446744073709551615.0, the upper_bound, the n - 1 clamp,
+ *                                the second upper_bound: the operations of the whole engine's selector on the same values, so the
+ *                                same bits.  pOut[i] = {grand total, the GLOBAL pick}; -1 in place of the pick where the chosen
+ *                                subtask lies whole on ANOTHER rank (that rank reports it; a cut subtask's pick is reported by every
+ *                                rank).  pRnd must be the same on every rank.  WrongMode if the part of `rank` does not carry the
+ *                                sequence number of this engine's latest pack -- or that pack was for another batch, or a quiz of
+ *                                it has recorded an answer since -- or if the headers' ranges do not tile [0, q_total).  No
+ *                                bookkeeping, no change of quiz state; world <= 64.  The parts are a snapshot of the cube, as a row
+ *                                package is: no rank may train between pack and pick.
+ *   (all-gather the picks; per quiz the one value that is not -1)
+ *   PqaEngine_TakeSampledPicks   host only.  pPicks[i]: the agreed GLOBAL pick.  A pick that is a gap or was asked falls back to
+ *                                the reference's FindNearestQuestion over the WHOLE question axis -- every rank keeps the axis'
+ *                                gap list and a quiz's answered questions, other ranks' among them, so every rank arrives at the
+ *                                same question; then the quiz's active question is set and one question asked is counted per
+ *                                quiz, on every rank.  pQuestions[i] = -1, and no error, for a quiz with no question left.
+ * Timed only with the shards side by side on one device (tools/sampled_ranks_bench.py, profiles/README.md), not over a process group. */
+PQACORE_API int64_t PqaHip_SampledPartBytes(void *pvEngine);
+PQACORE_API void *PqaHip_PackSampledParts(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, void *pDst, void *pFlag,
+                                          const uint64_t flagValue);
+PQACORE_API void *PqaHip_SampledPickFromParts(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const uint64_t *pRnd,
+                                              const void *pParts, const int64_t rank, const int64_t world, CiHipSelection *pOut);
+PQACORE_API void *PqaEngine_TakeSampledPicks(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pPicks,
+                                             int64_t *pQuestions);
+
 /* ---- Maintenance on shards that separate processes drive.  PqaEngine_AddQsTs, PqaEngine_RemoveQuestions and PqaEngine_RemoveTargets
  * are COLLECTIVE AND REPLICATED on such shards: every rank makes the same call with the same arguments (as every rank sees every
  * PqaEngine_Train), in maintenance mode.  Each shard keeps the bookkeeping of the whole question axis -- the gap list in the
@@ -394,6 +443,9 @@ PQACORE_API void *PqaEngine_CompactFromBlocks(void *pvEngine, const void *pBlock
    what = "merge_top": pIn = {maxCount, nLists, then per list n and n x {priority bits, index}}; pOut = {n, then n x {priority bits,
    index}}: the best maxCount of the shards' PqaEngine_ListTopQuestions lists under the listings' order (descending priority, ascending
    index among equal priorities; a priority that is not > 0 -- a NaN among them -- or a negative index is no candidate).
+   what = "sampled_part": pIn = {Q, nSub, qFirst, n}: a shard [qFirst, qFirst + n) of Q questions under nSub subtasks; pOut = {the
+   bytes of a selection part, the first subtask that lies whole in the shard, how many do, piece 0's subtask (-1: none) and its
+   length, piece 1's subtask and length} (probqa_amd/csrc/sampled_part.h).
    Returns the number of results written, or -1 for a malformed script / too small an output. */
 PQACORE_API int64_t PqaHip_HostLogicProbe(const char *what, const int64_t *pIn, const int64_t nIn, int64_t *pOut, const int64_t nOut);
 

@@ -20,6 +20,7 @@
 
 #include "c_abi_shims.h"
 #include "hip_engine.h"
+#include "sampled_part.h"
 
 using pqa::AQ;
 using pqa::ErrCode;
@@ -429,6 +430,23 @@ PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_
                                                     const void *pRows, int64_t *pQuizzes) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ResumeQuizBatchFromRows(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pRows, pQuizzes); });
 }
+// ---- the sampled selector on shards driven by processes of their own: every rank packs a selection part per quiz, picks from the
+// gathered parts of all ranks and takes the agreed pick (hip_engine_parts.cpp)
+PQACORE_API int64_t PqaHip_SampledPartBytes(void *pvEngine) {
+  return LoggedOf<int64_t>(pvEngine, -1, [&](IEngine &e) { return e.SampledPartBytes(); });
+}
+PQACORE_API void *PqaHip_PackSampledParts(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, void *pDst, void *pFlag,
+                                          const uint64_t flagValue) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackSampledParts(nQuizzes, pQuizzes, pDst, pFlag, flagValue); });
+}
+PQACORE_API void *PqaHip_SampledPickFromParts(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const uint64_t *pRnd,
+                                              const void *pParts, const int64_t rank, const int64_t world, CiHipSelection *pOut) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SampledPickFromParts(nQuizzes, pQuizzes, pRnd, pParts, rank, world, pOut); });
+}
+PQACORE_API void *PqaEngine_TakeSampledPicks(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pPicks,
+                                             int64_t *pQuestions) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.TakeSampledPicks(nQuizzes, pQuizzes, pPicks, pQuestions); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {
@@ -682,6 +700,14 @@ static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_
                             window ? pIn[5] * lay.rowBytes : -1, lay.valid ? lay.vbOff : -1, lay.valid ? lay.trailerOff : -1};
     std::copy(row, row + 8, pOut);
     return 8;
+  }
+  if (w == "sampled_part") {   // {Q, nSub, qFirst, n} -> {bytes, first whole subtask, their count, piece 0's subtask (-1: none) and length, piece 1's}
+    if (nIn != 4 || nOut < 7 || pIn[0] < 1 || pIn[1] < 1 || pIn[2] < 0 || pIn[3] < 1 || pIn[3] > pIn[0] - pIn[2]) return -1;
+    const pqa::SampledSplit sp = pqa::sampled_split(pIn[0], pIn[1]);
+    const pqa::SampledPartShape sh = pqa::sampled_part_shape(sp, pIn[2], pIn[3]);
+    const int64_t row[7] = {pqa::sampled_part_bytes(sp), sh.firstWhole, sh.nWhole, sh.p0Sub, sh.p0Len, sh.p1Sub, sh.p1Len};
+    std::copy(row, row + 7, pOut);
+    return 7;
   }
   if (w == "let_go") {
     if (nIn < 4 || pIn[3] < 0 || nIn != 4 + 2 * pIn[3]) return -1;

@@ -120,8 +120,19 @@ class IEngine {
                                   const int64_t **ppOldTargets) {
     return pBlocks ? NoBlocks("CompactFromBlocks with a package") : Compact(pnQuestions, ppOldQuestions, pnTargets, ppOldTargets);
   }
+  // The sampled selector across shards that separate processes drive (sampled_part.h): selection parts.  The one-process sharded
+  // engine selects over its shards itself.
+  virtual int64_t SampledPartBytes() const { return -1; }
+  virtual Error PackSampledParts(int64_t, const int64_t *, void *, void *, uint64_t) { return NoParts("PackSampledParts"); }
+  virtual Error SampledPickFromParts(int64_t, const int64_t *, const uint64_t *, const void *, int64_t, int64_t, CiHipSelection *) {
+    return NoParts("SampledPickFromParts");
+  }
+  virtual Error TakeSampledPicks(int64_t, const int64_t *, const int64_t *, int64_t *) { return NoParts("TakeSampledPicks"); }
 
  private:
+  static Error NoParts(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine", "Selection parts are for shards that separate processes drive.");
+  }
   static Error NoBlocks(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine", "Question block packages are for shards that separate processes drive.");
   }

@@ -268,6 +268,7 @@ HipEngine::~HipEngine() {
   if (_hTopQ) hipHostFree(_hTopQ);
   hipFree(_dTopExact);
   hipFree(_dRowStage);
+  hipFree(_dPartsWords); hipFree(_dPartsRun); hipFree(_dPartsGrand); hipFree(_dPartsPickRun);
   if (_hPack) hipHostFree(_hPack);
   if (_evPack) hipEventDestroy(_evPack);
   if (_evSweep[0]) { hipEventDestroy(_evSweep[0]); hipEventDestroy(_evSweep[1]); }

@@ -252,6 +252,14 @@ class HipEngine : public IEngine {
   Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) override;
   int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) override;
   Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) override;
+  // ---- the sampled selector across such shards (hip_engine_parts.cpp; layout: sampled_part.h): every rank packs a SELECTION PART per quiz
+  // behind its batched sweep, the ranks all-gather the parts, every rank picks from all of them, the ranks agree on the one pick
+  // that is not -1, and every rank takes it -- the fallback over the whole question axis, the active question, the count
+  int64_t SampledPartBytes() const override;
+  Error PackSampledParts(int64_t n, const int64_t *pQuizzes, void *pDst, void *pFlag, uint64_t flagValue) override;
+  Error SampledPickFromParts(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, const void *pParts, int64_t rank, int64_t world,
+                             CiHipSelection *pOut) override;
+  Error TakeSampledPicks(int64_t n, const int64_t *pQuizzes, const int64_t *pPicks, int64_t *pQuestions) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
   // An answer of a quiz as the sharded engine hands it to EVERY shard: the answered question in global numbering; for the shards
@@ -631,6 +639,19 @@ class HipEngine : public IEngine {
   Error ValidateBatchLocked(int64_t n, const int64_t *pQuizzes);
   Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
   Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
+  // The engine's latest pack of selection parts: what a pick must find unchanged -- the quizzes and their posteriors, the split, this
+  // shard's range -- and where the pack kernel left the run lengths of the shard's whole subtasks.
+  struct PartsPack {
+    uint64_t seq = 0;                         // 0: nothing packed yet
+    std::vector<int64_t> quizzes;
+    std::vector<uint64_t> serials, versions;
+    int64_t nSub = 0, qFirst = 0, nLocal = 0, qTotal = 0, runQuiz = 0, runStride = 0;
+    uint64_t kbVersion = 0;
+  } _parts;
+  int64_t SampledSubtasks() const { return _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers; }   // reference PqaCore/CpuEngine.cpp:339
+  uint64_t *_dPartsWords = nullptr;           // {arrival counter, pad}, then a stamp per quiz of a batch
+  double *_dPartsRun = nullptr, *_dPartsGrand = nullptr, *_dPartsPickRun = nullptr;
+  size_t _partsRunBytes = 0, _partsGrandBytes = 0, _partsPickRunBytes = 0;
   uint64_t _sampledBatches = 0, _sampledBatchDeviceNs = 0;   // read-only "sampled_batches", "sampled_batch_device_ns" (the selector's launches between events)
   uint64_t _priorityHostBytes = 0;     // read-only "priority_host_bytes": priorities the batched sweeps delivered to the host
   Error WaitBatchFlags(BatchCtx &c, int64_t n, uint64_t tag);

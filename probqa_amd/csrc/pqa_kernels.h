@@ -399,6 +399,48 @@ struct SampledBatch {
 };
 void SelectSampledBatchScratch(int64_t n, int64_t nSubtasks, int nSlots, int Bp, size_t *grandDoubles, size_t *runDoubles);
 hipError_t LaunchSelectSampledBatch(const SampledBatch &a, hipStream_t stream);
+// The same selection over shards that separate processes drive, in two launches with an exchange between them (sampled_part.h has
+// the layout).  LaunchSampledPackParts, behind a batched sweep on its stream: quiz b's part goes to dst + b * partBytes (any
+// device-visible, 16-byte aligned address), the run lengths of the shard's whole subtasks to `run` -- run[j * Bq + b] beside the
+// quiz-minor matrix (Bq = its Bp), run[b * nLocal + j] beside the quizzes' own vectors (Bq = the quiz count rounded up to a wave) --
+// and seq to stamp[b] as to the part's header; flag (optional): flagValue once every part is visible system-wide (counter: a zeroed
+// word in device memory).
+struct SampledPartsPack {
+  const QuizSlot *slots;          // device array
+  int nSlots, Bq;
+  const double *priorityT;        // the matrix, or nullptr: slots[b].priority
+  const uint32_t *qgap;           // over LOCAL questions, as slots[b].asked
+  int64_t qFirst, nLocal, qTotal, nWorkers;
+  char *dst;
+  int64_t partBytes;
+  double *run;
+  uint64_t *stamp;
+  uint64_t seq;
+  unsigned *counter;
+  uint64_t *flag;
+  uint64_t flagValue;
+};
+hipError_t LaunchSampledPackParts(const SampledPartsPack &a, hipStream_t stream);
+// LaunchSampledPickParts: parts = world x nSlots parts, rank-major.  Quiz b's {grand total, GLOBAL pick or -1 (the chosen subtask lies
+// whole on another rank)} goes to out[b] and then flagValue to seq[b] (host-coherent, as rnd).  Index -2: the part of `rank` or the
+// saved run lengths do not carry `seq`; -3: the headers' ranges do not tile [0, qTotal) or name another subtask count.
+// grand: nSlots x nS doubles, run: nSlots x L doubles of device scratch.
+constexpr int kSampledMaxWorld = 64;
+struct SampledPartsPick {
+  int nSlots, world, rank;
+  const char *parts;
+  int64_t partBytes, qTotal, nWorkers;
+  const uint64_t *rnd;
+  const double *packRun;
+  int64_t packRunQuiz, packRunStride;   // quiz b's run length j of this rank's questions: packRun[b * packRunQuiz + j * packRunStride]
+  const uint64_t *stamp;
+  uint64_t seq;
+  double *grand, *run;
+  SelectResult *out;
+  uint64_t *flags;
+  uint64_t flagValue;
+};
+hipError_t LaunchSampledPickParts(const SampledPartsPick &a, hipStream_t stream);
 
 // ---- prior updates (single workgroup, O(T)); nWorkers = emulated CPU worker count that fixes the summation order.
 // The subtasks' partial sums live in (8 nWorkers + 1) doubles of LDS, within the 64 KiB a launch gets without opting in.

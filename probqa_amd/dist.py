@@ -467,6 +467,114 @@ def resume_quiz_batch(engine, lists, rank: int, world: int, group: Optional[dist
     return quizzes
 
 
+# ---- the sampled selector in the process-per-GPU form ----------------------------------------------------------------------
+# The reference's selector (PqaEngine_NextQuestionSampled) splits the GLOBAL question axis into subtasks and runs one Kahan chain per
+# subtask; a shard holds a stretch of the axis.  Every rank packs a SELECTION PART per quiz (PqaHip_PackSampledParts: the totals of the
+# subtasks that lie whole inside its range, the raw priorities of the at most two its bounds cut), the parts are all-gathered, every
+# rank picks from all of them (PqaHip_SampledPickFromParts: a cut subtask's chain is continued through the ranks' pieces in rank
+# order, so every rank arrives at the whole engine's bits), the picks are all-gathered -- 8 bytes per quiz and rank; a rank reports -1
+# where the chosen subtask lies whole on another rank -- and every rank takes the one pick that is not -1
+# (PqaEngine_TakeSampledPicks).  Nothing of the size of the question axis crosses between ranks.  Over a
+# process group nothing here has been timed (tools/sampled_ranks_bench.py times the engine calls with the shards on one device).
+
+
+def broadcast_rnds(rnds, group: Optional[dist.ProcessGroup] = None) -> List[int]:
+    """The selector's random numbers (one unsigned 64-bit number per quiz) as rank 0 has them, on every rank."""
+    rnds = [int(r) for r in rnds]
+    if not (dist.is_initialized() and dist.get_world_size(group) > 1):
+        return rnds
+    words = torch.tensor([r - (1 << 64) if r >= (1 << 63) else r for r in rnds], dtype=torch.int64)   # (the bits, as signed words)
+    if dist.get_backend(group) == "nccl":
+        words = words.cuda()
+    dist.broadcast(words, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    return [w + (1 << 64) if w < 0 else w for w in words.cpu().tolist()]
+
+
+def merge_sampled_picks(picks) -> List[int]:
+    """picks: [world][n] GLOBAL picks of the ranks, -1 where a rank leaves the pick to the rank that holds the chosen subtask.  Per
+    quiz the one value that is not -1; ValueError if two ranks report different ones, or none reports any.  Plain Python."""
+    merged = []
+    for i in range(len(picks[0])):
+        seen = sorted({int(p[i]) for p in picks if int(p[i]) >= 0})
+        if len(seen) != 1:
+            raise ValueError("batch entry %d: the ranks report %s" % (i, "no pick" if not seen else "different picks %s" % seen))
+        merged.append(seen[0])
+    return merged
+
+
+def next_question_sampled_batch(engine, quizzes, rnds, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                                device: Optional[torch.device] = None) -> List[int]:
+    """PqaEngine_NextQuestionSampledBatch on the shards of `world` ranks: a collective every rank calls with the same quizzes and
+    the same random numbers (broadcast_rnds).  Returns the questions, the same on every rank: what the whole engine would select,
+    -1 for a quiz with no question left.  Under an NCCL (RCCL) group the parts and the picks travel on the device, under gloo
+    through the host.  A rank whose engine refuses a step still takes part in both all-gathers, so that the ranks stay in step;
+    the status word that follows fails the call everywhere, and no quiz's active question has changed then."""
+    from . import interop
+
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    quizzes, rnds = list(quizzes), [int(r) for r in rnds]
+    n = len(quizzes)
+    multi = dist.is_initialized() and dist.get_world_size(group) > 1
+    on_gpu = device.type == "cuda"
+    on_dev = on_gpu and multi and dist.get_backend(group) == "nccl"
+    words = max(engine.sampled_part_bytes(), 16) // 8
+    mine = torch.empty(max(n, 1), words, dtype=torch.int64, device=device)
+    error = None
+    try:
+        engine.pack_sampled_parts(quizzes, mine.data_ptr())
+    except interop.PqaException as e:
+        error = str(e)
+    engine.synchronize()                                   # the parts before the collective's stream (or the host) reads them
+    if multi:
+        if on_gpu and not on_dev:                          # gloo: through the host
+            host = [torch.empty(mine.shape, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(host, mine.cpu(), group=group)
+            parts = torch.stack(host).to(device)
+        else:
+            gathered = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(gathered, mine, group=group)
+            parts = torch.stack(gathered)
+        if on_gpu:
+            torch.cuda.current_stream(device).synchronize()
+    else:
+        parts = mine.unsqueeze(0)
+    local = torch.full((n + 1,), -1, dtype=torch.int64)       # the picks, then this rank's status: 0 = no step was refused
+    if error is None:
+        try:
+            picked = engine.sampled_pick_from_parts(quizzes, rnds, parts.data_ptr(), rank, world)
+            local[:n] = torch.from_numpy(picked[:, 1].astype("int64"))
+        except interop.PqaException as e:
+            error = str(e)
+    local[n] = 0 if error is None else 1
+    if multi:
+        if on_dev:
+            local = local.to(device)
+        gathered = [torch.empty_like(local) for _ in range(world)]
+        dist.all_gather(gathered, local, group=group)
+        words = [g.cpu().tolist() for g in gathered]
+    else:
+        words = [local.tolist()]
+    questions = []
+    if all(w[n] == 0 for w in words):                         # (else nobody takes anything: the status word below says who failed)
+        try:
+            questions = engine.take_sampled_picks(quizzes, merge_sampled_picks([w[:n] for w in words]) if n else [])
+        except (interop.PqaException, ValueError) as e:       # (disagreeing picks are the same finding on every rank)
+            error = str(e)
+    _settle(None, [], error, rank, world, device, group)
+    return questions
+
+
+def next_question_sampled(engine, quiz: int, rnd: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                          device: Optional[torch.device] = None) -> int:
+    """PqaEngine_NextQuestionSampled likewise, for one quiz; QuestionsExhausted if it has no question left."""
+    from . import interop
+
+    question = next_question_sampled_batch(engine, [quiz], [rnd], rank, world, group, device)[0]
+    if question < 0:
+        raise interop.PqaException("[Engine has run out of questions] message=[Found no unasked question that is not in a gap.] [nullptr]")   # (QuestionsExhausted, as the engine words it)
+    return question
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

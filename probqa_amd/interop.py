@@ -155,6 +155,10 @@ HIP_EXPORTS = {
     "PqaHip_RecordAnswerRemote": (_vp, [_vp, _i64, _i64]),
     "PqaHip_AnswerRowSlotBytes": (_i64, [_vp]),
     "PqaHip_PackAnswerRows": (_vp, [_vp, _i64, _pAQ, _vp, _vp, ctypes.c_uint64]),
+    "PqaHip_SampledPartBytes": (_i64, [_vp]),
+    "PqaHip_PackSampledParts": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
+    "PqaHip_SampledPickFromParts": (_vp, [_vp, _i64, _pi64, _pu64, _vp, _i64, _i64, ctypes.POINTER(CiHipSelection)]),
+    "PqaEngine_TakeSampledPicks": (_vp, [_vp, _i64, _pi64, _pi64, _pi64]),
     "PqaEngine_ResumeQuizFromRows": (_i64, [_vp, _pvp, _i64, _pAQ, _vp]),
     "PqaEngine_ResumeQuizBatchFromRows": (_vp, [_vp, _i64, _pi64, _pAQ, _vp, _pi64]),
     "PqaEngine_RecordAnswerBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
@@ -830,6 +834,43 @@ class PqaEngine:
         arr, _ = self.to_c_answered_questions([aq for l in lists for aq in l])
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_ResumeQuizBatchFromRows(self.c_engine, n, counts, arr, ctypes.c_void_p(rows or None), out))
+        return list(out[:n])
+
+    # ---- selection parts: the sampled selector on a shard that a process of its own drives (include/PqaHipExt.h) ----------
+    def sampled_part_bytes(self) -> int:
+        """Bytes of one selection part: a function of the whole question count and eval_subtasks alone."""
+        return _lib.PqaHip_SampledPartBytes(self.c_engine)
+
+    def pack_sampled_parts(self, quizzes, dst: int, flag: int = 0, flag_value: int = 0) -> None:
+        """Enqueue (no synchronisation) the batched sweep for these distinct quizzes and the launch that writes part i to
+        dst + i * sampled_part_bytes(), a device-visible 16-byte aligned address; `flag` (an address, 0 = none) receives
+        `flag_value` once the parts are visible."""
+        n = len(quizzes)
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        _check(_lib.PqaHip_PackSampledParts(self.c_engine, n, qs, ctypes.c_void_p(dst or None), ctypes.c_void_p(flag or None), flag_value))
+
+    def sampled_pick_from_parts(self, quizzes, rnds, parts: int, rank: int, world: int) -> np.ndarray:
+        """This rank's picks from the gathered parts (world x len(quizzes), rank-major, at device-visible address `parts`): array
+        [n, 2] of (grand total, GLOBAL question or -1 where the chosen subtask lies whole on another rank)."""
+        n = len(quizzes)
+        if len(rnds) != n:
+            raise ValueError("one random number per quiz")
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        rs = (ctypes.c_uint64 * max(n, 1))(*[int(r) for r in rnds])
+        out = (CiHipSelection * max(n, 1))()
+        _check(_lib.PqaHip_SampledPickFromParts(self.c_engine, n, qs, rs, ctypes.c_void_p(parts or None), rank, world, out))
+        return np.array([(out[i].priority, out[i].iQuestion) for i in range(n)], dtype=np.float64).reshape(n, 2)
+
+    def take_sampled_picks(self, quizzes, picks) -> List[int]:
+        """The agreed GLOBAL picks become the quizzes' active questions (host only): the reference's fallback over the whole
+        question axis for a pick that is a gap or was asked, one question asked counted per quiz; -1 for a quiz with none left."""
+        n = len(quizzes)
+        if len(picks) != n:
+            raise ValueError("one pick per quiz")
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        ps = (ctypes.c_int64 * max(n, 1))(*[int(p) for p in picks])
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_TakeSampledPicks(self.c_engine, n, qs, ps, out))
         return list(out[:n])
 
     def train_batch(self, records, throw: bool = True) -> Optional[PqaError]:
