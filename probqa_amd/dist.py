@@ -85,6 +85,108 @@ def select_batch(local_winners: torch.Tensor, group: Optional[dist.ProcessGroup]
     return pick_batch(torch.stack(parts))
 
 
+# ---- the process group as one collective sees it ----------------------------------------------------------------------------
+# The only place that knows about backends.  A collective's tensors live on the device exactly when the group's backend is "nccl" (RCCL);
+# under gloo a device payload makes the detour through the host.  The ranks stay in step only because every rank issues the same
+# sequence of collectives, a rank whose engine refused a step included: the helpers below never skip one.
+
+
+class _Ranks:
+    """Built from (group, device, rank, world) at the top of a public collective.  `world` and `rank` are the caller's, or the
+    group's where the public function takes none; `device` is the caller's, or the current one where it gives none."""
+
+    def __init__(self, group, device: Optional[torch.device] = None, rank: Optional[int] = None, world: Optional[int] = None):
+        self.group, self._device = group, device
+        size = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.multi = size > 1
+        self.world = size if world is None else world
+        self.rank = rank
+        self.on_dev = self.multi and dist.get_backend(group) == "nccl"
+
+    @property
+    def device(self) -> torch.device:
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        return self._device
+
+    def gather(self, t: torch.Tensor) -> torch.Tensor:
+        """ONE all_gather of t: the ranks' tensors stacked rank-major, on t's device."""
+        if not self.multi:
+            return t.unsqueeze(0)
+        wire = (t.to(self.device) if self.on_dev else t.cpu()).contiguous()
+        parts = [torch.empty_like(wire) for _ in range(self.world)]
+        dist.all_gather(parts, wire, group=self.group)   # (the list form: RCCL and gloo both have it)
+        out = torch.stack(parts).to(t.device)
+        if out.is_cuda:
+            torch.cuda.current_stream(out.device).synchronize()
+        return out
+
+    def sum_(self, t: torch.Tensor) -> torch.Tensor:
+        """ONE all_reduce(SUM) of t, in place."""
+        if self.multi:
+            if t.is_cuda and not self.on_dev:               # gloo: through the host
+                host = t.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group)
+                t.copy_(host)
+            else:
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            if t.is_cuda:
+                torch.cuda.current_stream(t.device).synchronize()
+        return t
+
+    def min_word(self, value: int) -> int:
+        """ONE all_reduce(MIN) of one int64."""
+        if not self.multi:
+            return value
+        word = torch.tensor([value], dtype=torch.int64, device=self.device if self.on_dev else "cpu")
+        dist.all_reduce(word, op=dist.ReduceOp.MIN, group=self.group)
+        return int(word.item())
+
+    def global_rank(self, r: int) -> int:
+        return dist.get_global_rank(self.group, r) if self.group is not None else r
+
+    def fail(self, first: int, error: Optional[str]) -> None:
+        """Every rank raises the text of rank `first`, which that rank broadcasts."""
+        from . import interop
+
+        text = [error if self.rank == first else None]
+        if self.multi:
+            dist.broadcast_object_list(text, src=self.global_rank(first), group=self.group, device=self.device if self.on_dev else None)
+        raise interop.PqaException("rank %d: %s" % (first, text[0]))
+
+    def settle(self, error: Optional[str], undo: Optional[Callable[[], None]] = None, name_alone: bool = False) -> None:
+        """One status word between the ranks: all succeeded, or every rank calls `undo` and raises the same PqaException (the
+        first failing rank's).  Without a group of several ranks the text is the engine's own, unless `name_alone`."""
+        from . import interop
+
+        if error is not None and not self.multi and not name_alone:
+            raise interop.PqaException(error)
+        first = self.min_word(self.rank if error is not None else self.world)
+        if first >= self.world:
+            return
+        if undo is not None:
+            undo()
+        self.fail(first, error)
+
+
+def _summed_package(ranks: _Ranks, engine, pkg: torch.Tensor, pack: Callable[[int], None]) -> Optional[str]:
+    """The owners pack into the zero-filled `pkg`, ONE all_reduce(SUM) combines the ranks' packages in place.  -> this rank's error
+    text or None: a rank whose pack is refused still takes part in the collective, so that the ranks stay in step; the status word
+    that follows fails the call everywhere."""
+    from . import interop
+
+    if pkg.is_cuda:
+        torch.cuda.current_stream(pkg.device).synchronize()   # the zeros are there before the engine's stream writes among them
+    error = None
+    try:
+        pack(pkg.data_ptr())
+    except interop.PqaException as e:
+        error = str(e)
+    engine.synchronize()                                      # ... and the rows before the collective's stream (or the host) reads them
+    ranks.sum_(pkg)
+    return error
+
+
 # ---- ListTopQuestions over the shards ---------------------------------------------------------------------------------------
 # On a shard (PqaEngineFactory_CreateHipEngineSharded) PqaEngine_ListTopQuestions lists the shard's own questions with GLOBAL ids.  The
 # best max_count of the whole question axis are among the shards' best max_count each: the ranks all-gather their records -- 16 bytes
@@ -100,8 +202,8 @@ def merge_top_questions(lists, max_count: int) -> List[Tuple[int, float]]:
 
 
 def _gather_top(local: List[List[Tuple[int, float]]], max_count: int, group, device: Optional[torch.device]) -> List[List[Tuple[int, float]]]:
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if world == 1 or max_count <= 0:
+    ranks = _Ranks(group, device)
+    if not ranks.multi or max_count <= 0:
         return [merge_top_questions([lst], max_count) for lst in local]
     # one [quizzes, max_count, 2] tensor of 8-byte words per rank: the question (-1: no record) and the priority's bits
     words = torch.full((len(local), max_count, 2), -1, dtype=torch.int64)
@@ -109,12 +211,7 @@ def _gather_top(local: List[List[Tuple[int, float]]], max_count: int, group, dev
         if lst:
             words[i, :len(lst), 0] = torch.tensor([q for q, _ in lst], dtype=torch.int64)
             words[i, :len(lst), 1] = torch.tensor([p for _, p in lst], dtype=torch.float64).view(torch.int64)
-    on_dev = dist.get_backend(group) == "nccl"
-    if on_dev:
-        words = words.to(device or torch.device("cuda", torch.cuda.current_device()))
-    parts = [torch.empty_like(words) for _ in range(world)]
-    dist.all_gather(parts, words, group=group)
-    parts = [p.cpu() for p in parts]
+    parts = ranks.gather(words)
     merged = []
     for i in range(len(local)):
         lists = []
@@ -152,7 +249,7 @@ class ShardedSelector:
         self.local_select = local_select
         self.device = device
         self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.world = _Ranks(group, device).world
         self.local = torch.zeros(2, dtype=torch.float64, device=device)
         self.gathered = torch.zeros(self.world, 2, dtype=torch.float64, device=device)
         on_gpu = device.type == "cuda"
@@ -178,6 +275,78 @@ class ShardedSelector:
         return pick_global(recs)
 
 
+class _ShmSegment:
+    """One /dev/shm file, mapped: `host` is its address, `dev` the address the GPU sees it at (PqaHip_HostRegister) if `register`,
+    `bytes` a numpy byte view.  Creating means truncate and zero-fill; the creator is the owner, whose close removes the file."""
+
+    def __init__(self, path: str, size: int, create: bool, register: bool):
+        import ctypes
+        import mmap
+        import os
+
+        import numpy as np
+
+        from . import interop
+
+        self.path, self._owner = path, create
+        fd = os.open(path, (os.O_CREAT | os.O_TRUNC | os.O_RDWR) if create else os.O_RDWR, 0o600)
+        try:
+            if create:
+                os.ftruncate(fd, size)
+            elif os.fstat(fd).st_size < size:
+                raise ValueError("%s is smaller than the %d bytes the exchange needs" % (path, size))
+            self._map = mmap.mmap(fd, size)
+        finally:
+            os.close(fd)
+        self.host = ctypes.addressof(ctypes.c_char.from_buffer(self._map))
+        self.bytes = np.frombuffer(self._map, dtype=np.uint8)
+        self._unregister = interop.host_unregister if register else None
+        self.dev = interop.host_register(self.host, size) if register else None
+
+    def close(self, unlink: bool = True) -> None:
+        """The user drops its own views of `bytes` first.  Safe to call twice."""
+        import os
+
+        if self._map is None:
+            return
+        if self._unregister is not None:
+            self._unregister(self.host)
+        self.bytes = None
+        try:
+            self._map.close()
+        except BufferError:
+            pass
+        self._map = None
+        if unlink and self._owner:
+            try:
+                os.unlink(self.path)
+            except OSError:
+                pass
+
+
+def _next_half(exchange) -> int:
+    """The next step of a selector or an exchange, and which of its two halves that step uses: they alternate by step parity."""
+    exchange.step += 1
+    return exchange.step & 1
+
+
+def _spin_until(read: Callable[[int], int], want, world: int, timeout_s: float, what: str) -> List[int]:
+    """Wait until read(r) is one of `want` for every rank r in turn, `timeout_s` for all of them together.  -> what was read."""
+    import time
+
+    t0 = time.perf_counter()
+    seen = []
+    for r in range(world):
+        while True:
+            v = int(read(r))
+            if v in want:
+                break
+            if time.perf_counter() - t0 > timeout_s:
+                raise TimeoutError(what % r)
+        seen.append(v)
+    return seen
+
+
 class ShmSelector:
     """Global next-question selection over question shards, the ranks' 16-byte records exchanged through a host
     shared-memory segment instead of a collective.
@@ -196,32 +365,12 @@ class ShmSelector:
     SLOT = 64
 
     def __init__(self, engine, quiz: int, rank: int, world: int, name: str, create: Optional[bool] = None):
-        import mmap
-        import os
-
-        from . import interop
-
         self.engine, self.quiz, self.rank, self.world = engine, quiz, rank, world
         self.path = "/dev/shm/pqa_select_%s" % name
-        size = 2 * world * self.SLOT
-        if create is None:
-            create = rank == 0
-        if create:
-            fd = os.open(self.path, os.O_CREAT | os.O_RDWR | os.O_TRUNC, 0o600)
-            os.ftruncate(fd, size)          # zero-filled: step 0 is never used
-        else:
-            fd = os.open(self.path, os.O_RDWR)
-        try:
-            self._map = mmap.mmap(fd, size)
-        finally:
-            os.close(fd)
-        import ctypes
-
-        self._host = ctypes.addressof(ctypes.c_char.from_buffer(self._map))
-        self._dev = interop.host_register(self._host, size)
-        self._interop = interop
+        # (zero-filled by its creator: step 0 is never used)
+        self._seg = _ShmSegment(self.path, 2 * world * self.SLOT, rank == 0 if create is None else create, register=True)
+        self._host, self._dev = self._seg.host, self._seg.dev
         self.step = 0
-        self._owner = create
 
     def select(self) -> Tuple[float, int]:
         self.step += 1
@@ -231,17 +380,7 @@ class ShmSelector:
                                                 self.step)
 
     def close(self) -> None:
-        import os
-
-        if self._map is not None:
-            self._interop.host_unregister(self._host)
-            self._map.close()
-            self._map = None
-            if self._owner:
-                try:
-                    os.unlink(self.path)
-                except OSError:
-                    pass
+        self._seg.close()
 
 
 class ShmBatchExchange:
@@ -251,27 +390,12 @@ class ShmBatchExchange:
     alternate by step parity (as ShmSelector).  x86 keeps stores in order: the records are written before the step number."""
 
     def __init__(self, n_quizzes: int, rank: int, world: int, name: str, create: Optional[bool] = None):
-        import mmap
-        import os
-
-        import numpy as np
-
         self.B, self.rank, self.world = n_quizzes, rank, world
         self.stride = 16 * n_quizzes + 64               # records, then the step number on its own line
         self.path = "/dev/shm/pqa_batch_%s" % name
-        size = 2 * world * self.stride
-        if create is None:
-            create = rank == 0
-        fd = os.open(self.path, (os.O_CREAT | os.O_TRUNC | os.O_RDWR) if create else os.O_RDWR, 0o600)
-        try:
-            if create:
-                os.ftruncate(fd, size)
-            self._map = mmap.mmap(fd, size)
-        finally:
-            os.close(fd)
-        self._bytes = np.frombuffer(self._map, dtype=np.uint8)
+        self._seg = _ShmSegment(self.path, 2 * world * self.stride, rank == 0 if create is None else create, register=False)
+        self._bytes = self._seg.bytes
         self.step = 0
-        self._owner = create
 
     def _slot(self, half: int, r: int):
         import numpy as np
@@ -283,45 +407,24 @@ class ShmBatchExchange:
 
     def exchange(self, local_winners, timeout_s: float = 600.0) -> List[int]:
         """local_winners: numpy [B, 2] of this rank -> the B global picks, the same on every rank."""
-        import time
-
         import numpy as np
 
-        self.step += 1
-        half = self.step & 1
+        half = _next_half(self)
         recs, flag = self._slot(half, self.rank)
         recs[:] = local_winners
         flag[0] = self.step
-        gathered = np.empty((self.world, self.B, 2), dtype=np.float64)
-        t0 = time.perf_counter()
-        for r in range(self.world):
-            rr, ff = self._slot(half, r)
-            while int(ff[0]) != self.step:
-                if time.perf_counter() - t0 > timeout_s:
-                    raise TimeoutError("rank %d never published step %d" % (r, self.step))
-            gathered[r] = rr
-        return pick_batch(gathered)
+        slots = [self._slot(half, r) for r in range(self.world)]
+        _spin_until(lambda r: slots[r][1][0], (self.step,), self.world, timeout_s, "rank %%d never published step %d" % self.step)
+        return pick_batch(np.stack([rr for rr, _ in slots]))
 
     def close(self) -> None:
-        import os
-
-        if self._map is not None:
-            self._bytes = None
-            try:
-                self._map.close()
-            except BufferError:
-                pass
-            self._map = None
-            if self._owner:
-                try:
-                    os.unlink(self.path)
-                except OSError:
-                    pass
+        self._bytes = None
+        self._seg.close()
 
 
 def broadcast_prior(prior: torch.Tensor, owner_rank: int, group: Optional[dist.ProcessGroup] = None) -> None:
     """After RecordAnswer on the owner of the answered question: replicate the new prior vector."""
-    if dist.is_initialized() and dist.get_world_size(group) > 1:
+    if _Ranks(group, prior.device).multi:
         dist.broadcast(prior, src=owner_rank, group=group)
 
 
@@ -370,57 +473,6 @@ def _package(engine, n_slots: int, device: torch.device) -> torch.Tensor:
     return torch.zeros(max(n_slots, 1), 2 * ld, dtype=torch.float64 if elem == 8 else torch.float32, device=device)
 
 
-def _combined_package(engine, flat, device: torch.device, group):
-    """-> (the combined package, this rank's error text or None).  A rank whose pack is refused still takes part in the
-    collective, so that the ranks stay in step; the status word that follows fails the call everywhere."""
-    from . import interop
-
-    pkg = _package(engine, len(flat), device)
-    on_gpu = device.type == "cuda"
-    if on_gpu:
-        torch.cuda.current_stream(device).synchronize()   # the zeros are there before the engine's stream writes among them
-    error = None
-    try:
-        engine.pack_answer_rows(flat, pkg.data_ptr())
-    except interop.PqaException as e:
-        error = str(e)
-    engine.synchronize()                                  # ... and the rows before the collective's stream (or the host) reads them
-    if dist.is_initialized() and dist.get_world_size(group) > 1:
-        if on_gpu and dist.get_backend(group) != "nccl":   # gloo: through the host
-            host = pkg.cpu()
-            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
-            pkg.copy_(host)
-        else:
-            dist.all_reduce(pkg, op=dist.ReduceOp.SUM, group=group)
-        if on_gpu:
-            torch.cuda.current_stream(device).synchronize()
-    return pkg, error
-
-
-def _settle(engine, quizzes: List[int], error: Optional[str], rank: int, world: int, device: torch.device, group) -> None:
-    """One status word between the ranks: all succeeded, or the quizzes of those that did are released again and every rank
-    raises the same PqaException (the first failing rank's)."""
-    from . import interop
-
-    if not (dist.is_initialized() and dist.get_world_size(group) > 1):
-        if error is not None:
-            raise interop.PqaException(error)
-        return
-    on_dev = device.type == "cuda" and dist.get_backend(group) == "nccl"
-    word = torch.tensor([rank if error is not None else world], dtype=torch.int64, device=device if on_dev else "cpu")
-    dist.all_reduce(word, op=dist.ReduceOp.MIN, group=group)
-    first = int(word.item())
-    if first >= world:
-        return
-    if error is None:
-        for q in quizzes:
-            engine.release_quiz(q)
-    text = [error if rank == first else None]
-    dist.broadcast_object_list(text, src=dist.get_global_rank(group, first) if group is not None else first, group=group,
-                               device=device if on_dev else None)
-    raise interop.PqaException("rank %d: %s" % (first, text[0]))
-
-
 def resume_quiz(engine, answered, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
                 device: Optional[torch.device] = None) -> int:
     """ResumeQuiz on the shards of `world` ranks: a collective every rank calls with the same list of AnsweredQuestion (GLOBAL
@@ -434,16 +486,17 @@ def resume_quiz(engine, answered, rank: int, world: int, group: Optional[dist.Pr
     The package is a snapshot of the cube: no rank may train between the pack and the resume inside this call."""
     from . import interop
 
-    device = device or torch.device("cuda", torch.cuda.current_device())
+    ranks = _Ranks(group, device, rank, world)
     answered = list(answered)
     quiz = -1
-    pkg, error = _combined_package(engine, answered, device, group)
+    pkg = _package(engine, len(answered), ranks.device)
+    error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_answer_rows(answered, ptr))
     if error is None:
         try:
             quiz = engine.resume_quiz_from_rows(answered, pkg.data_ptr())
         except interop.PqaException as e:
             error = str(e)
-    _settle(engine, [quiz], error, rank, world, device, group)
+    ranks.settle(error, lambda: error is None and engine.release_quiz(quiz))
     return quiz
 
 
@@ -453,17 +506,18 @@ def resume_quiz_batch(engine, lists, rank: int, world: int, group: Optional[dist
     lists' answered questions, one all_reduce, one batched resume per rank; all or none over the ranks as over the entries."""
     from . import interop
 
-    device = device or torch.device("cuda", torch.cuda.current_device())
+    ranks = _Ranks(group, device, rank, world)
     lists = [list(l) for l in lists]
     flat = [aq for l in lists for aq in l]
     quizzes = []
-    pkg, error = _combined_package(engine, flat, device, group)
+    pkg = _package(engine, len(flat), ranks.device)
+    error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_answer_rows(flat, ptr))
     if error is None:
         try:
             quizzes = engine.resume_quiz_batch_from_rows(lists, pkg.data_ptr())
         except interop.PqaException as e:
             error = str(e)
-    _settle(engine, quizzes, error, rank, world, device, group)
+    ranks.settle(error, lambda: [engine.release_quiz(q) for q in quizzes])   # (no quizzes where this rank is one that failed)
     return quizzes
 
 
@@ -481,12 +535,13 @@ def resume_quiz_batch(engine, lists, rank: int, world: int, group: Optional[dist
 def broadcast_rnds(rnds, group: Optional[dist.ProcessGroup] = None) -> List[int]:
     """The selector's random numbers (one unsigned 64-bit number per quiz) as rank 0 has them, on every rank."""
     rnds = [int(r) for r in rnds]
-    if not (dist.is_initialized() and dist.get_world_size(group) > 1):
+    ranks = _Ranks(group)
+    if not ranks.multi:
         return rnds
     words = torch.tensor([r - (1 << 64) if r >= (1 << 63) else r for r in rnds], dtype=torch.int64)   # (the bits, as signed words)
-    if dist.get_backend(group) == "nccl":
-        words = words.cuda()
-    dist.broadcast(words, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    if ranks.on_dev:
+        words = words.to(ranks.device)
+    dist.broadcast(words, src=ranks.global_rank(0), group=group)
     return [w + (1 << 64) if w < 0 else w for w in words.cpu().tolist()]
 
 
@@ -511,33 +566,18 @@ def next_question_sampled_batch(engine, quizzes, rnds, rank: int, world: int, gr
     the status word that follows fails the call everywhere, and no quiz's active question has changed then."""
     from . import interop
 
-    device = device or torch.device("cuda", torch.cuda.current_device())
+    ranks = _Ranks(group, device, rank, world)
     quizzes, rnds = list(quizzes), [int(r) for r in rnds]
     n = len(quizzes)
-    multi = dist.is_initialized() and dist.get_world_size(group) > 1
-    on_gpu = device.type == "cuda"
-    on_dev = on_gpu and multi and dist.get_backend(group) == "nccl"
     words = max(engine.sampled_part_bytes(), 16) // 8
-    mine = torch.empty(max(n, 1), words, dtype=torch.int64, device=device)
+    mine = torch.empty(max(n, 1), words, dtype=torch.int64, device=ranks.device)
     error = None
     try:
         engine.pack_sampled_parts(quizzes, mine.data_ptr())
     except interop.PqaException as e:
         error = str(e)
     engine.synchronize()                                   # the parts before the collective's stream (or the host) reads them
-    if multi:
-        if on_gpu and not on_dev:                          # gloo: through the host
-            host = [torch.empty(mine.shape, dtype=torch.int64) for _ in range(world)]
-            dist.all_gather(host, mine.cpu(), group=group)
-            parts = torch.stack(host).to(device)
-        else:
-            gathered = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(gathered, mine, group=group)
-            parts = torch.stack(gathered)
-        if on_gpu:
-            torch.cuda.current_stream(device).synchronize()
-    else:
-        parts = mine.unsqueeze(0)
+    parts = ranks.gather(mine)
     local = torch.full((n + 1,), -1, dtype=torch.int64)       # the picks, then this rank's status: 0 = no step was refused
     if error is None:
         try:
@@ -546,21 +586,14 @@ def next_question_sampled_batch(engine, quizzes, rnds, rank: int, world: int, gr
         except interop.PqaException as e:
             error = str(e)
     local[n] = 0 if error is None else 1
-    if multi:
-        if on_dev:
-            local = local.to(device)
-        gathered = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(gathered, local, group=group)
-        words = [g.cpu().tolist() for g in gathered]
-    else:
-        words = [local.tolist()]
+    words = ranks.gather(local).tolist()
     questions = []
     if all(w[n] == 0 for w in words):                         # (else nobody takes anything: the status word below says who failed)
         try:
             questions = engine.take_sampled_picks(quizzes, merge_sampled_picks([w[:n] for w in words]) if n else [])
         except (interop.PqaException, ValueError) as e:       # (disagreeing picks are the same finding on every rank)
             error = str(e)
-    _settle(None, [], error, rank, world, device, group)
+    ranks.settle(error)
     return questions
 
 
@@ -601,7 +634,7 @@ def save_kb(engine, path: str, rank: int, world: int, group: Optional[dist.Proce
 
     from . import interop
 
-    multi = dist.is_initialized() and dist.get_world_size(group) > 1
+    ranks = _Ranks(group, None, rank, world)
     creator = engine.get_option("q_first") == 0
     error = None
     if creator:
@@ -609,33 +642,22 @@ def save_kb(engine, path: str, rank: int, world: int, group: Optional[dist.Proce
             open(path, "wb").close()
         except OSError as e:
             error = "cannot create %s: %s" % (path, e)
-    if multi:
+    if ranks.multi:
         dist.barrier(group=group)
     if error is None:
         try:
             engine.save_kb_shard(path, precision)
         except interop.PqaException as e:
             error = str(e)
-    first = rank if error is not None else world
-    if multi:
-        word = torch.tensor([first], dtype=torch.int64)
-        on_dev = dist.get_backend(group) == "nccl"
-        if on_dev:
-            word = word.cuda()
-        dist.all_reduce(word, op=dist.ReduceOp.MIN, group=group)
-        first = int(word.item())
-    if first >= world:
-        return
-    if creator:
-        try:
-            os.remove(path)
-        except OSError:
-            pass
-    text = [error if rank == first else None]
-    if multi:
-        dist.broadcast_object_list(text, src=dist.get_global_rank(group, first) if group is not None else first, group=group,
-                                   device=torch.device("cuda", torch.cuda.current_device()) if on_dev else None)
-    raise interop.PqaException("rank %d: %s" % (first, text[0]))
+
+    def remove():
+        if creator:
+            try:
+                os.remove(path)
+            except OSError:
+                pass
+
+    ranks.settle(error, remove, name_alone=True)
 
 
 # ---- changing the KB in the process-per-GPU form -----------------------------------------------------------------------------------
@@ -650,14 +672,7 @@ def save_kb(engine, path: str, rank: int, world: int, group: Optional[dist.Proce
 def gather_bounds(engine, group: Optional[dist.ProcessGroup] = None) -> List[int]:
     """End bound of each rank's question range as the engines hold them now: an all_gather of (q_first, local question count)."""
     mine = [engine.get_option("q_first"), engine.get_option("local_questions")]
-    if not (dist.is_initialized() and dist.get_world_size(group) > 1):
-        return [mine[0] + mine[1]]
-    word = torch.tensor(mine, dtype=torch.int64)
-    if dist.get_backend(group) == "nccl":
-        word = word.cuda()
-    parts = [torch.empty_like(word) for _ in range(dist.get_world_size(group))]
-    dist.all_gather(parts, word, group=group)
-    return [int(p[0]) + int(p[1]) for p in (x.cpu() for x in parts)]
+    return [int(p[0]) + int(p[1]) for p in _Ranks(group).gather(torch.tensor(mine, dtype=torch.int64))]
 
 
 def owner_in(bounds: List[int], question: int) -> int:
@@ -675,13 +690,12 @@ def _replicated(call, rank: int, world: int, group, device: Optional[torch.devic
     device's memory, and that rank's engine is unchanged then.)"""
     from . import interop
 
-    device = device or torch.device("cuda", torch.cuda.current_device())
     result, error = None, None
     try:
         result = call()
     except interop.PqaException as e:
         error = str(e)
-    _settle(None, [], error, rank, world, device, group)
+    _Ranks(group, device, rank, world).settle(error)
     return result
 
 
@@ -716,60 +730,34 @@ def compact(engine, rank: int, world: int, group: Optional[dist.ProcessGroup] = 
     question count: see gather_bounds."""
     from . import interop
 
-    device = device or torch.device("cuda", torch.cuda.current_device())
-    multi = dist.is_initialized() and dist.get_world_size(group) > 1
-    on_gpu = device.type == "cuda"
-    on_dev = on_gpu and multi and dist.get_backend(group) == "nccl"
+    ranks = _Ranks(group, device, rank, world)
     plan, error = None, None
     try:
         plan = engine.compact_plan()
     except interop.PqaException as e:
         error = str(e)
     # the vote: 2 * rank for an error, 2 * rank + 1 for a shard that would be emptied, 2 * world for neither
-    mine = 2 * rank if error is not None else 2 * rank + 1 if plan[3] else 2 * world
-    if multi:
-        word = torch.tensor([mine], dtype=torch.int64, device=device if on_dev else "cpu")
-        dist.all_reduce(word, op=dist.ReduceOp.MIN, group=group)
-        mine = int(word.item())
-    if mine < 2 * world:
-        first = mine // 2
-        if mine % 2:
+    vote = ranks.min_word(2 * rank if error is not None else 2 * rank + 1 if plan[3] else 2 * world)
+    if vote < 2 * world:
+        first = vote // 2
+        if vote % 2:
             engine.compact_from_blocks(0, 0, first)      # (refused, with the text every rank gets: nothing has changed)
             raise AssertionError("a compaction that empties rank %d was not refused" % first)
-        text = [error if rank == first else None]
-        if multi:
-            dist.broadcast_object_list(text, src=dist.get_global_rank(group, first) if group is not None else first, group=group,
-                                       device=device if on_dev else None)
-        raise interop.PqaException("rank %d: %s" % (first, text[0]))
+        ranks.fail(first, error)
     moves = plan[2]
     slot = engine.question_block_slot_bytes()
     pkg = None
     if moves:
         elem = 4 if engine.get_option("precision") == 1 else 8
-        pkg = torch.zeros(len(moves), slot // elem, dtype=torch.float32 if elem == 4 else torch.float64, device=device)
-        if on_gpu:
-            torch.cuda.current_stream(device).synchronize()   # the zeros are there before the engine's stream writes among them
-        try:
-            engine.pack_question_blocks([src for _, src in moves], pkg.data_ptr())
-        except interop.PqaException as e:                     # (still takes part in the collective: the status word fails the call)
-            error = str(e)
-        engine.synchronize()
-        if multi:
-            if on_gpu and not on_dev:                         # gloo: through the host
-                host = pkg.cpu()
-                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
-                pkg.copy_(host)
-            else:
-                dist.all_reduce(pkg, op=dist.ReduceOp.SUM, group=group)
-            if on_gpu:
-                torch.cuda.current_stream(device).synchronize()
+        pkg = torch.zeros(len(moves), slot // elem, dtype=torch.float32 if elem == 4 else torch.float64, device=ranks.device)
+        error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_question_blocks([src for _, src in moves], ptr))
     result = None
     if error is None:
         try:
             result = engine.compact_from_blocks(pkg.data_ptr() if pkg is not None else 0, slot if pkg is not None else 0, -1)
         except interop.PqaException as e:
             error = str(e)
-    _settle(None, [], error, rank, world, device, group)
+    ranks.settle(error)
     return result
 
 
@@ -788,10 +776,6 @@ class ShmRowExchange:
         return 2 * (2 * world * cls.LINE + max_slots * slot_bytes)
 
     def __init__(self, rank: int, world: int, name: str, slot_bytes: int, max_slots: int):
-        import ctypes
-        import mmap
-        import os
-
         import numpy as np
 
         from . import interop
@@ -799,17 +783,9 @@ class ShmRowExchange:
         self.rank, self.world, self.slot_bytes, self.max_slots = rank, world, slot_bytes, max_slots
         self.path = "/dev/shm/pqa_rows_%s" % name
         self._half = 2 * world * self.LINE + max_slots * slot_bytes
-        size = self.size_for(world, slot_bytes, max_slots)
-        fd = os.open(self.path, os.O_RDWR)
-        try:
-            if os.fstat(fd).st_size < size:
-                raise ValueError("%s is smaller than the %d bytes the exchange needs" % (self.path, size))
-            self._map = mmap.mmap(fd, size)
-        finally:
-            os.close(fd)
-        self._host = ctypes.addressof(ctypes.c_char.from_buffer(self._map))
-        self._dev = interop.host_register(self._host, size)
-        self._words = np.frombuffer(self._map, dtype=np.uint64)
+        self._seg = _ShmSegment(self.path, self.size_for(world, slot_bytes, max_slots), create=False, register=True)
+        self._dev = self._seg.dev
+        self._words = self._seg.bytes.view(np.uint64)
         self._interop = interop
         self.step = 0
 
@@ -818,23 +794,15 @@ class ShmRowExchange:
         return (half * self._half + (kind * self.world + r) * self.LINE) // 8
 
     def _wait(self, half: int, kind: int, timeout_s: float):
-        import time
-
-        t0 = time.perf_counter()
-        seen = []
-        for r in range(self.world):
-            i = self._word(half, kind, r)
-            while (int(self._words[i]) >> kind) != self.step:
-                if time.perf_counter() - t0 > timeout_s:
-                    raise TimeoutError("rank %d never published %s %d" % (r, "status" if kind else "rows of step", self.step))
-            seen.append(int(self._words[i]))
-        return seen
+        """Every rank's flag (the step) or status (twice the step, plus 1 for a failure) of this step, as read."""
+        want = (2 * self.step, 2 * self.step + 1) if kind else (self.step,)
+        return _spin_until(lambda r: self._words[self._word(half, kind, r)], want, self.world, timeout_s,
+                           "rank %%d never published %s %d" % ("status" if kind else "rows of step", self.step))
 
     def _run(self, engine, flat, resume, release, timeout_s: float):
         if len(flat) > self.max_slots:
             raise ValueError("%d answered questions, the segment holds %d" % (len(flat), self.max_slots))
-        self.step += 1
-        half = self.step & 1
+        half = _next_half(self)
         rows = half * self._half + 2 * self.world * self.LINE
         result, error = None, None
         try:
@@ -873,14 +841,8 @@ class ShmRowExchange:
                          timeout_s)
 
     def close(self) -> None:
-        if self._map is not None:
-            self._interop.host_unregister(self._host)
-            self._words = None
-            try:
-                self._map.close()
-            except BufferError:
-                pass
-            self._map = None
+        self._words = None
+        self._seg.close()
 
 
 def tensor_from_device_ptr(ptr: int, n_doubles: int, device: torch.device) -> torch.Tensor:

@@ -3,19 +3,12 @@ include/PqaCInterop.h and include/PqaHipExt.h declare, the POD layouts match the
 factory fails loudly instead of falling back to a CPU path."""
 import ctypes
 import os
-import re
 import subprocess
 
 import pytest
 
+from abi_common import ROOT, declared_functions, exported_symbols
 from probqa_amd import interop
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return re.findall(r"PQACORE_API\s+[\w\s\*]+?\b(\w+)\s*\(", text)
 
 
 def test_headers_and_binding_agree():
@@ -30,8 +23,7 @@ def test_library_loads_and_exports_every_declared_symbol(factory):
     lib = interop.load_library()
     for name in declared_functions("PqaCInterop.h") + declared_functions("PqaHipExt.h"):
         assert getattr(lib, name) is not None
-    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    exported = exported_symbols()
     assert set(interop.REFERENCE_EXPORTS) <= exported and set(interop.HIP_EXPORTS) <= exported
 
 

@@ -3,18 +3,17 @@
 oracle here (tests may use it as a stand-in selector); on GPUs the same ShardedSelector wraps
 PqaHip_EnqueueSelectArgmax and RCCL."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import ranks_common as rc
+from probqa_amd import dist as pdist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-from probqa_amd import dist as pdist  # noqa: E402
 
 
 def test_shard_bounds_follow_calc_split():
@@ -39,22 +38,13 @@ def test_pick_global_ties_nan_and_empty():
     assert pdist.pick_global(rec([(0.0, -1), (0.0, -1)]))[1] == -1
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _worker(rank, world, port, ret):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import cases
     import orclib
 
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rc.init_group("gloo", rank, world, port)
     case = cases.Case("dist", 5, 61, 90, seed=77, qgaps=[4], answers=[])
     A, D, B = case.kb()
     q0, q1 = pdist.shard_range(case.Q, world, rank)
@@ -94,10 +84,7 @@ def _worker(rank, world, port, ret):
 
 
 def test_two_rank_sharded_selection_matches_single_process():
-    world, port = 2, _free_port()
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
+    ret = rc.run_gloo(_worker, 2)
     assert ret[0] == ret[1] and len(ret[0]) == 4 and len(set(ret[0])) == 4
 
 
@@ -153,8 +140,7 @@ def _batch_worker(rank, world, port, ret):
     import cases
     import orclib
 
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rc.init_group("gloo", rank, world, port)
     case = cases.Case("distb", 5, 47, 70, seed=78, qgaps=[11], answers=[])
     A, D, B = case.kb()
     q0, q1 = pdist.shard_range(case.Q, world, rank)
@@ -188,8 +174,81 @@ def _batch_worker(rank, world, port, ret):
 
 
 def test_two_rank_batched_selection_matches_single_process():
-    world, port = 2, _free_port()
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_batch_worker, args=(world, port, ret), nprocs=world, join=True)
+    ret = rc.run_gloo(_batch_worker, 2)
     assert ret[0] == ret[1] and len(ret[0]) == 6
+
+
+# ---- ShmBatchExchange between two processes (host only: numpy over /dev/shm) -------------------------------------------------------
+NAN = float("nan")
+# [step][rank] -> the rank's B = 3 records (priority, GLOBAL question or -1); step 3 reuses the half of step 1 with other winners
+EXCHANGE_RECORDS = [
+    [[(1.0, 5), (NAN, 2), (0.0, -1)], [(3.0, 9), (1.0, 7), (0.0, -1)]],
+    [[(2.0, 4), (2.0, 3), (NAN, 1)], [(2.0, 8), (0.0, -1), (0.0, -1)]],
+    [[(0.5, 0), (0.0, -1), (7.0, 2)], [(0.25, 6), (4.0, 10), (7.0, 11)]],
+]
+EXCHANGE_PICKS = [[9, 7, -1], [4, 3, 1], [0, 10, 2]]       # maximum; NaN and -1 lose; a tie goes to the lower question; a lone NaN still wins
+
+
+def _exchange_worker(rank, name):
+    ex = pdist.ShmBatchExchange(3, rank, 2, name, create=False)
+    res = {"picks": [ex.exchange(np.array(step[rank]), timeout_s=60.0) for step in EXCHANGE_RECORDS], "timeout": None}
+    if rank == 0:                               # a fourth step that rank 1 never takes
+        try:
+            ex.exchange(np.array(EXCHANGE_RECORDS[0][0]), timeout_s=0.2)
+        except TimeoutError as e:
+            res["timeout"] = str(e)
+    res["step"] = ex.step
+    ex.close()
+    return res
+
+
+def test_two_processes_exchange_batches_through_shared_memory():
+    assert [pdist.pick_batch(np.array(step)) for step in EXCHANGE_RECORDS] == EXCHANGE_PICKS
+    owner = pdist.ShmBatchExchange(3, 0, 2, "test_%d" % os.getpid(), create=True)     # the segment exists, zeroed, before a rank opens it
+    try:
+        assert owner.path == "/dev/shm/pqa_batch_test_%d" % os.getpid() and os.path.getsize(owner.path) == 2 * 2 * (16 * 3 + 64)
+        got = rc.run_ranks(_exchange_worker, 2, (owner.path[len("/dev/shm/pqa_batch_"):],), timeout_s=120)
+    finally:
+        owner.close()
+    assert not os.path.exists(owner.path)       # closing the owner removes the file; the ranks' closes did not
+    for r in range(2):
+        assert got[r]["picks"] == EXCHANGE_PICKS, (r, got[r])
+    assert got[0]["timeout"] == "rank 1 never published step 4" and (got[0]["step"], got[1]["step"]) == (4, 3), got
+
+
+# ---- list_top_questions_batch over gloo, against a fake engine ----------------------------------------------------------------------
+# [rank][quiz]: lists of unequal length, one empty list, and in quiz 2 the same priority on both ranks
+TOP_LISTS = [[[(4, 0.9), (1, 0.5), (2, 0.125)], [], [(3, 0.625)]],
+             [[(7, 0.75)], [(8, 0.25), (6, 0.125)], [(9, 0.625), (5, 0.5)]]]
+TOP_MERGED = [[(4, 0.9), (7, 0.75), (1, 0.5)], [(8, 0.25), (6, 0.125)], [(3, 0.625), (9, 0.625), (5, 0.5)]]
+
+
+class FakeTopEngine:
+    def __init__(self, rank):
+        self.lists, self.calls = TOP_LISTS[rank], []
+
+    def list_top_questions_batch(self, quizzes, max_count):
+        self.calls.append((list(quizzes), max_count))
+        return [self.lists[q][:max_count] for q in quizzes]
+
+    def list_top_questions(self, quiz, max_count):
+        return self.list_top_questions_batch([quiz], max_count)[0]
+
+
+def _top_worker(rank, world, port, ret):
+    rc.init_group("gloo", rank, world, port)
+    eng = FakeTopEngine(rank)
+    out = {"three": pdist.list_top_questions_batch(eng, [0, 1, 2], 3), "two": pdist.list_top_questions_batch(eng, (2, 0), 2),
+           "none": pdist.list_top_questions_batch(eng, [0, 1, 2], 0), "single": pdist.list_top_questions(eng, 2, 3), "calls": eng.calls}
+    ret[rank] = out
+    dist.destroy_process_group()
+
+
+def test_two_rank_top_questions_over_gloo():
+    assert [pdist.merge_top_questions([TOP_LISTS[0][q], TOP_LISTS[1][q]], 3) for q in range(3)] == TOP_MERGED
+    ret = rc.run_gloo(_top_worker, 2)
+    for r in range(2):
+        assert ret[r]["three"] == TOP_MERGED, (r, ret[r])
+        assert ret[r]["two"] == [TOP_MERGED[2][:2], TOP_MERGED[0][:2]] and ret[r]["single"] == TOP_MERGED[2], (r, ret[r])
+        assert ret[r]["none"] == [[], [], []], (r, ret[r])
+        assert ret[r]["calls"] == [([0, 1, 2], 3), ([2, 0], 2), ([0, 1, 2], 0), ([2], 3)], ret[r]["calls"]

@@ -7,15 +7,14 @@ The shapes are chosen for the dense side's alignment and the row forms, not for 
 101 (odd: every other dense row starts 8 bytes off a 16-byte line, the fp32 ones 4 or 12), 1025 (one element past a quad boundary), 4096
 (aligned throughout), 16387 (just past the long-row boundary, three tail elements)."""
 import json
-import multiprocessing as mp
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import ranks_common as rc
 from probqa_amd import dist as pdist
 from probqa_amd import interop
 
@@ -373,24 +372,18 @@ def test_one_process_sharded_engine(factory, kb_file, tmp_path):
     single.close()
 
 
-def _rank_main(rank, world, port, path, out_path, records, queue):
-    try:
-        import datetime
+def _rank_main(rank, world, port, path, out_path, records):
+    import torch.distributed as dist
 
-        import torch.distributed as dist
-
-        os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-        aq = interop.AnsweredQuestion
-        eng = pdist.load_shard(interop.PqaEngineFactory(), path, rank, world, P.FLOAT, device=0)
-        eng.train_batch([([aq(q, a) for q, a in pairs], t, amount) for pairs, t, amount in records])
-        pdist.save_kb(eng, out_path, rank, world, precision=P.DOUBLE)
-        dist.barrier()
-        eng.close()
-        dist.destroy_process_group()
-        queue.put((rank, "ok"))
-    except BaseException as e:   # noqa: BLE001 -- the parent reports it
-        queue.put((rank, "%s: %s" % (type(e).__name__, e)))
+    rc.init_group("gloo", rank, world, port)
+    aq = interop.AnsweredQuestion
+    eng = pdist.load_shard(interop.PqaEngineFactory(), path, rank, world, P.FLOAT, device=0)
+    eng.train_batch([([aq(q, a) for q, a in pairs], t, amount) for pairs, t, amount in records])
+    pdist.save_kb(eng, out_path, rank, world, precision=P.DOUBLE)
+    dist.barrier()
+    eng.close()
+    dist.destroy_process_group()
+    return {"ok": True}
 
 
 def test_two_processes_over_gloo(factory, edited_file, tmp_path):
@@ -402,23 +395,8 @@ def test_two_processes_over_gloo(factory, edited_file, tmp_path):
     whole.save_kb_as(want, P.DOUBLE)
     whole.close()
     got = str(tmp_path / "ranks.kb")
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    queue = ctx.Queue()
-    procs = [ctx.Process(target=_rank_main, args=(r, 2, port, path, got, records, queue)) for r in range(2)]
-    for p in procs:
-        p.start()
-    try:
-        results = dict(queue.get(timeout=240) for _ in procs)
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    assert results == {0: "ok", 1: "ok"}, results
+    results = rc.run_ranks(_rank_main, 2, (2, rc.free_port(), path, got, records), timeout_s=240)
+    assert results == {0: {"ok": True}, 1: {"ok": True}}, results
     assert open(got, "rb").read() == open(want, "rb").read()
 
 

@@ -4,93 +4,61 @@ each holds its range of the questions of the script `compact_across_granule` (te
 of the arrays of the numpy model.  At three ranks the compaction would leave the last one without a question: every rank must raise
 the same refusal and keep what it had.  Every wait is bounded: the collectives time out, and the parent takes the results with a time
 limit."""
-import multiprocessing as mp
-import os
-import socket
-
 import numpy as np
 import pytest
 
 import maintenance_cases as mc
+import ranks_common as rc
 
 pytestmark = pytest.mark.gpu
 
 SCRIPT = "compact_across_granule"
 
 
-def _rank_main(rank, world, port, out):
+def _rank_main(rank, world, port):
+    import torch
+    import torch.distributed as dist
+
     from probqa_amd import dist as pdist
     from probqa_amd import interop
 
+    (K, Q, T), seed, steps = mc.array_scripts(False)[SCRIPT]
+    model = mc.synthetic_model(K, Q, T, seed, False)
+    first, limit = pdist.shard_range(Q, world, rank)
+    eng = interop.PqaEngineFactory().create_hip_engine(interop.EngineDefinition(K, limit - first, T, init_amount=mc.INIT), first, Q, 0)
+    eng.set_kb(model.A[first:limit], model.D[first:limit], model.B)
+    torch.cuda.set_device(0)
+    rc.init_group("gloo", rank, world, port)
+    eng.start_maintenance(False)
+    res = {"bounds": [pdist.gather_bounds(eng)], "returned": [], "error": None}
     try:
-        import datetime
-
-        import torch
-        import torch.distributed as dist
-
-        (K, Q, T), seed, steps = mc.array_scripts(False)[SCRIPT]
-        model = mc.synthetic_model(K, Q, T, seed, False)
-        first, limit = pdist.shard_range(Q, world, rank)
-        eng = interop.PqaEngineFactory().create_hip_engine(interop.EngineDefinition(K, limit - first, T, init_amount=mc.INIT), first, Q, 0)
-        eng.set_kb(model.A[first:limit], model.D[first:limit], model.B)
-        os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-        eng.start_maintenance(False)
-        res = {"bounds": [pdist.gather_bounds(eng)], "returned": [], "error": None}
-        try:
-            for step in steps:
-                if step[0] == "remove_q":
-                    pdist.remove_questions(eng, step[1], rank, world)
-                elif step[0] == "remove_t":
-                    pdist.remove_targets(eng, step[1], rank, world)
-                elif step[0] == "add":
-                    aq = [interop.AddQuestionParam(a) for a in step[1]]
-                    at = [interop.AddTargetParam(a) for a in step[2]]
-                    pdist.add_qs_ts(eng, aq, at, rank, world)
-                    res["returned"].append(([p.i_question for p in aq], [p.i_target for p in at]))
-                else:
-                    res["returned"].append(pdist.compact(eng, rank, world))
-                if step[0] in ("add", "compact"):
-                    res["bounds"].append(pdist.gather_bounds(eng))
-        except interop.PqaException as e:
-            res["error"] = str(e)
-        res["dims"] = tuple(eng.get_option(o) for o in ("q_first", "local_questions", "q_total"))
-        res["plan"] = eng.compact_plan()[:3]
-        res["kb"] = eng.get_kb(res["dims"][1])
-        eng.finish_maintenance()
-        dist.destroy_process_group()
-        eng.close()
-        out.put((rank, res))
-    except Exception as e:  # noqa: BLE001 - reported to the parent
-        out.put((rank, repr(e)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+        for step in steps:
+            if step[0] == "remove_q":
+                pdist.remove_questions(eng, step[1], rank, world)
+            elif step[0] == "remove_t":
+                pdist.remove_targets(eng, step[1], rank, world)
+            elif step[0] == "add":
+                aq = [interop.AddQuestionParam(a) for a in step[1]]
+                at = [interop.AddTargetParam(a) for a in step[2]]
+                pdist.add_qs_ts(eng, aq, at, rank, world)
+                res["returned"].append(([p.i_question for p in aq], [p.i_target for p in at]))
+            else:
+                res["returned"].append(pdist.compact(eng, rank, world))
+            if step[0] in ("add", "compact"):
+                res["bounds"].append(pdist.gather_bounds(eng))
+    except interop.PqaException as e:
+        res["error"] = str(e)
+    res["dims"] = tuple(eng.get_option(o) for o in ("q_first", "local_questions", "q_total"))
+    res["plan"] = eng.compact_plan()[:3]
+    res["kb"] = eng.get_kb(res["dims"][1])
+    eng.finish_maintenance()
+    dist.destroy_process_group()
+    eng.close()
+    return res
 
 
 def _run_ranks(world):
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_rank_main, args=(r, world, port, out)) for r in range(world)]
-    for p in procs:
-        p.start()
-    try:
-        got = dict(out.get(timeout=300) for _ in range(world))     # (a rank that dies: queue.Empty here, not a hang)
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    for r in range(world):
-        assert isinstance(got[r], dict), got[r]
-    return got
+    return rc.run_ranks(_rank_main, world, (world, rc.free_port()))
 
 
 def _model(n_steps):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import cases
+import ranks_common as rc
 
 pytestmark = pytest.mark.gpu
 
@@ -75,10 +76,9 @@ def _two_rank_worker(rank, world, port, ret):
     from probqa_amd import dist as pdist
     from probqa_amd import interop
 
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     torch.cuda.set_device(rank)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", rank))
+    rc.init_group("nccl", rank, world, port, device_id=torch.device("cuda", rank))
     lib = rccl()
     uid = UniqueId()
     if rank == 0:
@@ -137,35 +137,16 @@ def _two_rank_worker(rank, world, port, ret):
 def test_two_ranks_on_two_devices():
     """PqaHip_SelectArgmaxRccl and probqa_amd.dist's selector over a communicator of TWO ranks, one per device: every rank returns the
     whole cube's pick (the oracle's) on every step, and the posterior broadcast after RecordAnswer keeps the shards bit-identical."""
-    import socket
-
     import torch
-    import torch.multiprocessing as mp
 
     if torch.cuda.device_count() < 2:
         pytest.skip("one device: RCCL refuses two ranks on it (the one-rank communicator above runs the same code)")
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_two_rank_worker, args=(2, port, ret), nprocs=2, join=True)
+    ret = rc.run_gloo(_two_rank_worker, 2)
     assert ret[0] == ret[1] and len(ret[0]) == 4
 
 
 def test_the_two_rank_worker_with_a_world_of_one():
     """The same worker as one process (what a one-GPU box can run of it): torch.distributed's nccl backend, a communicator made with
     RCCL's C API from a broadcast id, the sharded engine constructor, both selectors, the posterior hand-over."""
-    import socket
-
-    import torch.multiprocessing as mp
-
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_two_rank_worker, args=(1, port, ret), nprocs=1, join=True)
+    ret = rc.run_gloo(_two_rank_worker, 1)
     assert len(ret[0]) == 4 and len(set(ret[0])) == 4

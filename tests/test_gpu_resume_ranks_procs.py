@@ -2,12 +2,12 @@
 processes share the one GPU of the test box, each holding half of the questions; both must end with the posterior the parent's
 whole engine computes, under the same quiz ids, and a failure on one rank must fail both and leave no quiz behind.  Every wait is
 bounded: the ranks' collectives and flag waits time out, and the parent takes the results with a time limit."""
-import multiprocessing as mp
 import os
-import socket
 
 import numpy as np
 import pytest
+
+import ranks_common as rc
 
 pytestmark = pytest.mark.gpu
 
@@ -37,82 +37,56 @@ def _quiz_count(eng):
     return live
 
 
-def _rank_main(rank, mode, arg, out):
+def _rank_main(rank, mode, arg):
+    import torch
+    import torch.distributed as dist
+
     from probqa_amd import dist as pdist
     from probqa_amd import interop
 
-    try:
-        import torch
-        import torch.distributed as dist
-
-        first, limit = pdist.shard_range(Q, WORLD, rank)
-        dev = rank if mode == "nccl" else 0
-        eng = interop.PqaEngineFactory().create_hip_engine(interop.EngineDefinition(K, limit - first, T, init_amount=0.1), first, Q, dev)
-        eng.fill_synthetic(8.0, 0.5, SEED)
-        eng.set_option("workers", 16)
-        if mode in ("gloo", "nccl"):
-            import datetime
-
-            os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(arg)
-            torch.cuda.set_device(dev)
-            dist.init_process_group(mode, rank=rank, world_size=WORLD, timeout=datetime.timedelta(seconds=120))
-            single = lambda l: pdist.resume_quiz(eng, _aqs(l), rank, WORLD)                         # noqa: E731
-            batch = lambda ls: pdist.resume_quiz_batch(eng, [_aqs(l) for l in ls], rank, WORLD)     # noqa: E731
-            ex = None
-        else:
-            ex = pdist.ShmRowExchange(rank, WORLD, arg, eng.answer_row_slot_bytes(), 16)
-            single = lambda l: ex.resume_quiz(eng, _aqs(l), timeout_s=60.0)                          # noqa: E731
-            batch = lambda ls: ex.resume_quiz_batch(eng, [_aqs(l) for l in ls], timeout_s=60.0)      # noqa: E731
-        res = {}
-        quiz = single(SINGLE)
-        res["single"] = (quiz, eng.get_priors(quiz))
-        ids = batch(BATCH)
-        res["batch"] = (ids, [eng.get_priors(q) for q in ids])
-        res["again"] = single(SINGLE[:3])                      # (the second step of the exchange: the other half of the segment)
-        # a failure on ONE rank: every target a gap there (I64Underflow); both must raise, neither keeps a quiz
-        before = _quiz_count(eng)
-        if rank == 1:
-            eng.set_target_gaps(list(range(T)))
-        errors = []
-        for call in (lambda: single(SINGLE), lambda: batch(BATCH)):
-            try:
-                call()
-                errors.append(None)
-            except interop.PqaException as e:
-                errors.append(str(e))
-        res["errors"], res["before"], res["after"] = errors, before, _quiz_count(eng)
-        if ex is not None:
-            ex.close()
-        else:
-            dist.destroy_process_group()
-        eng.close()
-        out.put((rank, res))
-    except Exception as e:  # noqa: BLE001 - reported to the parent
-        out.put((rank, repr(e)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+    first, limit = pdist.shard_range(Q, WORLD, rank)
+    dev = rank if mode == "nccl" else 0
+    eng = interop.PqaEngineFactory().create_hip_engine(interop.EngineDefinition(K, limit - first, T, init_amount=0.1), first, Q, dev)
+    eng.fill_synthetic(8.0, 0.5, SEED)
+    eng.set_option("workers", 16)
+    if mode in ("gloo", "nccl"):
+        torch.cuda.set_device(dev)
+        rc.init_group(mode, rank, WORLD, arg)
+        single = lambda l: pdist.resume_quiz(eng, _aqs(l), rank, WORLD)                         # noqa: E731
+        batch = lambda ls: pdist.resume_quiz_batch(eng, [_aqs(l) for l in ls], rank, WORLD)     # noqa: E731
+        ex = None
+    else:
+        ex = pdist.ShmRowExchange(rank, WORLD, arg, eng.answer_row_slot_bytes(), 16)
+        single = lambda l: ex.resume_quiz(eng, _aqs(l), timeout_s=60.0)                          # noqa: E731
+        batch = lambda ls: ex.resume_quiz_batch(eng, [_aqs(l) for l in ls], timeout_s=60.0)      # noqa: E731
+    res = {}
+    quiz = single(SINGLE)
+    res["single"] = (quiz, eng.get_priors(quiz))
+    ids = batch(BATCH)
+    res["batch"] = (ids, [eng.get_priors(q) for q in ids])
+    res["again"] = single(SINGLE[:3])                      # (the second step of the exchange: the other half of the segment)
+    # a failure on ONE rank: every target a gap there (I64Underflow); both must raise, neither keeps a quiz
+    before = _quiz_count(eng)
+    if rank == 1:
+        eng.set_target_gaps(list(range(T)))
+    errors = []
+    for call in (lambda: single(SINGLE), lambda: batch(BATCH)):
+        try:
+            call()
+            errors.append(None)
+        except interop.PqaException as e:
+            errors.append(str(e))
+    res["errors"], res["before"], res["after"] = errors, before, _quiz_count(eng)
+    if ex is not None:
+        ex.close()
+    else:
+        dist.destroy_process_group()
+    eng.close()
+    return res
 
 
 def _run_ranks(mode, arg):
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    procs = [ctx.Process(target=_rank_main, args=(r, mode, arg, out)) for r in range(WORLD)]
-    for p in procs:
-        p.start()
-    try:
-        got = dict(out.get(timeout=300) for _ in range(WORLD))     # (a rank that dies: queue.Empty here, not a hang)
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    return got
+    return rc.run_ranks(_rank_main, WORLD, (mode, arg))
 
 
 def _check(got, factory, same_text):
@@ -144,7 +118,7 @@ def _check(got, factory, same_text):
 
 
 def test_two_processes_resume_over_gloo(factory):
-    _check(_run_ranks("gloo", _free_port()), factory, True)
+    _check(_run_ranks("gloo", rc.free_port()), factory, True)
 
 
 def test_two_processes_resume_through_shared_memory(factory):
@@ -171,4 +145,4 @@ def test_two_processes_resume_over_rccl(factory):
 
     if torch.cuda.device_count() < 2:
         pytest.skip("one device: RCCL refuses two ranks on it (the gloo test runs the same helpers with the package through the host)")
-    _check(_run_ranks("nccl", _free_port()), factory, True)
+    _check(_run_ranks("nccl", rc.free_port()), factory, True)

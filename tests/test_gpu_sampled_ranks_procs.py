@@ -2,13 +2,9 @@
 share the one GPU of the test box, each holding half of the questions; both must return the same questions, equal to the whole
 engine's in the parent for the guarded draws (tests/test_sampled_ranks_abi.py checks the draws without a GPU).  Every wait is
 bounded: the collectives time out, and the parent takes the results with a time limit."""
-import multiprocessing as mp
-import os
-import queue
-import socket
-
 import pytest
 
+import ranks_common as rc
 import sampled_batch_common as sb
 import sampled_ranks_common as sr
 
@@ -35,35 +31,29 @@ def engine_of(case, option, first, limit):
     return eng
 
 
-def _rank_main(rank, port, rnd_lists, out):
-    try:
-        import datetime
+def _rank_main(rank, port, rnd_lists):
+    import torch
+    import torch.distributed as dist
 
-        import torch
-        import torch.distributed as dist
+    from probqa_amd import dist as pdist
 
-        from probqa_amd import dist as pdist
-
-        case, option = config()
-        first, limit = pdist.shard_range(case.Q, WORLD, rank)
-        eng = engine_of(case, option, first, limit)
-        os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=WORLD, timeout=datetime.timedelta(seconds=120))
-        quizzes = eng.start_quiz_batch(3)            # (fresh quizzes: an answer would need the posterior's broadcast, which other tests cover)
-        res = {"batch": [], "rnds": []}
-        for rnds in rnd_lists:
-            mine = pdist.broadcast_rnds(rnds if rank == 0 else [0] * len(rnds))       # rank 0's numbers win
-            res["rnds"].append(mine)
-            res["batch"].append(pdist.next_question_sampled_batch(eng, quizzes, mine, rank, WORLD))
-            res["active"] = [eng.get_active_question_id(q) for q in quizzes]
-        res["single"] = pdist.next_question_sampled(eng, quizzes[1], rnd_lists[-1][1], rank, WORLD)
-        res["asked"] = eng.get_total_questions_asked()
-        dist.destroy_process_group()
-        eng.close()
-        out.put((rank, res))
-    except Exception as e:  # noqa: BLE001 - reported to the parent
-        out.put((rank, repr(e)))
+    case, option = config()
+    first, limit = pdist.shard_range(case.Q, WORLD, rank)
+    eng = engine_of(case, option, first, limit)
+    torch.cuda.set_device(0)
+    rc.init_group("gloo", rank, WORLD, port)
+    quizzes = eng.start_quiz_batch(3)            # (fresh quizzes: an answer would need the posterior's broadcast, which other tests cover)
+    res = {"batch": [], "rnds": []}
+    for rnds in rnd_lists:
+        mine = pdist.broadcast_rnds(rnds if rank == 0 else [0] * len(rnds))       # rank 0's numbers win
+        res["rnds"].append(mine)
+        res["batch"].append(pdist.next_question_sampled_batch(eng, quizzes, mine, rank, WORLD))
+        res["active"] = [eng.get_active_question_id(q) for q in quizzes]
+    res["single"] = pdist.next_question_sampled(eng, quizzes[1], rnd_lists[-1][1], rank, WORLD)
+    res["asked"] = eng.get_total_questions_asked()
+    dist.destroy_process_group()
+    eng.close()
+    return res
 
 
 def test_two_processes_select_over_gloo(factory):
@@ -71,33 +61,7 @@ def test_two_processes_select_over_gloo(factory):
     n_sub = sr.n_sub_of(option)
     _, draws, _ = sr.guarded_draws(case, n_sub)
     rnd_lists = [[r] * 3 for r in sb.EDGE_RNDS] + [[draws[0]] * 3]     # (every quiz is at step 0: the draw guarded for that step)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    procs = [ctx.Process(target=_rank_main, args=(r, port, rnd_lists, out)) for r in range(WORLD)]
-    for p in procs:
-        p.start()
-    got = {}
-    try:
-        for _ in range(300):                                       # (a rank that dies ends the wait at once, not a hang)
-            try:
-                rank, res = out.get(timeout=1)
-                got[rank] = res
-            except queue.Empty:
-                if any(not p.is_alive() for p in procs) and out.empty():
-                    break
-            if len(got) == WORLD:
-                break
-    finally:
-        for p in procs:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    for r in range(WORLD):   # (both ranks reported, before anything more is started on the device)
-        assert isinstance(got.get(r), dict), got.get(r)
+    got = rc.run_ranks(_rank_main, WORLD, (rc.free_port(), rnd_lists))   # (both ranks have reported before anything more is started on the device)
     whole = engine_of(case, option, 0, case.Q)
     quizzes = whole.start_quiz_batch(3)
     want = [whole.next_question_sampled_batch(quizzes, rnds) for rnds in rnd_lists]

@@ -5,16 +5,15 @@ dist.save_kb runs over gloo on the CPU against a stub engine that records what i
 import ctypes
 import os
 import re
-import socket
 import struct
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
+import abi_common as abi
+import ranks_common as rc
 from probqa_amd import dist as pdist
 from probqa_amd import interop
 
@@ -31,21 +30,16 @@ EXPORTS = {
 
 @pytest.mark.parametrize("name", sorted(EXPORTS))
 def test_header_declares_what_the_binding_declares(name):
-    text = open(os.path.join(ROOT, "include", "PqaHipExt.h")).read()
-    m = re.search(r"PQACORE_API\s+void\s*\*\s*" + name + r"\s*\(([^)]*)\)", text)
-    assert m, "PqaHipExt.h does not declare " + name
-    params = [re.sub(r"\s*\w+$", "", " ".join(a.split())).replace(" *", " *").strip() for a in m.group(1).split(",")]
+    params = [re.sub(r"\s*\w+$", "", " ".join(a.split())).replace(" *", " *").strip() for a in abi.header_params(name, r"void\s*\*").split(",")]
     assert params == EXPORTS[name][0], params
-    res, argtypes = interop.HIP_EXPORTS[name]
+    res, argtypes = abi.bound_as(name)
     assert res is _vp and argtypes == EXPORTS[name][1]
     owner, method = EXPORTS[name][2]
     assert callable(getattr(owner, method, None))
 
 
 def test_library_exports(factory):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(EXPORTS) <= exported, set(EXPORTS) - exported
+    assert set(EXPORTS) <= abi.exported_symbols(), set(EXPORTS) - abi.exported_symbols()
     lib = interop.load_library()
     for name in EXPORTS:
         assert getattr(lib, name).argtypes == EXPORTS[name][1]
@@ -167,18 +161,9 @@ class StubEngine:
             os.close(fd)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _worker(rank, world, port, folder, ret):
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rc.init_group("gloo", rank, world, port)
     out = {}
     src = os.path.join(folder, "src.kb")
     fac = StubFactory()
@@ -209,9 +194,7 @@ def _worker(rank, world, port, folder, ret):
 def test_load_shard_and_save_kb_bookkeeping_over_gloo(tmp_path, world):
     (tmp_path / "src.kb").write_bytes(struct.pack("<QqqqQ", 3 | (53 << 4) | (11 << 32), 5, Q_FILE, 7, 0))
     (tmp_path / "good.kb").write_bytes(b"stale" * 100)
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), ret), nprocs=world, join=True)
+    ret = rc.run_gloo(_worker, world, str(tmp_path))
     want = b""
     for r in range(world):
         first, limit = pdist.shard_range(Q_FILE, world, r)

@@ -7,12 +7,12 @@ import bisect
 import ctypes
 import os
 import random
-import re
-import subprocess
 
 import pytest
 
+import abi_common as abi
 import maintenance_cases as mc
+import ranks_common as rc
 from kb_model import KBModel, compact_model, random_step
 from probqa_amd import dist as pdist
 from probqa_amd import interop
@@ -29,28 +29,23 @@ EXPORTS = {
 
 @pytest.mark.parametrize("name", sorted(EXPORTS))
 def test_header_declares(name):
-    text = open(os.path.join(ROOT, "include", "PqaHipExt.h")).read()
-    m = re.search(r"PQACORE_API\s+\w+\s*\*?\s*" + name + r"\s*\(([^)]*)\)", text)
-    assert m, "PqaHipExt.h does not declare " + name
-    assert len([a for a in m.group(1).split(",") if a.strip()]) == EXPORTS[name][0], m.group(1)
+    params = abi.header_params(name)
+    assert len([a for a in params.split(",") if a.strip()]) == EXPORTS[name][0], params
 
 
 @pytest.mark.parametrize("name", sorted(EXPORTS))
 def test_binding_carries(name):
-    assert name in interop.HIP_EXPORTS
-    _, argtypes = interop.HIP_EXPORTS[name]
+    _, argtypes = abi.bound_as(name)
     assert len(argtypes) == EXPORTS[name][0]
     assert callable(getattr(interop.PqaEngine, EXPORTS[name][1], None))
 
 
 def test_library_exports(factory):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(EXPORTS) <= exported, set(EXPORTS) - exported
+    assert set(EXPORTS) <= abi.exported_symbols(), set(EXPORTS) - abi.exported_symbols()
     lib = interop.load_library()
     for name in EXPORTS:
         fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (interop.HIP_EXPORTS[name][0], interop.HIP_EXPORTS[name][1])
+        assert (fn.restype, list(fn.argtypes)) == tuple(abi.bound_as(name))
 
 
 def test_dist_has_the_collectives():
@@ -259,8 +254,7 @@ def _fake_worker(rank, world, port, ret):
     import torch.distributed as dist
 
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rc.init_group("gloo", rank, world, port)
     cpu = torch.device("cpu")
     out = {}
     first, limit = pdist.shard_range(9, world, rank)
@@ -297,16 +291,7 @@ def _fake_worker(rank, world, port, ret):
 
 
 def _run_fake(world):
-    import socket
-
-    import torch.multiprocessing as tmp
-
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ret = tmp.Manager().dict()
-    tmp.spawn(_fake_worker, args=(world, port, ret), nprocs=world, join=True)
+    ret = rc.run_gloo(_fake_worker, world)
     return [ret[r] for r in range(world)]
 
 

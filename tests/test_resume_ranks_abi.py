@@ -3,16 +3,14 @@ probqa_amd/interop.py and exported by the built libPqaCore.so; dist.row_owners a
 collective's bookkeeping (pack, combine, resume, one status word, release on a failure elsewhere) runs over gloo on the CPU
 against a fake engine that records what it is asked to do."""
 import os
-import re
-import socket
-import subprocess
 import sys
 
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
+import abi_common as abi
+import ranks_common as rc
 from probqa_amd import dist as pdist
 from probqa_amd import interop
 
@@ -28,24 +26,19 @@ EXPORTS = {
 
 @pytest.mark.parametrize("name", sorted(EXPORTS))
 def test_header_declares(name):
-    text = open(os.path.join(ROOT, "include", "PqaHipExt.h")).read()
-    m = re.search(r"PQACORE_API\s+\w+\s*\*?\s*" + name + r"\s*\(([^)]*)\)", text)
-    assert m, "PqaHipExt.h does not declare " + name
-    assert len([a for a in m.group(1).split(",") if a.strip()]) == EXPORTS[name][0], m.group(1)
+    params = abi.header_params(name)
+    assert len([a for a in params.split(",") if a.strip()]) == EXPORTS[name][0], params
 
 
 @pytest.mark.parametrize("name", sorted(EXPORTS))
 def test_binding_carries(name):
-    assert name in interop.HIP_EXPORTS
-    _, argtypes = interop.HIP_EXPORTS[name]
+    _, argtypes = abi.bound_as(name)
     assert len(argtypes) == EXPORTS[name][0]
     assert callable(getattr(interop.PqaEngine, EXPORTS[name][1], None))
 
 
 def test_library_exports(factory):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(EXPORTS) <= exported, set(EXPORTS) - exported
+    assert set(EXPORTS) <= abi.exported_symbols(), set(EXPORTS) - abi.exported_symbols()
     for name in EXPORTS:
         assert getattr(interop.load_library(), name) is not None
 
@@ -129,18 +122,9 @@ class FakeEngine:
         self.live.remove(quiz)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _fake_worker(rank, world, port, ret):
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rc.init_group("gloo", rank, world, port)
     cpu = torch.device("cpu")
     first, limit = pdist.shard_range(Q_TOTAL, world, rank)
     answered = [interop.AnsweredQuestion(q, k) for q, k in ((7, 1), (0, 2), (4, 0), (9, 3), (5, 4))]
@@ -172,10 +156,7 @@ def _fake_worker(rank, world, port, ret):
 
 
 def test_two_rank_collective_bookkeeping_over_gloo():
-    world, port = 2, _free_port()
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_fake_worker, args=(world, port, ret), nprocs=world, join=True)
+    ret = rc.run_gloo(_fake_worker, 2)
     a, b = ret[0], ret[1]
     for r in (a, b):
         assert r["package_ok"] and r["batch_package_ok"], r

@@ -2,25 +2,18 @@
 include/PqaHipExt.h, bound in probqa_amd/interop.py with their Python methods, and exported by the built libPqaCore.so.  Also
 without a GPU: the plain-Python selector of the GPU tests agrees with the oracle, and every seeded draw of those tests keeps its
 distance from the run-length boundaries (from the oracle's run lengths alone)."""
-import os
-import re
-import subprocess
-
 import pytest
 
+import abi_common as abi
 import sampled_batch_common as sb
 from probqa_amd import interop
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"PqaEngine_NextQuestionSampledBatch": 5, "PqaEngine_NextQuestionBatch": 4}
 
 
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_header_declares_sampled_batch(name):
-    text = open(os.path.join(ROOT, "include", "PqaHipExt.h")).read()
-    m = re.search(r"PQACORE_API\s+void\s*\*\s*" + name + r"\s*\(([^)]*)\)", text)
-    assert m, "PqaHipExt.h does not declare " + name
-    args = [a.strip() for a in m.group(1).split(",")]
+    args = [a.strip() for a in abi.header_params(name, r"void\s*\*").split(",")]
     assert len(args) == NAMES[name], args
     assert "int64_t *pQuestions" in args[-1] and "const" not in args[-1], args
     if name == "PqaEngine_NextQuestionSampledBatch":
@@ -29,8 +22,7 @@ def test_header_declares_sampled_batch(name):
 
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_binding_carries_sampled_batch(name):
-    assert name in interop.HIP_EXPORTS
-    _, argtypes = interop.HIP_EXPORTS[name]
+    _, argtypes = abi.bound_as(name)
     assert len(argtypes) == NAMES[name]
 
 
@@ -40,10 +32,8 @@ def test_python_methods_present():
 
 
 def test_library_exports_sampled_batch(factory):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     for name in NAMES:
-        assert name in exported
+        assert name in abi.exported_symbols()
         assert getattr(interop.load_library(), name) is not None
 
 

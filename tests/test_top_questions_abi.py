@@ -3,36 +3,30 @@ include/PqaHipExt.h, bound in probqa_amd/interop.py with their Python methods, e
 merges of the shards' lists (PqaHip_HostLogicProbe "merge_top" for the one-process sharded engine, dist.merge_top_questions for the
 process-per-GPU form) agree with a numpy sort by (-priority, index)."""
 import ctypes
-import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_common as abi
 from probqa_amd import interop
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"PqaEngine_ListTopQuestions": 5, "PqaEngine_ListTopQuestionsBatch": 6}
 
 
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_header_declares_top_questions(name):
-    text = open(os.path.join(ROOT, "include", "PqaHipExt.h")).read()
-    m = re.search(r"PQACORE_API\s+(?:int64_t|void\s*\*)\s*" + name + r"\s*\(([^)]*)\)", text)
-    assert m, "PqaHipExt.h does not declare " + name
-    args = [a.strip() for a in m.group(1).split(",")]
+    args = [a.strip() for a in abi.header_params(name, r"(?:int64_t|void\s*\*)").split(",")]
     assert len(args) == NAMES[name], args
     assert any("CiRatedQuestion" in a for a in args), args
-    s = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*CiRatedQuestion\s*;", text)
+    s = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*CiRatedQuestion\s*;", abi.header_text())
     assert s and re.search(r"int64_t\s+_iQuestion\s*;.*double\s+_priority\s*;", s.group(1), re.S), "CiRatedQuestion {int64_t _iQuestion; double _priority;}"
 
 
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_binding_carries_top_questions(name):
-    assert name in interop.HIP_EXPORTS
-    _, argtypes = interop.HIP_EXPORTS[name]
+    _, argtypes = abi.bound_as(name)
     assert len(argtypes) == NAMES[name]
 
 
@@ -44,10 +38,8 @@ def test_structure_and_python_methods():
 
 
 def test_library_exports_top_questions(factory):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", interop.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     for name in NAMES:
-        assert name in exported
+        assert name in abi.exported_symbols()
         assert getattr(interop.load_library(), name) is not None
 
 
