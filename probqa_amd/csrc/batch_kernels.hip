@@ -683,12 +683,7 @@ __global__ __launch_bounds__(64) void batch_pick_kernel(const BatchRecord *__res
   }
   if (lane != 0) return;
   const QuizSlot s = slots[b];
-  s.out->priority = bq < 0 ? 0.0 : bp;
-  s.out->index = bq < 0 ? -1 : bq + outBase;
-  if (s.seq != nullptr) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");             // system scope: the record before the flag
-    __hip_atomic_store(s.seq, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  host_publish(s.out, bq < 0 ? 0.0 : bp, bq < 0 ? -1 : bq + outBase, s.seq, flagValue);   // the record, then the flag
 }
 
 // ---- single-quiz sweep for Float engines: one 256-thread workgroup per question, lanes over targets (16 bytes per lane and

@@ -98,13 +98,28 @@ __device__ __forceinline__ void best_merge(Best &b, double op, int64_t oi) {
 __device__ __forceinline__ void best_offer(Best &b, double p, int64_t i) {
   best_merge(b, p != p ? -__builtin_huge_val() : p, i);   // NaN never wins over a number
 }
-__device__ __forceinline__ Best wave_best(Best b) {       // every lane ends up with the wave's best
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) {
-    const double op = __shfl_xor(b.p, m, kWave);
-    const int64_t oi = __shfl_xor(b.i, m, kWave);
-    best_merge(b, op, oi);
-  }
+// Every lane ends up with the wave's best: wave_sum's butterfly (pqa_device.h) -- four DPP steps inside the row of 16, then the
+// rows, then the halves by permlane swaps -- where __shfl_xor made four ds_bpermute round trips per step.  best_merge is a total
+// order over the candidates (ties to the lower index), so both partners of a step keep the same one whichever side it came from.
+template <int CTRL>
+__device__ __forceinline__ void best_step(Best &b) {
+  const double op = mov_dpp<CTRL>(b.p);
+  const int64_t oi = mov_dpp_i64<CTRL>(b.i);
+  best_merge(b, op, oi);
+}
+__device__ __forceinline__ Best wave_best(Best b) {
+  best_step<kDppXor1>(b);
+  best_step<kDppXor2>(b);
+  best_step<kDppHalfMirror>(b);
+  best_step<kDppMirror>(b);
+  Pair p = swap16(b.p);
+  PairI64 i = swap16_i64(b.i);
+  b = Best{p.a, i.a};
+  best_merge(b, p.b, i.b);
+  p = swap32(b.p);
+  i = swap32_i64(b.i);
+  b = Best{p.a, i.a};
+  best_merge(b, p.b, i.b);
   return b;
 }
 
@@ -193,12 +208,10 @@ __device__ __forceinline__ void fused_select(const EvalArgs &a, Best mine, int l
   }
   if (deferred) return;
   if (UNI || lane == 0) {
-    a.fs.out->priority = b.i < 0 ? 0.0 : b.p;
-    a.fs.out->index = !complete ? -3 : redo ? -4 : b.i < 0 ? -1 : b.i + a.fs.outBase;
-    if (a.fs.seq != nullptr) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // system scope: the record is visible to the host before the flag
-      __hip_atomic_store(a.fs.seq, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    // the record, write-through, and behind its acknowledgement the flag the host polls: no fence (pqa_device.h: host_publish)
+    // (the engine's own cell: record and tag in one granule -- select_record.h)
+    if (a.fs.packed) host_publish_packed(a.fs.out, b.i < 0 ? 0.0 : b.p, flagValue, !complete ? -3 : redo ? -4 : b.i < 0 ? -1 : b.i);
+    else host_publish(a.fs.out, b.i < 0 ? 0.0 : b.p, !complete ? -3 : redo ? -4 : b.i < 0 ? -1 : b.i + a.fs.outBase, a.fs.seq, flagValue);
     if (a.fs.tagCell != nullptr) {  // every workgroup has read the cell (it published): the next replay gets the next tag
       uint64_t next = seqValue + 1;
       if ((uint32_t)next == 0) next++;
@@ -819,12 +832,8 @@ __device__ __forceinline__ void sweep_body(EvalArgs a, bool copyTable) {
       __syncthreads();
       const bool complete = allReported[0], deferred = allReported[1], redo = allReported[2];
       if (!deferred && (SERVER ? wave == 0 : tid == 0)) {
-        a.fs.out->priority = 0.0;
-        a.fs.out->index = !complete ? -3 : redo ? -4 : 0;
-        if (a.fs.seq != nullptr) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-          __hip_atomic_store(a.fs.seq, a.fs.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (a.fs.packed) host_publish_packed(a.fs.out, 0.0, a.fs.flagValue, !complete ? -3 : redo ? -4 : 0);
+        else host_publish(a.fs.out, 0.0, !complete ? -3 : redo ? -4 : 0, a.fs.seq, a.fs.flagValue);
       }
     }
     return;
@@ -839,12 +848,8 @@ __device__ __forceinline__ void sweep_body(EvalArgs a, bool copyTable) {
       const SampledPick r = select_sampled_wg_lds<true>(a.priority, a.qgap, a.asked, a.qFirst, a.qLimit - a.qFirst,
                                                         a.fs.sampleSubtasks, a.fs.sampleRnd, tbl);
       if (tid == 0) {
-        a.fs.out->priority = r.priority;
-        a.fs.out->index = complete ? r.index + a.fs.outBase : -3;
-        if (a.fs.seq != nullptr) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-          __hip_atomic_store(a.fs.seq, a.fs.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (a.fs.packed) host_publish_packed(a.fs.out, r.priority, a.fs.flagValue, complete ? r.index : -3);
+        else host_publish(a.fs.out, r.priority, complete ? r.index + a.fs.outBase : -3, a.fs.seq, a.fs.flagValue);
       }
     }
   }
@@ -978,7 +983,8 @@ void eval_server_f64(EvalArgs a, ServerMailbox *mb, uint32_t *requestLine, int e
     b.fs.seq = reinterpret_cast<uint64_t *>(uniform64(reinterpret_cast<const uint64_t *>(step)[4]));
     b.fs.flagValue = uniform64(reinterpret_cast<const uint64_t *>(step)[5]);
     const uint64_t ob = uniform64(reinterpret_cast<const uint64_t *>(step)[6]);
-    b.fs.outBase = (int64_t)(ob & ~(kServerHandOver | kServerNoWatch));
+    b.fs.outBase = (int64_t)(ob & ~(kServerHandOver | kServerNoWatch | kServerPacked));
+    b.fs.packed = (ob & kServerPacked) ? 1 : 0;
     b.serverNoWatch = (ob & kServerNoWatch) != 0;
     b.fs.sampleSubtasks = (ob & kServerHandOver) ? 1 : 0;   // the priority vector goes to the host (FusedSelect::hostPriority), no argmax
     b.fs.seqValue = go;
@@ -1277,12 +1283,7 @@ __global__ __launch_bounds__(256) void batch_repick_kernel(const int64_t *__rest
     if (bq < 0 || p > bp || (p == bp && q < bq)) { bp = p; bq = q; }
   }
   const QuizSlot s = slots[b];
-  s.out->priority = bq < 0 ? 0.0 : bp;
-  s.out->index = bq < 0 ? -1 : bq + outBase;
-  if (s.seq != nullptr) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");             // system scope: the record before the flag
-    __hip_atomic_store(s.seq, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  host_publish(s.out, bq < 0 ? 0.0 : bp, bq < 0 ? -1 : bq + outBase, s.seq, flagValue);   // the record, then the flag
 }
 
 size_t BatchRerankScratchBytes() { return (size_t)256 * kRerank * (sizeof(int64_t) + sizeof(double)); }

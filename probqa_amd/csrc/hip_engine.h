@@ -465,12 +465,15 @@ class HipEngine : public IEngine {
   std::unordered_map<Quiz *, GraphEntry> _graphs;  // option "use_graph"
   SelectResult *_dGraphScratch = nullptr;
   uint64_t *_dTagCell = nullptr;
-  // The launched, graph-replayed and resident selections all report through _hPinned->sel / ->seq, each waiting for "its" value of
-  // the flag: the three sequences live in disjoint ranges, or a selection would find the flag already holding its value -- left by
-  // another path's earlier selection -- and return that one's question (graph tag 1, then the resident sweep's first request, also
-  // 1: found by the soak of tools/stress_more.py).  Launch tags (NextLaunchTag) count from 1 and stay below 2^40.
-  static constexpr uint64_t kGraphFlagBase = 1ull << 40, kServerFlagBase = 2ull << 40;
+  // The launched, graph-replayed and resident selections each report through a packed record of their OWN in _hPinned->own[]
+  // (select_record.h: the record carries 32 bits of its launch's tag, there is no flag), each waiting for "its" tag: with one record
+  // for all three a selection would find it already carrying its tag -- left by another path's earlier selection -- and return that
+  // one's question (graph tag 1, then the resident sweep's first request, also 1: found by the soak of tools/stress_more.py, when
+  // the paths shared a record and a flag).  The graph's tags keep the range of their own that told the flag's values apart then.
+  static constexpr uint64_t kGraphFlagBase = 1ull << 40;
   uint64_t _graphTag = kGraphFlagBase + 1;
+  uint64_t _serverTag = 0;   // of the resident sweep's last packed answer (NextSelectionTag)
+  enum OwnCell { kOwnLaunched = 0, kOwnGraph = 1, kOwnResident = 2 };
   void DropQuizBufferPool();
   SelectResult *_dSel = nullptr;
   struct Pinned {  // host-coherent: written by kernels, polled / read by the host without copies
@@ -481,7 +484,9 @@ class HipEngine : public IEngine {
     int64_t nOutQ;                 // ListTopQuestions of one quiz: lines of its own, so that a ListTopTargets between its two halves
     uint64_t topQFlag;             // (sharded engine) lists into top[] without touching them
     RatedTargetDev topQ[256];
+    PackedSelection own[3];        // the engine's own selections, by path (OwnCell); decoded into `sel` by WaitPacked
   };
+  SelectResult *OwnRecord(OwnCell c) { return reinterpret_cast<SelectResult *>(&_hPinned->own[c]); }
   // (Pinned::top: listings of more than kQuizTop targets; up to kQuizTop the quiz's own lines are used, where RecordAnswer's
   //  kernel lists the new posterior's best targets ahead of the ListTopTargets for the same quiz and posterior)
   uint64_t _opSeq = 0;
@@ -591,6 +596,9 @@ class HipEngine : public IEngine {
   volatile uint64_t *_pendingRecordFlag = nullptr;   // where _pendingRecordOp will appear
   // spin on a host-coherent flag until it holds `value` (the kernel's last store); falls back to the stream's status
   Error WaitFlag(volatile uint64_t *flag, uint64_t value, const char *what);
+  // the same wait for a packed record (FusedSelect::packed; resident: one the resident sweep answers): until it carries `tag`, then
+  // {priority, index + outBase or -1 / -3 / -4} into _hPinned->sel, where the callers look
+  Error WaitPacked(SelectResult *record, uint64_t tag, int64_t outBase, const char *what, bool resident = false);
   Error WaitFlagNapping(volatile uint64_t *flag, uint64_t value, const char *what);   // for many waiters at once: a short spin, then naps
   SelectResult *_dSelScratch = nullptr;  // its per-workgroup winner records
   double *_dPriorScratch = nullptr;      // the long-row posterior kernels' subtask sums (KbView::priorScratch)
@@ -778,7 +786,6 @@ class HipEngine : public IEngine {
   uint64_t _pendingRecordOp = 0;          // RecordAnswer's kernel is the newest work on _stream and publishes this op number
   bool ServerUsable() const;
   Error ServerPost(Quiz *q, SelectResult *out, uint64_t *flag, uint64_t flagValue, int64_t outBase);
-  Error ServerWait(volatile uint64_t *flag, uint64_t value, const char *what);
   void StopServer();
   void ServerQuiesce();   // returns once the posted step (if any) has finished: before anything that writes what it reads
   SelectorRng _rng;         // NextQuestion's random numbers, drawn under _rngMu

@@ -168,7 +168,7 @@ Error HipEngine::LaunchSingleSweep(Quiz *q, const FusedSelect *fused) {
     }
     HIP_TRY(LaunchEvalCluster(View(), q->dPrior, q->dAsked, _dPriority, _dClusterScratch, _stream));
     if (fused != nullptr)
-      HIP_TRY(LaunchSelectArgmax(_dPriority, _dQGap, q->dAsked, 0, _Q, fused->outBase, fused->out, fused->seq, fused->flagValue, _stream));
+      HIP_TRY(LaunchSelectArgmax(_dPriority, _dQGap, q->dAsked, 0, _Q, fused->outBase, fused->out, fused->seq, fused->flagValue, _stream, fused->packed != 0));
     return Error();
   }
   if (_elem == 8) {
@@ -188,7 +188,7 @@ Error HipEngine::LaunchSingleSweep(Quiz *q, const FusedSelect *fused) {
   else
     HIP_TRY(LaunchEvalQuestionsF32(View(), q->dPrior, q->dAsked, _dPriority, _stream));
   if (fused != nullptr)
-    HIP_TRY(LaunchSelectArgmax(_dPriority, _dQGap, q->dAsked, 0, _Q, fused->outBase, fused->out, fused->seq, fused->flagValue, _stream));
+    HIP_TRY(LaunchSelectArgmax(_dPriority, _dQGap, q->dAsked, 0, _Q, fused->outBase, fused->out, fused->seq, fused->flagValue, _stream, fused->packed != 0));
   return Error();
 }
 
@@ -295,6 +295,30 @@ Error HipEngine::WaitFlag(volatile uint64_t *flag, uint64_t value, const char *w
   return Error();
 }
 
+// The engine's own selections: the record carries its launch's tag (select_record.h) -- polled tag-first, as CollectHostPriority
+// takes a TaggedPriority -- and is then taken OUT of its cell (tag 0: no launch's), so that no later wait can accept it again.
+Error HipEngine::WaitPacked(SelectResult *record, uint64_t tag, int64_t outBase, const char *what, bool resident) {
+  volatile PackedSelection *cell = reinterpret_cast<volatile PackedSelection *>(record);
+  volatile ServerMailbox *mb = _hMailbox;
+  SpinWait w;
+  while (!PackedCarries(cell->tagAnswer, tag)) {
+    if (!w.Tick(std::chrono::seconds(30))) return HipErr(hipErrorNotReady, what);
+    if (!w.Due()) continue;
+    if (resident) {   // (the resident sweep left without this request's answer)
+      if (mb->state == kServerExited && mb->taken != _serverPosted && !PackedCarries(cell->tagAnswer, tag)) return HipErr(hipErrorUnknown, what);
+    } else if (hipStreamQuery(_stream) == hipSuccess && !PackedCarries(cell->tagAnswer, tag)) {  // the kernel retired without publishing
+      const hipError_t he = hipStreamSynchronize(_stream);
+      if (he != hipSuccess || !PackedCarries(cell->tagAnswer, tag)) return HipErr(he == hipSuccess ? hipErrorUnknown : he, what);
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const uint64_t tagAnswer = cell->tagAnswer, bits = cell->priorityBits;
+  cell->tagAnswer = 0;
+  std::memcpy(&_hPinned->sel.priority, &bits, sizeof(bits));
+  _hPinned->sel.index = UnpackSelection(tagAnswer, outBase);
+  return Error();
+}
+
 int64_t HipEngine::NextQuestionArgmax(Error &err, int64_t iQuiz) { return Combine(err, iQuiz, 0, 0); }
 
 // Synchronous single-quiz selections of a Double engine through a register shape (whose finisher knows whether anything was listed):
@@ -315,7 +339,7 @@ Error HipEngine::RunLazyFix(Quiz *q, const FusedSelect &swept, const char *what)
   fs.lazyFix = 0;
   fs.flagValue = NextLaunchTag();   // (the records of a hand-over keep the sweep's tag, seqValue)
   HIP_TRY(LaunchEvalPoleFixup(View(), q->dPrior, q->dAsked, _dPriority, fs, _stream));
-  Error err = WaitFlag(fs.seq, fs.flagValue, what);
+  Error err = fs.packed ? WaitPacked(fs.out, fs.flagValue, fs.outBase, what) : WaitFlag(fs.seq, fs.flagValue, what);
   std::atomic_thread_fence(std::memory_order_acquire);
   if (err.ok()) _poleListPending = false;   // (the fix-up has emptied the list)
   return err;
@@ -333,9 +357,9 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   if (_opt.useGraph && _elem == 8) return NextQuestionArgmaxGraph(err, q);
   if (_opt.server && !q->noServer && ServerUsable()) {
     // resident sweep: post the request, poll the answer -- no launch on the critical path
-    const uint64_t value = kServerFlagBase | ++_opSeq;   // (its own range: see kGraphFlagBase)
-    err = ServerPost(q, &_hPinned->sel, &_hPinned->seq, value, 0);
-    if (err.ok()) err = ServerWait(&_hPinned->seq, value, "NextQuestionArgmax");
+    const uint64_t value = _serverTag = NextSelectionTag(_serverTag);   // (its own record: see kGraphFlagBase)
+    err = ServerPost(q, OwnRecord(kOwnResident), &_hPinned->seq, value, (int64_t)kServerPacked);
+    if (err.ok()) err = WaitPacked(OwnRecord(kOwnResident), value, 0, "NextQuestionArgmax", true);
     if (!err.ok()) return -1;
     if (_hPinned->sel.index == -3) {
       err = HipErr(hipErrorLaunchFailure, "NextQuestionArgmax (incomplete sweep)");
@@ -354,15 +378,14 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   if (TakeSpeculation(q, 1 << 1, &seq) != 0) fs = _spec.fs;   // (RecordAnswer has launched this very sweep already)
   else {
     seq = NextLaunchTag();
-    fs = FusedSelect{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, 0, 0, nullptr, nullptr, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
+    fs = FusedSelect{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, 0, 0, nullptr, nullptr, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0, 1};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
     StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
     err = LaunchSingleSweep(q, &fs);
     if (!err.ok()) return -1;
     if (fs.lazyFix) _poleListPending = true;   // (whatever it lists stays listed until the fix has run or the sweep has said "nothing": a wait that fails leaves it for SettlePoleList)
   }
-  err = WaitFlag(&_hPinned->seq, seq, "NextQuestionArgmax");
+  err = WaitPacked(fs.out, seq, 0, "NextQuestionArgmax");
   if (!err.ok()) return -1;
-  std::atomic_thread_fence(std::memory_order_acquire);
   if (fs.lazyFix) {
     if (_hPinned->sel.index == -4) {   // the sweep listed rows at the pole of the lack term: the fix now, and its answer
       err = RunLazyFix(q, fs, "NextQuestionArgmax");   // (clears the mark once the fix has emptied the list)
@@ -842,7 +865,7 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
   if (it == _graphs.end() || it->second.variant != _opt.evalVariant || it->second.stream != _stream ||
       it->second.kbVersion != _kbVersion) {
     if (it != _graphs.end()) { hipGraphExecDestroy(it->second.exec); _graphs.erase(it); }
-    const FusedSelect fs{_dGraphScratch, &_hPinned->sel, &_hPinned->seq, 0, 0, 0, 0, _dTagCell, 0, 0, nullptr, nullptr};
+    const FusedSelect fs{_dGraphScratch, OwnRecord(kOwnGraph), &_hPinned->seq, 0, 0, 0, 0, _dTagCell, 0, 0, nullptr, nullptr, 0, 1};
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipError_t he = hipStreamBeginCapture(_stream, hipStreamCaptureModeThreadLocal);
@@ -862,10 +885,8 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
   if (!err.ok()) return -1;
   const hipError_t he = hipGraphLaunch(it->second.exec, _stream);
   if (he != hipSuccess) { err = HipErr(he, "hipGraphLaunch"); return -1; }
-  uint64_t next = _graphTag + 1;                     // the finisher's own rule (fused_select)
-  if ((uint32_t)next == 0) next++;
-  _graphTag = next;
-  err = WaitFlag(&_hPinned->seq, expect, "NextQuestionArgmax (graph)");
+  _graphTag = NextSelectionTag(_graphTag);           // the finisher's own rule (fused_select)
+  err = WaitPacked(OwnRecord(kOwnGraph), expect, 0, "NextQuestionArgmax (graph)");
   if (!err.ok()) return -1;
   if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionArgmax (incomplete sweep)"); return -1; }
   CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);
@@ -886,9 +907,9 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
   const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
   if (_opt.server && !q->noServer && _opt.hostSampled && !_opt.fusedSampled && ServerUsable()) {
     // resident sweep: post the request with the hand-over mark, poll the flag, select on the host -- no launch on the path
-    const uint64_t value = kServerFlagBase | ++_opSeq;   // (its own range: see kGraphFlagBase)
-    err = ServerPost(q, &_hPinned->sel, &_hPinned->seq, value, (int64_t)kServerHandOver);
-    if (err.ok()) err = ServerWait(&_hPinned->seq, value, "NextQuestionSampled");
+    const uint64_t value = _serverTag = NextSelectionTag(_serverTag);   // (its own record: see kGraphFlagBase)
+    err = ServerPost(q, OwnRecord(kOwnResident), &_hPinned->seq, value, (int64_t)(kServerHandOver | kServerPacked));
+    if (err.ok()) err = WaitPacked(OwnRecord(kOwnResident), value, 0, "NextQuestionSampled", true);
     if (!err.ok()) return -1;
     if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionSampled (incomplete sweep)"); return -1; }
     if (_hPinned->sel.index != -4) {
@@ -915,12 +936,12 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     else {
       { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
       seq = NextLaunchTag();
-      fs = FusedSelect{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, 1, 0, nullptr, _hHostPriority, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
+      fs = FusedSelect{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, 1, 0, nullptr, _hHostPriority, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0, 1};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
       const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
       if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
       if (fs.lazyFix) _poleListPending = true;   // (as NextQuestionArgmaxLocked)
     }
-    err = WaitFlag(&_hPinned->seq, seq, "NextQuestionSampled");
+    err = WaitPacked(fs.out, seq, 0, "NextQuestionSampled");
     if (!err.ok()) return -1;
     if (fs.lazyFix) {
       if (_hPinned->sel.index == -4) {   // (as NextQuestionArgmaxLocked: the corrected entries carry the sweep's tag)
@@ -942,10 +963,10 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     // ONE launch: the sweep's finisher workgroup runs the reference's selector once every workgroup has reported
     { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
     const uint64_t seq = NextLaunchTag();
-    const FusedSelect fs{_dSelScratch, &_hPinned->sel, &_hPinned->seq, seq, 0, 0, seq, nullptr, nSub, rnd, _dRunLength, nullptr};
+    const FusedSelect fs{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, nSub, rnd, _dRunLength, nullptr, 0, 1};
     const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
     if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
-    err = WaitFlag(&_hPinned->seq, seq, "NextQuestionSampled");
+    err = WaitPacked(fs.out, seq, 0, "NextQuestionSampled");
     if (!err.ok()) return -1;
     if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionSampled (incomplete sweep)"); return -1; }
     CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);

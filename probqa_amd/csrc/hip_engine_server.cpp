@@ -29,17 +29,6 @@ void HipEngine::ServerQuiesce() {
     if (!w.Tick(std::chrono::seconds(30))) return;
 }
 
-Error HipEngine::ServerWait(volatile uint64_t *flag, uint64_t value, const char *what) {
-  SpinWait w;
-  volatile ServerMailbox *mb = _hMailbox;
-  while (*flag != value) {
-    if (!w.Tick(std::chrono::seconds(30))) return HipErr(hipErrorNotReady, what);
-    if (w.Due() && mb->state == kServerExited && mb->taken != _serverPosted && *flag != value) return HipErr(hipErrorUnknown, what);
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return Error();
-}
-
 // Post one selection request for quiz `q`; the finisher writes {priority, index + outBase} to `out` and then flagValue to
 // `flag` (host-coherent memory).  Starts the kernel if none is resident.
 Error HipEngine::ServerPost(Quiz *q, SelectResult *out, uint64_t *flag, uint64_t flagValue, int64_t outBase) {

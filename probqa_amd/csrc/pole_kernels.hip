@@ -422,11 +422,17 @@ __global__ __launch_bounds__(kFixThreads) __attribute__((amdgpu_waves_per_eu(PQA
       outI = r.index + a.fs.outBase;
     }
     if (tid == 0) {
-      a.fs.out->priority = outP;
-      a.fs.out->index = outI;
-      if (a.fs.seq != nullptr) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");          // system scope: the record (and the handed-over priorities) before the flag
-        __hip_atomic_store(a.fs.seq, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (a.fs.packed) {
+        // the engine's own cell (outBase 0): one tagged granule.  No fence: the corrected records of a hand-over were acknowledged before
+        // their workgroups arrived (__threadfence_system above), the corrected priorities are read by later launches only.
+        host_publish_packed(a.fs.out, outP, flagValue, outI);
+      } else {
+        a.fs.out->priority = outP;
+        a.fs.out->index = outI;
+        if (a.fs.seq != nullptr) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");          // system scope: the record (and the handed-over priorities) before the flag
+          __hip_atomic_store(a.fs.seq, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
       }
       if (a.fs.tagCell != nullptr) {
         uint64_t next = seqValue + 1;
@@ -456,12 +462,7 @@ __global__ __launch_bounds__(kFixThreads) __attribute__((amdgpu_waves_per_eu(PQA
         }
       }
       if (lane == 0) {
-        qs.out->priority = handOver || best.i < 0 ? 0.0 : best.p;
-        qs.out->index = handOver ? 0 : best.i < 0 ? -1 : best.i + a.fs.outBase;
-        if (qs.seq != nullptr) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-          __hip_atomic_store(qs.seq, a.fs.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        host_publish(qs.out, handOver || best.i < 0 ? 0.0 : best.p, handOver ? 0 : best.i < 0 ? -1 : best.i + a.fs.outBase, qs.seq, a.fs.flagValue);
       }
     }
   }

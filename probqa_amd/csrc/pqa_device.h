@@ -8,6 +8,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "select_record.h"
+
 namespace pqa {
 
 constexpr int kWave = 64;  // CDNA wavefront
@@ -263,6 +265,59 @@ __device__ __forceinline__ double wave_sum(double v) {
   v = p.a + p.b;
   p = swap32(v);
   return p.a + p.b;
+}
+
+// The same moves for a 64-bit integer (the index half of a {priority, index} pair: eval_kernels.hip, wave_best)
+template <int CTRL>
+__device__ __forceinline__ int64_t mov_dpp_i64(int64_t v) {
+  int lo = (int)(uint32_t)(uint64_t)v, hi = (int)(uint32_t)((uint64_t)v >> 32);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
+  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+}
+struct PairI64 { int64_t a, b; };   // (a, b: the same sides as Pair's -- the two halves of a pair travel together)
+__device__ __forceinline__ PairI64 swap16_i64(int64_t v) {
+  const uint64_t b = (uint64_t)v;
+  const auto r0 = __builtin_amdgcn_permlane16_swap((uint32_t)b, (uint32_t)b, false, false);
+  const auto r1 = __builtin_amdgcn_permlane16_swap((uint32_t)(b >> 32), (uint32_t)(b >> 32), false, false);
+  return PairI64{(int64_t)(((uint64_t)r1[0] << 32) | r0[0]), (int64_t)(((uint64_t)r1[1] << 32) | r0[1])};
+}
+__device__ __forceinline__ PairI64 swap32_i64(int64_t v) {
+  const uint64_t b = (uint64_t)v;
+  const auto r0 = __builtin_amdgcn_permlane32_swap((uint32_t)b, (uint32_t)b, false, false);
+  const auto r1 = __builtin_amdgcn_permlane32_swap((uint32_t)(b >> 32), (uint32_t)(b >> 32), false, false);
+  return PairI64{(int64_t)(((uint64_t)r1[0] << 32) | r0[0]), (int64_t)(((uint64_t)r1[1] << 32) | r0[1])};
+}
+
+// ---- publishing to a polling host -----------------------------------------------------------------------------------
+// A result and then its flag, both in host-coherent memory.  The payload goes out as system-scope (sc0 sc1) stores: they
+// are written through to the host as they are issued, so there is nothing for a release fence to write back -- the fence
+// still walks this XCD's L2 (~1.7 us) before it waits.  What orders the flag behind the payload is the wait for the
+// payload stores' acknowledgements: inline asm, which the compiler neither drops nor moves memory operations across.
+// Every wave that stored part of a payload runs host_stores_done() (and, where another wave raises the flag, a workgroup
+// barrier) before host_flag().  Payloads that are, or may be, device memory read by a later load keep their fences.
+__device__ __forceinline__ void host_store(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ void host_store(int64_t *p, int64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ void host_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void host_flag(uint64_t *flag, uint64_t value) {
+  host_stores_done();
+  __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// a {priority, index} record (SelectResult and its like) by one lane, then the flag (null: none -- the stream's order does)
+template <class Rec>
+__device__ __forceinline__ void host_publish(Rec *out, double priority, int64_t index, uint64_t *flag, uint64_t flagValue) {
+  host_store(&out->priority, priority);
+  host_store(&out->index, index);
+  if (flag != nullptr) host_flag(flag, flagValue);
+}
+
+// The engine's own selections (select_record.h): record and tag in one 16-byte granule -- one store, nothing to order.  Every lane
+// that calls stores the same record to the same address.
+__device__ __forceinline__ void host_publish_packed(void *rec, double priority, uint64_t tag, int64_t localIndex) {
+  typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+  const uint64_t w0 = d2u(priority), w1 = PackSelection(tag, localIndex);
+  const u4 v = {(unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32)};
+  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(rec), "v"(v) : "memory");
 }
 
 // The same for a float: 4 DPP steps, 2 permlane swaps -- six full-rate instruction pairs instead of the six ds_bpermute round
@@ -707,6 +762,9 @@ __device__ __forceinline__ void top_targets_publish(const double *prior, const u
   if (threadIdx.x == 0) {
     *nOut = listed;
     if (flag != nullptr) {  // the host polls: no copy, no synchronise
+      // The fence stays (host_publish is not for this flag): behind RecordAnswer the flag also stands for the new POSTERIOR, plain
+      // stores to device memory by this workgroup -- the host posts the quiz's next request to the resident sweep, which no stream
+      // orders behind this kernel, as soon as it sees it (hip_engine_server.cpp: ServerPost, _pendingRecordFlag).
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
       __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }

@@ -16,6 +16,8 @@
 
 #include <atomic>
 
+#include "select_record.h"
+
 namespace pqa {
 
 constexpr size_t kLdsPerCU = 160 * 1024;     // LDS of a CU (gfx950)
@@ -178,6 +180,9 @@ struct FusedSelect {
   // that saw suspects publishes index -4 instead of leaving the publication to the fix; the caller then launches
   // LaunchEvalPoleFixup (same arguments, a new flagValue) and waits again.  A fresh quiz's selections so cost one launch, not two.
   int64_t lazyFix;
+  // The engine's own pinned cell as destination (select_record.h): `out` is a PackedSelection -- {priority, low 32 bits of flagValue :
+  // local index or code} in ONE write-through store, no fence, no flag (`seq` is not written), outBase added by the host.
+  int64_t packed;
 };
 // One quiz of a batched sweep (blockIdx.y selects it): everything that differs between the quizzes of one launch.
 struct QuizSlot {
@@ -352,6 +357,8 @@ constexpr uint64_t kServerHandOver = 1ull << 62;
 // a step that found one with index -4 -- the caller then takes the launched path, behind which the fix can run; a request whose outBase
 // carries kServerNoWatch is answered as if nothing had been found.
 constexpr uint64_t kServerNoWatch = 1ull << 61;
+// ... kServerPacked: `out` is a PackedSelection (FusedSelect::packed), tagged with the low 32 bits of flagValue.
+constexpr uint64_t kServerPacked = 1ull << 60;
 hipError_t LaunchEvalServer(const KbView &kb, int64_t qFirst, int64_t qLimit, double *priority, int variant,
                             SelectResult *scratch, ServerMailbox *mailbox, void *requestLine, bool everyonePolls,
                             ServerCtl *ctl, uint64_t lastSeq, uint64_t idleTicks, TaggedPriority *hostPriority, hipStream_t stream,
@@ -372,7 +379,8 @@ hipError_t LaunchEvalQuestionsWithUpdate(const KbView &kb, double *prior, uint32
 // (position in priority[]) + outBase
 hipError_t LaunchSelectArgmax(const double *priority, const uint32_t *qgap, const uint32_t *asked, int64_t qFirst,
                               int64_t n, int64_t outBase, SelectResult *out, uint64_t *flag, uint64_t flagValue,
-                              hipStream_t stream);   // flag (optional, host-coherent): receives flagValue after `out`
+                              hipStream_t stream, bool packed = false);   // flag (optional, host-coherent): receives flagValue after `out`;
+                                                                          // packed: `out` is a PackedSelection instead (FusedSelect::packed)
 // Reference selector (PqaCore/CpuEngine.cpp:362-400): per-subtask Kahan run lengths, grand totals, upper_bound.
 // runLength: scratch of n doubles. rnd: the 64-bit random number the reference would draw.
 hipError_t LaunchSelectSampled(const double *priority, const uint32_t *qgap, const uint32_t *asked, int64_t qFirst,

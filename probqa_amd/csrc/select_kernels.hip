@@ -27,7 +27,7 @@ __global__ __launch_bounds__(1024) void select_argmax_kernel(const double *__res
                                                              const uint32_t *__restrict__ qgap,
                                                              const uint32_t *__restrict__ asked, int64_t qFirst,
                                                              int64_t n, int64_t outBase, SelectResult *out, uint64_t *flag,
-                                                             uint64_t flagValue) {
+                                                             uint64_t flagValue, int packed) {
   __shared__ double sp[16];
   __shared__ int64_t si[16];
   Best b = {0.0, -1};
@@ -59,12 +59,10 @@ __global__ __launch_bounds__(1024) void select_argmax_kernel(const double *__res
       const Best c = {sp[w], si[w]};
       if (better(c, r)) r = c;
     }
-    out->priority = r.p;
-    out->index = r.i < 0 ? -1 : r.i - qFirst + outBase;
-    if (flag != nullptr) {  // `out` and `flag` in host-coherent memory: the host polls instead of copying + synchronising
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    // `out` and `flag` (where given) in host-coherent memory: the host polls instead of copying + synchronising
+    // (packed: the engine's own cell -- one tagged granule, the host adds outBase: select_record.h)
+    if (packed) host_publish_packed(out, r.p, flagValue, r.i < 0 ? -1 : r.i - qFirst);
+    else host_publish(out, r.p, r.i < 0 ? -1 : r.i - qFirst + outBase, flag, flagValue);
   }
 }
 
@@ -76,12 +74,8 @@ __global__ __launch_bounds__(1024) void select_sampled_kernel(const double *__re
   extern __shared__ double grand[];  // nSubtasks doubles
   const SampledPick r = select_sampled_wg_impl<false>(priority, qgap, asked, qFirst, n, nWorkers, rnd, runLength, grand);
   if (threadIdx.x == 0) {
-    out->priority = r.priority;
-    out->index = r.index;
-    if (flag != nullptr) {  // `out` and `flag` in host-coherent memory: the host polls instead of copying + synchronising
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    // `out` and `flag` (where given) in host-coherent memory: the host polls instead of copying + synchronising
+    host_publish(out, r.priority, r.index, flag, flagValue);
   }
 }
 
@@ -96,12 +90,7 @@ __global__ __launch_bounds__(256) void select_sampled_lds_kernel(const double *_
   extern __shared__ double lds[];
   const SampledPick r = select_sampled_wg_lds<false>(priority, qgap, asked, qFirst, n, nWorkers, rnd, lds);
   if (threadIdx.x == 0) {
-    out->priority = r.priority;
-    out->index = r.index;
-    if (flag != nullptr) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    host_publish(out, r.priority, r.index, flag, flagValue);
   }
 }
 
@@ -119,10 +108,7 @@ __global__ __launch_bounds__(256) void select_sampled_batch_vec_kernel(SampledBa
   if constexpr (LDS) r = select_sampled_wg_lds<false>(s.priority, a.qgap, s.asked, 0, a.n, a.nWorkers, rnd, lds);
   else r = select_sampled_wg_impl<false>(s.priority, a.qgap, s.asked, 0, a.n, a.nWorkers, rnd, a.run + (size_t)b * (size_t)a.n, lds);
   if (threadIdx.x == 0) {
-    a.out[b].priority = r.priority;
-    a.out[b].index = r.index + a.outBase;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    __hip_atomic_store(a.seq + b, a.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    host_publish(a.out + b, r.priority, r.index + a.outBase, a.seq + b, a.flagValue);
   }
 }
 
@@ -208,10 +194,7 @@ __global__ __launch_bounds__(64) void select_sampled_lanes_finish_kernel(Sampled
     sel = first + upper_bound_strided(run, limit - first, Bp, inWorkerRunLen);                      // :391
     if (sel >= limit) sel = limit - 1;                         // :392-400
   }
-  a.out[b].priority = totG;
-  a.out[b].index = sel + a.outBase;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-  __hip_atomic_store(a.seq + b, a.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  host_publish(a.out + b, totG, sel + a.outBase, a.seq + b, a.flagValue);
 }
 
 // ---- the same selector over shards that separate processes drive: selection parts (sampled_part.h) ---------------------------------
@@ -355,10 +338,7 @@ __global__ __launch_bounds__(64) void sampled_pick_parts_kernel(SampledPartsPick
   __syncthreads();
   if (bad != 0) {
     if (t == 0) {
-      a.out[b].priority = 0.0;
-      a.out[b].index = (bad & 1) ? -2 : -3;   // a stale part first: its header is not to be believed
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      __hip_atomic_store(a.flags + b, a.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      host_publish(a.out + b, 0.0, (bad & 1) ? -2 : -3, a.flags + b, a.flagValue);   // a stale part first: its header is not to be believed
     }
     return;
   }
@@ -416,20 +396,17 @@ __global__ __launch_bounds__(64) void sampled_pick_parts_kernel(SampledPartsPick
       sel = -1;                                                // whole on another rank: that rank reports it
     }
   }
-  a.out[b].priority = totG;
-  a.out[b].index = sel;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-  __hip_atomic_store(a.flags + b, a.flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  host_publish(a.out + b, totG, sel, a.flags + b, a.flagValue);
 }
 
 }  // namespace
 
 hipError_t LaunchSelectArgmax(const double *priority, const uint32_t *qgap, const uint32_t *asked, int64_t qFirst,
                               int64_t n, int64_t outBase, SelectResult *out, uint64_t *flag, uint64_t flagValue,
-                              hipStream_t stream) {
+                              hipStream_t stream, bool packed) {
   const unsigned threads = n >= 1024 ? 1024 : (unsigned)(((n + 63) / 64) * 64 ? ((n + 63) / 64) * 64 : 64);
   hipLaunchKernelGGL(select_argmax_kernel, dim3(1), dim3(threads), 0, stream, priority, qgap, asked, qFirst, n,
-                     outBase, out, flag, flagValue);
+                     outBase, out, flag, flagValue, packed ? 1 : 0);
   return hipGetLastError();
 }
 
