@@ -1526,7 +1526,7 @@ static EvalArgs make_args(const KbView &kb, int64_t qFirst, int64_t qLimit) {
   args.qFirst = qFirst;
   args.qLimit = qLimit;
   args.vCompTail = VCompTail(kb);
-  args.fs = FusedSelect{nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr};
+  args.fs = FusedSelect{};
   args.slots = nullptr;
   args.maxGrid = kb.maxGrid;
   args.poleNoFollow = kb.poleNoFollow;

@@ -11,7 +11,6 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <functional>
 #include <cstdint>
 #include <memory>
 #include <mutex>
@@ -26,6 +25,7 @@
 #include "engine_interface.h"   // ErrCode, Error, AQ, IEngine
 #include "pqa_kernels.h"
 #include "combining.h"
+#include "selection_host.h"   // the selection codes, PriorityView, TakePriorities, the host's selector and the finish over a snapshot
 #include "kb_plan.h"
 #include "engine_options.h"
 
@@ -273,7 +273,6 @@ class HipEngine : public IEngine {
   // quizzes' unavailable questions; CollectCombined waits for that launch -- without the engine's lock -- and gives per quiz the
   // shard's winner (argmax batches) or a view of its priority vector on the host (hostPriorities).
   struct CombinedFlight { uint64_t tag = 0; bool hostPriorities = false, quizMinor = false, tagged = false; int64_t Bp = 0, nQ = 0, n = 0; hipError_t he = hipSuccess; };
-  struct PriorityView { const double *pri = nullptr; int64_t stride = 0; uint64_t tag = 0; };   // local question k: pri[k * stride]; tag != 0: the word behind it must carry the tag first
   Error EnqueueCombined(int ctx, int64_t n, const int64_t *pQuizzes, bool hostPriorities, CombinedFlight *flight,
                         std::vector<uint32_t> *unavailable /* n x UnavailableWordCount() words, local bit order */);
   Error CollectCombined(int ctx, const CombinedFlight &flight, CiHipSelection *winners, PriorityView *views);
@@ -355,9 +354,10 @@ class HipEngine : public IEngine {
   int64_t CreateQuiz(Error &err, int64_t nAnswered, const AQ *pAQs, const void *const *rows, const double *srcPrior, int srcDevice,
                      hipEvent_t ready);  // CpuEngine::CreateQuizInternal
   void DestroyQuiz(Quiz *q);
-  int64_t FinishSelection(Error &err, Quiz *q, int64_t sel);  // gap/asked fallback + bookkeeping (CpuEngine.cpp:404-413)
-  int64_t FindNearestQuestion(int64_t iMiddleGlobal, const Quiz *q) const;  // BaseEngine.cpp:60-124
-  bool QuestionUnavailable(const Quiz *q, int64_t qGlobal) const;
+  // gap/asked fallback + bookkeeping (CpuEngine.cpp:403-413) over the quiz's own bits and the gaps, or over a snapshot of both
+  // (a combined sweep's, without the engine's lock: what is written is the quiz's own or atomic)
+  int64_t FinishSelection(Error &err, Quiz *q, int64_t selLocal) { return FinishSelection(err, q, selLocal, _Q, _hQGap.data(), q->hAsked.data()); }
+  int64_t FinishSelection(Error &err, Quiz *q, int64_t selLocal, int64_t nQ, const uint32_t *unavailable, const uint32_t *asked = nullptr);
   Error RecordAnswerImpl(int64_t iQuiz, int64_t iAnswer, bool remote);
   Error RecordAnswerLocked(int64_t iQuiz, int64_t iAnswer, bool remote, bool flushNow);
   // ---- batched ResumeQuiz (hip_engine_resume.cpp): the entries of a ResumeQuizBatch, of a drain's posted ResumeQuiz calls, or one
@@ -525,10 +525,8 @@ class HipEngine : public IEngine {
     int64_t result = -1;
     Error err;
     std::atomic<int> state{0};         // 0 waiting, 1 served, 2 lead handed over: serve the queue yourself,
-                                       // 3 the sweep is done: select for yourself from pri[] (the leader does not do it for everybody)
-    const double *pri = nullptr;       // state 3: priority of local question k at pri[k * priStride]
-    int64_t priStride = 0;
-    uint64_t priTag = 0;               // != 0: pri[k * priStride + 1] is the entry's launch tag -- the entry is taken once it carries this one
+                                       // 3 the sweep is done: select for yourself from `view` (the leader does not do it for everybody)
+    PriorityView view;                 // state 3: this quiz's priority vector on the host
     BatchCtx *ctx = nullptr;           // state 3: whose reader count is this request's to release
     uint64_t serial = 0;               // state 3: the quiz the sweep ran for
     Quiz *quiz = nullptr;              // state 3: held by inSelection
@@ -577,11 +575,9 @@ class HipEngine : public IEngine {
   Error RecordQuizTargetLocked(int64_t iQuiz, int64_t iTarget, double amount);
   int64_t PreferredCombinedBatch(int64_t m) const;
   struct Flight {                      // a combined sweep between its launch and its collection
+    CombinedFlight cf;                 // the sweep itself: EnqueueCombinedLocked fills it, CollectCombined waits for it
     std::vector<SelRequest *> live;
-    uint64_t tag = 0;
-    bool anySampled = false, quizMinor = false, tagged = false;
-    int64_t Bp = 0, nQ = 0;
-    hipError_t he = hipSuccess;
+    bool anySampled = false;
     std::chrono::steady_clock::time_point tA, tB, tC;
   };
   void LaunchBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flight &f);
@@ -672,7 +668,21 @@ class HipEngine : public IEngine {
   bool UseClusterSweep() const;       // rows beyond the register shapes, automatic variant, shape supported
   Error LaunchSingleSweep(Quiz *q, const FusedSelect *fused);
   bool LazyFix() const;
+  // (a quiz whose last late_eager selections all needed the fix gets it launched behind the sweep again)
+  bool LazyFor(const Quiz *q) const { return LazyFix() && q->lateStreak < _opt.lateEager; }
+  FusedSelect OwnLaunch(uint64_t tag) { return FusedSelect::OwnCell(_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, tag); }
+  FusedSelect GraphReplay() { return FusedSelect::Graph(_dGraphScratch, OwnRecord(kOwnGraph), &_hPinned->seq, _dTagCell); }
   Error RunLazyFix(Quiz *q, const FusedSelect &swept, const char *what);   // the single-quiz sweep of this engine's precision, on _stream
+  // The tail of a launched synchronous selection: the packed answer into _hPinned->sel (WaitPacked; waitWhat: its text where it is not
+  // `what`), the lazy pole fix where the sweep asks for it (lateStreak, _poleListPending), the error "<what> (incomplete sweep)".
+  Error AwaitLaunched(Quiz *q, const FusedSelect &fs, uint64_t tag, const char *what, const char *waitWhat = nullptr);
+  // The resident sweep's step for a quiz: posted with `flags`, waited for, checked.  *handedOver: it answered "redo with the fix" --
+  // this quiz's selections are launched from here on (Quiz::noServer), the caller goes on to launch this one.
+  Error AskResident(Quiz *q, int64_t flags, const char *what, bool *handedOver);
+  Error CollectCombined(BatchCtx &c, const CombinedFlight &flight, CiHipSelection *winners, PriorityView *views);   // (the engine's own leaders: no HIP call where flags are waited for)
+  PriorityView ViewOf(const BatchCtx &c, const CombinedFlight &flight, int64_t i) const;   // quiz i's vector as the sweep delivered it (flight.hostPriorities)
+  // EnqueueCombined behind its argument checks, the lock and the flush: tag, sweep, event; `quizzes`: the batch's, for the caller's snapshot
+  Error EnqueueCombinedLocked(BatchCtx &c, int64_t n, const int64_t *pQuizzes, bool hostPriorities, CombinedFlight *flight, std::vector<Quiz *> &quizzes);
   uint64_t _selSeq = 0;
   // Tag of the next fused launch: consecutive launches differ in the low 32 bits, and those are never 0 (the state of
   // freshly cleared records)
@@ -741,7 +751,7 @@ class HipEngine : public IEngine {
   void ApplyEnvironment();   // the PQA_* variables: defaults for unchanged wrappers
   TaggedPriority *_hHostPriority = nullptr;   // host-coherent, _hostPriorityCap records {priority, launch tag}
   std::vector<double> _hostRun;               // the vector the host-side selector works on
-  Error CollectHostPriority(uint64_t tag, const Quiz *q);   // the launch's entries out of _hHostPriority into _hostRun
+  Error CollectHostPriority(uint64_t tag, const Quiz *q);   // the launch's entries out of _hHostPriority into _hostRun (TakePriorities)
   int64_t _hostPriorityCap = 0;
   hipError_t EnsureHostPriority();
   int64_t ClusterFrom() const { return _elem == 8 ? _opt.clusterFrom : 16384; }   // rows longer than this take the cluster sweep (Float engines: their register shapes hold 16384 elements; not re-measured)
@@ -791,11 +801,6 @@ class HipEngine : public IEngine {
   SelectorRng _rng;         // NextQuestion's random numbers, drawn under _rngMu
 };
 
-void LogAnomaly(DefaultLogger::Severity sev, const char *what, double value);   // the reference's numeric-anomaly log entries (rate-limited)
-void CheckPriority(double priority, int64_t index);
-int64_t SelectSampledHost(double *run, int64_t n, int64_t nWorkers, uint64_t rnd, const std::function<bool(int64_t)> &skipped);
-int64_t SelectSampledHostBits(double *run, int64_t n, int64_t nWorkers, uint64_t rnd, const uint32_t *a, const uint32_t *b);
-int64_t FindNearestInPacks(int64_t iMiddle, int64_t nQuestions, const std::function<uint64_t(int64_t)> &avail);
 // One knowledge base over several devices of this process (sharded_engine.cpp); devices.size() >= 2.
 IEngine *CreateShardedEngine(Error &err, const CiEngineDefinition &def, const std::vector<int> &devices);
 IEngine *LoadShardedEngine(Error &err, const char *filePath, const std::vector<int> &devices, uint8_t precType = 0);

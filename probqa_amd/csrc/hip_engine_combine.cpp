@@ -238,8 +238,7 @@ int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
 }
 
 // One request of a combined sweep, after the sweep: this quiz's priority vector out of the batch's matrix, then the selector (as
-// the single-quiz path's host_sampled form: SelectSampledHost; the argmax by the device's rule: maximum, lowest index on ties,
-// NaN never wins), then NextQuestion's bookkeeping under the engine's lock.
+// the single-quiz path's host_sampled form: SelectSampledHost; the argmax by the device's rule), then NextQuestion's bookkeeping.
 int64_t HipEngine::SelectFromPriorities(SelRequest *r) {
   // No engine lock: the priorities are the sweep's, the asked / gap bits the leader's snapshot of the moment it launched the
   // sweep (what the kernel saw), the quiz object is held by inSelection, and the two things written -- the quiz's active
@@ -248,48 +247,15 @@ int64_t HipEngine::SelectFromPriorities(SelRequest *r) {
   const int64_t nQ = r->nQ;
   auto skip = [&](int64_t k) { return BitTest(r->unavailable, k); };
   std::vector<double> run((size_t)nQ);
-  if (r->priTag != 0) {
-    // (the quiz's flag said that every workgroup had reported, not that every one of its stores had landed: an entry is taken
-    //  once it carries the launch's tag -- it almost always does by now)
-    const volatile double *rec = r->pri;
-    SpinWait w;
-    for (int64_t k = 0; k < nQ; k++) {
-      if (skip(k)) { run[(size_t)k] = 0.0; continue; }
-      const volatile uint64_t *tagWord = reinterpret_cast<const volatile uint64_t *>(rec + 2 * k + 1);
-      while (*tagWord != r->priTag)
-        if (!w.Tick(std::chrono::seconds(30))) {
-          r->err = HipErr(hipErrorNotReady, "priority vector hand-over (combined sweep)");
-          q->inSelection.store(false, std::memory_order_release);
-          return r->result = -1;
-        }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      run[(size_t)k] = rec[2 * k];
-    }
-  } else {
-    for (int64_t k = 0; k < nQ; k++) run[(size_t)k] = skip(k) ? 0.0 : r->pri[(size_t)k * (size_t)r->priStride];
+  if (!TakePriorities(r->view, nQ, skip, run.data(), std::chrono::seconds(30))) {
+    r->err = HipErr(hipErrorNotReady, "priority vector hand-over (combined sweep)");
+    q->inSelection.store(false, std::memory_order_release);
+    return r->result = -1;
   }
-  int64_t pick = -1;
-  if (r->kind == 1) {
-    pick = SelectSampledHostBits(run.data(), nQ, r->nSub, r->rnd, r->unavailable.data(), nullptr);
-  } else {
-    double best = 0;
-    for (int64_t k = 0; k < nQ; k++) {
-      if (skip(k)) continue;
-      double p = run[(size_t)k];
-      if (p != p) p = -HUGE_VAL;
-      if (pick < 0 || p > best) { best = p; pick = k; }
-    }
-  }
-  // reference PqaCore/CpuEngine.cpp:403-413 (FinishSelection, over the snapshot)
-  if (pick >= 0 && skip(pick)) pick = FindNearestInPacks(pick, nQ, [&](int64_t p) { return ~Pack64(r->unavailable, p); });
-  if (pick < 0) {
-    r->err = Error::Make(ErrCode::QuestionsExhausted, "Found no unasked question that is not in a gap.");
-    r->result = -1;
-  } else {
-    q->activeQuestion = _qFirst + pick;
-    _nQuestionsAsked.fetch_add(1, std::memory_order_relaxed);
-    r->result = q->activeQuestion;
-  }
+  BestPick best;   // (kb_plan.h: the device's rule -- maximum priority, lowest index on ties, NaN never wins)
+  if (r->kind == 0) for (int64_t k = 0; k < nQ; k++) if (!skip(k)) best.Offer(run[(size_t)k], k);
+  const int64_t pick = r->kind == 1 ? SelectSampledHostBits(run.data(), nQ, r->nSub, r->rnd, r->unavailable.data(), nullptr) : best.index;
+  r->result = FinishSelection(r->err, q, pick, nQ, r->unavailable.data());
   q->inSelection.store(false, std::memory_order_release);
   return r->result;
 }
@@ -351,11 +317,10 @@ void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch,
     return;
   }
   const int64_t n = (int64_t)live.size();
-  f.tag = NextLaunchTag();
   std::vector<Quiz *> quizzes;
-  err = BatchSweep(c, n, ids.data(), quizzes, false, f.tag, f.anySampled, &f.quizMinor, &f.tagged);
+  err = EnqueueCombinedLocked(c, n, ids.data(), f.anySampled, &f.cf, quizzes);
   if (!err.ok()) { for (SelRequest *r : live) { r->err = err; r->result = -1; } return; }
-  const int64_t nSubtasks = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
+  const int64_t nSubtasks = SampledSubtasks();
   for (int64_t i = 0; i < n; i++) {
     SelRequest *r = live[(size_t)i];
     Quiz *q = quizzes[(size_t)i];
@@ -370,14 +335,9 @@ void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch,
     r->unavailable.resize(_hQGap.size());
     for (size_t w = 0; w < r->unavailable.size(); w++) r->unavailable[w] = _hQGap[w] | q->hAsked[w];
   }
-  f.Bp = c.lastBp;
-  f.nQ = _Q;
-  if (f.anySampled && !f.tagged) f.he = hipEventRecord(c.event, _stream);
   _combBatches++;
   _combRequests += (uint64_t)n;
   if ((uint64_t)n > _combMaxBatch) _combMaxBatch = (uint64_t)n;
-  _lastCombined.store(n, std::memory_order_relaxed);
-  _flushedSinceSweep.store(0, std::memory_order_relaxed);
   f.live.swap(live);
   c.inFlight.store(true, std::memory_order_relaxed);
   f.tC = std::chrono::steady_clock::now();
@@ -387,17 +347,11 @@ void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch,
 // ListTopTargets, StartQuiz ... and the next leader's launch).  Returns true if `own` is to select for itself.
 bool HipEngine::CollectBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flight &f, SelRequest *own) {
   const int64_t n = (int64_t)f.live.size();
-  Error err;
-  hipError_t he = f.he;
-  if (he == hipSuccess && f.anySampled && !f.tagged) he = hipEventSynchronize(c.event);
-  if (he == hipSuccess && (!f.anySampled || f.tagged)) err = WaitBatchFlags(c, n, f.tag);
-  if (err.ok() && f.tagged)
-    for (int64_t i = 0; i < n && err.ok(); i++)
-      if (c.h->out[i].index == -3) err = HipErr(hipErrorLaunchFailure, "combined selection (incomplete sweep)");
+  CiHipSelection winners[kMaxBatch];   // (argmax batches: the kernel's choices)
+  const Error err = CollectCombined(c, f.cf, f.anySampled ? nullptr : winners, nullptr);
   c.inFlight.store(false, std::memory_order_relaxed);
   const auto tD = std::chrono::steady_clock::now();
   auto ns = [](auto a, auto b) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count(); };
-  if (he != hipSuccess) err = HipErr(he, "combined selection");
   if (!err.ok()) {
     for (SelRequest *r : f.live) {
       r->err = err;
@@ -414,9 +368,7 @@ bool HipEngine::CollectBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flig
     bool ownLive = false;
     for (int64_t i = 0; i < n; i++) {
       SelRequest *r = f.live[(size_t)i];
-      r->pri = f.tagged ? c.hPri + 2 * (size_t)i * (size_t)f.nQ : f.quizMinor ? c.hPri + i : c.hPri + (size_t)i * (size_t)f.nQ;
-      r->priStride = f.tagged ? 2 : f.quizMinor ? f.Bp : 1;
-      r->priTag = f.tagged ? f.tag : 0;
+      r->view = ViewOf(c, f.cf, i);
       r->ctx = &c;
       if (r == own) { ownLive = true; continue; }
       Combiner<SelRequest, BatchCtx>::LetSelect(batch, r);
@@ -429,23 +381,9 @@ bool HipEngine::CollectBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flig
   const auto tE = std::chrono::steady_clock::now();
   for (int64_t i = 0; i < n; i++) {
     SelRequest *r = f.live[(size_t)i];
-    Quiz *q = r->quiz;
-    int64_t pick = c.h->out[i].index;
-    if (pick == -3) { r->err = HipErr(hipErrorLaunchFailure, "combined selection (incomplete sweep)"); r->result = -1; }
-    else {
-      CheckPriority(c.h->out[i].priority, pick);
-      // reference PqaCore/CpuEngine.cpp:403-413 (FinishSelection, over the snapshot)
-      if (pick >= 0 && BitTest(r->unavailable, pick)) pick = FindNearestInPacks(pick, r->nQ, [&](int64_t p) { return ~Pack64(r->unavailable, p); });
-      if (pick < 0) {
-        r->err = Error::Make(ErrCode::QuestionsExhausted, "Found no unasked question that is not in a gap.");
-        r->result = -1;
-      } else {
-        q->activeQuestion = _qFirst + pick;
-        _nQuestionsAsked.fetch_add(1, std::memory_order_relaxed);
-        r->result = q->activeQuestion;
-      }
-    }
-    q->inSelection.store(false, std::memory_order_release);
+    const int64_t pick = winners[i]._iQuestion < 0 ? kSelNone : winners[i]._iQuestion - _qFirst;
+    r->result = FinishSelection(r->err, r->quiz, pick, r->nQ, r->unavailable.data());
+    r->quiz->inSelection.store(false, std::memory_order_release);
   }
   _combNs[3] += ns(tD, tE);
   _combNs[4] += ns(tE, std::chrono::steady_clock::now());

@@ -14,7 +14,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <random>
 #include <sstream>
 
@@ -44,9 +43,6 @@ inline void BitSet(std::vector<uint32_t> &bits, int64_t i, bool v) {
   if (v) bits[i >> 5] |= 1u << (i & 31); else bits[i >> 5] &= ~(1u << (i & 31));
 }
 inline size_t BitWords(int64_t nBits) { return (size_t)((nBits + 63) / 64) * 2 + 2; }  // whole 64-bit packs + slack
-inline uint64_t Pack64(const std::vector<uint32_t> &bits, int64_t iPack) {
-  return (uint64_t)bits[2 * iPack] | ((uint64_t)bits[2 * iPack + 1] << 32);
-}
 
 // An id table of Compact as the C ABI hands it out: the caller frees it (never of size zero)
 inline int64_t *MallocCopy(const std::vector<int64_t> &v) {
@@ -54,30 +50,6 @@ inline int64_t *MallocCopy(const std::vector<int64_t> &v) {
   std::copy(v.begin(), v.end(), p);
   return p;
 }
-
-// A wait for a word the GPU writes: a pure spin while the answer is a kernel's time away (the first ~50 us), then the core is
-// offered to whoever else wants it between looks (sched_yield) -- a process whose clients outnumber its CPUs otherwise burns its
-// allowance on waiting -- and the clock is read only every so often.  Tick() returns false once `limit` has passed.
-struct SpinWait {
-  uint64_t spins = 0;
-  bool yielding = false;
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  // (by TIME, not by count: a pause is 15 - 40 ns on the hosts met so far, and a count that ran out just before a 20 us step's answer
-  //  put a system call -- a microsecond -- into every selection)
-  bool Tick(std::chrono::seconds limit) {
-    ++spins;
-    if (!yielding) {
-      _mm_pause();
-      if ((spins & 63) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(200)) yielding = true;
-      return true;
-    }
-    if ((spins & 0xFF) == 0 && std::chrono::steady_clock::now() - t0 > limit) return false;
-    sched_yield();
-    return true;
-  }
-  bool Due() const { return (spins & 0xFFF) == 0; }   // (for the occasional look at something else while waiting)
-};
-
 
 }  // namespace
 }  // namespace pqa

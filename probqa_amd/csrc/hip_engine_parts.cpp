@@ -136,7 +136,7 @@ Error HipEngine::SampledPickFromParts(int64_t n, const int64_t *pQuizzes, const 
   if (!err.ok()) return err;
   for (int64_t i = 0; i < n; i++) {
     if (c.h->out[i].index == -2) return PartsModeErr("the part of this rank is not of the engine's latest pack (a stale sequence number).");
-    if (c.h->out[i].index == -3) return PartsModeErr("the parts' question ranges do not tile the question axis, or they were packed under another subtask count.");
+    if (c.h->out[i].index == kSelIncomplete) return PartsModeErr("the parts' question ranges do not tile the question axis, or they were packed under another subtask count.");
   }
   for (int64_t i = 0; i < n; i++) {
     pOut[i]._priority = c.h->out[i].priority;

@@ -6,126 +6,22 @@ namespace pqa {
 // ------------------------------------------------------------------------------------------------------------------
 // NextQuestion
 // ------------------------------------------------------------------------------------------------------------------
-bool HipEngine::QuestionUnavailable(const Quiz *q, int64_t qLocal) const {
-  return BitTest(_hQGap, qLocal) || BitTest(q->hAsked, qLocal);
-}
-
-// BaseEngine::FindNearestQuestion, reference PqaCore/BaseEngine.cpp:60-124: the available question "nearest" to iMiddle as the
-// reference finds it -- exact within iMiddle's own 64-bit pack, then pack by pack outwards, comparing only the two packs at the
-// same pack distance.  avail(p): bit i set = question 64 p + i is neither asked nor a gap (bits past nQuestions clear).
-int64_t FindNearestInPacks(int64_t iMiddle, int64_t nQuestions, const std::function<uint64_t(int64_t)> &avail) {
-  const uint32_t dInf = 200;
-  const int64_t iPack64 = iMiddle >> 6;
-  const uint32_t iWithin = (uint32_t)(iMiddle & 63);
-  const uint64_t available = avail(iPack64);
-  if (available != 0) {
-    const uint64_t baseMask = (1ULL << iWithin) - 1;
-    const uint64_t higher = available & ~baseMask, lower = baseMask & available;
-    const uint32_t dHigher = higher ? ((uint32_t)__builtin_ctzll(higher) - iWithin) : dInf;
-    const uint32_t dLower = lower ? (iWithin - (uint32_t)(63 - __builtin_clzll(lower))) : dInf;
-    return (dHigher < dLower) ? iMiddle + dHigher : iMiddle - dLower;
-  }
-  const int64_t limPack64 = (nQuestions + 63) >> 6;
-  int64_t i = 1;
-  while ((iPack64 >= i) && (iPack64 + i < limPack64)) {
-    const uint64_t availLeft = avail(iPack64 - i), availRight = avail(iPack64 + i);
-    if ((availLeft | availRight) == 0) { i++; continue; }
-    const uint32_t dHigher = availRight ? ((uint32_t)__builtin_ctzll(availRight) + 64 - iWithin) : dInf;
-    const uint32_t dLower = availLeft ? (iWithin + 64 - (uint32_t)(63 - __builtin_clzll(availLeft))) : dInf;
-    if (dHigher < dLower) return iMiddle + dHigher + ((i - 1) << 6);
-    return iMiddle - dLower - ((i - 1) << 6);
-  }
-  while (iPack64 >= i) {
-    const uint64_t availLeft = avail(iPack64 - i);
-    if (!availLeft) { i++; continue; }
-    return iMiddle - (iWithin + 64 - (uint32_t)(63 - __builtin_clzll(availLeft))) - ((i - 1) << 6);
-  }
-  while (iPack64 + i < limPack64) {
-    const uint64_t availRight = avail(iPack64 + i);
-    if (!availRight) { i++; continue; }
-    return iMiddle + ((uint32_t)__builtin_ctzll(availRight) + 64 - iWithin) + ((i - 1) << 6);
-  }
-  return -1;
-}
-
-// The reference's selector (PqaCore/CpuEngine.cpp:362-400) on the host, over a priority vector the sweep has delivered: the same
-// per-subtask Kahan run lengths (CEEvalQsSubtaskConsider.cpp:52-58, :212-214), Kahan grand totals and two upper_bounds as
-// select_sampled_wg_impl (pqa_device.h) -- operation for operation, so with the same priorities, subtask count and random number it
-// picks the same question.  run: priorities in, run lengths out.  Returns the pick before the gap / asked fallback (:403-407).
-// The reference reports numeric anomalies of a sweep in its log -- non-finite grand totals of the priorities (CpuEngine.cpp:370-373),
-// a non-positive grand total (:375-377), a priority that is not a positive finite number (CEEvalQsSubtaskConsider.cpp:209-211) --
-// and goes on.  So does this engine, for what reaches the host: the selected question's priority, the totals of the sampled
-// selector.  (NaN never wins an argmax here, so a NaN winner means that every available question's priority is NaN.)  At most
-// kAnomalyLogLimit entries per process: a broken knowledge base would otherwise write one per selection.
+// The numeric-anomaly entries of selection_host.h in the engine's log.  At most kAnomalyLogLimit entries per process: a broken
+// knowledge base would otherwise write one per selection.
 namespace {
 std::atomic<int> gAnomaliesLogged{0};
 constexpr int kAnomalyLogLimit = 200;
 }  // namespace
-void LogAnomaly(DefaultLogger::Severity sev, const char *what, double value) {
+void LogAnomaly(bool isError, const char *what, double value) {
   if (gAnomaliesLogged.fetch_add(1, std::memory_order_relaxed) >= kAnomalyLogLimit) return;
   char buf[64];
   std::snprintf(buf, sizeof(buf), "%.17g", value);
-  DefaultLogger::Log(sev, std::string(what) + buf);
-}
-void CheckPriority(double priority, int64_t index) {   // CEEvalQsSubtaskConsider.cpp:209-211, for the question that was selected
-  if (index >= 0 && !(priority > 0 && std::isfinite(priority))) LogAnomaly(DefaultLogger::Severity::Warning, "Got priority=", priority);
+  DefaultLogger::Log(isError ? DefaultLogger::Severity::Error : DefaultLogger::Severity::Warning, std::string(what) + buf);
 }
 
-namespace {
-template <class Skip>
-int64_t SelectSampledHostT(double *run, int64_t n, int64_t nWorkers, uint64_t rnd, const Skip &skipped) {
-  struct Kahan {                 // SRAccumulator<SRDoubleNumber> (SRPlatform/Interface/SRAccumulator.h:15-39)
-    double sum = 0, corr = 0;
-    void add(double v) { const double y = v - corr; const double t = sum + y; corr = (t - sum) - y; sum = t; }
-    double get() const { return sum - corr; }
-  };
-  const int64_t quot = n / nWorkers, rem = n % nWorkers, nSubtasks = quot == 0 ? rem : nWorkers;   // SRPoolRunner::CalcSplit
-  auto bound = [&](int64_t i) { return (i + 1) * quot + std::min<int64_t>(i + 1, rem); };           // end of subtask i
-  std::vector<double> grand((size_t)nSubtasks);
-  for (int64_t s = 0; s < nSubtasks; s++) {
-    Kahan acc;
-    for (int64_t i = s == 0 ? 0 : bound(s - 1); i < bound(s); i++) {
-      if (!skipped(i)) acc.add(run[i]);   // gap / asked questions only copy the running sum
-      run[i] = acc.get();
-    }
-    grand[(size_t)s] = acc.get();
-  }
-  Kahan tot;                                                     // CpuEngine.cpp:362-368
-  for (int64_t s = 0; s < nSubtasks; s++) {
-    tot.add(grand[(size_t)s]);
-    grand[(size_t)s] = tot.get();
-    if (!std::isfinite(grand[(size_t)s]))                          // :370-373
-      LogAnomaly(DefaultLogger::Severity::Error, "Overflow or underflow has happened in the question evaluation subtasks: ", grand[(size_t)s]);
-  }
-  const double totG = grand[(size_t)nSubtasks - 1];
-  if (totG <= 0) LogAnomaly(DefaultLogger::Severity::Warning, "Grand-grand total is ", totG);   // :375-377
-  const double selRunLen = totG * (double)rnd / 18446744073709551615.0;   // :379, SRDoubleNumber::MakeRandom
-  const int64_t iWorker = std::upper_bound(grand.begin(), grand.end(), selRunLen) - grand.begin();   // :380-381
-  if (iWorker >= nSubtasks) return n - 1;                         // :384
-  const double inWorker = selRunLen - (iWorker == 0 ? 0.0 : grand[(size_t)iWorker - 1]);   // :388
-  const int64_t first = iWorker == 0 ? 0 : bound(iWorker - 1), limit = bound(iWorker);
-  int64_t sel = std::upper_bound(run + first, run + limit, inWorker) - run;   // :391
-  if (sel >= limit) sel = limit - 1;                              // :392-400
-  return sel;
-}
-}  // namespace
-int64_t SelectSampledHost(double *run, int64_t n, int64_t nWorkers, uint64_t rnd, const std::function<bool(int64_t)> &skipped) {
-  return SelectSampledHostT(run, n, nWorkers, rnd, skipped);
-}
-// (the same over bit words -- a question is skipped if its bit is set in either array; `b` may be null: the test inlined
-//  instead of a call through std::function per question, 1000 of them per selection)
-int64_t SelectSampledHostBits(double *run, int64_t n, int64_t nWorkers, uint64_t rnd, const uint32_t *a, const uint32_t *b) {
-  if (b == nullptr) return SelectSampledHostT(run, n, nWorkers, rnd, [a](int64_t i) { return ((a[i >> 5] >> (i & 31)) & 1u) != 0; });
-  return SelectSampledHostT(run, n, nWorkers, rnd, [a, b](int64_t i) { return (((a[i >> 5] | b[i >> 5]) >> (i & 31)) & 1u) != 0; });
-}
-
-int64_t HipEngine::FindNearestQuestion(int64_t iMiddle, const Quiz *q) const {   // (over the local question range)
-  return FindNearestInPacks(iMiddle, _Q, [&](int64_t p) { return ~(Pack64(_hQGap, p) | Pack64(q->hAsked, p)); });
-}
-
-int64_t HipEngine::FinishSelection(Error &err, Quiz *q, int64_t selLocal) {
-  // reference PqaCore/CpuEngine.cpp:403-413
-  if (selLocal >= 0 && QuestionUnavailable(q, selLocal)) selLocal = FindNearestQuestion(selLocal, q);
+// reference PqaCore/CpuEngine.cpp:403-413, over the bits given (selection_host.h: FinishOverSnapshot)
+int64_t HipEngine::FinishSelection(Error &err, Quiz *q, int64_t selLocal, int64_t nQ, const uint32_t *unavailable, const uint32_t *asked) {
+  selLocal = FinishOverSnapshot(selLocal, nQ, unavailable, asked);
   if (selLocal < 0) {
     err = Error::Make(ErrCode::QuestionsExhausted, "Found no unasked question that is not in a gap.");
     return -1;
@@ -199,7 +95,7 @@ Error HipEngine::EnqueueSelectArgmax(int64_t iQuiz, void *pOut) {
   Quiz *q = UseQuiz(err, iQuiz);
   if (!q) return err;
   // one launch: the sweep's last workgroup picks the argmax; reported index = local position + qFirst (GLOBAL id)
-  const FusedSelect fs{_dSelScratch, pOut ? (SelectResult *)pOut : _dSel, nullptr, NextLaunchTag(), _qFirst, 0, 0, nullptr, 0, 0, nullptr, nullptr};
+  const FusedSelect fs = FusedSelect::Record(_dSelScratch, pOut ? (SelectResult *)pOut : _dSel, nullptr, NextLaunchTag(), 0, _qFirst);
   hipSetDevice(_device);
   StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
   return LaunchSingleSweep(q, &fs);
@@ -220,7 +116,7 @@ Error HipEngine::EnqueueSelectArgmaxFlag(int64_t iQuiz, void *pOut, void *pFlag,
   // take the launched path" means nothing -- so while that fix is on (the default) this selection is always launched, with the fix
   // behind it: a late quiz state gets the reference-order sums on the sharded path as on the single-engine one.
   if (_opt.server && !_opt.poleFix && ServerUsable()) return ServerPost(q, (SelectResult *)pOut, (uint64_t *)pFlag, flagValue, _qFirst | (int64_t)kServerNoWatch);
-  const FusedSelect fs{_dSelScratch, (SelectResult *)pOut, (uint64_t *)pFlag, NextLaunchTag(), _qFirst, 0, flagValue, nullptr, 0, 0, nullptr, nullptr};
+  const FusedSelect fs = FusedSelect::Record(_dSelScratch, (SelectResult *)pOut, (uint64_t *)pFlag, NextLaunchTag(), flagValue, _qFirst);
   StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
   return LaunchSingleSweep(q, &fs);
 }
@@ -243,15 +139,9 @@ hipError_t HipEngine::EnsureHostPriority() {
 // that every workgroup has reported, not that every one of its stores has landed).
 Error HipEngine::CollectHostPriority(uint64_t tag, const Quiz *q) {
   _hostRun.resize((size_t)_Q);
-  const volatile TaggedPriority *rec = _hHostPriority;
-  SpinWait w;
-  for (int64_t i = 0; i < _Q; i++) {
-    if (BitTest(_hQGap, i) || BitTest(q->hAsked, i)) { _hostRun[(size_t)i] = 0.0; continue; }
-    while (rec[i].tag != tag)
-      if (!w.Tick(std::chrono::seconds(30))) return HipErr(hipErrorNotReady, "priority vector hand-over");
-    std::atomic_thread_fence(std::memory_order_acquire);
-    _hostRun[(size_t)i] = rec[i].priority;
-  }
+  const PriorityView v{&_hHostPriority->priority, 2, tag};
+  auto skip = [&](int64_t i) { return BitTest(_hQGap, i) || BitTest(q->hAsked, i); };
+  if (!TakePriorities(v, _Q, skip, _hostRun.data(), std::chrono::seconds(30))) return HipErr(hipErrorNotReady, "priority vector hand-over");
   return Error();
 }
 
@@ -345,6 +235,37 @@ Error HipEngine::RunLazyFix(Quiz *q, const FusedSelect &swept, const char *what)
   return err;
 }
 
+// The tail of every launched synchronous selection (argmax, host-sampled, fused-sampled, graph replay): see hip_engine.h.
+Error HipEngine::AwaitLaunched(Quiz *q, const FusedSelect &fs, uint64_t tag, const char *what, const char *waitWhat) {
+  Error err = WaitPacked(fs.out, tag, 0, waitWhat ? waitWhat : what);
+  if (!err.ok()) return err;
+  if (fs.lazyFix) {
+    if (_hPinned->sel.index == kSelRedo) {   // the sweep listed rows at the pole of the lack term: the fix now, and its answer
+      err = RunLazyFix(q, fs, what);         // (clears the mark once the fix has emptied the list; the corrected entries of a hand-over carry the sweep's tag)
+      if (!err.ok()) return err;
+      q->lateStreak++;
+    } else {
+      q->lateStreak = 0;
+      if (_hPinned->sel.index != kSelIncomplete) _poleListPending = false;   // (a complete sweep that listed nothing)
+    }
+  }
+  // the sweep's finisher gave up: some workgroup of the launch never reported
+  if (_hPinned->sel.index == kSelIncomplete) return HipErr(hipErrorLaunchFailure, (std::string(what) + " (incomplete sweep)").c_str());
+  return Error();
+}
+
+// resident sweep: post the request, poll the answer -- no launch on the critical path
+Error HipEngine::AskResident(Quiz *q, int64_t flags, const char *what, bool *handedOver) {
+  const uint64_t value = _serverTag = NextSelectionTag(_serverTag);   // (its own record: see kGraphFlagBase)
+  Error err = ServerPost(q, OwnRecord(kOwnResident), &_hPinned->seq, value, flags);
+  if (err.ok()) err = WaitPacked(OwnRecord(kOwnResident), value, 0, what, true);
+  if (!err.ok()) return err;
+  if (_hPinned->sel.index == kSelIncomplete) return HipErr(hipErrorLaunchFailure, (std::string(what) + " (incomplete sweep)").c_str());
+  *handedOver = _hPinned->sel.index == kSelRedo;
+  if (*handedOver) q->noServer = true;   // (a row at the pole of the lack term: this quiz's selections are launched from here on, the fix behind them)
+  return Error();
+}
+
 // One quiz, by itself (the caller holds _mu)
 int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   err = CheckRegular("compute next question");
@@ -356,54 +277,32 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   if (!err.ok()) return -1;
   if (_opt.useGraph && _elem == 8) return NextQuestionArgmaxGraph(err, q);
   if (_opt.server && !q->noServer && ServerUsable()) {
-    // resident sweep: post the request, poll the answer -- no launch on the critical path
-    const uint64_t value = _serverTag = NextSelectionTag(_serverTag);   // (its own record: see kGraphFlagBase)
-    err = ServerPost(q, OwnRecord(kOwnResident), &_hPinned->seq, value, (int64_t)kServerPacked);
-    if (err.ok()) err = WaitPacked(OwnRecord(kOwnResident), value, 0, "NextQuestionArgmax", true);
+    bool handedOver = false;
+    err = AskResident(q, (int64_t)kServerPacked, "NextQuestionArgmax", &handedOver);
     if (!err.ok()) return -1;
-    if (_hPinned->sel.index == -3) {
-      err = HipErr(hipErrorLaunchFailure, "NextQuestionArgmax (incomplete sweep)");
-      return -1;
-    }
-    if (_hPinned->sel.index != -4) {
+    if (!handedOver) {
       CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);
       return FinishSelection(err, q, _hPinned->sel.index);
     }
-    q->noServer = true;   // (a row at the pole of the lack term: this quiz's selections are launched from here on, the fix behind them)
   }
-  // One launch; the last workgroup writes the winner and then a sequence number straight into host-coherent pinned
-  // memory, which this thread polls: no D2H copy, no stream synchronisation on the critical path.
+  // One launch; the last workgroup writes the winner straight into host-coherent pinned memory, which this thread polls: no D2H
+  // copy, no stream synchronisation on the critical path.
   uint64_t seq;
   FusedSelect fs{};
   if (TakeSpeculation(q, 1 << 1, &seq) != 0) fs = _spec.fs;   // (RecordAnswer has launched this very sweep already)
   else {
     seq = NextLaunchTag();
-    fs = FusedSelect{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, 0, 0, nullptr, nullptr, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0, 1};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
+    fs = OwnLaunch(seq).Lazy(LazyFor(q));
     StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
     err = LaunchSingleSweep(q, &fs);
     if (!err.ok()) return -1;
     if (fs.lazyFix) _poleListPending = true;   // (whatever it lists stays listed until the fix has run or the sweep has said "nothing": a wait that fails leaves it for SettlePoleList)
   }
-  err = WaitPacked(fs.out, seq, 0, "NextQuestionArgmax");
+  err = AwaitLaunched(q, fs, seq, "NextQuestionArgmax");
   if (!err.ok()) return -1;
-  if (fs.lazyFix) {
-    if (_hPinned->sel.index == -4) {   // the sweep listed rows at the pole of the lack term: the fix now, and its answer
-      err = RunLazyFix(q, fs, "NextQuestionArgmax");   // (clears the mark once the fix has emptied the list)
-      if (!err.ok()) return -1;
-      q->lateStreak++;
-    } else {
-      q->lateStreak = 0;
-      if (_hPinned->sel.index != -3) _poleListPending = false;   // (a complete sweep that listed nothing)
-    }
-  }
-  if (_hPinned->sel.index == -3) {  // the sweep's finisher gave up: some workgroup of the launch never reported
-    err = HipErr(hipErrorLaunchFailure, "NextQuestionArgmax (incomplete sweep)");
-    return -1;
-  }
   CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);
   return FinishSelection(err, q, _hPinned->sel.index);
 }
-
 
 Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std::vector<Quiz *> &quizzes, bool wantPriorities, uint64_t tag,
                             bool hostPriorities, bool *pQuizMinor, bool *pTagged, bool devicePriorities) {
@@ -537,8 +436,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
   }
   c.lastBp = 0;   // (0: the quizzes' priorities are their own vectors in dPriority, not a matrix)
   if (!rowSharing) {
-    const FusedSelect fs{c.dScratch, nullptr, nullptr, tag, 0, kBatchGrid, tag, nullptr, tagged ? 1 : 0, 0, nullptr,
-                         tagged ? reinterpret_cast<TaggedPriority *>(c.hPri) : nullptr};
+    const FusedSelect fs = FusedSelect::Batch(c.dScratch, kBatchGrid, tag).HostPriority(tagged ? reinterpret_cast<TaggedPriority *>(c.hPri) : nullptr);
     // (the batch's suspect list and records -- pole_kernels.hip: grown with the batch, the head cleared once)
     const KbView kbv = View();
     BatchPlan pp{};
@@ -601,7 +499,7 @@ Error HipEngine::CollectBatchSelectionsLocked(int64_t n, uint64_t tag, CiHipSele
   Error err = WaitBatchFlags(c, n, tag);
   if (!err.ok()) return err;
   for (int64_t i = 0; i < n; i++) {
-    if (c.h->out[i].index == -3) return HipErr(hipErrorLaunchFailure, "batched selection (incomplete sweep)");
+    if (c.h->out[i].index == kSelIncomplete) return HipErr(hipErrorLaunchFailure, "batched selection (incomplete sweep)");
     CheckPriority(c.h->out[i].priority, c.h->out[i].index);
     pOut[i]._priority = c.h->out[i].priority;
     pOut[i]._iQuestion = c.h->out[i].index < 0 ? -1 : c.h->out[i].index + _qFirst;
@@ -657,7 +555,7 @@ Error HipEngine::NextQuestionArgmaxBatch(int64_t n, const int64_t *pQuizzes, int
   if (!err.ok()) return err;
   for (int64_t i = 0; i < n; i++) {
     Error e;   // -1 + QuestionsExhausted: reported as -1 only
-    pOut[i] = FinishSelection(e, _batchQuizzes[(size_t)i], sel[(size_t)i]._iQuestion < 0 ? -1 : sel[(size_t)i]._iQuestion - _qFirst);
+    pOut[i] = FinishSelection(e, _batchQuizzes[(size_t)i], sel[(size_t)i]._iQuestion < 0 ? kSelNone : sel[(size_t)i]._iQuestion - _qFirst);
   }
   return Error();
 }
@@ -725,7 +623,7 @@ Error HipEngine::ValidateBatchLocked(int64_t n, const int64_t *pQuizzes) {   // 
 }
 
 Error HipEngine::LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag) {
-  const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
+  const int64_t nSub = SampledSubtasks();
   std::memcpy(c.h->rnd, pRnd, (size_t)n * sizeof(uint64_t));   // (host-coherent: the selector reads them there)
   size_t grandDoubles = 0, runDoubles = 0;
   SelectSampledBatchScratch(_Q, nSub, (int)n, c.lastBp, &grandDoubles, &runDoubles);
@@ -765,36 +663,26 @@ Error HipEngine::NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizz
   if (!err.ok()) return err;
   BatchCtx &c = _ctx[0];
   const uint64_t tag = NextLaunchTag();
-  const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;
-  std::vector<int64_t> picks((size_t)n, -1);
+  const int64_t nSub = SampledSubtasks();
+  std::vector<int64_t> picks((size_t)n, kSelNone);
   if (_opt.sampledBatchHost) {
     // the A/B leg: the priorities to the host as a combined sweep delivers them, the host's selector per quiz (SelectFromPriorities)
     while (c.readers.load(std::memory_order_acquire) != 0) _mm_pause();   // (clients of an earlier combined sweep still read hPri)
-    bool quizMinor = false, tagged = false;
-    err = BatchSweep(c, n, pQuizzes, _batchQuizzes, false, tag, true, &quizMinor, &tagged);
+    CombinedFlight f;
+    f.tag = tag; f.hostPriorities = true; f.nQ = _Q; f.n = n;
+    err = BatchSweep(c, n, pQuizzes, _batchQuizzes, false, tag, true, &f.quizMinor, &f.tagged);
     if (!err.ok()) return err;
+    f.Bp = c.lastBp;
     HIP_TRY(hipStreamSynchronize(_stream));
     err = WaitBatchFlags(c, n, tag);
     if (!err.ok()) return err;
     _hostRun.resize((size_t)_Q);
     for (int64_t i = 0; i < n; i++) {
-      if (c.h->out[i].index == -3) return HipErr(hipErrorLaunchFailure, "sampled batch (incomplete sweep)");
+      if (c.h->out[i].index == kSelIncomplete) return HipErr(hipErrorLaunchFailure, "sampled batch (incomplete sweep)");
       const Quiz *q = _batchQuizzes[(size_t)i];
-      if (tagged) {
-        const volatile TaggedPriority *rec = reinterpret_cast<const TaggedPriority *>(c.hPri) + (size_t)i * (size_t)_Q;
-        SpinWait w;
-        for (int64_t k = 0; k < _Q; k++) {
-          if (BitTest(_hQGap, k) || BitTest(q->hAsked, k)) { _hostRun[(size_t)k] = 0.0; continue; }
-          while (rec[k].tag != tag)
-            if (!w.Tick(std::chrono::seconds(30))) return HipErr(hipErrorNotReady, "priority vector hand-over (sampled batch)");
-          std::atomic_thread_fence(std::memory_order_acquire);
-          _hostRun[(size_t)k] = rec[k].priority;
-        }
-      } else {
-        const double *pri = quizMinor ? c.hPri + i : c.hPri + (size_t)i * (size_t)_Q;
-        const size_t stride = quizMinor ? (size_t)c.lastBp : 1;
-        for (int64_t k = 0; k < _Q; k++) _hostRun[(size_t)k] = BitTest(_hQGap, k) || BitTest(q->hAsked, k) ? 0.0 : pri[(size_t)k * stride];
-      }
+      auto skip = [&](int64_t k) { return BitTest(_hQGap, k) || BitTest(q->hAsked, k); };
+      if (!TakePriorities(ViewOf(c, f, i), _Q, skip, _hostRun.data(), std::chrono::seconds(30)))
+        return HipErr(hipErrorNotReady, "priority vector hand-over (sampled batch)");
       picks[(size_t)i] = SelectSampledHostBits(_hostRun.data(), _Q, nSub, pRnd[i], _hQGap.data(), q->hAsked.data());
     }
   } else {
@@ -805,7 +693,7 @@ Error HipEngine::NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizz
     err = WaitBatchFlags(c, n, tag);
     if (!err.ok()) return err;
     for (int64_t i = 0; i < n; i++) {   // (the sweep published before the selector did)
-      if (c.h->sweepSeq[i] == tag && c.h->sweepOut[i].index == -3) return HipErr(hipErrorLaunchFailure, "sampled batch (incomplete sweep)");
+      if (c.h->sweepSeq[i] == tag && c.h->sweepOut[i].index == kSelIncomplete) return HipErr(hipErrorLaunchFailure, "sampled batch (incomplete sweep)");
       CheckPriority(c.h->out[i].priority, c.h->out[i].index);
       picks[(size_t)i] = c.h->out[i].index;
     }
@@ -865,7 +753,7 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
   if (it == _graphs.end() || it->second.variant != _opt.evalVariant || it->second.stream != _stream ||
       it->second.kbVersion != _kbVersion) {
     if (it != _graphs.end()) { hipGraphExecDestroy(it->second.exec); _graphs.erase(it); }
-    const FusedSelect fs{_dGraphScratch, OwnRecord(kOwnGraph), &_hPinned->seq, 0, 0, 0, 0, _dTagCell, 0, 0, nullptr, nullptr, 0, 1};
+    const FusedSelect fs = GraphReplay();
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipError_t he = hipStreamBeginCapture(_stream, hipStreamCaptureModeThreadLocal);
@@ -886,9 +774,8 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
   const hipError_t he = hipGraphLaunch(it->second.exec, _stream);
   if (he != hipSuccess) { err = HipErr(he, "hipGraphLaunch"); return -1; }
   _graphTag = NextSelectionTag(_graphTag);           // the finisher's own rule (fused_select)
-  err = WaitPacked(OwnRecord(kOwnGraph), expect, 0, "NextQuestionArgmax (graph)");
+  err = AwaitLaunched(q, GraphReplay(), expect, "NextQuestionArgmax", "NextQuestionArgmax (graph)");
   if (!err.ok()) return -1;
-  if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionArgmax (incomplete sweep)"); return -1; }
   CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);
   return FinishSelection(err, q, _hPinned->sel.index);
 }
@@ -904,21 +791,18 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
   err = FlushUpdates();
   if (!err.ok()) return -1;
   const KbView kb = View();
-  const int64_t nSub = _opt.evalSubtasks ? _opt.evalSubtasks : 8 * _opt.workers;  // reference PqaCore/CpuEngine.cpp:339
+  const int64_t nSub = SampledSubtasks();
   if (_opt.server && !q->noServer && _opt.hostSampled && !_opt.fusedSampled && ServerUsable()) {
-    // resident sweep: post the request with the hand-over mark, poll the flag, select on the host -- no launch on the path
-    const uint64_t value = _serverTag = NextSelectionTag(_serverTag);   // (its own record: see kGraphFlagBase)
-    err = ServerPost(q, OwnRecord(kOwnResident), &_hPinned->seq, value, (int64_t)(kServerHandOver | kServerPacked));
-    if (err.ok()) err = WaitPacked(OwnRecord(kOwnResident), value, 0, "NextQuestionSampled", true);
+    // (with the hand-over mark: the selection on the host)
+    bool handedOver = false;
+    err = AskResident(q, (int64_t)(kServerHandOver | kServerPacked), "NextQuestionSampled", &handedOver);
     if (!err.ok()) return -1;
-    if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionSampled (incomplete sweep)"); return -1; }
-    if (_hPinned->sel.index != -4) {
+    if (!handedOver) {
       err = CollectHostPriority(_serverPosted, q);
       if (!err.ok()) return -1;
       const int64_t sel = SelectSampledHostBits(_hostRun.data(), _Q, nSub, rnd, _hQGap.data(), q->hAsked.data());
       return FinishSelection(err, q, sel);
     }
-    q->noServer = true;   // (as NextQuestionArgmaxLocked)
   }
   uint64_t specTag = 0;
   const int took = TakeSpeculation(q, (1 << 2) | (1 << 3), &specTag);   // 2 / 3: RecordAnswer has launched the sweep already
@@ -936,24 +820,13 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     else {
       { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
       seq = NextLaunchTag();
-      fs = FusedSelect{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, 1, 0, nullptr, _hHostPriority, LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0, 1};   // (a quiz whose last selections all needed the fix: launched behind the sweep again)
+      fs = OwnLaunch(seq).HostPriority(_hHostPriority).Lazy(LazyFor(q));
       const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
       if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
       if (fs.lazyFix) _poleListPending = true;   // (as NextQuestionArgmaxLocked)
     }
-    err = WaitPacked(fs.out, seq, 0, "NextQuestionSampled");
+    err = AwaitLaunched(q, fs, seq, "NextQuestionSampled");
     if (!err.ok()) return -1;
-    if (fs.lazyFix) {
-      if (_hPinned->sel.index == -4) {   // (as NextQuestionArgmaxLocked: the corrected entries carry the sweep's tag)
-        err = RunLazyFix(q, fs, "NextQuestionSampled");
-        if (!err.ok()) return -1;
-        q->lateStreak++;
-      } else {
-        q->lateStreak = 0;
-        if (_hPinned->sel.index != -3) _poleListPending = false;
-      }
-    }
-    if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionSampled (incomplete sweep)"); return -1; }
     err = CollectHostPriority(seq, q);
     if (!err.ok()) return -1;
     const int64_t sel = SelectSampledHostBits(_hostRun.data(), _Q, nSub, rnd, _hQGap.data(), q->hAsked.data());
@@ -963,24 +836,20 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     // ONE launch: the sweep's finisher workgroup runs the reference's selector once every workgroup has reported
     { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
     const uint64_t seq = NextLaunchTag();
-    const FusedSelect fs{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, nSub, rnd, _dRunLength, nullptr, 0, 1};
+    const FusedSelect fs = OwnLaunch(seq).Sampled(nSub, rnd, _dRunLength);
     const hipError_t he = LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream);
     if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
-    err = WaitPacked(fs.out, seq, 0, "NextQuestionSampled");
+    err = AwaitLaunched(q, fs, seq, "NextQuestionSampled");
     if (!err.ok()) return -1;
-    if (_hPinned->sel.index == -3) { err = HipErr(hipErrorLaunchFailure, "NextQuestionSampled (incomplete sweep)"); return -1; }
     CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);
-  return FinishSelection(err, q, _hPinned->sel.index);
+    return FinishSelection(err, q, _hPinned->sel.index);
   }
   if (took != 3) {   // (else: the priorities are in _dPriority already, or on their way there in stream order)
     err = LaunchSingleSweep(q, nullptr);
     if (!err.ok()) return -1;
   }
-  hipError_t he = hipSuccess;
   const uint64_t op = ++_opSeq;  // the selector writes its record and then this number into host-coherent memory
-  if (he == hipSuccess)
-    he = LaunchSelectSampled(_dPriority, _dQGap, q->dAsked, 0, _Q, nSub, rnd, _dRunLength, &_hPinned->sel, &_hPinned->opFlag,
-                             op, _stream);
+  const hipError_t he = LaunchSelectSampled(_dPriority, _dQGap, q->dAsked, 0, _Q, nSub, rnd, _dRunLength, &_hPinned->sel, &_hPinned->opFlag, op, _stream);
   if (he != hipSuccess) { err = HipErr(he, "NextQuestionSampled"); return -1; }
   err = WaitFlag(&_hPinned->opFlag, op, "NextQuestionSampled");
   if (!err.ok()) return -1;

@@ -124,11 +124,8 @@ Error HipEngine::EnqueueCombined(int ctx, int64_t n, const int64_t *pQuizzes, bo
   hipSetDevice(_device);
   err = FlushUpdates();
   if (!err.ok()) return err;
-  BatchCtx &c = _ctx[ctx];
-  f->tag = NextLaunchTag();
-  f->hostPriorities = hostPriorities;
   std::vector<Quiz *> quizzes;
-  err = BatchSweep(c, n, pQuizzes, quizzes, false, f->tag, hostPriorities, &f->quizMinor, &f->tagged);
+  err = EnqueueCombinedLocked(_ctx[ctx], n, pQuizzes, hostPriorities, f, quizzes);
   if (!err.ok()) return err;
   if (unavailable != nullptr) {
     const size_t words = _hQGap.size();
@@ -136,32 +133,50 @@ Error HipEngine::EnqueueCombined(int ctx, int64_t n, const int64_t *pQuizzes, bo
     for (int64_t i = 0; i < n; i++)
       for (size_t w = 0; w < words; w++) (*unavailable)[(size_t)i * words + w] = _hQGap[w] | quizzes[(size_t)i]->hAsked[w];
   }
+  MarkStreamBusy();
+  return Error();
+}
+
+// ... the launch itself (the caller holds _mu and has flushed the deferred updates; HipEngine's own combined sweeps come here too,
+// LaunchBatchLocked): the batched sweep under a fresh tag, and the event behind it where the vectors reach the host by a copy.
+Error HipEngine::EnqueueCombinedLocked(BatchCtx &c, int64_t n, const int64_t *pQuizzes, bool hostPriorities, CombinedFlight *f, std::vector<Quiz *> &quizzes) {
+  f->tag = NextLaunchTag();
+  f->hostPriorities = hostPriorities;
+  Error err = BatchSweep(c, n, pQuizzes, quizzes, false, f->tag, hostPriorities, &f->quizMinor, &f->tagged);
+  if (!err.ok()) return err;
   f->Bp = c.lastBp;
   f->nQ = _Q;
   f->n = n;
   if (hostPriorities && !f->tagged) f->he = hipEventRecord(c.event, _stream);
   _lastCombined.store(n, std::memory_order_relaxed);
   _flushedSinceSweep.store(0, std::memory_order_relaxed);
-  MarkStreamBusy();
   return Error();
+}
+
+// Quiz i's priority vector where the sweep of `f` delivered it: tagged records of its own, a column of the quiz-minor matrix, or
+// its own plain vector.
+PriorityView HipEngine::ViewOf(const BatchCtx &c, const CombinedFlight &f, int64_t i) const {
+  if (f.tagged) return PriorityView{c.hPri + 2 * (size_t)i * (size_t)f.nQ, 2, f.tag};
+  return f.quizMinor ? PriorityView{c.hPri + i, f.Bp, 0} : PriorityView{c.hPri + (size_t)i * (size_t)f.nQ, 1, 0};
 }
 
 // Second half: no lock of the engine is taken -- the flags, the event and the host buffers belong to the batch context, which the
 // caller holds until every reader of the priority views is done.
 Error HipEngine::CollectCombined(int ctx, const CombinedFlight &f, CiHipSelection *winners, PriorityView *views) {
+  hipSetDevice(_device);   // (the sharded engine's thread drives several devices)
+  return CollectCombined(_ctx[ctx], f, winners, views);
+}
+Error HipEngine::CollectCombined(BatchCtx &c, const CombinedFlight &f, CiHipSelection *winners, PriorityView *views) {
   if (f.n <= 0) return Error();
-  BatchCtx &c = _ctx[ctx];
-  hipSetDevice(_device);
   hipError_t he = f.he;
-  Error err;
   const bool byEvent = f.hostPriorities && !f.tagged;
   if (he == hipSuccess && byEvent) he = hipEventSynchronize(c.event);
   if (he != hipSuccess) return HipErr(he, "combined selection");
   if (!byEvent) {
-    err = WaitBatchFlags(c, f.n, f.tag);
+    Error err = WaitBatchFlags(c, f.n, f.tag);
     if (!err.ok()) return err;
     for (int64_t i = 0; i < f.n; i++)
-      if (c.h->out[i].index == -3) return HipErr(hipErrorLaunchFailure, "combined selection (incomplete sweep)");
+      if (c.h->out[i].index == kSelIncomplete) return HipErr(hipErrorLaunchFailure, "combined selection (incomplete sweep)");
   }
   for (int64_t i = 0; i < f.n; i++) {
     if (winners != nullptr && !f.hostPriorities) {   // (a batch that hands priority vectors over is selected from those)
@@ -169,11 +184,7 @@ Error HipEngine::CollectCombined(int ctx, const CombinedFlight &f, CiHipSelectio
       winners[i]._priority = c.h->out[i].priority;
       winners[i]._iQuestion = c.h->out[i].index < 0 ? -1 : c.h->out[i].index + _qFirst;
     }
-    if (views != nullptr && f.hostPriorities) {
-      views[i].pri = f.tagged ? c.hPri + 2 * (size_t)i * (size_t)f.nQ : f.quizMinor ? c.hPri + i : c.hPri + (size_t)i * (size_t)f.nQ;
-      views[i].stride = f.tagged ? 2 : f.quizMinor ? f.Bp : 1;
-      views[i].tag = f.tagged ? f.tag : 0;
-    }
+    if (views != nullptr && f.hostPriorities) views[i] = ViewOf(c, f, i);
   }
   return Error();
 }

@@ -230,8 +230,7 @@ bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
   if (withUpdate) DropSpeculation();
   const uint64_t seq = NextLaunchTag();
   if (!SettlePoleList().ok()) return false;
-  const FusedSelect fs{_dSelScratch, OwnRecord(kOwnLaunched), &_hPinned->seq, seq, 0, 0, seq, nullptr, kind == 2 ? 1 : 0, 0, nullptr,
-                       kind == 2 ? _hHostPriority : nullptr, (kind == 1 || kind == 2) && LazyFix() && q->lateStreak < _opt.lateEager ? 1 : 0, 1};
+  const FusedSelect fs = OwnLaunch(seq).HostPriority(kind == 2 ? _hHostPriority : nullptr).Lazy((kind == 1 || kind == 2) && LazyFor(q));
   if (withUpdate) {
     const int64_t topCount = std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(_opt.topCache, _topWantRecent), kQuizTop), _T);
     const uint64_t op = _opSeq + 1;

@@ -183,6 +183,20 @@ struct FusedSelect {
   // The engine's own pinned cell as destination (select_record.h): `out` is a PackedSelection -- {priority, low 32 bits of flagValue :
   // local index or code} in ONE write-through store, no fence, no flag (`seq` is not written), outBase added by the host.
   int64_t packed;
+  // The forms the host builds, by name (the struct stays an aggregate of the fields above, in that order; FusedSelect{}: no selection):
+  // the engine's own packed cell (select_record.h), waited for by its tag; an outside reader's record, index + outBase, with flagValue
+  // to *flag behind it (flag may be null); a batch (grid.y = quiz: records and flags are the slots'); a graph replay into a packed cell
+  static FusedSelect OwnCell(SelectResult *scratch, SelectResult *cell, uint64_t *seq, uint64_t tag) { FusedSelect f = Record(scratch, cell, seq, tag, tag, 0); f.packed = 1; return f; }
+  static FusedSelect Record(SelectResult *scratch, SelectResult *out, uint64_t *flag, uint64_t tag, uint64_t flagValue, int64_t outBase) {
+    FusedSelect f{};
+    f.scratch = scratch; f.out = out; f.seq = flag; f.seqValue = tag; f.flagValue = flagValue; f.outBase = outBase;
+    return f;
+  }
+  static FusedSelect Batch(SelectResult *scratch, int64_t scratchStride, uint64_t tag) { FusedSelect f = Record(scratch, nullptr, nullptr, tag, tag, 0); f.scratchStride = scratchStride; return f; }
+  static FusedSelect Graph(SelectResult *scratch, SelectResult *cell, uint64_t *seq, uint64_t *tagCell) { FusedSelect f = OwnCell(scratch, cell, seq, 0); f.tagCell = tagCell; return f; }
+  FusedSelect Sampled(int64_t nSub, uint64_t rnd, double *run) const { FusedSelect f = *this; f.sampleSubtasks = nSub; f.sampleRnd = rnd; f.runLength = run; return f; }
+  FusedSelect HostPriority(TaggedPriority *buf) const { FusedSelect f = *this; f.sampleSubtasks = buf ? 1 : 0; f.hostPriority = buf; return f; }   // (null: the argmax stays)
+  FusedSelect Lazy(bool on) const { FusedSelect f = *this; f.lazyFix = on ? 1 : 0; return f; }
 };
 // One quiz of a batched sweep (blockIdx.y selects it): everything that differs between the quizzes of one launch.
 struct QuizSlot {

@@ -419,7 +419,7 @@ class ShardedEngine final : public IEngine {
     int64_t result = -1;
     Error err;
     std::atomic<int> state{0};         // 0 waiting, 1 served, 2 lead handed over: serve the queue yourself, 3 select for yourself from `views`
-    std::vector<HipEngine::PriorityView> views;   // state 3: per shard, this quiz's priority vector on the host
+    std::vector<PriorityView> views;   // state 3: per shard, this quiz's priority vector on the host
     std::vector<uint64_t> skip;        // state 3: asked questions and gaps in GLOBAL numbering as the sweeps saw them (64-bit packs)
     CombineCtx *ctx = nullptr;
   };
@@ -1060,7 +1060,7 @@ int64_t ShardedEngine::SelectArgmaxLocked(Error &err, int64_t iQuiz, double *pPr
   std::atomic_thread_fence(std::memory_order_acquire);
   BestPick best;   // (kb_plan.h: maximum priority, lowest index on ties)
   for (size_t s = 0; s < _sh.size(); s++) {
-    if (_slots[s].index == -3) { err = Error::Make(ErrCode::Internal, "A shard's sweep did not complete."); return -1; }
+    if (_slots[s].index == kSelIncomplete) { err = Error::Make(ErrCode::Internal, "A shard's sweep did not complete."); return -1; }
     best.Offer(_slots[s].priority, _slots[s].index);
   }
   CheckPriority(best.priority, best.index);   // (the reference's "Got priority=" warning, for the question that was selected)
@@ -1189,7 +1189,7 @@ bool ShardedEngine::CollectBatch(int ctx, std::vector<SelRequest *> &batch, Flig
   const size_t N = _sh.size();
   CombineCtx &c = _bctx[ctx];
   std::vector<std::vector<CiHipSelection>> winners(N);
-  std::vector<std::vector<HipEngine::PriorityView>> views(N);
+  std::vector<std::vector<PriorityView>> views(N);
   Error err;
   for (size_t s = 0; s < N; s++) {   // (every shard is waited for, whatever the others reported)
     winners[s].resize((size_t)n);
@@ -1235,30 +1235,16 @@ int64_t ShardedEngine::SelectFromViews(SelRequest *r) {
   const int64_t nQ = _Q;
   auto skipped = [&](int64_t q) { return Skipped(r->skip, q); };
   std::vector<double> run((size_t)nQ);
-  SpinWait w;
   for (size_t s = 0; s < _sh.size(); s++) {
-    const HipEngine::PriorityView &v = r->views[s];
-    const int64_t q0 = _sh[s]->FirstQuestion(), nLocal = _sh[s]->LocalQuestions();
-    for (int64_t k = 0; k < nLocal; k++) {
-      if (skipped(q0 + k)) { run[(size_t)(q0 + k)] = 0.0; continue; }
-      const volatile double *rec = v.pri + (size_t)k * (size_t)v.stride;
-      if (v.tag != 0) {
-        // (the quiz's flag said that every workgroup had reported, not that every one of its stores had landed: an entry is taken
-        //  once it carries the launch's tag -- it almost always does by now)
-        const volatile uint64_t *tagWord = reinterpret_cast<const volatile uint64_t *>(rec + 1);
-        while (*tagWord != v.tag)
-          if (!w.Tick(std::chrono::seconds(30))) {
-            r->err = Error::Make(ErrCode::Internal, "Timed out waiting for a shard's priority vector.");
-            return r->result = -1;
-          }
-        std::atomic_thread_fence(std::memory_order_acquire);
-      }
-      run[(size_t)(q0 + k)] = *rec;
+    const int64_t q0 = _sh[s]->FirstQuestion();
+    if (!TakePriorities(r->views[s], _sh[s]->LocalQuestions(), [&](int64_t k) { return skipped(q0 + k); }, run.data() + q0, std::chrono::seconds(30))) {
+      r->err = Error::Make(ErrCode::Internal, "Timed out waiting for a shard's priority vector.");
+      return r->result = -1;
     }
   }
   int64_t pick = -1;
   if (r->kind == SelKind::Sampled) {
-    pick = SelectSampledHost(run.data(), nQ, _sh[0]->GetOption("eval_subtasks"), r->rnd, [&](int64_t q) { return skipped(q); });
+    pick = SelectSampledHost(run.data(), nQ, _sh[0]->GetOption("eval_subtasks"), r->rnd, skipped);
   } else {
     BestPick best;
     for (int64_t q = 0; q < nQ; q++) if (!skipped(q)) best.Offer(run[(size_t)q], q);

@@ -190,6 +190,45 @@ def test_lazy_and_eager_fix_agree(i, factory):
     assert picks[0] == picks[1], (case.name, picks)
 
 
+@pytest.mark.parametrize("late_eager", [1, 0, 1000000])
+@pytest.mark.parametrize("select", [1, 0])
+def test_late_eager_after_a_lazy_fix(select, late_eager, factory):
+    """Engine option late_eager = 1 (Quiz::lateStreak): the first selection of a quiz whose sweep lists a row takes the lazy fix -- the
+    sweep answers "redo", the fix is launched behind that answer --, every later one has the fix launched right behind its sweep
+    again; 0: always behind the sweep; a large value: always lazily.  Two selections per step of the smallest single-quiz late case
+    of this file, through NextQuestion with the argmax (select = 1) and with the reference's selector at a fixed seed (select = 0):
+    the picks are those of an identical second engine with pole_lazy = 0, whose fix follows every sweep.  That the case's sweep
+    does list a row is shown by its priorities, which change when the fix is switched off.  (No counter of the engine tells a
+    lazily launched fix from an eager one, so beyond that the picks are all that is compared.)"""
+    leg, case, options = late_case(2)
+    picks, final = [], []
+    for lazy, fix in ((1, 1), (0, 1), (0, 0)):
+        eng = case.make_engine(factory)
+        for n, v in options:
+            eng.set_option(n, v)
+        eng.set_option("speculate", 0)
+        eng.set_option("pole_fix", fix)
+        eng.set_option("pole_lazy", lazy)
+        eng.set_option("late_eager", late_eager)
+        eng.set_option("select", select)
+        eng.set_option("seed", 20260)
+        quiz = eng.start_quiz()
+        got = []
+        for step in range(len(case.answers) + 1):
+            got.append((eng.next_question(quiz), eng.next_question(quiz)))
+            if step < len(case.answers):
+                q, a = case.answers[step]
+                eng.set_active_question(quiz, q)
+                eng.record_answer(quiz, a)
+        final.append(eng.eval_priorities(quiz).copy())
+        eng.close()
+        picks.append(got)
+    assert not np.array_equal(final[1], final[2]), (case.name, "the sweep lists no row: nothing for the fix to do")
+    assert np.array_equal(final[0], final[1])
+    assert all(q >= 0 for pair in picks[0] for q in pair), (case.name, picks[0])
+    assert picks[0] == picks[1], (case.name, picks)
+
+
 @pytest.mark.parametrize("i", [5, 6, 12, 17])
 def test_measurement_hook_without_the_fix_is_harmless(i, factory):
     """Option pole_follow = 0 (bench.py times the watching sweep by itself with it): in a late state the sweep then lists nothing and
