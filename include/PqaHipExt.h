@@ -380,6 +380,48 @@ PQACORE_API void *PqaHip_SampledPickFromParts(void *pvEngine, const int64_t nQui
 PQACORE_API void *PqaEngine_TakeSampledPicks(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pPicks,
                                              int64_t *pQuestions);
 
+/* ---- RecordAnswer for many quizzes on shards that separate processes drive.  Only the rank that holds a quiz's active question can
+ * compute the new posterior (it needs the question's two rows); the others only need to store it.  So the posteriors travel as a
+ * POSTERIOR PACKAGE: slot i = quiz i's new posterior as nTargets doubles at a pitch of RoundLdT(nTargets) doubles (RoundLdT: up to a
+ * 128-byte line), zeros behind them.  Posteriors are fp64 in Float and Double engines alike, and the pitch is a function of nTargets
+ * alone -- the same on every rank, whatever the pitch of its allocation.  The pack changes no quiz: every rank validates the whole
+ * batch first, the ranks exchange one status word, and only then does anybody record -- a refusal on any rank leaves every rank
+ * untouched.  The sequence, run by probqa_amd/dist.py (record_answer_batch); a whole engine is a world of one:
+ *   PqaHip_PosteriorSlotBytes    RoundLdT(nTargets) * 8.
+ *   PqaHip_PackAnswerPosteriors  stream-ordered, no host synchronisation, CHANGES NO QUIZ STATE.  nQuizzes <= 256 distinct quizzes,
+ *                                regular mode.  Every entry is validated before anything is launched, and an error names its batch
+ *                                entry: a known quiz; an active question that is valid and no gap (PqaEngine_RecordAnswer's checks
+ *                                and codes); an answer in [0, nAnswers).  Deferred updates are launched first.  For every entry
+ *                                whose active question THIS engine holds, the quiz's posterior is copied to engine scratch and the
+ *                                update kernels of PqaEngine_RecordAnswerBatch run on the copy in place (rows of more than 16384
+ *                                targets: the long-row launches), so the bits are PqaEngine_RecordAnswer's; then ONE launch, a
+ *                                workgroup per 16 KB of a slot, writes slot i of pDst.  Slots of other ranks' questions are not
+ *                                touched, so several shards fill one zero-filled buffer (or the ranks sum theirs: every slot has
+ *                                one writer, the values are finite, x + 0 == x).  pDst, pFlag, flagValue as PqaHip_PackAnswerRows;
+ *                                the flag is also published by an engine that holds none of the questions.  The engine remembers
+ *                                the pack: the quizzes, the answers, and every quiz's posterior version and active question.
+ *   (all-reduce(SUM) the packages, or fill one buffer; one status word: nobody goes on if a rank's pack was refused)
+ *   PqaEngine_RecordAnswerBatchFromPosteriors
+ *                                synchronises.  WrongMode, and nothing has changed, if the batch is not the one of this engine's
+ *                                latest PqaHip_PackAnswerPosteriors, or a quiz of it has changed its posterior or its active
+ *                                question since.  Otherwise every entry gets PqaEngine_RecordAnswer's bookkeeping -- the answer
+ *                                joins the quiz with the GLOBAL question id, no active question, on the holder the question counts
+ *                                as asked -- and ONE launch stores the nTargets doubles of slot i as quiz i's posterior (elements
+ *                                behind them stay) and sets the holder's bit in the quiz's device bitmap.  pPosteriors: device-
+ *                                visible, valid until the call returns; a package in registered host memory is copied to the
+ *                                device first under option "rows_stage".  No speculative sweep behind the batch, no best targets
+ *                                listed ahead: PqaEngine_ListTopTargets lists on demand and returns the same records.  Concurrent
+ *                                calls take the engine one after the other.
+ * A posterior depends on the cube: no rank may train between the pack and the consuming call.  PqaEngine_RecordAnswer on the holder,
+ * PqaHip_RecordAnswerRemote elsewhere and the caller's own copy of PqaHip_GetPriorDevicePtr's buffer stay as the single-quiz form.
+ * Read-only options "posterior_packs", "posteriors_packed" (entries this engine held), "posteriors_taken".  The one-process sharded
+ * engine (PQA_DEVICES) answers NotImplemented (-1 for the size): PqaEngine_RecordAnswerBatch records over its shards. */
+PQACORE_API int64_t PqaHip_PosteriorSlotBytes(void *pvEngine);
+PQACORE_API void *PqaHip_PackAnswerPosteriors(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pAnswers,
+                                              void *pDst, void *pFlag, const uint64_t flagValue);
+PQACORE_API void *PqaEngine_RecordAnswerBatchFromPosteriors(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes,
+                                                            const int64_t *pAnswers, const void *pPosteriors);
+
 /* ---- Maintenance on shards that separate processes drive.  PqaEngine_AddQsTs, PqaEngine_RemoveQuestions and PqaEngine_RemoveTargets
  * are COLLECTIVE AND REPLICATED on such shards: every rank makes the same call with the same arguments (as every rank sees every
  * PqaEngine_Train), in maintenance mode.  Each shard keeps the bookkeeping of the whole question axis -- the gap list in the

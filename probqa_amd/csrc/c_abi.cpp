@@ -447,6 +447,19 @@ PQACORE_API void *PqaEngine_TakeSampledPicks(void *pvEngine, const int64_t nQuiz
                                              int64_t *pQuestions) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.TakeSampledPicks(nQuizzes, pQuizzes, pPicks, pQuestions); });
 }
+// ---- RecordAnswer for many quizzes on shards driven by processes of their own: the holders of the active questions pack the new
+// posteriors without changing a quiz, every rank records from the combined package (hip_engine_record_parts.cpp)
+PQACORE_API int64_t PqaHip_PosteriorSlotBytes(void *pvEngine) {
+  return LoggedOf<int64_t>(pvEngine, -1, [&](IEngine &e) { return e.PosteriorSlotBytes(); });
+}
+PQACORE_API void *PqaHip_PackAnswerPosteriors(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pAnswers, void *pDst,
+                                              void *pFlag, const uint64_t flagValue) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackAnswerPosteriors(nQuizzes, pQuizzes, pAnswers, pDst, pFlag, flagValue); });
+}
+PQACORE_API void *PqaEngine_RecordAnswerBatchFromPosteriors(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pAnswers,
+                                                            const void *pPosteriors) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerBatchFromPosteriors(nQuizzes, pQuizzes, pAnswers, pPosteriors); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {

@@ -128,8 +128,18 @@ class IEngine {
     return NoParts("SampledPickFromParts");
   }
   virtual Error TakeSampledPicks(int64_t, const int64_t *, const int64_t *, int64_t *) { return NoParts("TakeSampledPicks"); }
+  // RecordAnswer for many quizzes across such shards: posterior packages.  The one-process sharded engine records over its shards
+  // itself (RecordAnswerBatch).
+  virtual int64_t PosteriorSlotBytes() const { return -1; }
+  virtual Error PackAnswerPosteriors(int64_t, const int64_t *, const int64_t *, void *, void *, uint64_t) { return NoPosteriors("PackAnswerPosteriors"); }
+  virtual Error RecordAnswerBatchFromPosteriors(int64_t, const int64_t *, const int64_t *, const void *) {
+    return NoPosteriors("RecordAnswerBatchFromPosteriors");
+  }
 
  private:
+  static Error NoPosteriors(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine", "Posterior packages are for shards that separate processes drive.");
+  }
   static Error NoParts(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine", "Selection parts are for shards that separate processes drive.");
   }

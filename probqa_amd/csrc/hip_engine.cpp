@@ -269,6 +269,7 @@ HipEngine::~HipEngine() {
   hipFree(_dTopExact);
   hipFree(_dRowStage);
   hipFree(_dPartsWords); hipFree(_dPartsRun); hipFree(_dPartsGrand); hipFree(_dPartsPickRun);
+  hipFree(_dPostScratch);
   if (_hPack) hipHostFree(_hPack);
   if (_evPack) hipEventDestroy(_evPack);
   if (_evSweep[0]) { hipEventDestroy(_evSweep[0]); hipEventDestroy(_evSweep[1]); }
@@ -353,7 +354,10 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"pack_calls", &HipEngine::_packCalls},                             // PackAnswerRows launches ...
       {"pack_bytes", &HipEngine::_packBytes},                             // ... and the bytes they were asked to move
       {"rows_staged", &HipEngine::_rowsStaged},                           // host packages copied to the device before they were read
-      {"resume_batches", &HipEngine::_resumeBatches},                     // launch sequences that ran posted ResumeQuiz calls together ...
+      {"posterior_packs", &HipEngine::_postPacks},                        // PackAnswerPosteriors calls that remembered a batch ...
+      {"posteriors_packed", &HipEngine::_postPacked},                     // ... the entries whose active question this engine held ...
+      {"posteriors_taken", &HipEngine::_postTaken},                       // ... and the posteriors RecordAnswerBatchFromPosteriors stored
+      {"resume_batches", &HipEngine::_resumeBatches},                    // launch sequences that ran posted ResumeQuiz calls together ...
       {"resumes_batched", &HipEngine::_resumesBatched},                   // ... this many of them
       {"train_bulk_calls", &HipEngine::_trainBulkCalls},                  // TrainBatch / RecordQuizTargetBatch calls that trained ...
       {"train_bulk_records", &HipEngine::_trainBulkRecords},              // ... their records ...

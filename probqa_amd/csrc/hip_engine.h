@@ -260,6 +260,12 @@ class HipEngine : public IEngine {
   Error SampledPickFromParts(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, const void *pParts, int64_t rank, int64_t world,
                              CiHipSelection *pOut) override;
   Error TakeSampledPicks(int64_t n, const int64_t *pQuizzes, const int64_t *pPicks, int64_t *pQuestions) override;
+  // ---- RecordAnswer for many quizzes across such shards (hip_engine_record_parts.cpp): a POSTERIOR PACKAGE -- slot i = quiz i's
+  // new posterior, T doubles at a pitch that depends on T alone -- filled by the holders of the active questions without changing
+  // any quiz, summed over the ranks, consumed by every rank
+  int64_t PosteriorSlotBytes() const override { std::lock_guard<EngineMutex> lk(_mu); return RoundLdT(_T, 8) * 8; }
+  Error PackAnswerPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, void *pDst, void *pFlag, uint64_t flagValue) override;
+  Error RecordAnswerBatchFromPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, const void *pPosteriors) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
   // An answer of a quiz as the sharded engine hands it to EVERY shard: the answered question in global numbering; for the shards
@@ -656,6 +662,16 @@ class HipEngine : public IEngine {
   uint64_t *_dPartsWords = nullptr;           // {arrival counter, pad}, then a stamp per quiz of a batch
   double *_dPartsRun = nullptr, *_dPartsGrand = nullptr, *_dPartsPickRun = nullptr;
   size_t _partsRunBytes = 0, _partsGrandBytes = 0, _partsPickRunBytes = 0;
+  // The engine's latest pack of posteriors: what RecordAnswerBatchFromPosteriors must find unchanged -- the batch, and every quiz's
+  // posterior and active question.
+  struct PosteriorPack {
+    bool valid = false;
+    std::vector<int64_t> quizzes, answers, active;
+    std::vector<uint64_t> serials, versions;
+  } _postPack;
+  double *_dPostScratch = nullptr;            // the owned entries' posteriors between their update and the pack launch: ldT doubles each
+  size_t _postScratchBytes = 0;
+  uint64_t _postPacks = 0, _postPacked = 0, _postTaken = 0;   // read-only "posterior_packs", "posteriors_packed", "posteriors_taken"
   uint64_t _sampledBatches = 0, _sampledBatchDeviceNs = 0;   // read-only "sampled_batches", "sampled_batch_device_ns" (the selector's launches between events)
   uint64_t _priorityHostBytes = 0;     // read-only "priority_host_bytes": priorities the batched sweeps delivered to the host
   Error WaitBatchFlags(BatchCtx &c, int64_t n, uint64_t tag);

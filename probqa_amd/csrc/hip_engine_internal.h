@@ -1,6 +1,8 @@
 // hip_engine_internal.h -- small helpers shared by the files that implement HipEngine (hip_engine.cpp: construction, options,
 // registry; hip_engine_select.cpp: the selection paths; hip_engine_combine.cpp: concurrent clients; hip_engine_update.cpp:
-// posterior updates, listings, training; hip_engine_shard.cpp: what a sharded engine asks of its shards; hip_engine_kb.cpp: id maps, .kb files, maintenance).
+// posterior updates, listings, training; hip_engine_shard.cpp: what a sharded engine asks of its shards; hip_engine_kb.cpp: id maps, .kb files, maintenance;
+// hip_engine_resume.cpp, hip_engine_parts.cpp, hip_engine_record_parts.cpp: row packages, selection parts and posterior packages of
+// shards that separate processes drive).
 #pragma once
 
 #include <sched.h>

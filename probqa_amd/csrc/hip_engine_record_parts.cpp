@@ -1,0 +1,205 @@
+// hip_engine_record_parts.cpp -- HipEngine: RecordAnswer for many quizzes on a shard that a process of its own drives
+// (probqa_amd/dist.py: record_answer_batch).  Only the rank that holds a quiz's active question can compute the new posterior; the
+// others only need to store it.  So the holders pack the posteriors into a POSTERIOR PACKAGE -- slot i = quiz i's new posterior, T
+// doubles at a pitch that depends on T alone -- WITHOUT changing any quiz, the ranks sum their packages and exchange one status
+// word, and only then every rank records from the combined package: a refusal on any rank leaves every rank untouched.  A whole
+// engine is a world of one.
+#include "hip_engine_internal.h"
+
+namespace pqa {
+
+namespace {
+Error PosteriorsModeErr(const std::string &why) {
+  return Error::Make(ErrCode::WrongMode, "Can't record from these posteriors - " + why);
+}
+Error AtEntry(int64_t i, Error err) {
+  err.message = "Batch entry " + std::to_string(i) + ": " + err.message;
+  return err;
+}
+static_assert(sizeof(PosteriorCopy) == 4 * sizeof(int64_t), "the copies travel in the answered-question buffer");
+}  // namespace
+
+// The posteriors RecordAnswer would leave, computed beside the quizzes: per owned entry a copy of the quiz's posterior in engine
+// scratch, the update kernels of FlushUpdates in place on the copy -- their rows given by pointer, as for a question another shard
+// holds, so that no quiz bitmap is touched, and nothing listed ahead -- and then ONE launch that writes the slots
+// (kb_kernels.hip: pack_posteriors_kernel).  Nothing here waits for the device, except that the pinned list is not rewritten while
+// an earlier call's copy of it is still under way.
+Error HipEngine::PackAnswerPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, void *pDst, void *pFlag, uint64_t flagValue) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "|nQuizzes| must be non-negative.");
+  if (n > kMaxBatch) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(n, 0, kMaxBatch), "Batch size is out of range.");
+  if (n > 0 && (!pQuizzes || !pAnswers || !pDst)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer or the package.");
+  if ((reinterpret_cast<uintptr_t>(pDst) & 15) != 0)
+    return Error::MakeP(ErrCode::IndexOutOfRange, "address mod 16=" + std::to_string(reinterpret_cast<uintptr_t>(pDst) & 15), "The package must be 16-byte aligned.");
+  CallScope scope(_activeCallers);
+  std::lock_guard<EngineMutex> lk(_mu);
+  Error err = CheckRegular("pack answer posteriors");
+  if (!err.ok()) return err;
+  // ---- everything is checked before anything is launched (RecordAnswerLocked's checks and codes)
+  std::vector<Quiz *> quizzes((size_t)n);
+  int64_t m = 0;
+  for (int64_t i = 0; i < n; i++) {
+    Quiz *q = quizzes[(size_t)i] = UseQuiz(err, pQuizzes[i]);
+    if (!q) return AtEntry(i, err);
+    for (int64_t j = 0; j < i; j++)
+      if (pQuizzes[j] == pQuizzes[i])
+        return AtEntry(i, Error::MakeP(ErrCode::IndexOutOfRange, "quizId=" + std::to_string(pQuizzes[i]), "A quiz appears twice in one batch."));
+    const int64_t iAnswer = pAnswers[i], aq = q->activeQuestion;
+    if (iAnswer < 0 || iAnswer >= _K)  // reference PqaCore/BaseEngine.cpp:447-451
+      return AtEntry(i, Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(iAnswer, 0, _K - 1), "Answer index is not in the answer range."));
+    if (aq == -1)   // CEQuiz::RecordAnswer, reference PqaCore/CEQuiz.h:77-122
+      return AtEntry(i, Error::MakeP(ErrCode::NoQuizActiveQuestion, "answerId=" + std::to_string(iAnswer),
+                                     "An attempt to record an answer in a quiz that doesn't have an active question"));
+    if (aq < 0 || aq >= _qTotal || (OwnsQuestion(aq) && BitTest(_hQGap, aq - _qFirst)))
+      return AtEntry(i, Error::MakeP(ErrCode::NoQuizActiveQuestion, "answerId=" + std::to_string(iAnswer),
+                                     "An attempt to record an answer in a quiz that has invalid active question"));
+    m += OwnsQuestion(aq) ? 1 : 0;
+  }
+  _postPack.valid = false;   // (whatever fails from here on: the previous pack is no longer to be recorded from)
+  hipSetDevice(_device);
+  err = FlushUpdates();      // the batch's quizzes' deferred updates: their posteriors are read below
+  if (!err.ok()) return err;
+  if (m > 0 || pFlag != nullptr) {
+    if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
+    const size_t vecBytes = (size_t)_ldT * sizeof(double);
+    if ((size_t)m * vecBytes > _postScratchBytes) {
+      HIP_TRY(hipStreamSynchronize(_stream));   // (nothing in flight reads the buffer about to go)
+      hipFree(_dPostScratch);
+      _dPostScratch = nullptr;
+      _postScratchBytes = 0;
+      HIP_TRY(hipMalloc((void **)&_dPostScratch, (size_t)m * vecBytes));
+      _postScratchBytes = (size_t)m * vecBytes;
+    }
+    // the list: {arrival counter, pad} and then a PosteriorCopy per entry of this engine's questions
+    const int64_t words = 2 + 4 * m;
+    err = EnsurePackList(words);
+    if (!err.ok()) return err;
+    PosteriorCopy *copies = reinterpret_cast<PosteriorCopy *>(_hPack + 2);
+    const size_t slotBytes = (size_t)RoundLdT(_T, 8) * sizeof(double);
+    MarkStreamBusy();
+    const KbView kb = View();
+    const int64_t nLoose = std::max<int64_t>(1, _opt.workers - 1);   // reference PqaCore/CEQuiz.h:98, PqaCore/BaseCpuEngine.cpp:22
+    const bool longRows = _ldT > 16384;
+    static thread_local RecordBatchInline b;   // (10 KB: not on a client thread's stack)
+    b.n = 0;
+    b.topCount = 0;
+    auto launchUpdates = [&]() -> hipError_t {
+      const hipError_t he = b.n > 0 ? LaunchRecordAnswerBatch(kb, b, nLoose, _stream) : hipSuccess;
+      b.n = 0;
+      return he;
+    };
+    for (int64_t i = 0, at = 0; i < n; i++) {
+      const Quiz *q = quizzes[(size_t)i];
+      if (!OwnsQuestion(q->activeQuestion)) continue;
+      const int64_t ql = q->activeQuestion - _qFirst;
+      double *vec = reinterpret_cast<double *>(reinterpret_cast<char *>(_dPostScratch) + (size_t)at * vecBytes);
+      HIP_TRY(hipMemcpyAsync(vec, q->dPrior, vecBytes, hipMemcpyDeviceToDevice, _stream));
+      const void *rowA = CubeAt(ql, pAnswers[i]), *rowD = CubeAt(ql, _K);
+      if (longRows) {   // the long-row stage and divide launches (one workgroup where the engine runs without them)
+        HIP_TRY(LaunchRecordAnswer(kb, vec, nullptr, ql, pAnswers[i], nLoose, nullptr, nullptr, nullptr, 0, 0, _stream, rowA, rowD));
+      } else {
+        b.s[b.n++] = RecordSlot{vec, nullptr, nullptr, (int32_t)ql, (int32_t)pAnswers[i], 0, rowA, rowD};
+        if (b.n == kRecordInline) HIP_TRY(launchUpdates());
+      }
+      copies[at++] = PosteriorCopy{vec, static_cast<char *>(pDst) + (size_t)i * slotBytes, nullptr, -1};
+    }
+    HIP_TRY(launchUpdates());
+    HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
+    HIP_TRY(hipEventRecord(_evPack, _stream));
+    HIP_TRY(LaunchPackPosteriors(reinterpret_cast<const PosteriorCopy *>(_dAqs + 2), m, _T, (int64_t)slotBytes, reinterpret_cast<unsigned *>(_dAqs),
+                                 static_cast<uint64_t *>(pFlag), flagValue, _stream));
+  }
+  _postPack.quizzes.assign(pQuizzes, pQuizzes + n);
+  _postPack.answers.assign(pAnswers, pAnswers + n);
+  _postPack.active.resize((size_t)n);
+  _postPack.serials.resize((size_t)n);
+  _postPack.versions.resize((size_t)n);
+  for (int64_t i = 0; i < n; i++) {
+    _postPack.active[(size_t)i] = quizzes[(size_t)i]->activeQuestion;
+    _postPack.serials[(size_t)i] = quizzes[(size_t)i]->serial;
+    _postPack.versions[(size_t)i] = quizzes[(size_t)i]->priorVersion;
+  }
+  _postPack.valid = true;
+  _postPacks++;
+  _postPacked += (uint64_t)m;
+  return Error();
+}
+
+// CEQuiz::RecordAnswer's bookkeeping for every entry (PqaCore/CEQuiz.h:77-122) and ONE launch that stores every quiz's posterior
+// from its slot and sets the holder's asked bits (kb_kernels.hip: take_posteriors_kernel).  Not a posted operation: concurrent
+// calls take the engine one after the other.  No speculative sweep behind the batch, nothing listed ahead.
+Error HipEngine::RecordAnswerBatchFromPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, const void *pPosteriors) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "|nQuizzes| must be non-negative.");
+  if (n > kMaxBatch) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(n, 0, kMaxBatch), "Batch size is out of range.");
+  if (n > 0 && (!pQuizzes || !pAnswers || !pPosteriors)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer or the package.");
+  if ((reinterpret_cast<uintptr_t>(pPosteriors) & 15) != 0)
+    return Error::MakeP(ErrCode::IndexOutOfRange, "address mod 16=" + std::to_string(reinterpret_cast<uintptr_t>(pPosteriors) & 15), "The package must be 16-byte aligned.");
+  CallScope scope(_activeCallers);
+  std::lock_guard<EngineMutex> lk(_mu);
+  Error err = CheckRegular("record answers from posteriors");
+  if (!err.ok()) return err;
+  // the engine's latest pack must be of this very batch, and no quiz of it may have moved since
+  if (!_postPack.valid) return PosteriorsModeErr("this engine has packed no posteriors since it last recorded from a package or failed to pack.");
+  bool same = (int64_t)_postPack.quizzes.size() == n;
+  for (int64_t i = 0; same && i < n; i++) {
+    const int64_t id = pQuizzes[i];
+    const Quiz *q = id >= 0 && (size_t)id < _quizzes.size() ? _quizzes[(size_t)id] : nullptr;
+    same = q != nullptr && _postPack.quizzes[(size_t)i] == id && _postPack.answers[(size_t)i] == pAnswers[i] && q->serial == _postPack.serials[(size_t)i] &&
+           q->priorVersion == _postPack.versions[(size_t)i] && q->activeQuestion == _postPack.active[(size_t)i];
+  }
+  if (!same) return PosteriorsModeErr("the engine's latest pack was made for another batch, or a quiz of it has changed its posterior or its active question since.");
+  _postPack.valid = false;
+  if (n == 0) return Error();
+  hipSetDevice(_device);
+  ServerQuiesce();   // (the posted step reads a posterior this call may be about to write)
+  if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
+  const size_t slotBytes = (size_t)RoundLdT(_T, 8) * sizeof(double);
+  const char *base = static_cast<const char *>(pPosteriors);
+  if (_opt.rowsStage) {   // a package in host memory (registered, as PqaHip_HostRegister leaves it): copied to the device first
+    hipPointerAttribute_t at;
+    const hipError_t q = hipPointerGetAttributes(&at, pPosteriors);
+    if (q != hipSuccess) (void)hipGetLastError();
+    if (q == hipSuccess && at.type == hipMemoryTypeHost) {
+      const size_t bytes = (size_t)n * slotBytes;
+      if (bytes > _rowStageBytes) {
+        hipFree(_dRowStage);   // (every call that used it has synchronised)
+        _dRowStage = nullptr;
+        _rowStageBytes = 0;
+        HIP_TRY(hipMalloc((void **)&_dRowStage, bytes));
+        _rowStageBytes = bytes;
+      }
+      HIP_TRY(hipMemcpyAsync(_dRowStage, base, bytes, hipMemcpyDefault, _stream));
+      base = _dRowStage;
+      _rowsStaged++;
+    }
+  }
+  const int64_t words = 2 + 4 * n;
+  err = EnsurePackList(words);
+  if (!err.ok()) return err;
+  PosteriorCopy *copies = reinterpret_cast<PosteriorCopy *>(_hPack + 2);
+  for (int64_t i = 0; i < n; i++) {
+    Quiz *q = _quizzes[(size_t)pQuizzes[i]];
+    const bool local = OwnsQuestion(q->activeQuestion);
+    copies[i] = PosteriorCopy{base + (size_t)i * slotBytes, q->dPrior, local ? q->dAsked : nullptr, local ? q->activeQuestion - _qFirst : -1};
+  }
+  MarkStreamBusy();
+  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
+  HIP_TRY(hipEventRecord(_evPack, _stream));
+  HIP_TRY(LaunchTakePosteriors(reinterpret_cast<const PosteriorCopy *>(_dAqs + 2), n, _T, _stream));
+  const time_t now = time(nullptr);
+  for (int64_t i = 0; i < n; i++) {
+    Quiz *q = _quizzes[(size_t)pQuizzes[i]];
+    const int64_t aq = q->activeQuestion;
+    q->answers.push_back(AQ{aq, pAnswers[i]});
+    q->activeQuestion = -1;
+    q->priorVersion++;
+    q->lastUsage = now;
+    if (OwnsQuestion(aq)) BitSet(q->hAsked, aq - _qFirst, true);
+  }
+  _postTaken += (uint64_t)n;
+  HIP_TRY(hipStreamSynchronize(_stream));
+  _mu.busy = false;   // (the stream has just been synchronised)
+  _pendingRecordOp = 0;
+  return Error();
+}
+
+}  // namespace pqa

@@ -311,7 +311,7 @@ Error HipEngine::PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFl
   return Error();
 }
 
-// The pointer list of a pack call (PackAnswerRows, PackQuestionBlocks): `words` 8-byte words fit the device buffer and its pinned
+// The pointer list of a pack call (PackAnswerRows, PackQuestionBlocks, the posterior packages' two calls): `words` 8-byte words fit the device buffer and its pinned
 // source, the copy of the previous call's list has left the pinned one, and the header -- the arrival counter -- is zero.
 Error HipEngine::EnsurePackList(int64_t words) {
   if (words > 2 * _aqCapacity) {

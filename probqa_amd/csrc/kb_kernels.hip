@@ -372,6 +372,66 @@ __global__ __launch_bounds__(256) void copy_question_blocks_kernel(const BlockCo
   __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// PqaHip_PackAnswerPosteriors / PqaEngine_RecordAnswerBatchFromPosteriors: one posterior -- T doubles -- between the engine and a slot
+// of a posterior package, whose pitch is that of the current T.  A workgroup moves chunk `chunk` (kPackChunkBytes) of the vector as
+// 16-byte units, all of a thread's loads requested before its first store; both sides start on 16-byte bounds.  An odd T leaves a
+// partial last unit.  kZeroTail (packing): its other half and every unit behind it up to dstUnits are stored as zeros, so a slot is
+// a function of the T doubles alone.  Otherwise (into a quiz's posterior) its half goes word by word and nothing behind it is
+// written: the elements from T on stay as they are.
+template <bool kZeroTail>
+__device__ __forceinline__ void copy_posterior_chunk(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t T, int64_t dstUnits, int64_t chunk) {
+  constexpr int kPer = (int)(kPackChunkBytes / 16 / 256);
+  const int64_t fullUnits = T >> 1;
+  const bool tail = (T & 1) != 0;
+  const int64_t dataUnits = fullUnits + (tail ? 1 : 0), lastUnit = kZeroTail ? dstUnits : dataUnits;
+  const int64_t u0 = chunk * (kPer * 256) + threadIdx.x;
+  uint4 v[kPer];
+#pragma unroll
+  for (int e = 0; e < kPer; e++) {
+    const int64_t u = u0 + e * 256;
+    v[e] = u < dataUnits ? src[u] : make_uint4(0, 0, 0, 0);
+  }
+#pragma unroll
+  for (int e = 0; e < kPer; e++) {
+    const int64_t u = u0 + e * 256;
+    if (u >= lastUnit) continue;
+    if (u != fullUnits || !tail) { dst[u] = v[e]; continue; }
+    if constexpr (kZeroTail) {
+      dst[u] = make_uint4(v[e].x, v[e].y, 0u, 0u);
+    } else {
+      uint32_t *w = reinterpret_cast<uint32_t *>(dst + u);
+      w[0] = v[e].x;
+      w[1] = v[e].y;
+    }
+  }
+}
+
+// Workgroup (entry, chunk of the slot's pitch).  The flag protocol is pack_answer_rows_kernel's; workgroups past `nWork` (a batch
+// without a question of this engine: one workgroup) only take part in that.
+__global__ __launch_bounds__(256) void pack_posteriors_kernel(const PosteriorCopy *__restrict__ copies, int64_t nWork, int64_t T, int64_t pitchUnits,
+                                                              int64_t chunksPerSlot, unsigned *counter, uint64_t *flag, uint64_t flagValue) {
+  if ((int64_t)blockIdx.x < nWork) {
+    const PosteriorCopy c = copies[blockIdx.x / chunksPerSlot];
+    copy_posterior_chunk<true>(static_cast<const uint4 *>(c.src), static_cast<uint4 *>(c.dst), T, pitchUnits, blockIdx.x % chunksPerSlot);
+  }
+  if (flag == nullptr) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: this thread's part of the slots before the count
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) != gridDim.x - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __hip_atomic_store(flag, flagValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Workgroup (entry, chunk of the T doubles).  The entry's first workgroup also marks the answered question as asked where this engine
+// holds it (CEQuiz::RecordAnswer, PqaCore/CEQuiz.h:92): the batch's quizzes are distinct, so the word has one writer.
+__global__ __launch_bounds__(256) void take_posteriors_kernel(const PosteriorCopy *__restrict__ copies, int64_t T, int64_t chunksPerVector) {
+  const int64_t chunk = blockIdx.x % chunksPerVector;
+  const PosteriorCopy c = copies[blockIdx.x / chunksPerVector];
+  copy_posterior_chunk<false>(static_cast<const uint4 *>(c.src), static_cast<uint4 *>(c.dst), T, 0, chunk);
+  if (chunk == 0 && threadIdx.x == 0 && c.asked != nullptr) c.asked[c.askedBit >> 5] |= 1u << (c.askedBit & 31);
+}
+
 // ---- .kb rows between the file's dense layout in one number type and the cube's padded layout in another -------------------------------
 // A thread moves four consecutive elements of one row, columns [4 g, 4 g + 4): on the cube's side that is a 16-byte aligned unit of a
 // Float row (two of a Double row), whatever the row -- rows start on 128-byte lines.  The dense side is only element-aligned: row r
@@ -510,6 +570,28 @@ hipError_t LaunchCopyQuestionBlocks(const BlockCopy *blocks, int64_t n, int64_t 
   else
     hipLaunchKernelGGL(copy_question_blocks_kernel<false>, grid, dim3(256), 0, stream, blocks, nWork, rows, rowWords, srcPitchBytes / 16, dstPitchBytes / 16,
                        chunksPerRow, counter, flag, flagValue);
+  return hipGetLastError();
+}
+
+hipError_t LaunchPackPosteriors(const PosteriorCopy *copies, int64_t n, int64_t T, int64_t pitchBytes, unsigned *counter, uint64_t *flag,
+                                uint64_t flagValue, hipStream_t stream) {
+  if (n < 0 || T < 1 || pitchBytes % 16 != 0 || pitchBytes < (T + 1) / 2 * 16 || (n > 0 && copies == nullptr) || (flag != nullptr && counter == nullptr))
+    return hipErrorInvalidValue;
+  if (n == 0 && flag == nullptr) return hipSuccess;
+  const int64_t chunksPerSlot = (pitchBytes + kPackChunkBytes - 1) / kPackChunkBytes;
+  if (n > 0x7fffffff / chunksPerSlot) return hipErrorInvalidValue;
+  const int64_t nWork = n * chunksPerSlot;
+  hipLaunchKernelGGL(pack_posteriors_kernel, dim3((unsigned)std::max<int64_t>(nWork, 1)), dim3(256), 0, stream, copies, nWork, T, pitchBytes / 16,
+                     chunksPerSlot, counter, flag, flagValue);
+  return hipGetLastError();
+}
+
+hipError_t LaunchTakePosteriors(const PosteriorCopy *copies, int64_t n, int64_t T, hipStream_t stream) {
+  if (n < 0 || T < 1 || (n > 0 && copies == nullptr)) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const int64_t chunksPerVector = ((T + 1) / 2 * 16 + kPackChunkBytes - 1) / kPackChunkBytes;
+  if (n > 0x7fffffff / chunksPerVector) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(take_posteriors_kernel, dim3((unsigned)(n * chunksPerVector)), dim3(256), 0, stream, copies, T, chunksPerVector);
   return hipGetLastError();
 }
 

@@ -606,6 +606,18 @@ hipError_t LaunchPackAnswerRows(const PackPair *pairs, int64_t n, int64_t rowByt
 struct BlockCopy { const void *src; void *dst; };
 hipError_t LaunchCopyQuestionBlocks(const BlockCopy *blocks, int64_t n, int64_t rows, int64_t rowWords, int64_t srcPitchBytes, int64_t dstPitchBytes,
                                     bool zeroTail, unsigned *counter, uint64_t *flag, uint64_t flagValue, hipStream_t stream);
+// Posteriors between the engine and a POSTERIOR PACKAGE (PqaHip_PackAnswerPosteriors, PqaEngine_RecordAnswerBatchFromPosteriors):
+// slot = T doubles at a pitch of pitchBytes (a multiple of 128), zeros behind them.  Entry i of `copies` (device memory) moves one
+// posterior from src to dst, both 16-byte aligned.  One launch each: a workgroup per (entry, chunk of kPackChunkBytes), 16-byte
+// accesses except the words of an odd T's last, partial unit.
+//   LaunchPackPosteriors: dst is the slot -- the partial unit's other half and every unit behind it up to the pitch are stored as
+//     zeros.  counter / flag / flagValue as LaunchPackAnswerRows.
+//   LaunchTakePosteriors: dst is a quiz's posterior -- elements from T on stay as they are -- and where `asked` is not null, one
+//     lane of the entry's first workgroup sets bit askedBit there (CEQuiz::RecordAnswer, PqaCore/CEQuiz.h:92, on the holder).
+struct PosteriorCopy { const void *src; void *dst; uint32_t *asked; int64_t askedBit; };
+hipError_t LaunchPackPosteriors(const PosteriorCopy *copies, int64_t n, int64_t T, int64_t pitchBytes, unsigned *counter, uint64_t *flag,
+                                uint64_t flagValue, hipStream_t stream);
+hipError_t LaunchTakePosteriors(const PosteriorCopy *copies, int64_t n, int64_t T, hipStream_t stream);
 // Rows between a .kb file's dense layout in one number type and the cube's padded layout in another (kb_kernels.hip:
 // convert_rows_kernel).  `dense`: nRows rows of T elements back to back, denseElem (4 | 8) bytes each, only element-aligned.
 // `cube`: the first row's question block; dense row r is the cube's row (r / rowsPerQ) * qStride + r % rowsPerQ + rowBase, rows ldT

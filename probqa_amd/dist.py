@@ -608,6 +608,48 @@ def next_question_sampled(engine, quiz: int, rnd: int, rank: int, world: int, gr
     return question
 
 
+# ---- RecordAnswer in the process-per-GPU form --------------------------------------------------------------------------------
+# Only the rank that holds a quiz's active question can compute the new posterior (it needs the question's two rows); the others
+# only need to store it.  The holders pack the posteriors into a POSTERIOR PACKAGE (PqaHip_PackAnswerPosteriors: slot i = quiz i's
+# new posterior, T doubles at a pitch that depends on T alone, zeros behind them) WITHOUT changing any quiz, the ranks sum their
+# packages and exchange one status word, and only then every rank records from the combined package
+# (PqaEngine_RecordAnswerBatchFromPosteriors).  The sum moves bits: every slot is written by exactly one rank -- the holder of the
+# quiz's active question -- into a zero-filled buffer, a posterior's elements and the zeros behind them are finite, and
+# x + 0 == x.  (-0.0 + 0.0 is +0.0, and a posterior holds no -0.0: its elements are products and quotients of non-negative numbers.)
+# A posterior depends on the cube: no rank may train between the pack and the recording inside the call.  The single-quiz,
+# caller-driven form -- RecordAnswer on the holder, RecordAnswerRemote elsewhere, broadcast_prior -- stays.  Over a process group
+# nothing here has been timed (tools/record_ranks_bench.py times the engine calls with the shards on one device).
+
+
+def record_answer_batch(engine, quizzes, answers, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                        device: Optional[torch.device] = None) -> None:
+    """PqaEngine_RecordAnswerBatch on the shards of `world` ranks: a collective every rank calls with the same quizzes -- each
+    with an active question, the same on every rank -- and the same answers, at most 256.  All or none over the ranks as over the
+    entries: the pack validates the whole batch and changes nothing, a rank whose pack is refused still takes part in the
+    all-reduce, and after the status word that follows NOBODY records if any rank's pack was refused -- every rank raises the
+    first failing rank's text, and no quiz has changed anywhere.  A second status word covers the recording itself.  Under an
+    NCCL (RCCL) group the package stays on the device, under gloo it goes through the host."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    quizzes, answers = [int(q) for q in quizzes], [int(a) for a in answers]
+    pitch = engine.posterior_slot_bytes() // 8
+    pkg = torch.zeros(max(len(quizzes), 1), pitch, dtype=torch.float64, device=ranks.device)
+    error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_answer_posteriors(quizzes, answers, ptr))
+    ranks.settle(error)
+    try:
+        engine.record_answer_batch_from_posteriors(quizzes, answers, pkg.data_ptr())
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)
+
+
+def record_answer(engine, quiz: int, answer: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                  device: Optional[torch.device] = None) -> None:
+    """PqaEngine_RecordAnswer likewise: the batch of one."""
+    record_answer_batch(engine, [quiz], [answer], rank, world, group, device)
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

@@ -159,6 +159,9 @@ HIP_EXPORTS = {
     "PqaHip_PackSampledParts": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
     "PqaHip_SampledPickFromParts": (_vp, [_vp, _i64, _pi64, _pu64, _vp, _i64, _i64, ctypes.POINTER(CiHipSelection)]),
     "PqaEngine_TakeSampledPicks": (_vp, [_vp, _i64, _pi64, _pi64, _pi64]),
+    "PqaHip_PosteriorSlotBytes": (_i64, [_vp]),
+    "PqaHip_PackAnswerPosteriors": (_vp, [_vp, _i64, _pi64, _pi64, _vp, _vp, ctypes.c_uint64]),
+    "PqaEngine_RecordAnswerBatchFromPosteriors": (_vp, [_vp, _i64, _pi64, _pi64, _vp]),
     "PqaEngine_ResumeQuizFromRows": (_i64, [_vp, _pvp, _i64, _pAQ, _vp]),
     "PqaEngine_ResumeQuizBatchFromRows": (_vp, [_vp, _i64, _pi64, _pAQ, _vp, _pi64]),
     "PqaEngine_RecordAnswerBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
@@ -872,6 +875,32 @@ class PqaEngine:
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_TakeSampledPicks(self.c_engine, n, qs, ps, out))
         return list(out[:n])
+
+    # ---- posterior packages: RecordAnswer for many quizzes on a shard that a process of its own drives (include/PqaHipExt.h) ----
+    def posterior_slot_bytes(self) -> int:
+        """Bytes of one slot of a posterior package: a function of the target count alone."""
+        return _lib.PqaHip_PosteriorSlotBytes(self.c_engine)
+
+    def pack_answer_posteriors(self, quizzes, answers, dst: int, flag: int = 0, flag_value: int = 0) -> None:
+        """Enqueue (no synchronisation, no change of any quiz) the posteriors that answers[i] to the active question of quizzes[i]
+        would leave, for the quizzes whose active question this engine holds, into their slots of the package at device-visible
+        16-byte aligned address `dst`; `flag` (an address, 0 = none) receives `flag_value` once they are visible."""
+        n = len(quizzes)
+        if len(answers) != n:
+            raise ValueError("one answer per quiz")
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        ans = (ctypes.c_int64 * max(n, 1))(*answers)
+        _check(_lib.PqaHip_PackAnswerPosteriors(self.c_engine, n, qs, ans, ctypes.c_void_p(dst or None), ctypes.c_void_p(flag or None), flag_value))
+
+    def record_answer_batch_from_posteriors(self, quizzes, answers, posteriors: int) -> None:
+        """RecordAnswer's bookkeeping for the batch of this engine's latest pack_answer_posteriors, every quiz's posterior taken
+        from its slot of the combined package at device-visible address `posteriors`."""
+        n = len(quizzes)
+        if len(answers) != n:
+            raise ValueError("one answer per quiz")
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        ans = (ctypes.c_int64 * max(n, 1))(*answers)
+        _check(_lib.PqaEngine_RecordAnswerBatchFromPosteriors(self.c_engine, n, qs, ans, ctypes.c_void_p(posteriors or None)))
 
     def train_batch(self, records, throw: bool = True) -> Optional[PqaError]:
         """Train for every (answered_questions, i_target, amount) of `records` in one call: the KB consecutive `train` calls
