@@ -254,6 +254,48 @@ PQACORE_API void *PqaEngine_ListTopQuestionsBatch(void *pvEngine, const int64_t 
  * lowest index on ties) and calls PqaEngine_SetActiveQuestion on every shard. */
 PQACORE_API void *PqaHip_SelectArgmaxBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, CiHipSelection *pOut);
 PQACORE_API void *PqaEngine_EvalPrioritiesBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, double *pOut);
+/* ---- The Among calls: evaluate and select over a LISTED set of questions per quiz (skipping a question, topics / locales / tenants
+ * on one knowledge base, re-evaluating a short list between full sweeps).  "Among a list L" means: for this call only, every question
+ * outside L counts as asked.  Quiz i's list is the pCounts[i] GLOBAL question ids starting at pQuestions[sum(pCounts[0..i))]; nQuizzes
+ * <= 256 distinct quizzes.  One launch evaluates all (quiz, question) pairs of the call (among_kernels.hip: eval_listed_kernel), so the
+ * cost follows the lists, not nQuestions: a Double engine's priorities are PqaEngine_EvalPriorities' to 1e-9 relative, late quiz states
+ * included (the listed sweep watches for rows at the pole and the pole fix runs behind it, option "pole_fix"); a Float engine's are the
+ * fp64 priorities on its fp32 cube rows (no fp32 sweep, no re-rank, no pole fix).
+ *   A listed question that is a gap or was asked has priority 0 and is never picked; one that another process's shard holds is skipped
+ *   on this shard (priority 0 here).  An empty list is no error: that quiz's pick is -1 and its state does not change.
+ *   Argmax: maximum priority, lowest global id among equals; a NaN never wins.  Sampled: the reference's selector
+ *   (PqaCore/CpuEngine.cpp:362-400) over the whole question axis with the skip bits gaps | asked | not listed; its fallback to the nearest
+ *   free question (:403-406) runs over the same bits and never leaves the list.
+ *   Errors: an id outside [0, nQuestions of the whole knowledge base) or repeated within one quiz's list is IndexOutOfRange naming the
+ *   batch entry and the position; a negative count NegativeCount; unknown or repeated quizzes, nQuizzes > 256, missing buffers and
+ *   maintenance mode as PqaEngine_EvalPrioritiesBatch / PqaEngine_NextQuestionSampledBatch answer them.  A refused call launches nothing,
+ *   draws no random number and changes nothing.  The one-process sharded engine (PQA_DEVICES) answers NotImplemented.
+ *   Nothing of size nQuestions crosses to the host: sum(pCounts) doubles for the evaluating call, the records for the selecting ones
+ *   (read-only option "priority_host_bytes" counts them).  Read-only options "among_calls" / "among_pairs": the accepted calls and the
+ *   pairs of theirs this engine holds.  No quiz's own speculative or resident state is touched: a PqaEngine_NextQuestion that follows
+ *   returns what it would have returned without the call.
+ *   When to use which (tools/among_bench.py, profiles/README.md): the listed sweep re-reads a question's rows from cache for its second pass
+ *   where the full sweeps keep them on chip -- measured on an MI355X for batches of 64-256 quizzes, the full
+ *   sweep (PqaEngine_NextQuestionArgmaxBatch) is the cheaper call from a list of about 7-8 % of nQuestions at 1000 x 5 x 1000 and on a Float
+ *   engine at 10000 x 5 x 10000, and from about 16 % on a Double engine at 10000 x 5 x 10000 (one quiz there: 23 %; one quiz at 1000 x 5 x 1000:
+ *   the single-quiz sweep is always cheaper).  With the whole axis listed the call is slower than the full sweep by 4-6 x (Double,
+ *   10000 x 5 x 10000) to 13 x (1000 x 5 x 1000; Float engines).  256 quizzes x 16 questions: 0.4 ms and 1.5 ms at the two sizes.
+ * pOut is parallel to pQuestions. */
+PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                     const int64_t *pQuestions, double *pOut);
+/* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
+ * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
+PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                const int64_t *pQuestions, CiHipSelection *pOut);
+/* The three selecting forms do PqaEngine_NextQuestion's bookkeeping: the active question, and one question asked per quiz that got one.
+ * pPicked[i]: the GLOBAL id, or -1.  PqaEngine_NextQuestionAmongBatch obeys option "select": with select = 0 it draws one number per
+ * quiz from the engine's generator in batch order, after the whole call has been validated (as PqaEngine_NextQuestionBatch). */
+PQACORE_API void *PqaEngine_NextQuestionArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                         const int64_t *pQuestions, int64_t *pPicked);
+PQACORE_API void *PqaEngine_NextQuestionSampledAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                          const int64_t *pQuestions, const uint64_t *pRnd, int64_t *pPicked);
+PQACORE_API void *PqaEngine_NextQuestionAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                   const int64_t *pQuestions, int64_t *pPicked);
 /* pOut[i] = the device's Log2Hot(pIn[i]) (host buffers): the function the sweep applies to every posterior element
  * (replaces SRVectMath::Log2Hot, reference SRPlatform/Interface/SRVectMath.h:87-135), exposed so that it can be held to
  * the reference's own SRVectMathTest.Log2Hot criteria (SRPlatformTests/SRVectMathTest.cpp:45-103). */

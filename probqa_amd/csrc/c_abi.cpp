@@ -388,6 +388,26 @@ PQACORE_API void *PqaEngine_ListTopQuestionsBatch(void *pvEngine, const int64_t 
                                                   CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListTopQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
 }
+PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                     const int64_t *pQuestions, double *pOut) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalPrioritiesAmongBatch(nQuizzes, pQuizzes, pCounts, pQuestions, pOut); });
+}
+PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                const int64_t *pQuestions, CiHipSelection *pOut) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.SelectArgmaxAmongBatch(nQuizzes, pQuizzes, pCounts, pQuestions, pOut); });
+}
+PQACORE_API void *PqaEngine_NextQuestionArgmaxAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                         const int64_t *pQuestions, int64_t *pPicked) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.NextQuestionArgmaxAmongBatch(nQuizzes, pQuizzes, pCounts, pQuestions, pPicked); });
+}
+PQACORE_API void *PqaEngine_NextQuestionSampledAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                          const int64_t *pQuestions, const uint64_t *pRnd, int64_t *pPicked) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.NextQuestionSampledAmongBatch(nQuizzes, pQuizzes, pCounts, pQuestions, pRnd, pPicked); });
+}
+PQACORE_API void *PqaEngine_NextQuestionAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                   const int64_t *pQuestions, int64_t *pPicked) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.NextQuestionAmongBatch(nQuizzes, pQuizzes, pCounts, pQuestions, pPicked); });
+}
 PQACORE_API void *PqaHip_SelectArgmaxBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, CiHipSelection *pOut) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.SelectArgmaxBatch(nQuizzes, pQuizzes, pOut); });
 }

@@ -135,8 +135,21 @@ class IEngine {
   virtual Error RecordAnswerBatchFromPosteriors(int64_t, const int64_t *, const int64_t *, const void *) {
     return NoPosteriors("RecordAnswerBatchFromPosteriors");
   }
+  // The Among calls: evaluate and select over a listed set of questions.  A process-per-GPU host merges its shards' winners itself
+  // (PqaHip_SelectArgmaxAmongBatch); the one-process sharded engine does not offer them.
+  virtual Error EvalPrioritiesAmongBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, double *) { return NoAmong("EvalPrioritiesAmongBatch"); }
+  virtual Error SelectArgmaxAmongBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, CiHipSelection *) { return NoAmong("SelectArgmaxAmongBatch"); }
+  virtual Error NextQuestionArgmaxAmongBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t *) { return NoAmong("NextQuestionArgmaxAmongBatch"); }
+  virtual Error NextQuestionSampledAmongBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, const uint64_t *, int64_t *) {
+    return NoAmong("NextQuestionSampledAmongBatch");
+  }
+  virtual Error NextQuestionAmongBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t *) { return NoAmong("NextQuestionAmongBatch"); }
 
  private:
+  static Error NoAmong(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
+                        "The Among calls are for whole engines and for shards that separate processes drive.");
+  }
   static Error NoPosteriors(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine", "Posterior packages are for shards that separate processes drive.");
   }

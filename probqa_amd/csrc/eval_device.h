@@ -84,4 +84,24 @@ __device__ __forceinline__ double eval_epilogue(const double *mW, double whSum, 
   return eval_epilogue_strided(mW, whSum, mWV, K, lackSum, vCompTail, 1);
 }
 
+// One element pair of pass 2 (:95-128).  lh: likelihoods, id: 1/D, pr: masked priors.
+__device__ __forceinline__ void pass2_pair(double2 lh, double2 id, double2 pr, double invWk, const double *tbl,
+                                           double &hW, double &v, double &accL) {
+  const double p0 = lh.x * invWk, p1 = lh.y * invWk;           // :97
+  const double d0 = p0 - pr.x, d1 = p1 - pr.y;                 // :119 (first: log2hot may then rework p's registers in place)
+  const double l20 = log2hot(p0, tbl), l21 = log2hot(p1, tbl); // :106 (gap lanes: p = 0 -> -1023, contributes -0)
+  hW = fma(lh.x, l20, hW);                                     // :113-114 weighted by W_k (see eval_epilogue)
+  hW = fma(lh.y, l21, hW);
+  // :117 lack += invD^2 / log2(p) for both elements over one reciprocal: (ix^2*l21 + iy^2*l20) / (l20*l21), the
+  // reciprocal by v_rcp_f64 + one Newton step (2^-48.8, below the sum's own rounding).  The squares are written
+  // (ix*l)*ix: as ix^2*l they are invariant over the answers and the compiler hoists 2*NP of them into registers.
+  const double prod = l20 * l21;
+  double r = __builtin_amdgcn_rcp(prod);
+  r = fma(r, fma(-prod, r, 1.0), r);
+  const double num = fma(id.y * l20, id.y, (id.x * l21) * id.x);
+  accL = fma(num, r, accL);
+  v = fma(d0, d0, v);                                          // :126-127
+  v = fma(d1, d1, v);
+}
+
 }  // namespace pqa

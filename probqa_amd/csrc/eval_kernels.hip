@@ -220,25 +220,7 @@ __device__ __forceinline__ void fused_select(const EvalArgs &a, Best mine, int l
   }
 }
 
-// One element pair of pass 2 (:95-128).  lh: likelihoods, id: 1/D, pr: masked priors.
-__device__ __forceinline__ void pass2_pair(double2 lh, double2 id, double2 pr, double invWk, const double *tbl,
-                                           double &hW, double &v, double &accL) {
-  const double p0 = lh.x * invWk, p1 = lh.y * invWk;           // :97
-  const double d0 = p0 - pr.x, d1 = p1 - pr.y;                 // :119 (first: log2hot may then rework p's registers in place)
-  const double l20 = log2hot(p0, tbl), l21 = log2hot(p1, tbl); // :106 (gap lanes: p = 0 -> -1023, contributes -0)
-  hW = fma(lh.x, l20, hW);                                     // :113-114 weighted by W_k (see eval_epilogue)
-  hW = fma(lh.y, l21, hW);
-  // :117 lack += invD^2 / log2(p) for both elements over one reciprocal: (ix^2*l21 + iy^2*l20) / (l20*l21), the
-  // reciprocal by v_rcp_f64 + one Newton step (2^-48.8, below the sum's own rounding).  The squares are written
-  // (ix*l)*ix: as ix^2*l they are invariant over the answers and the compiler hoists 2*NP of them into registers.
-  const double prod = l20 * l21;
-  double r = __builtin_amdgcn_rcp(prod);
-  r = fma(r, fma(-prod, r, 1.0), r);
-  const double num = fma(id.y * l20, id.y, (id.x * l21) * id.x);
-  accL = fma(num, r, accL);
-  v = fma(d0, d0, v);                                          // :126-127
-  v = fma(d1, d1, v);
-}
+// (eval_device.h: pass2_pair -- one element pair of pass 2, shared with among_kernels.hip)
 
 // ------------------------------------------------------------------------------------------------------------------
 // Rows at the pole of the lack term.  lack = -sum invD^2 / log2(p) (:117) has a pole at p -> 1: with a posterior element at
@@ -260,8 +242,7 @@ __device__ __forceinline__ void pass2_pair(double2 lh, double2 id, double2 pr, d
 // inside the row loop from the registers (+10 - 50 % in EVERY state: the blocks between pass 1 and pass 2 cost the loop its
 // registers), the fix as a called function (+13 %: scratch).
 // ------------------------------------------------------------------------------------------------------------------
-constexpr double kNearOneShare = 1.0 - 0x1p-9;   // (of W_k, in the streaming kernel's votes: see above; the bar is pole_device.h: kNearOneHi)
-constexpr double kQuarterShare = 0.2499;         // ... and the wider watch (a strict compare: a wave of padding lanes, all sums 0, does not pass) for rows with a vanishing velocity sum (pole_device.h: kSmallV)
+// (pole_device.h: kNearOneShare, kQuarterShare -- the bars of the streaming kernel's votes, shared with among_kernels.hip)
 constexpr int kSusDoubles = 4;                 // LDS: words [0], [1] by question parity (the answer rows that passed the watch, a bit each), [4] the list slot -- an EVEN count of doubles: the LDS priors behind it are read as 16-byte pairs
 
 // ------------------------------------------------------------------------------------------------------------------

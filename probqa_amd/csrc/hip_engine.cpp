@@ -177,6 +177,7 @@ Error HipEngine::Init(const CiEngineDefinition &def, const CiHipShard *shard) {
       if (tblErr == hipSuccess) tblErr = UploadLog2TableBatch(tbl.data());
       if (tblErr == hipSuccess) tblErr = UploadLog2TableCluster(tbl.data());
       if (tblErr == hipSuccess) tblErr = UploadLog2TablePole(tbl.data());
+      if (tblErr == hipSuccess) tblErr = UploadLog2TableAmong(tbl.data());
     });
     HIP_TRY(tblErr);
   }
@@ -252,7 +253,7 @@ HipEngine::~HipEngine() {
   hipFree(_dCube); hipFree(_dVB); hipFree(_dPriority); hipFree(_dRunLength); hipFree(_dPoleScratch); hipFree(_dExps); hipFree(_dStatus);
   hipFree(_dNOut); hipFree(_dSel); hipFree(_dSelScratch); hipFree(_dPriorScratch); hipFree(_dClusterScratch);
   for (BatchCtx &c : _ctx) {
-    hipFree(c.dSlots); hipFree(c.dScratch); hipFree(c.dPriority); hipFree(c.dPT); hipFree(c.dAcc); hipFree(c.dRecs); hipFree(c.dPriT); hipFree(c.dRerank); hipFree(c.dPole); hipFree(c.dSelGrand); hipFree(c.dSelRun);
+    hipFree(c.dSlots); hipFree(c.dScratch); hipFree(c.dPriority); hipFree(c.dPT); hipFree(c.dAcc); hipFree(c.dRecs); hipFree(c.dPriT); hipFree(c.dRerank); hipFree(c.dPole); hipFree(c.dSelGrand); hipFree(c.dSelRun); hipFree(c.dAmong); hipFree(c.dAmongMask);
     if (c.evSel[0]) { hipEventDestroy(c.evSel[0]); hipEventDestroy(c.evSel[1]); }
     if (c.hPri) hipHostFree(c.hPri);
     if (c.event) hipEventDestroy(c.event);
@@ -342,6 +343,8 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"sampled_batches", &HipEngine::_sampledBatches},                   // NextQuestionSampledBatch calls that selected ...
       {"sampled_batch_device_ns", &HipEngine::_sampledBatchDeviceNs},     // ... and their selector launches' time between events
       {"priority_host_bytes", &HipEngine::_priorityHostBytes},            // priorities the batched sweeps delivered to the host
+      {"among_calls", &HipEngine::_amongCalls},                           // Among calls that were accepted (hip_engine_among.cpp) ...
+      {"among_pairs", &HipEngine::_amongPairs},                           // ... and the (quiz, question) pairs of theirs this engine holds
       {"fused_updates", &HipEngine::_fusedUpdates},                       // RecordAnswers whose update ran inside the sweep's launch
       {"top_exact_listings", &HipEngine::_topExactListings},
       {"combined_batches", &HipEngine::_combBatches},                     // sweeps that served more than one NextQuestion call ...

@@ -246,6 +246,14 @@ class HipEngine : public IEngine {
   // the best next questions by priority (hip_engine_list.cpp): what EvalPriorities / EvalPrioritiesBatch return, listed on the device
   int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
   Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
+  // ---- the Among calls (hip_engine_among.cpp): evaluate and select over a listed set of questions per quiz -- for the call, every
+  // question outside the list counts as asked.  Quiz i's list: pCounts[i] GLOBAL ids from pQuestions[sum(pCounts[0..i))].
+  Error EvalPrioritiesAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, double *pOut) override;
+  Error SelectArgmaxAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, CiHipSelection *pOut) override;
+  Error NextQuestionArgmaxAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, int64_t *pPicked) override;
+  Error NextQuestionSampledAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, const uint64_t *pRnd,
+                                      int64_t *pPicked) override;
+  Error NextQuestionAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, int64_t *pPicked) override;
   // ---- a shard driven by a process of its own (hip_engine_resume.cpp): the rows of answered questions as a package -- slot i
   // = sA[q_i][k_i][0..ldT) then mD[q_i][0..ldT), in the cube's element type -- filled by the owners, consumed by every rank
   int64_t AnswerRowSlotBytes() const override { return 2 * _ldT * (int64_t)_elem; }
@@ -632,6 +640,10 @@ class HipEngine : public IEngine {
     double *dSelGrand = nullptr, *dSelRun = nullptr;   // the batched sampled selector's totals and run lengths (select_kernels.hip)
     size_t selGrandBytes = 0, selRunBytes = 0;
     hipEvent_t evSel[2] = {nullptr, nullptr};          // around that selector's launch
+    void *dAmong = nullptr;              // the Among calls' staging: list offsets per quiz | pairs | the gathered priorities
+    size_t amongBytes = 0;
+    uint32_t *dAmongMask = nullptr;      // ... and the quizzes' bitmaps asked | not listed, for the sampled selector
+    size_t amongMaskBytes = 0;
     int lastBp = 0;
     double *hPri = nullptr;              // pinned: the batch's priority vectors for the host-side selector -- copied there behind the
     size_t hPriDoubles = 0;              // row-sharing sweep, or written there by the grid.y = quiz sweep itself as {priority, launch tag} records
@@ -647,6 +659,23 @@ class HipEngine : public IEngine {
   // devicePriorities: the batch's form as for an argmax batch, every quiz's priorities left on the device (its own vector or the
   // quiz-minor matrix: lastBp), the sweep's own winners published to sweepOut / sweepSeq -- for the selector launched behind it
   Error ValidateBatchLocked(int64_t n, const int64_t *pQuizzes);
+  Error EnsureBatchStaging(BatchCtx &c);    // the pinned staging lines, the device slots and the winner records: the first batch allocates them
+  Error EnsureBatchVectors(BatchCtx &c);    // the per-quiz priority vectors dPriority, (re)sized with the knowledge base
+  // The Among calls (hip_engine_among.cpp).  AmongStage: one call's lists as the kernels take them -- the quizzes with a non-empty list in
+  // batch order (slot j), their pairs back to back, and where pair p of the call's pQuestions went.
+  struct AmongStage {
+    std::vector<int64_t> entry;            // slot j -> batch entry i
+    std::vector<int64_t> offsets;          // slot j's pairs: [offsets[j], offsets[j + 1])
+    std::vector<ListedPair> pairs;
+    std::vector<uint32_t> masks;           // sampled forms: slot j's asked | not listed, maskWords words each (bits past Q clear, as `asked`)
+    std::vector<int64_t> stamp;            // validation: the batch entry (+ 1) that listed a question last
+    int64_t local = 0;                     // pairs whose question this engine holds
+  } _among;
+  enum class AmongForm { Eval, Select, Argmax, Sampled };
+  Error ValidateAmongLocked(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, bool haveOut);
+  Error AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, const uint64_t *pRnd,
+                    double *pPriorities, CiHipSelection *pSel, int64_t *pPicked);
+  uint64_t _amongCalls = 0, _amongPairs = 0;   // read-only "among_calls", "among_pairs"
   Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
   Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
   // The engine's latest pack of selection parts: what a pick must find unchanged -- the quizzes and their posteriors, the split, this

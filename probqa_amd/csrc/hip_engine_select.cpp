@@ -304,15 +304,30 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   return FinishSelection(err, q, _hPinned->sel.index);
 }
 
+Error HipEngine::EnsureBatchStaging(BatchCtx &c) {
+  if (c.h) return Error();
+  // first batch: staging in host-coherent pinned memory, winner records
+  HIP_TRY(hipHostMalloc(&c.h, sizeof(BatchPinned), hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(c.h, 0, sizeof(BatchPinned));
+  HIP_TRY(hipMalloc(&c.dSlots, kMaxBatch * sizeof(QuizSlot)));
+  HIP_TRY(hipMalloc(&c.dScratch, (size_t)kMaxBatch * kBatchGrid * sizeof(SelectResult)));
+  HIP_TRY(hipMemset(c.dScratch, 0, (size_t)kMaxBatch * kBatchGrid * sizeof(SelectResult)));
+  return Error();
+}
+
+Error HipEngine::EnsureBatchVectors(BatchCtx &c) {   // per-quiz priority vectors, (re)sized with the knowledge base
+  if (c.priorityQ == _Q) return Error();
+  if (c.dPriority) hipFree(c.dPriority);
+  c.dPriority = nullptr;
+  c.priorityQ = -1;
+  HIP_TRY(hipMalloc(&c.dPriority, (size_t)kMaxBatch * (size_t)_Q * sizeof(double)));
+  c.priorityQ = _Q;
+  return Error();
+}
+
 Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std::vector<Quiz *> &quizzes, bool wantPriorities, uint64_t tag,
                             bool hostPriorities, bool *pQuizMinor, bool *pTagged, bool devicePriorities) {
-  if (!c.h) {  // first batch: staging in host-coherent pinned memory, winner records
-    HIP_TRY(hipHostMalloc(&c.h, sizeof(BatchPinned), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(c.h, 0, sizeof(BatchPinned));
-    HIP_TRY(hipMalloc(&c.dSlots, kMaxBatch * sizeof(QuizSlot)));
-    HIP_TRY(hipMalloc(&c.dScratch, (size_t)kMaxBatch * kBatchGrid * sizeof(SelectResult)));
-    HIP_TRY(hipMemset(c.dScratch, 0, (size_t)kMaxBatch * kBatchGrid * sizeof(SelectResult)));
-  }
+  { Error se = EnsureBatchStaging(c); if (!se.ok()) return se; }
   // Which form: the row-sharing sweep has one wave per 64 quizzes and block of questions -- on a small cube a small batch
   // leaves most of the chip's 1024 SIMDs without a wave (1000 x 5 x 1000, 64 quizzes: 500 waves, 40 k selections/s against
   // 92 k for grid.y = quiz, whose 48 MB cube is re-read from the Infinity Cache), while 256 quizzes fill it (133 k vs 95 k).
@@ -356,13 +371,7 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
     _priorityHostBytes += doubles * sizeof(double);
     return Error();
   };
-  if (!rowSharing && c.priorityQ != _Q) {  // per-quiz priority vectors of the grid.y form, (re)sized with the knowledge base
-    if (c.dPriority) hipFree(c.dPriority);
-    c.dPriority = nullptr;
-    c.priorityQ = -1;
-    HIP_TRY(hipMalloc(&c.dPriority, (size_t)kMaxBatch * (size_t)_Q * sizeof(double)));
-    c.priorityQ = _Q;
-  }
+  if (!rowSharing) { Error ve = EnsureBatchVectors(c); if (!ve.ok()) return ve; }   // (the grid.y form's per-quiz priority vectors)
   Error err;
   quizzes.assign((size_t)n, nullptr);
   for (int64_t i = 0; i < n; i++) {

@@ -25,6 +25,12 @@ constexpr uint32_t kNearOneHi = 0x3FEFF800u;   // high word of 1 - 2^-10
 constexpr double kSmallV = 2e-12;
 constexpr uint32_t kQuarterHi = 0x3FCE0000u;   // high word of 0.234: the element of a listed row whose terms are corrected
 
+// The same bars as shares of W_k, for sweeps that vote per row on a lane's pass-1 sum (eval_kernels.hip: eval_questions_f64_stream,
+// among_kernels.hip: eval_listed_kernel): all terms are >= 0, so the lane that holds an element within 2^-10 of 1 has at least
+// (1 - 2^-9) of W_k.
+constexpr double kNearOneShare = 1.0 - 0x1p-9;   // (of W_k, in the streaming kernel's votes: see above; the bar is pole_device.h: kNearOneHi)
+constexpr double kQuarterShare = 0.2499;         // ... and the wider watch (a strict compare: a wave of padding lanes, all sums 0, does not pass) for rows with a vanishing velocity sum (pole_device.h: kSmallV)
+
 // a sweep's entry for a question that passed its watch (pqa_kernels.h: PoleHeader; one thread)
 __device__ __forceinline__ uint32_t pole_list_append(PoleHeader *list, uint32_t q, uint32_t rowMask, uint32_t b, uint32_t gap = 0u) {
   const uint32_t at = atomicAdd(&list->count, 1u);

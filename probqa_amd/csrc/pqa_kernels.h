@@ -310,6 +310,24 @@ hipError_t LaunchEvalMidBatch(const KbView &kb, const QuizSlot *slots, int nSlot
 size_t BatchRerankScratchBytes();
 hipError_t LaunchBatchRerank(const KbView &kb, const QuizSlot *slots, int nSlots, int Bp, const double *priorityT, void *scratch,
                              int64_t outBase, uint64_t flagValue, hipStream_t stream);
+// ---- the sweep over a LIST of (quiz, question) pairs (among_kernels.hip; the Among calls): pair i = {slot b of `slots`, LOCAL
+// question q, or q < 0: a question another shard holds -- nothing is evaluated}.  One launch for all pairs; the priority of pair i
+// goes to slots[b].priority[q] (0 for a gap or an asked question -- slots[b].asked is tested), in fp64 on either cube type.
+// pole (optional, Double engines with a pole list): EvalListedPoleBytes(kb, nPairs) bytes whose first kBatchPoleClear bytes were cleared
+// once after allocation (every launch leaves them cleared: the batched sweeps' scratch serves) -- the sweep then watches for rows at the
+// pole of the lack term and pole_fixup_kernel runs behind it, storing the corrected priorities to the same places.
+struct ListedPair { int32_t b, q; };
+hipError_t UploadLog2TableAmong(const double *hostTable);
+size_t EvalListedPoleBytes(const KbView &kb, int64_t nPairs);   // 0: this engine's listed sweep does not watch
+hipError_t LaunchEvalListed(const KbView &kb, const QuizSlot *slots, int nSlots, const ListedPair *pairs, int64_t nPairs, void *pole,
+                            hipStream_t stream);
+// out[i] = slots[b].priority[q] of pair i (0 where q < 0): what EvalPrioritiesAmongBatch copies to the host
+hipError_t LaunchListedGather(const QuizSlot *slots, const ListedPair *pairs, int64_t nPairs, double *out, hipStream_t stream);
+// Quiz b's best question among its pairs [offsets[b], offsets[b + 1]) -- maximum priority, lowest question among equals, NaN never wins;
+// gaps, asked and other shards' questions are no candidates -- as {priority, q + outBase or -1} to slots[b].out, then flagValue to
+// slots[b].seq (host-coherent).
+hipError_t LaunchListedArgmax(const KbView &kb, const QuizSlot *slots, int nSlots, const int64_t *offsets, const ListedPair *pairs, int64_t outBase,
+                              uint64_t flagValue, hipStream_t stream);
 // Single-quiz sweep of a Float engine: priority[q] for every local question (0 for gap / asked).
 hipError_t LaunchEvalQuestionsF32(const KbView &kb, const double *prior, const uint32_t *asked, double *priority, hipStream_t stream);
 // ... with the question's rows held in registers (eval_f32_kernels.hip): rows of up to 16384 targets, up to 16 answers

@@ -85,6 +85,18 @@ def select_batch(local_winners: torch.Tensor, group: Optional[dist.ProcessGroup]
     return pick_batch(torch.stack(parts))
 
 
+def select_among_batch(engine, quizzes, lists, group: Optional[dist.ProcessGroup] = None, device: Optional[torch.device] = None) -> List[int]:
+    """The argmax AMONG LISTS over the shards (PqaHip_SelectArgmaxAmongBatch): every rank calls with the same quizzes and the same
+    lists of GLOBAL question ids; each shard evaluates the listed questions it holds and reports its winner per quiz, then the
+    gather and pick of select_batch -> the same picks on every rank (-1: no eligible question in the list).  The active questions
+    are NOT set: the caller follows with PqaEngine_SetActiveQuestion on every rank.  device: where the collective's tensors live
+    (the group's device under RCCL; None: the CPU, as under gloo)."""
+    local = torch.from_numpy(engine.select_argmax_among_batch(quizzes, lists))
+    if device is not None:
+        local = local.to(device)
+    return select_batch(local, group)
+
+
 # ---- the process group as one collective sees it ----------------------------------------------------------------------------
 # The only place that knows about backends.  A collective's tensors live on the device exactly when the group's backend is "nccl" (RCCL);
 # under gloo a device payload makes the detour through the host.  The ranks stay in step only because every rank issues the same

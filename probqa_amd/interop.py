@@ -136,6 +136,11 @@ HIP_EXPORTS = {
     "PqaHip_SelectArgmaxBatch": (_vp, [_vp, _i64, _pi64, ctypes.POINTER(CiHipSelection)]),
     "PqaEngine_NextQuestionArgmaxBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_NextQuestionSampledBatch": (_vp, [_vp, _i64, _pi64, _pu64, _pi64]),
+    "PqaEngine_EvalPrioritiesAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _pdbl]),
+    "PqaHip_SelectArgmaxAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, ctypes.POINTER(CiHipSelection)]),
+    "PqaEngine_NextQuestionArgmaxAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _pi64]),
+    "PqaEngine_NextQuestionSampledAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _pu64, _pi64]),
+    "PqaEngine_NextQuestionAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _pi64]),
     "PqaEngine_NextQuestionBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_NextQuestionSampled": (_i64, [_vp, _pvp, _i64, _u64]),
     "PqaHip_GetPriors": (_vp, [_vp, _i64, _pdbl, _i64]),
@@ -717,6 +722,68 @@ class PqaEngine:
         out = (CiHipSelection * max(n, 1))()
         _check(_lib.PqaHip_SelectArgmaxBatch(self.c_engine, n, qs, out))
         return np.array([(out[i].priority, out[i].iQuestion) for i in range(n)], dtype=np.float64).reshape(n, 2)
+
+    # ---- the Among calls: evaluate and select over a listed set of questions per quiz (GLOBAL ids; for the call, every question
+    # outside a quiz's list counts as asked)
+    @staticmethod
+    def _among_args(quizzes, lists):
+        n = len(quizzes)
+        if len(lists) != n:
+            raise ValueError("one list of question ids per quiz")
+        flat = [int(q) for ids in lists for q in ids]
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        counts = (ctypes.c_int64 * max(n, 1))(*[len(ids) for ids in lists])
+        ids = (ctypes.c_int64 * max(len(flat), 1))(*flat)
+        return n, qs, counts, ids, len(flat)
+
+    def eval_priorities_among_batch(self, quizzes, lists) -> List[np.ndarray]:
+        """The priorities of every quiz's listed questions from one launch over the (quiz, question) pairs: entry i is parallel to
+        lists[i]; 0 for a gap, an asked question, or a question another process's shard holds."""
+        n, qs, counts, ids, total = self._among_args(quizzes, lists)
+        out = np.zeros(max(total, 1), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalPrioritiesAmongBatch(self.c_engine, n, qs, counts, ids, _dptr(out)))
+        ends = np.cumsum([len(x) for x in lists]) if n else []
+        return [out[e - len(x):e].copy() for e, x in zip(ends, lists)]
+
+    def select_argmax_among_batch(self, quizzes, lists) -> np.ndarray:
+        """This engine's (shard's) winners among the lists: array [n, 2] of (priority, GLOBAL question id or -1); no bookkeeping."""
+        n, qs, counts, ids, _ = self._among_args(quizzes, lists)
+        out = (CiHipSelection * max(n, 1))()
+        _check(_lib.PqaHip_SelectArgmaxAmongBatch(self.c_engine, n, qs, counts, ids, out))
+        return np.array([(out[i].priority, out[i].iQuestion) for i in range(n)], dtype=np.float64).reshape(n, 2)
+
+    def next_question_argmax_among_batch(self, quizzes, lists) -> List[int]:
+        """Argmax NextQuestion of several distinct quizzes, each among its list; -1 for a quiz whose list holds no eligible question."""
+        n, qs, counts, ids, _ = self._among_args(quizzes, lists)
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_NextQuestionArgmaxAmongBatch(self.c_engine, n, qs, counts, ids, out))
+        return list(out[:n])
+
+    def next_question_sampled_among_batch(self, quizzes, rnds, lists) -> List[int]:
+        """The reference's selector for several distinct quizzes, each among its list (skip bits: gaps | asked | not listed)."""
+        n, qs, counts, ids, _ = self._among_args(quizzes, lists)
+        if len(rnds) != n:
+            raise ValueError("one random number per quiz")
+        rs = (ctypes.c_uint64 * max(n, 1))(*[int(r) for r in rnds])
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_NextQuestionSampledAmongBatch(self.c_engine, n, qs, counts, ids, rs, out))
+        return list(out[:n])
+
+    def next_question_among_batch(self, quizzes, lists) -> List[int]:
+        """NextQuestion of several distinct quizzes, each among its list, by the engine's `select` option."""
+        n, qs, counts, ids, _ = self._among_args(quizzes, lists)
+        out = (ctypes.c_int64 * max(n, 1))()
+        _check(_lib.PqaEngine_NextQuestionAmongBatch(self.c_engine, n, qs, counts, ids, out))
+        return list(out[:n])
+
+    def next_question_argmax_among(self, i_quiz: int, ids) -> int:
+        return self.next_question_argmax_among_batch([i_quiz], [list(ids)])[0]
+
+    def next_question_sampled_among(self, i_quiz: int, rnd: int, ids) -> int:
+        return self.next_question_sampled_among_batch([i_quiz], [rnd], [list(ids)])[0]
+
+    def eval_priorities_among(self, i_quiz: int, ids) -> np.ndarray:
+        return self.eval_priorities_among_batch([i_quiz], [list(ids)])[0]
 
     def eval_priorities_batch(self, quizzes, n_local_questions: Optional[int] = None) -> np.ndarray:
         """Priority vectors [len(quizzes), Q] of several distinct quizzes from one sweep that reads the cube once."""
