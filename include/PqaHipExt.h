@@ -283,6 +283,36 @@ PQACORE_API void *PqaEngine_EvalPrioritiesBatch(void *pvEngine, const int64_t nQ
  * pOut is parallel to pQuestions. */
 PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
                                                      const int64_t *pQuestions, double *pOut);
+/* The best targets of nQuizzes quizzes WITHIN A LISTED SET of targets each -- a tenant's catalogue, what is in stock, a platform's
+ * titles -- and how much of the posterior the set holds.  The lists are given once and the quizzes point at them: list l is
+ * pListCounts[l] target ids from pTargets[sum(pListCounts[0..l))], in any order; quiz i takes list pListOf[i], or list i where pListOf
+ * is NULL (then nLists == nQuizzes).  The reference has no such call.
+ *  (a) Candidates: a target of the quiz's list that is no gap and whose posterior is > 0 -- PqaEngine_ListTopTargets' rule.
+ *  (b) Order: probability descending, target id ascending among equal probabilities, whatever the list's order -- the order of the fast
+ *      listing (option "top_exact" 0) and of PqaEngine_ListTopQuestions, NOT the reference's heap order among ties: its heaps are
+ *      defined over the whole target axis, and no call of the reference lists within a set.
+ *  (c) Counts: quiz i gets pCounts[i] = min(maxCount, candidates) records at pDest + i * maxCount.
+ *  (d) Values: the probabilities are the posterior's own bits; nothing is renormalised.
+ *  (e) Mass: pMass[i] (pMass may be NULL) is the sum of the candidates' probabilities in fp64; a client divides by it to renormalise.
+ *  (f) Determinism: the mass is summed in a fixed order without atomics.  The same call gives the same bits, and a quiz's records and
+ *      mass do not depend on what else is in the batch.
+ *  (g) State: no quiz state changes.  Regular mode only; deferred answers are applied first, as in PqaEngine_ListTopTargetsBatch.
+ *  (h) Batch shape: any number of quizzes (256 per launch sequence); a quiz may appear more than once (one quiz under several
+ *      catalogues); a list may be empty (count 0, mass 0); a list no quiz points at is validated and otherwise ignored.
+ *  (i) Refusals, all decided before anything is launched or written: negative nQuizzes, nLists, maxCount (NegativeCount) or list length
+ *      (NegativeCount, "list="); a NULL buffer that is needed (NullArgument); pListOf == NULL with nLists != nQuizzes; pListOf[i] out
+ *      of [0, nLists) ("entry="); an unknown quiz ("entry="); a target id out of [0, nTargets) or twice in one list (IndexOutOfRange,
+ *      "list=", "position=", "targetId=").
+ * The cost follows the lists, not nTargets: the ids are staged once per call (int32), every wave gathers 1024 entries of its quiz's
+ * list and lists its own best, the existing merges do the rest; per quiz, maxCount records, a count and a mass cross to the host.  A
+ * quiz whose min(maxCount, its list's length) exceeds 256 has the posteriors of its LIST gathered and is selected on the host in the
+ * same order (b), its mass summed in the list's order -- still no copy of all nTargets posteriors.  Which of the two ways a quiz takes
+ * depends on maxCount and its own list alone, which is what keeps (f).
+ * Every shard of a sharded engine holds every quiz's whole posterior: the call works on a shard engine
+ * (PqaEngineFactory_CreateHipEngineSharded) as on a whole engine, and the one-process sharded engine lets its first shard list. */
+PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pListOf,
+                                                     int64_t nLists, const int64_t *pListCounts, const int64_t *pTargets, int64_t maxCount,
+                                                     CiRatedTarget *pDest, int64_t *pCounts, double *pMass);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

@@ -388,6 +388,12 @@ PQACORE_API void *PqaEngine_ListTopQuestionsBatch(void *pvEngine, const int64_t 
                                                   CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListTopQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
 }
+PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pListOf, const int64_t nLists,
+                                                     const int64_t *pListCounts, const int64_t *pTargets, const int64_t maxCount, CiRatedTarget *pDest,
+                                                     int64_t *pCounts, double *pMass) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListTopTargetsAmongBatch(nQuizzes, pQuizzes, pListOf, nLists, pListCounts, pTargets, maxCount, pDest, pCounts, pMass); });
+}
+
 PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
                                                      const int64_t *pQuestions, double *pOut) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalPrioritiesAmongBatch(nQuizzes, pQuizzes, pCounts, pQuestions, pOut); });

@@ -266,6 +266,8 @@ HipEngine::~HipEngine() {
   FreeTrainBulk();
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   if (_hTopBatch) hipHostFree(_hTopBatch);
+  hipFree(_topAmong.dLists); hipFree(_topAmong.dPartial); hipFree(_topAmong.dGather);
+  if (_topAmong.hLines) hipHostFree(_topAmong.hLines);
   if (_hTopQ) hipHostFree(_hTopQ);
   hipFree(_dTopExact);
   hipFree(_dRowStage);

@@ -243,6 +243,9 @@ class HipEngine : public IEngine {
   Error TrainBatch(int64_t n, const int64_t *pCounts, const AQ *pAQs, const int64_t *pTargets, const double *pAmounts) override;
   Error RecordQuizTargetBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, const double *pAmounts) override;
   Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
+  // the best targets within a listed set, and the posterior's total over it (hip_engine_top_among.cpp)
+  Error ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pListOf, int64_t nLists, const int64_t *pListCounts,
+                                 const int64_t *pTargets, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts, double *pMass) override;
   // the best next questions by priority (hip_engine_list.cpp): what EvalPriorities / EvalPrioritiesBatch return, listed on the device
   int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
   Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
@@ -447,6 +450,21 @@ class HipEngine : public IEngine {
   int64_t _hTopBatchRecords = 0;
   Error EnsureTopScratch(int64_t nQuizzes, int64_t want);
   Error EnsureTopScratchRecords(int64_t need);   // (both buffers; the question listing shares them)
+  // ListTopTargetsAmongBatch (hip_engine_top_among.cpp): one call's lists as staged -- offsets[nLists + 1] | ids (int32) on the device --,
+  // the level-0 partial sums, the gathered posteriors of listings beyond 256 records, and the host-coherent result lines
+  // (records | counts | masses).  The buffers grow and never shrink.
+  struct TopAmongStage {
+    std::vector<int64_t> stamp, offsets;
+    std::vector<int32_t> ids;
+    void *dLists = nullptr;
+    size_t listBytes = 0;
+    double *dPartial = nullptr, *dGather = nullptr;
+    size_t partials = 0, gathered = 0;
+    RatedTargetDev *hLines = nullptr;
+    int64_t hRecords = 0;
+  } _topAmong;
+  Error ValidateTopAmongLocked(int64_t n, const int64_t *pQuizzes, const int64_t *pListOf, int64_t nLists, const int64_t *pListCounts, const int64_t *pTargets,
+                               int64_t maxCount, bool haveDest, bool haveCounts);
   // ListTopQuestions (hip_engine_list.cpp): what a listing in flight between its two halves is, and the host-coherent lines a batch's
   // results arrive in -- records, then counts, then one flag per quiz.  Between the halves _mu is free (the sharded engine has every
   // shard's listing in flight before it waits for the first), so the single and the batch listing keep a record each -- the single one

@@ -721,7 +721,7 @@ __device__ __forceinline__ void top_scratch_init(TopScratch *scratch) {
   }
   __syncthreads();
 }
-template <int E>
+template <int E, bool ORDERED>
 __device__ __forceinline__ int64_t top_merge_rounds(const TopOut *cand, int64_t n, int64_t maxCount, TopScratch *scratch) {
   double p[E];
   int t[E];
@@ -732,12 +732,13 @@ __device__ __forceinline__ int64_t top_merge_rounds(const TopOut *cand, int64_t 
     p[e] = c.prob > 0.0 ? c.prob : -1.0;
     t[e] = (int)c.iTarget;
   }
-  return top_rounds<E>(p, t, maxCount, scratch->staged, scratch->sp, scratch->st);
+  return top_rounds<E, ORDERED>(p, t, maxCount, scratch->staged, scratch->sp, scratch->st);
 }
 // workgroup (group, quiz): lists [group * fanIn, ...) of the quiz's nLists lists of maxCount records -> list `group` of the next level
 // (256 threads for up to 4096 candidates, 1024 beyond: a round costs every wave its all-reduces, whatever it holds).  The winners are
 // staged in LDS and leave in one burst: the last level's list goes to host-coherent memory, where a store per round would cost more
-// than the round.
+// than the round.  ORDERED = false: the lists of a listing among a listed set, whose targets follow the caller's list (lane_best).
+template <bool ORDERED>
 __global__ __launch_bounds__(1024) void top_merge_kernel(const TopOut *__restrict__ lists, int64_t nLists, int64_t fanIn, int64_t maxCount,
                                                          TopOut *outLists, int64_t *nOut, uint64_t *flag, uint64_t flagValue) {
   __shared__ TopScratch scratch;
@@ -747,9 +748,9 @@ __global__ __launch_bounds__(1024) void top_merge_kernel(const TopOut *__restric
   const TopOut *cand = lists + (quiz * nLists + first) * maxCount;
   const int64_t n = (limit - first) * maxCount;
   int64_t listed;
-  if (n <= blockDim.x) listed = top_merge_rounds<1>(cand, n, maxCount, &scratch);
-  else if (n <= 4 * (int64_t)blockDim.x) listed = top_merge_rounds<4>(cand, n, maxCount, &scratch);
-  else listed = top_merge_rounds<16>(cand, n, maxCount, &scratch);
+  if (n <= blockDim.x) listed = top_merge_rounds<1, ORDERED>(cand, n, maxCount, &scratch);
+  else if (n <= 4 * (int64_t)blockDim.x) listed = top_merge_rounds<4, ORDERED>(cand, n, maxCount, &scratch);
+  else listed = top_merge_rounds<16, ORDERED>(cand, n, maxCount, &scratch);
   __syncthreads();
   TopOut *list = outLists + (quiz * gridDim.x + group) * maxCount;
   for (int64_t i = threadIdx.x; i < maxCount; i += blockDim.x) list[i] = i < listed ? scratch.staged[i] : TopOut{-1, -1.0};
@@ -764,6 +765,66 @@ __global__ __launch_bounds__(1024) void top_merge_kernel(const TopOut *__restric
     }
   }
 }
+// ---- ListTopTargetsAmongBatch: the best targets within a LISTED set ---------------------------------------------------------------------
+// Level 0 that gathers instead of streaming: grid (chunks of the group's longest list, quiz).  Every wave takes 1024 consecutive entries
+// of its quiz's list, 16 per lane: the ids loaded coalesced (int32, staged by the host: in [0, T), no id twice in a list), prior[id] and
+// the gap word gathered -- sixteen independent loads a lane, issued before the first is used.  The candidates (no gap, probability > 0)
+// go through the wave's rounds with t = the id; nothing ascends along a caller's list, hence the rounds' unordered form.  A wave past
+// the end of its quiz's list holds no candidate and writes only the padding.  partial[quiz][list]: the sum of the wave's candidates --
+// a lane's sixteen in order, then the wave's butterfly: a fixed order, and no atomics.
+struct TopAmongQuizzes { int32_t listOf[kTopBatchQuizzes]; };
+__global__ __launch_bounds__(kTopChunkThreads) void top_among_chunks_kernel(TopBatchPriors priors, TopAmongQuizzes quizzes, const int64_t *__restrict__ offsets,
+                                                                            const int32_t *__restrict__ ids, const uint32_t *__restrict__ tgap,
+                                                                            int64_t maxCount, TopOut *lists, double *__restrict__ partial) {
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int64_t quiz = blockIdx.y, nLists = (int64_t)gridDim.x * (kTopChunkThreads / kWave);
+  const int64_t list = (int64_t)blockIdx.x * (kTopChunkThreads / kWave) + wave;
+  const int64_t first = offsets[quizzes.listOf[quiz]], len = offsets[quizzes.listOf[quiz] + 1] - first;
+  const int64_t iFirst = list * kTopWaveTargets;
+  const double *prior = priors.prior[quiz];
+  double p[16];
+  int t[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const int64_t i = iFirst + lane + e * kWave;
+    t[e] = i < len ? ids[first + i] : -1;
+  }
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const bool ok = t[e] >= 0 && !bit_test(tgap, t[e]);
+    p[e] = ok ? prior[t[e]] : -1.0;
+    if (!(p[e] > 0.0)) p[e] = -1.0;       // gaps and probabilities <= 0 are no candidates (pqa_device.h)
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int e = 0; e < 16; e++) sum += p[e] > 0.0 ? p[e] : 0.0;
+  sum = wave_sum(sum);
+  if (lane == 0) partial[quiz * nLists + list] = sum;
+  TopOut *mine = lists + (quiz * nLists + list) * maxCount;
+  const int64_t listed = top_rounds_wave<16, false>(p, t, maxCount, mine);
+  for (int64_t i = listed + lane; i < maxCount; i += kWave) mine[i] = TopOut{-1, -1.0};   // the rest of the list says "no candidate"
+}
+// mass[quiz] = the quiz's partial sums, list 0 first: one thread per quiz, into the host-coherent result lines.  (A wave beyond the quiz's
+// own list has left +0: the sum does not depend on how long the group's longest list is.)
+__global__ __launch_bounds__(kWave) void top_among_mass_kernel(const double *__restrict__ partial, int64_t nLists, int64_t nQuizzes, double *mass) {
+  const int64_t quiz = (int64_t)blockIdx.x * kWave + threadIdx.x;
+  if (quiz >= nQuizzes) return;
+  double sum = 0.0;
+  for (int64_t l = 0; l < nLists; l++) sum += partial[quiz * nLists + l];
+  mass[quiz] = sum;
+}
+// Lists of more than 256 records a quiz: out[quiz * pitch + i] = the posterior of entry i of the quiz's list, -1 for a gap -- what the
+// host then selects from.  grid (chunks of 256 entries of the group's longest list, quiz).
+__global__ __launch_bounds__(256) void top_among_gather_kernel(TopBatchPriors priors, TopAmongQuizzes quizzes, const int64_t *__restrict__ offsets,
+                                                               const int32_t *__restrict__ ids, const uint32_t *__restrict__ tgap, int64_t pitch,
+                                                               double *__restrict__ out) {
+  const int64_t quiz = blockIdx.y, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t first = offsets[quizzes.listOf[quiz]], len = offsets[quizzes.listOf[quiz] + 1] - first;
+  if (i >= len) return;
+  const int id = ids[first + i];
+  out[quiz * pitch + i] = bit_test(tgap, id) ? -1.0 : priors.prior[quiz][id];
+}
+
 // ---- ListTopQuestions: the best next questions of a quiz, by priority ------------------------------------------------------------------
 // The question-side twin of the listing above, over the priorities a sweep has left on the device: descending priority, ascending
 // question among equal priorities.  A question is a candidate if its bit is clear in the question-gap bitmap AND in the quiz's asked
@@ -1050,6 +1111,7 @@ static int64_t TopBatchLists(int64_t T) { return (T <= 0 ? 1 : (T + kTopChunkTar
 static int64_t TopFanIn(int64_t maxCount) { const int64_t f = kTopMergeCapacity / maxCount; return f < 2 ? 2 : f; }
 // The merge levels over nLists lists of maxCount records per quiz in scratchA: 16384 / maxCount lists per workgroup and level, until one
 // list per quiz is left; that level writes out / nOut (and flag[quiz], where a flag is given).
+template <bool ORDERED = true>
 static hipError_t LaunchTopMerges(int64_t nLists, int64_t nQuizzes, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB,
                                   RatedTargetDev *out, int64_t *nOut, uint64_t *flag, uint64_t flagValue, hipStream_t stream) {
   const int64_t fanIn = TopFanIn(maxCount);
@@ -1058,7 +1120,7 @@ static hipError_t LaunchTopMerges(int64_t nLists, int64_t nQuizzes, int64_t maxC
     const int64_t nGroups = (nLists + fanIn - 1) / fanIn;
     const bool last = nGroups == 1;
     const int threads = (nLists < fanIn ? nLists : fanIn) * maxCount <= 4096 ? 256 : 1024;
-    hipLaunchKernelGGL(top_merge_kernel, dim3((unsigned)nGroups, (unsigned)nQuizzes), dim3(threads), 0, stream, reinterpret_cast<const TopOut *>(src), nLists,
+    hipLaunchKernelGGL(top_merge_kernel<ORDERED>, dim3((unsigned)nGroups, (unsigned)nQuizzes), dim3(threads), 0, stream, reinterpret_cast<const TopOut *>(src), nLists,
                        fanIn, maxCount, reinterpret_cast<TopOut *>(last ? out : dst), last ? nOut : nullptr, last ? flag : nullptr, flagValue);
     if (last) break;
     nLists = nGroups;
@@ -1097,5 +1159,35 @@ hipError_t LaunchTopQuestions(const TopQuestions &a, int64_t maxCount, RatedTarg
                        stream, a.priority, (int64_t)a.Bp, a.slots, a.nQuizzes, a.qgap, a.Q, maxCount, reinterpret_cast<TopOut *>(scratchA));
   }
   return LaunchTopMerges(nLists, a.nQuizzes, maxCount, scratchA, scratchB, out, nOut, flags, flagValue, stream);
+}
+
+// ListTopTargetsAmongBatch: level 0 over the staged lists (offsets | ids on the device, listOf[quiz] the quiz's list), the masses, then
+// the merges.  nLists lists a quiz: a wave per 1024 entries of the group's longest list.
+static int64_t TopAmongLists(int64_t longest) { return TopBatchLists(longest); }
+int64_t TopAmongScratchRecords(int64_t longest, int64_t maxCount) { return TopAmongLists(longest) * maxCount; }
+int64_t TopAmongPartials(int64_t longest) { return TopAmongLists(longest); }
+hipError_t LaunchTopTargetsAmong(const KbView &kb, const TopBatchPriors &priors, const int32_t *listOf, int64_t nQuizzes, const int64_t *offsets,
+                                 const int32_t *ids, int64_t longest, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB,
+                                 double *partial, RatedTargetDev *out, int64_t *nOut, double *mass, hipStream_t stream) {
+  if (nQuizzes <= 0 || nQuizzes > kTopBatchQuizzes || maxCount <= 0 || maxCount > 256 || longest <= 0 || longest > kb.T || offsets == nullptr || ids == nullptr ||
+      listOf == nullptr || partial == nullptr || mass == nullptr)
+    return hipErrorInvalidValue;
+  TopAmongQuizzes qs;
+  for (int64_t i = 0; i < nQuizzes; i++) qs.listOf[i] = listOf[i];
+  const int64_t nLists = TopAmongLists(longest);
+  hipLaunchKernelGGL(top_among_chunks_kernel, dim3((unsigned)(nLists / (kTopChunkThreads / kWave)), (unsigned)nQuizzes), dim3(kTopChunkThreads), 0, stream, priors,
+                     qs, offsets, ids, kb.tgap, maxCount, reinterpret_cast<TopOut *>(scratchA), partial);
+  hipLaunchKernelGGL(top_among_mass_kernel, dim3((unsigned)((nQuizzes + kWave - 1) / kWave)), dim3(kWave), 0, stream, partial, nLists, nQuizzes, mass);
+  return LaunchTopMerges<false>(nLists, nQuizzes, maxCount, scratchA, scratchB, out, nOut, nullptr, 0, stream);
+}
+hipError_t LaunchTopAmongGather(const KbView &kb, const TopBatchPriors &priors, const int32_t *listOf, int64_t nQuizzes, const int64_t *offsets,
+                                const int32_t *ids, int64_t longest, double *out, hipStream_t stream) {
+  if (nQuizzes <= 0 || nQuizzes > kTopBatchQuizzes || longest <= 0 || longest > kb.T || offsets == nullptr || ids == nullptr || listOf == nullptr || out == nullptr)
+    return hipErrorInvalidValue;
+  TopAmongQuizzes qs;
+  for (int64_t i = 0; i < nQuizzes; i++) qs.listOf[i] = listOf[i];
+  hipLaunchKernelGGL(top_among_gather_kernel, dim3((unsigned)((longest + 255) / 256), (unsigned)nQuizzes), dim3(256), 0, stream, priors, qs, offsets, ids, kb.tgap,
+                     longest, out);
+  return hipGetLastError();
 }
 }  // namespace pqa

@@ -643,25 +643,33 @@ constexpr int kTopNone = 0x7FFFFFFF;
 // The lane's own best candidate: the highest probability it holds, the lowest target among equals.  A lane's targets ascend with e
 // wherever its probabilities tie (t = base + tid + e * blockDim over a posterior; position in a sequence of lists that are each
 // ascending among equals and cover ascending target ranges), so the first e that holds the maximum is the one.
-template <int E>
+// ORDERED = false: candidates GATHERED through a list of targets in any order (the listing among a listed set) -- nothing ascends, so
+// the lowest target among the lane's equals is looked for.
+template <int E, bool ORDERED = true>
 __device__ __forceinline__ void lane_best(const double (&p)[E], const int (&t)[E], double &bp, int &bt) {
   bp = p[0];
 #pragma unroll
   for (int e = 1; e < E; e++) bp = max_raw(bp, p[e]);
-  bt = t[E - 1];
+  if (ORDERED) {
+    bt = t[E - 1];
 #pragma unroll
-  for (int e = E - 2; e >= 0; e--) bt = p[e] == bp ? t[e] : bt;
+    for (int e = E - 2; e >= 0; e--) bt = p[e] == bp ? t[e] : bt;
+  } else {
+    bt = kTopNone;
+#pragma unroll
+    for (int e = 0; e < E; e++) bt = p[e] == bp && t[e] < bt ? t[e] : bt;
+  }
 }
 // The rounds over what the threads of a WORKGROUP hold: p[e] > 0 for a candidate (anything else, -1, is never listed), t[e] its target.
 // Every lane carries its own best from round to round; a round is the all-reduce of those, and only the lane that held the winner --
 // one lane of one wave -- looks at its E candidates again.
-template <int E>
+template <int E, bool ORDERED = true>
 __device__ __forceinline__ int64_t top_rounds(double (&p)[E], int (&t)[E], int64_t maxCount, TopOut *out, double (*sp)[16], int (*st)[16]) {
   const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
   int64_t listed = 0;
   double bp;
   int bt;
-  lane_best<E>(p, t, bp, bt);
+  lane_best<E, ORDERED>(p, t, bp, bt);
   for (int64_t r = 0; r < maxCount; r++) {
     const double wm = wave_max(bp);
     const int wt = wave_min(bp == wm ? bt : kTopNone);
@@ -681,20 +689,20 @@ __device__ __forceinline__ int64_t top_rounds(double (&p)[E], int (&t)[E], int64
 #pragma unroll
       for (int e = 0; e < E; e++)
         if (t[e] == gt) p[e] = -1.0;
-      lane_best<E>(p, t, bp, bt);
+      lane_best<E, ORDERED>(p, t, bp, bt);
     }
     listed++;
   }
   return listed;
 }
 // The same for ONE WAVE by itself (no LDS, no barrier): its lanes' candidates only; every lane learns every round's winner.
-template <int E>
+template <int E, bool ORDERED = true>
 __device__ __forceinline__ int64_t top_rounds_wave(double (&p)[E], int (&t)[E], int64_t maxCount, TopOut *out) {
   const int lane = threadIdx.x % kWave;
   int64_t listed = 0;
   double bp;
   int bt;
-  lane_best<E>(p, t, bp, bt);
+  lane_best<E, ORDERED>(p, t, bp, bt);
   for (int64_t r = 0; r < maxCount; r++) {
     const double gm = wave_max(bp);
     if (!(gm > 0.0)) break;
@@ -704,7 +712,7 @@ __device__ __forceinline__ int64_t top_rounds_wave(double (&p)[E], int (&t)[E], 
 #pragma unroll
       for (int e = 0; e < E; e++)
         if (t[e] == gt) p[e] = -1.0;
-      lane_best<E>(p, t, bp, bt);
+      lane_best<E, ORDERED>(p, t, bp, bt);
     }
     listed++;
   }

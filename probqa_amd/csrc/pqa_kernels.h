@@ -691,4 +691,19 @@ int64_t TopQuestionsScratchRecords(int64_t Q, int64_t maxCount);
 hipError_t LaunchTopQuestions(const TopQuestions &a, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB, RatedTargetDev *out,
                               int64_t *nOut, uint64_t *flags, uint64_t flagValue, hipStream_t stream);
 
+// ListTopTargetsAmongBatch: the best maxCount (<= 256) targets of nQuizzes (<= kTopBatchQuizzes) quizzes within LISTED sets -- the lists
+// staged on the device as offsets[nLists + 1] | ids (int32, in [0, T), no id twice in a list), listOf[quiz] (host) the quiz's list,
+// `longest` the longest list of the launch's quizzes.  The order is the batched listing's (probability descending, target ascending)
+// whatever the lists' order.  out[quiz][maxCount], nOut[quiz] and mass[quiz] (the sum of the quiz's candidates, in a fixed order) are
+// device or host-coherent.  The two scratch buffers hold nQuizzes * TopAmongScratchRecords(longest, maxCount) records each, `partial`
+// nQuizzes * TopAmongPartials(longest) doubles.
+int64_t TopAmongScratchRecords(int64_t longest, int64_t maxCount);
+int64_t TopAmongPartials(int64_t longest);
+hipError_t LaunchTopTargetsAmong(const KbView &kb, const TopBatchPriors &priors, const int32_t *listOf, int64_t nQuizzes, const int64_t *offsets,
+                                 const int32_t *ids, int64_t longest, int64_t maxCount, RatedTargetDev *scratchA, RatedTargetDev *scratchB,
+                                 double *partial, RatedTargetDev *out, int64_t *nOut, double *mass, hipStream_t stream);
+// ... and for longer listings: out[quiz * longest + i] = the posterior of entry i of the quiz's list (-1 for a gap), for the host to select from
+hipError_t LaunchTopAmongGather(const KbView &kb, const TopBatchPriors &priors, const int32_t *listOf, int64_t nQuizzes, const int64_t *offsets,
+                                const int32_t *ids, int64_t longest, double *out, hipStream_t stream);
+
 }  // namespace pqa

@@ -225,6 +225,16 @@ class ShardedEngine final : public IEngine {
     if (!e.ok()) return e;
     return _sh[0]->ListTopTargetsBatch(n, pQuizzes, maxCount, pDest, pCounts);
   }
+  Error ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pListOf, int64_t nLists, const int64_t *pListCounts,
+                                 const int64_t *pTargets, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts, double *pMass) override {
+    // the posteriors are replicated: the gathered answers reach the shards, a quiz whose replicas may differ is refused, shard 0 lists
+    Error e = FlushNow();
+    for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) e = FailedQuiz(pQuizzes[i]);
+    if (!e.ok()) return e;
+    e = _sh[0]->ListTopTargetsAmongBatch(n, pQuizzes, pListOf, nLists, pListCounts, pTargets, maxCount, pDest, pCounts, pMass);
+    for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) Touch(pQuizzes[i]);
+    return e;
+  }
   int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
   Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
   Error StartQuizBatch(int64_t n, int64_t *pQuizzes) override {

@@ -175,6 +175,7 @@ HIP_EXPORTS = {
     "PqaEngine_TrainBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64, _pdbl]),
     "PqaEngine_RecordQuizTargetBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaEngine_ListTopTargetsAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64, _pdbl]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1011,6 +1012,35 @@ class PqaEngine:
         arr = (CiRatedTarget * max(n * max_count, 1))()
         _check(_lib.PqaEngine_ListTopTargetsBatch(self.c_engine, n, qs, max_count, arr, counts))
         return [[RatedTarget(arr[i * max_count + j].iTarget, arr[i * max_count + j].prob) for j in range(counts[i])] for i in range(n)]
+
+    def list_top_targets_among_batch(self, quizzes, lists, max_count: int, list_of=None) -> Tuple[List[List[RatedTarget]], List[float]]:
+        """The best targets of several quizzes (a quiz may repeat) WITHIN LISTED SETS of targets, and the posterior's total over each
+        quiz's set: quiz i takes lists[list_of[i]], or lists[i] without list_of.  Probability descending, target id ascending among
+        equal probabilities, whatever a list's order; the probabilities are the posterior's own, nothing is renormalised -- divide by
+        the mass to do so.  The cost follows the lists, not the number of targets."""
+        n = len(quizzes)
+        qs = np.ascontiguousarray(quizzes, dtype=np.int64)
+        lens = np.array([len(x) for x in lists], dtype=np.int64)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in lists]) if len(lists) and lens.sum() else np.zeros(1), dtype=np.int64)
+        lof = None if list_of is None else np.ascontiguousarray(list_of, dtype=np.int64)
+        if lof is not None and len(lof) != n:
+            raise ValueError("one list index per quiz")
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        mass = np.zeros(max(n, 1), dtype=np.float64)
+        arr = (CiRatedTarget * max(n * max_count, 1))()
+        _check(_lib.PqaEngine_ListTopTargetsAmongBatch(self.c_engine, n, qs.ctypes.data_as(_pi64), None if lof is None else lof.ctypes.data_as(_pi64), len(lists),
+                                                       lens.ctypes.data_as(_pi64), ids.ctypes.data_as(_pi64), max_count, arr, counts.ctypes.data_as(_pi64),
+                                                       mass.ctypes.data_as(_pdbl)))
+        rec = np.frombuffer(arr, dtype=np.dtype([("t", np.int64), ("p", np.float64)]))
+        out = []
+        for i in range(n):
+            r = rec[i * max_count:i * max_count + int(counts[i])]
+            out.append([RatedTarget(int(t), float(p)) for t, p in zip(r["t"], r["p"])])
+        return out, [float(m) for m in mass[:n]]
+
+    def list_top_targets_among(self, i_quiz: int, targets, max_count: int) -> Tuple[List[RatedTarget], float]:
+        got, mass = self.list_top_targets_among_batch([i_quiz], [list(targets)], max_count)
+        return got[0], mass[0]
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
