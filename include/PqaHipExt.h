@@ -313,6 +313,49 @@ PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, int64_t nQu
 PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pListOf,
                                                      int64_t nLists, const int64_t *pListCounts, const int64_t *pTargets, int64_t maxCount,
                                                      CiRatedTarget *pDest, int64_t *pCounts, double *pMass);
+/* Targets that answer like a given one: "more like this" behind PqaEngine_ListTopTargets, and the duplicate hunt in front of
+ * PqaEngine_RemoveTargets -- two targets no quiz can ever tell apart are two whose answer distributions agree on every question.
+ * With p_qk(t) = A[q][k][t] / D[q][t]:
+ *      BC_q(s, t) = sum_k sqrt(p_qk(s)) sqrt(p_qk(t))           the Bhattacharyya coefficient, in (0, 1], 1 iff equal
+ *      sim(s, t)  = (sum over q not a gap of BC_q(s, t)) / nValidQuestions
+ * nValidQuestions: the questions of the WHOLE knowledge base that are not gaps; 0 makes every sim 0.  The reference has no such call.
+ *  (a) Arithmetic: fp64 throughout (a Float engine's elements are converted exactly); sqrt(A * (1 / D)), fma accumulation, a fixed
+ *      summation order, no atomics.  Against math.fsum of sqrt(p_qk(s) p_qk(t)) a value is within (Q K + 16) 2^-52 relative.
+ *  (b) Fixed: the value of (s, t) is a function of columns s and t of the cube alone -- not of the other sources of the call, the place
+ *      of s in it, or where t falls.  A column t that is a bit-for-bit copy of column s has sim(s, t) == sim(s, s) in every bit.
+ *  (c) Modes: regular AND maintenance mode (where an operator looks for duplicates); the calls read only the knowledge base and change
+ *      neither it nor any quiz.  They take the engine as PqaEngine_TrainBatch does: a training enqueued earlier is ordered in front.
+ *  (d) Refusals, all decided before anything is launched or written: negative nSources / maxCount (NegativeCount); a NULL buffer that is
+ *      needed (NullArgument); a source id out of [0, nTargets) (IndexOutOfRange, "entry=", "targetId="); more than 256 sources on the
+ *      pack / from-sums pair (IndexOutOfRange, "Batch size is out of range.", as PqaHip_PackAnswerPosteriors).
+ *   PqaEngine_EvalTargetSimilarity        pOut[i * n + t] = sim(pSources[i], t), t == pSources[i] included; n must be nTargets.  0 where t
+ *                                         is a gap; a row of zeros for a source that is a gap.  Any number of sources, ids may repeat.
+ *   PqaEngine_ListSimilarTargetsBatch     source i's candidates are the targets t != pSources[i] that are no gaps and have sim > 0;
+ *                                         pCounts[i] = min(maxCount, candidates) records at pDest + i * maxCount, sim descending, target
+ *                                         id ascending among equal values (PqaEngine_ListTopQuestions' order); _prob carries the bits
+ *                                         PqaEngine_EvalTargetSimilarity returns for the pair.  A gap source lists nothing; maxCount 0 is
+ *                                         no error.  Up to 256 records a source the rows stay on the device and nSources x maxCount
+ *                                         records come back; beyond that the rows are copied and the prefix is taken on the host.
+ *   PqaHip_PackTargetSimilaritySums       a shard's part: stream-ordered, no host synchronisation.  nSources <= 256.  Slot i of the package
+ *                                         at pDst (16-byte aligned, device-visible, pitch PqaHip_PosteriorSlotBytes) receives, for
+ *                                         t < nTargets, the sum over the questions THIS engine holds that are not gaps of
+ *                                         BC_q(pSources[i], t) -- 0 at gap targets, all 0 for a gap source -- and zeros behind.  Every
+ *                                         slot is written whole by every rank; the ranks' packages are SUMMED.  pFlag / flagValue as
+ *                                         PqaHip_PackAnswerRows.
+ *   PqaEngine_ListSimilarTargetsFromSums  divides the summed package by nValidQuestions (IEEE division), drops the source and the gaps
+ *                                         and lists as PqaEngine_ListSimilarTargetsBatch does.  A package in registered host memory is
+ *                                         staged under option "rows_stage".
+ * A whole engine's Eval and List ARE pack -> divide and pack -> list in one sequence, 256 sources at a time.  On an engine made by
+ * PqaEngineFactory_CreateHipEngineSharded they answer NotImplemented and name the pair; the one-process sharded engine (PQA_DEVICES)
+ * answers NotImplemented for all four.  Read-only counters: "similarity_calls", "similarity_sources", and with "time_sweeps"
+ * "similarity_device_ns" (a whole engine's sweeps). */
+PQACORE_API void *PqaEngine_EvalTargetSimilarity(void *pvEngine, int64_t nSources, const int64_t *pSources, double *pOut, int64_t n);
+PQACORE_API void *PqaEngine_ListSimilarTargetsBatch(void *pvEngine, int64_t nSources, const int64_t *pSources, int64_t maxCount,
+                                                    CiRatedTarget *pDest, int64_t *pCounts);
+PQACORE_API void *PqaHip_PackTargetSimilaritySums(void *pvEngine, int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag,
+                                                  uint64_t flagValue);
+PQACORE_API void *PqaEngine_ListSimilarTargetsFromSums(void *pvEngine, int64_t nSources, const int64_t *pSources, const void *pSums,
+                                                       int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

@@ -486,6 +486,23 @@ PQACORE_API void *PqaEngine_RecordAnswerBatchFromPosteriors(void *pvEngine, cons
                                                             const void *pPosteriors) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerBatchFromPosteriors(nQuizzes, pQuizzes, pAnswers, pPosteriors); });
 }
+// ---- targets that answer like a given one (hip_engine_similarity.cpp): a whole engine's matrix and listing, and the pair for shards
+// driven by processes of their own -- every rank packs its questions' sums, every rank lists from the summed package
+PQACORE_API void *PqaEngine_EvalTargetSimilarity(void *pvEngine, const int64_t nSources, const int64_t *pSources, double *pOut, const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalTargetSimilarity(nSources, pSources, pOut, n); });
+}
+PQACORE_API void *PqaEngine_ListSimilarTargetsBatch(void *pvEngine, const int64_t nSources, const int64_t *pSources, const int64_t maxCount,
+                                                    CiRatedTarget *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListSimilarTargetsBatch(nSources, pSources, maxCount, pDest, pCounts); });
+}
+PQACORE_API void *PqaHip_PackTargetSimilaritySums(void *pvEngine, const int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag,
+                                                  const uint64_t flagValue) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackTargetSimilaritySums(nSources, pSources, pDst, pFlag, flagValue); });
+}
+PQACORE_API void *PqaEngine_ListSimilarTargetsFromSums(void *pvEngine, const int64_t nSources, const int64_t *pSources, const void *pSums,
+                                                       const int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListSimilarTargetsFromSums(nSources, pSources, pSums, maxCount, pDest, pCounts); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {

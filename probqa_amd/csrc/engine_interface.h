@@ -147,8 +147,20 @@ class IEngine {
     return NoAmong("NextQuestionSampledAmongBatch");
   }
   virtual Error NextQuestionAmongBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t *) { return NoAmong("NextQuestionAmongBatch"); }
+  // Targets that answer like a given one (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity and its neighbours); the one-process
+  // sharded engine does not offer them.
+  virtual Error EvalTargetSimilarity(int64_t, const int64_t *, double *, int64_t) { return NoSimilarity("EvalTargetSimilarity"); }
+  virtual Error ListSimilarTargetsBatch(int64_t, const int64_t *, int64_t, CiRatedTarget *, int64_t *) { return NoSimilarity("ListSimilarTargetsBatch"); }
+  virtual Error PackTargetSimilaritySums(int64_t, const int64_t *, void *, void *, uint64_t) { return NoSimilarity("PackTargetSimilaritySums"); }
+  virtual Error ListSimilarTargetsFromSums(int64_t, const int64_t *, const void *, int64_t, CiRatedTarget *, int64_t *) {
+    return NoSimilarity("ListSimilarTargetsFromSums");
+  }
 
  private:
+  static Error NoSimilarity(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
+                        "Target similarity is for whole engines and for shards that separate processes drive.");
+  }
   static Error NoAmong(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
                         "The Among calls are for whole engines and for shards that separate processes drive.");

@@ -268,6 +268,9 @@ HipEngine::~HipEngine() {
   if (_hTopBatch) hipHostFree(_hTopBatch);
   hipFree(_topAmong.dLists); hipFree(_topAmong.dPartial); hipFree(_topAmong.dGather);
   if (_topAmong.hLines) hipHostFree(_topAmong.hLines);
+  hipFree(_sim.dRS); hipFree(_sim.dPartial); hipFree(_sim.dSums); hipFree(_sim.dRows);
+  if (_sim.hLines) hipHostFree(_sim.hLines);
+  if (_sim.ev[0]) { hipEventDestroy(_sim.ev[0]); if (_sim.ev[1]) hipEventDestroy(_sim.ev[1]); }
   if (_hTopQ) hipHostFree(_hTopQ);
   hipFree(_dTopExact);
   hipFree(_dRowStage);
@@ -347,6 +350,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"priority_host_bytes", &HipEngine::_priorityHostBytes},            // priorities the batched sweeps delivered to the host
       {"among_calls", &HipEngine::_amongCalls},                           // Among calls that were accepted (hip_engine_among.cpp) ...
       {"among_pairs", &HipEngine::_amongPairs},                           // ... and the (quiz, question) pairs of theirs this engine holds
+      {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_similarity.cpp) ...
+      {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
+      {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
       {"fused_updates", &HipEngine::_fusedUpdates},                       // RecordAnswers whose update ran inside the sweep's launch
       {"top_exact_listings", &HipEngine::_topExactListings},
       {"combined_batches", &HipEngine::_combBatches},                     // sweeps that served more than one NextQuestion call ...

@@ -277,6 +277,14 @@ class HipEngine : public IEngine {
   int64_t PosteriorSlotBytes() const override { std::lock_guard<EngineMutex> lk(_mu); return RoundLdT(_T, 8) * 8; }
   Error PackAnswerPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, void *pDst, void *pFlag, uint64_t flagValue) override;
   Error RecordAnswerBatchFromPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, const void *pPosteriors) override;
+  // ---- targets that answer like a given one (hip_engine_similarity.cpp): sim(s, t) = the mean over the questions that are not gaps
+  // of sum_k sqrt(p_qk(s) p_qk(t)).  Eval / List on a whole engine; on a shard that a process of its own drives, the sums over its
+  // questions as a package at the posterior packages' pitch, summed over the ranks and listed from by every rank
+  Error EvalTargetSimilarity(int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) override;
+  Error ListSimilarTargetsBatch(int64_t nSources, const int64_t *pSources, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
+  Error PackTargetSimilaritySums(int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue) override;
+  Error ListSimilarTargetsFromSums(int64_t nSources, const int64_t *pSources, const void *pSums, int64_t maxCount, CiRatedTarget *pDest,
+                                   int64_t *pCounts) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
   // An answer of a quiz as the sharded engine hands it to EVERY shard: the answered question in global numbering; for the shards
@@ -694,6 +702,27 @@ class HipEngine : public IEngine {
   Error AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, const uint64_t *pRnd,
                     double *pPriorities, CiHipSelection *pSel, int64_t *pPicked);
   uint64_t _amongCalls = 0, _amongPairs = 0;   // read-only "among_calls", "among_pairs"
+  // Target similarity (hip_engine_similarity.cpp): the source columns of a tile, the sweep's partial sums per question chunk, the engine's
+  // own package of a whole engine's calls (also where a host package is staged), the rows the listing reads, its host-coherent result
+  // lines (records | counts) and the host copy of listings beyond 256 records.  The buffers grow and never shrink.
+  struct SimilarityStage {
+    double *dRS = nullptr, *dPartial = nullptr, *dSums = nullptr, *dRows = nullptr;
+    size_t rsBytes = 0, partialBytes = 0, sumsBytes = 0, rowsBytes = 0;
+    RatedTargetDev *hLines = nullptr;
+    int64_t hRecords = 0;
+    std::vector<double> rows;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // option "time_sweeps": around a whole engine's sweeps
+  } _sim;
+  int64_t SimPitch() const { return RoundLdT(_T, 8); }   // doubles of a slot: PosteriorSlotBytes() / 8
+  int64_t ValidQuestionsOfKb() const;                     // questions of the WHOLE knowledge base that are not gaps
+  Error ValidateSimilarityLocked(const char *what, int64_t n, const int64_t *pSources) const;
+  Error EnsureSimilaritySums(int64_t n);
+  Error PackSimilarityLocked(int64_t n, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
+  Error SimilarityRowsLocked(int64_t n, const int64_t *dSources, const double *dSums, bool zeroSelf);
+  Error ListFromSumsLocked(int64_t n, const int64_t *dSources, const double *dSums, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts);
+  void SimilarityTimerStart();
+  void SimilarityTimerStop();
+  uint64_t _simCalls = 0, _simSources = 0, _simDeviceNs = 0;   // read-only "similarity_calls", "similarity_sources", "similarity_device_ns"
   Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
   Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
   // The engine's latest pack of selection parts: what a pick must find unchanged -- the quizzes and their posteriors, the split, this

@@ -706,4 +706,24 @@ hipError_t LaunchTopTargetsAmong(const KbView &kb, const TopBatchPriors &priors,
 hipError_t LaunchTopAmongGather(const KbView &kb, const TopBatchPriors &priors, const int32_t *listOf, int64_t nQuizzes, const int64_t *offsets,
                                 const int32_t *ids, int64_t longest, double *out, hipStream_t stream);
 
+// Target similarity (similarity_kernels.hip): per source s_i and target t the sum over this cube's questions that are not gaps of
+// sum_k sqrt(p_qk(s_i)) sqrt(p_qk(t)), p_qk(t) = A[q][k][t] / D[q][t], in fp64 whatever the cube's element type.
+//   LaunchSimilaritySums: `sources` (device memory, ids in [0, T)) in tiles of kSimTile -- per tile the sources' columns into `rs`
+//     (SimSourceScratchBytes), one streaming pass over the cube into `partial` (SimPartialBytes) and the chunks added in order into
+//     dst[i][pitch]: slot i = T sums, 0 at gap targets, all 0 for a gap source, zeros behind T up to `pitch` doubles (a multiple of
+//     16, T <= pitch <= ldT).  dst may be any device-visible address.  counter / flag / flagValue as LaunchPackAnswerRows, over all
+//     the launches of the call; nSources == 0 with a flag launches that store alone.  A tile of up to kSimTileSmall sources runs the
+//     narrow instantiation: the same arithmetic per (source, target), fewer accumulators.
+//   LaunchSimilarityRows: rows[i][pitch] = sums[i][pitch] / nValidQuestions (0 where that is 0), 0 at gaps and behind T, and with
+//     zeroSelf at t == sources[i] -- the rows the listing takes (LaunchTopTargetsBatch: what is <= 0 is no candidate).
+constexpr int kSimTile = 32, kSimTileSmall = 4;
+int64_t SimQuestionsPerChunk(int64_t Q, int64_t ldT);
+int64_t SimChunks(int64_t Q, int64_t ldT);
+size_t SimSourceScratchBytes(const KbView &kb);
+size_t SimPartialBytes(const KbView &kb);
+hipError_t LaunchSimilaritySums(const KbView &kb, const int64_t *sources, int64_t nSources, double *rs, double *partial, double *dst, int64_t pitch,
+                                unsigned *counter, uint64_t *flag, uint64_t flagValue, hipStream_t stream);
+hipError_t LaunchSimilarityRows(const KbView &kb, const double *sums, int64_t pitch, const int64_t *sources, int64_t nSources, bool zeroSelf, int64_t nValidQuestions,
+                                double *rows, hipStream_t stream);
+
 }  // namespace pqa

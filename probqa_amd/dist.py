@@ -662,6 +662,40 @@ def record_answer(engine, quiz: int, answer: int, rank: int, world: int, group: 
     record_answer_batch(engine, [quiz], [answer], rank, world, group, device)
 
 
+# ---- targets that answer like a given one, over the shards ------------------------------------------------------------------------
+# The similarity of a source and a target is a sum over the questions: every rank packs the sums over ITS questions into a
+# zero-filled package (PqaHip_PackTargetSimilaritySums; every slot is written whole by every rank), ONE all_reduce(SUM) adds them,
+# and every rank divides, drops the source and the gaps and lists from the same summed package -- the same records everywhere.
+# The calls read only the knowledge base: no rank may train or maintain between the pack and the listing inside the call.
+
+
+def list_similar_targets_batch(engine, sources, max_count: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                               device: Optional[torch.device] = None):
+    """PqaEngine_ListSimilarTargetsBatch on the shards of `world` ranks: a collective every rank calls with the same sources and
+    max_count; any number of sources, 256 per exchange.  All or none as record_answer_batch is: a rank whose pack is refused still
+    takes part in the all-reduce, and after the status word every rank raises the first failing rank's text.  Under an NCCL
+    (RCCL) group the package stays on the device, under gloo it goes through the host."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    sources = [int(s) for s in sources]
+    pitch = engine.posterior_slot_bytes() // 8
+    out = []
+    for first in range(0, len(sources), 256):
+        chunk = sources[first:first + 256]
+        pkg = torch.zeros(len(chunk), pitch, dtype=torch.float64, device=ranks.device)
+        error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_target_similarity_sums(chunk, ptr))
+        ranks.settle(error)
+        listed = None
+        try:
+            listed = engine.list_similar_targets_from_sums(chunk, pkg.data_ptr(), max_count)
+        except interop.PqaException as e:
+            error = str(e)
+        ranks.settle(error)
+        out.extend(listed)
+    return out
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

@@ -176,6 +176,10 @@ HIP_EXPORTS = {
     "PqaEngine_RecordQuizTargetBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_ListTopTargetsAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64, _pdbl]),
+    "PqaEngine_EvalTargetSimilarity": (_vp, [_vp, _i64, _pi64, _pdbl, _i64]),
+    "PqaEngine_ListSimilarTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaHip_PackTargetSimilaritySums": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
+    "PqaEngine_ListSimilarTargetsFromSums": (_vp, [_vp, _i64, _pi64, _vp, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1041,6 +1045,57 @@ class PqaEngine:
     def list_top_targets_among(self, i_quiz: int, targets, max_count: int) -> Tuple[List[RatedTarget], float]:
         got, mass = self.list_top_targets_among_batch([i_quiz], [list(targets)], max_count)
         return got[0], mass[0]
+
+    # ---- targets that answer like a given one (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity and its neighbours) ----
+    def eval_target_similarity(self, sources) -> np.ndarray:
+        """sim(sources[i], t) for every target t as an [S, T] array: the mean over the questions that are not gaps of
+        sum_k sqrt(p_qk(s) p_qk(t)) -- 1 for targets no quiz can tell apart, 0 at gaps.  Reads only the knowledge base: regular
+        and maintenance mode."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        t = self.copy_dims().n_targets
+        out = np.zeros((len(src), t), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalTargetSimilarity(self.c_engine, len(src), src.ctypes.data_as(_pi64), _dptr(out), t))
+        return out
+
+    @staticmethod
+    def _similar_records(arr, counts, n: int, max_count: int) -> List[List[RatedTarget]]:
+        rec = np.frombuffer(arr, dtype=np.dtype([("t", np.int64), ("p", np.float64)]))
+        out = []
+        for i in range(n):
+            r = rec[i * max_count:i * max_count + int(counts[i])]
+            out.append([RatedTarget(int(t), float(p)) for t, p in zip(r["t"], r["p"])])
+        return out
+
+    def list_similar_targets_batch(self, sources, max_count: int) -> List[List[RatedTarget]]:
+        """Per source the targets most like it, the source itself and the gaps left out: similarity descending, target id
+        ascending among equal values; the values are eval_target_similarity's bits.  Any number of sources, ids may repeat."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        n = len(src)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        arr = (CiRatedTarget * max(n * max_count, 1))()
+        _check(_lib.PqaEngine_ListSimilarTargetsBatch(self.c_engine, n, src.ctypes.data_as(_pi64), max_count, arr, counts.ctypes.data_as(_pi64)))
+        return self._similar_records(arr, counts, n, max_count)
+
+    def list_similar_targets(self, source: int, max_count: int) -> List[RatedTarget]:
+        return self.list_similar_targets_batch([source], max_count)[0]
+
+    def pack_target_similarity_sums(self, sources, ptr: int, flag_ptr: int = 0, flag_value: int = 0) -> None:
+        """Enqueue (no synchronisation) this engine's part of the similarity of up to 256 sources -- the sums over the questions
+        it holds -- into the package at device-visible 16-byte aligned address `ptr`, slots at posterior_slot_bytes(); the
+        ranks' packages are summed.  `flag_ptr` (an address, 0 = none) receives `flag_value` once the slots are visible."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        _check(_lib.PqaHip_PackTargetSimilaritySums(self.c_engine, len(src), src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None),
+                                                    ctypes.c_void_p(flag_ptr or None), flag_value))
+
+    def list_similar_targets_from_sums(self, sources, ptr: int, max_count: int) -> List[List[RatedTarget]]:
+        """list_similar_targets_batch from the summed package at device-visible address `ptr`."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        n = len(src)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        arr = (CiRatedTarget * max(n * max_count, 1))()
+        _check(_lib.PqaEngine_ListSimilarTargetsFromSums(self.c_engine, n, src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None), max_count, arr,
+                                                         counts.ctypes.data_as(_pi64)))
+        return self._similar_records(arr, counts, n, max_count)
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):

@@ -1,0 +1,295 @@
+"""Target similarity on the GPU (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity, PqaEngine_ListSimilarTargetsBatch;
+similarity_kernels.hip; hip_engine_similarity.cpp).
+
+The model is built from get_kb()'s A and D: ref(s, t) = math.fsum(sqrt(p_qk(s) p_qk(t))) over the questions that are not gaps, divided by
+the number of such questions, p = A / D.  The bar is derived, not measured: every term is positive, device and model terms each carry
+a few ulp, and any summation order of n = Q K terms adds at most (n - 1) 2^-53 relative, hence |gpu - ref| <= (Q K + 16) 2^-52 ref.
+Listings are held to the engine's own Eval rows record for record, bit for bit."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+import cases
+from probqa_amd import interop
+
+pytestmark = pytest.mark.gpu
+
+F32 = dict(prec_type=interop.PrecisionType.FLOAT, prec_exponent=8, prec_mantissa=24)
+AQ = interop.AnsweredQuestion
+
+
+def make_engine(factory, K, Q, T, tgaps=(), qgaps=(), seed=7, trains=5, **kw):
+    eng, err = factory.create_cpu_engine(interop.EngineDefinition(K, Q, T, init_amount=0.1, **kw))
+    assert err is None and eng is not None, err
+    eng.fill_synthetic(8.0, 0.5, seed)
+    eng.set_option("workers", cases.WORKERS)
+    if tgaps:
+        eng.set_target_gaps(list(tgaps))
+    if qgaps:
+        eng.set_question_gaps(list(qgaps))
+    rng = np.random.default_rng(seed)
+    free_q = [q for q in range(Q) if q not in qgaps]
+    free_t = [t for t in range(T) if t not in tgaps]
+    for _ in range(trains):
+        qs = rng.permutation(free_q)[:min(3, len(free_q))]
+        eng.train([AQ(int(q), int(rng.integers(K))) for q in qs], int(rng.choice(free_t)), 1.5)
+    return eng
+
+
+def bar(Q, K):
+    return (Q * K + 16) * 2.0 ** -52
+
+
+def model_rows(A, D, sources, tgaps, qgaps, n_valid=None):
+    """ref[i][t] by the definition: math.fsum over the non-gap questions' terms, / nValidQuestions; 0 at gap targets, a gap source's
+    row all 0.  The terms come from numpy (IEEE division, multiplication and square root, as math.sqrt's)."""
+    Q, K, T = A.shape
+    valid = [q for q in range(Q) if q not in qgaps]
+    n_valid = len(valid) if n_valid is None else n_valid
+    p = A[valid] / D[valid][:, None, :]
+    out = np.zeros((len(sources), T))
+    if n_valid == 0:
+        return out
+    for i, s in enumerate(sources):
+        if s in tgaps:
+            continue
+        terms = np.sqrt(p[:, :, s:s + 1] * p).reshape(-1, T)
+        for t in range(T):
+            if t not in tgaps:
+                out[i, t] = math.fsum(terms[:, t]) / n_valid
+    return out
+
+
+def within_bar(name, got, ref, Q, K):
+    err = np.abs(got - ref)
+    worst = float((err / np.maximum(ref, 1e-300)).max()) if ref.size else 0.0
+    print("%s: worst relative error %.3g, bar %.3g" % (name, worst, bar(Q, K)))
+    assert (err <= bar(Q, K) * ref).all(), (name, worst)
+    assert ((got == 0) == (ref == 0)).all(), name
+
+
+def records(listing):
+    return [(t.i_target, t.prob) for t in listing]
+
+
+def listing_of_row(row, source, max_count):
+    """what the listing must be, from the engine's own Eval row: not the source, value > 0 (gaps are 0), by (-value, id)"""
+    ids = np.array([t for t in range(len(row)) if t != source and row[t] > 0], dtype=np.int64)
+    if len(ids) == 0:
+        return []
+    take = np.lexsort((ids, -row[ids]))[:max_count]
+    return [(int(t), float(row[t])) for t in ids[take]]
+
+
+def valid_top_k(name, got, ref_row, source, tgaps, max_count, Q, K):
+    """A listing made by other arithmetic than the model's: sorted by (-value, id), every value within the bar of the model's, and no
+    unlisted candidate's model value above the last listed value plus the bar."""
+    b = bar(Q, K)
+    cand = [t for t in range(len(ref_row)) if t != source and t not in tgaps and ref_row[t] > 0]
+    assert len(got) == min(max_count, len(cand)), (name, len(got), len(cand))
+    assert got == sorted(got, key=lambda r: (-r[1], r[0])), name
+    assert len({t for t, _ in got}) == len(got) and all(t in cand for t, _ in got), name
+    for t, v in got:
+        assert abs(v - ref_row[t]) <= b * ref_row[t], (name, t, v, ref_row[t])
+    if got and len(got) < len(cand):
+        last = got[-1][1]
+        listed = {t for t, _ in got}
+        over = [t for t in cand if t not in listed and ref_row[t] > last + b * ref_row[t]]
+        assert not over, (name, over[:5])
+
+
+# ---- the matrix against the model, the listings against the matrix ---------------------------------------------------------------------
+SHAPES = {
+    "gaps5x37x101": dict(K=5, Q=37, T=101, tgaps=(3, 17, 100), qgaps=(0, 5, 36)),
+    "ragged3x65x64": dict(K=3, Q=65, T=64),
+    "odd7x130x1025": dict(K=7, Q=130, T=1025),
+    "chunk5x300x4097": dict(K=5, Q=300, T=4097),
+    "float5x37x101": dict(K=5, Q=37, T=101, tgaps=(3, 17, 100), qgaps=(0, 5, 36), f32=True),
+}
+
+
+def sources_of(name, T, tgaps):
+    if T <= 101:   # more than two source tiles, a gap, a repeated id, both ends
+        rng = np.random.default_rng(11)
+        return [0, T - 1, 3, 9, 9] + [int(t) for t in rng.integers(0, T, size=65)]
+    return [0, T - 1, 5, T // 2, T // 2]
+
+
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_matrix_and_listings(factory, name):
+    sh = dict(SHAPES[name])
+    K, Q, T, tgaps, qgaps = sh["K"], sh["Q"], sh["T"], sh.get("tgaps", ()), sh.get("qgaps", ())
+    eng = make_engine(factory, K, Q, T, tgaps, qgaps, **(F32 if sh.get("f32") else {}))
+    A, D, _ = eng.get_kb()
+    sources = sources_of(name, T, tgaps)
+    assert T > 101 or len(sources) == 70
+    calls0, swept0 = eng.get_option("similarity_calls"), eng.get_option("similarity_sources")
+    got = eng.eval_target_similarity(sources)
+    assert eng.get_option("similarity_calls") == calls0 + 1 and eng.get_option("similarity_sources") == swept0 + len(sources)
+    ref = model_rows(A, D, sources, tgaps, qgaps)
+    within_bar(name, got, ref, Q, K)
+    for i, s in enumerate(sources):   # sim(s, s) with it (about 1: exactly as far as D is the sum of A in the cube's number type)
+        if s not in tgaps:
+            assert abs(got[i, s] - ref[i, s]) <= bar(Q, K) * ref[i, s] and abs(got[i, s] - 1.0) < 1e-6, (s, got[i, s], ref[i, s])
+    assert np.array_equal(got[3], got[4])                                   # the repeated id
+    assert eng.eval_target_similarity(sources).tobytes() == got.tobytes()   # the same call, the same bytes
+    # a source alone, and at the other places of a call of 70 (entry 0, 31, 32, 69): the same bytes
+    if T <= 101:
+        s = sources[1]
+        alone = eng.eval_target_similarity([s])
+        assert alone.tobytes() == got[1].tobytes()
+        for at in (0, 31, 32, 69):
+            moved = list(sources)
+            moved[at] = s
+            assert eng.eval_target_similarity(moved)[at].tobytes() == alone.tobytes(), at
+    counts = [0, 1, 10, T + 5] + ([300] if T == 1025 else [])
+    for max_count in counts:
+        listed = eng.list_similar_targets_batch(sources, max_count)
+        assert len(listed) == len(sources)
+        for i, s in enumerate(sources):
+            assert records(listed[i]) == listing_of_row(got[i], s, max_count), (name, max_count, i, s)
+        if max_count == 10:
+            assert records(eng.list_similar_targets(sources[1], 10)) == records(listed[1])
+            assert [records(x) for x in eng.list_similar_targets_batch(sources, 10)] == [records(x) for x in listed]
+    if tgaps:
+        assert not got[2].any() and eng.list_similar_targets(3, 10) == []     # a gap source: zeros, nothing listed
+        assert not got[:, list(tgaps)].any()
+    eng.close()
+
+
+def test_single_target_has_no_candidates(factory):
+    """The smallest knowledge base: (K, Q, T) = (2, 1, 1) is refused by the engine itself (InsufficientEngineDimensions: at least two
+    targets), so the one live target is made at (2, 1, 2) with the other target a gap: its own similarity, and nothing to list."""
+    eng, err = factory.create_cpu_engine(interop.EngineDefinition(2, 1, 1, init_amount=0.1))
+    assert eng is None and "nTargets=1 of 2" in err.to_string(True)
+    eng = make_engine(factory, 2, 1, 2, tgaps=(1,), trains=1)
+    got = eng.eval_target_similarity([0, 0])
+    assert got.shape == (2, 2) and abs(got[0, 0] - 1.0) < 1e-6 and got[0, 0] == got[1, 0] and not got[:, 1].any()
+    assert eng.list_similar_targets_batch([0, 0, 1], 5) == [[], [], []]
+    assert eng.list_similar_targets_batch([], 5) == [] and eng.eval_target_similarity([]).shape == (0, 2)
+    eng.close()
+
+
+def test_all_questions_gaps_gives_zeros(factory):
+    eng = make_engine(factory, 3, 4, 20, trains=0)
+    eng.set_question_gaps([0, 1, 2, 3])
+    assert not eng.eval_target_similarity([0, 5]).any()
+    assert eng.list_similar_targets_batch([0, 5], 3) == [[], []]
+    eng.close()
+
+
+# ---- copies of a column -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("f32", [False, True])
+def test_copied_columns_tie_bit_for_bit(factory, f32):
+    K, Q, T = 5, 37, 101
+    eng = make_engine(factory, K, Q, T, **(F32 if f32 else {}))
+    A, D, B = eng.get_kb()
+    for dst in (40, 77):   # two copies of target 9
+        A[:, :, dst], D[:, dst] = A[:, :, 9], D[:, 9]
+    eng.set_kb(A, D, B)
+    sources = [9, 0, 40, 100, 55]
+    got = eng.eval_target_similarity(sources)
+    assert got[0, 40] == got[0, 9] and got[0, 77] == got[0, 9]                  # the bits of sim(9, 9)
+    assert got[2, 9] == got[2, 40]
+    listed = eng.list_similar_targets_batch(sources, 4)
+    assert records(listed[0])[:2] == [(40, got[0, 9]), (77, got[0, 9])]          # source 9: its copies first, by ascending id
+    assert records(listed[2])[:2] == [(9, got[2, 40]), (77, got[2, 40])]
+    for i, s in enumerate(sources):   # the copies tie for EVERY source and are listed by ascending id
+        assert got[i, 40] == got[i, 77]
+        full = [t for t, _ in records(eng.list_similar_targets(s, T))]
+        if s not in (40, 77):
+            assert full.index(77) == full.index(40) + 1, s
+    eng.close()
+
+
+# ---- a training changes the row; maintenance mode --------------------------------------------------------------------------------------
+def test_train_then_maintenance(factory):
+    K, Q, T = 5, 37, 101
+    eng = make_engine(factory, K, Q, T)
+    A, D, B = eng.get_kb()
+    A[:, :, 40], D[:, 40] = A[:, :, 9], D[:, 9]
+    eng.set_kb(A, D, B)
+    before = eng.eval_target_similarity([9])
+    first = eng.list_similar_targets(9, 3)
+    assert first[0].i_target == 40
+    eng.train([AQ(1, 2), AQ(7, 0), AQ(20, 4)], 40, 3.0)       # on a listed target: the call behind it sees the new columns
+    after = eng.eval_target_similarity([9])
+    assert after[0, 40] != before[0, 40] and after[0, 40] < after[0, 9]
+    A, D, _ = eng.get_kb()
+    within_bar("after train", after, model_rows(A, D, [9], (), ()), Q, K)
+    assert records(eng.list_similar_targets(9, 10)) == listing_of_row(after[0], 9, 10)
+    eng.start_maintenance(True)
+    in_maintenance = eng.eval_target_similarity([9, 40])
+    assert in_maintenance[0].tobytes() == after[0].tobytes()
+    assert records(eng.list_similar_targets(9, 10)) == listing_of_row(after[0], 9, 10)
+    eng.remove_targets([40])
+    rows = eng.eval_target_similarity([9, 40])
+    assert rows[0, 40] == 0 and not rows[1].any()
+    listed = eng.list_similar_targets_batch([9, 40], T)
+    assert 40 not in [t for t, _ in records(listed[0])] and listed[1] == []
+    assert records(listed[0]) == listing_of_row(rows[0], 9, T)
+    eng.finish_maintenance()
+    assert eng.eval_target_similarity([9])[0].tobytes() == rows[0].tobytes()
+    eng.close()
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_buffers_untouched(factory):
+    K, Q, T = 5, 37, 101
+    eng = make_engine(factory, K, Q, T, trains=0)
+    lib = interop.load_library()
+    p64, pd, prec = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(interop.CiRatedTarget)
+    src = np.array([1, 2, T], dtype=np.int64)
+    ok = np.array([1, 2, 3], dtype=np.int64)
+    out = np.full((3, T), -7.0)
+    rec = np.full(3 * 4 * 2, -7.0)
+    counts = np.full(3, -7, dtype=np.int64)
+    calls0 = eng.get_option("similarity_calls")
+
+    def refused(err, code, *texts):
+        assert err, texts
+        s = interop.PqaError(err).to_string(True)
+        assert s.startswith("[" + code + "]") and all(t in s for t in texts), s
+        assert (out == -7.0).all() and (rec == -7.0).all() and (counts == -7).all()
+
+    e = eng.c_engine
+    A = lambda a: a.ctypes.data_as(p64)
+    R = rec.ctypes.data_as(prec)
+    NEG, NULL, RANGE = "The count is negative", "Expected non-null argument", "Index is out of range"
+    refused(lib.PqaEngine_EvalTargetSimilarity(e, -1, A(ok), out.ctypes.data_as(pd), T), NEG, "count=-1")
+    refused(lib.PqaEngine_EvalTargetSimilarity(e, 3, None, out.ctypes.data_as(pd), T), NULL)
+    refused(lib.PqaEngine_EvalTargetSimilarity(e, 3, A(ok), None, T), NULL)
+    refused(lib.PqaEngine_EvalTargetSimilarity(e, 3, A(ok), out.ctypes.data_as(pd), T - 1), RANGE, "subjIndex=%d" % (T - 1))
+    refused(lib.PqaEngine_EvalTargetSimilarity(e, 3, A(src), out.ctypes.data_as(pd), T), RANGE, "entry=2", "targetId=%d" % T)
+    refused(lib.PqaEngine_ListSimilarTargetsBatch(e, -2, A(ok), 4, R, A(counts)), NEG, "count=-2")
+    refused(lib.PqaEngine_ListSimilarTargetsBatch(e, 3, A(ok), -4, R, A(counts)), NEG, "count=-4")
+    refused(lib.PqaEngine_ListSimilarTargetsBatch(e, 3, A(ok), 4, None, A(counts)), NULL)
+    refused(lib.PqaEngine_ListSimilarTargetsBatch(e, 3, A(ok), 4, R, None), NULL)
+    refused(lib.PqaEngine_ListSimilarTargetsBatch(e, 3, A(np.array([1, -1, 2], dtype=np.int64)), 4, R, A(counts)), RANGE, "entry=1", "targetId=-1")
+    many = np.zeros(257, dtype=np.int64)
+    refused(lib.PqaHip_PackTargetSimilaritySums(e, 257, A(many), ctypes.c_void_p(16), None, 0), RANGE, "Batch size is out of range.")
+    refused(lib.PqaHip_PackTargetSimilaritySums(e, -1, A(ok), ctypes.c_void_p(16), None, 0), NEG)
+    refused(lib.PqaHip_PackTargetSimilaritySums(e, 3, A(ok), None, None, 0), NULL)
+    refused(lib.PqaHip_PackTargetSimilaritySums(e, 3, A(src), ctypes.c_void_p(16), None, 0), RANGE, "entry=2", "targetId=%d" % T)
+    refused(lib.PqaEngine_ListSimilarTargetsFromSums(e, 3, A(ok), None, 4, R, A(counts)), NULL)
+    refused(lib.PqaEngine_ListSimilarTargetsFromSums(e, 3, A(src), ctypes.c_void_p(16), 4, R, A(counts)), RANGE, "entry=2", "targetId=%d" % T)
+    refused(lib.PqaEngine_ListSimilarTargetsFromSums(e, 3, A(ok), ctypes.c_void_p(16), -1, R, A(counts)), NEG)
+    assert eng.get_option("similarity_calls") == calls0                      # nothing was accepted
+    # maxCount 0 lists nothing and is no error, without a destination; the next good call is correct
+    assert not lib.PqaEngine_ListSimilarTargetsBatch(e, 3, A(ok), 0, None, A(counts)) and (counts == 0).all()
+    row = eng.eval_target_similarity([2])[0]
+    assert records(eng.list_similar_targets(2, 6)) == listing_of_row(row, 2, 6)
+    eng.close()
+
+
+def test_one_process_sharded_engine_refuses(factory, monkeypatch):
+    monkeypatch.setenv("PQA_DEVICES", "0,0")        # two shards side by side on the one device
+    eng, err = factory.create_cpu_engine(interop.EngineDefinition(5, 37, 101, init_amount=0.1))
+    assert err is None and eng.get_option("shards") == 2
+    for call in (lambda: eng.eval_target_similarity([1]), lambda: eng.list_similar_targets_batch([1], 3), lambda: eng.pack_target_similarity_sums([1], 16),
+                 lambda: eng.list_similar_targets_from_sums([1], 16, 3)):
+        with pytest.raises(interop.PqaException, match=r"Not implemented.*Target similarity is for whole engines"):
+            call()
+    eng.close()
