@@ -129,7 +129,8 @@ PQACORE_API void *PqaHip_SaveKBShard(void *pvEngine, const char *filePath, uint8
  * "combine_spin" (clients waiting for the engine spin first while they are fewer than the CPUs the process may use; default 1, 0 =
  * they always sleep), "batch_form" (the batched sweep's form: 0 = by the batch's size and the cube's shape [default], 1 = grid.y = quiz,
  * 2 = row-sharing, 3 = (quiz, chunk) lanes), "batch_qb" (questions per block of the row-sharing sweep, 0..4, 0 = default), "rerank"
- * (Float engines' batched argmax: the fp32 sweep's best 8 questions per quiz re-ranked in fp64; default 1).
+ * (Float engines' batched argmax: the fp32 sweep's best 8 questions per quiz re-ranked in fp64, so the pick is the fp64 argmax of those 8
+ * -- the fp64 argmax of all questions whenever that question is among them; default 1).
  * Described with the calls they belong to: "sampled_batch_host", "time_sweeps", "train_chunk_steps", "rows_stage".
  * The whole list -- name, accepted values, default, side effects, PQA_* variable -- is the table of probqa_amd/csrc/engine_options.h.
  * An option named a flag there takes any integer and stores 0 or 1; every other one refuses a value outside its range with

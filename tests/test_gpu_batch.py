@@ -430,10 +430,11 @@ def test_long_rows_many_questions_per_cluster(K, prec, factory):
                          ids=lambda c: c.name)
 def test_float_batched_argmax_is_the_fp64_argmax(case, factory):
     """north_star: "bit-exact for the argmax index".  A Float engine's batched NextQuestion re-ranks the fp32 sweep's 8 best
-    questions per quiz in fp64 (eval_kernels.hip: batch_rerank_kernel), so its pick is the fp64 oracle's argmax on the rounded
-    cube whenever that argmax is decided beyond fp64's own 1e-9 -- not only where the margin exceeds the fp32 tolerance, which is
-    all round 2 could assert.  Without the re-rank (option rerank = 0) the fp32 argmax is allowed to differ; the share of equal
-    picks is printed for both."""
+    questions per quiz in fp64 (eval_kernels.hip: batch_rerank_kernel), so its pick is the fp64 argmax of those 8: the fp64
+    oracle's argmax on the rounded cube whenever that question is among them and decided beyond fp64's own 1e-9 -- not only where
+    the margin exceeds the fp32 tolerance, which is all round 2 could assert.  In these states it always is among them, and mostly
+    the fp32 sweep's first; states where the nomination and the re-rank decide are in tests/test_gpu_float_select.py.  Without the
+    re-rank (option rerank = 0) the fp32 argmax is allowed to differ; the share of equal picks is printed for both."""
     rng = np.random.default_rng(123)
     eng, orc = float_engine(case, factory)
     eng.set_option("batch_min", 1)
