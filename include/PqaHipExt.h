@@ -357,6 +357,70 @@ PQACORE_API void *PqaHip_PackTargetSimilaritySums(void *pvEngine, int64_t nSourc
                                                   uint64_t flagValue);
 PQACORE_API void *PqaEngine_ListSimilarTargetsFromSums(void *pvEngine, int64_t nSources, const int64_t *pSources, const void *pSums,
                                                        int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts);
+/* Questions whose answers a given one predicts: the duplicate hunt in front of PqaEngine_RemoveQuestions, and for a client the
+ * follow-ups the question just asked already implies -- near-duplicates, negations, rephrasings -- to dim, drop or hand to the Among
+ * calls.  Sources and candidates are questions.  With w[t] = vB[t] for a target that is no gap (0 for a gap) and
+ * p_qk(t) = A[q][k][t] * (1 / D[q][t]), for a source s and a question q, neither a gap:
+ *      J[k][k'] = sum over t of (w[t] p_sk(t)) p_qk'(t)                   a K x K table, every term >= 0
+ *      Z = sum J,  r[k] = sum_k' J[k][k'],  c[k'] = sum_k J[k][k']
+ *      I(s, q)  = sum over J[k][k'] > 0 of (J[k][k'] / Z) log2(J[k][k'] Z / (r[k] c[k']))      bits; 0 if Z == 0
+ * Draw a target from the knowledge base's prior and ask both questions: I(s, q) is the mutual information between the two answers --
+ * how much of q's answer the answer to s already tells.  0 for independent questions; unchanged when a question's answers are
+ * relabelled, so a negated question counts as redundant.  The table is normalised by its own total: neither sum vB == 1 nor
+ * D == sum_k A is assumed.  I(s, s) is computed by the same formula.  The reference has no such call.
+ *  (a) Arithmetic: fp64 throughout (a Float engine's elements are converted exactly); u = w * (A * (1 / D)), v = A * (1 / D), fma
+ *      accumulation over the targets in a fixed order, no atomics; Z, r, c in index order, the sum in row-major order with the device's
+ *      fp64 log2.  Against math.fsum per table entry and the formula in double precision a value is within
+ *      (8 + K^2) (T + 16) 2^-52 bits ABSOLUTE (I is a difference of entropies and may be near 0).
+ *  (b) Fixed: I(s, q) is a function of block s, block q, vB, the target gaps and nTargets alone -- not of the other sources of the
+ *      call, the place of s in the call or in its tile, the tile's width, or where q falls in the grid or in a shard.  A question whose
+ *      block is a bit-for-bit copy of the source's has I(s, q) == I(s, s) in every bit; the same call returns the same bits twice; and
+ *      shards return the whole engine's bits (the summation over t does not depend on the split of the question axis).
+ *  (c) Modes: regular AND maintenance mode; the calls read only the knowledge base and change neither it nor any quiz.  They take the
+ *      engine as PqaEngine_TrainBatch does: a training enqueued earlier is ordered in front.
+ *  (d) Refusals, all decided before anything is launched or written: negative nSources / maxCount (NegativeCount); a NULL buffer that is
+ *      needed (NullArgument); a source id out of [0, nQuestions of the WHOLE knowledge base) (IndexOutOfRange, "entry=",
+ *      "questionId="); more than 256 sources on the pack / from-weights calls (IndexOutOfRange, "Batch size is out of range."); a
+ *      wrong n (IndexOutOfRange, as PqaEngine_EvalTargetSimilarity).  Source ids are GLOBAL on every call.
+ *   PqaEngine_EvalQuestionRedundancy             pOut[i * n + q] = I(pSources[i], q), q == pSources[i] included; n must be nQuestions.  0
+ *                                                where q is a gap; a row of zeros for a source that is a gap.  Any number of sources,
+ *                                                ids may repeat.
+ *   PqaEngine_ListRedundantQuestionsBatch        source i's candidates are the questions q != pSources[i] that are no gaps and have
+ *                                                I > 0; pCounts[i] = min(maxCount, candidates) records at pDest + i * maxCount, I
+ *                                                descending, question id ascending among equal values; _priority carries the bits
+ *                                                PqaEngine_EvalQuestionRedundancy returns for the pair.  maxCount 0 is no error.  Up to
+ *                                                256 records a source the rows stay on the device (the listing kernels of
+ *                                                PqaEngine_ListTopQuestions) and nSources x maxCount records come back; beyond that
+ *                                                the rows are copied and the prefix is taken on the host in the same order.
+ *   PqaHip_QuestionWeightSlotBytes               nAnswers * RoundLdT(nTargets) * 8: a function of the dimensions, the same on every rank.
+ *   PqaHip_PackQuestionWeights                   a shard's part: stream-ordered, no host synchronisation.  nSources <= 256.  For every
+ *                                                source THIS engine holds, slot i of the package at pDst (16-byte aligned,
+ *                                                device-visible) receives the K rows u_k[t] = w[t] p_sk(t): nTargets doubles each at
+ *                                                the slot's pitch (RoundLdT(nTargets) doubles a row), 0 at gap targets, all 0 for a
+ *                                                gap source, zeros behind the row.  Slots of sources other ranks hold are NOT touched:
+ *                                                the ranks' zero-filled packages are SUMMED -- one writer per slot, x + 0 == x, so the
+ *                                                bits are the owner's.  pFlag / flagValue as PqaHip_PackAnswerRows; an engine that
+ *                                                holds none of the sources still publishes the flag.
+ *   PqaEngine_EvalQuestionRedundancyFromWeights  the questions this engine holds against the package: n must be the LOCAL question
+ *                                                count, column j is question q_first + j.  nSources <= 256.
+ *   PqaEngine_ListRedundantQuestionsFromWeights  lists the questions this engine holds against the package, GLOBAL ids in the records;
+ *                                                a host merges the ranks' lists (probqa_amd/dist.py: list_redundant_questions_batch).
+ *                                                nSources <= 256.  A package in registered host memory is staged under "rows_stage".
+ * A whole engine's Eval and List ARE pack -> evaluate and pack -> list in one sequence, 256 sources at a time.  On an engine made by
+ * PqaEngineFactory_CreateHipEngineSharded they answer NotImplemented and name the from-weights pair; the one-process sharded engine
+ * (PQA_DEVICES) answers NotImplemented for all of them and -1 for the size call.  Read-only counters: "redundancy_calls",
+ * "redundancy_sources", and with "time_sweeps" "redundancy_device_ns" (a whole engine's pack, sweeps and listing kernels). */
+PQACORE_API void *PqaEngine_EvalQuestionRedundancy(void *pvEngine, int64_t nSources, const int64_t *pSources, double *pOut, int64_t n);
+PQACORE_API void *PqaEngine_ListRedundantQuestionsBatch(void *pvEngine, int64_t nSources, const int64_t *pSources, int64_t maxCount,
+                                                        CiRatedQuestion *pDest, int64_t *pCounts);
+PQACORE_API int64_t PqaHip_QuestionWeightSlotBytes(void *pvEngine);
+PQACORE_API void *PqaHip_PackQuestionWeights(void *pvEngine, int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag,
+                                             uint64_t flagValue);
+PQACORE_API void *PqaEngine_EvalQuestionRedundancyFromWeights(void *pvEngine, int64_t nSources, const int64_t *pSources,
+                                                              const void *pWeights, double *pOut, int64_t n);
+PQACORE_API void *PqaEngine_ListRedundantQuestionsFromWeights(void *pvEngine, int64_t nSources, const int64_t *pSources,
+                                                              const void *pWeights, int64_t maxCount, CiRatedQuestion *pDest,
+                                                              int64_t *pCounts);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

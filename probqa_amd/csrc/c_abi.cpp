@@ -503,6 +503,31 @@ PQACORE_API void *PqaEngine_ListSimilarTargetsFromSums(void *pvEngine, const int
                                                        const int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListSimilarTargetsFromSums(nSources, pSources, pSums, maxCount, pDest, pCounts); });
 }
+// ---- questions whose answers a given one predicts (hip_engine_redundancy.cpp): a whole engine's rows and listing, and the calls for
+// shards driven by processes of their own -- the owners pack their sources' weighted rows, every rank evaluates / lists its own
+// questions from the summed package
+PQACORE_API void *PqaEngine_EvalQuestionRedundancy(void *pvEngine, const int64_t nSources, const int64_t *pSources, double *pOut, const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalQuestionRedundancy(nSources, pSources, pOut, n); });
+}
+PQACORE_API void *PqaEngine_ListRedundantQuestionsBatch(void *pvEngine, const int64_t nSources, const int64_t *pSources, const int64_t maxCount,
+                                                        CiRatedQuestion *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListRedundantQuestionsBatch(nSources, pSources, maxCount, pDest, pCounts); });
+}
+PQACORE_API int64_t PqaHip_QuestionWeightSlotBytes(void *pvEngine) {
+  return LoggedOf<int64_t>(pvEngine, -1, [&](IEngine &e) { return e.QuestionWeightSlotBytes(); });
+}
+PQACORE_API void *PqaHip_PackQuestionWeights(void *pvEngine, const int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag,
+                                             const uint64_t flagValue) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackQuestionWeights(nSources, pSources, pDst, pFlag, flagValue); });
+}
+PQACORE_API void *PqaEngine_EvalQuestionRedundancyFromWeights(void *pvEngine, const int64_t nSources, const int64_t *pSources, const void *pWeights,
+                                                              double *pOut, const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalQuestionRedundancyFromWeights(nSources, pSources, pWeights, pOut, n); });
+}
+PQACORE_API void *PqaEngine_ListRedundantQuestionsFromWeights(void *pvEngine, const int64_t nSources, const int64_t *pSources, const void *pWeights,
+                                                              const int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListRedundantQuestionsFromWeights(nSources, pSources, pWeights, maxCount, pDest, pCounts); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {

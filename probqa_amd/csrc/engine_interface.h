@@ -155,8 +155,24 @@ class IEngine {
   virtual Error ListSimilarTargetsFromSums(int64_t, const int64_t *, const void *, int64_t, CiRatedTarget *, int64_t *) {
     return NoSimilarity("ListSimilarTargetsFromSums");
   }
+  // Questions whose answers a given one predicts (include/PqaHipExt.h: PqaEngine_EvalQuestionRedundancy and its neighbours); the
+  // one-process sharded engine does not offer them.
+  virtual Error EvalQuestionRedundancy(int64_t, const int64_t *, double *, int64_t) { return NoRedundancy("EvalQuestionRedundancy"); }
+  virtual Error ListRedundantQuestionsBatch(int64_t, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) { return NoRedundancy("ListRedundantQuestionsBatch"); }
+  virtual int64_t QuestionWeightSlotBytes() const { return -1; }
+  virtual Error PackQuestionWeights(int64_t, const int64_t *, void *, void *, uint64_t) { return NoRedundancy("PackQuestionWeights"); }
+  virtual Error EvalQuestionRedundancyFromWeights(int64_t, const int64_t *, const void *, double *, int64_t) {
+    return NoRedundancy("EvalQuestionRedundancyFromWeights");
+  }
+  virtual Error ListRedundantQuestionsFromWeights(int64_t, const int64_t *, const void *, int64_t, CiRatedQuestion *, int64_t *) {
+    return NoRedundancy("ListRedundantQuestionsFromWeights");
+  }
 
  private:
+  static Error NoRedundancy(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
+                        "Question redundancy is for whole engines and for shards that separate processes drive.");
+  }
   static Error NoSimilarity(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
                         "Target similarity is for whole engines and for shards that separate processes drive.");

@@ -271,6 +271,9 @@ HipEngine::~HipEngine() {
   hipFree(_sim.dRS); hipFree(_sim.dPartial); hipFree(_sim.dSums); hipFree(_sim.dRows);
   if (_sim.hLines) hipHostFree(_sim.hLines);
   if (_sim.ev[0]) { hipEventDestroy(_sim.ev[0]); if (_sim.ev[1]) hipEventDestroy(_sim.ev[1]); }
+  hipFree(_red.dWeights); hipFree(_red.dRows); hipFree(_red.dTables); hipFree(_red.dSlots);
+  if (_red.hLines) hipHostFree(_red.hLines);
+  if (_red.ev[0]) { hipEventDestroy(_red.ev[0]); if (_red.ev[1]) hipEventDestroy(_red.ev[1]); }
   if (_hTopQ) hipHostFree(_hTopQ);
   hipFree(_dTopExact);
   hipFree(_dRowStage);
@@ -353,6 +356,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_similarity.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
+      {"redundancy_calls", &HipEngine::_redCalls},                        // question redundancy calls that were accepted (hip_engine_redundancy.cpp) ...
+      {"redundancy_sources", &HipEngine::_redSources},                    // ... the sources swept for ...
+      {"redundancy_device_ns", &HipEngine::_redDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
       {"fused_updates", &HipEngine::_fusedUpdates},                       // RecordAnswers whose update ran inside the sweep's launch
       {"top_exact_listings", &HipEngine::_topExactListings},
       {"combined_batches", &HipEngine::_combBatches},                     // sweeps that served more than one NextQuestion call ...

@@ -285,6 +285,17 @@ class HipEngine : public IEngine {
   Error PackTargetSimilaritySums(int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue) override;
   Error ListSimilarTargetsFromSums(int64_t nSources, const int64_t *pSources, const void *pSums, int64_t maxCount, CiRatedTarget *pDest,
                                    int64_t *pCounts) override;
+  // ---- questions whose answers a given one predicts (hip_engine_redundancy.cpp): I(s, q), the mutual information in bits between the
+  // answers to questions s and q for a target drawn from vB.  Eval / List on a whole engine; on a shard that a process of its own
+  // drives, the sources' weighted rows as a package (the owner of a source writes its slot, the ranks' packages are summed) and the
+  // evaluation / listing of the shard's own questions from it
+  Error EvalQuestionRedundancy(int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) override;
+  Error ListRedundantQuestionsBatch(int64_t nSources, const int64_t *pSources, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
+  int64_t QuestionWeightSlotBytes() const override { std::lock_guard<EngineMutex> lk(_mu); return _K * RoundLdT(_T, 8) * 8; }
+  Error PackQuestionWeights(int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue) override;
+  Error EvalQuestionRedundancyFromWeights(int64_t nSources, const int64_t *pSources, const void *pWeights, double *pOut, int64_t n) override;
+  Error ListRedundantQuestionsFromWeights(int64_t nSources, const int64_t *pSources, const void *pWeights, int64_t maxCount, CiRatedQuestion *pDest,
+                                          int64_t *pCounts) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
   // An answer of a quiz as the sharded engine hands it to EVERY shard: the answered question in global numbering; for the shards
@@ -723,6 +734,30 @@ class HipEngine : public IEngine {
   void SimilarityTimerStart();
   void SimilarityTimerStop();
   uint64_t _simCalls = 0, _simSources = 0, _simDeviceNs = 0;   // read-only "similarity_calls", "similarity_sources", "similarity_device_ns"
+  // Question redundancy (hip_engine_redundancy.cpp): the engine's own package of a whole engine's calls (also where a host package is
+  // staged), the rows the listing reads and the slots that show them to it, the generic sweep's tables, the listing's host-coherent
+  // result lines (records | counts) and the host copy of listings beyond 256 records.  The buffers grow and never shrink.
+  struct RedundancyStage {
+    double *dWeights = nullptr, *dRows = nullptr, *dTables = nullptr;
+    QuizSlot *dSlots = nullptr;
+    size_t weightsBytes = 0, rowsBytes = 0, tablesBytes = 0;
+    RatedTargetDev *hLines = nullptr;
+    int64_t hRecords = 0;
+    std::vector<double> rows;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // option "time_sweeps": around a whole engine's sweeps
+  } _red;
+  int64_t RedPitch() const { return RoundLdT(_T, 8); }                     // doubles of a row of a slot
+  int64_t RedRowPitch() const { return (_Q + 15) & ~(int64_t)15; }         // doubles of a row of results
+  Error RedundancyArgs(int64_t nSources, int64_t maxCount, bool limited) const;
+  Error ValidateRedundancyLocked(const char *what, int64_t n, const int64_t *pSources) const;
+  Error EnsureRedundancyWeights(int64_t n);
+  Error StageRedundancyLocked(int64_t n, const int64_t *pSources, const void *pWeights, const double **dWeights);
+  Error PackRedundancyLocked(int64_t n, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
+  Error RedundancyRowsLocked(int64_t n, const int64_t *dSources, const double *dWeights, bool zeroSelf);
+  Error ListFromWeightsLocked(int64_t n, const int64_t *dSources, const double *dWeights, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts);
+  void RedundancyTimerStart();
+  void RedundancyTimerStop();
+  uint64_t _redCalls = 0, _redSources = 0, _redDeviceNs = 0;   // read-only "redundancy_calls", "redundancy_sources", "redundancy_device_ns"
   Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
   Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
   // The engine's latest pack of selection parts: what a pick must find unchanged -- the quizzes and their posteriors, the split, this

@@ -726,4 +726,25 @@ hipError_t LaunchSimilaritySums(const KbView &kb, const int64_t *sources, int64_
 hipError_t LaunchSimilarityRows(const KbView &kb, const double *sums, int64_t pitch, const int64_t *sources, int64_t nSources, bool zeroSelf, int64_t nValidQuestions,
                                 double *rows, hipStream_t stream);
 
+// Question redundancy (redundancy_kernels.hip): I(s, q), the mutual information in bits between the answers to a source question s
+// and a question q of this cube for a target drawn from vB, in fp64 whatever the cube's element type.
+//   LaunchQuestionWeights: `sources` (device memory, GLOBAL ids; this cube holds [qFirst, qFirst + Q)) -- slot i of dst = K rows of
+//     `pitch` doubles (a multiple of 16, T <= pitch <= ldT), u_k[t] = vB[t] * (A[s][k][t] * (1 / D[s][t])), 0 at gap targets and
+//     behind T, all 0 for a gap source; the slots of sources this cube does not hold are NOT touched.  dst may be any device-visible
+//     address.  counter / flag / flagValue as LaunchPackAnswerRows; nSources == 0 with a flag launches that store alone.
+//   LaunchRedundancySweep: rows[i][rowPitch], column j = I(sources[i], qFirst + j) from the package at `weights` (16-byte aligned): 0
+//     for a gap question and a source whose rows are zeros, and with zeroSelf where qFirst + j == sources[i] -- the rows the listing
+//     takes (LaunchTopQuestions: what is <= 0 is no candidate).  A tile of RedundancyTileWidth(K) sources per workgroup where the
+//     call has as many, one source a tile for the rest: the value of a pair is the same either way.  Answer counts without an
+//     instantiation (K > 5) need `tables`, RedundancyTableBytes bytes of device scratch.
+//   LaunchRedundancySlots: the listing's view of the rows -- slot i's priority vector is row i.
+constexpr int RedundancyTileWidth(int K) { return K == 2 ? 8 : K <= 4 ? 4 : K == 5 ? 2 : 1; }   // NS K K accumulators <= 64 doubles a lane
+constexpr int64_t kRedGenericWorkgroups = 2048;
+size_t RedundancyTableBytes(const KbView &kb);
+hipError_t LaunchQuestionWeights(const KbView &kb, const int64_t *sources, int64_t nSources, int64_t qFirst, double *dst, int64_t pitch, unsigned *counter,
+                                 uint64_t *flag, uint64_t flagValue, hipStream_t stream);
+hipError_t LaunchRedundancySweep(const KbView &kb, const double *weights, int64_t pitch, const int64_t *sources, int64_t nSources, int64_t qFirst, bool zeroSelf,
+                                 double *rows, int64_t rowPitch, double *tables, hipStream_t stream);
+hipError_t LaunchRedundancySlots(QuizSlot *slots, double *rows, int64_t rowPitch, const uint32_t *qgap, int64_t nSources, hipStream_t stream);
+
 }  // namespace pqa

@@ -696,6 +696,40 @@ def list_similar_targets_batch(engine, sources, max_count: int, rank: int, world
     return out
 
 
+# ---- questions whose answers a given one predicts, over the shards -----------------------------------------------------------------
+# The table of a (source, question) pair contracts over the targets, which every rank holds whole: what a rank lacks is the SOURCE's
+# block.  The owner of a source packs its weighted answer rows into a zero-filled package (PqaHip_PackQuestionWeights: one writer per
+# slot), ONE all_reduce(SUM) hands every rank every source's rows -- x + 0 == x, the owner's bits --, every rank lists its own
+# questions against them, and the ranks' lists are all-gathered and merged as list_top_questions merges.
+
+
+def list_redundant_questions_batch(engine, sources, max_count: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                                   device: Optional[torch.device] = None) -> List[List[Tuple[int, float]]]:
+    """PqaEngine_ListRedundantQuestionsBatch on the shards of `world` ranks: a collective every rank calls with the same sources
+    (GLOBAL ids) and max_count; any number of sources, 256 per exchange.  Every rank returns the same (question, bits) records.  All
+    or none as list_similar_targets_batch is: a rank whose pack is refused still takes part in the all-reduce, and after the status
+    word every rank raises the first failing rank's text."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    sources = [int(s) for s in sources]
+    pitch = engine.question_weight_slot_bytes() // 8
+    out = []
+    for first in range(0, len(sources), 256):
+        chunk = sources[first:first + 256]
+        pkg = torch.zeros(len(chunk), pitch, dtype=torch.float64, device=ranks.device)
+        error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_question_weights(chunk, ptr))
+        ranks.settle(error)
+        listed = None
+        try:
+            listed = engine.list_redundant_questions_from_weights(chunk, pkg.data_ptr(), max_count)
+        except interop.PqaException as e:
+            error = str(e)
+        ranks.settle(error)
+        out.extend(_gather_top(listed, max_count, group, device))
+    return out
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

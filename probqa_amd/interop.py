@@ -180,6 +180,12 @@ HIP_EXPORTS = {
     "PqaEngine_ListSimilarTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaHip_PackTargetSimilaritySums": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
     "PqaEngine_ListSimilarTargetsFromSums": (_vp, [_vp, _i64, _pi64, _vp, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaEngine_EvalQuestionRedundancy": (_vp, [_vp, _i64, _pi64, _pdbl, _i64]),
+    "PqaEngine_ListRedundantQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
+    "PqaHip_QuestionWeightSlotBytes": (_i64, [_vp]),
+    "PqaHip_PackQuestionWeights": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
+    "PqaEngine_EvalQuestionRedundancyFromWeights": (_vp, [_vp, _i64, _pi64, _vp, _pdbl, _i64]),
+    "PqaEngine_ListRedundantQuestionsFromWeights": (_vp, [_vp, _i64, _pi64, _vp, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1096,6 +1102,73 @@ class PqaEngine:
         _check(_lib.PqaEngine_ListSimilarTargetsFromSums(self.c_engine, n, src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None), max_count, arr,
                                                          counts.ctypes.data_as(_pi64)))
         return self._similar_records(arr, counts, n, max_count)
+
+    # ---- questions whose answers a given one predicts (include/PqaHipExt.h: PqaEngine_EvalQuestionRedundancy and its neighbours) ----
+    def eval_question_redundancy(self, sources) -> np.ndarray:
+        """I(sources[i], q) for every question q as an [S, Q] array: the mutual information in bits between the answers to the two
+        questions for a target drawn from the prior -- 0 for independent questions and at gaps, the same for a question and its
+        negation.  Reads only the knowledge base: regular and maintenance mode."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        q = self.copy_dims().n_questions
+        out = np.zeros((len(src), q), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalQuestionRedundancy(self.c_engine, len(src), src.ctypes.data_as(_pi64), _dptr(out), q))
+        return out
+
+    @staticmethod
+    def _redundant_records(arr, counts, n: int, max_count: int) -> List[List[Tuple[int, float]]]:
+        rec = np.frombuffer(arr, dtype=np.dtype([("q", np.int64), ("p", np.float64)]))
+        out = []
+        for i in range(n):
+            r = rec[i * max_count:i * max_count + int(counts[i])]
+            out.append([(int(q), float(p)) for q, p in zip(r["q"], r["p"])])
+        return out
+
+    def list_redundant_questions_batch(self, sources, max_count: int) -> List[List[Tuple[int, float]]]:
+        """Per source the questions whose answers it predicts best as (question, bits), the source itself and the gaps left out: bits
+        descending, question id ascending among equal values; the values are eval_question_redundancy's bits.  Any number of
+        sources, ids may repeat."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        n = len(src)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        arr = (CiRatedQuestion * max(n * max_count, 1))()
+        _check(_lib.PqaEngine_ListRedundantQuestionsBatch(self.c_engine, n, src.ctypes.data_as(_pi64), max_count, arr, counts.ctypes.data_as(_pi64)))
+        return self._redundant_records(arr, counts, n, max_count)
+
+    def list_redundant_questions(self, source: int, max_count: int) -> List[Tuple[int, float]]:
+        return self.list_redundant_questions_batch([source], max_count)[0]
+
+    def question_weight_slot_bytes(self) -> int:
+        """Bytes of a slot of a question-weight package: nAnswers rows of RoundLdT(nTargets) doubles; the same on every rank."""
+        return _lib.PqaHip_QuestionWeightSlotBytes(self.c_engine)
+
+    def pack_question_weights(self, sources, ptr: int, flag_ptr: int = 0, flag_value: int = 0) -> None:
+        """Enqueue (no synchronisation) the weighted answer rows of those of up to 256 sources (GLOBAL ids) that this engine holds
+        into the package at device-visible 16-byte aligned address `ptr`, slots of question_weight_slot_bytes(); the slots of
+        other ranks' sources are not touched, and the ranks' zero-filled packages are summed.  `flag_ptr` (an address, 0 = none)
+        receives `flag_value` once the slots are visible."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        _check(_lib.PqaHip_PackQuestionWeights(self.c_engine, len(src), src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None),
+                                               ctypes.c_void_p(flag_ptr or None), flag_value))
+
+    def eval_question_redundancy_from_weights(self, sources, ptr: int, n_local_questions: Optional[int] = None) -> np.ndarray:
+        """eval_question_redundancy over the questions THIS engine holds from the summed package at device-visible address `ptr`:
+        an [S, local questions] array, column j question q_first + j (a shard: give n_local_questions, as for eval_priorities)."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        q = n_local_questions if n_local_questions is not None else self.copy_dims().n_questions
+        out = np.zeros((len(src), q), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalQuestionRedundancyFromWeights(self.c_engine, len(src), src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None), _dptr(out), q))
+        return out
+
+    def list_redundant_questions_from_weights(self, sources, ptr: int, max_count: int) -> List[List[Tuple[int, float]]]:
+        """list_redundant_questions_batch over the questions THIS engine holds from the summed package at device-visible address
+        `ptr`; GLOBAL ids.  The ranks' lists are merged by dist.merge_top_questions."""
+        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        n = len(src)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        arr = (CiRatedQuestion * max(n * max_count, 1))()
+        _check(_lib.PqaEngine_ListRedundantQuestionsFromWeights(self.c_engine, n, src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None), max_count, arr,
+                                                                counts.ctypes.data_as(_pi64)))
+        return self._redundant_records(arr, counts, n, max_count)
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
