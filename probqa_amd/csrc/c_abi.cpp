@@ -486,7 +486,7 @@ PQACORE_API void *PqaEngine_RecordAnswerBatchFromPosteriors(void *pvEngine, cons
                                                             const void *pPosteriors) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerBatchFromPosteriors(nQuizzes, pQuizzes, pAnswers, pPosteriors); });
 }
-// ---- targets that answer like a given one (hip_engine_similarity.cpp): a whole engine's matrix and listing, and the pair for shards
+// ---- targets that answer like a given one (hip_engine_sources.cpp): a whole engine's matrix and listing, and the pair for shards
 // driven by processes of their own -- every rank packs its questions' sums, every rank lists from the summed package
 PQACORE_API void *PqaEngine_EvalTargetSimilarity(void *pvEngine, const int64_t nSources, const int64_t *pSources, double *pOut, const int64_t n) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalTargetSimilarity(nSources, pSources, pOut, n); });
@@ -503,7 +503,7 @@ PQACORE_API void *PqaEngine_ListSimilarTargetsFromSums(void *pvEngine, const int
                                                        const int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListSimilarTargetsFromSums(nSources, pSources, pSums, maxCount, pDest, pCounts); });
 }
-// ---- questions whose answers a given one predicts (hip_engine_redundancy.cpp): a whole engine's rows and listing, and the calls for
+// ---- questions whose answers a given one predicts (hip_engine_sources.cpp): a whole engine's rows and listing, and the calls for
 // shards driven by processes of their own -- the owners pack their sources' weighted rows, every rank evaluates / lists its own
 // questions from the summed package
 PQACORE_API void *PqaEngine_EvalQuestionRedundancy(void *pvEngine, const int64_t nSources, const int64_t *pSources, double *pOut, const int64_t n) {
@@ -880,6 +880,22 @@ static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_
     pOut[0] = (int64_t)best.size();
     for (size_t k = 0; k < best.size(); k++) { std::memcpy(&pOut[1 + 2 * k], &best[k].priority, 8); pOut[2 + 2 * k] = best[k].index; }
     return 1 + 2 * (int64_t)best.size();
+  }
+  if (w == "rated_prefix") {   // {want, id base, n, then n x {value bits, eligible (0 / 1)}} -> {count, then the listed ids}: entry i has id base + i
+    if (nIn < 3 || pIn[0] < 0 || pIn[2] < 0 || nIn != 3 + 2 * pIn[2]) return -1;
+    const int64_t n = pIn[2];
+    std::vector<double> v((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+      if (pIn[4 + 2 * i] != 0 && pIn[4 + 2 * i] != 1) return -1;
+      std::memcpy(&v[(size_t)i], &pIn[3 + 2 * i], 8);
+    }
+    std::vector<pqa::RatedIndex> recs((size_t)std::min(pIn[0], n));
+    std::vector<int64_t> idx;
+    const int64_t c = pqa::RatedPrefix(v.data(), n, pIn[0], [&](int64_t i) { return pIn[4 + 2 * i] == 1; }, [&](int64_t i) { return pIn[1] + i; }, recs.data(), idx);
+    if (1 + c > nOut) return -1;
+    pOut[0] = c;
+    for (int64_t k = 0; k < c; k++) pOut[1 + k] = recs[(size_t)k].index;
+    return 1 + c;
   }
   if (w == "better_pick") {
     if (nIn % 2 != 0 || nOut < 2) return -1;

@@ -241,6 +241,50 @@ void HipEngine::ApplyEnvironment() {
   if (SeedFromEnvironment(x, true)) _rng.Seed((uint64_t)x);
 }
 
+// ---- the buffers every listing family shares (hip_engine.h) -----------------------------------------------------------------------
+hipError_t HipEngine::GrowDeviceBytes(void **p, size_t &have, size_t need) {
+  if (need <= have) return hipSuccess;
+  hipError_t e = hipStreamSynchronize(_stream);
+  if (e != hipSuccess) return e;
+  hipFree(*p);
+  *p = nullptr;
+  have = 0;
+  e = hipMalloc(p, need);
+  if (e == hipSuccess) have = need;
+  return e;
+}
+
+hipError_t ResultLines::Ensure(hipStream_t stream, int64_t needRecords, size_t tailBytesPerEntry, int64_t nEntries, unsigned flags) {
+  if (needRecords <= capacity) return hipSuccess;
+  hipError_t e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return e;
+  Free();
+  const size_t bytes = (size_t)needRecords * sizeof(RatedTargetDev) + (size_t)nEntries * (sizeof(int64_t) + tailBytesPerEntry);
+  e = hipHostMalloc((void **)&records, bytes, flags);
+  if (e != hipSuccess) { records = nullptr; return e; }
+  std::memset(records, 0, bytes);
+  capacity = needRecords;
+  entries = nEntries;
+  return hipSuccess;
+}
+void ResultLines::Free() {
+  if (records) hipHostFree(records);
+  records = nullptr;
+  capacity = 0;
+}
+
+void HipEngine::TimerStart(hipEvent_t (&ev)[2]) {
+  if (!_opt.timeSweeps) return;
+  if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) { (void)hipGetLastError(); return; }
+  if (hipEventRecord(ev[0], _stream) != hipSuccess) (void)hipGetLastError();
+}
+void HipEngine::TimerStop(hipEvent_t (&ev)[2], uint64_t &ns) {
+  if (!_opt.timeSweeps || !ev[1]) return;
+  float ms = 0;
+  if (hipEventRecord(ev[1], _stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ns += (uint64_t)(ms * 1e6);
+  else (void)hipGetLastError();
+}
+
 HipEngine::~HipEngine() {
   hipSetDevice(_device);
   StopServer();
@@ -265,16 +309,13 @@ HipEngine::~HipEngine() {
   for (QuizPinned *slab : _pinSlabs) hipHostFree(slab);
   FreeTrainBulk();
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
-  if (_hTopBatch) hipHostFree(_hTopBatch);
+  _hTopBatch.Free(); _hTopQ.Free(); _topAmong.lines.Free();
   hipFree(_topAmong.dLists); hipFree(_topAmong.dPartial); hipFree(_topAmong.dGather);
-  if (_topAmong.hLines) hipHostFree(_topAmong.hLines);
-  hipFree(_sim.dRS); hipFree(_sim.dPartial); hipFree(_sim.dSums); hipFree(_sim.dRows);
-  if (_sim.hLines) hipHostFree(_sim.hLines);
-  if (_sim.ev[0]) { hipEventDestroy(_sim.ev[0]); if (_sim.ev[1]) hipEventDestroy(_sim.ev[1]); }
-  hipFree(_red.dWeights); hipFree(_red.dRows); hipFree(_red.dTables); hipFree(_red.dSlots);
-  if (_red.hLines) hipHostFree(_red.hLines);
-  if (_red.ev[0]) { hipEventDestroy(_red.ev[0]); if (_red.ev[1]) hipEventDestroy(_red.ev[1]); }
-  if (_hTopQ) hipHostFree(_hTopQ);
+  for (SourceStage *st : {&_sim, &_red}) {
+    hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
+    st->lines.Free();
+    for (hipEvent_t e : st->ev) if (e) hipEventDestroy(e);
+  }
   hipFree(_dTopExact);
   hipFree(_dRowStage);
   hipFree(_dPartsWords); hipFree(_dPartsRun); hipFree(_dPartsGrand); hipFree(_dPartsPickRun);
@@ -353,10 +394,10 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"priority_host_bytes", &HipEngine::_priorityHostBytes},            // priorities the batched sweeps delivered to the host
       {"among_calls", &HipEngine::_amongCalls},                           // Among calls that were accepted (hip_engine_among.cpp) ...
       {"among_pairs", &HipEngine::_amongPairs},                           // ... and the (quiz, question) pairs of theirs this engine holds
-      {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_similarity.cpp) ...
+      {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
-      {"redundancy_calls", &HipEngine::_redCalls},                        // question redundancy calls that were accepted (hip_engine_redundancy.cpp) ...
+      {"redundancy_calls", &HipEngine::_redCalls},                        // question redundancy calls that were accepted (hip_engine_sources.cpp) ...
       {"redundancy_sources", &HipEngine::_redSources},                    // ... the sources swept for ...
       {"redundancy_device_ns", &HipEngine::_redDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
       {"fused_updates", &HipEngine::_fusedUpdates},                       // RecordAnswers whose update ran inside the sweep's launch

@@ -138,6 +138,17 @@ struct QuizPinned {
   uint64_t pad[6];
 };
 
+// The pinned result lines of a batched listing, records | counts[entries] | tail[entries]: written by the listing kernels, read behind a stream synchronise or polled.
+// They only grow: Ensure synchronises `stream` before a block goes, zero-fills the new one (no listing has operation number 0), and leaves {nullptr, 0} where it fails.
+struct ResultLines {
+  RatedTargetDev *records = nullptr;
+  int64_t capacity = 0, entries = 0;   // the records the block holds, and the counts (and tail entries) behind them
+  hipError_t Ensure(hipStream_t stream, int64_t needRecords, size_t tailBytesPerEntry, int64_t nEntries, unsigned flags);
+  int64_t *Counts() const { return reinterpret_cast<int64_t *>(records + capacity); }
+  template <typename T> T *Tail() const { return reinterpret_cast<T *>(Counts() + entries); }
+  void Free();
+};
+
 struct Quiz {
   time_t lastUsage = 0;                // reference BaseQuiz::OnUsage
   double *dPrior = nullptr;            // ldT doubles, device
@@ -277,18 +288,14 @@ class HipEngine : public IEngine {
   int64_t PosteriorSlotBytes() const override { std::lock_guard<EngineMutex> lk(_mu); return RoundLdT(_T, 8) * 8; }
   Error PackAnswerPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, void *pDst, void *pFlag, uint64_t flagValue) override;
   Error RecordAnswerBatchFromPosteriors(int64_t n, const int64_t *pQuizzes, const int64_t *pAnswers, const void *pPosteriors) override;
-  // ---- targets that answer like a given one (hip_engine_similarity.cpp): sim(s, t) = the mean over the questions that are not gaps
-  // of sum_k sqrt(p_qk(s) p_qk(t)).  Eval / List on a whole engine; on a shard that a process of its own drives, the sums over its
-  // questions as a package at the posterior packages' pitch, summed over the ranks and listed from by every rank
+  // ---- the source queries (hip_engine_sources.cpp): targets that answer like a given one (sim(s, t)) and questions whose answers a
+  // given one predicts (I(s, q)).  Eval / List on a whole engine; on a shard that a process of its own drives, its part of a package
+  // that the ranks sum -- similarity: the sums over its questions; redundancy: its sources' weighted rows -- and Eval / List from the sum
   Error EvalTargetSimilarity(int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) override;
   Error ListSimilarTargetsBatch(int64_t nSources, const int64_t *pSources, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override;
   Error PackTargetSimilaritySums(int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue) override;
   Error ListSimilarTargetsFromSums(int64_t nSources, const int64_t *pSources, const void *pSums, int64_t maxCount, CiRatedTarget *pDest,
                                    int64_t *pCounts) override;
-  // ---- questions whose answers a given one predicts (hip_engine_redundancy.cpp): I(s, q), the mutual information in bits between the
-  // answers to questions s and q for a target drawn from vB.  Eval / List on a whole engine; on a shard that a process of its own
-  // drives, the sources' weighted rows as a package (the owner of a source writes its slot, the ranks' packages are summed) and the
-  // evaluation / listing of the shard's own questions from it
   Error EvalQuestionRedundancy(int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) override;
   Error ListRedundantQuestionsBatch(int64_t nSources, const int64_t *pSources, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
   int64_t QuestionWeightSlotBytes() const override { std::lock_guard<EngineMutex> lk(_mu); return _K * RoundLdT(_T, 8) * 8; }
@@ -406,10 +413,18 @@ class HipEngine : public IEngine {
   // a package's slots as row pointers (this engine's own questions: its cube); a package in host memory staged by option "rows_stage"
   Error PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pRows, std::vector<const void *> &rows);
   Error EnsurePackList(int64_t words); // room for `words` 8-byte words in _dAqs and _hPack, the previous list's copy finished, the header zeroed
+  Error SubmitPackList(int64_t words); // the copy of _hPack's first `words` words to _dAqs on the engine's stream, and the event behind it
+  Error SubmitSources(int64_t n, const int64_t *pSources);   // EnsurePackList, the sources into _hPack[2 + i], MarkStreamBusy, SubmitPackList: they stay in _dAqs + 2
   int64_t *_hPack = nullptr;           // PackAnswerRows / PackQuestionBlocks: the pinned source of the pointer list, and the event behind the list's copy
   int64_t _hPackWords = 0;
   hipEvent_t _evPack = nullptr;
-  char *_dRowStage = nullptr;          // ResumeQuizFromRows: where a host package is copied first
+  // A device buffer {*p, have} that only grows: the engine's stream is synchronised before it is freed, a failed allocation leaves {nullptr, 0}
+  hipError_t GrowDeviceBytes(void **p, size_t &have, size_t need);
+  template <typename T> hipError_t GrowDevice(T **p, size_t &have, size_t need) { return GrowDeviceBytes(reinterpret_cast<void **>(p), have, need); }
+  // Option "rows_stage", a package in registered host memory: p, or where its `bytes` were copied to (enqueued) in the growing buffer {*buf, have}, "rows_staged" counted; nullptr: err
+  bool IsStagedHostMemory(const void *p) const;
+  const void *StageHostPackage(const void *p, size_t bytes, void **buf, size_t &have, Error &err);
+  void *_dRowStage = nullptr;          // the row and posterior packages' staging buffer
   size_t _rowStageBytes = 0;
   uint64_t _packCalls = 0, _packBytes = 0, _rowsStaged = 0;   // read-only "pack_calls", "pack_bytes", "rows_staged"
   hipError_t TakeQuizBuffers(Quiz *q);
@@ -462,25 +477,22 @@ class HipEngine : public IEngine {
   int64_t *_dExps = nullptr, *_dAqs = nullptr, *_dStatus = nullptr, *_dNOut = nullptr;
   int64_t _aqCapacity = 0;
   // ListTopTargets over rows of more than 16384 targets / for many quizzes at once (kb_kernels.hip: LaunchTopTargetsBatch): the two
-  // buffers of candidate lists on the device, and the host-coherent lines a batch's results arrive in (records, then the counts)
+  // buffers of candidate lists on the device, and the pinned lines a batch's results arrive in (records, then the counts)
   RatedTargetDev *_dTopScratch[2] = {nullptr, nullptr};
-  int64_t _topScratchRecords = 0;
-  RatedTargetDev *_hTopBatch = nullptr;
-  int64_t _hTopBatchRecords = 0;
+  size_t _topScratchBytes[2] = {0, 0};
+  ResultLines _hTopBatch;
   Error EnsureTopScratch(int64_t nQuizzes, int64_t want);
   Error EnsureTopScratchRecords(int64_t need);   // (both buffers; the question listing shares them)
   // ListTopTargetsAmongBatch (hip_engine_top_among.cpp): one call's lists as staged -- offsets[nLists + 1] | ids (int32) on the device --,
-  // the level-0 partial sums, the gathered posteriors of listings beyond 256 records, and the host-coherent result lines
+  // the level-0 partial sums, the gathered posteriors of listings beyond 256 records, and the pinned result lines
   // (records | counts | masses).  The buffers grow and never shrink.
   struct TopAmongStage {
     std::vector<int64_t> stamp, offsets;
     std::vector<int32_t> ids;
     void *dLists = nullptr;
-    size_t listBytes = 0;
     double *dPartial = nullptr, *dGather = nullptr;
-    size_t partials = 0, gathered = 0;
-    RatedTargetDev *hLines = nullptr;
-    int64_t hRecords = 0;
+    size_t listBytes = 0, partialBytes = 0, gatherBytes = 0;
+    ResultLines lines;
   } _topAmong;
   Error ValidateTopAmongLocked(int64_t n, const int64_t *pQuizzes, const int64_t *pListOf, int64_t nLists, const int64_t *pListCounts, const int64_t *pTargets,
                                int64_t maxCount, bool haveDest, bool haveCounts);
@@ -491,8 +503,7 @@ class HipEngine : public IEngine {
   // quiz: a list of more than 256 questions takes its copy of the priorities and of the asked bits in the first half.
   struct TopQFlight { int64_t n = 0, want = 0; uint64_t op = 0; bool onHost = false; std::vector<double> pri; std::vector<std::vector<uint32_t>> asked; };
   TopQFlight _topQ, _topQBatch;
-  RatedTargetDev *_hTopQ = nullptr;
-  int64_t _hTopQRecords = 0;
+  ResultLines _hTopQ;   // (mapped and coherent: the host polls its tail, one flag per quiz)
   Error EnqueueTopQuestionsLocked(Quiz *q, int64_t maxCount);
   int64_t CollectTopQuestionsLocked(Error &err, CiRatedQuestion *pDest);
   Error EnqueueTopQuestionsBatchLocked(int64_t n, const int64_t *pQuizzes, int64_t maxCount);
@@ -650,6 +661,8 @@ class HipEngine : public IEngine {
   SelectResult *_dSelScratch = nullptr;  // its per-workgroup winner records
   double *_dPriorScratch = nullptr;      // the long-row posterior kernels' subtask sums (KbView::priorScratch)
   hipEvent_t _evSweep[2] = {nullptr, nullptr};   // option "time_sweeps": around every launched fp64 sweep; read-only "last_sweep_ns"
+  void TimerStart(hipEvent_t (&ev)[2]);   // the event-pair timer of that option: events created on first use; Stop waits for its event and adds to `ns`
+  void TimerStop(hipEvent_t (&ev)[2], uint64_t &ns);
   mutable bool _sweepTimed = false;
   // batched selections (NextQuestionArgmaxBatch); allocated on first use
   static constexpr int64_t kMaxBatch = 256, kBatchGrid = 1024;
@@ -713,51 +726,38 @@ class HipEngine : public IEngine {
   Error AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, const uint64_t *pRnd,
                     double *pPriorities, CiHipSelection *pSel, int64_t *pPicked);
   uint64_t _amongCalls = 0, _amongPairs = 0;   // read-only "among_calls", "among_pairs"
-  // Target similarity (hip_engine_similarity.cpp): the source columns of a tile, the sweep's partial sums per question chunk, the engine's
-  // own package of a whole engine's calls (also where a host package is staged), the rows the listing reads, its host-coherent result
-  // lines (records | counts) and the host copy of listings beyond 256 records.  The buffers grow and never shrink.
-  struct SimilarityStage {
-    double *dRS = nullptr, *dPartial = nullptr, *dSums = nullptr, *dRows = nullptr;
-    size_t rsBytes = 0, partialBytes = 0, sumsBytes = 0, rowsBytes = 0;
-    RatedTargetDev *hLines = nullptr;
-    int64_t hRecords = 0;
-    std::vector<double> rows;
-    hipEvent_t ev[2] = {nullptr, nullptr};   // option "time_sweeps": around a whole engine's sweeps
-  } _sim;
-  int64_t SimPitch() const { return RoundLdT(_T, 8); }   // doubles of a slot: PosteriorSlotBytes() / 8
-  int64_t ValidQuestionsOfKb() const;                     // questions of the WHOLE knowledge base that are not gaps
-  Error ValidateSimilarityLocked(const char *what, int64_t n, const int64_t *pSources) const;
-  Error EnsureSimilaritySums(int64_t n);
-  Error PackSimilarityLocked(int64_t n, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
-  Error SimilarityRowsLocked(int64_t n, const int64_t *dSources, const double *dSums, bool zeroSelf);
-  Error ListFromSumsLocked(int64_t n, const int64_t *dSources, const double *dSums, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts);
-  void SimilarityTimerStart();
-  void SimilarityTimerStop();
-  uint64_t _simCalls = 0, _simSources = 0, _simDeviceNs = 0;   // read-only "similarity_calls", "similarity_sources", "similarity_device_ns"
-  // Question redundancy (hip_engine_redundancy.cpp): the engine's own package of a whole engine's calls (also where a host package is
-  // staged), the rows the listing reads and the slots that show them to it, the generic sweep's tables, the listing's host-coherent
-  // result lines (records | counts) and the host copy of listings beyond 256 records.  The buffers grow and never shrink.
-  struct RedundancyStage {
-    double *dWeights = nullptr, *dRows = nullptr, *dTables = nullptr;
+  // ---- The source queries (hip_engine_sources.cpp): two families over one skeleton.  A family's stage: the engine's own package of a
+  // whole engine's calls (also where a host package is staged), the rows, the family's scratch, the slots that show the rows to the
+  // question listing, the listing's pinned lines (records | counts), the host copy of listings beyond 256 records, the events of option
+  // "time_sweeps" around a whole engine's sweeps, the counters.  The buffers grow and never shrink.  The entries (argument checks, lock,
+  // refusals in the one order, chunks of kMaxBatch sources), their steps under the lock, and SourceRowsLocked, which a family does its own way:
+  struct SourceStage {
+    const bool questions;   // sources and results are questions (redundancy); otherwise targets (similarity)
+    uint64_t &calls, &sources, &deviceNs;
+    double *dPackage = nullptr, *dRows = nullptr, *dScratch[2] = {nullptr, nullptr};
+    size_t packageBytes = 0, rowsBytes = 0, scratchBytes[2] = {0, 0};
     QuizSlot *dSlots = nullptr;
-    size_t weightsBytes = 0, rowsBytes = 0, tablesBytes = 0;
-    RatedTargetDev *hLines = nullptr;
-    int64_t hRecords = 0;
+    ResultLines lines;
     std::vector<double> rows;
-    hipEvent_t ev[2] = {nullptr, nullptr};   // option "time_sweeps": around a whole engine's sweeps
-  } _red;
-  int64_t RedPitch() const { return RoundLdT(_T, 8); }                     // doubles of a row of a slot
-  int64_t RedRowPitch() const { return (_Q + 15) & ~(int64_t)15; }         // doubles of a row of results
-  Error RedundancyArgs(int64_t nSources, int64_t maxCount, bool limited) const;
-  Error ValidateRedundancyLocked(const char *what, int64_t n, const int64_t *pSources) const;
-  Error EnsureRedundancyWeights(int64_t n);
-  Error StageRedundancyLocked(int64_t n, const int64_t *pSources, const void *pWeights, const double **dWeights);
-  Error PackRedundancyLocked(int64_t n, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
-  Error RedundancyRowsLocked(int64_t n, const int64_t *dSources, const double *dWeights, bool zeroSelf);
-  Error ListFromWeightsLocked(int64_t n, const int64_t *dSources, const double *dWeights, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts);
-  void RedundancyTimerStart();
-  void RedundancyTimerStop();
-  uint64_t _redCalls = 0, _redSources = 0, _redDeviceNs = 0;   // read-only "redundancy_calls", "redundancy_sources", "redundancy_device_ns"
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  };
+  uint64_t _simCalls = 0, _simSources = 0, _simDeviceNs = 0, _redCalls = 0, _redSources = 0, _redDeviceNs = 0;   // read-only "similarity_calls", "..._sources", "..._device_ns", "redundancy_calls", ...
+  SourceStage _sim{false, _simCalls, _simSources, _simDeviceNs}, _red{true, _redCalls, _redSources, _redDeviceNs};
+  int64_t PackagePitch() const { return RoundLdT(_T, 8); }                 // doubles of a similarity slot (PosteriorSlotBytes() / 8), of a row of a question-weight slot
+  int64_t RedRowPitch() const { return (_Q + 15) & ~(int64_t)15; }         // doubles of a row of redundancy results
+  int64_t SourceRowPitch(const SourceStage &st) const { return st.questions ? RedRowPitch() : PackagePitch(); }
+  int64_t SourceSlotDoubles(const SourceStage &st) const { return (st.questions ? _K : 1) * PackagePitch(); }
+  Error EvalSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, double *pOut, int64_t n);
+  Error ListSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts);
+  Error PackSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
+  Error EvalSourcesFromPackage(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, const void *pPackage, double *pOut, int64_t n);
+  Error ListSourcesFromPackage(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, const void *pPackage, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts);
+  Error AdmitSourcesLocked(const SourceStage &st, const char *call, bool wholeOnly, int64_t rowLength, int64_t n, const int64_t *pSources) const;
+  Error PackSourcesLocked(SourceStage &st, int64_t n, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
+  Error StageSourcesLocked(SourceStage &st, int64_t n, const int64_t *pSources, const void *pPackage, const double **dPackage);
+  Error SourceRowsOutLocked(SourceStage &st, int64_t n, double *pOut, int64_t rowLength);   // (synchronises the stream)
+  Error ListSourcesLocked(SourceStage &st, int64_t n, const double *dPackage, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts);
+  Error SourceRowsLocked(SourceStage &st, int64_t n, const double *dPackage, bool zeroSelf);
   Error NextQuestionSampledBatchLocked(int64_t n, const int64_t *pQuizzes, const uint64_t *pRnd, int64_t *pOut);
   Error LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd, uint64_t tag);
   // The engine's latest pack of selection parts: what a pick must find unchanged -- the quizzes and their posteriors, the split, this
@@ -833,7 +833,6 @@ class HipEngine : public IEngine {
   uint16_t _precExponent = 0;
   std::vector<Quiz *> _quizzes;
   std::vector<int64_t> _quizGaps;
-  friend struct KbIo;
   // The engine's lock.  Taking it also marks the engine's stream as possibly busy: the resident sweep runs on its own
   // stream, so a request is posted only after whatever the other operations enqueued on `_stream` has finished
   // (ServerPost); the selection paths, which leave nothing running, restore the mark they found.

@@ -86,18 +86,8 @@ Error HipEngine::AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes,
   }
   if (nz == 0) return Error();
 
-  auto grow = [&](void **p, size_t &have, size_t need) -> hipError_t {
-    if (need <= have) return hipSuccess;
-    hipStreamSynchronize(_stream);
-    hipFree(*p);
-    *p = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc(p, need);
-    if (e == hipSuccess) have = need;
-    return e;
-  };
   const size_t offBytes = ((size_t)(nz + 1) * sizeof(int64_t) + 15) / 16 * 16, pairBytes = (size_t)nPairs * sizeof(ListedPair);
-  HIP_TRY(grow(&c.dAmong, c.amongBytes, offBytes + pairBytes + (form == AmongForm::Eval ? (size_t)nPairs * sizeof(double) : 0)));
+  HIP_TRY(GrowDevice(&c.dAmong, c.amongBytes, offBytes + pairBytes + (form == AmongForm::Eval ? (size_t)nPairs * sizeof(double) : 0)));
   int64_t *dOffsets = static_cast<int64_t *>(c.dAmong);
   ListedPair *dPairs = reinterpret_cast<ListedPair *>(static_cast<char *>(c.dAmong) + offBytes);
   double *dGather = reinterpret_cast<double *>(static_cast<char *>(c.dAmong) + offBytes + pairBytes);
@@ -115,7 +105,7 @@ Error HipEngine::AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes,
       const std::vector<uint32_t> &asked = _batchQuizzes[(size_t)st.entry[(size_t)j]]->hAsked;
       for (size_t w = 0; w < maskWords && w < asked.size(); w++) st.masks[(size_t)j * maskWords + w] |= asked[w];
     }
-    HIP_TRY(grow((void **)&c.dAmongMask, c.amongMaskBytes, st.masks.size() * sizeof(uint32_t)));
+    HIP_TRY(GrowDevice(&c.dAmongMask, c.amongMaskBytes, st.masks.size() * sizeof(uint32_t)));
     HIP_TRY(hipMemcpyAsync(c.dAmongMask, st.masks.data(), st.masks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, _stream));
     HIP_TRY(hipMemsetAsync(c.dPriority, 0, (size_t)nz * (size_t)_Q * sizeof(double), _stream));
   }
@@ -132,7 +122,7 @@ Error HipEngine::AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes,
   const KbView kb = View();
   const size_t poleBytes = EvalListedPoleBytes(kb, nPairs);
   if (poleBytes > c.poleBytes) {
-    HIP_TRY(grow(&c.dPole, c.poleBytes, poleBytes));
+    HIP_TRY(GrowDevice(&c.dPole, c.poleBytes, poleBytes));
     HIP_TRY(hipMemsetAsync(c.dPole, 0, kBatchPoleClear, _stream));   // (the head, once: every launch leaves it cleared)
   }
   HIP_TRY(LaunchEvalListed(kb, c.dSlots, (int)nz, dPairs, nPairs, poleBytes > 0 ? c.dPole : nullptr, _stream));

@@ -2,7 +2,9 @@
 // registry; hip_engine_select.cpp: the selection paths; hip_engine_combine.cpp: concurrent clients; hip_engine_update.cpp:
 // posterior updates, listings, training; hip_engine_shard.cpp: what a sharded engine asks of its shards; hip_engine_kb.cpp: id maps, .kb files, maintenance;
 // hip_engine_resume.cpp, hip_engine_parts.cpp, hip_engine_record_parts.cpp: row packages, selection parts and posterior packages of
-// shards that separate processes drive).
+// shards that separate processes drive; hip_engine_train.cpp: many trainings in one call; hip_engine_server.cpp: the resident sweep;
+// hip_engine_list.cpp: ListTopQuestions; hip_engine_among.cpp, hip_engine_top_among.cpp: the Among calls and the listing within listed
+// sets; hip_engine_sources.cpp: the source queries, target similarity and question redundancy).
 #pragma once
 
 #include <sched.h>

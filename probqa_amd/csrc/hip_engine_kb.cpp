@@ -974,8 +974,8 @@ Error HipEngine::PackQuestionBlocks(int64_t n, const int64_t *pQuestions, void *
   for (int64_t i = 0, at = 0; i < n; i++)
     if (OwnsQuestion(pQuestions[i])) blocks[at++] = BlockCopy{CubeAt(pQuestions[i] - _qFirst), static_cast<char *>(pDst) + (size_t)i * slotBytes};
   MarkStreamBusy();
-  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
-  HIP_TRY(hipEventRecord(_evPack, _stream));
+  e = SubmitPackList(words);
+  if (!e.ok()) return e;
   HIP_TRY(LaunchCopyQuestionBlocks(reinterpret_cast<const BlockCopy *>(_dAqs + 2), m, _K + 1, _T * _elem / 4, _ldT * _elem, (int64_t)slotBytes / (_K + 1), true,
                                    reinterpret_cast<unsigned *>(_dAqs), static_cast<uint64_t *>(pFlag), flagValue, _stream));
   _packCalls++;

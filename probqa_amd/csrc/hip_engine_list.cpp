@@ -23,13 +23,7 @@ Error TopQuestionsArgs(int64_t maxCount, bool haveDest) {   // (the codes ListTo
 // The host's listing of a priority vector: the eligible questions with a priority > 0 by (priority descending, question ascending).
 int64_t HipEngine::TopQuestionsOfVector(const double *pri, const std::vector<uint32_t> &asked, int64_t want, CiRatedQuestion *pDest) const {
   std::vector<int64_t> idx;
-  idx.reserve((size_t)_Q);
-  for (int64_t i = 0; i < _Q; i++)
-    if (!BitTest(_hQGap, i) && !BitTest(asked, i) && pri[i] > 0.0) idx.push_back(i);
-  const int64_t n = std::min<int64_t>(want, (int64_t)idx.size());
-  std::partial_sort(idx.begin(), idx.begin() + n, idx.end(), [&](int64_t a, int64_t b) { return pri[a] > pri[b] || (pri[a] == pri[b] && a < b); });
-  for (int64_t i = 0; i < n; i++) { pDest[i]._iQuestion = _qFirst + idx[(size_t)i]; pDest[i]._priority = pri[idx[(size_t)i]]; }
-  return n;
+  return RatedPrefix(pri, _Q, want, [&](int64_t i) { return !BitTest(_hQGap, i) && !BitTest(asked, i); }, [&](int64_t i) { return _qFirst + i; }, pDest, idx);
 }
 
 // ---- one quiz: the engine's own priority vector and pinned lines -------------------------------------------------------------------
@@ -125,18 +119,9 @@ Error HipEngine::EnqueueTopQuestionsBatchLocked(int64_t n, const int64_t *pQuizz
   if (!onHost) {
     err = EnsureTopScratchRecords(n * TopQuestionsScratchRecords(_Q, want));
     if (!err.ok()) return err;
-    const int64_t needRecords = n * want;
-    if (needRecords > _hTopQRecords) {
-      HIP_TRY(hipStreamSynchronize(_stream));
-      if (_hTopQ) hipHostFree(_hTopQ);
-      _hTopQ = nullptr; _hTopQRecords = 0;
-      const size_t bytes = (size_t)needRecords * sizeof(RatedTargetDev) + (size_t)kMaxBatch * (sizeof(int64_t) + sizeof(uint64_t));
-      HIP_TRY(hipHostMalloc((void **)&_hTopQ, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-      std::memset(_hTopQ, 0, bytes);   // (no listing has operation number 0)
-      _hTopQRecords = needRecords;
-    }
-    hCounts = reinterpret_cast<int64_t *>(_hTopQ + _hTopQRecords);
-    hFlags = reinterpret_cast<uint64_t *>(hCounts + kMaxBatch);
+    HIP_TRY(_hTopQ.Ensure(_stream, n * want, sizeof(uint64_t), kMaxBatch, hipHostMallocMapped | hipHostMallocCoherent));   // records | counts | flags
+    hCounts = _hTopQ.Counts();
+    hFlags = _hTopQ.Tail<uint64_t>();
   }
   uint64_t tag = 0;
   err = EnqueueBatchLocked(n, pQuizzes, true, &tag);
@@ -147,7 +132,7 @@ Error HipEngine::EnqueueTopQuestionsBatchLocked(int64_t n, const int64_t *pQuizz
     TopQuestions a{};
     a.slots = c.dSlots; a.priority = c.lastBp > 0 ? c.dPriT : nullptr; a.qgap = _dQGap; a.nQuizzes = (int)n; a.Bp = c.lastBp; a.Q = _Q;
     op = ++_opSeq;
-    HIP_TRY(LaunchTopQuestions(a, want, _dTopScratch[0], _dTopScratch[1], _hTopQ, hCounts, hFlags, op, _stream));
+    HIP_TRY(LaunchTopQuestions(a, want, _dTopScratch[0], _dTopScratch[1], _hTopQ.records, hCounts, hFlags, op, _stream));
   }
   if (onHost) for (int64_t i = 0; i < n; i++) _topQBatch.asked.push_back(_batchQuizzes[(size_t)i]->hAsked);
   _topQBatch.n = n; _topQBatch.want = want; _topQBatch.op = op; _topQBatch.onHost = onHost;
@@ -168,15 +153,15 @@ Error HipEngine::CollectTopQuestionsBatchLocked(int64_t n, int64_t stride, CiRat
     for (int64_t i = 0; i < n; i++) pCounts[i] = TopQuestionsOfVector(pri.data() + (size_t)i * (size_t)_Q, f.asked[(size_t)i], f.want, pDest + i * stride);
     return Error();
   }
-  const int64_t *hCounts = reinterpret_cast<const int64_t *>(_hTopQ + _hTopQRecords);
-  volatile uint64_t *hFlags = reinterpret_cast<volatile uint64_t *>(const_cast<int64_t *>(hCounts) + kMaxBatch);
+  const int64_t *hCounts = _hTopQ.Counts();
+  volatile uint64_t *hFlags = _hTopQ.Tail<volatile uint64_t>();
   for (int64_t i = 0; i < n; i++) {   // (the quizzes' last merges retire together: the first wait is the long one)
     Error err = WaitFlag(&hFlags[i], f.op, "ListTopQuestionsBatch");
     if (!err.ok()) return err;
   }
   for (int64_t i = 0; i < n; i++) {
     const int64_t c = std::max<int64_t>(0, std::min<int64_t>(hCounts[i], f.want));
-    const RatedTargetDev *rec = _hTopQ + i * f.want;
+    const RatedTargetDev *rec = _hTopQ.records + i * f.want;
     CiRatedQuestion *dst = pDest + i * stride;
     for (int64_t j = 0; j < c; j++) { dst[j]._iQuestion = _qFirst + rec[j].iTarget; dst[j]._priority = rec[j].prob; }
     pCounts[i] = c;

@@ -44,20 +44,10 @@ Error HipEngine::PackSampledParts(int64_t n, const int64_t *pQuizzes, void *pDst
   } else if (_serverLaunched) {
     StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
   }
-  auto grow = [&](void **p, size_t &have, size_t need) -> hipError_t {
-    if (need <= have) return hipSuccess;
-    hipStreamSynchronize(_stream);
-    hipFree(*p);
-    *p = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc(p, need);
-    if (e == hipSuccess) have = need;
-    return e;
-  };
   if (_dPartsWords == nullptr) HIP_TRY(hipMalloc((void **)&_dPartsWords, (2 + (size_t)kMaxBatch) * sizeof(uint64_t)));
   const bool matrix = c.lastBp > 0;
   const int Bq = matrix ? c.lastBp : (int)((n + 63) / 64 * 64);
-  HIP_TRY(grow((void **)&_dPartsRun, _partsRunBytes, (size_t)_Q * (size_t)std::max(Bq, 64) * sizeof(double)));
+  HIP_TRY(GrowDevice(&_dPartsRun, _partsRunBytes, (size_t)_Q * (size_t)std::max(Bq, 64) * sizeof(double)));
   HIP_TRY(hipMemsetAsync(_dPartsWords, 0, 2 * sizeof(uint64_t), _stream));   // the arrival counter
   const uint64_t seq = ++_opSeq;
   SampledPartsPack a{};
@@ -107,18 +97,8 @@ Error HipEngine::SampledPickFromParts(int64_t n, const int64_t *pQuizzes, const 
   if (!same) return PartsModeErr("the engine's latest pack was made for another batch, or a quiz, the gaps or the split have changed since.");
   hipSetDevice(_device);
   const SampledSplit sp = sampled_split(_qTotal, _parts.nSub);
-  auto grow = [&](double **p, size_t &have, size_t need) -> hipError_t {
-    if (need <= have) return hipSuccess;
-    hipStreamSynchronize(_stream);
-    hipFree(*p);
-    *p = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc((void **)p, need);
-    if (e == hipSuccess) have = need;
-    return e;
-  };
-  HIP_TRY(grow(&_dPartsGrand, _partsGrandBytes, (size_t)n * (size_t)sp.nS * sizeof(double)));
-  HIP_TRY(grow(&_dPartsPickRun, _partsPickRunBytes, (size_t)n * (size_t)sp.L * sizeof(double)));
+  HIP_TRY(GrowDevice(&_dPartsGrand, _partsGrandBytes, (size_t)n * (size_t)sp.nS * sizeof(double)));
+  HIP_TRY(GrowDevice(&_dPartsPickRun, _partsPickRunBytes, (size_t)n * (size_t)sp.L * sizeof(double)));
   std::memcpy(c.h->rnd, pRnd, (size_t)n * sizeof(uint64_t));   // (host-coherent: the kernel reads them there)
   const uint64_t tag = NextLaunchTag();
   SampledPartsPick a{};

@@ -61,14 +61,7 @@ Error HipEngine::PackAnswerPosteriors(int64_t n, const int64_t *pQuizzes, const 
   if (m > 0 || pFlag != nullptr) {
     if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
     const size_t vecBytes = (size_t)_ldT * sizeof(double);
-    if ((size_t)m * vecBytes > _postScratchBytes) {
-      HIP_TRY(hipStreamSynchronize(_stream));   // (nothing in flight reads the buffer about to go)
-      hipFree(_dPostScratch);
-      _dPostScratch = nullptr;
-      _postScratchBytes = 0;
-      HIP_TRY(hipMalloc((void **)&_dPostScratch, (size_t)m * vecBytes));
-      _postScratchBytes = (size_t)m * vecBytes;
-    }
+    HIP_TRY(GrowDevice(&_dPostScratch, _postScratchBytes, (size_t)m * vecBytes));
     // the list: {arrival counter, pad} and then a PosteriorCopy per entry of this engine's questions
     const int64_t words = 2 + 4 * m;
     err = EnsurePackList(words);
@@ -103,8 +96,8 @@ Error HipEngine::PackAnswerPosteriors(int64_t n, const int64_t *pQuizzes, const 
       copies[at++] = PosteriorCopy{vec, static_cast<char *>(pDst) + (size_t)i * slotBytes, nullptr, -1};
     }
     HIP_TRY(launchUpdates());
-    HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
-    HIP_TRY(hipEventRecord(_evPack, _stream));
+    err = SubmitPackList(words);
+    if (!err.ok()) return err;
     HIP_TRY(LaunchPackPosteriors(reinterpret_cast<const PosteriorCopy *>(_dAqs + 2), m, _T, (int64_t)slotBytes, reinterpret_cast<unsigned *>(_dAqs),
                                  static_cast<uint64_t *>(pFlag), flagValue, _stream));
   }
@@ -153,25 +146,8 @@ Error HipEngine::RecordAnswerBatchFromPosteriors(int64_t n, const int64_t *pQuiz
   ServerQuiesce();   // (the posted step reads a posterior this call may be about to write)
   if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
   const size_t slotBytes = (size_t)RoundLdT(_T, 8) * sizeof(double);
-  const char *base = static_cast<const char *>(pPosteriors);
-  if (_opt.rowsStage) {   // a package in host memory (registered, as PqaHip_HostRegister leaves it): copied to the device first
-    hipPointerAttribute_t at;
-    const hipError_t q = hipPointerGetAttributes(&at, pPosteriors);
-    if (q != hipSuccess) (void)hipGetLastError();
-    if (q == hipSuccess && at.type == hipMemoryTypeHost) {
-      const size_t bytes = (size_t)n * slotBytes;
-      if (bytes > _rowStageBytes) {
-        hipFree(_dRowStage);   // (every call that used it has synchronised)
-        _dRowStage = nullptr;
-        _rowStageBytes = 0;
-        HIP_TRY(hipMalloc((void **)&_dRowStage, bytes));
-        _rowStageBytes = bytes;
-      }
-      HIP_TRY(hipMemcpyAsync(_dRowStage, base, bytes, hipMemcpyDefault, _stream));
-      base = _dRowStage;
-      _rowsStaged++;
-    }
-  }
+  const char *base = static_cast<const char *>(StageHostPackage(pPosteriors, (size_t)n * slotBytes, &_dRowStage, _rowStageBytes, err));
+  if (!base) return err;
   const int64_t words = 2 + 4 * n;
   err = EnsurePackList(words);
   if (!err.ok()) return err;
@@ -182,8 +158,8 @@ Error HipEngine::RecordAnswerBatchFromPosteriors(int64_t n, const int64_t *pQuiz
     copies[i] = PosteriorCopy{base + (size_t)i * slotBytes, q->dPrior, local ? q->dAsked : nullptr, local ? q->activeQuestion - _qFirst : -1};
   }
   MarkStreamBusy();
-  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
-  HIP_TRY(hipEventRecord(_evPack, _stream));
+  err = SubmitPackList(words);
+  if (!err.ok()) return err;
   HIP_TRY(LaunchTakePosteriors(reinterpret_cast<const PosteriorCopy *>(_dAqs + 2), n, _T, _stream));
   const time_t now = time(nullptr);
   for (int64_t i = 0; i < n; i++) {

@@ -302,8 +302,8 @@ Error HipEngine::PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFl
                            static_cast<char *>(pDst) + (size_t)i * slotBytes};
   }
   MarkStreamBusy();
-  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
-  HIP_TRY(hipEventRecord(_evPack, _stream));
+  err = SubmitPackList(words);
+  if (!err.ok()) return err;
   HIP_TRY(LaunchPackAnswerRows(reinterpret_cast<const PackPair *>(_dAqs + 2), m, (int64_t)(slotBytes / 2), reinterpret_cast<unsigned *>(_dAqs),
                                static_cast<uint64_t *>(pFlag), flagValue, _stream));
   _packCalls++;
@@ -336,8 +336,39 @@ Error HipEngine::EnsurePackList(int64_t words) {
   return Error();
 }
 
-// The 2 `total` row pointers of a package's slots; a package in host memory (registered, as PqaHip_HostRegister leaves it) is
-// first copied into the engine's own device scratch when option "rows_stage" says so: `base` then points there.
+Error HipEngine::SubmitPackList(int64_t words) {
+  HIP_TRY(hipMemcpyAsync(_dAqs, _hPack, (size_t)words * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
+  HIP_TRY(hipEventRecord(_evPack, _stream));
+  return Error();
+}
+
+Error HipEngine::SubmitSources(int64_t n, const int64_t *pSources) {
+  const int64_t words = 2 + n;   // {arrival counter, pad}, then the sources
+  Error err = EnsurePackList(words);
+  if (!err.ok()) return err;
+  for (int64_t i = 0; i < n; i++) _hPack[2 + i] = pSources[i];
+  MarkStreamBusy();
+  return SubmitPackList(words);
+}
+
+bool HipEngine::IsStagedHostMemory(const void *p) const {
+  if (!_opt.rowsStage) return false;
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return at.type == hipMemoryTypeHost;
+}
+
+const void *HipEngine::StageHostPackage(const void *p, size_t bytes, void **buf, size_t &have, Error &err) {
+  if (!IsStagedHostMemory(p)) return p;
+  hipError_t e = GrowDeviceBytes(buf, have, bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(*buf, p, bytes, hipMemcpyDefault, _stream);
+  if (e != hipSuccess) { err = HipErr(e, "StageHostPackage"); return nullptr; }
+  _rowsStaged++;
+  return *buf;
+}
+
+// The 2 `total` row pointers of a package's slots; a package in host memory is first copied into the engine's own device scratch when
+// option "rows_stage" says so (IsStagedHostMemory): `base` then points there.
 Error HipEngine::PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pRows, std::vector<const void *> &rows) {
   rows.assign(2 * (size_t)total, nullptr);
   bool anyForeign = false;
@@ -347,27 +378,18 @@ Error HipEngine::PackageRowsLocked(int64_t total, const AQ *pAQs, const void *pR
   const char *base = static_cast<const char *>(pRows);
   if (anyForeign && _opt.rowsStage) {
     hipSetDevice(_device);
-    hipPointerAttribute_t at;
-    const hipError_t q = hipPointerGetAttributes(&at, pRows);
-    if (q != hipSuccess) (void)hipGetLastError();
-    if (q == hipSuccess && at.type == hipMemoryTypeHost) {
-      const size_t bytes = (size_t)total * slotBytes;
-      if (bytes > _rowStageBytes) {
-        hipFree(_dRowStage);   // (every call that used it has synchronised)
-        _dRowStage = nullptr;
-        _rowStageBytes = 0;
-        HIP_TRY(hipMalloc((void **)&_dRowStage, bytes));
-        _rowStageBytes = bytes;
-      }
+    if (IsStagedHostMemory(pRows)) {
+      HIP_TRY(GrowDeviceBytes(&_dRowStage, _rowStageBytes, (size_t)total * slotBytes));
+      char *stage = static_cast<char *>(_dRowStage);
       // one copy per run of slots of other engines' questions: this engine's own slots may be unfilled and are not read
       for (int64_t i = 0; i < total;) {
         if (OwnsQuestion(pAQs[i].iQuestion)) { i++; continue; }
         int64_t j = i + 1;
         while (j < total && !OwnsQuestion(pAQs[j].iQuestion)) j++;
-        HIP_TRY(hipMemcpyAsync(_dRowStage + (size_t)i * slotBytes, base + (size_t)i * slotBytes, (size_t)(j - i) * slotBytes, hipMemcpyDefault, _stream));
+        HIP_TRY(hipMemcpyAsync(stage + (size_t)i * slotBytes, base + (size_t)i * slotBytes, (size_t)(j - i) * slotBytes, hipMemcpyDefault, _stream));
         i = j;
       }
-      base = _dRowStage;
+      base = stage;
       _rowsStaged++;
     }
   }

@@ -407,22 +407,12 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
   }
   HIP_TRY(hipMemcpyAsync(c.dSlots, c.h->slots, (size_t)n * sizeof(QuizSlot), hipMemcpyHostToDevice, _stream));
   StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
-  auto grow = [&](void **p, size_t &have, size_t need) -> hipError_t {
-    if (need <= have) return hipSuccess;
-    hipStreamSynchronize(_stream);
-    hipFree(*p);
-    *p = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc(p, need);
-    if (e == hipSuccess) have = need;
-    return e;
-  };
   // the batched sweeps' pole scratch (pole_kernels.hip): grown with the batch, its head cleared once
   auto growPole = [&](BatchPlan &plan) -> hipError_t {
     plan.pole = nullptr;
     if (plan.poleBytes == 0) return hipSuccess;
     if (plan.poleBytes > c.poleBytes) {
-      const hipError_t e = grow(&c.dPole, c.poleBytes, plan.poleBytes);
+      const hipError_t e = GrowDevice(&c.dPole, c.poleBytes, plan.poleBytes);
       if (e != hipSuccess) return e;
       const hipError_t me = hipMemsetAsync(c.dPole, 0, kBatchPoleClear, _stream);
       if (me != hipSuccess) return me;
@@ -434,11 +424,11 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
     const KbView kb = View();
     BatchPlan plan{};
     HIP_TRY(LaunchEvalMidBatch(kb, c.dSlots, (int)n, &plan, nullptr, nullptr, nullptr, 0, tag, true, _stream));
-    HIP_TRY(grow(&c.dPT, c.ptBytes, plan.ptBytes));
-    HIP_TRY(grow((void **)&c.dRecs, c.recBytes, plan.recBytes));
+    HIP_TRY(GrowDevice(&c.dPT, c.ptBytes, plan.ptBytes));
+    HIP_TRY(GrowDevice(&c.dRecs, c.recBytes, plan.recBytes));
     HIP_TRY(growPole(plan));
     const bool matrix = wantPriorities || devicePriorities || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
-    if (matrix) HIP_TRY(grow((void **)&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
+    if (matrix) HIP_TRY(GrowDevice(&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
     HIP_TRY(LaunchEvalMidBatch(kb, c.dSlots, (int)n, &plan, c.dPT, c.dRecs, matrix ? c.dPriT : nullptr, 0, tag, false, _stream));
     c.lastBp = plan.Bp;
     return Error();
@@ -462,15 +452,15 @@ Error HipEngine::BatchSweep(BatchCtx &c, int64_t n, const int64_t *pQuizzes, std
   plan.questionGroups = (int)_opt.batchGroups;
   plan.splitTail = (int)_opt.batchTail;
   HIP_TRY(LaunchEvalBatch(kb, c.dSlots, (int)n, &plan, nullptr, nullptr, nullptr, nullptr, 0, tag, true, _stream));
-  HIP_TRY(grow(&c.dPT, c.ptBytes, plan.ptBytes));
-  HIP_TRY(grow((void **)&c.dAcc, c.accBytes, plan.accBytes));
-  HIP_TRY(grow((void **)&c.dRecs, c.recBytes, plan.recBytes));
+  HIP_TRY(GrowDevice(&c.dPT, c.ptBytes, plan.ptBytes));
+  HIP_TRY(GrowDevice(&c.dAcc, c.accBytes, plan.accBytes));
+  HIP_TRY(GrowDevice(&c.dRecs, c.recBytes, plan.recBytes));
   // Float engines: the fp32 sweep nominates every quiz's best questions, fp64 decides among them (option "rerank", default on)
   const bool rerank = _elem == 4 && _opt.rerank != 0 && !devicePriorities;   // (an argmax device: the sampled selector reads the matrix itself)
   HIP_TRY(growPole(plan));
   const bool matrix = wantPriorities || devicePriorities || rerank || plan.poleBytes > 0;   // (the fix corrects the priority matrix, the pick reads it)
-  if (matrix) HIP_TRY(grow((void **)&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
-  if (rerank) HIP_TRY(grow(&c.dRerank, c.rerankBytes, BatchRerankScratchBytes()));
+  if (matrix) HIP_TRY(GrowDevice(&c.dPriT, c.priTBytes, (size_t)_Q * (size_t)plan.Bp * sizeof(double)));
+  if (rerank) HIP_TRY(GrowDevice(&c.dRerank, c.rerankBytes, BatchRerankScratchBytes()));
   HIP_TRY(LaunchEvalBatch(kb, c.dSlots, (int)n, &plan, c.dPT, c.dAcc, c.dRecs, matrix ? c.dPriT : nullptr, 0, tag,
                           false, _stream, rerank));
   if (rerank) HIP_TRY(LaunchBatchRerank(kb, c.dSlots, (int)n, plan.Bp, c.dPriT, c.dRerank, 0, tag, _stream));
@@ -636,18 +626,8 @@ Error HipEngine::LaunchSampledBatch(BatchCtx &c, int64_t n, const uint64_t *pRnd
   std::memcpy(c.h->rnd, pRnd, (size_t)n * sizeof(uint64_t));   // (host-coherent: the selector reads them there)
   size_t grandDoubles = 0, runDoubles = 0;
   SelectSampledBatchScratch(_Q, nSub, (int)n, c.lastBp, &grandDoubles, &runDoubles);
-  auto grow = [&](double **p, size_t &have, size_t need) -> hipError_t {
-    if (need <= have) return hipSuccess;
-    hipStreamSynchronize(_stream);
-    hipFree(*p);
-    *p = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc((void **)p, need);
-    if (e == hipSuccess) have = need;
-    return e;
-  };
-  HIP_TRY(grow(&c.dSelGrand, c.selGrandBytes, grandDoubles * sizeof(double)));
-  HIP_TRY(grow(&c.dSelRun, c.selRunBytes, runDoubles * sizeof(double)));
+  HIP_TRY(GrowDevice(&c.dSelGrand, c.selGrandBytes, grandDoubles * sizeof(double)));
+  HIP_TRY(GrowDevice(&c.dSelRun, c.selRunBytes, runDoubles * sizeof(double)));
   SampledBatch a{};
   a.slots = c.dSlots; a.nSlots = (int)n; a.Bp = c.lastBp;
   a.priorityT = c.lastBp > 0 ? c.dPriT : nullptr;

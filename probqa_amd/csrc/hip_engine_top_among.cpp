@@ -88,13 +88,7 @@ Error HipEngine::ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, co
   st.ids.resize((size_t)total);
   for (int64_t k = 0; k < total; k++) st.ids[(size_t)k] = (int32_t)pTargets[k];
   const size_t offBytes = ((size_t)(nLists + 1) * sizeof(int64_t) + 15) / 16 * 16, listBytes = offBytes + (size_t)total * sizeof(int32_t);
-  if (listBytes > st.listBytes) {
-    HIP_TRY(hipStreamSynchronize(_stream));
-    hipFree(st.dLists);
-    st.dLists = nullptr; st.listBytes = 0;
-    HIP_TRY(hipMalloc(&st.dLists, listBytes));
-    st.listBytes = listBytes;
-  }
+  HIP_TRY(GrowDevice(&st.dLists, st.listBytes, listBytes));
   const int64_t *dOffsets = static_cast<const int64_t *>(st.dLists);
   const int32_t *dIds = reinterpret_cast<const int32_t *>(static_cast<const char *>(st.dLists) + offBytes);
   HIP_TRY(hipMemcpyAsync(st.dLists, st.offsets.data(), (size_t)(nLists + 1) * sizeof(int64_t), hipMemcpyHostToDevice, _stream));
@@ -116,30 +110,17 @@ Error HipEngine::ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, co
     const int64_t want = std::max<int64_t>(1, std::min(maxCount, longest));   // (<= 256: every quiz of the group asks for no more)
     err = EnsureTopScratchRecords(m * TopAmongScratchRecords(longest, want));
     if (!err.ok()) return err;
-    const size_t needPartials = (size_t)(m * TopAmongPartials(longest));
-    if (needPartials > st.partials) {
-      HIP_TRY(hipStreamSynchronize(_stream));
-      hipFree(st.dPartial);
-      st.dPartial = nullptr; st.partials = 0;
-      HIP_TRY(hipMalloc((void **)&st.dPartial, needPartials * sizeof(double)));
-      st.partials = needPartials;
-    }
-    const int64_t needRecords = m * want;
-    if (needRecords > st.hRecords) {   // records | counts | masses
-      HIP_TRY(hipStreamSynchronize(_stream));
-      if (st.hLines) hipHostFree(st.hLines);
-      st.hLines = nullptr; st.hRecords = 0;
-      HIP_TRY(hipHostMalloc((void **)&st.hLines, (size_t)needRecords * sizeof(RatedTargetDev) + (size_t)kTopBatchQuizzes * (sizeof(int64_t) + sizeof(double)), hipHostMallocDefault));
-      st.hRecords = needRecords;
-    }
-    int64_t *hCounts = reinterpret_cast<int64_t *>(st.hLines + st.hRecords);
-    double *hMass = reinterpret_cast<double *>(hCounts + kTopBatchQuizzes);
-    HIP_TRY(LaunchTopTargetsAmong(kb, pr, lists, m, dOffsets, dIds, longest, want, _dTopScratch[0], _dTopScratch[1], st.dPartial, st.hLines, hCounts, hMass, _stream));
+    HIP_TRY(GrowDevice(&st.dPartial, st.partialBytes, (size_t)(m * TopAmongPartials(longest)) * sizeof(double)));
+    HIP_TRY(st.lines.Ensure(_stream, m * want, sizeof(double), kTopBatchQuizzes, hipHostMallocDefault));   // records | counts | masses
+    RatedTargetDev *const hLines = st.lines.records;
+    int64_t *const hCounts = st.lines.Counts();
+    double *const hMass = st.lines.Tail<double>();
+    HIP_TRY(LaunchTopTargetsAmong(kb, pr, lists, m, dOffsets, dIds, longest, want, _dTopScratch[0], _dTopScratch[1], st.dPartial, hLines, hCounts, hMass, _stream));
     HIP_TRY(hipStreamSynchronize(_stream));
     for (int64_t j = 0; j < m; j++) {
       const int64_t i = small[first + (size_t)j], c = std::min<int64_t>(std::min<int64_t>(hCounts[j], want), maxCount);
       pCounts[i] = c;
-      std::memcpy(pDest + i * maxCount, st.hLines + j * want, (size_t)c * sizeof(RatedTargetDev));
+      std::memcpy(pDest + i * maxCount, hLines + j * want, (size_t)c * sizeof(RatedTargetDev));
       if (pMass) pMass[i] = hMass[j];
     }
   }
@@ -162,13 +143,7 @@ Error HipEngine::ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, co
       lists[j] = (int32_t)listOf(i);
     }
     const size_t need = (size_t)(m * longest);
-    if (need > st.gathered) {
-      HIP_TRY(hipStreamSynchronize(_stream));
-      hipFree(st.dGather);
-      st.dGather = nullptr; st.gathered = 0;
-      HIP_TRY(hipMalloc((void **)&st.dGather, need * sizeof(double)));
-      st.gathered = need;
-    }
+    HIP_TRY(GrowDevice(&st.dGather, st.gatherBytes, need * sizeof(double)));
     HIP_TRY(LaunchTopAmongGather(kb, pr, lists, m, dOffsets, dIds, longest, st.dGather, _stream));
     pri.resize(need);
     HIP_TRY(hipMemcpyAsync(pri.data(), st.dGather, need * sizeof(double), hipMemcpyDeviceToHost, _stream));
@@ -177,15 +152,11 @@ Error HipEngine::ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, co
       const int64_t i = large[first + (size_t)j], len = pListCounts[listOf(i)];
       const int64_t *ids = pTargets + st.offsets[(size_t)listOf(i)];
       const double *p = pri.data() + (size_t)(j * longest);
-      idx.clear();
       double mass = 0.0;
       for (int64_t k = 0; k < len; k++)
-        if (p[k] > 0.0) { idx.push_back(k); mass += p[k]; }   // (list order: fixed)
-      const int64_t c = std::min<int64_t>(maxCount, (int64_t)idx.size());
-      std::partial_sort(idx.begin(), idx.begin() + c, idx.end(), [&](int64_t a, int64_t b) { return p[a] > p[b] || (p[a] == p[b] && ids[a] < ids[b]); });
-      CiRatedTarget *dest = pDest + i * maxCount;
-      for (int64_t k = 0; k < c; k++) { dest[k]._iTarget = ids[idx[(size_t)k]]; dest[k]._prob = p[idx[(size_t)k]]; }
-      pCounts[i] = c;
+        if (p[k] > 0.0) mass += p[k];   // (list order: fixed)
+      // ties by the listed id, whatever the list's order
+      pCounts[i] = RatedPrefix(p, len, maxCount, [](int64_t) { return true; }, [&](int64_t k) { return ids[k]; }, pDest + i * maxCount, idx);
       if (pMass) pMass[i] = mass;
     }
     first += (size_t)m;

@@ -400,12 +400,7 @@ int64_t HipEngine::ListTopTargetsExact(Error &err, int64_t iQuiz, int64_t maxCou
 
 Error HipEngine::EnsureTopExactScratch(int64_t nQuizzes, int64_t want) {
   const size_t need = TopExactScratchBytes(_T, _opt.workers, want, nQuizzes);
-  if (need <= _topExactBytes) return Error();
-  HIP_TRY(hipStreamSynchronize(_stream));
-  if (_dTopExact) hipFree(_dTopExact);
-  _dTopExact = nullptr; _topExactBytes = 0;
-  HIP_TRY(hipMalloc(&_dTopExact, need));
-  _topExactBytes = need;
+  HIP_TRY(GrowDevice(&_dTopExact, _topExactBytes, need));
   return Error();
 }
 
@@ -573,26 +568,15 @@ int64_t HipEngine::ListTopTargetsOnHost(Error &err, Quiz *q, int64_t want, CiRat
     }
     return listed;
   }
-  std::vector<int64_t> idx;
-  idx.reserve((size_t)_T);
   // gaps and probabilities <= 0 are no candidates (reference PqaCore/CEHeapifyPriorsSubtaskMake.cpp:43-49)
-  for (int64_t t = 0; t < _T; t++) if (!BitTest(_hTGap, t) && pri[(size_t)t] > 0.0) idx.push_back(t);
-  const int64_t n = std::min<int64_t>(want, (int64_t)idx.size());
-  std::partial_sort(idx.begin(), idx.begin() + n, idx.end(),
-                    [&](int64_t a, int64_t b) { return pri[a] > pri[b] || (pri[a] == pri[b] && a < b); });
-  for (int64_t i = 0; i < n; i++) { pDest[i]._iTarget = idx[i]; pDest[i]._prob = pri[idx[i]]; }
-  return n;
+  std::vector<int64_t> idx;
+  return RatedPrefix(pri.data(), _T, want, [&](int64_t t) { return !BitTest(_hTGap, t); }, [](int64_t t) { return t; }, pDest, idx);
 }
 
 // The device scratch of the chunked listing (two buffers of candidate lists) for nQuizzes quizzes at once.
 Error HipEngine::EnsureTopScratch(int64_t nQuizzes, int64_t want) { return EnsureTopScratchRecords(nQuizzes * TopBatchScratchRecords(_T, want)); }
 Error HipEngine::EnsureTopScratchRecords(int64_t need) {
-  if (need <= _topScratchRecords) return Error();
-  HIP_TRY(hipStreamSynchronize(_stream));   // (nothing in flight reads the buffers about to go)
-  for (int i = 0; i < 2; i++) { if (_dTopScratch[i]) hipFree(_dTopScratch[i]); _dTopScratch[i] = nullptr; }
-  _topScratchRecords = 0;
-  for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc((void **)&_dTopScratch[i], (size_t)need * sizeof(RatedTargetDev)));
-  _topScratchRecords = need;
+  for (int i = 0; i < 2; i++) HIP_TRY(GrowDevice(&_dTopScratch[i], _topScratchBytes[i], (size_t)need * sizeof(RatedTargetDev)));
   return Error();
 }
 
@@ -636,25 +620,19 @@ Error HipEngine::ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t
   err = EnsureTopScratch(group, probe);
   if (!err.ok()) return err;
   // the results' lines: host-coherent, written by the last level's workgroups
-  const int64_t needRecords = group * probe;
-  if (needRecords > _hTopBatchRecords) {
-    HIP_TRY(hipStreamSynchronize(_stream));
-    if (_hTopBatch) hipHostFree(_hTopBatch);
-    _hTopBatch = nullptr; _hTopBatchRecords = 0;
-    HIP_TRY(hipHostMalloc((void **)&_hTopBatch, (size_t)needRecords * sizeof(RatedTargetDev) + (size_t)kTopBatchQuizzes * sizeof(int64_t), hipHostMallocDefault));
-    _hTopBatchRecords = needRecords;
-  }
-  int64_t *hCounts = reinterpret_cast<int64_t *>(_hTopBatch + _hTopBatchRecords);
+  HIP_TRY(_hTopBatch.Ensure(_stream, group * probe, 0, kTopBatchQuizzes, hipHostMallocDefault));
+  RatedTargetDev *const hLines = _hTopBatch.records;
+  int64_t *const hCounts = _hTopBatch.Counts();
   std::vector<int64_t> tied;   // positions in the batch
   for (int64_t first = 0; first < n; first += group) {
     const int64_t m = std::min<int64_t>(group, n - first);
     TopBatchPriors pr;
     for (int64_t i = 0; i < m; i++) pr.prior[i] = quizzes[(size_t)(first + i)]->dPrior;
-    HIP_TRY(LaunchTopTargetsBatch(View(), pr, m, probe, _dTopScratch[0], _dTopScratch[1], _hTopBatch, hCounts, nullptr, 0, _stream));
+    HIP_TRY(LaunchTopTargetsBatch(View(), pr, m, probe, _dTopScratch[0], _dTopScratch[1], hLines, hCounts, nullptr, 0, _stream));
     HIP_TRY(hipStreamSynchronize(_stream));
     for (int64_t i = 0; i < m; i++) {
       const int64_t got = std::min<int64_t>(hCounts[i], probe), c = std::min(got, want);
-      const CiRatedTarget *rec = reinterpret_cast<const CiRatedTarget *>(_hTopBatch + i * probe);
+      const CiRatedTarget *rec = reinterpret_cast<const CiRatedTarget *>(hLines + i * probe);
       pCounts[first + i] = c;
       std::memcpy(pDest + (first + i) * maxCount, rec, (size_t)c * sizeof(RatedTargetDev));
       if (exact && ((probe == want && got == want && want < _T) || ListingHasTies(rec, got, want, probe))) tied.push_back(first + i);
@@ -670,12 +648,12 @@ Error HipEngine::ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t
     const int64_t m = std::min<int64_t>(tgroup, (int64_t)(tied.size() - first));
     TopBatchPriors pr;
     for (int64_t i = 0; i < m; i++) pr.prior[i] = quizzes[(size_t)tied[first + (size_t)i]]->dPrior;
-    HIP_TRY(LaunchTopTargetsExact(View(), pr, m, _opt.workers, want, _dTopExact, _hTopBatch, hCounts, nullptr, 0, _stream));   // (want <= probe: the lines hold it)
+    HIP_TRY(LaunchTopTargetsExact(View(), pr, m, _opt.workers, want, _dTopExact, hLines, hCounts, nullptr, 0, _stream));   // (want <= probe: the lines hold it)
     HIP_TRY(hipStreamSynchronize(_stream));
     for (int64_t i = 0; i < m; i++) {
       const int64_t at = tied[first + (size_t)i], c = std::min<int64_t>(hCounts[i], want);
       pCounts[at] = c;
-      std::memcpy(pDest + at * maxCount, _hTopBatch + i * want, (size_t)c * sizeof(RatedTargetDev));
+      std::memcpy(pDest + at * maxCount, hLines + i * want, (size_t)c * sizeof(RatedTargetDev));
     }
     _topExactListings += m;
   }

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -146,6 +147,24 @@ inline std::vector<RatedIndex> MergeTop(const std::vector<std::pair<const RatedI
   std::partial_sort(all.begin(), all.begin() + n, all.end(), RatedBefore);
   all.resize(n);
   return all;
+}
+
+// The host's prefix of a rated vector -- every listing of more than 256 records, in the device listings' order: of the n entries that
+// are eligible(i) and whose value is > 0 (a NaN is not), the first `want` by value descending, idOf(i) ascending, as {id, value} records
+// (Rec: CiRatedTarget, CiRatedQuestion or RatedIndex).  idx: the caller's scratch, reused from vector to vector.  Returns the count.
+template <typename Rec, typename Eligible, typename IdOf>
+inline int64_t RatedPrefix(const double *v, int64_t n, int64_t want, Eligible eligible, IdOf idOf, Rec *dest, std::vector<int64_t> &idx) {
+  static_assert(sizeof(Rec) == sizeof(RatedIndex), "a record is {int64 id, double value}");
+  idx.clear();
+  for (int64_t i = 0; i < n; i++)
+    if (eligible(i) && v[i] > 0.0) idx.push_back(i);
+  const int64_t c = std::max<int64_t>(0, std::min<int64_t>(want, (int64_t)idx.size()));
+  std::partial_sort(idx.begin(), idx.begin() + c, idx.end(), [&](int64_t a, int64_t b) { return v[a] > v[b] || (v[a] == v[b] && idOf(a) < idOf(b)); });
+  for (int64_t k = 0; k < c; k++) {
+    const RatedIndex r{idOf(idx[(size_t)k]), v[idx[(size_t)k]]};
+    std::memcpy(dest + k, &r, sizeof(r));
+  }
+  return c;
 }
 
 // Where the arrays of a .kb file lie (layout: hip_engine_kb.cpp), in bytes from the file's start, and where the rows of a window of

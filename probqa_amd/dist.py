@@ -662,6 +662,29 @@ def record_answer(engine, quiz: int, answer: int, rank: int, world: int, group: 
     record_answer_batch(engine, [quiz], [answer], rank, world, group, device)
 
 
+def _list_from_summed_packages(engine, ranks: _Ranks, sources, pitch: int, pack, list_from, finish=None) -> list:
+    """The source listings' exchange, 256 sources at a time: a zero-filled package of `pitch` doubles a source, pack(chunk, address)
+    and the all-reduce (_summed_package), the status word, list_from(chunk, address), the status word; finish (optional): what turns a
+    chunk's local listings into the call's (a collective of its own)."""
+    from . import interop
+
+    sources = [int(s) for s in sources]
+    out = []
+    for first in range(0, len(sources), 256):
+        chunk = sources[first:first + 256]
+        pkg = torch.zeros(len(chunk), pitch, dtype=torch.float64, device=ranks.device)
+        error = _summed_package(ranks, engine, pkg, lambda ptr: pack(chunk, ptr))
+        ranks.settle(error)
+        listed = None
+        try:
+            listed = list_from(chunk, pkg.data_ptr())
+        except interop.PqaException as e:
+            error = str(e)
+        ranks.settle(error)
+        out.extend(finish(listed) if finish else listed)
+    return out
+
+
 # ---- targets that answer like a given one, over the shards ------------------------------------------------------------------------
 # The similarity of a source and a target is a sum over the questions: every rank packs the sums over ITS questions into a
 # zero-filled package (PqaHip_PackTargetSimilaritySums; every slot is written whole by every rank), ONE all_reduce(SUM) adds them,
@@ -675,25 +698,8 @@ def list_similar_targets_batch(engine, sources, max_count: int, rank: int, world
     max_count; any number of sources, 256 per exchange.  All or none as record_answer_batch is: a rank whose pack is refused still
     takes part in the all-reduce, and after the status word every rank raises the first failing rank's text.  Under an NCCL
     (RCCL) group the package stays on the device, under gloo it goes through the host."""
-    from . import interop
-
-    ranks = _Ranks(group, device, rank, world)
-    sources = [int(s) for s in sources]
-    pitch = engine.posterior_slot_bytes() // 8
-    out = []
-    for first in range(0, len(sources), 256):
-        chunk = sources[first:first + 256]
-        pkg = torch.zeros(len(chunk), pitch, dtype=torch.float64, device=ranks.device)
-        error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_target_similarity_sums(chunk, ptr))
-        ranks.settle(error)
-        listed = None
-        try:
-            listed = engine.list_similar_targets_from_sums(chunk, pkg.data_ptr(), max_count)
-        except interop.PqaException as e:
-            error = str(e)
-        ranks.settle(error)
-        out.extend(listed)
-    return out
+    return _list_from_summed_packages(engine, _Ranks(group, device, rank, world), sources, engine.posterior_slot_bytes() // 8, engine.pack_target_similarity_sums,
+                                      lambda chunk, ptr: engine.list_similar_targets_from_sums(chunk, ptr, max_count))
 
 
 # ---- questions whose answers a given one predicts, over the shards -----------------------------------------------------------------
@@ -709,25 +715,9 @@ def list_redundant_questions_batch(engine, sources, max_count: int, rank: int, w
     (GLOBAL ids) and max_count; any number of sources, 256 per exchange.  Every rank returns the same (question, bits) records.  All
     or none as list_similar_targets_batch is: a rank whose pack is refused still takes part in the all-reduce, and after the status
     word every rank raises the first failing rank's text."""
-    from . import interop
-
-    ranks = _Ranks(group, device, rank, world)
-    sources = [int(s) for s in sources]
-    pitch = engine.question_weight_slot_bytes() // 8
-    out = []
-    for first in range(0, len(sources), 256):
-        chunk = sources[first:first + 256]
-        pkg = torch.zeros(len(chunk), pitch, dtype=torch.float64, device=ranks.device)
-        error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_question_weights(chunk, ptr))
-        ranks.settle(error)
-        listed = None
-        try:
-            listed = engine.list_redundant_questions_from_weights(chunk, pkg.data_ptr(), max_count)
-        except interop.PqaException as e:
-            error = str(e)
-        ranks.settle(error)
-        out.extend(_gather_top(listed, max_count, group, device))
-    return out
+    return _list_from_summed_packages(engine, _Ranks(group, device, rank, world), sources, engine.question_weight_slot_bytes() // 8, engine.pack_question_weights,
+                                      lambda chunk, ptr: engine.list_redundant_questions_from_weights(chunk, ptr, max_count),
+                                      lambda listed: _gather_top(listed, max_count, group, device))
 
 
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------

@@ -443,6 +443,13 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(_pdbl)
 
 
+_RECORD = np.dtype([("id", np.int64), ("value", np.float64)])   # CiRatedTarget, CiRatedQuestion
+
+
+def _pair(index: int, value: float) -> Tuple[int, float]:
+    return index, value
+
+
 class PqaEngine:
     """Reference ProbQA.py:423-741 plus the additive MI355X methods."""
 
@@ -1014,14 +1021,26 @@ class PqaEngine:
         return _check(_lib.PqaEngine_RecordQuizTargetBatch(self.c_engine, n, quizzes.ctypes.data_as(_pi64), targets.ctypes.data_as(_pi64),
                                                            amounts.ctypes.data_as(_pdbl)), throw)
 
+    # ---- the batched listings: one decoder of their records, one caller of their entries ------------------------------------------
+    @staticmethod
+    def _records(arr, counts, n: int, max_count: int, make_record) -> list:
+        """Entry i's counts[i] records, from arr[i * max_count] on, each as make_record(id, value)."""
+        rec = np.frombuffer(arr, dtype=_RECORD)
+        return [[make_record(k, v) for k, v in zip(r["id"].tolist(), r["value"].tolist())]
+                for r in (rec[i * max_count:i * max_count + int(counts[i])] for i in range(n))]
+
+    def _list_batch(self, entry, record_type, make_record, ids, max_count: int, *package) -> list:
+        """entry(engine, n, ids, [package,] max_count, records, counts) for the quizzes or sources `ids` -> their n listings."""
+        src = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n = len(src)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        arr = (record_type * max(n * max_count, 1))()
+        _check(entry(self.c_engine, n, src.ctypes.data_as(_pi64), *package, max_count, arr, counts.ctypes.data_as(_pi64)))
+        return self._records(arr, counts, n, max_count, make_record)
+
     def list_top_targets_batch(self, quizzes, max_count: int) -> List[List[RatedTarget]]:
         """ListTopTargets of several quizzes with one launch sequence; no posterior leaves the device."""
-        n = len(quizzes)
-        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
-        counts = (ctypes.c_int64 * max(n, 1))()
-        arr = (CiRatedTarget * max(n * max_count, 1))()
-        _check(_lib.PqaEngine_ListTopTargetsBatch(self.c_engine, n, qs, max_count, arr, counts))
-        return [[RatedTarget(arr[i * max_count + j].iTarget, arr[i * max_count + j].prob) for j in range(counts[i])] for i in range(n)]
+        return self._list_batch(_lib.PqaEngine_ListTopTargetsBatch, CiRatedTarget, RatedTarget, quizzes, max_count)
 
     def list_top_targets_among_batch(self, quizzes, lists, max_count: int, list_of=None) -> Tuple[List[List[RatedTarget]], List[float]]:
         """The best targets of several quizzes (a quiz may repeat) WITHIN LISTED SETS of targets, and the posterior's total over each
@@ -1041,12 +1060,7 @@ class PqaEngine:
         _check(_lib.PqaEngine_ListTopTargetsAmongBatch(self.c_engine, n, qs.ctypes.data_as(_pi64), None if lof is None else lof.ctypes.data_as(_pi64), len(lists),
                                                        lens.ctypes.data_as(_pi64), ids.ctypes.data_as(_pi64), max_count, arr, counts.ctypes.data_as(_pi64),
                                                        mass.ctypes.data_as(_pdbl)))
-        rec = np.frombuffer(arr, dtype=np.dtype([("t", np.int64), ("p", np.float64)]))
-        out = []
-        for i in range(n):
-            r = rec[i * max_count:i * max_count + int(counts[i])]
-            out.append([RatedTarget(int(t), float(p)) for t, p in zip(r["t"], r["p"])])
-        return out, [float(m) for m in mass[:n]]
+        return self._records(arr, counts, n, max_count, RatedTarget), [float(m) for m in mass[:n]]
 
     def list_top_targets_among(self, i_quiz: int, targets, max_count: int) -> Tuple[List[RatedTarget], float]:
         got, mass = self.list_top_targets_among_batch([i_quiz], [list(targets)], max_count)
@@ -1063,24 +1077,10 @@ class PqaEngine:
         _check(_lib.PqaEngine_EvalTargetSimilarity(self.c_engine, len(src), src.ctypes.data_as(_pi64), _dptr(out), t))
         return out
 
-    @staticmethod
-    def _similar_records(arr, counts, n: int, max_count: int) -> List[List[RatedTarget]]:
-        rec = np.frombuffer(arr, dtype=np.dtype([("t", np.int64), ("p", np.float64)]))
-        out = []
-        for i in range(n):
-            r = rec[i * max_count:i * max_count + int(counts[i])]
-            out.append([RatedTarget(int(t), float(p)) for t, p in zip(r["t"], r["p"])])
-        return out
-
     def list_similar_targets_batch(self, sources, max_count: int) -> List[List[RatedTarget]]:
         """Per source the targets most like it, the source itself and the gaps left out: similarity descending, target id
         ascending among equal values; the values are eval_target_similarity's bits.  Any number of sources, ids may repeat."""
-        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
-        n = len(src)
-        counts = np.zeros(max(n, 1), dtype=np.int64)
-        arr = (CiRatedTarget * max(n * max_count, 1))()
-        _check(_lib.PqaEngine_ListSimilarTargetsBatch(self.c_engine, n, src.ctypes.data_as(_pi64), max_count, arr, counts.ctypes.data_as(_pi64)))
-        return self._similar_records(arr, counts, n, max_count)
+        return self._list_batch(_lib.PqaEngine_ListSimilarTargetsBatch, CiRatedTarget, RatedTarget, sources, max_count)
 
     def list_similar_targets(self, source: int, max_count: int) -> List[RatedTarget]:
         return self.list_similar_targets_batch([source], max_count)[0]
@@ -1095,13 +1095,7 @@ class PqaEngine:
 
     def list_similar_targets_from_sums(self, sources, ptr: int, max_count: int) -> List[List[RatedTarget]]:
         """list_similar_targets_batch from the summed package at device-visible address `ptr`."""
-        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
-        n = len(src)
-        counts = np.zeros(max(n, 1), dtype=np.int64)
-        arr = (CiRatedTarget * max(n * max_count, 1))()
-        _check(_lib.PqaEngine_ListSimilarTargetsFromSums(self.c_engine, n, src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None), max_count, arr,
-                                                         counts.ctypes.data_as(_pi64)))
-        return self._similar_records(arr, counts, n, max_count)
+        return self._list_batch(_lib.PqaEngine_ListSimilarTargetsFromSums, CiRatedTarget, RatedTarget, sources, max_count, ctypes.c_void_p(ptr or None))
 
     # ---- questions whose answers a given one predicts (include/PqaHipExt.h: PqaEngine_EvalQuestionRedundancy and its neighbours) ----
     def eval_question_redundancy(self, sources) -> np.ndarray:
@@ -1114,25 +1108,11 @@ class PqaEngine:
         _check(_lib.PqaEngine_EvalQuestionRedundancy(self.c_engine, len(src), src.ctypes.data_as(_pi64), _dptr(out), q))
         return out
 
-    @staticmethod
-    def _redundant_records(arr, counts, n: int, max_count: int) -> List[List[Tuple[int, float]]]:
-        rec = np.frombuffer(arr, dtype=np.dtype([("q", np.int64), ("p", np.float64)]))
-        out = []
-        for i in range(n):
-            r = rec[i * max_count:i * max_count + int(counts[i])]
-            out.append([(int(q), float(p)) for q, p in zip(r["q"], r["p"])])
-        return out
-
     def list_redundant_questions_batch(self, sources, max_count: int) -> List[List[Tuple[int, float]]]:
         """Per source the questions whose answers it predicts best as (question, bits), the source itself and the gaps left out: bits
         descending, question id ascending among equal values; the values are eval_question_redundancy's bits.  Any number of
         sources, ids may repeat."""
-        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
-        n = len(src)
-        counts = np.zeros(max(n, 1), dtype=np.int64)
-        arr = (CiRatedQuestion * max(n * max_count, 1))()
-        _check(_lib.PqaEngine_ListRedundantQuestionsBatch(self.c_engine, n, src.ctypes.data_as(_pi64), max_count, arr, counts.ctypes.data_as(_pi64)))
-        return self._redundant_records(arr, counts, n, max_count)
+        return self._list_batch(_lib.PqaEngine_ListRedundantQuestionsBatch, CiRatedQuestion, _pair, sources, max_count)
 
     def list_redundant_questions(self, source: int, max_count: int) -> List[Tuple[int, float]]:
         return self.list_redundant_questions_batch([source], max_count)[0]
@@ -1162,13 +1142,7 @@ class PqaEngine:
     def list_redundant_questions_from_weights(self, sources, ptr: int, max_count: int) -> List[List[Tuple[int, float]]]:
         """list_redundant_questions_batch over the questions THIS engine holds from the summed package at device-visible address
         `ptr`; GLOBAL ids.  The ranks' lists are merged by dist.merge_top_questions."""
-        src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
-        n = len(src)
-        counts = np.zeros(max(n, 1), dtype=np.int64)
-        arr = (CiRatedQuestion * max(n * max_count, 1))()
-        _check(_lib.PqaEngine_ListRedundantQuestionsFromWeights(self.c_engine, n, src.ctypes.data_as(_pi64), ctypes.c_void_p(ptr or None), max_count, arr,
-                                                                counts.ctypes.data_as(_pi64)))
-        return self._redundant_records(arr, counts, n, max_count)
+        return self._list_batch(_lib.PqaEngine_ListRedundantQuestionsFromWeights, CiRatedQuestion, _pair, sources, max_count, ctypes.c_void_p(ptr or None))
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
@@ -1184,12 +1158,7 @@ class PqaEngine:
 
     def list_top_questions_batch(self, quizzes, max_count: int) -> List[List[Tuple[int, float]]]:
         """list_top_questions of up to 256 distinct quizzes behind one batched sweep (eval_priorities_batch's values)."""
-        n = len(quizzes)
-        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
-        counts = (ctypes.c_int64 * max(n, 1))()
-        arr = (CiRatedQuestion * max(n * max_count, 1))()
-        _check(_lib.PqaEngine_ListTopQuestionsBatch(self.c_engine, n, qs, max_count, arr, counts))
-        return [[(arr[i * max_count + j].iQuestion, arr[i * max_count + j].priority) for j in range(counts[i])] for i in range(n)]
+        return self._list_batch(_lib.PqaEngine_ListTopQuestionsBatch, CiRatedQuestion, _pair, quizzes, max_count)
 
     def record_answer_remote(self, i_quiz: int, i_answer: int):
         _check(_lib.PqaHip_RecordAnswerRemote(self.c_engine, i_quiz, i_answer))

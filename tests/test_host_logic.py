@@ -414,6 +414,69 @@ def test_malformed_plan_scripts_are_refused():
     assert probe("better_pick", [bits(1.0)], 2)[0] == -1
 
 
+# ---- the host's prefix of a rated vector (kb_plan.h: RatedPrefix), the one listing of more than 256 records ------------------------
+def rated_prefix(values, eligible, id_base, want):
+    words = [want, id_base, len(values)]
+    for v, e in zip(values, eligible):
+        words += [bits(v), int(e)]
+    n, out = probe("rated_prefix", words, 1 + len(values))
+    assert n == 1 + out[0], (n, out)
+    return out[1:]
+
+
+def prefix_model(values, eligible, id_base, want):
+    """the eligible entries with a value > 0 (a NaN is not), value descending, id ascending, the first `want`"""
+    v = np.asarray(values, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        at = np.flatnonzero(np.asarray(eligible, dtype=bool) & (v > 0)) if len(v) else np.zeros(0, dtype=np.int64)
+    ids = at + id_base
+    return [int(i) for i in ids[np.lexsort((ids, -v[at]))][:want]]
+
+
+def test_rated_prefix_named_cases():
+    def check(values, eligible=None, id_base=0, want=3):
+        eligible = [1] * len(values) if eligible is None else eligible
+        got = rated_prefix(values, eligible, id_base, want)
+        assert got == prefix_model(values, eligible, id_base, want), (values, eligible, id_base, want, got)
+        return got
+
+    assert check([2.5] * 7, want=4) == [0, 1, 2, 3]                                      # all values equal: by id
+    assert check([1.0, 3.0, 3.0, 2.0, 3.0, 2.0, 2.0, 1.0], want=4) == [1, 2, 4, 3]       # runs of ties across the boundary of `want`
+    assert check([1.0, 3.0, 3.0, 2.0, 3.0, 2.0, 2.0, 1.0], want=2) == [1, 2]
+    assert check([3.0, 2.0, 3.0, 2.0], eligible=[0, 1, 1, 1], id_base=100, want=2) == [102, 101]
+    assert check([0.0, 1.0, 0.0, 2.0], want=4) == [3, 1]                                 # zeros
+    assert check([-0.0, 1.0, -0.0], want=3) == [1]                                       # negative zero
+    assert check([-1.0, -math.inf, 5e-324], want=3) == [2]
+    assert check([1.0, math.nan, 2.0, math.nan], want=4) == [2, 0]                       # a NaN is not > 0: never listed
+    assert check([math.inf, 1.0, math.inf], want=3) == [0, 2, 1]
+    assert check([3.0, 1.0, 2.0], want=0) == []                                          # `want` of 0
+    assert check([1.0, 3.0, 2.0], want=1) == [1]                                         # ... of 1
+    assert check([1.0, 0.0, 3.0, 2.0], eligible=[1, 1, 1, 0], want=2) == [2, 0]          # ... exactly the eligible count
+    assert check([1.0, 0.0, 3.0, 2.0], eligible=[1, 1, 1, 0], want=9) == [2, 0]          # ... beyond it
+    assert check([], want=5) == []                                                       # an empty vector
+    assert check([4.0, 4.0], eligible=[0, 0], want=2) == []
+
+
+def test_rated_prefix_against_lexsort():
+    rng = np.random.default_rng(77)
+    for _ in range(50):   # values from 4 distinct numbers: ties are the rule
+        n = int(rng.integers(1, 301))
+        values = rng.choice([0.0, 0.25, 1.0, 7.5], size=n)
+        eligible = rng.random(n) < 0.8
+        id_base, want = int(rng.integers(0, 1000)), int(rng.integers(0, n + 5))
+        assert rated_prefix(values, eligible, id_base, want) == prefix_model(values, eligible, id_base, want), (n, id_base, want)
+
+
+def test_malformed_rated_prefix_scripts_are_refused():
+    assert probe("rated_prefix", [1, 0], 4)[0] == -1                                  # no count
+    assert probe("rated_prefix", [1, 0, 2, bits(1.0), 1], 4)[0] == -1                 # the vector is cut short
+    assert probe("rated_prefix", [1, 0, 1, bits(1.0), 1, 7], 4)[0] == -1              # words left over
+    assert probe("rated_prefix", [-1, 0, 1, bits(1.0), 1], 4)[0] == -1                # a negative `want`
+    assert probe("rated_prefix", [1, 0, -1], 4)[0] == -1                              # a negative count
+    assert probe("rated_prefix", [1, 0, 1, bits(1.0), 2], 4)[0] == -1                 # eligibility is a bit
+    assert probe("rated_prefix", [2, 0, 2, bits(1.0), 1, bits(2.0), 1], 2)[0] == -1   # output too small
+
+
 # ---- the options (engine_options.h) -----------------------------------------------------------------------------------------------
 # Every option PqaHip_SetOption accepts, as SetOption, GetOption and ApplyEnvironment treated it before there was a table (this
 # list was written from those three functions, not from the table): the accepted values lo..hi, the default, whether it is a flag
