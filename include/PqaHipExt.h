@@ -421,6 +421,47 @@ PQACORE_API void *PqaEngine_EvalQuestionRedundancyFromWeights(void *pvEngine, in
 PQACORE_API void *PqaEngine_ListRedundantQuestionsFromWeights(void *pvEngine, int64_t nSources, const int64_t *pSources,
                                                               const void *pWeights, int64_t maxCount, CiRatedQuestion *pDest,
                                                               int64_t *pCounts);
+/* Questions that tell listed targets apart: what an operator asks once PqaEngine_ListSimilarTargetsBatch has reported a confusable pair or
+ * cluster -- no question separates them: duplicates for PqaEngine_RemoveTargets; a few do: the questions to train, or to hand to the Among
+ * calls when a quiz is down to these candidates.  A GROUP is a list of n targets, 2 <= n <= 64; ids may repeat, a repeat counts twice.
+ * pTargets holds the groups one after another, pGroupCounts[g] targets each.  For a question q that is no gap, with
+ * p_k(j) = A[q][k][t_j] * (1 / D[q][t_j]) for member j:
+ *      f(x) = x log2 x, f(0) = 0;    m_k = (sum over j of p_k(j)) * (1 / n)
+ *      sep(G, q) = max(0, (1 / n) sum_j sum_k f(p_k(j)) - sum_k f(m_k))                                     bits
+ * the Jensen-Shannon divergence of the members' answer distributions under equal weights, which is the mutual information between the
+ * answer and which member it is: 0 when the members answer q alike, log2 n when no two of them share an answer, and for a pair 1 exactly
+ * where the Bhattacharyya term of PqaEngine_EvalTargetSimilarity is 0.  The weights are equal on purpose: the value depends on the
+ * group's columns of q's block alone -- not on vB, other targets or other questions.  0 where q is a gap; a group with a gap member gets a
+ * row of zeros and lists nothing.  The reference has no such call.
+ *  (a) Arithmetic: fp64 throughout (a Float engine's elements are converted exactly); per member sum_k f(p_k) with k ascending, the
+ *      members added in a fixed tree over their places in the group, sum_k f(m_k) with k ascending, the device's fp64 log2, no atomics.
+ *      Against math.fsum and math.log2 over the same p a value is within (16 + 8 n K) 2^-52 bits ABSOLUTE.
+ *  (b) Fixed, bit for bit: a group's values depend on n, nAnswers and the listed order of its members only -- not on what else is in the
+ *      call, where the group stands in it or how the call is chunked; a shard returns the whole engine's bits for its questions; a
+ *      question block that is a bitwise copy of another gets the other's bits for every group.
+ *  (c) Modes: regular AND maintenance mode; the calls read only the knowledge base and change neither it nor any quiz.  They take the
+ *      engine as PqaEngine_TrainBatch does: a training enqueued earlier is ordered in front.
+ *  (d) Refusals, all decided before anything is launched or written, in this order: negative nGroups / maxCount (NegativeCount); a NULL
+ *      buffer that is needed (NullArgument); a group count outside [2, 64] (IndexOutOfRange, "entry=", "count="); a target outside
+ *      [0, nTargets) (IndexOutOfRange, "entry=", "member=", "targetId="); a wrong n (IndexOutOfRange); a shut down engine
+ *      (ObjectShutDown).
+ *   PqaEngine_EvalTargetSeparation          pOut[g * n + j] = sep(G_g, q_first + j); n must be the engine's own question count (a whole
+ *                                           engine: nQuestions).  Any number of groups: the host chunks at group boundaries.
+ *   PqaEngine_ListSeparatingQuestionsBatch  group g's candidates are the engine's questions that are no gaps and have sep > 0;
+ *                                           pCounts[g] = min(maxCount, candidates) records at pDest + g * maxCount, sep descending,
+ *                                           question id ascending among equal values; GLOBAL ids; _priority carries the bits
+ *                                           PqaEngine_EvalTargetSeparation returns.  maxCount 0 is no error.  Up to 256 records a group
+ *                                           the rows stay on the device (the listing kernels of PqaEngine_ListTopQuestions); beyond that
+ *                                           the rows are copied and the prefix is taken on the host in the same order.
+ * Both calls work on a whole engine AND directly on an engine made by PqaEngineFactory_CreateHipEngineSharded, for the questions it
+ * holds: a value needs nothing from another rank, so there is no package and no pack call; a host merges the ranks' lists
+ * (probqa_amd/dist.py: list_separating_questions_batch).  The one-process sharded engine (PQA_DEVICES) keeps the interface's default and
+ * answers NotImplemented, like the Among, similarity and redundancy families.  Read-only counters: "separation_calls",
+ * "separation_groups", and with "time_sweeps" "separation_device_ns" (the staging copies, sweeps and listing kernels). */
+PQACORE_API void *PqaEngine_EvalTargetSeparation(void *pvEngine, int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets,
+                                                 double *pOut, int64_t n);
+PQACORE_API void *PqaEngine_ListSeparatingQuestionsBatch(void *pvEngine, int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets,
+                                                         int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

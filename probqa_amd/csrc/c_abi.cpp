@@ -528,6 +528,16 @@ PQACORE_API void *PqaEngine_ListRedundantQuestionsFromWeights(void *pvEngine, co
                                                               const int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListRedundantQuestionsFromWeights(nSources, pSources, pWeights, maxCount, pDest, pCounts); });
 }
+// ---- questions that tell listed targets apart (hip_engine_sources.cpp): a value needs the group's columns of one question's block and
+// nothing else, so a shard driven by a process of its own answers for its questions directly -- no package, no pack call
+PQACORE_API void *PqaEngine_EvalTargetSeparation(void *pvEngine, const int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets, double *pOut,
+                                                 const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalTargetSeparation(nGroups, pGroupCounts, pTargets, pOut, n); });
+}
+PQACORE_API void *PqaEngine_ListSeparatingQuestionsBatch(void *pvEngine, const int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets,
+                                                         const int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListSeparatingQuestionsBatch(nGroups, pGroupCounts, pTargets, maxCount, pDest, pCounts); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {
@@ -896,6 +906,16 @@ static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_
     pOut[0] = c;
     for (int64_t k = 0; k < c; k++) pOut[1 + k] = recs[(size_t)k].index;
     return 1 + c;
+  }
+  if (w == "group_tiles") {   // {maxEntries, maxGroups, nGroups, then the groups' counts} -> {nTiles, then the first group of every tile, nGroups}
+    if (nIn < 3 || pIn[0] < 1 || pIn[1] < 1 || pIn[2] < 0 || nIn != 3 + pIn[2]) return -1;
+    for (int64_t g = 0; g < pIn[2]; g++)
+      if (pIn[3 + g] < 0) return -1;
+    const std::vector<int64_t> tiles = pqa::PlanGroupTiles(pIn[2], pIn + 3, pIn[0], pIn[1]);
+    if (1 + (int64_t)tiles.size() > nOut) return -1;
+    pOut[0] = (int64_t)tiles.size() - 1;
+    for (size_t k = 0; k < tiles.size(); k++) pOut[1 + k] = tiles[k];
+    return 1 + (int64_t)tiles.size();
   }
   if (w == "better_pick") {
     if (nIn % 2 != 0 || nOut < 2) return -1;

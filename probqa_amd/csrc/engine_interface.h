@@ -167,8 +167,18 @@ class IEngine {
   virtual Error ListRedundantQuestionsFromWeights(int64_t, const int64_t *, const void *, int64_t, CiRatedQuestion *, int64_t *) {
     return NoRedundancy("ListRedundantQuestionsFromWeights");
   }
+  // Questions that tell listed targets apart (include/PqaHipExt.h: PqaEngine_EvalTargetSeparation and its neighbour); the one-process
+  // sharded engine does not offer them.
+  virtual Error EvalTargetSeparation(int64_t, const int64_t *, const int64_t *, double *, int64_t) { return NoSeparation("EvalTargetSeparation"); }
+  virtual Error ListSeparatingQuestionsBatch(int64_t, const int64_t *, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) {
+    return NoSeparation("ListSeparatingQuestionsBatch");
+  }
 
  private:
+  static Error NoSeparation(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
+                        "Target separation is for whole engines and for shards that separate processes drive.");
+  }
   static Error NoRedundancy(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
                         "Question redundancy is for whole engines and for shards that separate processes drive.");

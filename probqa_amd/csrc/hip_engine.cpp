@@ -311,7 +311,7 @@ HipEngine::~HipEngine() {
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   _hTopBatch.Free(); _hTopQ.Free(); _topAmong.lines.Free();
   hipFree(_topAmong.dLists); hipFree(_topAmong.dPartial); hipFree(_topAmong.dGather);
-  for (SourceStage *st : {&_sim, &_red}) {
+  for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
     for (hipEvent_t e : st->ev) if (e) hipEventDestroy(e);
@@ -400,6 +400,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"redundancy_calls", &HipEngine::_redCalls},                        // question redundancy calls that were accepted (hip_engine_sources.cpp) ...
       {"redundancy_sources", &HipEngine::_redSources},                    // ... the sources swept for ...
       {"redundancy_device_ns", &HipEngine::_redDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
+      {"separation_calls", &HipEngine::_sepCalls},                        // target separation calls that were accepted (hip_engine_sources.cpp) ...
+      {"separation_groups", &HipEngine::_sepGroups},                      // ... the groups swept for ...
+      {"separation_device_ns", &HipEngine::_sepDeviceNs},                 // ... and, with time_sweeps, their staging, sweeps and listing kernels between events
       {"fused_updates", &HipEngine::_fusedUpdates},                       // RecordAnswers whose update ran inside the sweep's launch
       {"top_exact_listings", &HipEngine::_topExactListings},
       {"combined_batches", &HipEngine::_combBatches},                     // sweeps that served more than one NextQuestion call ...

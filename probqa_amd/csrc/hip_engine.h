@@ -303,6 +303,10 @@ class HipEngine : public IEngine {
   Error EvalQuestionRedundancyFromWeights(int64_t nSources, const int64_t *pSources, const void *pWeights, double *pOut, int64_t n) override;
   Error ListRedundantQuestionsFromWeights(int64_t nSources, const int64_t *pSources, const void *pWeights, int64_t maxCount, CiRatedQuestion *pDest,
                                           int64_t *pCounts) override;
+  // ... and questions that tell listed targets apart (sep(G, q)): Eval / List on a whole engine AND on such a shard, for its own questions
+  Error EvalTargetSeparation(int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets, double *pOut, int64_t n) override;
+  Error ListSeparatingQuestionsBatch(int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets, int64_t maxCount, CiRatedQuestion *pDest,
+                                     int64_t *pCounts) override;
 
   // ---- what a sharded engine needs from its shards (sharded_engine.cpp; implemented in hip_engine_shard.cpp)
   // An answer of a quiz as the sharded engine hands it to EVERY shard: the answered question in global numbering; for the shards
@@ -726,13 +730,17 @@ class HipEngine : public IEngine {
   Error AmongLocked(AmongForm form, int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const int64_t *pQuestions, const uint64_t *pRnd,
                     double *pPriorities, CiHipSelection *pSel, int64_t *pPicked);
   uint64_t _amongCalls = 0, _amongPairs = 0;   // read-only "among_calls", "among_pairs"
-  // ---- The source queries (hip_engine_sources.cpp): two families over one skeleton.  A family's stage: the engine's own package of a
+  // ---- The source queries (hip_engine_sources.cpp): three families over one skeleton.  A family's stage: the engine's own package of a
   // whole engine's calls (also where a host package is staged), the rows, the family's scratch, the slots that show the rows to the
   // question listing, the listing's pinned lines (records | counts), the host copy of listings beyond 256 records, the events of option
   // "time_sweeps" around a whole engine's sweeps, the counters.  The buffers grow and never shrink.  The entries (argument checks, lock,
-  // refusals in the one order, chunks of kMaxBatch sources), their steps under the lock, and SourceRowsLocked, which a family does its own way:
+  // refusals in the one order, chunks of kMaxBatch sources), their steps under the lock, and SourceRowsLocked, which a family does its own way.
+  // The third family's sources are GROUPS of targets (separation): pGroupCounts beside pSources, which then holds the groups' targets one
+  // after another; it has no package -- its "pack" stages a chunk's groups and tiles on the device --, so it has no pack / from-package
+  // calls and works on a shard directly.
   struct SourceStage {
-    const bool questions;   // sources and results are questions (redundancy); otherwise targets (similarity)
+    const bool questions;   // the results are questions (redundancy, separation); otherwise targets (similarity)
+    const bool groups;      // a source is a group of targets (separation); otherwise one id of the results' kind
     uint64_t &calls, &sources, &deviceNs;
     double *dPackage = nullptr, *dRows = nullptr, *dScratch[2] = {nullptr, nullptr};
     size_t packageBytes = 0, rowsBytes = 0, scratchBytes[2] = {0, 0};
@@ -740,20 +748,30 @@ class HipEngine : public IEngine {
     ResultLines lines;
     std::vector<double> rows;
     hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<int64_t> offsets;               // groups: where a group's entries begin in the call's pSources, [nSources + 1]
+    const int64_t *dGroupStart = nullptr, *dTileGroup = nullptr, *dTileWidth = nullptr, *dEntries = nullptr;   // ... the staged chunk (in _dAqs) ...
+    int64_t nTiles = 0;                                                                  // ... and its tiles (kb_plan.h: PlanGroupTiles)
   };
   uint64_t _simCalls = 0, _simSources = 0, _simDeviceNs = 0, _redCalls = 0, _redSources = 0, _redDeviceNs = 0;   // read-only "similarity_calls", "..._sources", "..._device_ns", "redundancy_calls", ...
-  SourceStage _sim{false, _simCalls, _simSources, _simDeviceNs}, _red{true, _redCalls, _redSources, _redDeviceNs};
+  uint64_t _sepCalls = 0, _sepGroups = 0, _sepDeviceNs = 0;                                                      // ... "separation_calls", "separation_groups", "separation_device_ns"
+  SourceStage _sim{false, false, _simCalls, _simSources, _simDeviceNs}, _red{true, false, _redCalls, _redSources, _redDeviceNs},
+      _sep{true, true, _sepCalls, _sepGroups, _sepDeviceNs};
   int64_t PackagePitch() const { return RoundLdT(_T, 8); }                 // doubles of a similarity slot (PosteriorSlotBytes() / 8), of a row of a question-weight slot
   int64_t RedRowPitch() const { return (_Q + 15) & ~(int64_t)15; }         // doubles of a row of redundancy results
   int64_t SourceRowPitch(const SourceStage &st) const { return st.questions ? RedRowPitch() : PackagePitch(); }
-  int64_t SourceSlotDoubles(const SourceStage &st) const { return (st.questions ? _K : 1) * PackagePitch(); }
-  Error EvalSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, double *pOut, int64_t n);
-  Error ListSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts);
+  int64_t SourceSlotDoubles(const SourceStage &st) const { return st.groups ? 0 : (st.questions ? _K : 1) * PackagePitch(); }
+  // (pGroupCounts: the groups family's counts, nullptr for the others)
+  Error EvalSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pGroupCounts, const int64_t *pSources, double *pOut, int64_t n);
+  Error ListSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pGroupCounts, const int64_t *pSources, int64_t maxCount, RatedTargetDev *pDest,
+                    int64_t *pCounts);
   Error PackSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
   Error EvalSourcesFromPackage(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, const void *pPackage, double *pOut, int64_t n);
   Error ListSourcesFromPackage(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, const void *pPackage, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts);
   Error AdmitSourcesLocked(const SourceStage &st, const char *call, bool wholeOnly, int64_t rowLength, int64_t n, const int64_t *pSources) const;
+  Error AdmitGroupsLocked(const char *call, int64_t rowLength, int64_t n, const int64_t *pGroupCounts, const int64_t *pTargets) const;
   Error PackSourcesLocked(SourceStage &st, int64_t n, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue);
+  static void GroupOffsets(SourceStage &st, int64_t nGroups, const int64_t *pGroupCounts);   // st.offsets of a call
+  Error StageGroupsLocked(SourceStage &st, int64_t first, int64_t n, const int64_t *pTargets);   // the groups family's "pack": groups [first, first + n) of st.offsets
   Error StageSourcesLocked(SourceStage &st, int64_t n, const int64_t *pSources, const void *pPackage, const double **dPackage);
   Error SourceRowsOutLocked(SourceStage &st, int64_t n, double *pOut, int64_t rowLength);   // (synchronises the stream)
   Error ListSourcesLocked(SourceStage &st, int64_t n, const double *dPackage, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts);

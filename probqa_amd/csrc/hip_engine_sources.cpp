@@ -1,10 +1,14 @@
-// hip_engine_sources.cpp -- HipEngine: the source queries (hip_engine.h: SourceStage; include/PqaHipExt.h), two families over one skeleton.
+// hip_engine_sources.cpp -- HipEngine: the source queries (hip_engine.h: SourceStage; include/PqaHipExt.h), three families over one skeleton.
 // Target similarity -- EvalTargetSimilarity, ListSimilarTargetsBatch, and the pair for shards that processes of their own drive,
 // PackTargetSimilaritySums / ListSimilarTargetsFromSums: sim(s, t) = (sum over the questions of the WHOLE knowledge base that are not
 // gaps of sum_k sqrt(p_qk(s) p_qk(t))) / nValidQuestions, p_qk(t) = A[q][k][t] / D[q][t]: 1 for targets no quiz can tell apart.
 // Question redundancy -- EvalQuestionRedundancy, ListRedundantQuestionsBatch, PackQuestionWeights / EvalQuestionRedundancyFromWeights /
 // ListRedundantQuestionsFromWeights: I(s, q), the mutual information in bits between the answers to questions s and q for a target
 // drawn from vB, over the K x K table J[k][k'] = sum_t (w[t] p_sk(t)) p_qk'(t).
+// Target separation -- EvalTargetSeparation, ListSeparatingQuestionsBatch: sep(G, q), the Jensen-Shannon divergence in bits of the answer
+// distributions of a GROUP G of 2 .. 64 listed targets at question q, equal weights.  A value needs the group's columns of q's block and
+// nothing else: there is no package, the family's "pack" (StageGroupsLocked) stages a chunk's groups and the sweep's tiles on the device,
+// and a shard that a process of its own drives answers for its own questions directly.
 // One code path per family: PackSourcesLocked enqueues, per up to 256 sources, this engine's part of a package; SourceRowsLocked turns
 // a package -- the engine's own, or the ranks' summed one -- into rows on the device; ListSourcesLocked lists them on the device, or
 // copies them and takes the prefix here beyond 256 records.  A whole engine's Eval and List are pack -> rows and pack -> list, in
@@ -18,8 +22,8 @@ namespace pqa {
 namespace {
 // What does not need the engine: the counts, the `limit` of sources of the pack / from-package calls (0: none), the buffers, and the
 // package's alignment (nullptr where a call has none).
-Error SourceArgs(int64_t nSources, int64_t maxCount, int64_t limit, bool haveBuffers, const char *nullText, const void *package) {
-  if (nSources < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(nSources), "|nSources| must be non-negative.");
+Error SourceArgs(int64_t nSources, int64_t maxCount, int64_t limit, bool haveBuffers, const char *nullText, const void *package, const char *countName = "nSources") {
+  if (nSources < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(nSources), std::string("|") + countName + "| must be non-negative.");
   if (maxCount < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(maxCount), "|maxCount| must be non-negative.");
   if (limit > 0 && nSources > limit) return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(nSources, 0, limit), "Batch size is out of range.");
   if (nSources > 0 && !haveBuffers) return Error::Make(ErrCode::NullArgument, nullText);
@@ -53,6 +57,59 @@ Error HipEngine::AdmitSourcesLocked(const SourceStage &st, const char *call, boo
   return Error();
 }
 
+// The groups family's refusals under the lock, in its one order: a group's count, a target, the row length (rowLength >= 0), shutdown.
+Error HipEngine::AdmitGroupsLocked(const char *call, int64_t rowLength, int64_t n, const int64_t *pGroupCounts, const int64_t *pTargets) const {
+  for (int64_t g = 0; g < n; g++)
+    if (pGroupCounts[g] < 2 || pGroupCounts[g] > kSepMaxGroup)
+      return Error::MakeP(ErrCode::IndexOutOfRange, "entry=" + std::to_string(g) + " count=" + std::to_string(pGroupCounts[g]) + " " + RangeParams(pGroupCounts[g], 2, kSepMaxGroup),
+                          "A group's target count is out of range.");
+  for (int64_t g = 0, at = 0; g < n; g++)
+    for (int64_t j = 0; j < pGroupCounts[g]; j++, at++)
+      if (pTargets[at] < 0 || pTargets[at] >= _T)
+        return Error::MakeP(ErrCode::IndexOutOfRange,
+                            "entry=" + std::to_string(g) + " member=" + std::to_string(j) + " targetId=" + std::to_string(pTargets[at]) + " " + RangeParams(pTargets[at], 0, _T - 1),
+                            "A group's target is out of range.");
+  if (rowLength >= 0 && rowLength != _Q)
+    return Error::MakeP(ErrCode::IndexOutOfRange, RangeParams(rowLength, _Q, _Q), "Separation row length must equal the question count.");
+  if (_mode == Mode::Shutdown) return Error::MakeP(ErrCode::ObjectShutDown, std::string("RejectedOperation=") + call, "Engine is shut down.");
+  return Error();
+}
+
+// Groups [first, first + n) of the call (st.offsets: where their entries begin in pTargets) onto the device, through the pack list: the
+// groups' starts within the chunk | the first group of every tile of the sweep (kb_plan.h: PlanGroupTiles, whole groups) | per tile the
+// power of two that holds its longest group | the entries.
+// They stay in _dAqs + 2 for the launches behind this one.
+Error HipEngine::StageGroupsLocked(SourceStage &st, int64_t first, int64_t n, const int64_t *pTargets) {
+  hipSetDevice(_device);
+  if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
+  const int64_t *off = st.offsets.data() + first, e0 = off[0], nEntries = off[n] - e0;
+  std::vector<int64_t> counts((size_t)n);
+  for (int64_t g = 0; g < n; g++) counts[(size_t)g] = off[g + 1] - off[g];
+  const std::vector<int64_t> tiles = PlanGroupTiles(n, counts.data(), kSepTileEntries, kSepTileGroups);
+  const int64_t nTiles = (int64_t)tiles.size() - 1;
+  const int64_t words = 2 + (n + 1) + (nTiles + 1) + nTiles + nEntries;   // {arrival counter, pad}, then the four lists
+  const Error err = EnsurePackList(words);
+  if (!err.ok()) return err;
+  int64_t *w = _hPack + 2;
+  for (int64_t g = 0; g <= n; g++) *w++ = off[g] - e0;
+  for (int64_t t : tiles) *w++ = t;
+  for (int64_t t = 0; t < nTiles; t++) {
+    int64_t width = 2;
+    for (int64_t g = tiles[(size_t)t]; g < tiles[(size_t)t + 1]; g++)
+      while (width < counts[(size_t)g]) width *= 2;
+    *w++ = width;
+  }
+  std::memcpy(w, pTargets + e0, (size_t)nEntries * sizeof(int64_t));
+  MarkStreamBusy();
+  st.dGroupStart = _dAqs + 2;
+  st.dTileGroup = st.dGroupStart + (n + 1);
+  st.dTileWidth = st.dTileGroup + (nTiles + 1);
+  st.dEntries = st.dTileWidth + nTiles;
+  st.nTiles = nTiles;
+  st.sources += (uint64_t)n;
+  return SubmitPackList(words);
+}
+
 // This engine's part of the package of up to kMaxBatch validated sources, into the slots at pDst: enqueued, nothing waited for --
 // except where a scratch buffer has to grow, and that the pinned list is not rewritten while an earlier call's copy of it is under
 // way.  The sources stay in _dAqs + 2 for the launches behind this one.  Similarity: the sums over THIS engine's questions, slots of
@@ -82,11 +139,14 @@ Error HipEngine::PackSourcesLocked(SourceStage &st, int64_t n, const int64_t *pS
 
 // rows[i][SourceRowPitch(st)] of the n sources in _dAqs + 2 from the package at dPackage (device-visible), on the engine's stream.
 // Similarity: the sums divided by the questions of the WHOLE knowledge base that are not gaps, the gap targets zeroed; redundancy: the
-// sweep of this engine's questions against the weighted rows.
+// sweep of this engine's questions against the weighted rows; separation: the gathering sweep of this engine's questions over the staged
+// groups (no package).
 Error HipEngine::SourceRowsLocked(SourceStage &st, int64_t n, const double *dPackage, bool zeroSelf) {
   const KbView kb = View();
   HIP_TRY(GrowDevice(&st.dRows, st.rowsBytes, (size_t)n * (size_t)SourceRowPitch(st) * sizeof(double)));
-  if (st.questions) {
+  if (st.groups) {
+    HIP_TRY(LaunchSeparationSweep(kb, st.dGroupStart, st.dTileGroup, st.dTileWidth, st.dEntries, n, st.nTiles, st.dRows, RedRowPitch(), _stream));
+  } else if (st.questions) {
     HIP_TRY(GrowDevice(&st.dScratch[0], st.scratchBytes[0], RedundancyTableBytes(kb)));   // the generic sweep's tables
     HIP_TRY(LaunchRedundancySweep(kb, dPackage, PackagePitch(), _dAqs + 2, n, _qFirst, zeroSelf, st.dRows, RedRowPitch(), st.dScratch[0], _stream));
   } else {
@@ -116,7 +176,7 @@ Error HipEngine::SourceRowsOutLocked(SourceStage &st, int64_t n, double *pOut, i
 
 // The listing of up to kMaxBatch sources (on the device: _dAqs + 2) from a package (device-visible), maxCount > 0: at most 256 records
 // a source on the device -- similarity: the batched target listing over the rows as posteriors (kb_kernels.hip: LaunchTopTargetsBatch);
-// redundancy: the question listing over slots that show it the rows (LaunchRedundancySlots, LaunchTopQuestions) --, beyond that the
+// redundancy and separation: the question listing over slots that show it the rows (LaunchRedundancySlots, LaunchTopQuestions) --, beyond that the
 // rows copied and the prefix taken here in the same order: value descending, id ascending; the source itself, the gaps and what is
 // not > 0 are no candidates (zeros in the rows).  GLOBAL ids.
 Error HipEngine::ListSourcesLocked(SourceStage &st, int64_t n, const double *dPackage, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts) {
@@ -157,20 +217,28 @@ Error HipEngine::ListSourcesLocked(SourceStage &st, int64_t n, const double *dPa
   return Error();
 }
 
-Error HipEngine::EvalSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) {
-  Error err = SourceArgs(nSources, 0, 0, pSources && pOut, st.questions ? "Nullptr is passed in place of the sources or the redundancy buffer."
-                                                                             : "Nullptr is passed in place of the sources or the similarity buffer.", nullptr);
+// (the groups family: sources [first, first + m) of a chunk are GROUPS, their targets in pSources from st.offsets[first])
+void HipEngine::GroupOffsets(SourceStage &st, int64_t nGroups, const int64_t *pGroupCounts) {
+  st.offsets.assign((size_t)nGroups + 1, 0);
+  for (int64_t g = 0; g < nGroups; g++) st.offsets[(size_t)g + 1] = st.offsets[(size_t)g] + pGroupCounts[g];
+}
+
+Error HipEngine::EvalSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pGroupCounts, const int64_t *pSources, double *pOut, int64_t n) {
+  Error err = st.groups ? SourceArgs(nSources, 0, 0, pGroupCounts && pSources && pOut, "Nullptr is passed in place of the groups or the separation buffer.", nullptr, "nGroups")
+                        : SourceArgs(nSources, 0, 0, pSources && pOut, st.questions ? "Nullptr is passed in place of the sources or the redundancy buffer."
+                                                                                      : "Nullptr is passed in place of the sources or the similarity buffer.", nullptr);
   if (!err.ok()) return err;
   CallScope scope(_activeCallers);
   std::lock_guard<EngineMutex> lk(_mu);
-  err = AdmitSourcesLocked(st, call, true, n, nSources, pSources);
+  err = st.groups ? AdmitGroupsLocked(call, n, nSources, pGroupCounts, pSources) : AdmitSourcesLocked(st, call, true, n, nSources, pSources);
   if (!err.ok() || nSources == 0) return err;
   st.calls++;
+  if (st.groups) GroupOffsets(st, nSources, pGroupCounts);
   HIP_TRY(GrowDevice(&st.dPackage, st.packageBytes, (size_t)(std::min<int64_t>(nSources, kMaxBatch) * SourceSlotDoubles(st)) * sizeof(double)));
   for (int64_t first = 0; first < nSources; first += kMaxBatch) {
     const int64_t m = std::min<int64_t>(kMaxBatch, nSources - first);
     TimerStart(st.ev);
-    err = PackSourcesLocked(st, m, pSources + first, st.dPackage, nullptr, 0);
+    err = st.groups ? StageGroupsLocked(st, first, m, pSources) : PackSourcesLocked(st, m, pSources + first, st.dPackage, nullptr, 0);
     if (err.ok()) err = SourceRowsLocked(st, m, st.dPackage, false);
     if (!err.ok()) return err;
     TimerStop(st.ev, st.deviceNs);   // (the copy behind it synchronises the stream)
@@ -181,23 +249,26 @@ Error HipEngine::EvalSources(SourceStage &st, const char *call, int64_t nSources
   return Error();
 }
 
-Error HipEngine::ListSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pSources, int64_t maxCount, RatedTargetDev *pDest, int64_t *pCounts) {
-  Error err = SourceArgs(nSources, maxCount, 0, pSources && pCounts && (maxCount == 0 || pDest), kNullBatch, nullptr);
+Error HipEngine::ListSources(SourceStage &st, const char *call, int64_t nSources, const int64_t *pGroupCounts, const int64_t *pSources, int64_t maxCount,
+                             RatedTargetDev *pDest, int64_t *pCounts) {
+  Error err = SourceArgs(nSources, maxCount, 0, (!st.groups || pGroupCounts) && pSources && pCounts && (maxCount == 0 || pDest), kNullBatch, nullptr,
+                         st.groups ? "nGroups" : "nSources");
   if (!err.ok()) return err;
   CallScope scope(_activeCallers);
   std::lock_guard<EngineMutex> lk(_mu);
-  err = AdmitSourcesLocked(st, call, true, -1, nSources, pSources);
+  err = st.groups ? AdmitGroupsLocked(call, -1, nSources, pGroupCounts, pSources) : AdmitSourcesLocked(st, call, true, -1, nSources, pSources);
   if (!err.ok() || nSources == 0) return err;
   st.calls++;
+  if (st.groups) GroupOffsets(st, nSources, pGroupCounts);
   for (int64_t i = 0; i < nSources; i++) pCounts[i] = 0;
   if (maxCount == 0) return Error();
   HIP_TRY(GrowDevice(&st.dPackage, st.packageBytes, (size_t)(std::min<int64_t>(nSources, kMaxBatch) * SourceSlotDoubles(st)) * sizeof(double)));
   for (int64_t first = 0; first < nSources; first += kMaxBatch) {
     const int64_t m = std::min<int64_t>(kMaxBatch, nSources - first);
     TimerStart(st.ev);
-    err = PackSourcesLocked(st, m, pSources + first, st.dPackage, nullptr, 0);
+    err = st.groups ? StageGroupsLocked(st, first, m, pSources) : PackSourcesLocked(st, m, pSources + first, st.dPackage, nullptr, 0);
     if (!err.ok()) return err;
-    // "similarity_device_ns" covers the pack; "redundancy_device_ns" the pack, the sweep and the listing (the stream has been synchronised)
+    // "similarity_device_ns" covers the pack; "redundancy_device_ns" and "separation_device_ns" the pack, the sweep and the listing (the stream has been synchronised)
     if (!st.questions) TimerStop(st.ev, st.deviceNs);
     err = ListSourcesLocked(st, m, st.dPackage, maxCount, pDest + first * maxCount, pCounts + first);
     if (!err.ok()) return err;
@@ -254,10 +325,10 @@ Error HipEngine::ListSourcesFromPackage(SourceStage &st, const char *call, int64
 
 // ---- the C ABI's entries ----------------------------------------------------------------------------------------------------------------
 Error HipEngine::EvalTargetSimilarity(int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) {
-  return EvalSources(_sim, "EvalTargetSimilarity", nSources, pSources, pOut, n);
+  return EvalSources(_sim, "EvalTargetSimilarity", nSources, nullptr, pSources, pOut, n);
 }
 Error HipEngine::ListSimilarTargetsBatch(int64_t nSources, const int64_t *pSources, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) {
-  return ListSources(_sim, "ListSimilarTargetsBatch", nSources, pSources, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
+  return ListSources(_sim, "ListSimilarTargetsBatch", nSources, nullptr, pSources, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
 }
 Error HipEngine::PackTargetSimilaritySums(int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue) {
   return PackSources(_sim, "PackTargetSimilaritySums", nSources, pSources, pDst, pFlag, flagValue);
@@ -266,10 +337,10 @@ Error HipEngine::ListSimilarTargetsFromSums(int64_t nSources, const int64_t *pSo
   return ListSourcesFromPackage(_sim, "ListSimilarTargetsFromSums", nSources, pSources, pSums, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
 }
 Error HipEngine::EvalQuestionRedundancy(int64_t nSources, const int64_t *pSources, double *pOut, int64_t n) {
-  return EvalSources(_red, "EvalQuestionRedundancy", nSources, pSources, pOut, n);
+  return EvalSources(_red, "EvalQuestionRedundancy", nSources, nullptr, pSources, pOut, n);
 }
 Error HipEngine::ListRedundantQuestionsBatch(int64_t nSources, const int64_t *pSources, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) {
-  return ListSources(_red, "ListRedundantQuestionsBatch", nSources, pSources, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
+  return ListSources(_red, "ListRedundantQuestionsBatch", nSources, nullptr, pSources, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
 }
 Error HipEngine::PackQuestionWeights(int64_t nSources, const int64_t *pSources, void *pDst, void *pFlag, uint64_t flagValue) {
   return PackSources(_red, "PackQuestionWeights", nSources, pSources, pDst, pFlag, flagValue);
@@ -280,6 +351,13 @@ Error HipEngine::EvalQuestionRedundancyFromWeights(int64_t nSources, const int64
 Error HipEngine::ListRedundantQuestionsFromWeights(int64_t nSources, const int64_t *pSources, const void *pWeights, int64_t maxCount, CiRatedQuestion *pDest,
                                                    int64_t *pCounts) {
   return ListSourcesFromPackage(_red, "ListRedundantQuestionsFromWeights", nSources, pSources, pWeights, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
+}
+Error HipEngine::EvalTargetSeparation(int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets, double *pOut, int64_t n) {
+  return EvalSources(_sep, "EvalTargetSeparation", nGroups, pGroupCounts, pTargets, pOut, n);
+}
+Error HipEngine::ListSeparatingQuestionsBatch(int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets, int64_t maxCount, CiRatedQuestion *pDest,
+                                              int64_t *pCounts) {
+  return ListSources(_sep, "ListSeparatingQuestionsBatch", nGroups, pGroupCounts, pTargets, maxCount, reinterpret_cast<RatedTargetDev *>(pDest), pCounts);
 }
 
 }  // namespace pqa

@@ -167,6 +167,25 @@ inline int64_t RatedPrefix(const double *v, int64_t n, int64_t want, Eligible el
   return c;
 }
 
+// The tiles of the separation sweep (separation_kernels.hip) over the groups of a launch, counts[g] entries each: a tile is a run of
+// whole groups -- a group is never split -- with at most maxEntries entries and at most maxGroups groups, filled in order; a group
+// longer than maxEntries (the callers admit none) gets a tile of its own.  -> the first group of every tile and nGroups behind them:
+// nTiles + 1 words, {0} for no groups.
+inline std::vector<int64_t> PlanGroupTiles(int64_t nGroups, const int64_t *counts, int64_t maxEntries, int64_t maxGroups) {
+  std::vector<int64_t> tileGroup{0};
+  int64_t entries = 0;
+  for (int64_t g = 0; g < nGroups; g++) {
+    const int64_t first = tileGroup.back();
+    if (g > first && (entries + counts[g] > maxEntries || g - first >= maxGroups)) {
+      tileGroup.push_back(g);
+      entries = 0;
+    }
+    entries += counts[g];
+  }
+  if (nGroups > 0) tileGroup.push_back(nGroups);
+  return tileGroup;
+}
+
 // Where the arrays of a .kb file lie (layout: hip_engine_kb.cpp), in bytes from the file's start, and where the rows of a window of
 // questions [qFirst, qFirst + nLocal) lie within them: a shard seeks to its two blocks instead of reading through the others'.
 //   header 40 | sA [Q][K][T] | mD [Q][T] | vB [T] | trailer

@@ -747,4 +747,15 @@ hipError_t LaunchRedundancySweep(const KbView &kb, const double *weights, int64_
                                  double *rows, int64_t rowPitch, double *tables, hipStream_t stream);
 hipError_t LaunchRedundancySlots(QuizSlot *slots, double *rows, int64_t rowPitch, const uint32_t *qgap, int64_t nSources, hipStream_t stream);
 
+// Target separation (separation_kernels.hip): sep(G, q), the Jensen-Shannon divergence in bits of the answer distributions of the
+// targets of a group G at a question q of this cube, equal weights, in fp64 whatever the cube's element type.
+//   LaunchSeparationSweep: rows[g][rowPitch], column j = sep(group g, question j) for the nGroups (<= kTopBatchQuizzes) groups staged on
+//     the device as groupStart[nGroups + 1] | tileGroup[nTiles + 1] | tileWidth[nTiles] | entries (ids in [0, T), 2 .. kSepMaxGroup a
+//     group): 0 for a gap question and for a group with a gap member -- the rows the listing takes.  The tiles are kb_plan.h's
+//     PlanGroupTiles over kSepTileEntries and kSepTileGroups: runs of whole groups; a tile's width is a power of two that holds its
+//     longest group (it sets how many groups a wave reduces side by side, not a bit of any value).
+constexpr int kSepMaxGroup = 64, kSepTileEntries = 256, kSepTileGroups = 128;
+hipError_t LaunchSeparationSweep(const KbView &kb, const int64_t *groupStart, const int64_t *tileGroup, const int64_t *tileWidth, const int64_t *entries,
+                                 int64_t nGroups, int64_t nTiles, double *rows, int64_t rowPitch, hipStream_t stream);
+
 }  // namespace pqa

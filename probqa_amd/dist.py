@@ -720,6 +720,30 @@ def list_redundant_questions_batch(engine, sources, max_count: int, rank: int, w
                                       lambda listed: _gather_top(listed, max_count, group, device))
 
 
+# ---- questions that tell listed targets apart, over the shards ---------------------------------------------------------------------
+# The separation of a group at a question needs the group's columns of that question's block and nothing else, and every rank holds its
+# questions' blocks whole: there is no package and nothing to sum.  Every rank lists its own questions, one status word keeps the ranks
+# in step, and the lists are all-gathered and merged as list_top_questions merges.
+
+
+def list_separating_questions_batch(engine, groups, max_count: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                                    device: Optional[torch.device] = None) -> List[List[Tuple[int, float]]]:
+    """PqaEngine_ListSeparatingQuestionsBatch on the shards of `world` ranks: a collective every rank calls with the same groups of
+    targets and max_count; any number of groups.  Every rank returns the same (GLOBAL question, bits) records.  All or none: a rank
+    whose call is refused still takes part in the status word, after which every rank raises the first failing rank's text."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    groups = [[int(t) for t in g] for g in groups]
+    error, listed = None, None
+    try:
+        listed = engine.list_separating_questions_batch(groups, max_count)
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)
+    return _gather_top(listed, max_count, group, device)
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

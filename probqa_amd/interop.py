@@ -186,6 +186,8 @@ HIP_EXPORTS = {
     "PqaHip_PackQuestionWeights": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
     "PqaEngine_EvalQuestionRedundancyFromWeights": (_vp, [_vp, _i64, _pi64, _vp, _pdbl, _i64]),
     "PqaEngine_ListRedundantQuestionsFromWeights": (_vp, [_vp, _i64, _pi64, _vp, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
+    "PqaEngine_EvalTargetSeparation": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl, _i64]),
+    "PqaEngine_ListSeparatingQuestionsBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1143,6 +1145,35 @@ class PqaEngine:
         """list_redundant_questions_batch over the questions THIS engine holds from the summed package at device-visible address
         `ptr`; GLOBAL ids.  The ranks' lists are merged by dist.merge_top_questions."""
         return self._list_batch(_lib.PqaEngine_ListRedundantQuestionsFromWeights, CiRatedQuestion, _pair, sources, max_count, ctypes.c_void_p(ptr or None))
+
+    # ---- questions that tell listed targets apart (include/PqaHipExt.h: PqaEngine_EvalTargetSeparation and its neighbour) ----
+    @staticmethod
+    def _groups(groups) -> Tuple[np.ndarray, np.ndarray]:
+        """(counts, targets one group after another) of a list of groups of targets, as the separation calls take them"""
+        lens = np.array([len(g) for g in groups], dtype=np.int64)
+        flat = np.concatenate([np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]) if len(groups) and lens.sum() else np.zeros(0, dtype=np.int64)
+        return np.ascontiguousarray(np.append(lens, 0)), np.ascontiguousarray(np.append(flat, 0))   # (never empty: a pointer to pass)
+
+    def eval_target_separation(self, groups) -> np.ndarray:
+        """sep(groups[g], q) for every question q THIS engine holds as a [G, local questions] array (column j: question q_first + j): the
+        Jensen-Shannon divergence in bits of the answer distributions of the group's 2 .. 64 targets (a repeated id counts twice) under
+        equal weights -- 0 where they answer alike and at gaps, log2 n where no two share an answer; a row of zeros for a group with a
+        gap member.  Reads only the knowledge base: regular and maintenance mode, whole engines and shards."""
+        counts, targets = self._groups(groups)
+        q = self.get_option("local_questions")
+        out = np.zeros((len(groups), q), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalTargetSeparation(self.c_engine, len(groups), counts.ctypes.data_as(_pi64), targets.ctypes.data_as(_pi64), _dptr(out), q))
+        return out
+
+    def list_separating_questions_batch(self, groups, max_count: int) -> List[List[Tuple[int, float]]]:
+        """Per group the questions THIS engine holds that tell its targets apart best as (question, bits), the gaps and what separates
+        nothing left out: bits descending, question id ascending among equal values; GLOBAL ids; the values are
+        eval_target_separation's bits.  Any number of groups."""
+        counts, targets = self._groups(groups)
+        return self._list_batch(_lib.PqaEngine_ListSeparatingQuestionsBatch, CiRatedQuestion, _pair, counts[:-1], max_count, targets.ctypes.data_as(_pi64))
+
+    def list_separating_questions(self, targets, max_count: int) -> List[Tuple[int, float]]:
+        return self.list_separating_questions_batch([list(targets)], max_count)[0]
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):

@@ -1,0 +1,56 @@
+"""No-GPU checks that the two target-separation calls -- PqaEngine_EvalTargetSeparation, PqaEngine_ListSeparatingQuestionsBatch -- are part
+of the boundary: declared in include/PqaHipExt.h, bound in probqa_amd/interop.py with as many argument types, exported by the built
+libPqaCore.so, with their Python methods and the collective of probqa_amd/dist.py."""
+import inspect
+
+import pytest
+
+import abi_common as abi
+from probqa_amd import dist as pdist
+from probqa_amd import interop
+
+ARGS = {
+    "PqaEngine_EvalTargetSeparation": 6,
+    "PqaEngine_ListSeparatingQuestionsBatch": 7,
+}
+
+
+def params(name, returns=r"void\s*\*"):
+    return [a.strip() for a in abi.header_params(name, returns).split(",")]
+
+
+@pytest.mark.parametrize("name", sorted(ARGS))
+def test_header_declares_the_call(name):
+    args = params(name)
+    assert len(args) == ARGS[name], args
+    assert args[:4] == ["void *pvEngine", "int64_t nGroups", "const int64_t *pGroupCounts", "const int64_t *pTargets"], args
+
+
+def test_header_argument_kinds():
+    ev = params("PqaEngine_EvalTargetSeparation")
+    assert ev[4] == "double *pOut" and ev[5] == "int64_t n", ev
+    ls = params("PqaEngine_ListSeparatingQuestionsBatch")
+    assert ls[4] == "int64_t maxCount" and ls[5] == "CiRatedQuestion *pDest" and ls[6] == "int64_t *pCounts", ls
+
+
+@pytest.mark.parametrize("name", sorted(ARGS))
+def test_binding_carries_the_call(name):
+    _, argtypes = abi.bound_as(name)
+    assert len(argtypes) == ARGS[name]
+
+
+def test_python_methods_present():
+    for m in ("eval_target_separation", "list_separating_questions_batch", "list_separating_questions"):
+        assert callable(getattr(interop.PqaEngine, m, None)), m
+    assert list(inspect.signature(interop.PqaEngine.eval_target_separation).parameters) == ["self", "groups"]
+    assert list(inspect.signature(interop.PqaEngine.list_separating_questions_batch).parameters) == ["self", "groups", "max_count"]
+    assert list(inspect.signature(interop.PqaEngine.list_separating_questions).parameters) == ["self", "targets", "max_count"]
+    assert list(inspect.signature(pdist.list_separating_questions_batch).parameters) == ["engine", "groups", "max_count", "rank", "world", "group", "device"]
+
+
+def test_library_exports_the_calls(factory):
+    exported = abi.exported_symbols()
+    lib = interop.load_library()
+    for name in ARGS:
+        assert name in exported, name
+        assert getattr(lib, name) is not None
