@@ -19,22 +19,11 @@ import pytest
 
 import cases
 import test_gpu_batch as tb
+from deep_cases import LateCase
 from probqa_amd import synth
 from test_gpu_parity import run_script
 
 pytestmark = pytest.mark.gpu
-
-
-class LateCase(cases.Case):
-    """A window of Q questions of the T-question dichotomy cube around `hidden` (question q asks about target q_offset + q)."""
-
-    def __init__(self, name, K, Q, T, seed, hidden, q_offset, **kw):
-        super().__init__(name, K, Q, T, seed, **kw)
-        self.hidden, self.q_offset = hidden, q_offset
-
-    def kb(self):
-        return synth.synthetic_kb(self.K, self.Q, self.T, self.init, self.n_train, self.noise, self.seed,
-                                  q_offset=self.q_offset, q_total=self.T)
 
 
 # (leg, row lengths, engine options)
