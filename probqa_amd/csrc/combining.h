@@ -34,6 +34,13 @@ inline void PublishState(std::atomic<int> *word, int state) {
   FutexWakeOne(word);
 }
 static_assert(sizeof(std::atomic<int>) == sizeof(int), "the state word is slept on as a futex");
+// What the state words hold (plain ints: the word is slept on as a futex).
+// A posted operation's (PostingLock): posted; posted and its thread asleep on this word; done -- the record is its thread's again.
+constexpr int kOpPosted = 0, kOpDone = 1, kOpAsleep = 2;
+// A selection request's (Combiner): waiting; served; the lead handed over -- serve the queue yourself; the sweep is done -- select
+// for yourself, then release one reader of the request's context.
+constexpr int kReqWaiting = 0, kReqServed = 1, kReqLead = 2, kReqSelect = 3;
+enum class SelKind { Argmax, Sampled };   // what a selection request asks for (Sampled: with its random number)
 
 struct CallScope {   // a client thread inside the engine's quiz-level calls
   std::atomic<int> &n;
@@ -46,7 +53,7 @@ struct CallScope {   // a client thread inside the engine's quiz-level calls
 // latency per call, serially.  So a call that finds the lock taken may POST its operation instead (PostAndWait) and sleep on the
 // record's own word; whoever holds the lock runs everything posted so far, in post order, right before it lets go (the owner's
 // `run` over the ordered list) and wakes the posters after releasing.
-// Op: a record with `std::atomic<int> state` (0 posted, 2 posted and its thread asleep on this word, 1 done) and `Op *next`.
+// Op: a record with `std::atomic<int> state` (kOpPosted, kOpAsleep, kOpDone) and `Op *next`.
 template <typename Op, typename Owner>
 class PostingLock {
  public:
@@ -102,7 +109,7 @@ class PostingLock {
   }
   void Publish(Op *op) {   // (the record is its thread's again the moment its state says so: nothing of it is read after)
     std::atomic<int> *word = &op->state;
-    if (word->exchange(1, std::memory_order_acq_rel) == 2) {
+    if (word->exchange(kOpDone, std::memory_order_acq_rel) == kOpAsleep) {
       if (_nWake < 64) _wake[_nWake++] = word;
       else _more.push_back(word);
     }
@@ -126,17 +133,29 @@ void PostAndWait(Lock &lock, Op &op) {
   for (;;) {
     if (lock.try_lock()) lock.unlock();   // (free after all: the release runs it -- and the others')
     for (int spins = 0; spins < 300; spins++) {
-      if (op.state.load(std::memory_order_acquire) == 1) return;
+      if (op.state.load(std::memory_order_acquire) == kOpDone) return;
       _mm_pause();
     }
-    int expected = 0;
-    if (op.state.compare_exchange_strong(expected, 2, std::memory_order_seq_cst) || expected == 2) {
+    int expected = kOpPosted;
+    if (op.state.compare_exchange_strong(expected, kOpAsleep, std::memory_order_seq_cst) || expected == kOpAsleep) {
       // (the timeout is a belt to the braces of unlock(): a millisecond, then the lock is tried again)
       struct timespec ts{0, 1000000};
-      syscall(SYS_futex, reinterpret_cast<int *>(&op.state), FUTEX_WAIT_PRIVATE, 2, &ts, nullptr, 0);
+      syscall(SYS_futex, reinterpret_cast<int *>(&op.state), FUTEX_WAIT_PRIVATE, kOpAsleep, &ts, nullptr, 0);
     }
-    if (op.state.load(std::memory_order_acquire) == 1) return;
+    if (op.state.load(std::memory_order_acquire) == kOpDone) return;
   }
+}
+
+// `op` posted to `lock`'s holder if the lock is taken -- or in any case with `force` -- and run by the time this returns: true.
+// Otherwise false: `lk` holds the lock, and `op` is the caller's to run in whatever form it likes (nothing has seen it).
+template <typename Lock, typename Op>
+bool TryLockOrPost(Lock &lock, std::unique_lock<Lock> &lk, Op &op, bool force = false) {
+  if (!force && lock.try_lock()) {
+    lk = std::unique_lock<Lock>(lock, std::adopt_lock);
+    return false;
+  }
+  PostAndWait(lock, op);
+  return true;
 }
 
 template <typename Op, typename Owner>
@@ -162,27 +181,26 @@ struct CombineCtx {
   std::atomic<bool> inFlight{false};   // a leader's sweep launched and not yet collected
 };
 
-// Req: `int64_t iQuiz` and `std::atomic<int> state` -- 0 waiting, 1 served, 2 lead handed over: serve the queue yourself, 3 the
-// sweep is done: select for yourself, then release one reader of the request's context.  Ctx: derived from CombineCtx.
+// Req: `int64_t iQuiz` and `std::atomic<int> state` (kReqWaiting, kReqServed, kReqLead, kReqSelect).  Ctx: derived from CombineCtx.
 template <typename Req, typename Ctx>
 class Combiner {
  public:
   using Clock = std::chrono::steady_clock;
   explicit Combiner(Ctx *ctx) : _ctx(ctx) {}
 
-  // Queue `r` and wait for its state: 2 at once if nobody leads.  sweepNs: the followers' wait is averaged into it, and with `nap`
+  // Queue `r` and wait for its state: kReqLead at once if nobody leads.  sweepNs: the followers' wait is averaged into it, and with `nap`
   // (fewer clients than CPUs) a follower sleeps most of that expected wait in short naps, then spins; without, a short spin, then
   // the futex (spinning waiters would take the CPUs from the threads that have work).
   int Wait(Req &r, std::atomic<int64_t> *sweepNs = nullptr, bool nap = false) {
     {
       std::lock_guard<std::mutex> lk(_mu);
       _queue.push_back(&r);
-      if (!_leaderActive) { _leaderActive = true; return 2; }
+      if (!_leaderActive) { _leaderActive = true; return kReqLead; }
     }
-    int st = 0;
+    int st = kReqWaiting;
     const auto tw0 = Clock::now();
-    for (int spins = 0; spins < 1500 && (st = r.state.load(std::memory_order_acquire)) == 0; spins++) _mm_pause();
-    if (st == 0 && nap && sweepNs != nullptr) {
+    for (int spins = 0; spins < 1500 && (st = r.state.load(std::memory_order_acquire)) == kReqWaiting; spins++) _mm_pause();
+    if (st == kReqWaiting && nap && sweepNs != nullptr) {
       // (woken through the kernel the clients of one sweep arrive tens of microseconds apart)
       const int64_t expect = sweepNs->load(std::memory_order_relaxed);
       if (expect > 90000) {
@@ -190,15 +208,15 @@ class Combiner {
         if (!slackSet) { prctl(PR_SET_TIMERSLACK, 2000UL, 0, 0, 0); slackSet = true; }
         const auto until = tw0 + std::chrono::nanoseconds(std::min<int64_t>(expect - 50000, 2000000));
         // (in naps of 40 us: the lead may be handed to this request meanwhile, and the next sweep waits for its leader)
-        while ((st = r.state.load(std::memory_order_acquire)) == 0 && Clock::now() < until) {
+        while ((st = r.state.load(std::memory_order_acquire)) == kReqWaiting && Clock::now() < until) {
           struct timespec ts{0, 40000};
           nanosleep(&ts, nullptr);
         }
       }
-      for (int spins = 0; spins < 12000 && (st = r.state.load(std::memory_order_acquire)) == 0; spins++) _mm_pause();
+      for (int spins = 0; spins < 12000 && (st = r.state.load(std::memory_order_acquire)) == kReqWaiting; spins++) _mm_pause();
     }
-    while (st == 0) {
-      FutexWait(&r.state, 0);   // (returns at once if the state is no longer 0)
+    while (st == kReqWaiting) {
+      FutexWait(&r.state, kReqWaiting);   // (returns at once if the state is no longer that)
       st = r.state.load(std::memory_order_acquire);
     }
     if (sweepNs != nullptr) {
@@ -234,7 +252,7 @@ class Combiner {
   // trim(size) -- in the next context, once its previous sweep has been collected and the clients selecting out of it are done.
   // launch(ctx, batch, tPicked) launches it (what could not be launched has its error, or its result); the lead goes on at once;
   // collect(ctx, batch) waits for the sweep and hands the results out (a request told to select for itself through LetSelect
-  // leaves the batch) and returns true if `own` is to select for itself.  Returns `own`'s state: 1 or 3.
+  // leaves the batch) and returns true if `own` is to select for itself.  Returns `own`'s state: kReqServed or kReqSelect.
   template <typename Trim, typename Launch, typename Collect>
   int Lead(Req &own, int64_t maxBatch, Trim &&trim, Launch &&launch, Collect &&collect) {
     Ctx &c = _ctx[_next];
@@ -264,20 +282,20 @@ class Combiner {
     {
       std::lock_guard<std::mutex> lk(_mu);
       if (_queue.empty()) _leaderActive = false;
-      else PublishState(&_queue.front()->state, 2);
+      else PublishState(&_queue.front()->state, kReqLead);
     }
     const bool ownSelects = collect(c, batch);
     ctxLock.unlock();
     for (Req *r : batch)
-      if (r != nullptr && r != &own) PublishState(&r->state, 1);   // (r is its caller's again from here on)
-    return ownSelects ? 3 : 1;
+      if (r != nullptr && r != &own) PublishState(&r->state, kReqServed);   // (r is its caller's again from here on)
+    return ownSelects ? kReqSelect : kReqServed;
   }
 
   // (collect's) `r` is to select for itself out of its context: it is told so now, and leaves the batch -- not the leader's to
   // publish again
   static void LetSelect(std::vector<Req *> &batch, Req *r) {
     for (Req *&slot : batch) if (slot == r) slot = nullptr;
-    PublishState(&r->state, 3);
+    PublishState(&r->state, kReqSelect);
   }
 
  private:

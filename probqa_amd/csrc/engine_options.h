@@ -27,7 +27,7 @@ struct EngineOptions {
   int64_t combine = 1;                // 0 = every call by itself
   int64_t combineSpin = 1;            // 1 = waiting clients spin while they are fewer than the allowed CPUs, 0 = they always sleep
   int64_t lingerUs = 20;              // how long a ListTopTargets waits for the other clients' RecordAnswers before it launches the updates
-  int64_t postAlways = 0;             // test hook: the posted form of RecordAnswer / ListTopTargets even when the engine is free
+  int64_t postAlways = 0;             // test hook: the posted form of every call that can be posted (HipEngine::TakeOrPost) even when the engine is free
   // ---- rows at the pole of the lack term (pole_kernels.hip)
   int64_t poleFix = 1;                // 0: questions with a row at the pole keep the sweep's own sums
   int64_t poleGate = 1;               // a fused single-quiz ARGMAX has only the listed questions redone that can still win (pole_bounds_kernel); 0: every listed question

@@ -676,16 +676,9 @@ int64_t HipEngine::CreateQuiz(Error &err, int64_t nAnswered, const AQ *pAQs, con
 
 int64_t HipEngine::StartQuiz(Error &err) {
   CallScope scope(_activeCallers);
-  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {   // (the engine is taken: the quizzes started meanwhile share ONE launch)
-    PostedOp op;
-    op.kind = 4;
-    PostAndWait(_mu, op);
-    err = op.err;
-    return op.result;
-  }
-  std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else lk.lock();
+  std::unique_lock<EngineMutex> lk;
+  StartQuizOp op;
+  if (TakeOrPost(lk, op)) { err = op.err; return op.result; }   // (the engine is taken: the quizzes started meanwhile share ONE launch)
   return SpeculateFor(CreateQuiz(err, 0, nullptr, nullptr, nullptr, 0, nullptr));
 }
 
@@ -705,16 +698,9 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
     return -1;
   }
   CallScope scope(_activeCallers);
-  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {   // (the engine is taken: the resumes posted meanwhile share ONE launch)
-    PostedOp op;
-    op.kind = 7; op.arg = nAnswered; op.aqs = pAQs;   // (this thread waits for the result: the list stays valid)
-    PostAndWait(_mu, op);
-    err = op.err;
-    return op.result;
-  }
-  std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else lk.lock();
+  std::unique_lock<EngineMutex> lk;
+  ResumeQuizOp op(nAnswered, pAQs);
+  if (TakeOrPost(lk, op)) { err = op.err; return op.result; }   // (the engine is taken: the resumes posted meanwhile share ONE launch)
   if (nAnswered > 0 && ResumeTakesLongRow(View())) {   // long rows: the multi-workgroup form (hip_engine_resume.cpp), as a batch of one
     std::vector<ResumeEntry> e(1);
     e[0].nAnswered = nAnswered;
@@ -728,15 +714,9 @@ int64_t HipEngine::ResumeQuiz(Error &err, int64_t nAnswered, const AQ *pAQs) {
 
 Error HipEngine::ReleaseQuiz(int64_t iQuiz) {
   CallScope scope(_activeCallers);
-  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {
-    PostedOp op;
-    op.kind = 5; op.iQuiz = iQuiz;
-    PostAndWait(_mu, op);
-    return op.err;
-  }
-  std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else lk.lock();
+  std::unique_lock<EngineMutex> lk;
+  ReleaseQuizOp op(iQuiz);
+  if (TakeOrPost(lk, op)) return op.err;
   return ReleaseQuizLocked(iQuiz, true);
 }
 

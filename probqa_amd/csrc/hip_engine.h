@@ -12,6 +12,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdint>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <cstdio>
@@ -586,17 +587,16 @@ class HipEngine : public IEngine {
   // again, passes the lead to the oldest of them.  One request: the single-quiz path, as before.
   struct SelRequest {
     int64_t iQuiz = -1;
-    int kind = 0;                      // 0: argmax, 1: sampled (rnd)
+    SelKind kind = SelKind::Argmax;    // (Sampled: with rnd)
     uint64_t rnd = 0;
     int64_t result = -1;
     Error err;
-    std::atomic<int> state{0};         // 0 waiting, 1 served, 2 lead handed over: serve the queue yourself,
-                                       // 3 the sweep is done: select for yourself from `view` (the leader does not do it for everybody)
-    PriorityView view;                 // state 3: this quiz's priority vector on the host
-    BatchCtx *ctx = nullptr;           // state 3: whose reader count is this request's to release
-    uint64_t serial = 0;               // state 3: the quiz the sweep ran for
-    Quiz *quiz = nullptr;              // state 3: held by inSelection
-    std::vector<uint32_t> unavailable; // state 3: the quiz's asked questions and the gaps as they were when the sweep was launched
+    std::atomic<int> state{kReqWaiting};   // (combining.h) kReqSelect: select for yourself from `view` (the leader does not do it for everybody)
+    PriorityView view;                 // kReqSelect: this quiz's priority vector on the host
+    BatchCtx *ctx = nullptr;           // kReqSelect: whose reader count is this request's to release
+    uint64_t serial = 0;               // kReqSelect: the quiz the sweep ran for
+    Quiz *quiz = nullptr;              // kReqSelect: held by inSelection
+    std::vector<uint32_t> unavailable; // kReqSelect: the quiz's asked questions and the gaps as they were when the sweep was launched
     int64_t nQ = 0, nSub = 0;
   };
   int64_t SelectFromPriorities(SelRequest *r);     // the host-side selector + FinishSelection for one request of a combined sweep
@@ -604,7 +604,7 @@ class HipEngine : public IEngine {
   std::atomic<int64_t> _flushedSinceSweep{0};      // RecordAnswers launched since the newest combined sweep: their clients' NextQuestions are on their way
   std::atomic<int64_t> _sweepNsEwma{0};            // how long a follower of a combined sweep waits for its result (moving average): it sleeps most of that, then spins
   std::atomic<int64_t> _lastCombined{0};           // requests of the newest combined sweep: as many RecordAnswers are about to arrive
-  int64_t Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd);
+  int64_t Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t rnd);
   // ---- posted operations.  With dozens of client threads the engine's lock is not held long but changes hands through the
   // kernel every time: each RecordAnswer and ListTopTargets slept on it and was woken by the thread before it, one wake-up
   // latency per call, serially (64 threads: 200 us inside a RecordAnswer that works for 1).  So a call that finds the lock
@@ -612,30 +612,51 @@ class HipEngine : public IEngine {
   // everything posted so far right before it lets go (combining.h: PostingLock) -- the RecordAnswers of a drain into the list of
   // deferred updates, ONE launch for all the posteriors its ListTopTargets ask for -- and wakes the posters, all at once.
   struct Flight;
-  struct PostedOp {
-    int kind = 0;                      // 1: RecordAnswer(iQuiz, arg = iAnswer, remote); 2: ListTopTargets' launch (arg = maxCount);
-                                       // 3: a leader's LaunchBatch(ctx, batch, flight); 4: StartQuiz (result = the quiz);
-                                       // 5: ReleaseQuiz(iQuiz); 6: RecordQuizTarget(iQuiz, arg = iTarget, amount);
-                                       // 7: ResumeQuiz(arg = nAnswered, aqs) (result = the quiz)
+  struct EngineMutex;
+  enum class OpKind { RecordAnswer, ListTopTargets, LaunchBatch, StartQuiz, ReleaseQuiz, RecordQuizTarget, ResumeQuiz };
+  struct PostedOp {   // (made as one of the records named after the kinds, below: each takes what its kind reads)
+    const OpKind kind;
+    int64_t iQuiz = -1, iAnswer = 0, maxCount = 0, iTarget = 0, nAnswered = 0;
     const AQ *aqs = nullptr;
     double amount = 0;
-    int64_t iQuiz = -1, arg = 0;
     bool remote = false;
+    BatchCtx *ctx = nullptr;
+    std::vector<SelRequest *> *batch = nullptr;
+    Flight *flight = nullptr;
     Error err;
-    int64_t result = 0;                // kind 2: the number of targets to take from `pin` once it carries `flagOp`; -2: take the lock yourself
+    static constexpr int64_t kTakeLockYourself = -2;   // ListTopTargets' result: a list longer than the quiz's lines hold -- the poster's own work
+    int64_t result = 0;                // ListTopTargets: the number of targets to take from `pin` once it carries `flagOp`
     QuizPinned *pin = nullptr;
     uint64_t flagOp = 0;
     Quiz *quiz = nullptr;              // (the drain's own, between its two passes)
     uint64_t serial = 0;
-    BatchCtx *ctx = nullptr;
-    std::vector<SelRequest *> *batch = nullptr;
-    Flight *flight = nullptr;
-    std::atomic<int> state{0};         // 0 posted, 2 posted and its thread asleep on this word, 1 done
+    std::atomic<int> state{kOpPosted};
     PostedOp *next = nullptr;
+   protected:
+    explicit PostedOp(OpKind k) : kind(k) {}
   };
+  struct RecordAnswerOp : PostedOp { RecordAnswerOp(int64_t quiz, int64_t answer, bool rem) : PostedOp(OpKind::RecordAnswer) { iQuiz = quiz; iAnswer = answer; remote = rem; } };
+  struct ListTopTargetsOp : PostedOp { ListTopTargetsOp(int64_t quiz, int64_t count) : PostedOp(OpKind::ListTopTargets) { iQuiz = quiz; maxCount = count; } };   // (the launch)
+  struct LaunchBatchOp : PostedOp { LaunchBatchOp(BatchCtx &c, std::vector<SelRequest *> &b, Flight &f) : PostedOp(OpKind::LaunchBatch) { ctx = &c; batch = &b; flight = &f; } };
+  struct StartQuizOp : PostedOp { StartQuizOp() : PostedOp(OpKind::StartQuiz) {} };   // (result = the quiz)
+  struct ReleaseQuizOp : PostedOp { explicit ReleaseQuizOp(int64_t quiz) : PostedOp(OpKind::ReleaseQuiz) { iQuiz = quiz; } };
+  struct RecordQuizTargetOp : PostedOp { RecordQuizTargetOp(int64_t quiz, int64_t target, double amt) : PostedOp(OpKind::RecordQuizTarget) { iQuiz = quiz; iTarget = target; amount = amt; } };
+  struct ResumeQuizOp : PostedOp { ResumeQuizOp(int64_t n, const AQ *list) : PostedOp(OpKind::ResumeQuiz) { nAnswered = n; aqs = list; } };   // (result = the quiz; the poster waits: the list stays valid)
+  // The way in of every call that can be posted.  True: `op` was posted -- the engine is taken, or option "post_always" -- and its holder has run it.  False: `lk`
+  // holds _mu (without option "combine" always, waited for): the call runs its direct form, which differs from the drained one on purpose (flushes at once, may wait, speculates).
+  bool TakeOrPost(std::unique_lock<EngineMutex> &lk, PostedOp &op) {
+    if (_opt.combine) return TryLockOrPost(_mu, lk, op, _opt.postAlways != 0);
+    lk = std::unique_lock<EngineMutex>(_mu);
+    return false;
+  }
   uint64_t _postedOps = 0, _postedDrains = 0;
-  void DrainPosted(PostedOp *ordered);             // (the engine's lock held: everything posted so far, in post order)
+  void DrainPosted(PostedOp *ordered);             // (the engine's lock held: everything posted so far, in post order) -- in these stages:
+  struct PostedCounts { int64_t trains = 0, starts = 0, resumes = 0; bool needFlush = false; };
+  PostedCounts RunPostedInPlace(PostedOp *ordered);   // RecordAnswer and ReleaseQuiz as they come; the listings validated (needFlush: a deferred update); the rest counted
   void TrainPosted(PostedOp *ordered);             // the drain's RecordQuizTarget calls
+  void StartPosted(PostedOp *ordered);             // its StartQuiz calls: one launch per kStartInline of them
+  void ResumePosted(PostedOp *ordered, int64_t nResumes);
+  void ListPosted(PostedOp *ordered, const Error &flushErr);   // the listings, each record handed back as it is done
   uint64_t _trainBatches = 0, _trainBatchCalls = 0;
   Error ReleaseQuizLocked(int64_t iQuiz, bool mayWait);
   Error RecordQuizTargetLocked(int64_t iQuiz, int64_t iTarget, double amount);
@@ -651,6 +672,7 @@ class HipEngine : public IEngine {
   bool CollectBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flight &f, SelRequest *own);   // true: `own` is to select for itself
   int64_t NextQuestionArgmaxLocked(Error &err, int64_t iQuiz);
   int64_t NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t rnd);
+  int64_t SelectLocked(Error &err, int64_t iQuiz, SelKind kind, uint64_t rnd) { return kind == SelKind::Argmax ? NextQuestionArgmaxLocked(err, iQuiz) : NextQuestionSampledLocked(err, iQuiz, rnd); }
   std::mutex _rngMu;
   uint64_t _quizSerial = 0;
   uint64_t _combBatches = 0, _combRequests = 0, _combMaxBatch = 0;
@@ -904,10 +926,12 @@ class HipEngine : public IEngine {
   // overhead, ListTopTargets, a person reading the question) overlaps with it, and that NextQuestion only waits for the flag.
   // The result is used only if nothing has touched the quiz, the cube, the gaps or the hand-over buffers since (every such
   // operation drops it); the random number of the sampled selector is drawn when NextQuestion is called, as before.
+  // what a speculative sweep leaves: the winner's record in _hPinned->sel; the priority vector in _hHostPriority; the priorities in _dPriority
+  enum class SpecKind { None, ArgmaxRecord, HostPriorities, DevicePriorities };
   struct Speculation {
     Quiz *quiz = nullptr;
     uint64_t priorVersion = 0, tag = 0;
-    int kind = 0;            // 1: argmax record in _hPinned->sel; 2: priority vector in _hHostPriority; 3: priorities in _dPriority
+    SpecKind kind = SpecKind::None;
     int64_t variant = 0;
     hipStream_t stream = nullptr;
     FusedSelect fs{};        // the launch's own arguments: a speculative sweep is launched WITHOUT the pole fix-up behind it (lazyFix) --
@@ -922,7 +946,7 @@ class HipEngine : public IEngine {
   bool Speculate(Quiz *q, int64_t updQuestion = -1, int64_t updAnswer = -1);
   uint64_t _fusedUpdates = 0;   // read-only "fused_updates": RecordAnswers whose update ran inside the sweep's launch (option "fuse_update")
   int64_t SpeculateFor(int64_t iQuiz);
-  int TakeSpeculation(Quiz *q, int kindMask, uint64_t *pTag);
+  SpecKind TakeSpeculation(Quiz *q, std::initializer_list<SpecKind> accepted, uint64_t *pTag);
   void DropSpeculation() {
     if (_spec.quiz != nullptr) { _spec.quiz = nullptr; _specDropped++; if (_specScore > -8) _specScore--; }
   }

@@ -33,92 +33,111 @@ int HipEngine::AllowedCpus() {
   return n;
 }
 
-// Everything posted so far, in the order it was posted.  The RecordAnswers first go where RecordAnswer puts them (the list of
-// deferred updates), ReleaseQuiz and RecordQuizTarget run as they come; the StartQuiz calls then share one launch; then ONE launch runs every deferred update if a ListTopTargets of this drain needs its quiz's posterior;
-// then the combined sweeps leaders have posted; then the listings that the update kernel has not made already.
+// Everything posted so far, in the order it was posted.  The order of the stages is the contract: the RecordAnswers first go where
+// RecordAnswer puts them (the list of deferred updates) and ReleaseQuiz runs as it comes; then ONE launch runs every deferred update if a
+// ListTopTargets of this drain needs its quiz's posterior; then the RecordQuizTarget calls (the updates read the cube as it was), the StartQuiz
+// calls in one launch and the ResumeQuiz calls in theirs; then the combined sweeps leaders have posted; then the listings not made already.
 void HipEngine::DrainPosted(PostedOp *ordered) {
   _postedDrains++;
-  bool needFlush = false;
-  int64_t nStarts = 0, nTrains = 0, nResumes = 0;
+  const PostedCounts n = RunPostedInPlace(ordered);
+  Error flushErr;
+  if (n.needFlush) flushErr = FlushUpdates();
+  if (n.trains > 0) { TrainPosted(ordered); MarkStreamBusy(); }
+  if (n.starts > 0) StartPosted(ordered);
+  if (n.resumes > 0) ResumePosted(ordered, n.resumes);
+  for (PostedOp *op = ordered; op != nullptr; op = op->next)   // (behind the updates, ahead of the listings: the sweep is what the most clients wait for)
+    if (op->kind == OpKind::LaunchBatch) LaunchBatchLocked(*op->ctx, *op->batch, *op->flight);
+  ListPosted(ordered, flushErr);
+  // The drain runs on the holder's way out -- possibly after a selection path declared the stream idle -- and may have launched
+  // updates, trainings, quiz starts and listings: whoever takes the lock next finds the stream marked busy.
+  MarkStreamBusy();
+}
+
+HipEngine::PostedCounts HipEngine::RunPostedInPlace(PostedOp *ordered) {
+  PostedCounts n;
   for (PostedOp *op = ordered; op != nullptr; op = op->next) {
     _postedOps++;
-    if (op->kind == 1) { op->err = RecordAnswerLocked(op->iQuiz, op->arg, op->remote, false); continue; }
-    if (op->kind == 5) { op->err = ReleaseQuizLocked(op->iQuiz, false); continue; }
-    if (op->kind == 6) { nTrains++; continue; }
-    if (op->kind == 4) { nStarts++; continue; }
-    if (op->kind == 7) { nResumes++; continue; }
-    if (op->kind == 3) continue;
-    op->result = -1;
-    op->err = CheckRegular("list top targets");
-    if (!op->err.ok()) continue;
-    op->quiz = UseQuiz(op->err, op->iQuiz);
-    if (op->quiz != nullptr) op->serial = op->quiz->serial;
-    if (op->quiz != nullptr && op->quiz->updatePending) needFlush = true;
-  }
-  Error flushErr;
-  if (needFlush) flushErr = FlushUpdates();
-  if (nTrains > 0) { TrainPosted(ordered); MarkStreamBusy(); }
-  if (nStarts > 0) {
-    MarkStreamBusy();
-    // the StartQuiz calls of this drain: ONE launch sets all their priors (as StartQuizBatch; chunks of kStartInline)
-    hipSetDevice(_device);
-    static thread_local StartBatchInline batch;   // (4 KB of pointers: not on a client thread's stack)
-    batch.n = 0;
-    batch.askedWords = (int64_t)BitWords(_Q);
-    std::vector<PostedOp *> chunk;
-    auto launch = [&]() {
-      if (batch.n > 0) {
-        const hipError_t he = LaunchStartQuizBatch(View(), batch, _opt.workers, _stream);
-        if (he != hipSuccess)
-          for (PostedOp *o : chunk)
-            if (o->result >= 0) {
-              Quiz *q = _quizzes[(size_t)o->result];
-              UnassignQuiz(o->result);
-              DestroyQuiz(q);
-              o->result = -1;
-              o->err = HipErr(he, "StartQuiz");
-            }
-      }
-      batch.n = 0;
-      chunk.clear();
-    };
-    for (PostedOp *op = ordered; op != nullptr; op = op->next) {
-      if (op->kind != 4) continue;
-      _startBatch = &batch;
-      op->result = CreateQuiz(op->err, 0, nullptr, nullptr, nullptr, 0, nullptr);
-      _startBatch = nullptr;
-      chunk.push_back(op);
-      if (batch.n == kStartInline) launch();
+    switch (op->kind) {
+      case OpKind::RecordAnswer: op->err = RecordAnswerLocked(op->iQuiz, op->iAnswer, op->remote, false); break;
+      case OpKind::ReleaseQuiz: op->err = ReleaseQuizLocked(op->iQuiz, false); break;
+      case OpKind::RecordQuizTarget: n.trains++; break;
+      case OpKind::StartQuiz: n.starts++; break;
+      case OpKind::ResumeQuiz: n.resumes++; break;
+      case OpKind::LaunchBatch: break;
+      case OpKind::ListTopTargets:
+        op->result = -1;
+        op->err = CheckRegular("list top targets");
+        if (!op->err.ok()) break;
+        op->quiz = UseQuiz(op->err, op->iQuiz);
+        if (op->quiz != nullptr) { op->serial = op->quiz->serial; n.needFlush = n.needFlush || op->quiz->updatePending; }
+        break;
     }
-    launch();
   }
-  if (nResumes > 0) {
-    // the ResumeQuiz calls of this drain: one launch sequence and one synchronisation per chunk for all of them (as ResumeQuizBatch),
-    // each call failing or succeeding on its own
-    MarkStreamBusy();
-    std::vector<ResumeEntry> es;
-    es.reserve((size_t)nResumes);
-    for (PostedOp *op = ordered; op != nullptr; op = op->next)
-      if (op->kind == 7) { es.emplace_back(); es.back().nAnswered = op->arg; es.back().pAQs = op->aqs; }
-    (void)ResumeEntriesLocked(es, false);
-    size_t i = 0;
-    for (PostedOp *op = ordered; op != nullptr; op = op->next)
-      if (op->kind == 7) { op->err = es[i].err; op->result = es[i].err.ok() ? es[i].id : -1; i++; }
-    _resumeBatches++;
-    _resumesBatched += (uint64_t)nResumes;
+  return n;
+}
+
+// The StartQuiz calls of a drain: ONE launch sets all their priors (as StartQuizBatch; chunks of kStartInline)
+void HipEngine::StartPosted(PostedOp *ordered) {
+  MarkStreamBusy();
+  hipSetDevice(_device);
+  static thread_local StartBatchInline batch;   // (4 KB of pointers: not on a client thread's stack)
+  batch.n = 0;
+  batch.askedWords = (int64_t)BitWords(_Q);
+  std::vector<PostedOp *> chunk;
+  auto launch = [&]() {
+    if (batch.n > 0) {
+      const hipError_t he = LaunchStartQuizBatch(View(), batch, _opt.workers, _stream);
+      if (he != hipSuccess)
+        for (PostedOp *o : chunk)
+          if (o->result >= 0) {
+            Quiz *q = _quizzes[(size_t)o->result];
+            UnassignQuiz(o->result);
+            DestroyQuiz(q);
+            o->result = -1;
+            o->err = HipErr(he, "StartQuiz");
+          }
+    }
+    batch.n = 0;
+    chunk.clear();
+  };
+  for (PostedOp *op = ordered; op != nullptr; op = op->next) {
+    if (op->kind != OpKind::StartQuiz) continue;
+    _startBatch = &batch;
+    op->result = CreateQuiz(op->err, 0, nullptr, nullptr, nullptr, 0, nullptr);
+    _startBatch = nullptr;
+    chunk.push_back(op);
+    if (batch.n == kStartInline) launch();
   }
+  launch();
+}
+
+// The ResumeQuiz calls of a drain: one launch sequence and one synchronisation per chunk for all (as ResumeQuizBatch), each call failing or succeeding on its own
+void HipEngine::ResumePosted(PostedOp *ordered, int64_t nResumes) {
+  MarkStreamBusy();
+  std::vector<ResumeEntry> es;
+  es.reserve((size_t)nResumes);
   for (PostedOp *op = ordered; op != nullptr; op = op->next)
-    if (op->kind == 3) LaunchBatchLocked(*op->ctx, *op->batch, *op->flight);   // (behind the updates, ahead of the listings: the sweep is what the most clients wait for)
+    if (op->kind == OpKind::ResumeQuiz) { es.emplace_back(); es.back().nAnswered = op->nAnswered; es.back().pAQs = op->aqs; }
+  (void)ResumeEntriesLocked(es, false);
+  size_t i = 0;
+  for (PostedOp *op = ordered; op != nullptr; op = op->next)
+    if (op->kind == OpKind::ResumeQuiz) { op->err = es[i].err; op->result = es[i].err.ok() ? es[i].id : -1; i++; }
+  _resumeBatches++;
+  _resumesBatched += (uint64_t)nResumes;
+}
+
+// The listings that the update kernel has not made already (flushErr: the deferred updates' launch).  The last stage: every record is handed back here.
+void HipEngine::ListPosted(PostedOp *ordered, const Error &flushErr) {
   for (PostedOp *op = ordered; op != nullptr;) {
     PostedOp *const next = op->next;   // (the operation is its thread's again the moment it is done)
-    if (op->kind == 2 && op->quiz != nullptr) {
+    if (op->kind == OpKind::ListTopTargets && op->quiz != nullptr) {
       Quiz *q = op->quiz;
-      const int64_t want = std::min<int64_t>(op->arg, _T);
+      const int64_t want = std::min<int64_t>(op->maxCount, _T);
       // (a ReleaseQuiz of the same quiz later in this drain -- a client's error, IPqaEngine.h:44 -- has taken it away since)
       const bool gone = (size_t)op->iQuiz >= _quizzes.size() || _quizzes[(size_t)op->iQuiz] != q || q->serial != op->serial;
       if (gone) { op->result = -1; op->err = Error::MakeP(ErrCode::AbsentId, "id=" + std::to_string(op->iQuiz), "Quiz index is not in the registry (but rather at a gap)."); }
       else if (!flushErr.ok()) op->err = flushErr;
-      else if (want > kQuizTop || _T > 16384) op->result = -2;
+      else if (want > kQuizTop || _T > 16384) op->result = PostedOp::kTakeLockYourself;
       else {
         _topWantRecent = want >= _topWantRecent ? want : want + (_topWantRecent - want) * 7 / 8;
         const bool cached = q->topOp != 0 && q->topVersion == q->priorVersion && want <= q->topCount;
@@ -136,12 +155,9 @@ void HipEngine::DrainPosted(PostedOp *ordered) {
     _mu.Done(op);
     op = next;
   }
-  // The drain runs on the holder's way out -- possibly after a selection path declared the stream idle -- and may have launched
-  // updates, trainings, quiz starts and listings: whoever takes the lock next finds the stream marked busy.
-  MarkStreamBusy();
 }
 
-// The RecordQuizTarget calls of a drain (kind 6), in the order they were posted: calls with different targets touch disjoint cells
+// The RecordQuizTarget calls of a drain, in the order they were posted: calls with different targets touch disjoint cells
 // and go out in ONE launch (train_batch_inline_kernel: a workgroup per call); a call whose target is already in the batch, or that
 // does not fit the kernel's arguments, closes the batch first (or runs alone, the usual way).
 void HipEngine::TrainPosted(PostedOp *ordered) {
@@ -161,10 +177,10 @@ void HipEngine::TrainPosted(PostedOp *ordered) {
   };
   bool stopped = false;
   for (PostedOp *op = ordered; op != nullptr; op = op->next) {
-    if (op->kind != 6) continue;
+    if (op->kind != OpKind::RecordQuizTarget) continue;
     op->err = CheckRegular("record quiz target");
     if (!op->err.ok()) continue;
-    const int64_t iTarget = op->arg;
+    const int64_t iTarget = op->iTarget;
     Quiz *q = UseQuiz(op->err, op->iQuiz);
     if (q == nullptr) continue;
     op->err = ValidateTrainLocked((int64_t)q->answers.size(), q->answers.data(), iTarget);
@@ -199,12 +215,12 @@ void HipEngine::TrainPosted(PostedOp *ordered) {
   launch();
 }
 
-int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
+int64_t HipEngine::Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t rnd) {
   CallScope scope(_activeCallers);
   _mu.spinFirst.store(ClientsFitCpus() && _activeCallers.load(std::memory_order_relaxed) > 1, std::memory_order_relaxed);
   if (!_opt.combine) {
     std::lock_guard<EngineMutex> lk(_mu);
-    return kind == 0 ? NextQuestionArgmaxLocked(err, iQuiz) : NextQuestionSampledLocked(err, iQuiz, rnd);
+    return SelectLocked(err, iQuiz, kind, rnd);
   }
   // Nobody else is inside a quiz-level call (the usual case of the reference's wrappers: one quiz loop on one thread): straight to
   // the single-quiz path -- no request to queue, no batch context, no flight.  Racing with a client that arrives just now is
@@ -212,12 +228,12 @@ int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
   if (_activeCallers.load(std::memory_order_relaxed) == 1 && _extCallers == nullptr && _mu.try_lock()) {
     std::lock_guard<EngineMutex> lk(_mu, std::adopt_lock);
     _flushedSinceSweep.store(0, std::memory_order_relaxed);
-    return kind == 0 ? NextQuestionArgmaxLocked(err, iQuiz) : NextQuestionSampledLocked(err, iQuiz, rnd);
+    return SelectLocked(err, iQuiz, kind, rnd);
   }
   SelRequest r;
   r.iQuiz = iQuiz; r.kind = kind; r.rnd = rnd;
   int st = _comb.Wait(r, &_sweepNsEwma, ClientsFitCpus());
-  if (st == 2) {   // (the lead: nobody else led, or the leader before served its own batch and handed the lead to this, the oldest request)
+  if (st == kReqLead) {   // (the lead: nobody else led, or the leader before served its own batch and handed the lead to this, the oldest request)
     if (_opt.lingerUs > 0 && Concurrent())   // (alone in the engine: nobody to wait for)
       _comb.Linger(_opt.lingerUs, _flushedSinceSweep.load(std::memory_order_relaxed), _activeCallers);
     Flight f;
@@ -229,7 +245,7 @@ int64_t HipEngine::Combine(Error &err, int64_t iQuiz, int kind, uint64_t rnd) {
         },
         [&](BatchCtx &c, std::vector<SelRequest *> &batch) { return !f.live.empty() && CollectBatch(c, batch, f, &r); });
   }
-  if (st == 3) {   // the sweep has run: this quiz's priorities are on the host, the selection is this thread's own work
+  if (st == kReqSelect) {   // the sweep has run: this quiz's priorities are on the host, the selection is this thread's own work
     SelectFromPriorities(&r);
     r.ctx->readers.fetch_sub(1, std::memory_order_release);
   }
@@ -253,8 +269,8 @@ int64_t HipEngine::SelectFromPriorities(SelRequest *r) {
     return r->result = -1;
   }
   BestPick best;   // (kb_plan.h: the device's rule -- maximum priority, lowest index on ties, NaN never wins)
-  if (r->kind == 0) for (int64_t k = 0; k < nQ; k++) if (!skip(k)) best.Offer(run[(size_t)k], k);
-  const int64_t pick = r->kind == 1 ? SelectSampledHostBits(run.data(), nQ, r->nSub, r->rnd, r->unavailable.data(), nullptr) : best.index;
+  if (r->kind == SelKind::Argmax) for (int64_t k = 0; k < nQ; k++) if (!skip(k)) best.Offer(run[(size_t)k], k);
+  const int64_t pick = r->kind == SelKind::Sampled ? SelectSampledHostBits(run.data(), nQ, r->nSub, r->rnd, r->unavailable.data(), nullptr) : best.index;
   r->result = FinishSelection(r->err, q, pick, nQ, r->unavailable.data());
   q->inSelection.store(false, std::memory_order_release);
   return r->result;
@@ -278,22 +294,17 @@ int64_t HipEngine::PreferredCombinedBatch(int64_t m) const {
 // Validate and launch (the caller holds the context; the engine's lock is taken and released here).  f.live: the requests whose
 // sweep is in flight; every other request of `batch` has its result or error.
 void HipEngine::LaunchBatch(BatchCtx &c, std::vector<SelRequest *> &batch, Flight &f) {
-  if (batch.size() > 1 && !_mu.try_lock()) {   // (the engine is taken: its holder launches this sweep on its way out)
-    PostedOp op;
-    op.kind = 3; op.ctx = &c; op.batch = &batch; op.flight = &f;
-    PostAndWait(_mu, op);
-    return;
-  }
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (batch.size() > 1) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else lk.lock();
+  if (batch.size() > 1) {
+    // (taken: its holder launches this sweep on its way out.  Not TakeOrPost: "post_always" forces the clients' calls only)
+    LaunchBatchOp op(c, batch, f);
+    if (TryLockOrPost(_mu, lk, op)) return;
+  } else lk.lock();   // (a batch of one is the single-quiz path: nothing for a holder to share, so it waits for the lock)
   LaunchBatchLocked(c, batch, f);
 }
 
 void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch, Flight &f) {
-  auto single = [&](SelRequest *r) {
-    r->result = r->kind == 0 ? NextQuestionArgmaxLocked(r->err, r->iQuiz) : NextQuestionSampledLocked(r->err, r->iQuiz, r->rnd);
-  };
+  auto single = [&](SelRequest *r) { r->result = SelectLocked(r->err, r->iQuiz, r->kind, r->rnd); };
   f.tB = std::chrono::steady_clock::now();
   if (batch.size() == 1) { _flushedSinceSweep.store(0, std::memory_order_relaxed); single(batch[0]); return; }
   auto failAll = [&](const Error &e) { for (SelRequest *r : batch) { r->err = e; r->result = -1; } };
@@ -309,7 +320,7 @@ void HipEngine::LaunchBatchLocked(BatchCtx &c, std::vector<SelRequest *> &batch,
     if (UseQuiz(qe, r->iQuiz) == nullptr) { r->err = qe; r->result = -1; continue; }
     live.push_back(r);
     ids.push_back(r->iQuiz);
-    f.anySampled = f.anySampled || r->kind == 1;
+    f.anySampled = f.anySampled || r->kind == SelKind::Sampled;
   }
   if (live.empty()) return;
   if (live.size() == 1 || (_opt.server && ServerUsable()) || _opt.useGraph) {   // (the resident sweep and graph replay serve one quiz at a time)

@@ -209,7 +209,7 @@ Error HipEngine::WaitPacked(SelectResult *record, uint64_t tag, int64_t outBase,
   return Error();
 }
 
-int64_t HipEngine::NextQuestionArgmax(Error &err, int64_t iQuiz) { return Combine(err, iQuiz, 0, 0); }
+int64_t HipEngine::NextQuestionArgmax(Error &err, int64_t iQuiz) { return Combine(err, iQuiz, SelKind::Argmax, 0); }
 
 // Synchronous single-quiz selections of a Double engine through a register shape (whose finisher knows whether anything was listed):
 // the fix of pole_kernels.hip is launched only when the sweep says so (FusedSelect::lazyFix) -- one launch per selection of a fresh quiz.
@@ -289,7 +289,7 @@ int64_t HipEngine::NextQuestionArgmaxLocked(Error &err, int64_t iQuiz) {
   // copy, no stream synchronisation on the critical path.
   uint64_t seq;
   FusedSelect fs{};
-  if (TakeSpeculation(q, 1 << 1, &seq) != 0) fs = _spec.fs;   // (RecordAnswer has launched this very sweep already)
+  if (TakeSpeculation(q, {SpecKind::ArgmaxRecord}, &seq) != SpecKind::None) fs = _spec.fs;   // (RecordAnswer has launched this very sweep already)
   else {
     seq = NextLaunchTag();
     fs = OwnLaunch(seq).Lazy(LazyFor(q));
@@ -769,7 +769,7 @@ int64_t HipEngine::NextQuestionArgmaxGraph(Error &err, Quiz *q) {
   return FinishSelection(err, q, _hPinned->sel.index);
 }
 
-int64_t HipEngine::NextQuestionSampled(Error &err, int64_t iQuiz, uint64_t rnd) { return Combine(err, iQuiz, 1, rnd); }
+int64_t HipEngine::NextQuestionSampled(Error &err, int64_t iQuiz, uint64_t rnd) { return Combine(err, iQuiz, SelKind::Sampled, rnd); }
 
 int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t rnd) {
   err = CheckRegular("compute next question");
@@ -794,10 +794,10 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     }
   }
   uint64_t specTag = 0;
-  const int took = TakeSpeculation(q, (1 << 2) | (1 << 3), &specTag);   // 2 / 3: RecordAnswer has launched the sweep already
-  const bool speculated = took == 2;
-  if (took == 0) StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
-  if (took != 3 && _opt.hostSampled && !_opt.fusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_opt.evalVariant)) {
+  const SpecKind took = TakeSpeculation(q, {SpecKind::HostPriorities, SpecKind::DevicePriorities}, &specTag);   // RecordAnswer has launched the sweep already
+  const bool speculated = took == SpecKind::HostPriorities;
+  if (took == SpecKind::None) StopServer();   // a launched sweep has no room beside the resident one and would wait for it to idle out
+  if (took != SpecKind::DevicePriorities && _opt.hostSampled && !_opt.fusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_opt.evalVariant)) {
     // ONE launch, and the selection on the host: the sweep's finisher workgroup copies the finished priority vector (8 bytes per
     // question) into host-coherent memory and sets the flag; the selector's O(Q) scalar Kahan steps take the host a few
     // microseconds -- less than the dispatch of the selector kernel they replace.
@@ -821,7 +821,7 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     const int64_t sel = SelectSampledHostBits(_hostRun.data(), _Q, nSub, rnd, _hQGap.data(), q->hAsked.data());
     return FinishSelection(err, q, sel);
   }
-  if (took != 3 && _opt.fusedSampled && _elem == 8 && EvalVariantFusesSampled(kb, (int)_opt.evalVariant, nSub)) {
+  if (took != SpecKind::DevicePriorities && _opt.fusedSampled && _elem == 8 && EvalVariantFusesSampled(kb, (int)_opt.evalVariant, nSub)) {
     // ONE launch: the sweep's finisher workgroup runs the reference's selector once every workgroup has reported
     { Error se = SettlePoleList(); if (!se.ok()) { err = se; return -1; } }
     const uint64_t seq = NextLaunchTag();
@@ -833,7 +833,7 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
     CheckPriority(_hPinned->sel.priority, _hPinned->sel.index);
     return FinishSelection(err, q, _hPinned->sel.index);
   }
-  if (took != 3) {   // (else: the priorities are in _dPriority already, or on their way there in stream order)
+  if (took != SpecKind::DevicePriorities) {   // (else: the priorities are in _dPriority already, or on their way there in stream order)
     err = LaunchSingleSweep(q, nullptr);
     if (!err.ok()) return -1;
   }
@@ -847,10 +847,10 @@ int64_t HipEngine::NextQuestionSampledLocked(Error &err, int64_t iQuiz, uint64_t
 }
 
 int64_t HipEngine::NextQuestion(Error &err, int64_t iQuiz) {
-  if (_opt.select == 1) return Combine(err, iQuiz, 0, 0);
+  if (_opt.select == 1) return Combine(err, iQuiz, SelKind::Argmax, 0);
   uint64_t rnd;
   { std::lock_guard<std::mutex> lk(_rngMu); rnd = _rng.Next(); }   // (drawn when the call arrives, whatever sweep serves it)
-  return Combine(err, iQuiz, 1, rnd);
+  return Combine(err, iQuiz, SelKind::Sampled, rnd);
 }
 
 }  // namespace pqa

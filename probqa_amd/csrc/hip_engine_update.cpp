@@ -8,15 +8,9 @@ namespace pqa {
 // ------------------------------------------------------------------------------------------------------------------
 Error HipEngine::RecordAnswerImpl(int64_t iQuiz, int64_t iAnswer, bool remote) {
   CallScope scope(_activeCallers);
-  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {   // somebody is inside the engine: it runs this call's bookkeeping on its way out
-    PostedOp op;
-    op.kind = 1; op.iQuiz = iQuiz; op.arg = iAnswer; op.remote = remote;
-    PostAndWait(_mu, op);
-    return op.err;
-  }
-  std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else lk.lock();
+  std::unique_lock<EngineMutex> lk;
+  RecordAnswerOp op(iQuiz, iAnswer, remote);
+  if (TakeOrPost(lk, op)) return op.err;   // somebody is inside the engine: it has run this call's bookkeeping on its way out
   return RecordAnswerLocked(iQuiz, iAnswer, remote, !Concurrent());
 }
 
@@ -219,18 +213,18 @@ bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
   if (withUpdate && (!_opt.fuseUpdate || _specScore < -4)) return false;
   if (_specScore < -4 && (++_specProbe & 31) != 0) return false;   // the client does not follow RecordAnswer with NextQuestion: probe now and then
   const KbView kb = View();
-  int kind = 0;
-  if (_opt.select == 1) kind = 1;
-  else if (_opt.hostSampled && !_opt.fusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_opt.evalVariant)) kind = 2;
-  else if (!(_opt.fusedSampled && _elem == 8)) kind = 3;   // Float engines, long rows: the sweep now, the selector kernel at NextQuestion
-  if (kind == 0) return false;
+  SpecKind kind = SpecKind::None;
+  if (_opt.select == 1) kind = SpecKind::ArgmaxRecord;
+  else if (_opt.hostSampled && !_opt.fusedSampled && _elem == 8 && EvalVariantHasFinisherWorkgroup(kb, (int)_opt.evalVariant)) kind = SpecKind::HostPriorities;
+  else if (!(_opt.fusedSampled && _elem == 8)) kind = SpecKind::DevicePriorities;   // Float engines, long rows: the sweep now, the selector kernel at NextQuestion
+  if (kind == SpecKind::None) return false;
   const int64_t nLoose = std::max<int64_t>(1, _opt.workers - 1);   // reference PqaCore/CEQuiz.h:98, PqaCore/BaseCpuEngine.cpp:22
-  if (withUpdate && (kind == 3 || UseClusterSweep() || !EvalFusesUpdate(kb, (int)_opt.evalVariant, nLoose))) return false;
-  if (kind == 2 && EnsureHostPriority() != hipSuccess) return false;
+  if (withUpdate && (kind == SpecKind::DevicePriorities || UseClusterSweep() || !EvalFusesUpdate(kb, (int)_opt.evalVariant, nLoose))) return false;
+  if (kind == SpecKind::HostPriorities && EnsureHostPriority() != hipSuccess) return false;
   if (withUpdate) DropSpeculation();
   const uint64_t seq = NextLaunchTag();
   if (!SettlePoleList().ok()) return false;
-  const FusedSelect fs = OwnLaunch(seq).HostPriority(kind == 2 ? _hHostPriority : nullptr).Lazy((kind == 1 || kind == 2) && LazyFor(q));
+  const FusedSelect fs = OwnLaunch(seq).HostPriority(kind == SpecKind::HostPriorities ? _hHostPriority : nullptr).Lazy(kind != SpecKind::DevicePriorities && LazyFor(q));
   if (withUpdate) {
     const int64_t topCount = std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(_opt.topCache, _topWantRecent), kQuizTop), _T);
     const uint64_t op = _opSeq + 1;
@@ -243,9 +237,9 @@ bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
     q->topOp = op; q->topVersion = q->priorVersion; q->topCount = topCount;
     _flushes++; _flushedUpdates++; _fusedUpdates++;
     if (_maxFlush < 1) _maxFlush = 1;
-  } else if (kind == 1   ? !LaunchSingleSweep(q, &fs).ok()
-             : kind == 3 ? !LaunchSingleSweep(q, nullptr).ok()
-                         : LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream) != hipSuccess) {
+  } else if (kind == SpecKind::ArgmaxRecord       ? !LaunchSingleSweep(q, &fs).ok()
+             : kind == SpecKind::DevicePriorities ? !LaunchSingleSweep(q, nullptr).ok()
+                                                  : LaunchEvalQuestions(kb, q->dPrior, q->dAsked, 0, _Q, _dPriority, (int)_opt.evalVariant, &fs, _stream) != hipSuccess) {
     (void)hipGetLastError();   // NextQuestion will launch for itself and report
     return false;
   }
@@ -258,14 +252,15 @@ bool HipEngine::Speculate(Quiz *q, int64_t updQuestion, int64_t updAnswer) {
   return withUpdate;
 }
 
-// The kind (and the launch tag to wait for) of the pending speculative sweep if it is exactly a launch a NextQuestion accepting the
-// kinds of `kindMask` (bit k: kind k) would make for `q` now -- same quiz and posterior, no fused launch since (they share the
-// records and the hand-over buffers) -- else 0, and the speculation is dropped.
-int HipEngine::TakeSpeculation(Quiz *q, int kindMask, uint64_t *pTag) {
-  if (_spec.quiz == nullptr) return 0;
-  const bool match = _spec.quiz == q && ((kindMask >> _spec.kind) & 1) && _spec.priorVersion == q->priorVersion && _spec.tag == _selSeq &&
+// The kind (and the launch tag to wait for) of the pending speculative sweep if it is exactly a launch a NextQuestion that can use
+// the `accepted` kinds would make for `q` now -- same quiz and posterior, no fused launch since (they share the records and the
+// hand-over buffers) -- else None, and the speculation is dropped.
+HipEngine::SpecKind HipEngine::TakeSpeculation(Quiz *q, std::initializer_list<SpecKind> accepted, uint64_t *pTag) {
+  if (_spec.quiz == nullptr) return SpecKind::None;
+  const bool match = _spec.quiz == q && std::find(accepted.begin(), accepted.end(), _spec.kind) != accepted.end() &&
+                     _spec.priorVersion == q->priorVersion && _spec.tag == _selSeq &&
                      _spec.variant == _opt.evalVariant && _spec.stream == _stream && (!_opt.server || q->noServer) && !_opt.useGraph;
-  if (!match) { DropSpeculation(); return 0; }
+  if (!match) { DropSpeculation(); return SpecKind::None; }
   _spec.quiz = nullptr;
   _specHits++;
   if (_specScore < 8) _specScore++;
@@ -407,24 +402,24 @@ Error HipEngine::EnsureTopExactScratch(int64_t nQuizzes, int64_t want) {
 int64_t HipEngine::ListTopTargetsFast(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedTarget *pDest) {
   CallScope scope(_activeCallers);
   std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (!_opt.combine || maxCount <= 0 || pDest == nullptr) lk.lock();
-  else if (!_opt.postAlways && _mu.try_lock()) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else {
-    // somebody is inside the engine: it launches what this call needs on its way out (the quiz's deferred update among all that
+  // the wait for a quiz's own lines -- the engine open to the other clients meanwhile -- and the list out of them
+  auto takeLines = [&](QuizPinned *pin, uint64_t flagOp, int64_t want) -> int64_t {
+    err = WaitFlagNapping(&pin->topFlag, flagOp, "ListTopTargets");
+    if (!err.ok()) return -1;
+    const int64_t n = std::min<int64_t>(pin->nOut, want);
+    std::memcpy(pDest, pin->top, (size_t)n * sizeof(RatedTargetDev));
+    return n;
+  };
+  ListTopTargetsOp posted(iQuiz, maxCount);
+  if (maxCount <= 0 || pDest == nullptr) lk.lock();   // (nothing to launch for a holder: the answer below needs the lock only)
+  else if (TakeOrPost(lk, posted)) {
+    // somebody is inside the engine: it has launched what this call needs on its way out (the quiz's deferred update among all that
     // have gathered, the listing if the update kernel has not made it); the wait for the quiz's own lines is this thread's
-    PostedOp op;
-    op.kind = 2; op.iQuiz = iQuiz; op.arg = maxCount;
-    PostAndWait(_mu, op);
-    if (op.result != -2) {
-      err = op.err;
-      if (!err.ok() || op.result < 0) return -1;
-      err = WaitFlagNapping(&op.pin->topFlag, op.flagOp, "ListTopTargets");
-      if (!err.ok()) return -1;
-      const int64_t n = std::min<int64_t>(op.pin->nOut, op.result);
-      std::memcpy(pDest, op.pin->top, (size_t)n * sizeof(RatedTargetDev));
-      return n;
+    if (posted.result != PostedOp::kTakeLockYourself) {
+      err = posted.err;
+      return !err.ok() || posted.result < 0 ? -1 : takeLines(posted.pin, posted.flagOp, posted.result);
     }
-    lk.lock();   // (a list longer than the quiz's lines hold)
+    lk.lock();
   }
   err = CheckRegular("list top targets");
   if (!err.ok()) return -1;
@@ -472,11 +467,7 @@ int64_t HipEngine::ListTopTargetsFast(Error &err, int64_t iQuiz, int64_t maxCoun
     if (Concurrent()) {
       // other clients are inside the engine: wait with the engine open to them (the lines are this quiz's own)
       lk.unlock();
-      err = WaitFlagNapping(&pin->topFlag, op, "ListTopTargets");
-      if (!err.ok()) return -1;
-      const int64_t n = std::min<int64_t>(pin->nOut, want);
-      std::memcpy(pDest, pin->top, (size_t)n * sizeof(RatedTargetDev));
-      return n;
+      return takeLines(pin, op, want);
     }
     err = WaitFlag(&pin->topFlag, op, "ListTopTargets");
     if (!err.ok()) return -1;
@@ -808,15 +799,9 @@ Error HipEngine::RecordQuizTarget(int64_t iQuiz, int64_t iTarget, double amount)
   if (amount <= 0)
     return Error::MakeP(ErrCode::NonPositiveAmount, "amount=" + std::to_string(amount), "|amount| must be positive.");
   CallScope scope(_activeCallers);
-  if (_opt.combine && (_opt.postAlways || !_mu.try_lock())) {
-    PostedOp op;
-    op.kind = 6; op.iQuiz = iQuiz; op.arg = iTarget; op.amount = amount;
-    PostAndWait(_mu, op);
-    return op.err;
-  }
-  std::unique_lock<EngineMutex> lk(_mu, std::defer_lock);
-  if (_opt.combine) lk = std::unique_lock<EngineMutex>(_mu, std::adopt_lock);
-  else lk.lock();
+  std::unique_lock<EngineMutex> lk;
+  RecordQuizTargetOp op(iQuiz, iTarget, amount);
+  if (TakeOrPost(lk, op)) return op.err;
   return RecordQuizTargetLocked(iQuiz, iTarget, amount);
 }
 

@@ -1,5 +1,5 @@
 // redundancy_kernels.hip -- questions whose answers a given one predicts (include/PqaHipExt.h: PqaEngine_EvalQuestionRedundancy and
-// its neighbours; host side: hip_engine_redundancy.cpp).
+// its neighbours; host side: hip_engine_sources.cpp).
 //
 // With w[t] = vB[t] (0 at a gap target) and p_qk(t) = A[q][k][t] * (1 / D[q][t]), a source question s and a question q have the K x K
 // table  J[k][k'] = sum_t (w[t] p_sk(t)) p_qk'(t)  and the mutual information of their answers, in bits,

@@ -253,7 +253,6 @@ class ShardedEngine final : public IEngine {
   // ---- the engine's lock and its posted operations ---------------------------------------------------------------------------
   struct SelRequest;
   struct Flight;
-  enum class SelKind { Argmax, Sampled };
   enum class OpKind {
     StartQuiz,          // result = the quiz
     ReleaseQuiz,        // (iQuiz)
@@ -271,7 +270,7 @@ class ShardedEngine final : public IEngine {
     int ctx = 0;
     std::vector<SelRequest *> *batch = nullptr;
     Flight *flight = nullptr;
-    std::atomic<int> state{0};         // 0 posted, 2 posted and its thread asleep on this word, 1 done
+    std::atomic<int> state{kOpPosted};
     Op *next = nullptr;
   };
   using OpLock = PostingLock<Op, ShardedEngine>;   // (a sleeping lock; releasing it runs whatever was posted meanwhile: Execute)
@@ -428,9 +427,9 @@ class ShardedEngine final : public IEngine {
     uint64_t rnd = 0;
     int64_t result = -1;
     Error err;
-    std::atomic<int> state{0};         // 0 waiting, 1 served, 2 lead handed over: serve the queue yourself, 3 select for yourself from `views`
-    std::vector<PriorityView> views;   // state 3: per shard, this quiz's priority vector on the host
-    std::vector<uint64_t> skip;        // state 3: asked questions and gaps in GLOBAL numbering as the sweeps saw them (64-bit packs)
+    std::atomic<int> state{kReqWaiting};   // (combining.h) kReqSelect: select for yourself from `views`
+    std::vector<PriorityView> views;   // kReqSelect: per shard, this quiz's priority vector on the host
+    std::vector<uint64_t> skip;        // kReqSelect: asked questions and gaps in GLOBAL numbering as the sweeps saw them (64-bit packs)
     CombineCtx *ctx = nullptr;
   };
   struct Flight {
@@ -1128,7 +1127,7 @@ int64_t ShardedEngine::Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t
     return r.result;
   }
   int st = _comb.Wait(r);
-  if (st == 2) {   // (the lead: nobody else led, or the leader before launched its batch and handed the lead to this, the oldest request)
+  if (st == kReqLead) {   // (the lead: nobody else led, or the leader before launched its batch and handed the lead to this, the oldest request)
     if (_optLingerUs > 0 && Concurrent()) _comb.Linger(_optLingerUs, _answersSinceSweep.load(std::memory_order_relaxed), _activeCallers);
     Flight f;
     st = _comb.Lead(
@@ -1138,7 +1137,7 @@ int64_t ShardedEngine::Combine(Error &err, int64_t iQuiz, SelKind kind, uint64_t
         },
         [&](CombineCtx &c, std::vector<SelRequest *> &batch) { return !f.live.empty() && CollectBatch((int)(&c - _bctx), batch, f, &r); });
   }
-  if (st == 3) {   // the sweeps have run: this quiz's priorities are on the host, the selection is this thread's own work
+  if (st == kReqSelect) {   // the sweeps have run: this quiz's priorities are on the host, the selection is this thread's own work
     SelectFromViews(&r);
     r.ctx->readers.fetch_sub(1, std::memory_order_release);
   }

@@ -1,5 +1,5 @@
 // similarity_kernels.hip -- targets that answer like a given one (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity and its
-// neighbours; host side: hip_engine_similarity.cpp).
+// neighbours; host side: hip_engine_sources.cpp).
 //
 // With p_qk(t) = A[q][k][t] / D[q][t] the similarity of a source s and a target t is the mean over the questions that are not gaps of
 // the Bhattacharyya coefficient  BC_q(s, t) = sum_k sqrt(p_qk(s)) sqrt(p_qk(t)).  Every other sweep of the engine contracts a question's

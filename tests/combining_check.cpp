@@ -2,6 +2,7 @@
 // with g++, plain and with -fsanitize=thread).  Prints one "ok" line per part and exits 0, or names the broken property and exits 1.
 //   combining_check lock <posters> <ops each>      the posting lock
 //   combining_check combine <clients> <calls each>  the combiner
+//   combining_check take <threads> <ops each>       TryLockOrPost: one way in for posted and direct calls
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,7 +42,7 @@ static void JoinWithin(std::vector<std::thread> &threads, std::atomic<int> &fini
 struct Op {
   int tid = 0, idx = 0;
   std::atomic<int> runs{0};
-  std::atomic<int> state{0};
+  std::atomic<int> state{kOpPosted};
   Op *next = nullptr;
 };
 
@@ -56,7 +57,7 @@ struct LockOwner {
     const bool handBack = drains % 2 == 1;   // (every other drain hands its records back one by one as they are done)
     for (Op *op = ordered; op != nullptr;) {
       Op *const next = op->next;
-      CHECK(op->state.load() != 1, "record of thread %d published before it ran", op->tid);
+      CHECK(op->state.load() != kOpDone, "record of thread %d published before it ran", op->tid);
       CHECK(op->runs.fetch_add(1) == 0, "record %d of thread %d ran twice", op->idx, op->tid);
       CHECK(op->idx > last[(size_t)op->tid], "thread %d: record %d ran after %d (not in post order)", op->tid, op->idx, last[(size_t)op->tid]);
       last[(size_t)op->tid] = op->idx;
@@ -91,7 +92,7 @@ static void CheckLock(int posters, int opsEach) {
           const int end = std::min(opsEach, i + burst);
           for (int k = i; k < end - 1; k++) owner.lock.Push(mine[(size_t)k]);
           PostAndWait(owner.lock, mine[(size_t)end - 1]);
-          for (int k = i; k < end; k++) CHECK(mine[(size_t)k].state.load(std::memory_order_acquire) == 1, "an earlier record of a burst is not done");
+          for (int k = i; k < end; k++) CHECK(mine[(size_t)k].state.load(std::memory_order_acquire) == kOpDone, "an earlier record of a burst is not done");
         }
       } else {
         for (Op &op : mine) {
@@ -108,10 +109,74 @@ static void CheckLock(int posters, int opsEach) {
   std::printf("ok lock: %d threads, %lld records in %lld drains\n", nThreads, (long long)owner.ran, (long long)owner.drains);
 }
 
+// ---- one way in: TryLockOrPost ---------------------------------------------------------------------------------------------------------
+struct TakeOp {
+  bool forced = false;                 // posted whether the lock is free or not: must never run on the direct path
+  std::atomic<int> runs{0};
+  bool direct = false;                 // run by its own thread, holding the lock
+  std::atomic<int> state{kOpPosted};
+  TakeOp *next = nullptr;
+};
+
+struct TakeOwner {
+  PostingLock<TakeOp, TakeOwner> lock{this, &TakeOwner::Drain};
+  std::atomic<int> holders{0};         // threads inside the lock: 1 wherever a record runs
+  int64_t drained = 0, direct = 0;     // (the lock held)
+  void RunOne(TakeOp &op) {
+    CHECK(holders.fetch_add(1) == 0, "a record ran while another thread held the lock");
+    CHECK(op.runs.fetch_add(1) == 0, "a record ran twice");
+    SpinFor(1);
+    CHECK(holders.fetch_sub(1) == 1, "the lock was shared while a record ran");
+  }
+  void Drain(TakeOp *ordered) {
+    for (TakeOp *op = ordered; op != nullptr; op = op->next) { RunOne(*op); drained++; }
+  }
+};
+
+static void CheckTake(int nThreads, int opsEach) {
+  TakeOwner owner;
+  std::vector<std::vector<TakeOp>> ops((size_t)nThreads);
+  for (auto &v : ops) v = std::vector<TakeOp>((size_t)opsEach);
+  std::atomic<int> finished{0};
+  std::vector<std::thread> threads;
+  for (int t = 0; t < nThreads; t++)
+    threads.emplace_back([&, t] {
+      for (int i = 0; i < opsEach; i++) {
+        TakeOp &op = ops[(size_t)t][(size_t)i];
+        op.forced = (t + i) % 3 == 0;
+        std::unique_lock<PostingLock<TakeOp, TakeOwner>> lk;
+        if (TryLockOrPost(owner.lock, lk, op, op.forced)) {
+          CHECK(!lk.owns_lock(), "a posted call came back holding the lock");
+          CHECK(op.runs.load() == 1, "TryLockOrPost returned before its posted record ran");
+        } else {
+          CHECK(lk.owns_lock(), "a direct call came back without the lock");
+          CHECK(!op.forced, "a forced record came back for the direct path");
+          op.direct = true;
+          owner.RunOne(op);
+          owner.direct++;
+        }
+        if (t % 2 == 0) SpinFor(i % 3);   // (half the threads come back at once: the lock is mostly taken)
+      }
+      finished.fetch_add(1);
+    });
+  JoinWithin(threads, finished, 20);
+  int64_t direct = 0;
+  for (auto &v : ops)
+    for (TakeOp &op : v) {
+      CHECK(op.runs.load() == 1, "a record ran %d times", op.runs.load());
+      CHECK(!(op.forced && op.direct), "a forced record ran on the direct path");
+      direct += op.direct;
+    }
+  CHECK(direct == owner.direct && owner.drained + owner.direct == (int64_t)nThreads * opsEach, "%lld drained + %lld direct records",
+        (long long)owner.drained, (long long)owner.direct);
+  CHECK(owner.drained > 0 && owner.direct > 0, "one of the two outcomes never happened (%lld drained, %lld direct)", (long long)owner.drained, (long long)owner.direct);
+  std::printf("ok take: %d threads, %lld records posted and drained, %lld run by their own threads\n", nThreads, (long long)owner.drained, (long long)owner.direct);
+}
+
 // ---- the combiner -----------------------------------------------------------------------------------------------------------------
 struct Req {
   int64_t iQuiz = -1;
-  std::atomic<int> state{0};
+  std::atomic<int> state{kReqWaiting};
   int64_t result = -1;
   int served = 0;                      // times a result was given (by the leader, or by the client from its context)
   struct Ctx *ctx = nullptr;
@@ -142,7 +207,7 @@ static void ClientCall(Combine &S, int64_t iQuiz, bool nap) {
   Req r;
   r.iQuiz = iQuiz;
   int st = S.comb.Wait(r, nap ? &S.sweepNs : nullptr, nap);
-  if (st == 2) {
+  if (st == kReqLead) {
     S.leads.fetch_add(1);
     S.comb.Linger(20, S.sinceSweep.load(), S.callers);
     int batchNo = 0;
@@ -184,14 +249,14 @@ static void ClientCall(Combine &S, int64_t iQuiz, bool nap) {
         });
     (void)batchNo;
   }
-  if (st == 3) {   // select for yourself out of the context, then let it go
+  if (st == kReqSelect) {   // select for yourself out of the context, then let it go
     SpinFor(3);
     r.result = r.ctx->value[r.slot];
     r.served++;
     r.ctx->readers.fetch_sub(1, std::memory_order_release);
     S.selfSelected.fetch_add(1);
   }
-  CHECK(st == 1 || st == 3, "final state %d", st);
+  CHECK(st == kReqServed || st == kReqSelect, "final state %d", st);
   CHECK(r.served == 1, "request of quiz %lld served %d times", (long long)iQuiz, r.served);
   CHECK(r.result % 1000003 != 0 && (r.result - r.result % 1000003) / 1000003 == iQuiz, "request of quiz %lld got the result %lld", (long long)iQuiz, (long long)r.result);
 }
@@ -221,6 +286,7 @@ static void CheckCombine(int clients, int callsEach) {
 int main(int argc, char **argv) {
   if (argc == 4 && std::strcmp(argv[1], "lock") == 0) CheckLock(std::atoi(argv[2]), std::atoi(argv[3]));
   else if (argc == 4 && std::strcmp(argv[1], "combine") == 0) CheckCombine(std::atoi(argv[2]), std::atoi(argv[3]));
-  else { std::fprintf(stderr, "usage: %s lock|combine <threads> <per thread>\n", argv[0]); return 2; }
+  else if (argc == 4 && std::strcmp(argv[1], "take") == 0) CheckTake(std::atoi(argv[2]), std::atoi(argv[3]));
+  else { std::fprintf(stderr, "usage: %s lock|combine|take <threads> <per thread>\n", argv[0]); return 2; }
   return 0;
 }

@@ -203,8 +203,9 @@ def test_release_of_a_quiz_inside_a_selection_is_refused_not_waited_for(factory)
 
 
 def test_posted_operations_equal_direct_calls(factory):
-    """RecordAnswer and ListTopTargets in their posted form (what a call does that finds the engine taken: hip_engine.h, posted
-    operations) against the direct form: the same transcripts, top lists and errors.  Option post_always forces the form."""
+    """RecordAnswer and ListTopTargets -- then RecordQuizTarget, ReleaseQuiz, StartQuiz and ResumeQuiz -- in their posted form (what
+    a call does that finds the engine taken: hip_engine.h, posted operations) against the direct form: the same transcripts, top
+    lists, quiz ids, posteriors and errors.  Option post_always forces the form."""
     a = _engine(factory, 5, 60, 200, 4, 1)
     b = _engine(factory, 5, 60, 200, 4, 1)
     b.set_option("post_always", 1)
@@ -227,6 +228,27 @@ def test_posted_operations_equal_direct_calls(factory):
     b.release_quiz(qb)
     qa, qb = a.start_quiz(), b.start_quiz()
     assert np.array_equal(a.eval_priorities(qa), b.eval_priorities(qb)) and np.array_equal(a.get_priors(qa), b.get_priors(qb))
+    # ResumeQuiz and ReleaseQuiz in the posted form: the same quiz ids, posteriors, next questions and errors
+    for pairs in ([], [(3, 1)], [(7, 0), (12, 4), (19, 2)], [(59, 3), (0, 0), (31, 2), (44, 1)]):
+        aqs = [interop.AnsweredQuestion(q, ans) for q, ans in pairs]
+        ra, rb = a.resume_quiz(aqs), b.resume_quiz(aqs)
+        assert ra == rb
+        assert np.array_equal(a.get_priors(ra), b.get_priors(rb))
+        assert a.next_question(ra) == b.next_question(rb)
+        if len(pairs) % 2 == 1:          # (released ids are handed out again: the registries stay in step)
+            a.release_quiz(ra)
+            b.release_quiz(rb)
+            for eng, z in ((a, ra), (b, rb)):
+                with pytest.raises(interop.PqaException):
+                    eng.release_quiz(z)  # (gone: the error comes back through the operation)
+    resume_errors = []
+    for eng in (a, b):
+        with pytest.raises(interop.PqaException) as e0:
+            eng.resume_quiz([interop.AnsweredQuestion(2, 1), interop.AnsweredQuestion(60 + 7, 0)])
+        resume_errors.append(str(e0.value))
+    assert resume_errors[0] == resume_errors[1] and "Question index" in resume_errors[0]
+    # (every resume of `b` above was posted: the four lists of the loop and the failing one; none of `a`'s)
+    assert b.get_option("resumes_batched") == 4 + 1 and a.get_option("resumes_batched") == 0
     with pytest.raises(interop.PqaException):
         b.release_quiz(4321)
     with pytest.raises(interop.PqaException):

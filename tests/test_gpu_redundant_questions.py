@@ -1,5 +1,5 @@
 """Question redundancy on the GPU (include/PqaHipExt.h: PqaEngine_EvalQuestionRedundancy, PqaEngine_ListRedundantQuestionsBatch;
-redundancy_kernels.hip; hip_engine_redundancy.cpp).
+redundancy_kernels.hip; hip_engine_sources.cpp).
 
 The model works over get_kb(): with w = vB (0 at a gap target) and p = A * (1 / D), numpy forms the products (w p_sk)(t) p_qk'(t), math.fsum
 adds each of the K x K table entries over the targets that are no gaps, and the formula

@@ -1,5 +1,5 @@
 """Target similarity on the GPU (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity, PqaEngine_ListSimilarTargetsBatch;
-similarity_kernels.hip; hip_engine_similarity.cpp).
+similarity_kernels.hip; hip_engine_sources.cpp).
 
 The model is built from get_kb()'s A and D: ref(s, t) = math.fsum(sqrt(p_qk(s) p_qk(t))) over the questions that are not gaps, divided by
 the number of such questions, p = A / D.  The bar is derived, not measured: every term is positive, device and model terms each carry
