@@ -314,6 +314,39 @@ PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, int64_t nQu
 PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pListOf,
                                                      int64_t nLists, const int64_t *pListCounts, const int64_t *pTargets, int64_t maxCount,
                                                      CiRatedTarget *pDest, int64_t *pCounts, double *pMass);
+/* What each answer WOULD do to a quiz, before the user gives one: for nPairs (quiz pQuizzes[i], GLOBAL question pQuestions[i]) pairs, all
+ * nAnswers would-be posteriors in one call, read-only.  Row r = i * nAnswers + k stands for "pair i answered with k".  The reference has
+ * no such call.
+ *  (a) Posterior: x_t = prior_t * (A[q][k][t] / D[q][t]) (0 at target gaps), total = the reference-order sum of x, p_t = x_t / total --
+ *      RecordAnswer's operations in its order: bit for bit what PqaEngine_SetActiveQuestion(q) + PqaEngine_RecordAnswer(k) would leave
+ *      in that quiz, on Double and Float engines, at every row length.
+ *  (b) pLikelihood[r] (may be NULL) = total: the predictive probability of answer k.
+ *  (c) pEntropy[r] (may be NULL) = -sum p_t log2 p_t over the p_t > 0, in bits: fp64, from the divided values, in a fixed order without
+ *      atomics.  Against -math.fsum(p log2 p) it is within (nTargets + 16) 2^-52 max(1, H) bits.
+ *  (d) Records: pCounts[r] = min(maxCount, candidates) records at pDest + r * maxCount; a candidate is a target that is no gap with
+ *      p_t > 0; probability descending, target id ascending among equals -- the order of PqaEngine_ListTopTargetsAmongBatch and of the
+ *      fast listing (option "top_exact" 0), not the reference's heap order; _prob carries the posterior's own bits.  pDest and pCounts
+ *      may be NULL only when maxCount == 0.
+ *  (e) A dead answer (total is 0 or not finite): likelihood = that total, entropy = a quiet NaN, count 0.
+ *  (f) State: no quiz state changes -- posterior, active question, asked bits, answers, versions, speculative and resident state all stay;
+ *      a NextQuestion that follows returns what it would have returned without the call.  Regular mode only; deferred answers are
+ *      applied first, as in PqaEngine_ListTopTargetsBatch.
+ *  (g) Batch shape: any number of pairs (256 rows per launch sequence); a quiz may appear in several pairs and a pair may repeat; an
+ *      asked question is previewed like any other.  A row's outputs depend on its quiz, question and answer alone.
+ *  (h) Refusals, all decided before anything is launched or written, in this order: negative nPairs or maxCount (NegativeCount);
+ *      maxCount > 256 (IndexOutOfRange: a preview is a screenful, there is no bulk path); a needed buffer NULL (NullArgument); maintenance
+ *      mode or shutdown, as PqaEngine_ListTopTargetsBatch answers them; an unknown quiz ("entry="); a question outside
+ *      [0, nQuestions of the whole knowledge base) or a gap on the engine that holds it (IndexOutOfRange, "entry=", "questionId=").
+ * One workgroup per row computes the posterior into engine scratch and reduces it to likelihood and entropy; the batched listing takes
+ * the scratch rows; records, counts and two doubles per row cross to the host, nothing of size nTargets.
+ * A shard engine (PqaEngineFactory_CreateHipEngineSharded) holds every posterior whole and answers for the pairs whose question it
+ * holds; for the others it writes zeros (likelihood 0.0, entropy 0.0, count 0) -- there is no package: a host takes each pair from
+ * the rank that holds its question (probqa_amd/dist.py: preview_answers_batch).  The one-process sharded engine (PQA_DEVICES) answers
+ * NotImplemented.  Read-only options "preview_calls" / "preview_pairs": the accepted calls and the pairs this engine held; with
+ * "time_sweeps", "preview_device_ns". */
+PQACORE_API void *PqaEngine_PreviewAnswersBatch(void *pvEngine, int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions,
+                                                int64_t maxCount, double *pLikelihood, double *pEntropy,
+                                                CiRatedTarget *pDest, int64_t *pCounts);
 /* Targets that answer like a given one: "more like this" behind PqaEngine_ListTopTargets, and the duplicate hunt in front of
  * PqaEngine_RemoveTargets -- two targets no quiz can ever tell apart are two whose answer distributions agree on every question.
  * With p_qk(t) = A[q][k][t] / D[q][t]:

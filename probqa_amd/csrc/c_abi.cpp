@@ -393,6 +393,10 @@ PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, const int64
                                                      int64_t *pCounts, double *pMass) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListTopTargetsAmongBatch(nQuizzes, pQuizzes, pListOf, nLists, pListCounts, pTargets, maxCount, pDest, pCounts, pMass); });
 }
+PQACORE_API void *PqaEngine_PreviewAnswersBatch(void *pvEngine, const int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions, const int64_t maxCount,
+                                                double *pLikelihood, double *pEntropy, CiRatedTarget *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PreviewAnswersBatch(nPairs, pQuizzes, pQuestions, maxCount, pLikelihood, pEntropy, pDest, pCounts); });
+}
 
 PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
                                                      const int64_t *pQuestions, double *pOut) {

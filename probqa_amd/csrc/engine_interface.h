@@ -173,6 +173,12 @@ class IEngine {
   virtual Error ListSeparatingQuestionsBatch(int64_t, const int64_t *, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) {
     return NoSeparation("ListSeparatingQuestionsBatch");
   }
+  // What every answer to a question would do to a quiz (include/PqaHipExt.h: PqaEngine_PreviewAnswersBatch); the one-process sharded
+  // engine does not offer it.
+  virtual Error PreviewAnswersBatch(int64_t, const int64_t *, const int64_t *, int64_t, double *, double *, CiRatedTarget *, int64_t *) {
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=PreviewAnswersBatch on this engine",
+                        "Answer previews are for whole engines and for shards that separate processes drive.");
+  }
 
  private:
   static Error NoSeparation(const char *what) {

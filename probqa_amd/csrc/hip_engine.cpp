@@ -311,6 +311,8 @@ HipEngine::~HipEngine() {
   hipFree(_dTGap); hipFree(_dQGap); hipFree(_dAqs); hipFree(_dResume); hipHostFree(_hResume); hipFree(_dTopScratch[0]); hipFree(_dTopScratch[1]);
   _hTopBatch.Free(); _hTopQ.Free(); _topAmong.lines.Free();
   hipFree(_topAmong.dLists); hipFree(_topAmong.dPartial); hipFree(_topAmong.dGather);
+  hipFree(_preview.dRows); _preview.lines.Free();
+  for (hipEvent_t e : _preview.ev) if (e) hipEventDestroy(e);
   for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
@@ -394,6 +396,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"priority_host_bytes", &HipEngine::_priorityHostBytes},            // priorities the batched sweeps delivered to the host
       {"among_calls", &HipEngine::_amongCalls},                           // Among calls that were accepted (hip_engine_among.cpp) ...
       {"among_pairs", &HipEngine::_amongPairs},                           // ... and the (quiz, question) pairs of theirs this engine holds
+      {"preview_calls", &HipEngine::_previewCalls},                       // PreviewAnswersBatch calls that were accepted (hip_engine_preview.cpp) ...
+      {"preview_pairs", &HipEngine::_previewPairs},                       // ... the (quiz, question) pairs of theirs this engine holds ...
+      {"preview_device_ns", &HipEngine::_previewDeviceNs},                // ... and, with time_sweeps, their rows and listing kernels between events
       {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events

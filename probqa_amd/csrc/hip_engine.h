@@ -258,6 +258,9 @@ class HipEngine : public IEngine {
   // the best targets within a listed set, and the posterior's total over it (hip_engine_top_among.cpp)
   Error ListTopTargetsAmongBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pListOf, int64_t nLists, const int64_t *pListCounts,
                                  const int64_t *pTargets, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts, double *pMass) override;
+  // what every answer to a question would do to a quiz: likelihood, entropy and best targets of each would-be posterior (hip_engine_preview.cpp)
+  Error PreviewAnswersBatch(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions, int64_t maxCount, double *pLikelihood, double *pEntropy,
+                            CiRatedTarget *pDest, int64_t *pCounts) override;
   // the best next questions by priority (hip_engine_list.cpp): what EvalPriorities / EvalPrioritiesBatch return, listed on the device
   int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
   Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
@@ -501,6 +504,17 @@ class HipEngine : public IEngine {
   } _topAmong;
   Error ValidateTopAmongLocked(int64_t n, const int64_t *pQuizzes, const int64_t *pListOf, int64_t nLists, const int64_t *pListCounts, const int64_t *pTargets,
                                int64_t maxCount, bool haveDest, bool haveCounts);
+  // PreviewAnswersBatch (hip_engine_preview.cpp): the would-be posteriors of a chunk of up to kTopBatchQuizzes rows, _ldT doubles each (also
+  // where a row that does not fit LDS is staged), the pinned result lines (records | counts | likelihood and entropy per row), the events of
+  // option "time_sweeps".  The buffers grow and never shrink.
+  struct PreviewStage {
+    double *dRows = nullptr;
+    size_t rowsBytes = 0;
+    ResultLines lines;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } _preview;
+  Error ValidatePreviewLocked(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions);
+  uint64_t _previewCalls = 0, _previewPairs = 0, _previewDeviceNs = 0;   // read-only "preview_calls", "preview_pairs", "preview_device_ns"
   // ListTopQuestions (hip_engine_list.cpp): what a listing in flight between its two halves is, and the host-coherent lines a batch's
   // results arrive in -- records, then counts, then one flag per quiz.  Between the halves _mu is free (the sharded engine has every
   // shard's listing in flight before it waits for the first), so the single and the batch listing keep a record each -- the single one

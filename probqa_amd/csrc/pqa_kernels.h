@@ -706,6 +706,18 @@ hipError_t LaunchTopTargetsAmong(const KbView &kb, const TopBatchPriors &priors,
 hipError_t LaunchTopAmongGather(const KbView &kb, const TopBatchPriors &priors, const int32_t *listOf, int64_t nQuizzes, const int64_t *offsets,
                                 const int32_t *ids, int64_t longest, double *out, hipStream_t stream);
 
+// PreviewAnswersBatch (preview_kernels.hip): the posteriors RecordAnswer WOULD leave, one workgroup per row.  Row r: the quiz's
+// posterior `prior` (read only) under the rows sA[q][k][.] and mD[q][.] of one question block -- p = x / total, bit for bit
+// RecordAnswer's (nWorkers: its reference-order sum's).  likelihood[r] = total, entropy[r] = -sum p log2 p in bits over the p > 0
+// (either may be null; device or host-coherent); writeRows: p into scratch[r][pitch] (pitch >= ldT), where LaunchTopTargetsBatch
+// takes it for a posterior.  A dead answer (total 0 or not finite): a row of zeros, a quiet NaN for an entropy.  `scratch` is also
+// where x is staged when a row does not fit LDS (PreviewStagesInLds false); otherwise it may be null without writeRows.
+// nRows <= kTopBatchQuizzes; `rows` in device memory.
+struct PreviewRow { const double *prior; const void *rowA, *rowD; };
+bool PreviewStagesInLds(const KbView &kb, int64_t nWorkers);
+hipError_t LaunchPreviewRows(const KbView &kb, const PreviewRow *rows, int64_t nRows, int64_t nWorkers, double *scratch, int64_t pitch, bool writeRows,
+                             double *likelihood, double *entropy, hipStream_t stream);
+
 // Target similarity (similarity_kernels.hip): per source s_i and target t the sum over this cube's questions that are not gaps of
 // sum_k sqrt(p_qk(s_i)) sqrt(p_qk(t)), p_qk(t) = A[q][k][t] / D[q][t], in fp64 whatever the cube's element type.
 //   LaunchSimilaritySums: `sources` (device memory, ids in [0, T)) in tiles of kSimTile -- per tile the sources' columns into `rs`

@@ -93,6 +93,39 @@ struct PriorArgs {
 };
 __device__ __forceinline__ double *prior_stage(const PriorArgs &a, double *lds) { return a.stage ? lds + 8 * a.nWorkers + 1 : a.prior; }
 
+// The un-normalised posterior of one answer, stage[t] = old[t] * (A[t] / D[t]) and 0 at target gaps, over the whole row of a.ldT
+// elements (CERecordAnswerSubtaskMul.cpp:25-37): RecordAnswer's element step, shared by the update kernels (record_answer_body, where
+// `old` is the quiz's posterior itself) and the preview of all answers (preview_kernels.hip, which only reads it).  rowA / rowD: the
+// rows' offsets in elements from a.cube.  COH: as record_answer_body.
+template <bool SMALL, bool COH>
+__device__ __forceinline__ void answer_products(const PriorArgs &a, int64_t rowA, int64_t rowD, const double *old, double *stage) {
+  // (four elements per thread and round: their twelve loads are requested together -- a long row is ~100 rounds of one L2 round
+  //  trip each otherwise; the element arithmetic and its order per element are unchanged)
+  const int64_t step = blockDim.x;
+  int64_t t = threadIdx.x;
+  if constexpr (!SMALL)
+  for (; t + 3 * step < a.ldT; t += 4 * step) {
+    double av[4], dv[4], ov[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      av[e] = cube_ld(a.cube, a.elem, rowA + t + e * step);
+      dv[e] = cube_ld(a.cube, a.elem, rowD + t + e * step);
+      ov[e] = COH ? __hip_atomic_load(old + t + e * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : old[t + e * step];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const double product = ov[e] * (av[e] / dv[e]);          // :31, :34
+      stage[t + e * step] = bit_test(a.tgap, t + e * step) ? 0.0 : product;   // :35-37
+    }
+  }
+  for (; t < a.ldT; t += step) {
+    const double pQaGivenT = cube_ld(a.cube, a.elem, rowA + t) / cube_ld(a.cube, a.elem, rowD + t);   // :31
+    const double ov = COH ? __hip_atomic_load(old + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : old[t];
+    const double product = ov * pQaGivenT;                     // :34
+    stage[t] = bit_test(a.tgap, t) ? 0.0 : product;            // :35-37
+  }
+}
+
 // `top` (optional): the call that follows RecordAnswer in every quiz loop is ListTopTargets (PqaClient.cpp:185, the website,
 // DichotomyTest.cpp:91), and a dependent launch costs ~8 us of dispatch whatever its size -- so the new posterior's top
 // targets are listed here, into host-coherent memory, and ListTopTargets finds them waiting.
@@ -128,33 +161,10 @@ __device__ __forceinline__ void record_answer_body(PriorArgs a, int64_t iQuestio
     rowD = (int64_t)((static_cast<const char *>(rowsElsewhere.d) - static_cast<const char *>(rowsElsewhere.a)) / a.elem);
   }
   double *stage = prior_stage(a, lds);
-  // (four elements per thread and round: their twelve loads are requested together -- a long row is ~100 rounds of one L2 round
-  //  trip each otherwise; the element arithmetic and its order per element are unchanged)
+  answer_products<SMALL, COH>(a, rowA, rowD, a.prior, stage);
+  const double total = reference_order_sum<!SMALL>(stage, nVects, a.nWorkers, lds);
   const int64_t step = blockDim.x;
   int64_t t = threadIdx.x;
-  if constexpr (!SMALL)
-  for (; t + 3 * step < a.ldT; t += 4 * step) {
-    double av[4], dv[4], old[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      av[e] = cube_ld(a.cube, a.elem, rowA + t + e * step);
-      dv[e] = cube_ld(a.cube, a.elem, rowD + t + e * step);
-      old[e] = COH ? __hip_atomic_load(a.prior + t + e * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.prior[t + e * step];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const double product = old[e] * (av[e] / dv[e]);         // :31, :34
-      stage[t + e * step] = bit_test(a.tgap, t + e * step) ? 0.0 : product;   // :35-37
-    }
-  }
-  for (; t < a.ldT; t += step) {
-    const double pQaGivenT = cube_ld(a.cube, a.elem, rowA + t) / cube_ld(a.cube, a.elem, rowD + t);   // :31
-    const double old = COH ? __hip_atomic_load(a.prior + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.prior[t];
-    const double product = old * pQaGivenT;                    // :34
-    stage[t] = bit_test(a.tgap, t) ? 0.0 : product;            // :35-37
-  }
-  const double total = reference_order_sum<!SMALL>(stage, nVects, a.nWorkers, lds);
-  t = threadIdx.x;
   if constexpr (!SMALL)
   for (; t + 3 * step < a.ldT; t += 4 * step) {
     double x[4];

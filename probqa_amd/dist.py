@@ -820,6 +820,58 @@ def owner_in(bounds: List[int], question: int) -> int:
     return bisect.bisect_right(bounds, question)
 
 
+# ---- what each answer would do to a quiz, over the shards ---------------------------------------------------------------------------
+# Every rank holds every posterior whole, and a would-be posterior needs nothing but the previewed question's rows: the rank that holds
+# the question answers for the pair, the others leave zeros.  There is no package and nothing to sum: one status word, one all-gather
+# of the ranks' results, and every rank takes each pair from its owner.
+
+
+def preview_answers_batch(engine, pairs, max_count: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                          device: Optional[torch.device] = None) -> list:
+    """PqaEngine_PreviewAnswersBatch on the shards of `world` ranks: a collective every rank calls with the same (quiz, GLOBAL question)
+    pairs and max_count.  Every rank returns the same lists of interop.AnswerPreview, K per pair.  All or none: a rank whose call is
+    refused still takes part in the status word, after which every rank raises the first failing rank's text."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    error, mine = None, None
+    try:
+        mine = engine.preview_answers_batch(pairs, max_count)
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)
+    if not ranks.multi:
+        return mine
+    bounds = gather_bounds(engine, group)
+    # one [rows, 3 + 2 max_count] tensor of 8-byte words per rank: likelihood and entropy bits, the count, then (target, probability bits)
+    flat = [p for previews in mine for p in previews]
+    words = torch.zeros((max(len(flat), 1), 3 + 2 * max_count), dtype=torch.int64)
+    if flat:
+        words[:len(flat), 0] = torch.tensor([p.likelihood for p in flat], dtype=torch.float64).view(torch.int64)
+        words[:len(flat), 1] = torch.tensor([p.entropy for p in flat], dtype=torch.float64).view(torch.int64)
+    for r, p in enumerate(flat):
+        words[r, 2] = len(p.targets)
+        if p.targets:
+            words[r, 3:3 + 2 * len(p.targets):2] = torch.tensor([t.i_target for t in p.targets], dtype=torch.int64)
+            words[r, 4:4 + 2 * len(p.targets):2] = torch.tensor([t.prob for t in p.targets], dtype=torch.float64).view(torch.int64)
+    parts = ranks.gather(words)
+    k = len(mine[0]) if mine else 0
+
+    def previews_of(part, i):
+        out = []
+        for r in range(i * k, (i + 1) * k):
+            row = part[r]
+            n = int(row[2])
+            vals = row[:2].contiguous().view(torch.float64).tolist()
+            ids = row[3:3 + 2 * n:2].tolist()
+            probs = row[4:4 + 2 * n:2].contiguous().view(torch.float64).tolist()
+            out.append(interop.AnswerPreview(vals[0], vals[1], [interop.RatedTarget(t, pr) for t, pr in zip(ids, probs)]))
+        return out
+
+    return [previews_of(parts[owner_in(bounds, q)], i) for i, (_, q) in enumerate(pairs)]
+
+
 def _replicated(call, rank: int, world: int, group, device: Optional[torch.device]):
     """One replicated maintenance call and a status word: if any rank failed, every rank raises the first failure.  (The calls
     validate against state every rank holds alike, so they fail on all ranks or on none; what can fail on one rank alone is its

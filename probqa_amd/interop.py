@@ -176,6 +176,7 @@ HIP_EXPORTS = {
     "PqaEngine_RecordQuizTargetBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl]),
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_ListTopTargetsAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64, _pdbl]),
+    "PqaEngine_PreviewAnswersBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_EvalTargetSimilarity": (_vp, [_vp, _i64, _pi64, _pdbl, _i64]),
     "PqaEngine_ListSimilarTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaHip_PackTargetSimilaritySums": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
@@ -301,6 +302,19 @@ class RatedTarget:
 
     def __repr__(self):
         return f"[t={self.i_target}, p={self.prob}]"
+
+
+class AnswerPreview:
+    """What one answer would do to a quiz (PqaEngine.preview_answers_batch): the answer's predictive probability, the entropy in
+    bits of the posterior it would leave (NaN for a dead answer) and that posterior's best targets."""
+
+    def __init__(self, likelihood: float, entropy: float, targets: List[RatedTarget]):
+        self.likelihood = likelihood
+        self.entropy = entropy
+        self.targets = targets
+
+    def __repr__(self):
+        return f"[l={self.likelihood}, H={self.entropy}, {self.targets}]"
 
 
 class EngineDefinition:
@@ -1067,6 +1081,27 @@ class PqaEngine:
     def list_top_targets_among(self, i_quiz: int, targets, max_count: int) -> Tuple[List[RatedTarget], float]:
         got, mass = self.list_top_targets_among_batch([i_quiz], [list(targets)], max_count)
         return got[0], mass[0]
+
+    # ---- what each answer would do to a quiz (include/PqaHipExt.h: PqaEngine_PreviewAnswersBatch) ----
+    def preview_answers_batch(self, pairs, max_count: int) -> List[List[AnswerPreview]]:
+        """For every (quiz, GLOBAL question) of `pairs`, per answer k what recording k would leave: the answer's likelihood, the
+        entropy of the would-be posterior in bits and its best max_count (<= 256) targets -- RecordAnswer's own bits, probability
+        descending, target id ascending among equals.  Read-only: no quiz changes.  A quiz may appear in several pairs.  On a shard
+        engine the pairs whose question another rank holds come back as zeros (dist.preview_answers_batch merges the ranks)."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n, k = len(pr), self.copy_dims().n_answers
+        quizzes, questions = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        rows = max(n * k, 1)
+        likelihood, entropy = np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.float64)
+        counts = np.zeros(rows, dtype=np.int64)
+        arr = (CiRatedTarget * max(n * k * max_count, 1))()
+        _check(_lib.PqaEngine_PreviewAnswersBatch(self.c_engine, n, quizzes.ctypes.data_as(_pi64), questions.ctypes.data_as(_pi64), max_count,
+                                                  likelihood.ctypes.data_as(_pdbl), entropy.ctypes.data_as(_pdbl), arr, counts.ctypes.data_as(_pi64)))
+        targets = self._records(arr, counts, n * k, max_count, RatedTarget)
+        return [[AnswerPreview(float(likelihood[r]), float(entropy[r]), targets[r]) for r in range(i * k, (i + 1) * k)] for i in range(n)]
+
+    def preview_answers(self, i_quiz: int, i_question: int, max_count: int) -> List[AnswerPreview]:
+        return self.preview_answers_batch([(i_quiz, i_question)], max_count)[0]
 
     # ---- targets that answer like a given one (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity and its neighbours) ----
     def eval_target_similarity(self, sources) -> np.ndarray:
