@@ -347,6 +347,60 @@ PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, int64_t nQu
 PQACORE_API void *PqaEngine_PreviewAnswersBatch(void *pvEngine, int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions,
                                                 int64_t maxCount, double *pLikelihood, double *pEntropy,
                                                 CiRatedTarget *pDest, int64_t *pCounts);
+/* The answers a quiz holds: returns their count and writes the first min(count, capacity) of them to pDest, in the order
+ * PqaEngine_RecordQuizTarget would train them (the resumed ones, then the recorded ones), with GLOBAL question ids.  pDest == NULL with
+ * capacity == 0 only counts.  Errors (the return is -1): an unknown quiz as PqaEngine_ListTopTargets answers it; a negative capacity
+ * (NegativeCount); pDest NULL with capacity > 0 (NullArgument).  Whole engines, shard engines and the one-process sharded engine (which
+ * hands its gathered answers to the shards first) answer alike: every engine records every answer of every quiz. */
+PQACORE_API int64_t PqaHip_GetQuizAnswers(void *pvEngine, void **ppError, int64_t iQuiz, CiAnsweredQuestion *pDest, int64_t capacity);
+/* A quiz with each of its answers LEFT OUT, looking back where PqaEngine_PreviewAnswersBatch looks ahead: row i stands for quiz
+ * pQuizzes[i] as if its answer at position pPositions[i] (a position of PqaHip_GetQuizAnswers) had never been given.  Read-only; the
+ * reference has no such call and no undo.
+ *  (a) Posterior: bit for bit what PqaEngine_ResumeQuiz over the remaining answers, in their order, leaves on this engine under its
+ *      current options "workers" and "bug_compat", on Double and Float engines at every row length -- the exponent-separated product
+ *      chain, the exponent maximum and correction, the reference-order sum over `workers` subtasks, the division.  A quiz with one
+ *      answer leaves PqaEngine_StartQuiz's posterior; a question answered more than once is a chain like any other.  The review reads
+ *      the knowledge base as it is now, as ResumeQuiz does, and the quiz's recorded answers -- not the quiz's own posterior.
+ *  (b) pLikelihood[i] (may be NULL) = the predictive probability, under that posterior, of the answer that was left out: the bits
+ *      PqaEngine_PreviewAnswersBatch returns for (a twin quiz resumed from the remaining answers, the left-out question) at the
+ *      left-out answer (the reference-order sum over max(1, workers - 1) subtasks).  A small value marks the answer the others
+ *      contradict.
+ *  (c) pEntropy[i] (may be NULL) = -sum p_t log2 p_t over the p_t > 0, in bits: fp64, from the divided values, in a fixed order without
+ *      atomics.  Against -math.fsum(p log2 p) it is within (nTargets + 16) 2^-52 max(1, H) bits.
+ *  (d) Records: pCounts[i] = min(maxCount, candidates) records at pDest + i * maxCount; a candidate is a target that is no gap with
+ *      p_t > 0; probability descending, target id ascending among equals -- the order of PqaEngine_ListTopTargetsAmongBatch and of the
+ *      fast listing (option "top_exact" 0), not the reference's heap order; _prob carries the posterior's own bits.  maxCount <= 256;
+ *      pDest and pCounts may be NULL only when maxCount == 0.
+ *  (e) A dead row -- the remaining answers would make PqaEngine_ResumeQuiz fail with I64Underflow, or their total is 0 or not finite:
+ *      likelihood = a quiet NaN, entropy = a quiet NaN, count 0.  It is no error of the call.
+ *  (f) State: nothing of any quiz changes -- posterior, asked bits, answers, active question, versions, speculative and resident state
+ *      all stay; a NextQuestion that follows returns what it would have returned without the call.  Regular mode only.
+ *  (g) Batch shape: any number of pairs; a quiz may appear under many positions and a pair may repeat.  A row's outputs depend on its
+ *      quiz and position alone, not on the rest of the call or on where its chunks fall.
+ *  (h) Refusals, all decided before anything is launched or written, in this order: negative nPairs or maxCount (NegativeCount);
+ *      maxCount > 256 (IndexOutOfRange); a needed buffer NULL (NullArgument); maintenance mode or shutdown, as
+ *      PqaEngine_PreviewAnswersBatch answers them; an unknown quiz ("entry="); a position outside [0, the quiz's answer count)
+ *      (IndexOutOfRange, "entry=", "position=": a quiz without answers refuses every position); on a shard engine an answered question
+ *      another shard holds whose rows the row needs -- a remaining one, or the left-out one when pLikelihood is given -- (NotImplemented,
+ *      PqaEngine_ResumeQuiz's wording, pointing at PqaEngine_ReviewAnswersBatchFromRows).
+ * Two launches and a listing per chunk (review_kernels.hip): the leave-one-out chains of a quiz share its answers' ratios, one division
+ * per (answer, target), and their prefixes -- n divisions and about n^2 / 2 multiplications per target where n resumes take n (n - 1) of
+ * each; a workgroup per row then normalises as ResumeQuiz does.  Rows go in chunks of at most 256, a quiz's rows together where they fit,
+ * a chunk's scratch within 64 MiB; records, counts and two doubles per row cross to the host, nothing of size nTargets.
+ * The one-process sharded engine (PQA_DEVICES) answers NotImplemented.  Read-only options "review_calls" / "review_rows": the accepted
+ * calls and their pairs; with "time_sweeps", "review_device_ns"; "review_lds_answers": the most answers whose ratios stay in LDS. */
+PQACORE_API void *PqaEngine_ReviewAnswersBatch(void *pvEngine, int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions,
+                                               int64_t maxCount, double *pLikelihood, double *pEntropy,
+                                               CiRatedTarget *pDest, int64_t *pCounts);
+/* ... on a shard that a process of its own drives: pair i's quiz has its n answers' row pairs in slots pRowFirst[i] .. pRowFirst[i] + n - 1
+ * of the package pRows, in answer order; slot format and pitch are PqaHip_PackAnswerRows' (PqaHip_AnswerRowSlotBytes).  Slots of
+ * questions this engine holds need not be filled and are not read; pRows may be NULL where no needed row is another engine's.  A
+ * package in host memory is staged under option "rows_stage".  Pairs of one quiz name the same slots.  Everything else as above, with
+ * pRowFirst NULL (NullArgument) and a negative slot (IndexOutOfRange, "entry=") among the refusals.  The posterior is replicated, so
+ * every rank returns the whole engine's bits and nothing is merged (probqa_amd/dist.py: review_answers_batch). */
+PQACORE_API void *PqaEngine_ReviewAnswersBatchFromRows(void *pvEngine, int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions,
+                                                       int64_t maxCount, double *pLikelihood, double *pEntropy,
+                                                       CiRatedTarget *pDest, int64_t *pCounts, const void *pRows, const int64_t *pRowFirst);
 /* Targets that answer like a given one: "more like this" behind PqaEngine_ListTopTargets, and the duplicate hunt in front of
  * PqaEngine_RemoveTargets -- two targets no quiz can ever tell apart are two whose answer distributions agree on every question.
  * With p_qk(t) = A[q][k][t] / D[q][t]:

@@ -20,6 +20,7 @@
 
 #include "c_abi_shims.h"
 #include "hip_engine.h"
+#include "review_plan.h"
 #include "sampled_part.h"
 
 using pqa::AQ;
@@ -396,6 +397,18 @@ PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, const int64
 PQACORE_API void *PqaEngine_PreviewAnswersBatch(void *pvEngine, const int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions, const int64_t maxCount,
                                                 double *pLikelihood, double *pEntropy, CiRatedTarget *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.PreviewAnswersBatch(nPairs, pQuizzes, pQuestions, maxCount, pLikelihood, pEntropy, pDest, pCounts); });
+}
+PQACORE_API int64_t PqaHip_GetQuizAnswers(void *pvEngine, void **ppError, const int64_t iQuiz, CiAnsweredQuestion *pDest, const int64_t capacity) {
+  return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.GetQuizAnswers(err, iQuiz, reinterpret_cast<AQ *>(pDest), capacity); });
+}
+PQACORE_API void *PqaEngine_ReviewAnswersBatch(void *pvEngine, const int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions, const int64_t maxCount,
+                                               double *pLikelihood, double *pEntropy, CiRatedTarget *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ReviewAnswersBatch(nPairs, pQuizzes, pPositions, maxCount, pLikelihood, pEntropy, pDest, pCounts); });
+}
+PQACORE_API void *PqaEngine_ReviewAnswersBatchFromRows(void *pvEngine, const int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions, const int64_t maxCount,
+                                                       double *pLikelihood, double *pEntropy, CiRatedTarget *pDest, int64_t *pCounts, const void *pRows,
+                                                       const int64_t *pRowFirst) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ReviewAnswersBatchFromRows(nPairs, pQuizzes, pPositions, maxCount, pLikelihood, pEntropy, pDest, pCounts, pRows, pRowFirst); });
 }
 
 PQACORE_API void *PqaEngine_EvalPrioritiesAmongBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
@@ -920,6 +933,22 @@ static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_
     pOut[0] = (int64_t)tiles.size() - 1;
     for (size_t k = 0; k < tiles.size(); k++) pOut[1 + k] = tiles[k];
     return 1 + (int64_t)tiles.size();
+  }
+  if (w == "review_plan") {   // {ldT, rowCap, budgetBytes, ldsAnswers, nPairs, then nPairs x {quiz, its answer count}} -> {nChunks, then per chunk its count and its pairs}
+    if (nIn < 5 || pIn[0] < 1 || pIn[1] < 1 || pIn[2] < 0 || pIn[3] < 0 || pIn[4] < 0 || nIn != 5 + 2 * pIn[4]) return -1;
+    std::vector<int64_t> quizOf((size_t)pIn[4]), answersOf((size_t)pIn[4]);
+    for (int64_t i = 0; i < pIn[4]; i++) {
+      quizOf[(size_t)i] = pIn[5 + 2 * i];
+      answersOf[(size_t)i] = pIn[6 + 2 * i];
+      if (answersOf[(size_t)i] < 1) return -1;
+    }
+    const std::vector<std::vector<int64_t>> chunks = pqa::PlanReviewChunks(pIn[4], quizOf.data(), answersOf.data(), pIn[0], pIn[1], pIn[2], pIn[3]);
+    if (nOut < 1) return -1;
+    pOut[0] = (int64_t)chunks.size();
+    nRes = 1;
+    for (const std::vector<int64_t> &c : chunks)
+      if (!put(c)) return -1;
+    return nRes;
   }
   if (w == "better_pick") {
     if (nIn % 2 != 0 || nOut < 2) return -1;

@@ -179,6 +179,17 @@ class IEngine {
     return Error::MakeP(ErrCode::NotImplemented, "Feature=PreviewAnswersBatch on this engine",
                         "Answer previews are for whole engines and for shards that separate processes drive.");
   }
+  // A quiz with each of its answers left out (include/PqaHipExt.h: PqaEngine_ReviewAnswersBatch) and the quiz's recorded answers; the
+  // one-process sharded engine reads the answers and does not offer the review.
+  virtual int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) = 0;
+  virtual Error ReviewAnswersBatch(int64_t, const int64_t *, const int64_t *, int64_t, double *, double *, CiRatedTarget *, int64_t *) {
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=ReviewAnswersBatch on this engine",
+                        "Answer reviews are for whole engines and for shards that separate processes drive.");
+  }
+  virtual Error ReviewAnswersBatchFromRows(int64_t n, const int64_t *pQuizzes, const int64_t *pPositions, int64_t maxCount, double *pLikelihood, double *pEntropy,
+                                           CiRatedTarget *pDest, int64_t *pCounts, const void *, const int64_t *) {
+    return ReviewAnswersBatch(n, pQuizzes, pPositions, maxCount, pLikelihood, pEntropy, pDest, pCounts);
+  }
 
  private:
   static Error NoSeparation(const char *what) {

@@ -313,6 +313,8 @@ HipEngine::~HipEngine() {
   hipFree(_topAmong.dLists); hipFree(_topAmong.dPartial); hipFree(_topAmong.dGather);
   hipFree(_preview.dRows); _preview.lines.Free();
   for (hipEvent_t e : _preview.ev) if (e) hipEventDestroy(e);
+  hipFree(_review.dRows); hipFree(_review.dRatios); _review.lines.Free();
+  for (hipEvent_t e : _review.ev) if (e) hipEventDestroy(e);
   for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
@@ -399,6 +401,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"preview_calls", &HipEngine::_previewCalls},                       // PreviewAnswersBatch calls that were accepted (hip_engine_preview.cpp) ...
       {"preview_pairs", &HipEngine::_previewPairs},                       // ... the (quiz, question) pairs of theirs this engine holds ...
       {"preview_device_ns", &HipEngine::_previewDeviceNs},                // ... and, with time_sweeps, their rows and listing kernels between events
+      {"review_calls", &HipEngine::_reviewCalls},                         // ReviewAnswersBatch calls that were accepted (hip_engine_review.cpp) ...
+      {"review_rows", &HipEngine::_reviewRows},                           // ... their (quiz, position) pairs ...
+      {"review_device_ns", &HipEngine::_reviewDeviceNs},                  // ... and, with time_sweeps, their chains, rows and listing kernels between events
       {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
@@ -462,6 +467,7 @@ int64_t HipEngine::GetOption(const char *name) const {
   if (n == "server_active") return (_opt.server && ServerUsable()) ? 1 : 0;
   if (n == "allowed_cpus") return AllowedCpus();
   if (n == "debug_mailbox") return (int64_t)(uintptr_t)_hMailbox;
+  if (n == "review_lds_answers") return kReviewLdsAnswers;   // the answers a quiz may hold for its review's ratios to stay in LDS (review_kernels.hip)
   if (n == "precision") return _precType;
   if (n == "ldT") return _ldT;
   if (n == "capQ") return _capQ;   // questions the allocation holds: like ldT it only grows (ReallocKB)

@@ -261,6 +261,13 @@ class HipEngine : public IEngine {
   // what every answer to a question would do to a quiz: likelihood, entropy and best targets of each would-be posterior (hip_engine_preview.cpp)
   Error PreviewAnswersBatch(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions, int64_t maxCount, double *pLikelihood, double *pEntropy,
                             CiRatedTarget *pDest, int64_t *pCounts) override;
+  // a quiz's recorded answers, and the quiz with each of them left out: likelihood of the left-out answer, entropy and best targets of the
+  // others' posterior (hip_engine_review.cpp)
+  int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override;
+  Error ReviewAnswersBatch(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions, int64_t maxCount, double *pLikelihood, double *pEntropy,
+                           CiRatedTarget *pDest, int64_t *pCounts) override;
+  Error ReviewAnswersBatchFromRows(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions, int64_t maxCount, double *pLikelihood, double *pEntropy,
+                                   CiRatedTarget *pDest, int64_t *pCounts, const void *pRows, const int64_t *pRowFirst) override;
   // the best next questions by priority (hip_engine_list.cpp): what EvalPriorities / EvalPrioritiesBatch return, listed on the device
   int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
   Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
@@ -515,6 +522,18 @@ class HipEngine : public IEngine {
   } _preview;
   Error ValidatePreviewLocked(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions);
   uint64_t _previewCalls = 0, _previewPairs = 0, _previewDeviceNs = 0;   // read-only "preview_calls", "preview_pairs", "preview_device_ns"
+  // ReviewAnswersBatch (hip_engine_review.cpp): per row of a chunk _ldT mantissas (then the divided row) and, behind all of them, _ldT
+  // exponent sums; the ratios of the chunk's quizzes that do not stay in LDS; the pinned result lines (records | counts | likelihood and
+  // entropy per row); the events of option "time_sweeps".  The buffers grow and never shrink.
+  struct ReviewStage {
+    double *dRows = nullptr, *dRatios = nullptr;
+    size_t rowsBytes = 0, ratiosBytes = 0;
+    ResultLines lines;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } _review;
+  Error ReviewAnswers(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions, int64_t maxCount, double *pLikelihood, double *pEntropy,
+                      CiRatedTarget *pDest, int64_t *pCounts, bool fromRows, const void *pRows, const int64_t *pRowFirst);
+  uint64_t _reviewCalls = 0, _reviewRows = 0, _reviewDeviceNs = 0;   // read-only "review_calls", "review_rows", "review_device_ns"
   // ListTopQuestions (hip_engine_list.cpp): what a listing in flight between its two halves is, and the host-coherent lines a batch's
   // results arrive in -- records, then counts, then one flag per quiz.  Between the halves _mu is free (the sharded engine has every
   // shard's listing in flight before it waits for the first), so the single and the batch listing keep a record each -- the single one

@@ -718,6 +718,26 @@ bool PreviewStagesInLds(const KbView &kb, int64_t nWorkers);
 hipError_t LaunchPreviewRows(const KbView &kb, const PreviewRow *rows, int64_t nRows, int64_t nWorkers, double *scratch, int64_t pitch, bool writeRows,
                              double *likelihood, double *entropy, hipStream_t stream);
 
+// ReviewAnswersBatch (review_kernels.hip): the posteriors ResumeQuiz would leave with one answer left out.  Row r of a chunk has ldT-long
+// (pitch >= ldT) lines mants[r] and exps[r].
+//   LaunchReviewChains: grid.y = a distinct quiz of the chunk.  `rows`: its 2 nAnswered row pointers as ResumeSlot's; `requests`: its
+//     requested (position, row of the chunk) pairs, position ascending, a position may repeat; `ratios`: nAnswered x ldT doubles of scratch,
+//     or null when nAnswered <= maxLdsAnswers (<= kReviewLdsAnswers) and the ratios stay in LDS.  Leaves every requested row's mantissas
+//     and exponent sums; rows without remaining answers (nAnswered == 1) are written too and ignored by the rows kernel.
+//   LaunchReviewRows: a workgroup per row normalises it as resume_quiz_body does (nWorkers subtasks), leaves the divided row in mants[r]
+//     (a posterior for LaunchTopTargetsBatch), the entropy in bits, and the likelihood of the left-out answer (rowA / rowD) under it as
+//     PreviewAnswersBatch computes it (max(1, nWorkers - 1) subtasks).  likelihood / entropy: device or host-coherent, either may be null.
+//     nRemaining == 0: StartQuiz's posterior.  A dead row: zeros, two quiet NaNs.
+// Everything in device memory; nQuizzes, nRows <= kTopBatchQuizzes.
+constexpr int64_t kReviewLdsAnswers = 24;   // 24 x 256 doubles = 48 KiB: three chains workgroups per CU
+struct ReviewRequest { int32_t position, row; };
+struct ReviewQuiz { const void *const *rows; const ReviewRequest *requests; double *ratios; int64_t nAnswered, nRequests; };
+struct ReviewRow { const void *rowA, *rowD; int64_t nRemaining; };
+hipError_t LaunchReviewChains(const KbView &kb, const ReviewQuiz *quizzes, int64_t nQuizzes, int64_t maxLdsAnswers, bool bugCompat, double *mants, int64_t *exps,
+                              int64_t pitch, hipStream_t stream);
+hipError_t LaunchReviewRows(const KbView &kb, const ReviewRow *rows, int64_t nRows, int64_t nWorkers, double *mants, int64_t *exps, int64_t pitch,
+                            double *likelihood, double *entropy, hipStream_t stream);
+
 // Target similarity (similarity_kernels.hip): per source s_i and target t the sum over this cube's questions that are not gaps of
 // sum_k sqrt(p_qk(s_i)) sqrt(p_qk(t)), p_qk(t) = A[q][k][t] / D[q][t], in fp64 whatever the cube's element type.
 //   LaunchSimilaritySums: `sources` (device memory, ids in [0, T)) in tiles of kSimTile -- per tile the sources' columns into `rs`

@@ -126,6 +126,36 @@ __device__ __forceinline__ void answer_products(const PriorArgs &a, int64_t rowA
   }
 }
 
+// ---- ResumeQuiz's element steps (CEUpdatePriorsSubtaskMul, CpuEngine::NormalizePriors), shared by resume_quiz_body
+// (prior_kernels.hip) and the leave-one-out chains of review_kernels.hip.
+__device__ __forceinline__ int ceil_log2_u64(uint64_t val) {  // SRPlatform/Interface/SRMath.h:46-51
+  if (!val) return 0;
+  const int index = 63 - __clzll((long long)val);
+  return index + ((val & (val - 1)) ? 1 : 0);
+}
+// One factor of a target's product chain: the product's exponent moves into the sum, the mantissa keeps exponent 0.  The first
+// factor is vB[t] as it is (mant = vB[t], ex = 0): CEUpdatePriorsSubtaskMul.cpp:53-59; the others :75-82.
+__device__ __forceinline__ void chain_step(double &mant, int64_t &ex, double pQaGivenT) {
+  const uint64_t up = d2u(mant * pQaGivenT);
+  mant = u2d(kExp0Up | (up & ~kExpMaskUp));    // MakeExponent0
+  ex += (int64_t)((up & kExpMaskUp) >> 52);    // ExtractExponents64<false>
+}
+// CENormPriorsSubtaskMax's operand
+__device__ __forceinline__ long long chain_total_exp(double mant, int64_t ex) { return ex + (long long)((d2u(mant) & kExpMaskUp) >> 52); }
+// The correction that brings the largest exponent to the top of the range, INT64_MIN for I64Underflow (CpuEngine.cpp:316-322)
+__device__ __forceinline__ long long exponent_correction(long long fullMax, int64_t T) {
+  const long long highBound = 1023 + 1023 - ceil_log2_u64((uint64_t)T) - 2;  // :316
+  const long long minAllowed = INT64_MIN + highBound + 1;                     // :317
+  return fullMax <= minAllowed ? INT64_MIN : highBound - fullMax;             // :318-322
+}
+// CENormPriorsSubtaskCorrSum::Process (CENormPriorsSubtaskCorrSum.cpp:25-40): the corrected exponent back into the mantissa
+__device__ __forceinline__ double replace_exponent(double mant, int64_t ex, long long corrExp, bool gap) {
+  const uint64_t um = d2u(mant);
+  const long long normExp = ex + (long long)((um & kExpMaskUp) >> 52) + corrExp;
+  const bool assume0 = (1 > normExp) || gap;
+  return assume0 ? 0.0 : u2d(((uint64_t)normExp << 52) | (um & ~kExpMaskUp));  // ReplaceExponents
+}
+
 // `top` (optional): the call that follows RecordAnswer in every quiz loop is ListTopTargets (PqaClient.cpp:185, the website,
 // DichotomyTest.cpp:91), and a dependent launch costs ~8 us of dispatch whatever its size -- so the new posterior's top
 // targets are listed here, into host-coherent memory, and ListTopTargets finds them waiting.

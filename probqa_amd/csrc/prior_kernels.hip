@@ -78,12 +78,6 @@ __global__ __launch_bounds__(SMALL ? kSmallThreads : kThreads) void record_answe
   record_answer_body<SMALL, false>(a, s.iQuestion, s.iAnswer, s.asked, top, lds, &topScratch, RowPair{s.rowA, s.rowD});
 }
 
-__device__ __forceinline__ int ceil_log2_u64(uint64_t val) {  // SRPlatform/Interface/SRMath.h:46-51
-  if (!val) return 0;
-  const int index = 63 - __clzll((long long)val);
-  return index + ((val & (val - 1)) ? 1 : 0);
-}
-
 // rows: for answered question i the rows sA[q_i][a_i][.] (rows[2i]) and mD[q_i][.] (rows[2i + 1]) -- pointers instead of
 // indices, so that the rows of a question held by ANOTHER device of the process (a shard of the question axis,
 // sharded_engine.cpp) are read in place over xGMI peer access.
@@ -96,25 +90,15 @@ __device__ __forceinline__ void resume_quiz_body(PriorArgs a, int64_t *__restric
   // a8: every target runs its own chain of products over the answered questions, mantissa and exponent kept apart.
   long long myMax = INT64_MIN;
   for (int64_t t = threadIdx.x; t < a.ldT; t += blockDim.x) {
-    double mant;
-    int64_t ex;
-    {
-      const double pQaGivenT = cube_ld(rows[0], a.elem, t) / cube_ld(rows[1], a.elem, t);
-      const double oldMant = bugCompat ? a.vB[t & 3] : a.vB[t];  // CEUpdatePriorsSubtaskMul.cpp:53 loads pvB, not pvB+j
-      const uint64_t up = d2u(oldMant * pQaGivenT);              // :54
-      mant = u2d(kExp0Up | (up & ~kExpMaskUp));                  // :56 MakeExponent0
-      ex = (int64_t)((up & kExpMaskUp) >> 52);                   // :59 ExtractExponents64<false>
-    }
-    for (int64_t i = 1; i < nAnswered; i++) {
-      const double pQaGivenT = cube_ld(rows[2 * i], a.elem, t) / cube_ld(rows[2 * i + 1], a.elem, t);
-      const uint64_t up = d2u(mant * pQaGivenT);                 // :75
-      mant = u2d(kExp0Up | (up & ~kExpMaskUp));                  // :77
-      ex += (int64_t)((up & kExpMaskUp) >> 52);                  // :80-82
-    }
+    double mant = bugCompat ? a.vB[t & 3] : a.vB[t];  // CEUpdatePriorsSubtaskMul.cpp:53 loads pvB, not pvB+j
+    int64_t ex = 0;
+    chain_step(mant, ex, cube_ld(rows[0], a.elem, t) / cube_ld(rows[1], a.elem, t));   // :54-59
+    for (int64_t i = 1; i < nAnswered; i++)
+      chain_step(mant, ex, cube_ld(rows[2 * i], a.elem, t) / cube_ld(rows[2 * i + 1], a.elem, t));   // :75-82
     a.prior[t] = mant;
     exps[t] = ex;
     // a9 part 1: CENormPriorsSubtaskMax (gap lanes retain the running maximum)
-    const long long totExp = ex + (long long)((d2u(mant) & kExpMaskUp) >> 52);
+    const long long totExp = chain_total_exp(mant, ex);
     if (t < 4 * nVects && !bit_test(a.tgap, t) && totExp > myMax) myMax = totExp;
   }
 #pragma unroll
@@ -127,26 +111,17 @@ __device__ __forceinline__ void resume_quiz_body(PriorArgs a, int64_t *__restric
   if (threadIdx.x == 0) {
     long long fullMax = sMax[0];
     for (int w = 1; w < nWaves; w++) fullMax = sMax[w] > fullMax ? sMax[w] : fullMax;
-    const long long highBound = 1023 + 1023 - ceil_log2_u64((uint64_t)a.T) - 2;  // CpuEngine.cpp:316
-    const long long minAllowed = INT64_MIN + highBound + 1;                      // :317
+    const long long corr = exponent_correction(fullMax, a.T);   // CpuEngine.cpp:316-322
     status[1] = fullMax;
-    if (fullMax <= minAllowed) {                                                 // :318-321 I64Underflow
-      status[0] = 16;
-      sCorr = INT64_MIN;
-    } else {
-      status[0] = 0;
-      sCorr = highBound - fullMax;                                               // :322
-    }
+    status[0] = corr == INT64_MIN ? 16 : 0;                     // :318-321 I64Underflow
+    sCorr = corr;
   }
   __syncthreads();
   const long long corrExp = sCorr;
   if (corrExp == INT64_MIN) return;  // error: priors left un-normalised, the host destroys the quiz
   // a9 part 2: CENormPriorsSubtaskCorrSum::Process (CENormPriorsSubtaskCorrSum.cpp:25-40)
   for (int64_t t = threadIdx.x; t < a.ldT; t += blockDim.x) {
-    const uint64_t um = d2u(a.prior[t]);
-    const long long normExp = exps[t] + (long long)((um & kExpMaskUp) >> 52) + corrExp;
-    const bool assume0 = (1 > normExp) || bit_test(a.tgap, t);
-    a.prior[t] = assume0 ? 0.0 : u2d(((uint64_t)normExp << 52) | (um & ~kExpMaskUp));  // ReplaceExponents
+    a.prior[t] = replace_exponent(a.prior[t], exps[t], corrExp, bit_test(a.tgap, t));
     exps[t] = 0;
   }
   const double total = reference_order_sum(a.prior, nVects, a.nWorkers, lds);

@@ -235,6 +235,12 @@ class ShardedEngine final : public IEngine {
     for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) Touch(pQuizzes[i]);
     return e;
   }
+  int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override {
+    // every shard records every answer of every quiz: the gathered answers reach the shards, then one of them reads
+    err = FlushNow();
+    if (!err.ok()) return -1;
+    return _sh[0]->GetQuizAnswers(err, iQuiz, pDest, capacity);
+  }
   int64_t ListTopQuestions(Error &err, int64_t iQuiz, int64_t maxCount, CiRatedQuestion *pDest) override;
   Error ListTopQuestionsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
   Error StartQuizBatch(int64_t n, int64_t *pQuizzes) override {

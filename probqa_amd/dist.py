@@ -872,6 +872,43 @@ def preview_answers_batch(engine, pairs, max_count: int, rank: int, world: int, 
     return [previews_of(parts[owner_in(bounds, q)], i) for i, (_, q) in enumerate(pairs)]
 
 
+# ---- a quiz with each of its answers left out, over the shards ---------------------------------------------------------------------
+# The review resumes from the rows of the quiz's answered questions, and those lie on whichever rank holds the question: the exchange is
+# resume_quiz_batch's -- one package whose slots count through the distinct quizzes' answers, packed by the owners and summed -- and
+# every rank reviews from the combined package.  The posterior is replicated: every rank computes the whole engine's bits, nothing is merged.
+
+
+def review_answers_batch(engine, pairs, max_count: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                         device: Optional[torch.device] = None) -> list:
+    """PqaEngine_ReviewAnswersBatchFromRows on the shards of `world` ranks: a collective every rank calls with the same (quiz, position)
+    pairs and max_count.  Every rank returns the same list of interop.AnswerPreview, one per pair.  All or none: a rank whose call is
+    refused still takes part in the exchange and the status words (one behind the reading of the answers, one behind the review),
+    after which every rank raises the first failing rank's text.  The package is a snapshot of the cube: no rank may train between the pack and the review inside this call."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    error, out = None, []
+    first_of, flat = {}, []
+    try:
+        for quiz, _ in pairs:   # (the answers are the same on every rank: every engine records every answer)
+            if quiz not in first_of:
+                first_of[quiz] = len(flat)
+                flat.extend(engine.get_quiz_answers(quiz))
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)   # (before the exchange: the ranks' packages must be of one size)
+    pkg = _package(engine, len(flat), ranks.device)
+    error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_answer_rows(flat, ptr))
+    if error is None:
+        try:
+            out = engine.review_answers_batch_from_rows(pairs, max_count, pkg.data_ptr(), [first_of[quiz] for quiz, _ in pairs])
+        except interop.PqaException as e:
+            error = str(e)
+    ranks.settle(error)
+    return out
+
+
 def _replicated(call, rank: int, world: int, group, device: Optional[torch.device]):
     """One replicated maintenance call and a status word: if any rank failed, every rank raises the first failure.  (The calls
     validate against state every rank holds alike, so they fail on all ranks or on none; what can fail on one rank alone is its

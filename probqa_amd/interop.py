@@ -177,6 +177,9 @@ HIP_EXPORTS = {
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_ListTopTargetsAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64, _pdbl]),
     "PqaEngine_PreviewAnswersBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaHip_GetQuizAnswers": (_i64, [_vp, ctypes.POINTER(_vp), _i64, _pAQ, _i64]),
+    "PqaEngine_ReviewAnswersBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaEngine_ReviewAnswersBatchFromRows": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64, _vp, _pi64]),
     "PqaEngine_EvalTargetSimilarity": (_vp, [_vp, _i64, _pi64, _pdbl, _i64]),
     "PqaEngine_ListSimilarTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaHip_PackTargetSimilaritySums": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
@@ -1102,6 +1105,49 @@ class PqaEngine:
 
     def preview_answers(self, i_quiz: int, i_question: int, max_count: int) -> List[AnswerPreview]:
         return self.preview_answers_batch([(i_quiz, i_question)], max_count)[0]
+
+    # ---- a quiz with each of its answers left out (include/PqaHipExt.h: PqaHip_GetQuizAnswers, PqaEngine_ReviewAnswersBatch) ----
+    def get_quiz_answers(self, i_quiz: int) -> List[AnsweredQuestion]:
+        """The answers the quiz holds, in the order RecordQuizTarget would train them, with GLOBAL question ids."""
+        c_err = ctypes.c_void_p()
+        n = _lib.PqaHip_GetQuizAnswers(self.c_engine, ctypes.byref(c_err), i_quiz, None, 0)
+        _check(c_err.value)
+        arr = (CiAnsweredQuestion * max(n, 1))()
+        n = min(n, _lib.PqaHip_GetQuizAnswers(self.c_engine, ctypes.byref(c_err), i_quiz, arr, n))
+        _check(c_err.value)
+        return [AnsweredQuestion(arr[i].iQuestion, arr[i].iAnswer) for i in range(n)]
+
+    def review_answers_batch(self, pairs, max_count: int) -> List[AnswerPreview]:
+        """For every (quiz, position) of `pairs` the quiz as if the answer at that position had never been given: the left-out
+        answer's likelihood under the posterior of the others, that posterior's entropy in bits and its best max_count (<= 256)
+        targets -- ResumeQuiz's own bits over the remaining answers.  Read-only: no quiz changes.  A dead row has NaN for both numbers
+        and no targets."""
+        return self.review_answers_batch_from_rows(pairs, max_count, None, None)
+
+    def review_answers(self, i_quiz: int, max_count: int) -> List[AnswerPreview]:
+        """review_answers_batch for every position of one quiz."""
+        return self.review_answers_batch([(i_quiz, i) for i in range(len(self.get_quiz_answers(i_quiz)))], max_count)
+
+    def review_answers_batch_from_rows(self, pairs, max_count: int, rows, row_first) -> List[AnswerPreview]:
+        """review_answers_batch on a shard that a process of its own drives: pair i's quiz has its answers' rows in slots
+        row_first[i] ... of the package at device-visible address `rows` (pack_answer_rows).  row_first None: the plain call."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(pr)
+        quizzes, positions = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        likelihood, entropy = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.float64)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        arr = (CiRatedTarget * max(n * max_count, 1))()
+        head = (self.c_engine, n, quizzes.ctypes.data_as(_pi64), positions.ctypes.data_as(_pi64), max_count, likelihood.ctypes.data_as(_pdbl),
+                entropy.ctypes.data_as(_pdbl), arr, counts.ctypes.data_as(_pi64))
+        if row_first is None:
+            _check(_lib.PqaEngine_ReviewAnswersBatch(*head))
+        else:
+            first = np.ascontiguousarray(row_first, dtype=np.int64).reshape(-1)
+            if len(first) != n:
+                raise ValueError("row_first names %d pairs, the call has %d" % (len(first), n))
+            _check(_lib.PqaEngine_ReviewAnswersBatchFromRows(*head, ctypes.c_void_p(rows or None), first.ctypes.data_as(_pi64)))
+        targets = self._records(arr, counts, n, max_count, RatedTarget)
+        return [AnswerPreview(float(likelihood[i]), float(entropy[i]), targets[i]) for i in range(n)]
 
     # ---- targets that answer like a given one (include/PqaHipExt.h: PqaEngine_EvalTargetSimilarity and its neighbours) ----
     def eval_target_similarity(self, sources) -> np.ndarray:
