@@ -27,6 +27,14 @@ typedef struct {     /* result of a stream-ordered selection; lives in device or
   double _priority;
   int64_t _iQuestion; /* GLOBAL question index, -1 if no eligible question in this shard */
 } CiHipSelection;
+
+typedef struct {     /* a quiz's record of PqaEngine_QuizStatusBatch, 40 bytes */
+  double _entropy;      /* -sum p log2 p over the candidates, in bits */
+  double _mass;         /* sum p over the candidates */
+  double _topProb;      /* the largest candidate probability, 0.0 without a candidate */
+  int64_t _iTopTarget;  /* its target, the lowest id among equals; -1 without a candidate */
+  int64_t _nCandidates; /* targets that are no gaps and hold p > 0 */
+} CiHipQuizStatus;
 #pragma pack(pop)
 
 #ifdef __cplusplus
@@ -401,6 +409,49 @@ PQACORE_API void *PqaEngine_ReviewAnswersBatch(void *pvEngine, int64_t nPairs, c
 PQACORE_API void *PqaEngine_ReviewAnswersBatchFromRows(void *pvEngine, int64_t nPairs, const int64_t *pQuizzes, const int64_t *pPositions,
                                                        int64_t maxCount, double *pLikelihood, double *pEntropy,
                                                        CiRatedTarget *pDest, int64_t *pCounts, const void *pRows, const int64_t *pRowFirst);
+/* Where a quiz stands NOW, where PqaEngine_PreviewAnswersBatch looks ahead and PqaEngine_ReviewAnswersBatch looks back: a handful of
+ * numbers per quiz instead of its nTargets doubles (PqaHip_GetPriors) -- what a stopping rule needs ("one target holds 0.9", "95 % of the
+ * mass sits in seven targets", "less than a bit is left") and the H_now of a question's information gain,
+ * H_now - sum_k likelihood_k * H_k with PqaEngine_PreviewAnswersBatch's likelihood_k and H_k.  Read-only; the reference has no such call.
+ * Per quiz i, over its posterior p as PqaHip_GetPriors would return it at that moment:
+ *  (a) Candidates: a target that is no gap and has p_t > 0 -- PqaEngine_ListTopTargets' rule; a NaN is never one.  _nCandidates counts them.
+ *  (b) _entropy = -sum p_t log2 p_t over the candidates, in bits: fp64, in a fixed order without atomics -- the order of
+ *      PqaEngine_PreviewAnswersBatch's entropies, so the pEntropy[k] it returned for (quiz, q, k), followed by
+ *      PqaEngine_SetActiveQuestion(q) + PqaEngine_RecordAnswer(k), is this value bit for bit, on Double and Float engines at every row
+ *      length.  Against -math.fsum(p log2 p) it is within (nTargets + 16) 2^-52 max(1, H) bits.
+ *  (c) _mass = sum p_t over the candidates, by the same partition and order; within (nTargets + 16) 2^-52 relative of math.fsum.
+ *  (d) _topProb / _iTopTarget: the largest candidate probability and its target, the lowest id among equals -- entry 0 of
+ *      PqaEngine_ListTopTargetsAmongBatch's order and of the fast listing (option "top_exact" 0); 0.0 and -1 without a candidate.
+ *  (e) Levels, 0 <= nLevels <= 16, shared by the whole call: pLevelCounts[i * nLevels + j] = the number of candidates with
+ *      p_t >= pLevels[j], pLevelMass[i * nLevels + j] = their sum in the order of (b).  A level <= 0 counts every candidate, +inf none; a
+ *      NaN is refused.  Either level buffer may be NULL where the caller does not want it, both only when nLevels == 0.
+ *  (f) State: nothing of any quiz changes -- posterior, asked bits, answers, active question, versions, speculative and resident state
+ *      all stay; a NextQuestion that follows returns what it would have returned without the call.  Regular mode only; deferred answers
+ *      are applied first, as in PqaEngine_ListTopTargetsBatch; a resident sweep is stopped, as PqaEngine_PreviewAnswersBatch stops it.
+ *  (g) Batch shape: any number of quizzes, 256 per launch; a quiz may repeat.  A quiz's outputs depend on that quiz and the levels
+ *      alone, never on the rest of the call.
+ *  (h) Refusals, all decided before anything is launched or written, in this order: negative nQuizzes or nLevels (NegativeCount);
+ *      nLevels > 16 (IndexOutOfRange); a needed buffer NULL (NullArgument); a NaN level (IndexOutOfRange, "level="); maintenance mode or
+ *      shutdown, as PqaEngine_PreviewAnswersBatch answers them; an unknown quiz ("entry=", "quizId=").
+ * One workgroup per quiz streams the posterior once (status_kernels.hip); 40 bytes and the level vectors per quiz cross to the host.
+ * Every engine holds every posterior whole: a shard engine (PqaEngineFactory_CreateHipEngineSharded) answers like a whole engine, every
+ * rank the same bits -- no package, no collective --, and the one-process sharded engine (PQA_DEVICES) lets its shard 0 answer.  Read-only
+ * options "status_calls" / "status_quizzes" (and "rank_calls" / "rank_pairs" for the call below): the accepted calls and their entries;
+ * with "time_sweeps", "status_device_ns" for both. */
+PQACORE_API void *PqaEngine_QuizStatusBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes,
+                                            int64_t nLevels, const double *pLevels,
+                                            CiHipQuizStatus *pStatus, int64_t *pLevelCounts, double *pLevelMass);
+/* Where named targets stand in their quizzes: pair i = (pQuizzes[i], pTargets[i]).  pProb[i] = the posterior's own bits at the target;
+ * pRank[i] = the number of candidates that come before it in the order "probability descending, target id ascending among equals",
+ * 0-based: where it is below maxCount, PqaEngine_ListTopTargetsAmongBatch and PqaEngine_ListTopTargetsBatch (option "top_exact" 0) list
+ * the target at exactly that index.  A target that is a gap or whose probability is not > 0 gets rank -1; pProb is the stored value all
+ * the same.  What a service asks when the user names the target (PqaEngine_RecordQuizTarget): reciprocal rank, hit@10.
+ * Any number of pairs; a quiz under many targets; pairs may repeat; a pair's outputs depend on that pair alone.  The pairs of a quiz are
+ * served 32 to a pass over its posterior.  State and refusals as above -- negative nPairs (NegativeCount), a buffer NULL (NullArgument),
+ * the mode, an unknown quiz ("entry=", "quizId=") -- and then a target outside [0, nTargets) (IndexOutOfRange, "entry=", "targetId=").
+ * Shard engines and the one-process sharded engine answer as for PqaEngine_QuizStatusBatch. */
+PQACORE_API void *PqaEngine_RankTargetsBatch(void *pvEngine, int64_t nPairs, const int64_t *pQuizzes, const int64_t *pTargets,
+                                             double *pProb, int64_t *pRank);
 /* Targets that answer like a given one: "more like this" behind PqaEngine_ListTopTargets, and the duplicate hunt in front of
  * PqaEngine_RemoveTargets -- two targets no quiz can ever tell apart are two whose answer distributions agree on every question.
  * With p_qk(t) = A[q][k][t] / D[q][t]:

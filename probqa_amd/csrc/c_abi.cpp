@@ -21,6 +21,7 @@
 #include "c_abi_shims.h"
 #include "hip_engine.h"
 #include "review_plan.h"
+#include "status_plan.h"
 #include "sampled_part.h"
 
 using pqa::AQ;
@@ -397,6 +398,13 @@ PQACORE_API void *PqaEngine_ListTopTargetsAmongBatch(void *pvEngine, const int64
 PQACORE_API void *PqaEngine_PreviewAnswersBatch(void *pvEngine, const int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions, const int64_t maxCount,
                                                 double *pLikelihood, double *pEntropy, CiRatedTarget *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.PreviewAnswersBatch(nPairs, pQuizzes, pQuestions, maxCount, pLikelihood, pEntropy, pDest, pCounts); });
+}
+PQACORE_API void *PqaEngine_QuizStatusBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t nLevels, const double *pLevels,
+                                            CiHipQuizStatus *pStatus, int64_t *pLevelCounts, double *pLevelMass) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.QuizStatusBatch(nQuizzes, pQuizzes, nLevels, pLevels, pStatus, pLevelCounts, pLevelMass); });
+}
+PQACORE_API void *PqaEngine_RankTargetsBatch(void *pvEngine, const int64_t nPairs, const int64_t *pQuizzes, const int64_t *pTargets, double *pProb, int64_t *pRank) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RankTargetsBatch(nPairs, pQuizzes, pTargets, pProb, pRank); });
 }
 PQACORE_API int64_t PqaHip_GetQuizAnswers(void *pvEngine, void **ppError, const int64_t iQuiz, CiAnsweredQuestion *pDest, const int64_t capacity) {
   return ValueOf<int64_t>(pvEngine, ppError, -1, [&](IEngine &e, Error &err) { return e.GetQuizAnswers(err, iQuiz, reinterpret_cast<AQ *>(pDest), capacity); });
@@ -948,6 +956,15 @@ static int64_t HostLogicProbe(const char *what, const int64_t *pIn, const int64_
     nRes = 1;
     for (const std::vector<int64_t> &c : chunks)
       if (!put(c)) return -1;
+    return nRes;
+  }
+  if (w == "status_plan") {   // {tileCap, nPairs, then the pairs' quizzes} -> {nTiles, then per tile its count and its pairs}
+    if (nIn < 2 || pIn[0] < 1 || pIn[1] < 0 || nIn != 2 + pIn[1] || nOut < 1) return -1;
+    const pqa::RankTiles plan = pqa::PlanRankTiles(pIn[1], pIn + 2, pIn[0]);
+    pOut[0] = plan.Tiles();
+    nRes = 1;
+    for (int64_t i = 0; i < plan.Tiles(); i++)
+      if (!put(std::vector<int64_t>(plan.order.begin() + (std::ptrdiff_t)plan.start[(size_t)i], plan.order.begin() + (std::ptrdiff_t)plan.start[(size_t)i + 1]))) return -1;
     return nRes;
   }
   if (w == "better_pick") {

@@ -179,6 +179,14 @@ class IEngine {
     return Error::MakeP(ErrCode::NotImplemented, "Feature=PreviewAnswersBatch on this engine",
                         "Answer previews are for whole engines and for shards that separate processes drive.");
   }
+  // Where a quiz stands and where named targets stand in it (include/PqaHipExt.h: PqaEngine_QuizStatusBatch, PqaEngine_RankTargetsBatch):
+  // every engine that holds posteriors answers -- whole engines, shards, and the one-process sharded engine through its shard 0.
+  virtual Error QuizStatusBatch(int64_t, const int64_t *, int64_t, const double *, CiHipQuizStatus *, int64_t *, double *) {
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=QuizStatusBatch on this engine", "This engine does not report a quiz's status.");
+  }
+  virtual Error RankTargetsBatch(int64_t, const int64_t *, const int64_t *, double *, int64_t *) {
+    return Error::MakeP(ErrCode::NotImplemented, "Feature=RankTargetsBatch on this engine", "This engine does not rank named targets.");
+  }
   // A quiz with each of its answers left out (include/PqaHipExt.h: PqaEngine_ReviewAnswersBatch) and the quiz's recorded answers; the
   // one-process sharded engine reads the answers and does not offer the review.
   virtual int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) = 0;

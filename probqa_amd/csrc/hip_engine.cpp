@@ -315,6 +315,8 @@ HipEngine::~HipEngine() {
   for (hipEvent_t e : _preview.ev) if (e) hipEventDestroy(e);
   hipFree(_review.dRows); hipFree(_review.dRatios); _review.lines.Free();
   for (hipEvent_t e : _review.ev) if (e) hipEventDestroy(e);
+  _status.lines.Free(); _status.rankLines.Free();
+  for (hipEvent_t e : _status.ev) if (e) hipEventDestroy(e);
   for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
@@ -404,7 +406,12 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"review_calls", &HipEngine::_reviewCalls},                         // ReviewAnswersBatch calls that were accepted (hip_engine_review.cpp) ...
       {"review_rows", &HipEngine::_reviewRows},                           // ... their (quiz, position) pairs ...
       {"review_device_ns", &HipEngine::_reviewDeviceNs},                  // ... and, with time_sweeps, their chains, rows and listing kernels between events
-      {"similarity_calls", &HipEngine::_simCalls},                        // target similarity calls that were accepted (hip_engine_sources.cpp) ...
+      {"status_calls", &HipEngine::_statusCalls},                         // QuizStatusBatch calls that were accepted (hip_engine_status.cpp) ...
+      {"status_quizzes", &HipEngine::_statusQuizzes},                     // ... and their quizzes
+      {"rank_calls", &HipEngine::_rankCalls},                             // RankTargetsBatch calls that were accepted ...
+      {"rank_pairs", &HipEngine::_rankPairs},                             // ... and their (quiz, target) pairs
+      {"status_device_ns", &HipEngine::_statusDeviceNs},                  // with time_sweeps, both calls' kernels between events
+      {"similarity_calls", &HipEngine::_simCalls},                       // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
       {"redundancy_calls", &HipEngine::_redCalls},                        // question redundancy calls that were accepted (hip_engine_sources.cpp) ...

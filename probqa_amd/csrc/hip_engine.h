@@ -261,6 +261,11 @@ class HipEngine : public IEngine {
   // what every answer to a question would do to a quiz: likelihood, entropy and best targets of each would-be posterior (hip_engine_preview.cpp)
   Error PreviewAnswersBatch(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions, int64_t maxCount, double *pLikelihood, double *pEntropy,
                             CiRatedTarget *pDest, int64_t *pCounts) override;
+  // where a quiz stands -- entropy, mass, best target, candidates, the candidates above given levels -- and where named targets stand in
+  // it: rank and probability (hip_engine_status.cpp)
+  Error QuizStatusBatch(int64_t nQuizzes, const int64_t *pQuizzes, int64_t nLevels, const double *pLevels, CiHipQuizStatus *pStatus, int64_t *pLevelCounts,
+                        double *pLevelMass) override;
+  Error RankTargetsBatch(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pTargets, double *pProb, int64_t *pRank) override;
   // a quiz's recorded answers, and the quiz with each of them left out: likelihood of the left-out answer, entropy and best targets of the
   // others' posterior (hip_engine_review.cpp)
   int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override;
@@ -522,6 +527,14 @@ class HipEngine : public IEngine {
   } _preview;
   Error ValidatePreviewLocked(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pQuestions);
   uint64_t _previewCalls = 0, _previewPairs = 0, _previewDeviceNs = 0;   // read-only "preview_calls", "preview_pairs", "preview_device_ns"
+  // QuizStatusBatch / RankTargetsBatch (hip_engine_status.cpp): the pinned result lines -- a chunk's status lines (kStatusLineWords words per
+  // quiz, behind one unused record) and a chunk's {rank, probability} records --, the events of option "time_sweeps".  Allocated once.
+  struct StatusStage {
+    ResultLines lines, rankLines;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } _status;
+  Error ValidateStatusLocked(const char *what, int64_t n, const int64_t *pQuizzes, const int64_t *pTargets);
+  uint64_t _statusCalls = 0, _statusQuizzes = 0, _rankCalls = 0, _rankPairs = 0, _statusDeviceNs = 0;   // read-only "status_calls", "status_quizzes", "rank_calls", "rank_pairs", "status_device_ns"
   // ReviewAnswersBatch (hip_engine_review.cpp): per row of a chunk _ldT mantissas (then the divided row) and, behind all of them, _ldT
   // exponent sums; the ratios of the chunk's quizzes that do not stay in LDS; the pinned result lines (records | counts | likelihood and
   // entropy per row); the events of option "time_sweeps".  The buffers grow and never shrink.

@@ -738,6 +738,26 @@ hipError_t LaunchReviewChains(const KbView &kb, const ReviewQuiz *quizzes, int64
 hipError_t LaunchReviewRows(const KbView &kb, const ReviewRow *rows, int64_t nRows, int64_t nWorkers, double *mants, int64_t *exps, int64_t pitch,
                             double *likelihood, double *entropy, hipStream_t stream);
 
+// QuizStatusBatch / RankTargetsBatch (status_kernels.hip): where a quiz stands, read off its posterior; a CANDIDATE is a target that is no
+// gap and holds p > 0.  Only [0, T) of a posterior is read.
+//   LaunchQuizStatus: a workgroup per quiz (nQuizzes <= kTopBatchQuizzes).  Quiz i's line, kStatusLineWords 8-byte words at
+//     lines + i * kStatusLineWords (device or host-coherent): the entropy in bits over the candidates -- preview_rows_kernel's partition
+//     and order, so the bits PreviewAnswersBatch promised for this posterior --, their mass in the same order, the largest probability (0
+//     without a candidate), its target (the lowest among equals; -1), the number of candidates; from kStatusLineCounts on, per level j <
+//     levels.n the number of candidates with p >= level[j], and from kStatusLineMasses on their sum in the entropy's order.  The words of
+//     the levels beyond levels.n are not written.
+//   LaunchRankTargets: a workgroup per tile (nTiles <= kTopBatchQuizzes; `tiles` and `ids` in device memory): tile = {the quiz's
+//     posterior, first, count <= kRankTile}, its named targets ids[first .. first + count), each in [0, T).  out[first + x] = {the
+//     number of candidates before the named target by (probability descending, target ascending) or -1 where it is no candidate
+//     itself, the posterior's own value there} (device or host-coherent).
+constexpr int kStatusLevels = 16, kRankTile = 32;
+constexpr int kStatusLineCounts = 5, kStatusLineMasses = kStatusLineCounts + kStatusLevels, kStatusLineWords = 40;
+static_assert(kStatusLineMasses + kStatusLevels <= kStatusLineWords, "a line holds the record and both level vectors");
+struct StatusLevels { int32_t n, pad; double level[kStatusLevels]; };
+struct RankTile { const double *prior; int32_t first, count; };
+hipError_t LaunchQuizStatus(const KbView &kb, const TopBatchPriors &priors, int64_t nQuizzes, const StatusLevels &levels, int64_t *lines, hipStream_t stream);
+hipError_t LaunchRankTargets(const KbView &kb, const RankTile *tiles, int64_t nTiles, const int32_t *ids, RatedTargetDev *out, hipStream_t stream);
+
 // Target similarity (similarity_kernels.hip): per source s_i and target t the sum over this cube's questions that are not gaps of
 // sum_k sqrt(p_qk(s_i)) sqrt(p_qk(t)), p_qk(t) = A[q][k][t] / D[q][t], in fp64 whatever the cube's element type.
 //   LaunchSimilaritySums: `sources` (device memory, ids in [0, T)) in tiles of kSimTile -- per tile the sources' columns into `rs`

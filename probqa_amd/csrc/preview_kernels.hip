@@ -60,12 +60,10 @@ __global__ __launch_bounds__(SMALL ? kSmallThreads : kThreads) void preview_rows
     if (writeRows) slot[t] = p;
     if (p > 0.0) h += p * log2(p);
   }
-  h = wave_sum(h);
-  if (threadIdx.x % kWave == 0) sWave[threadIdx.x / kWave] = h;
+  ordered_sum_share(h, sWave);
   __syncthreads();
   if (threadIdx.x == 0) {
-    double sum = sWave[0];
-    for (int w = 1; w < (int)(blockDim.x / kWave); w++) sum += sWave[w];
+    const double sum = ordered_sum_collect(sWave);
     if (likelihood != nullptr) likelihood[blockIdx.x] = total;
     if (entropy != nullptr) entropy[blockIdx.x] = dead ? u2d(0x7FF8000000000000ULL) : 0.0 - sum;
   }

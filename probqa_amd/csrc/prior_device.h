@@ -79,6 +79,20 @@ __device__ double reference_order_sum(const double *__restrict__ v, int64_t nVec
   return lds[8 * nSubtasks];
 }
 
+// ---- a workgroup's sum in the fixed order of the entropies (preview_kernels.hip, status_kernels.hip): every thread has added its
+// elements t = threadIdx.x, threadIdx.x + blockDim.x, ... in ascending order; the wave's lanes are added by wave_sum, lane 0 leaves the
+// wave's sum in waves[wave]; behind a barrier of the caller's, thread 0 adds the waves in order.  The same shares under the same
+// workgroup shape give the same bits, whichever kernel asks.
+__device__ __forceinline__ void ordered_sum_share(double v, double *waves) {
+  v = wave_sum(v);
+  if (threadIdx.x % kWave == 0) waves[threadIdx.x / kWave] = v;
+}
+__device__ __forceinline__ double ordered_sum_collect(const double *waves) {
+  double sum = waves[0];
+  for (int w = 1; w < (int)(blockDim.x / kWave); w++) sum += waves[w];
+  return sum;
+}
+
 struct PriorArgs {
   const void *cube;
   int elem;

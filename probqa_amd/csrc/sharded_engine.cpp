@@ -235,6 +235,24 @@ class ShardedEngine final : public IEngine {
     for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) Touch(pQuizzes[i]);
     return e;
   }
+  // (as ListTopTargetsAmongBatch: replicated posteriors, shard 0 answers)
+  Error QuizStatusBatch(int64_t n, const int64_t *pQuizzes, int64_t nLevels, const double *pLevels, CiHipQuizStatus *pStatus, int64_t *pLevelCounts,
+                        double *pLevelMass) override {
+    Error e = FlushNow();
+    for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) e = FailedQuiz(pQuizzes[i]);
+    if (!e.ok()) return e;
+    e = _sh[0]->QuizStatusBatch(n, pQuizzes, nLevels, pLevels, pStatus, pLevelCounts, pLevelMass);
+    for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) Touch(pQuizzes[i]);
+    return e;
+  }
+  Error RankTargetsBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pTargets, double *pProb, int64_t *pRank) override {
+    Error e = FlushNow();
+    for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) e = FailedQuiz(pQuizzes[i]);
+    if (!e.ok()) return e;
+    e = _sh[0]->RankTargetsBatch(n, pQuizzes, pTargets, pProb, pRank);
+    for (int64_t i = 0; e.ok() && i < n && pQuizzes; i++) Touch(pQuizzes[i]);
+    return e;
+  }
   int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override {
     // every shard records every answer of every quiz: the gathered answers reach the shards, then one of them reads
     err = FlushNow();

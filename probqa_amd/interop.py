@@ -65,6 +65,12 @@ class CiHipSelection(ctypes.Structure):
     _fields_ = [("priority", ctypes.c_double), ("iQuestion", ctypes.c_int64)]
 
 
+class CiHipQuizStatus(ctypes.Structure):  # include/PqaHipExt.h, 40 bytes
+    _pack_ = 8
+    _fields_ = [("entropy", ctypes.c_double), ("mass", ctypes.c_double), ("topProb", ctypes.c_double), ("iTopTarget", ctypes.c_int64),
+                ("nCandidates", ctypes.c_int64)]
+
+
 _vp, _i64, _u64, _u8, _dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_double
 _pvp = ctypes.POINTER(ctypes.c_void_p)
 _pi64 = ctypes.POINTER(ctypes.c_int64)
@@ -177,6 +183,8 @@ HIP_EXPORTS = {
     "PqaEngine_ListTopTargetsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_ListTopTargetsAmongBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedTarget), _pi64, _pdbl]),
     "PqaEngine_PreviewAnswersBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64]),
+    "PqaEngine_QuizStatusBatch": (_vp, [_vp, _i64, _pi64, _i64, _pdbl, ctypes.POINTER(CiHipQuizStatus), _pi64, _pdbl]),
+    "PqaEngine_RankTargetsBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl, _pi64]),
     "PqaHip_GetQuizAnswers": (_i64, [_vp, ctypes.POINTER(_vp), _i64, _pAQ, _i64]),
     "PqaEngine_ReviewAnswersBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64]),
     "PqaEngine_ReviewAnswersBatchFromRows": (_vp, [_vp, _i64, _pi64, _pi64, _i64, _pdbl, _pdbl, ctypes.POINTER(CiRatedTarget), _pi64, _vp, _pi64]),
@@ -318,6 +326,25 @@ class AnswerPreview:
 
     def __repr__(self):
         return f"[l={self.likelihood}, H={self.entropy}, {self.targets}]"
+
+
+class QuizStatus:
+    """Where a quiz stands (PqaEngine.quiz_status_batch): the entropy of its posterior in bits, the posterior's mass, the best target
+    and its probability (-1 and 0.0 without a candidate), the number of candidates, and per level of the call the number and the
+    mass of the candidates at or above it."""
+
+    def __init__(self, entropy: float, mass: float, top_prob: float, i_top_target: int, n_candidates: int, level_counts: List[int],
+                 level_mass: List[float]):
+        self.entropy = entropy
+        self.mass = mass
+        self.top_prob = top_prob
+        self.i_top_target = i_top_target
+        self.n_candidates = n_candidates
+        self.level_counts = level_counts
+        self.level_mass = level_mass
+
+    def __repr__(self):
+        return f"[H={self.entropy}, mass={self.mass}, top={self.i_top_target}:{self.top_prob}, n={self.n_candidates}, {self.level_counts}, {self.level_mass}]"
 
 
 class EngineDefinition:
@@ -1105,6 +1132,42 @@ class PqaEngine:
 
     def preview_answers(self, i_quiz: int, i_question: int, max_count: int) -> List[AnswerPreview]:
         return self.preview_answers_batch([(i_quiz, i_question)], max_count)[0]
+
+    # ---- where a quiz stands (include/PqaHipExt.h: PqaEngine_QuizStatusBatch, PqaEngine_RankTargetsBatch) ----
+    def quiz_status_batch(self, quizzes, levels=()) -> List[QuizStatus]:
+        """Per quiz (a quiz may repeat) the entropy of its posterior in bits -- the bits preview_answers_batch promised for it --, its
+        mass, its best target, the number of candidates (targets that are no gaps with p > 0) and, per level (at most 16, shared by
+        the call), the number and the mass of the candidates with p >= level.  Read-only: no quiz changes, no posterior leaves the
+        device.  What a stopping rule needs, and the H_now of a question's gain H_now - sum_k likelihood_k * H_k."""
+        qs = np.ascontiguousarray(quizzes, dtype=np.int64).reshape(-1)
+        lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        n, m = len(qs), len(lv)
+        status = (CiHipQuizStatus * max(n, 1))()
+        counts = np.zeros(max(n * m, 1), dtype=np.int64)
+        mass = np.zeros(max(n * m, 1), dtype=np.float64)
+        _check(_lib.PqaEngine_QuizStatusBatch(self.c_engine, n, qs.ctypes.data_as(_pi64), m, lv.ctypes.data_as(_pdbl) if m else None, status,
+                                              counts.ctypes.data_as(_pi64), mass.ctypes.data_as(_pdbl)))
+        return [QuizStatus(status[i].entropy, status[i].mass, status[i].topProb, status[i].iTopTarget, status[i].nCandidates,
+                           [int(c) for c in counts[i * m:(i + 1) * m]], [float(x) for x in mass[i * m:(i + 1) * m]]) for i in range(n)]
+
+    def quiz_status(self, i_quiz: int, levels=()) -> QuizStatus:
+        return self.quiz_status_batch([i_quiz], levels)[0]
+
+    def rank_targets_batch(self, pairs) -> List[Tuple[int, float]]:
+        """For every (quiz, target) of `pairs` (rank, prob): the number of candidates that come before the target by probability
+        descending, target id ascending among equals -- its index in list_top_targets_among and in the fast listing -- or -1 for a
+        gap or a probability that is not > 0, and the posterior's own value at the target.  Read-only: no quiz changes."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(pr)
+        quizzes, targets = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        prob = np.zeros(max(n, 1), dtype=np.float64)
+        rank = np.zeros(max(n, 1), dtype=np.int64)
+        _check(_lib.PqaEngine_RankTargetsBatch(self.c_engine, n, quizzes.ctypes.data_as(_pi64), targets.ctypes.data_as(_pi64), prob.ctypes.data_as(_pdbl),
+                                               rank.ctypes.data_as(_pi64)))
+        return [(int(rank[i]), float(prob[i])) for i in range(n)]
+
+    def rank_target(self, i_quiz: int, i_target: int) -> Tuple[int, float]:
+        return self.rank_targets_batch([(i_quiz, i_target)])[0]
 
     # ---- a quiz with each of its answers left out (include/PqaHipExt.h: PqaHip_GetQuizAnswers, PqaEngine_ReviewAnswersBatch) ----
     def get_quiz_answers(self, i_quiz: int) -> List[AnsweredQuestion]:
