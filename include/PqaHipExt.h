@@ -600,6 +600,49 @@ PQACORE_API void *PqaEngine_EvalTargetSeparation(void *pvEngine, int64_t nGroups
                                                  double *pOut, int64_t n);
 PQACORE_API void *PqaEngine_ListSeparatingQuestionsBatch(void *pvEngine, int64_t nGroups, const int64_t *pGroupCounts, const int64_t *pTargets,
                                                          int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts);
+/* What every question would tell a quiz: the information gain, in bits, of every question of the engine for each of many quizzes, from
+ * one streaming pass over the cube per tile of quizzes (gain_kernels.hip).  With the quiz's posterior p (PqaHip_GetPriors, taken as 0 at
+ * target gaps and where it is not > 0), r_k(t) = A[q][k][t] * (1 / D[q][t]) and f(x) = x log2 x (f(0) = 0), question q's joint table is
+ * J[k][t] = p_t r_k(t), its answer totals W_k = sum_t J[k][t], Z = sum_k W_k, and
+ *     gain(quiz, q) = max(0, (f(Z) - sum_k f(W_k) - sum_t p_t g_q(t)) / Z),   g_q(t) = f(sum_k r_k(t)) - sum_k f(r_k(t));
+ * 0 if Z is not > 0 or not finite.  It is the mutual information between the answer to q and the target for a target drawn from the
+ * posterior: the entropy of the answer under the posterior's mixture minus the posterior mean of each target's own answer entropy, 0 for
+ * a question every candidate answers alike, at most log2 nAnswers.  The table is normalised by its own total: neither sum p == 1 nor
+ * D == sum_k A is assumed (as in PqaEngine_EvalQuestionRedundancy); where both hold, the gain is _entropy of PqaEngine_QuizStatusBatch
+ * minus sum_k likelihood_k * entropy_k of PqaEngine_PreviewAnswersBatch, up to rounding.  The reference has no such call.
+ *  (a) Arithmetic: fp64 throughout (a Float engine's elements are converted exactly; posteriors are doubles on both engine types);
+ *      r_k by the exact reciprocal, sum_k with k ascending, a lane's sums over its targets ascending, the lanes added in a fixed tree,
+ *      the waves in wave order, Z and sum_k f(W_k) with k ascending; the device's fp64 log2; no atomics.  Against math.fsum and
+ *      math.log2 over the table a value is within (nTargets + 16) (nAnswers + 8) 2^-52 bits ABSOLUTE.
+ *  (b) Fixed, bit for bit: a value depends on the quiz's posterior, question q's block, the target gaps and nAnswers only -- not on the
+ *      other quizzes of the call, the quiz's place in the call or in its tile, the tile's width, the chunking, or where q falls in the
+ *      grid or in a shard.  A question block that is a bitwise copy of another gets the other's bits; a quiz listed twice gets the same
+ *      row twice.
+ *  (c) State: nothing of any quiz changes -- posterior, asked bits, answers, active question, versions, speculative and resident state;
+ *      a PqaEngine_NextQuestion that follows returns what it would have returned without the call.  Regular mode only.  Deferred
+ *      answers are applied first and a resident sweep is stopped, as for PqaEngine_QuizStatusBatch.
+ *  (d) Refusals, all decided before anything is launched or written, in this order: negative nQuizzes / maxCount (NegativeCount); a
+ *      NULL buffer that is needed (NullArgument); a wrong n (IndexOutOfRange); maintenance mode or shutdown, as
+ *      PqaEngine_QuizStatusBatch answers them; an unknown quiz ("entry=", "quizId=").
+ *   PqaEngine_EvalQuestionGainsBatch        pOut[i * n + j] = gain(pQuizzes[i], q_first + j); n must be the engine's own question count
+ *                                           (a whole engine: nQuestions).  0 for a gap question; an asked question is evaluated like
+ *                                           any other (what asking it again would gain); a quiz whose Z is 0 or not finite gets a row
+ *                                           of zeros.  Any number of quizzes, in chunks of 256; a quiz may repeat.
+ *   PqaEngine_ListInformativeQuestionsBatch quiz i's candidates are the engine's questions that are no gaps, not asked by that quiz, and
+ *                                           have gain > 0; pCounts[i] = min(maxCount, candidates) records at pDest + i * maxCount, gain
+ *                                           descending, question id ascending among equal values; GLOBAL ids; _priority carries the bits
+ *                                           PqaEngine_EvalQuestionGainsBatch returns; entry 0 is the most informative question.
+ *                                           maxCount 0 is no error.  Up to 256 records a quiz the rows stay on the device (the listing
+ *                                           kernels of PqaEngine_ListTopQuestions, each quiz's own asked bitmap); beyond that the rows
+ *                                           are copied and the prefix is taken on the host in the same order.
+ * Both calls work on a whole engine AND directly on an engine made by PqaEngineFactory_CreateHipEngineSharded, for the questions it
+ * holds: the posterior is replicated, so there is no package; a host merges the ranks' lists (probqa_amd/dist.py:
+ * list_informative_questions_batch).  The one-process sharded engine (PQA_DEVICES) keeps the interface's default and answers
+ * NotImplemented.  Read-only counters: "gain_calls", "gain_quizzes", and with "time_sweeps" "gain_device_ns" (sweeps and listing
+ * kernels). */
+PQACORE_API void *PqaEngine_EvalQuestionGainsBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, double *pOut, int64_t n);
+PQACORE_API void *PqaEngine_ListInformativeQuestionsBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, int64_t maxCount,
+                                                          CiRatedQuestion *pDest, int64_t *pCounts);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

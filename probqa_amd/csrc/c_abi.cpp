@@ -563,6 +563,13 @@ PQACORE_API void *PqaEngine_ListSeparatingQuestionsBatch(void *pvEngine, const i
                                                          const int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListSeparatingQuestionsBatch(nGroups, pGroupCounts, pTargets, maxCount, pDest, pCounts); });
 }
+PQACORE_API void *PqaEngine_EvalQuestionGainsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, double *pOut, const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalQuestionGainsBatch(nQuizzes, pQuizzes, pOut, n); });
+}
+PQACORE_API void *PqaEngine_ListInformativeQuestionsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t maxCount,
+                                                          CiRatedQuestion *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListInformativeQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {

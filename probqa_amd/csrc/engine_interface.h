@@ -187,6 +187,10 @@ class IEngine {
   virtual Error RankTargetsBatch(int64_t, const int64_t *, const int64_t *, double *, int64_t *) {
     return Error::MakeP(ErrCode::NotImplemented, "Feature=RankTargetsBatch on this engine", "This engine does not rank named targets.");
   }
+  // What every question would tell a quiz, in bits (include/PqaHipExt.h: PqaEngine_EvalQuestionGainsBatch and its neighbour); the
+  // one-process sharded engine does not offer them.
+  virtual Error EvalQuestionGainsBatch(int64_t, const int64_t *, double *, int64_t) { return NoGains("EvalQuestionGainsBatch"); }
+  virtual Error ListInformativeQuestionsBatch(int64_t, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) { return NoGains("ListInformativeQuestionsBatch"); }
   // A quiz with each of its answers left out (include/PqaHipExt.h: PqaEngine_ReviewAnswersBatch) and the quiz's recorded answers; the
   // one-process sharded engine reads the answers and does not offer the review.
   virtual int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) = 0;
@@ -200,6 +204,10 @@ class IEngine {
   }
 
  private:
+  static Error NoGains(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
+                        "Question gains are for whole engines and for shards that separate processes drive.");
+  }
   static Error NoSeparation(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
                         "Target separation is for whole engines and for shards that separate processes drive.");

@@ -317,6 +317,8 @@ HipEngine::~HipEngine() {
   for (hipEvent_t e : _review.ev) if (e) hipEventDestroy(e);
   _status.lines.Free(); _status.rankLines.Free();
   for (hipEvent_t e : _status.ev) if (e) hipEventDestroy(e);
+  hipFree(_gain.dRows); hipFree(_gain.dSlots); _gain.lines.Free();
+  for (hipEvent_t e : _gain.ev) if (e) hipEventDestroy(e);
   for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
@@ -411,6 +413,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"rank_calls", &HipEngine::_rankCalls},                             // RankTargetsBatch calls that were accepted ...
       {"rank_pairs", &HipEngine::_rankPairs},                             // ... and their (quiz, target) pairs
       {"status_device_ns", &HipEngine::_statusDeviceNs},                  // with time_sweeps, both calls' kernels between events
+      {"gain_calls", &HipEngine::_gainCalls},                             // question gain calls that were accepted (hip_engine_gain.cpp) ...
+      {"gain_quizzes", &HipEngine::_gainQuizzes},                         // ... their quizzes ...
+      {"gain_device_ns", &HipEngine::_gainDeviceNs},                      // ... and, with time_sweeps, their sweeps and listing kernels between events
       {"similarity_calls", &HipEngine::_simCalls},                       // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events

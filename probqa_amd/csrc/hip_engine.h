@@ -266,6 +266,9 @@ class HipEngine : public IEngine {
   Error QuizStatusBatch(int64_t nQuizzes, const int64_t *pQuizzes, int64_t nLevels, const double *pLevels, CiHipQuizStatus *pStatus, int64_t *pLevelCounts,
                         double *pLevelMass) override;
   Error RankTargetsBatch(int64_t nPairs, const int64_t *pQuizzes, const int64_t *pTargets, double *pProb, int64_t *pRank) override;
+  // what every question of this engine would tell a quiz: its information gain in bits, as rows and as a listing (hip_engine_gain.cpp)
+  Error EvalQuestionGainsBatch(int64_t nQuizzes, const int64_t *pQuizzes, double *pOut, int64_t n) override;
+  Error ListInformativeQuestionsBatch(int64_t nQuizzes, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
   // a quiz's recorded answers, and the quiz with each of them left out: likelihood of the left-out answer, entropy and best targets of the
   // others' posterior (hip_engine_review.cpp)
   int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override;
@@ -535,6 +538,20 @@ class HipEngine : public IEngine {
   } _status;
   Error ValidateStatusLocked(const char *what, int64_t n, const int64_t *pQuizzes, const int64_t *pTargets);
   uint64_t _statusCalls = 0, _statusQuizzes = 0, _rankCalls = 0, _rankPairs = 0, _statusDeviceNs = 0;   // read-only "status_calls", "status_quizzes", "rank_calls", "rank_pairs", "status_device_ns"
+  // EvalQuestionGainsBatch / ListInformativeQuestionsBatch (hip_engine_gain.cpp): a chunk's rows of RedRowPitch() doubles on the device, the
+  // slots that show them to the question listing, its pinned result lines, the host's copy of the rows for listings beyond 256 records, the
+  // events of option "time_sweeps".  The buffers grow and never shrink.
+  struct GainStage {
+    double *dRows = nullptr;
+    size_t rowsBytes = 0;
+    QuizSlot *dSlots = nullptr;
+    ResultLines lines;
+    std::vector<double> rows;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } _gain;
+  Error AdmitGainsLocked(int64_t rowLength, int64_t n, const int64_t *pQuizzes);
+  Error GainRowsLocked(int64_t first, int64_t m, const int64_t *pQuizzes);   // a chunk's rows into _gain.dRows, enqueued
+  uint64_t _gainCalls = 0, _gainQuizzes = 0, _gainDeviceNs = 0;   // read-only "gain_calls", "gain_quizzes", "gain_device_ns"
   // ReviewAnswersBatch (hip_engine_review.cpp): per row of a chunk _ldT mantissas (then the divided row) and, behind all of them, _ldT
   // exponent sums; the ratios of the chunk's quizzes that do not stay in LDS; the pinned result lines (records | counts | likelihood and
   // entropy per row); the events of option "time_sweeps".  The buffers grow and never shrink.

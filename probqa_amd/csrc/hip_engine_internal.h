@@ -4,7 +4,8 @@
 // hip_engine_resume.cpp, hip_engine_parts.cpp, hip_engine_record_parts.cpp: row packages, selection parts and posterior packages of
 // shards that separate processes drive; hip_engine_train.cpp: many trainings in one call; hip_engine_server.cpp: the resident sweep;
 // hip_engine_list.cpp: ListTopQuestions; hip_engine_among.cpp, hip_engine_top_among.cpp: the Among calls and the listing within listed
-// sets; hip_engine_sources.cpp: the source queries, target similarity, question redundancy and target separation).
+// sets; hip_engine_sources.cpp: the source queries, target similarity, question redundancy and target separation; hip_engine_gain.cpp:
+// the information gain of every question of a quiz).
 #pragma once
 
 #include <sched.h>

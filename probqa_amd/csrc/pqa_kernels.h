@@ -810,4 +810,18 @@ constexpr int kSepMaxGroup = 64, kSepTileEntries = 256, kSepTileGroups = 128;
 hipError_t LaunchSeparationSweep(const KbView &kb, const int64_t *groupStart, const int64_t *tileGroup, const int64_t *tileWidth, const int64_t *entries,
                                  int64_t nGroups, int64_t nTiles, double *rows, int64_t rowPitch, hipStream_t stream);
 
+// Question gains (gain_kernels.hip): gain(quiz, q), the mutual information in bits between the answer to question q of this cube and
+// the target for a target drawn from the quiz's posterior (0 at a gap target and where it is not > 0), in fp64 whatever the cube's
+// element type.  Only [0, T) of a posterior is read, in 16-byte pieces (the posteriors are 16-byte aligned, ldT doubles long).
+//   LaunchQuestionGains: rows[i][rowPitch], column j = gain(quiz i, question j) for nQuizzes (<= kTopBatchQuizzes) posteriors: 0 for a
+//     gap question and for a quiz whose table's total is 0 or not finite -- the rows the listing takes (LaunchTopQuestions: what is
+//     <= 0 is no candidate).  One streaming pass over the cube per tile of GainTileWidth(K) quizzes -- the K + 1 logarithms of an
+//     element are paid once per tile --, a lone quiz in a tile of one; a value is the same bits at either width.  Answer counts
+//     without an instantiation (K > 5) go (question, quiz) by (question, quiz).
+//   LaunchGainSlots: the listing's view of the rows -- slot i's priority vector is row i, its asked bitmap asked.asked[i].
+constexpr int GainTileWidth(int K) { return K == 2 ? 16 : K == 3 ? 12 : K <= 5 ? 8 : 1; }   // NQ (K + 1) accumulators <= 48 doubles a lane
+struct GainAsked { const uint32_t *asked[kTopBatchQuizzes]; };
+hipError_t LaunchQuestionGains(const KbView &kb, const TopBatchPriors &priors, int64_t nQuizzes, double *rows, int64_t rowPitch, hipStream_t stream);
+hipError_t LaunchGainSlots(QuizSlot *slots, double *rows, int64_t rowPitch, const GainAsked &asked, int64_t nQuizzes, hipStream_t stream);
+
 }  // namespace pqa

@@ -744,6 +744,30 @@ def list_separating_questions_batch(engine, groups, max_count: int, rank: int, w
     return _gather_top(listed, max_count, group, device)
 
 
+# ---- what every question would tell a quiz, over the shards -------------------------------------------------------------------------
+# The gain of a question for a quiz needs the quiz's posterior, which every rank holds whole, and that question's block, which its
+# owner holds whole: there is no package and nothing to sum.  Every rank lists its own questions under the quiz's asked bits, one status
+# word keeps the ranks in step, and the lists are all-gathered and merged as list_top_questions merges.
+
+
+def list_informative_questions_batch(engine, quizzes, max_count: int, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                                     device: Optional[torch.device] = None) -> List[List[Tuple[int, float]]]:
+    """PqaEngine_ListInformativeQuestionsBatch on the shards of `world` ranks: a collective every rank calls with the same quizzes and
+    max_count; any number of quizzes.  Every rank returns the same (GLOBAL question, bits) records; entry 0 is the most informative
+    question of the whole knowledge base.  All or none: a rank whose call is refused still takes part in the status word, after which
+    every rank raises the first failing rank's text."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    error, listed = None, None
+    try:
+        listed = engine.list_informative_questions_batch([int(z) for z in quizzes], max_count)
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)
+    return _gather_top(listed, max_count, group, device)
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

@@ -200,6 +200,8 @@ HIP_EXPORTS = {
     "PqaEngine_ListRedundantQuestionsFromWeights": (_vp, [_vp, _i64, _pi64, _vp, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_EvalTargetSeparation": (_vp, [_vp, _i64, _pi64, _pi64, _pdbl, _i64]),
     "PqaEngine_ListSeparatingQuestionsBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
+    "PqaEngine_EvalQuestionGainsBatch": (_vp, [_vp, _i64, _pi64, _pdbl, _i64]),
+    "PqaEngine_ListInformativeQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1318,6 +1320,27 @@ class PqaEngine:
 
     def list_separating_questions(self, targets, max_count: int) -> List[Tuple[int, float]]:
         return self.list_separating_questions_batch([list(targets)], max_count)[0]
+
+    # ---- what every question would tell a quiz (include/PqaHipExt.h: PqaEngine_EvalQuestionGainsBatch and its neighbour) ----
+    def eval_question_gains_batch(self, quizzes) -> np.ndarray:
+        """gain(quizzes[i], q) for every question q THIS engine holds as an [n, local questions] array (column j: question q_first + j):
+        the information gain in bits -- the mutual information between the answer to q and the target for a target drawn from the
+        quiz's posterior.  0 at gaps and for a question every candidate answers alike, at most log2 nAnswers; an asked question is
+        evaluated like any other.  Changes no quiz; regular mode; whole engines and shards.  A quiz may repeat."""
+        qs = np.ascontiguousarray(quizzes, dtype=np.int64).reshape(-1)
+        q = self.get_option("local_questions")
+        out = np.zeros((len(qs), q), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalQuestionGainsBatch(self.c_engine, len(qs), qs.ctypes.data_as(_pi64), _dptr(out), q))
+        return out
+
+    def list_informative_questions_batch(self, quizzes, max_count: int) -> List[List[Tuple[int, float]]]:
+        """Per quiz the questions THIS engine holds that would tell it most as (question, bits), the gaps, the quiz's asked questions and
+        what gains nothing left out: bits descending, question id ascending among equal values; GLOBAL ids; the values are
+        eval_question_gains_batch's bits.  Entry 0 is the most informative question: follow with set_active_question to ask it."""
+        return self._list_batch(_lib.PqaEngine_ListInformativeQuestionsBatch, CiRatedQuestion, _pair, quizzes, max_count)
+
+    def list_informative_questions(self, quiz: int, max_count: int) -> List[Tuple[int, float]]:
+        return self.list_informative_questions_batch([quiz], max_count)[0]
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
