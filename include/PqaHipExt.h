@@ -643,6 +643,54 @@ PQACORE_API void *PqaEngine_ListSeparatingQuestionsBatch(void *pvEngine, int64_t
 PQACORE_API void *PqaEngine_EvalQuestionGainsBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, double *pOut, int64_t n);
 PQACORE_API void *PqaEngine_ListInformativeQuestionsBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, int64_t maxCount,
                                                           CiRatedQuestion *pDest, int64_t *pCounts);
+/* Question pages: what every question would tell a quiz ONCE the answers to a set of questions are known, and a page of questions filled
+ * greedily by that number -- for clients that put several questions on one screen, where the best m questions by
+ * PqaEngine_ListInformativeQuestionsBatch are typically near-duplicates of each other (page_kernels.hip).  The conditional gain is
+ *     CG(q | S) = I(A_q ; T | A_S)   bits;
+ * by the chain rule the conditional gains of a page add up to the page's joint information I(A_page ; T).  pGiven holds the quizzes'
+ * given sets one after another, GLOBAL question ids in listed order, pGivenCounts[i] the length of quiz i's; both may be NULL: every
+ * set is empty.  The reference has no such call.
+ *  (a) Definition.  p: the quiz's posterior (PqaHip_GetPriors), taken as 0 at target gaps and where it is not > 0.
+ *      r_k^q(t) = A[q][k][t] * (1 / D[q][t]), the gain sweep's own product, 0 at gap targets.  For S = (q_1 .. q_j), BRANCH
+ *      b = ((k_1 nAnswers + k_2) nAnswers + ...) + k_j is the row w_b(t) = (((p_t r_k1^q1(t)) r_k2^q2(t)) ...), each product rounded and
+ *      stored as a double; its mass m_b is the sum of the STORED values -- a lane's 16-byte pieces ascending, the lanes added in a fixed
+ *      tree, the waves in wave order --; M = sum_b m_b with b ascending; and
+ *          CG(q | S) = sum_b (m_b / M) gain(w_b, q),   b ascending, one fma chain,
+ *      gain(w_b, q) being exactly the value PqaEngine_EvalQuestionGainsBatch's sweep produces for a posterior w_b (it is normalised by
+ *      its own table, so the rows are NOT normalised).  A branch whose m_b is not > 0 contributes nothing; M not > 0 or not finite: a
+ *      row of zeros.  With S empty there is one branch and m / M == 1.0 exactly: the row is PqaEngine_EvalQuestionGainsBatch's bit for
+ *      bit.  Against math.fsum and math.log2 a value is within
+ *      ((nTargets + 16) (nAnswers + 8) + (2 (nTargets + 16) + B + 2) log2 nAnswers) 2^-52 bits ABSOLUTE, B = nAnswers^|S|.
+ *  (b) Fixed, bit for bit: a value depends on the quiz's posterior, the blocks of S and of q, the listed ORDER of S (another order agrees
+ *      to rounding), the target gaps and nAnswers only -- not on the other quizzes of the call, the quiz's place in it, tiles or
+ *      chunking.  A duplicate id in S is a chain like any other.
+ *  (c) State: nothing of any quiz changes; regular mode only; deferred answers are applied first and a resident sweep is stopped, as for
+ *      PqaEngine_EvalQuestionGainsBatch.
+ *  (d) Limits, refused before any launch: the largest branch count of a step -- nAnswers^|S_i| for Eval,
+ *      nAnswers^(|S_i| + pageSize - 1) for a page -- must be at most 256 (one chunk of the gain sweep), and a quiz's branch rows must fit
+ *      64 MiB of scratch: IndexOutOfRange with "entry=" and "branches=".
+ *  (e) Refusals, all decided before anything is launched or written, in this order: negative nQuizzes / pageSize / a negative given
+ *      count (NegativeCount); a NULL buffer that is needed (NullArgument; pGiven may be NULL only with pGivenCounts NULL or all counts
+ *      0); a wrong n (IndexOutOfRange); maintenance mode or shutdown, as PqaEngine_EvalQuestionGainsBatch answers them; an unknown quiz
+ *      ("entry=", "quizId="); a given question outside the knowledge base, or a gap ("entry=", "questionId="); the limits of (d).
+ *   PqaEngine_EvalConditionalGainsBatch  pOut[i * n + j] = CG(q_first + j | S_i); n must be the engine's own question count.  0 for a gap
+ *                                        question; asked questions and the members of S are evaluated like any other.
+ *   PqaEngine_ListQuestionPageBatch      the page starts from S_i; each step takes the question with the largest CG > 0 among those that
+ *                                        are no gaps, not asked by the quiz and not in the set so far (the lowest id among equals),
+ *                                        appends it to the set and repeats, until pageSize questions are taken or no candidate is
+ *                                        left.  pCounts[i] records at pDest + i * pageSize in pick order: _iQuestion the GLOBAL id,
+ *                                        _priority the bits PqaEngine_EvalConditionalGainsBatch returns for that question given the
+ *                                        prefix before it.  Entry 0 of a page with S empty is entry 0 of
+ *                                        PqaEngine_ListInformativeQuestionsBatch.  pageSize 0 is no error.  The picks are made on the
+ *                                        device and a page's steps are enqueued back to back: the host waits once per chunk of quizzes.
+ * Whole engines only.  The branch rows need the given questions' blocks, which live on one rank: an engine made by
+ * PqaEngineFactory_CreateHipEngineSharded and the one-process sharded engine (PQA_DEVICES) answer NotImplemented; a row-package form in
+ * the manner of PqaHip_PackAnswerRows is left to a later change.  Read-only counters: "page_calls", "page_quizzes", and with
+ * "time_sweeps" "page_device_ns". */
+PQACORE_API void *PqaEngine_EvalConditionalGainsBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
+                                                      const int64_t *pGiven, double *pOut, int64_t n);
+PQACORE_API void *PqaEngine_ListQuestionPageBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
+                                                  const int64_t *pGiven, int64_t pageSize, CiRatedQuestion *pDest, int64_t *pCounts);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

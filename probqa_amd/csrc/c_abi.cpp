@@ -570,6 +570,15 @@ PQACORE_API void *PqaEngine_ListInformativeQuestionsBatch(void *pvEngine, const 
                                                           CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListInformativeQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
 }
+// ---- question pages (hip_engine_page.cpp): whole engines only -- the branch rows need the given questions' blocks, which one rank holds
+PQACORE_API void *PqaEngine_EvalConditionalGainsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
+                                                      const int64_t *pGiven, double *pOut, const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalConditionalGainsBatch(nQuizzes, pQuizzes, pGivenCounts, pGiven, pOut, n); });
+}
+PQACORE_API void *PqaEngine_ListQuestionPageBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven,
+                                                  const int64_t pageSize, CiRatedQuestion *pDest, int64_t *pCounts) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListQuestionPageBatch(nQuizzes, pQuizzes, pGivenCounts, pGiven, pageSize, pDest, pCounts); });
+}
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {
   return ReturnErr(Guarded([&]() -> Error {

@@ -191,6 +191,12 @@ class IEngine {
   // one-process sharded engine does not offer them.
   virtual Error EvalQuestionGainsBatch(int64_t, const int64_t *, double *, int64_t) { return NoGains("EvalQuestionGainsBatch"); }
   virtual Error ListInformativeQuestionsBatch(int64_t, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) { return NoGains("ListInformativeQuestionsBatch"); }
+  // What every question would tell a quiz once a given set is answered, and a greedy page of questions (include/PqaHipExt.h:
+  // PqaEngine_EvalConditionalGainsBatch and its neighbour): whole engines only.
+  virtual Error EvalConditionalGainsBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, double *, int64_t) { return NoPages("EvalConditionalGainsBatch"); }
+  virtual Error ListQuestionPageBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) {
+    return NoPages("ListQuestionPageBatch");
+  }
   // A quiz with each of its answers left out (include/PqaHipExt.h: PqaEngine_ReviewAnswersBatch) and the quiz's recorded answers; the
   // one-process sharded engine reads the answers and does not offer the review.
   virtual int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) = 0;
@@ -201,6 +207,12 @@ class IEngine {
   virtual Error ReviewAnswersBatchFromRows(int64_t n, const int64_t *pQuizzes, const int64_t *pPositions, int64_t maxCount, double *pLikelihood, double *pEntropy,
                                            CiRatedTarget *pDest, int64_t *pCounts, const void *, const int64_t *) {
     return ReviewAnswersBatch(n, pQuizzes, pPositions, maxCount, pLikelihood, pEntropy, pDest, pCounts);
+  }
+
+ protected:
+  static Error NoPages(const char *what) {
+    return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
+                        "Question pages need the given questions' blocks, which one rank holds: they are for whole engines.");
   }
 
  private:

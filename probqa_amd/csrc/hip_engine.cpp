@@ -319,6 +319,9 @@ HipEngine::~HipEngine() {
   for (hipEvent_t e : _status.ev) if (e) hipEventDestroy(e);
   hipFree(_gain.dRows); hipFree(_gain.dSlots); _gain.lines.Free();
   for (hipEvent_t e : _gain.ev) if (e) hipEventDestroy(e);
+  hipFree(_page.dRows); hipFree(_page.dMasses); hipFree(_page.dGains); hipFree(_page.dCombined); hipFree(_page.dExcl); hipFree(_page.dSet); hipFree(_page.dSlots);
+  _page.lines.Free();
+  for (hipEvent_t e : _page.ev) if (e) hipEventDestroy(e);
   for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
@@ -416,6 +419,9 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"gain_calls", &HipEngine::_gainCalls},                             // question gain calls that were accepted (hip_engine_gain.cpp) ...
       {"gain_quizzes", &HipEngine::_gainQuizzes},                         // ... their quizzes ...
       {"gain_device_ns", &HipEngine::_gainDeviceNs},                      // ... and, with time_sweeps, their sweeps and listing kernels between events
+      {"page_calls", &HipEngine::_pageCalls},                             // question page calls that were accepted (hip_engine_page.cpp) ...
+      {"page_quizzes", &HipEngine::_pageQuizzes},                         // ... their quizzes ...
+      {"page_device_ns", &HipEngine::_pageDeviceNs},                      // ... and, with time_sweeps, their chunks' kernels between events
       {"similarity_calls", &HipEngine::_simCalls},                       // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events

@@ -269,6 +269,11 @@ class HipEngine : public IEngine {
   // what every question of this engine would tell a quiz: its information gain in bits, as rows and as a listing (hip_engine_gain.cpp)
   Error EvalQuestionGainsBatch(int64_t nQuizzes, const int64_t *pQuizzes, double *pOut, int64_t n) override;
   Error ListInformativeQuestionsBatch(int64_t nQuizzes, const int64_t *pQuizzes, int64_t maxCount, CiRatedQuestion *pDest, int64_t *pCounts) override;
+  // what every question would tell a quiz once the answers to a given set of questions are known, and a page of questions filled
+  // greedily by that number (hip_engine_page.cpp)
+  Error EvalConditionalGainsBatch(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, double *pOut, int64_t n) override;
+  Error ListQuestionPageBatch(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, int64_t pageSize, CiRatedQuestion *pDest,
+                              int64_t *pCounts) override;
   // a quiz's recorded answers, and the quiz with each of them left out: likelihood of the left-out answer, entropy and best targets of the
   // others' posterior (hip_engine_review.cpp)
   int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override;
@@ -552,6 +557,25 @@ class HipEngine : public IEngine {
   Error AdmitGainsLocked(int64_t rowLength, int64_t n, const int64_t *pQuizzes);
   Error GainRowsLocked(int64_t first, int64_t m, const int64_t *pQuizzes);   // a chunk's rows into _gain.dRows, enqueued
   uint64_t _gainCalls = 0, _gainQuizzes = 0, _gainDeviceNs = 0;   // read-only "gain_calls", "gain_quizzes", "gain_device_ns"
+  // EvalConditionalGainsBatch / ListQuestionPageBatch (hip_engine_page.cpp): a chunk's branch rows of _ldT doubles in two halves and their
+  // masses, the gain sweep's rows for them, the quizzes' combined rows, exclusion bitmaps and sets, the slots that show the combined rows
+  // to the question listing, the pinned lines a page's picks arrive in (step s of quiz j at record s * 256 + j; the expansions read them
+  // on the device), the call's given sets as validated, the events of option "time_sweeps".  The buffers grow and never shrink.
+  struct PageStage {
+    double *dRows = nullptr, *dMasses = nullptr, *dGains = nullptr, *dCombined = nullptr;
+    uint32_t *dExcl = nullptr;
+    int32_t *dSet = nullptr;
+    size_t rowsBytes = 0, massesBytes = 0, gainsBytes = 0, combinedBytes = 0, exclBytes = 0;
+    QuizSlot *dSlots = nullptr;
+    ResultLines lines;
+    std::vector<int32_t> given;                  // LOCAL ids, one set after another
+    std::vector<int64_t> givenFirst, largest;    // nQuizzes + 1; the quizzes' branch rows at their largest step
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } _page;
+  Error AdmitPageLocked(const char *call, int64_t rowLength, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven,
+                        int64_t pageSize, bool page);
+  Error PageChunkLocked(int64_t first, int64_t m, const int64_t *pQuizzes, int64_t steps);   // a chunk's launches, enqueued
+  uint64_t _pageCalls = 0, _pageQuizzes = 0, _pageDeviceNs = 0;   // read-only "page_calls", "page_quizzes", "page_device_ns"
   // ReviewAnswersBatch (hip_engine_review.cpp): per row of a chunk _ldT mantissas (then the divided row) and, behind all of them, _ldT
   // exponent sums; the ratios of the chunk's quizzes that do not stay in LDS; the pinned result lines (records | counts | likelihood and
   // entropy per row); the events of option "time_sweeps".  The buffers grow and never shrink.

@@ -5,7 +5,7 @@
 // shards that separate processes drive; hip_engine_train.cpp: many trainings in one call; hip_engine_server.cpp: the resident sweep;
 // hip_engine_list.cpp: ListTopQuestions; hip_engine_among.cpp, hip_engine_top_among.cpp: the Among calls and the listing within listed
 // sets; hip_engine_sources.cpp: the source queries, target similarity, question redundancy and target separation; hip_engine_gain.cpp:
-// the information gain of every question of a quiz).
+// the information gain of every question of a quiz; hip_engine_page.cpp: conditional gains and question pages).
 #pragma once
 
 #include <sched.h>

@@ -824,4 +824,33 @@ struct GainAsked { const uint32_t *asked[kTopBatchQuizzes]; };
 hipError_t LaunchQuestionGains(const KbView &kb, const TopBatchPriors &priors, int64_t nQuizzes, double *rows, int64_t rowPitch, hipStream_t stream);
 hipError_t LaunchGainSlots(QuizSlot *slots, double *rows, int64_t rowPitch, const GainAsked &asked, int64_t nQuizzes, hipStream_t stream);
 
+// Question pages (page_kernels.hip): the BRANCH rows of a quiz under a set of questions -- its posterior times the answer ratios of
+// every combination of the set's answers, not normalised, branch b = ((k_1 K + k_2) K + ...) + k_j --, their masses, and the
+// conditional gain CG(q | S) = sum_b (m_b / M) gain(row b, q) over LaunchQuestionGains' rows for them.  rows[row][pitch] and
+// masses[row] are one scratch area of a call's chunk; a quiz's rows of a step lie next to each other, b ascending.  PageQuiz, in device
+// memory, is one quiz of ONE launch (the host writes a list per launch):
+//   LaunchPageRoots    row0 <- the quiz's posterior, 0 at gap targets, where it is not > 0 and behind T; masses[row0] its sum.
+//   LaunchPageExpand   a workgroup per parent row (grid.x = maxParents >= every nParents; a quiz with nParents == 0 sits the launch
+//                      out): rows [row0 + x K, row0 + (x + 1) K) <- parent parent0 + x times r_k of `question`, a LOCAL id, or with
+//                      kPagePickListed the id in pick->iTarget where *nPick > 0 -- no pick: zero rows, zero masses.  set[nSet] <- the
+//                      question (-1: none).  Parents and children must not overlap.
+//   LaunchPageCombine  combined[i][j] = sum_b (m_b / M) gains[gain0 + b][j] over the quiz's nRows rows at row0 (masses) and gain0
+//                      (gains): b ascending in one fma chain, a branch with a mass not > 0 left out, zeros where M is not > 0 or not
+//                      finite.  excl (optional): excl[i][exclWords] = the quiz's asked words | the bits of set[0 .. nSet).
+// All sums in a fixed order; no atomics.  K <= kTopBatchQuizzes; nRows <= kTopBatchQuizzes.
+constexpr int32_t kPagePickListed = -2;
+struct PageQuiz {
+  const uint32_t *asked;         // the combine's exclusion bitmap starts from it
+  const RatedTargetDev *pick;    // kPagePickListed: where the listing left the question ...
+  const int64_t *nPick;          // ... and how many it listed
+  int32_t *set;                  // the quiz's set so far, LOCAL ids in listed order (-1: a step without a pick)
+  int32_t parent0, nParents, row0, nRows, gain0, question, nSet, pad;
+};
+hipError_t LaunchPageRoots(const KbView &kb, const TopBatchPriors &priors, const PageQuiz *quizzes, int64_t nQuizzes, double *rows, int64_t pitch, double *masses,
+                           hipStream_t stream);
+hipError_t LaunchPageExpand(const KbView &kb, const PageQuiz *quizzes, int64_t nQuizzes, int64_t maxParents, double *rows, int64_t pitch, double *masses,
+                            hipStream_t stream);
+hipError_t LaunchPageCombine(const KbView &kb, const PageQuiz *quizzes, int64_t nQuizzes, const double *gains, int64_t gainPitch, const double *masses,
+                             double *combined, int64_t combPitch, uint32_t *excl, int64_t exclWords, hipStream_t stream);
+
 }  // namespace pqa

@@ -202,6 +202,8 @@ HIP_EXPORTS = {
     "PqaEngine_ListSeparatingQuestionsBatch": (_vp, [_vp, _i64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_EvalQuestionGainsBatch": (_vp, [_vp, _i64, _pi64, _pdbl, _i64]),
     "PqaEngine_ListInformativeQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
+    "PqaEngine_EvalConditionalGainsBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _pdbl, _i64]),
+    "PqaEngine_ListQuestionPageBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1341,6 +1343,43 @@ class PqaEngine:
 
     def list_informative_questions(self, quiz: int, max_count: int) -> List[Tuple[int, float]]:
         return self.list_informative_questions_batch([quiz], max_count)[0]
+
+    # ---- question pages (include/PqaHipExt.h: PqaEngine_EvalConditionalGainsBatch and its neighbour) ----
+    @staticmethod
+    def _given_sets(n: int, given):
+        """(counts pointer, ids pointer, keep-alive) of the quizzes' given sets; None: every set is empty (two NULL pointers)"""
+        if given is None:
+            return None, None, ()
+        assert len(given) == n, "one given set per quiz"
+        counts, ids = PqaEngine._groups(given)
+        return counts.ctypes.data_as(_pi64), ids.ctypes.data_as(_pi64), (counts, ids)
+
+    def eval_conditional_gains_batch(self, quizzes, given=None) -> np.ndarray:
+        """CG(q | given[i]) for every question q of the engine as an [n, questions] array: what q tells quizzes[i] about the target in
+        bits once the answers to the questions of given[i] (GLOBAL ids, in listed order) are known -- the answer combinations of the
+        set weighted by their probabilities under the quiz's posterior.  given=None or an empty set: eval_question_gains_batch's row
+        bit for bit.  At most 256 answer combinations a quiz.  Changes no quiz; regular mode; whole engines."""
+        qs = np.ascontiguousarray(quizzes, dtype=np.int64).reshape(-1)
+        counts, ids, keep = self._given_sets(len(qs), given)
+        q = self.get_option("local_questions")
+        out = np.zeros((len(qs), q), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalConditionalGainsBatch(self.c_engine, len(qs), qs.ctypes.data_as(_pi64), counts, ids, _dptr(out), q))
+        del keep
+        return out
+
+    def list_question_page_batch(self, quizzes, page_size: int, given=None) -> List[List[Tuple[int, float]]]:
+        """Per quiz a page of up to page_size questions as (question, bits) in pick order, filled greedily: each step takes the question
+        that tells most GIVEN the set so far (given[i], then the page's earlier picks) among those that are no gaps, not asked and
+        not in the set; bits are eval_conditional_gains_batch's for that prefix, and they add up to the page's joint information.
+        Changes no quiz: follow with set_active_question and record_answer per question the user answers."""
+        qs = np.ascontiguousarray(quizzes, dtype=np.int64).reshape(-1)
+        counts, ids, keep = self._given_sets(len(qs), given)
+        out = self._list_batch(_lib.PqaEngine_ListQuestionPageBatch, CiRatedQuestion, _pair, qs, page_size, counts, ids)
+        del keep
+        return out
+
+    def list_question_page(self, quiz: int, page_size: int, given=()) -> List[Tuple[int, float]]:
+        return self.list_question_page_batch([quiz], page_size, [list(given)])[0]
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
