@@ -683,14 +683,54 @@ PQACORE_API void *PqaEngine_ListInformativeQuestionsBatch(void *pvEngine, int64_
  *                                        prefix before it.  Entry 0 of a page with S empty is entry 0 of
  *                                        PqaEngine_ListInformativeQuestionsBatch.  pageSize 0 is no error.  The picks are made on the
  *                                        device and a page's steps are enqueued back to back: the host waits once per chunk of quizzes.
- * Whole engines only.  The branch rows need the given questions' blocks, which live on one rank: an engine made by
- * PqaEngineFactory_CreateHipEngineSharded and the one-process sharded engine (PQA_DEVICES) answer NotImplemented; a row-package form in
- * the manner of PqaHip_PackAnswerRows is left to a later change.  Read-only counters: "page_calls", "page_quizzes", and with
- * "time_sweeps" "page_device_ns". */
+ * These two calls are for whole engines.  The branch rows need the given questions' blocks, which live on one rank: an engine made by
+ * PqaEngineFactory_CreateHipEngineSharded and the one-process sharded engine (PQA_DEVICES) answer them NotImplemented; shards that
+ * separate processes drive use the block-package forms below.  Read-only counters: "page_calls", "page_quizzes", and with
+ * "time_sweeps" "page_device_ns" and, of it, "page_head_ns" (the roots and the given sets' expansions: what runs before the first sweep). */
 PQACORE_API void *PqaEngine_EvalConditionalGainsBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
                                                       const int64_t *pGiven, double *pOut, int64_t n);
 PQACORE_API void *PqaEngine_ListQuestionPageBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
                                                   const int64_t *pGiven, int64_t pageSize, CiRatedQuestion *pDest, int64_t *pCounts);
+/* Question pages across shards that separate processes drive.  The branch rows are functions of the quiz's posterior, which every shard
+ * holds whole, and of the blocks of the set's questions, which their owners hold: handed those blocks as a BLOCK PACKAGE
+ * (PqaHip_QuestionBlockSlotBytes a slot, the layout of PqaHip_PackQuestionBlocks), a shard builds the rows bit for bit as the owner would,
+ * sweeps ITS questions with the unchanged gain sweep and returns the whole engine's bits for them.
+ *   PqaHip_PackGivenBlocks      PqaHip_PackQuestionBlocks in REGULAR mode: GLOBAL ids; slot i receives the block where this engine holds
+ *                               question i, other slots are untouched; stream-ordered, no host wait; pFlag / flagValue as
+ *                               PqaHip_PackAnswerRows; everything is checked before any launch.  Deferred answers and a resident sweep are
+ *                               handled as PqaEngine_EvalQuestionGainsBatch handles them.  A gap question -- every shard knows the whole
+ *                               axis' gaps -- is IndexOutOfRange naming "questionId=".  Counted by "pack_calls" / "pack_bytes".
+ *   PqaEngine_EvalConditionalGainsBatchFromBlocks
+ *                               PqaEngine_EvalConditionalGainsBatch in everything -- (a) to (e), the chunking, n = the engine's OWN
+ *                               question count, pOut[i * n + j] = CG(q_first + j | S_i) -- except where a given question's block comes
+ *                               from: this engine's own cube where it holds the question, otherwise the slot of pBlocks whose entry in
+ *                               pBlockQuestions[0 .. nBlocks) names it (GLOBAL ids, distinct; a slot may serve many quizzes and
+ *                               positions).  Slots of questions the engine holds itself need not be filled and are not read.  Further
+ *                               refusals, decided before any launch and after the plain call's own: a negative nBlocks (NegativeCount)
+ *                               and NULL pBlockQuestions with nBlocks > 0 (NullArgument), with the argument checks; then slotBytes other
+ *                               than PqaHip_QuestionBlockSlotBytes (IndexOutOfRange; not looked at when nBlocks is 0 and pBlocks NULL); a
+ *                               given question this engine does not hold and the package does not name (IndexOutOfRange, "entry=" and
+ *                               "questionId="); pBlocks NULL while such a question exists (NullArgument).  pBlocks: device-visible
+ *                               memory, 16-byte aligned, valid until the call returns; a package in registered host memory is staged to
+ *                               the device first under option "rows_stage" (the needed slots only).  A whole engine accepts nBlocks 0 and
+ *                               pBlocks NULL and returns the plain call's bits.
+ *   PqaHip_SelectPageStepFromBlocks
+ *                               ONE step of a page for this engine's questions: per quiz {CG, GLOBAL id} of the question with the
+ *                               largest CG(q | S_i) > 0 among the engine's own questions that are no gaps, not asked by the quiz and not
+ *                               members of S_i, the lowest id among equals; {0, -1} without a candidate.  _priority carries exactly the
+ *                               bits the Eval form returns for that question.  It is the first step of PqaEngine_ListQuestionPageBatch's
+ *                               chunk: roots, the given levels' expansions, the gain sweep, the combine with the exclusion bitmap, the
+ *                               listing of one record; the host waits once per chunk.  Limit: nAnswers^|S_i| <= 256 and the scratch, as
+ *                               for Eval.  The same further refusals.  A host merges the ranks' records (the largest CG, the lowest id
+ *                               among equals), appends the pick to the sets and calls again: probqa_amd/dist.py list_question_page_batch.
+ * The one-process sharded engine answers all three NotImplemented.  "page_calls", "page_quizzes", "page_device_ns" count them too. */
+PQACORE_API void *PqaHip_PackGivenBlocks(void *pvEngine, int64_t nQuestions, const int64_t *pQuestions, void *pDst, void *pFlag, uint64_t flagValue);
+PQACORE_API void *PqaEngine_EvalConditionalGainsBatchFromBlocks(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
+                                                                const int64_t *pGiven, int64_t nBlocks, const int64_t *pBlockQuestions,
+                                                                const void *pBlocks, int64_t slotBytes, double *pOut, int64_t n);
+PQACORE_API void *PqaHip_SelectPageStepFromBlocks(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
+                                                  const int64_t *pGiven, int64_t nBlocks, const int64_t *pBlockQuestions, const void *pBlocks,
+                                                  int64_t slotBytes, CiHipSelection *pOut);
 /* This engine's (shard's) winner per quiz among its list, {priority, GLOBAL question id or -1}, without NextQuestion's bookkeeping: a
  * process-per-GPU host merges the shards' records (probqa_amd/dist.py: select_among_batch) and calls PqaEngine_SetActiveQuestion. */
 PQACORE_API void *PqaHip_SelectArgmaxAmongBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,

@@ -570,7 +570,8 @@ PQACORE_API void *PqaEngine_ListInformativeQuestionsBatch(void *pvEngine, const 
                                                           CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListInformativeQuestionsBatch(nQuizzes, pQuizzes, maxCount, pDest, pCounts); });
 }
-// ---- question pages (hip_engine_page.cpp): whole engines only -- the branch rows need the given questions' blocks, which one rank holds
+// ---- question pages (hip_engine_page.cpp): the plain calls on whole engines only -- the branch rows need the given questions' blocks, which
+// one rank holds --, the FromBlocks forms on shards that separate processes drive, the blocks in a package
 PQACORE_API void *PqaEngine_EvalConditionalGainsBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
                                                       const int64_t *pGiven, double *pOut, const int64_t n) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.EvalConditionalGainsBatch(nQuizzes, pQuizzes, pGivenCounts, pGiven, pOut, n); });
@@ -578,6 +579,23 @@ PQACORE_API void *PqaEngine_EvalConditionalGainsBatch(void *pvEngine, const int6
 PQACORE_API void *PqaEngine_ListQuestionPageBatch(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven,
                                                   const int64_t pageSize, CiRatedQuestion *pDest, int64_t *pCounts) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ListQuestionPageBatch(nQuizzes, pQuizzes, pGivenCounts, pGiven, pageSize, pDest, pCounts); });
+}
+PQACORE_API void *PqaHip_PackGivenBlocks(void *pvEngine, const int64_t nQuestions, const int64_t *pQuestions, void *pDst, void *pFlag, const uint64_t flagValue) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.PackGivenBlocks(nQuestions, pQuestions, pDst, pFlag, flagValue); });
+}
+PQACORE_API void *PqaEngine_EvalConditionalGainsBatchFromBlocks(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts,
+                                                                const int64_t *pGiven, const int64_t nBlocks, const int64_t *pBlockQuestions, const void *pBlocks,
+                                                                const int64_t slotBytes, double *pOut, const int64_t n) {
+  return ErrorOf(pvEngine, [&](IEngine &e) {
+    return e.EvalConditionalGainsBatchFromBlocks(nQuizzes, pQuizzes, pGivenCounts, pGiven, nBlocks, pBlockQuestions, pBlocks, slotBytes, pOut, n);
+  });
+}
+PQACORE_API void *PqaHip_SelectPageStepFromBlocks(void *pvEngine, const int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven,
+                                                  const int64_t nBlocks, const int64_t *pBlockQuestions, const void *pBlocks, const int64_t slotBytes,
+                                                  CiHipSelection *pOut) {
+  return ErrorOf(pvEngine, [&](IEngine &e) {
+    return e.SelectPageStepFromBlocks(nQuizzes, pQuizzes, pGivenCounts, pGiven, nBlocks, pBlockQuestions, pBlocks, slotBytes, pOut);
+  });
 }
 // Host memory (e.g. a shared-memory segment mapped by every rank) made writable by this process's GPU.
 PQACORE_API void *PqaHip_HostRegister(void *pHost, const int64_t nBytes, void **ppDevice) {

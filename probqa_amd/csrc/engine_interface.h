@@ -197,6 +197,16 @@ class IEngine {
   virtual Error ListQuestionPageBatch(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t, CiRatedQuestion *, int64_t *) {
     return NoPages("ListQuestionPageBatch");
   }
+  // ... and their forms for a shard that a process of its own drives, the given questions' blocks in a block package (PqaHip_PackGivenBlocks,
+  // PqaEngine_EvalConditionalGainsBatchFromBlocks, PqaHip_SelectPageStepFromBlocks); the one-process sharded engine does not offer them.
+  virtual Error PackGivenBlocks(int64_t, const int64_t *, void *, void *, uint64_t) { return NoPages("PackGivenBlocks"); }
+  virtual Error EvalConditionalGainsBatchFromBlocks(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t, const int64_t *, const void *, int64_t, double *,
+                                                    int64_t) {
+    return NoPages("EvalConditionalGainsBatchFromBlocks");
+  }
+  virtual Error SelectPageStepFromBlocks(int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t, const int64_t *, const void *, int64_t, CiHipSelection *) {
+    return NoPages("SelectPageStepFromBlocks");
+  }
   // A quiz with each of its answers left out (include/PqaHipExt.h: PqaEngine_ReviewAnswersBatch) and the quiz's recorded answers; the
   // one-process sharded engine reads the answers and does not offer the review.
   virtual int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) = 0;
@@ -212,7 +222,8 @@ class IEngine {
  protected:
   static Error NoPages(const char *what) {
     return Error::MakeP(ErrCode::NotImplemented, std::string("Feature=") + what + " on this engine",
-                        "Question pages need the given questions' blocks, which one rank holds: they are for whole engines.");
+                        "Question pages need the given questions' blocks, which one rank holds: the plain calls are for whole engines, the FromBlocks forms "
+                        "for shards that separate processes drive.");
   }
 
  private:

@@ -322,6 +322,7 @@ HipEngine::~HipEngine() {
   hipFree(_page.dRows); hipFree(_page.dMasses); hipFree(_page.dGains); hipFree(_page.dCombined); hipFree(_page.dExcl); hipFree(_page.dSet); hipFree(_page.dSlots);
   _page.lines.Free();
   for (hipEvent_t e : _page.ev) if (e) hipEventDestroy(e);
+  if (_page.evHead) hipEventDestroy(_page.evHead);
   for (SourceStage *st : {&_sim, &_red, &_sep}) {
     hipFree(st->dPackage); hipFree(st->dRows); hipFree(st->dScratch[0]); hipFree(st->dScratch[1]); hipFree(st->dSlots);
     st->lines.Free();
@@ -421,7 +422,8 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"gain_device_ns", &HipEngine::_gainDeviceNs},                      // ... and, with time_sweeps, their sweeps and listing kernels between events
       {"page_calls", &HipEngine::_pageCalls},                             // question page calls that were accepted (hip_engine_page.cpp) ...
       {"page_quizzes", &HipEngine::_pageQuizzes},                         // ... their quizzes ...
-      {"page_device_ns", &HipEngine::_pageDeviceNs},                      // ... and, with time_sweeps, their chunks' kernels between events
+      {"page_device_ns", &HipEngine::_pageDeviceNs},                      // ... and, with time_sweeps, their chunks' kernels between events ...
+      {"page_head_ns", &HipEngine::_pageHeadNs},                          // ... of which the roots and the given sets' expansions, before the first sweep
       {"similarity_calls", &HipEngine::_simCalls},                       // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events

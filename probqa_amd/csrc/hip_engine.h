@@ -274,6 +274,13 @@ class HipEngine : public IEngine {
   Error EvalConditionalGainsBatch(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, double *pOut, int64_t n) override;
   Error ListQuestionPageBatch(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, int64_t pageSize, CiRatedQuestion *pDest,
                               int64_t *pCounts) override;
+  // ... and on a shard that a process of its own drives: the given questions' blocks travel as a BLOCK PACKAGE (PackQuestionBlocks'
+  // slots, packed in regular mode), the rank sweeps its own questions over the same branch rows, the host merges a page's steps
+  Error PackGivenBlocks(int64_t n, const int64_t *pQuestions, void *pDst, void *pFlag, uint64_t flagValue) override;
+  Error EvalConditionalGainsBatchFromBlocks(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, int64_t nBlocks,
+                                            const int64_t *pBlockQuestions, const void *pBlocks, int64_t slotBytes, double *pOut, int64_t n) override;
+  Error SelectPageStepFromBlocks(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, int64_t nBlocks,
+                                 const int64_t *pBlockQuestions, const void *pBlocks, int64_t slotBytes, CiHipSelection *pOut) override;
   // a quiz's recorded answers, and the quiz with each of them left out: likelihood of the left-out answer, entropy and best targets of the
   // others' posterior (hip_engine_review.cpp)
   int64_t GetQuizAnswers(Error &err, int64_t iQuiz, AQ *pDest, int64_t capacity) override;
@@ -568,14 +575,22 @@ class HipEngine : public IEngine {
     size_t rowsBytes = 0, massesBytes = 0, gainsBytes = 0, combinedBytes = 0, exclBytes = 0;
     QuizSlot *dSlots = nullptr;
     ResultLines lines;
-    std::vector<int32_t> given;                  // LOCAL ids, one set after another
+    std::vector<int32_t> given;                  // LOCAL ids, one set after another (-1: a question another engine holds) ...
+    std::vector<int64_t> givenSlot;              // ... and for those the slot of the call's block package (-1: this engine's own cube)
     std::vector<int64_t> givenFirst, largest;    // nQuizzes + 1; the quizzes' branch rows at their largest step
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    const char *blocks = nullptr;                // the call's block package as the kernels read it (staged, where it was in host memory)
+    hipEvent_t ev[2] = {nullptr, nullptr}, evHead = nullptr;   // evHead: behind the last launch before a chunk's first sweep
   } _page;
+  // the block package of the FromBlocks forms (nullptr: the plain calls, which a shard refuses)
+  struct PageBlocks { int64_t n; const int64_t *questions; const void *blocks; int64_t slotBytes; };
   Error AdmitPageLocked(const char *call, int64_t rowLength, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven,
-                        int64_t pageSize, bool page);
+                        int64_t pageSize, bool page, const PageBlocks *pkg = nullptr);
+  Error EvalPageRows(const char *call, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, const PageBlocks *pkg, double *pOut,
+                     int64_t n);   // both Eval forms
+  Error StagePageBlocksLocked(const PageBlocks &pkg);   // st.blocks <- the package, its needed slots copied to the device first under option "rows_stage"
   Error PageChunkLocked(int64_t first, int64_t m, const int64_t *pQuizzes, int64_t steps);   // a chunk's launches, enqueued
-  uint64_t _pageCalls = 0, _pageQuizzes = 0, _pageDeviceNs = 0;   // read-only "page_calls", "page_quizzes", "page_device_ns"
+  // read-only "page_calls", "page_quizzes", "page_device_ns", "page_head_ns" (of the latter: the roots and the given sets' expansions, what comes before the first sweep)
+  uint64_t _pageCalls = 0, _pageQuizzes = 0, _pageDeviceNs = 0, _pageHeadNs = 0;
   // ReviewAnswersBatch (hip_engine_review.cpp): per row of a chunk _ldT mantissas (then the divided row) and, behind all of them, _ldT
   // exponent sums; the ratios of the chunk's quizzes that do not stay in LDS; the pinned result lines (records | counts | likelihood and
   // entropy per row); the events of option "time_sweeps".  The buffers grow and never shrink.

@@ -26,23 +26,30 @@ constexpr int64_t kPageMaxSteps = 9;
 
 // Everything both calls can be refused for under the lock, in the header's order from the row length on.  Fills st.given (LOCAL ids,
 // one set after another), st.givenFirst (nQuizzes + 1) and st.largest (the quizzes' branch rows at their largest step).
+// pkg (the FromBlocks forms): a given question another engine holds gets given -1 and givenSlot its slot of the package; the package's
+// own refusals come last.
 Error HipEngine::AdmitPageLocked(const char *call, int64_t rowLength, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven,
-                                 int64_t pageSize, bool page) {
-  if (IsShard()) return NoPages(call);
+                                 int64_t pageSize, bool page, const PageBlocks *pkg) {
+  if (!pkg && IsShard()) return NoPages(call);
   Error err = AdmitGainsLocked(rowLength, nQuizzes, pQuizzes);
   if (!err.ok()) return err;
   PageStage &st = _page;
   st.given.clear();
+  st.givenSlot.clear();
   st.givenFirst.assign(1, 0);
   st.largest.clear();
+  st.blocks = nullptr;
   for (int64_t i = 0, at = 0; i < nQuizzes; i++) {
     const int64_t c = pGivenCounts ? pGivenCounts[i] : 0;
     for (int64_t j = 0; j < c; j++) {
       const int64_t id = pGiven[at + j];
       const std::string where = "entry=" + std::to_string(i) + " questionId=" + std::to_string(id);
       if (id < 0 || id >= _qTotal) return Error::MakeP(ErrCode::IndexOutOfRange, where + " " + RangeParams(id, 0, _qTotal - 1), "A given question is out of range.");
-      if (BitTest(_hQGap, id - _qFirst)) return Error::MakeP(ErrCode::IndexOutOfRange, where, "A given question is a gap.");
-      st.given.push_back((int32_t)(id - _qFirst));
+      const bool own = OwnsQuestion(id);   // (a shard knows the whole axis' gaps)
+      if (own ? BitTest(_hQGap, id - _qFirst) : std::find(_globalQuestionGaps.begin(), _globalQuestionGaps.end(), id) != _globalQuestionGaps.end())
+        return Error::MakeP(ErrCode::IndexOutOfRange, where, "A given question is a gap.");
+      st.given.push_back(own ? (int32_t)(id - _qFirst) : -1);
+      st.givenSlot.push_back(-1);
     }
     at += c;
     st.givenFirst.push_back(at);
@@ -55,6 +62,52 @@ Error HipEngine::AdmitPageLocked(const char *call, int64_t rowLength, int64_t nQ
                           "A quiz's answer combinations must be at most 256 and their rows fit 64 MiB of scratch.");
     st.largest.push_back(branches);
   }
+  if (!pkg) return Error();
+  // ---- the package: its slot size, a slot for every given question this engine does not hold, and the package itself
+  if ((pkg->n > 0 || pkg->blocks) && pkg->slotBytes != QuestionBlockSlotBytes())
+    return Error::MakeP(ErrCode::IndexOutOfRange, "[slotBytes=" + std::to_string(pkg->slotBytes) + " of " + std::to_string(QuestionBlockSlotBytes()) + "]",
+                        "The block package's slot size is not this engine's (PqaHip_QuestionBlockSlotBytes).");
+  std::unordered_map<int64_t, int64_t> slotOf;
+  for (int64_t s = 0; s < pkg->n; s++) slotOf.emplace(pkg->questions[s], s);
+  bool foreign = false;
+  for (int64_t i = 0; i < nQuizzes; i++)
+    for (int64_t g = st.givenFirst[(size_t)i]; g < st.givenFirst[(size_t)i + 1]; g++) {
+      if (st.given[(size_t)g] >= 0) continue;
+      const auto it = slotOf.find(pGiven[g]);
+      if (it == slotOf.end())
+        return Error::MakeP(ErrCode::IndexOutOfRange, "entry=" + std::to_string(i) + " questionId=" + std::to_string(pGiven[g]),
+                            "A given question that this engine does not hold is not in the block package.");
+      st.givenSlot[(size_t)g] = it->second;
+      foreign = true;
+    }
+  if (foreign && !pkg->blocks) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the block package.");
+  if (foreign && (reinterpret_cast<uintptr_t>(pkg->blocks) & 15) != 0)
+    return Error::MakeP(ErrCode::IndexOutOfRange, "address mod 16=" + std::to_string(reinterpret_cast<uintptr_t>(pkg->blocks) & 15), "The package must be 16-byte aligned.");
+  return Error();
+}
+
+// The slots the call reads, where the kernels read them: a package in registered host memory is copied to the device first under option
+// "rows_stage" -- one copy per run of needed slots; this engine's own questions' slots may be unfilled and are not read.
+Error HipEngine::StagePageBlocksLocked(const PageBlocks &pkg) {
+  PageStage &st = _page;
+  st.blocks = static_cast<const char *>(pkg.blocks);
+  std::vector<char> needed((size_t)pkg.n, 0);
+  bool any = false;
+  for (int64_t s : st.givenSlot)
+    if (s >= 0) needed[(size_t)s] = 1, any = true;
+  if (!any || !IsStagedHostMemory(pkg.blocks)) return Error();
+  const size_t slotBytes = (size_t)pkg.slotBytes;
+  HIP_TRY(GrowDeviceBytes(&_dRowStage, _rowStageBytes, (size_t)pkg.n * slotBytes));
+  char *stage = static_cast<char *>(_dRowStage);
+  for (int64_t i = 0; i < pkg.n;) {
+    if (!needed[(size_t)i]) { i++; continue; }
+    int64_t j = i + 1;
+    while (j < pkg.n && needed[(size_t)j]) j++;
+    HIP_TRY(hipMemcpyAsync(stage + (size_t)i * slotBytes, st.blocks + (size_t)i * slotBytes, (size_t)(j - i) * slotBytes, hipMemcpyDefault, _stream));
+    i = j;
+  }
+  st.blocks = stage;
+  _rowsStaged++;
   return Error();
 }
 
@@ -65,6 +118,7 @@ Error HipEngine::PageChunkLocked(int64_t first, int64_t m, const int64_t *pQuizz
   if (steps > kPageMaxSteps) return Error::Make(ErrCode::Internal, "Internal error at hip_engine_page.cpp: a page outgrew its result lines.");   // (2^8 rows: 9 steps)
   const KbView kb = View();
   const int64_t pitch = _ldT, gainPitch = RedRowPitch(), exclWords = (_Q + 31) / 32;
+  const int64_t slotBytes = QuestionBlockSlotBytes(), blockLdT = st.blocks ? slotBytes / (_K + 1) / _elem : 0;   // (a slot's pitch: RoundLdT(T), not the allocation's)
   Error err;
   // ---- where the quizzes' rows lie: quiz j's at off[j] of either half of R rows
   std::vector<int64_t> off((size_t)m), branches((size_t)m, 1), side((size_t)m, 0), nGiven((size_t)m);
@@ -122,7 +176,12 @@ Error HipEngine::PageChunkLocked(int64_t first, int64_t m, const int64_t *pQuizz
         z.row0 = rowOf(j);
         z.nRows = (int32_t)branches[(size_t)j];
         if (level >= 0) {
-          z.question = st.given[(size_t)(st.givenFirst[(size_t)(first + j)] + level)];
+          const size_t g = (size_t)(st.givenFirst[(size_t)(first + j)] + level);
+          z.question = st.given[g];
+          if (st.givenSlot[g] >= 0) {   // another engine's question: its block in the package
+            z.question = kPageBlockGiven;
+            z.block = st.blocks + (size_t)st.givenSlot[g] * (size_t)slotBytes;
+          }
           z.nSet = (int32_t)level;
         } else {
           z.question = kPagePickListed;
@@ -173,13 +232,19 @@ Error HipEngine::PageChunkLocked(int64_t first, int64_t m, const int64_t *pQuizz
   if (!err.ok()) return err;
   TimerStart(st.ev);
   if (steps > 0) HIP_TRY(LaunchGainSlots(st.dSlots, st.dCombined, gainPitch, excl, m, _stream));
+  bool headTimed = false;
   for (const Launch &l : launches) {
+    if (l.kind == kSweep && !headTimed && _opt.timeSweeps) {   // what came before the first sweep: the roots and the given sets' expansions
+      headTimed = true;
+      if (!st.evHead && hipEventCreate(&st.evHead) != hipSuccess) { (void)hipGetLastError(); st.evHead = nullptr; }
+      if (st.evHead && hipEventRecord(st.evHead, _stream) != hipSuccess) (void)hipGetLastError();
+    }
     switch (l.kind) {
       case kRoot:
         HIP_TRY(LaunchPageRoots(kb, priors, dList + l.at, m, st.dRows, pitch, st.dMasses, _stream));
         break;
       case kExpand:
-        if (l.maxParents > 0) HIP_TRY(LaunchPageExpand(kb, dList + l.at, m, l.maxParents, st.dRows, pitch, st.dMasses, _stream));
+        if (l.maxParents > 0) HIP_TRY(LaunchPageExpand(kb, dList + l.at, m, l.maxParents, st.dRows, pitch, st.dMasses, blockLdT, _stream));
         break;
       case kSweep: {
         TopBatchPriors rows;
@@ -198,7 +263,12 @@ Error HipEngine::PageChunkLocked(int64_t first, int64_t m, const int64_t *pQuizz
       }
     }
   }
-  TimerStop(st.ev, _pageDeviceNs);
+  TimerStop(st.ev, _pageDeviceNs);   // (waits for its event, which lies behind evHead)
+  float headMs = 0;
+  if (headTimed && st.evHead && st.ev[0]) {
+    if (hipEventElapsedTime(&headMs, st.ev[0], st.evHead) == hipSuccess) _pageHeadNs += (uint64_t)(headMs * 1e6);
+    else (void)hipGetLastError();
+  }
   return Error();
 }
 
@@ -215,14 +285,32 @@ Error PageArguments(int64_t nQuizzes, int64_t pageSize, const int64_t *pGivenCou
   if (nQuizzes > 0 && (!buffersThere || (any && !pGiven))) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
   return Error();
 }
+// ... and of the FromBlocks forms, behind the plain call's own
+Error BlockArguments(int64_t nQuizzes, int64_t nBlocks, const int64_t *pBlockQuestions) {
+  if (nBlocks < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(nBlocks), "|nBlocks| must be non-negative.");
+  if (nQuizzes > 0 && nBlocks > 0 && !pBlockQuestions) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the package's questions.");
+  return Error();
+}
 }  // namespace
 
 Error HipEngine::EvalConditionalGainsBatch(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, double *pOut, int64_t n) {
+  return EvalPageRows("EvalConditionalGainsBatch", nQuizzes, pQuizzes, pGivenCounts, pGiven, nullptr, pOut, n);
+}
+
+Error HipEngine::EvalConditionalGainsBatchFromBlocks(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, int64_t nBlocks,
+                                                     const int64_t *pBlockQuestions, const void *pBlocks, int64_t slotBytes, double *pOut, int64_t n) {
+  const PageBlocks pkg{nBlocks, pBlockQuestions, pBlocks, slotBytes};
+  return EvalPageRows("EvalConditionalGainsBatchFromBlocks", nQuizzes, pQuizzes, pGivenCounts, pGiven, &pkg, pOut, n);
+}
+
+Error HipEngine::EvalPageRows(const char *call, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, const PageBlocks *pkg,
+                              double *pOut, int64_t n) {
   Error err = PageArguments(nQuizzes, 0, pGivenCounts, pGiven, pQuizzes && pOut);
+  if (err.ok() && pkg) err = BlockArguments(nQuizzes, pkg->n, pkg->questions);
   if (!err.ok()) return err;
   CallScope scope(_activeCallers);
   std::lock_guard<EngineMutex> lk(_mu);
-  err = AdmitPageLocked("EvalConditionalGainsBatch", n, nQuizzes, pQuizzes, pGivenCounts, pGiven, 0, false);
+  err = AdmitPageLocked(call, n, nQuizzes, pQuizzes, pGivenCounts, pGiven, 0, false, pkg);
   if (!err.ok() || nQuizzes == 0) return err;
   _pageCalls++;
   _pageQuizzes += (uint64_t)nQuizzes;
@@ -230,6 +318,10 @@ Error HipEngine::EvalConditionalGainsBatch(int64_t nQuizzes, const int64_t *pQui
   err = FlushUpdates();   // (the quizzes' deferred answers: their posteriors are read below)
   if (!err.ok()) return err;
   if (_serverLaunched) StopServer();   // a launched kernel has no room beside the resident sweep and would wait for it to idle out
+  if (pkg) {
+    err = StagePageBlocksLocked(*pkg);
+    if (!err.ok()) return err;
+  }
   const PageChunks plan = PlanPageChunks(nQuizzes, _page.largest.data(), _ldT);
   for (int64_t c = 0; c < plan.Chunks(); c++) {
     const int64_t first = plan.start[(size_t)c], m = plan.start[(size_t)c + 1] - first;
@@ -281,6 +373,83 @@ Error HipEngine::ListQuestionPageBatch(int64_t nQuizzes, const int64_t *pQuizzes
   }
   _mu.busy = false;   // (the stream has just been synchronised)
   _pendingRecordOp = 0;
+  return Error();
+}
+
+// One step of a page for this engine's questions: PageChunkLocked with one step, the record of quiz j at st.lines record j.
+Error HipEngine::SelectPageStepFromBlocks(int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pGivenCounts, const int64_t *pGiven, int64_t nBlocks,
+                                          const int64_t *pBlockQuestions, const void *pBlocks, int64_t slotBytes, CiHipSelection *pOut) {
+  Error err = PageArguments(nQuizzes, 1, pGivenCounts, pGiven, pQuizzes && pOut);
+  if (err.ok()) err = BlockArguments(nQuizzes, nBlocks, pBlockQuestions);
+  if (!err.ok()) return err;
+  const PageBlocks pkg{nBlocks, pBlockQuestions, pBlocks, slotBytes};
+  CallScope scope(_activeCallers);
+  std::lock_guard<EngineMutex> lk(_mu);
+  err = AdmitPageLocked("SelectPageStepFromBlocks", -1, nQuizzes, pQuizzes, pGivenCounts, pGiven, 1, true, &pkg);
+  if (!err.ok() || nQuizzes == 0) return err;
+  _pageCalls++;
+  _pageQuizzes += (uint64_t)nQuizzes;
+  hipSetDevice(_device);
+  err = FlushUpdates();
+  if (!err.ok()) return err;
+  if (_serverLaunched) StopServer();
+  err = StagePageBlocksLocked(pkg);
+  if (!err.ok()) return err;
+  const PageChunks plan = PlanPageChunks(nQuizzes, _page.largest.data(), _ldT);
+  for (int64_t c = 0; c < plan.Chunks(); c++) {
+    const int64_t first = plan.start[(size_t)c], m = plan.start[(size_t)c + 1] - first;
+    err = PageChunkLocked(first, m, pQuizzes, 1);
+    if (!err.ok()) return err;
+    HIP_TRY(hipStreamSynchronize(_stream));
+    for (int64_t j = 0; j < m; j++) {
+      const RatedTargetDev &rec = _page.lines.records[j];
+      const bool picked = _page.lines.Counts()[j] > 0 && rec.iTarget >= 0;
+      pOut[first + j]._priority = picked ? rec.prob : 0.0;
+      pOut[first + j]._iQuestion = picked ? _qFirst + rec.iTarget : -1;
+    }
+  }
+  _mu.busy = false;   // (the stream has just been synchronised)
+  _pendingRecordOp = 0;
+  return Error();
+}
+
+// PackQuestionBlocks in regular mode, for the given questions of the FromBlocks forms: the same launch, the same slots; a gap is refused.
+Error HipEngine::PackGivenBlocks(int64_t n, const int64_t *pQuestions, void *pDst, void *pFlag, uint64_t flagValue) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "The number of question blocks must be non-negative.");
+  if (n > 0 && (!pQuestions || !pDst)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of the questions or the package.");
+  CallScope scope(_activeCallers);
+  std::lock_guard<EngineMutex> lk(_mu);
+  Error err = CheckRegular("pack given blocks");
+  if (!err.ok()) return err;
+  int64_t m = 0;
+  for (int64_t i = 0; i < n; i++) {   // (everything is checked before anything is launched)
+    const int64_t id = pQuestions[i];
+    if (id < 0 || id >= _qTotal)
+      return Error::MakeP(ErrCode::IndexOutOfRange, "questionId=" + std::to_string(id) + " " + RangeParams(id, 0, _qTotal - 1), "Question index is not in KB range.");
+    const bool own = OwnsQuestion(id);
+    if (own ? BitTest(_hQGap, id - _qFirst) : std::find(_globalQuestionGaps.begin(), _globalQuestionGaps.end(), id) != _globalQuestionGaps.end())
+      return Error::MakeP(ErrCode::IndexOutOfRange, "questionId=" + std::to_string(id), "A given question is a gap.");
+    m += own ? 1 : 0;
+  }
+  if (m == 0 && pFlag == nullptr) return Error();
+  hipSetDevice(_device);
+  err = FlushUpdates();   // (the stream's order: nothing of a cube changes, but the deferred launches keep their place)
+  if (!err.ok()) return err;
+  if (_serverLaunched) StopServer();
+  const int64_t words = 2 + 2 * m;   // {arrival counter, pad}, then a BlockCopy per block of this engine's
+  err = EnsurePackList(words);
+  if (!err.ok()) return err;
+  BlockCopy *blocks = reinterpret_cast<BlockCopy *>(_hPack + 2);
+  const size_t slotBytes = (size_t)QuestionBlockSlotBytes();
+  for (int64_t i = 0, at = 0; i < n; i++)
+    if (OwnsQuestion(pQuestions[i])) blocks[at++] = BlockCopy{CubeAt(pQuestions[i] - _qFirst), static_cast<char *>(pDst) + (size_t)i * slotBytes};
+  MarkStreamBusy();
+  err = SubmitPackList(words);
+  if (!err.ok()) return err;
+  HIP_TRY(LaunchCopyQuestionBlocks(reinterpret_cast<const BlockCopy *>(_dAqs + 2), m, _K + 1, _T * _elem / 4, _ldT * _elem, (int64_t)slotBytes / (_K + 1), true,
+                                   reinterpret_cast<unsigned *>(_dAqs), static_cast<uint64_t *>(pFlag), flagValue, _stream));
+  _packCalls++;
+  _packBytes += (uint64_t)m * slotBytes;
   return Error();
 }
 

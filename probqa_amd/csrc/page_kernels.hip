@@ -18,7 +18,10 @@
 //                        ordered_sum_collect).  The question is a launch argument (a given one) or read HERE from the record the
 //                        listing left (a page's pick): no pick -- a row of zeros and a mass of 0 for every child, which the later
 //                        steps of that quiz then inherit.  Answer counts above kPagePiece: the same in pieces of kPagePiece answers.
-//                        The expansion also notes its question in the quiz's set.
+//                        The expansion also notes its question in the quiz's set.  A given question that another engine holds
+//                        (kPageBlockGiven) is read at the record's own pointer, a slot of a block package at the package's row
+//                        pitch: the same loads, the same arithmetic, so a child row has the bits the owner's cube gives; it is
+//                        noted as -1, which excludes nothing and is NOT "no pick".
 //   page_combine_kernel  a thread per (quiz, question): sum_b (m_b / M) rows[b][q] over the quiz's rows of the gain sweep's output
 //                        into the quiz's combined row; the first workgroup of a quiz also writes the quiz's exclusion bitmap, its
 //                        asked bits | its set so far, which the listing takes for an asked bitmap.
@@ -83,6 +86,7 @@ struct PageRows {
   const uint32_t *tgap;
   double *rows, *masses;    // [row][pitch], [row]
   int64_t Q, K, T, ldT, pitch;
+  int64_t blockLdT;         // the row pitch of a block package's slots in elements (kPageBlockGiven)
 };
 
 __global__ __launch_bounds__(kPageThreads) void page_root_kernel(PageRows a, TopBatchPriors priors) {
@@ -116,12 +120,13 @@ __global__ __launch_bounds__(kPageThreads) void page_expand_kernel(PageRows a) {
   const PageQuiz z = a.quizzes[blockIdx.y];
   if ((int)blockIdx.x >= z.nParents) return;
   int64_t q = z.question;
+  const bool packaged = q == kPageBlockGiven;   // (workgroup-uniform) another engine's question: no local id, its block lies in a package
   if (q == kPagePickListed) q = *z.nPick > 0 ? z.pick->iTarget : -1;
   if (q < 0 || q >= a.Q) q = -1;
   if (blockIdx.x == 0 && tid == 0) z.set[z.nSet] = (int32_t)q;
   const int K = (int)a.K;
   const int64_t child0 = (int64_t)z.row0 + (int64_t)blockIdx.x * K, T4 = (a.T + 3) & ~(int64_t)3;
-  if (q < 0) {   // (workgroup-uniform) no pick: nothing of this quiz is listed from here on
+  if (q < 0 && !packaged) {   // (workgroup-uniform) no pick: nothing of this quiz is listed from here on
     const double zeros[V] = {};
     for (int k = 0; k < K; k++) {
       for (int64_t t0 = (int64_t)tid * V; t0 < T4; t0 += (int64_t)kPageThreads * V) page_store_row<V>(a.rows + (child0 + k) * a.pitch, t0, zeros);
@@ -130,8 +135,8 @@ __global__ __launch_bounds__(kPageThreads) void page_expand_kernel(PageRows a) {
     return;
   }
   const double *parent = a.rows + (int64_t)(z.parent0 + (int)blockIdx.x) * a.pitch;
-  const int64_t ldT = a.ldT;
-  const E *block = static_cast<const E *>(a.cube) + q * (K + 1) * ldT;
+  const int64_t ldT = packaged ? a.blockLdT : a.ldT;
+  const E *block = packaged ? static_cast<const E *>(z.block) : static_cast<const E *>(a.cube) + q * (K + 1) * ldT;
   for (int k0 = 0; k0 < K; k0 += KP) {
     double acc[KP];
 #pragma unroll
@@ -240,17 +245,18 @@ hipError_t LaunchPageRoots(const KbView &kb, const TopBatchPriors &priors, const
     return hipErrorInvalidValue;
   for (int64_t i = 0; i < nQuizzes; i++)
     if (priors.prior[i] == nullptr || (reinterpret_cast<uintptr_t>(priors.prior[i]) & 15) != 0) return hipErrorInvalidValue;
-  const PageRows a{quizzes, kb.cube, kb.tgap, rows, masses, kb.Q, kb.K, kb.T, kb.ldT, pitch};
+  const PageRows a{quizzes, kb.cube, kb.tgap, rows, masses, kb.Q, kb.K, kb.T, kb.ldT, pitch, 0};
   hipLaunchKernelGGL(page_root_kernel, dim3((unsigned)nQuizzes), dim3(kPageThreads), 0, stream, a, priors);
   return hipGetLastError();
 }
 
 hipError_t LaunchPageExpand(const KbView &kb, const PageQuiz *quizzes, int64_t nQuizzes, int64_t maxParents, double *rows, int64_t pitch, double *masses,
-                            hipStream_t stream) {
+                            int64_t blockLdT, hipStream_t stream) {
   if (nQuizzes <= 0 || nQuizzes > kTopBatchQuizzes || maxParents <= 0 || maxParents > kTopBatchQuizzes || quizzes == nullptr || rows == nullptr || masses == nullptr ||
-      !page_kb_ok(kb, pitch) || (reinterpret_cast<uintptr_t>(rows) & 15) != 0)
+      !page_kb_ok(kb, pitch) || (reinterpret_cast<uintptr_t>(rows) & 15) != 0 ||
+      (blockLdT != 0 && (blockLdT < ((kb.T + 3) & ~(int64_t)3) || blockLdT % 4 != 0)))   // (a slot's rows are read 16 bytes a lane up to T4, as the cube's)
     return hipErrorInvalidValue;
-  const PageRows a{quizzes, kb.cube, kb.tgap, rows, masses, kb.Q, kb.K, kb.T, kb.ldT, pitch};
+  const PageRows a{quizzes, kb.cube, kb.tgap, rows, masses, kb.Q, kb.K, kb.T, kb.ldT, pitch, blockLdT};
   return kb.elem == 8 ? launch_expand<double>(a, nQuizzes, maxParents, stream) : launch_expand<float>(a, nQuizzes, maxParents, stream);
 }
 

@@ -833,15 +833,20 @@ hipError_t LaunchGainSlots(QuizSlot *slots, double *rows, int64_t rowPitch, cons
 //   LaunchPageExpand   a workgroup per parent row (grid.x = maxParents >= every nParents; a quiz with nParents == 0 sits the launch
 //                      out): rows [row0 + x K, row0 + (x + 1) K) <- parent parent0 + x times r_k of `question`, a LOCAL id, or with
 //                      kPagePickListed the id in pick->iTarget where *nPick > 0 -- no pick: zero rows, zero masses.  set[nSet] <- the
-//                      question (-1: none).  Parents and children must not overlap.
+//                      question (-1: none).  Parents and children must not overlap.  With kPageBlockGiven the question is one this
+//                      engine does not hold: its K + 1 rows are read at `block`, a slot of a block package (pitch blockLdT elements,
+//                      zeros behind T), set[nSet] <- -1 -- it has no local id and excludes nothing here.
 //   LaunchPageCombine  combined[i][j] = sum_b (m_b / M) gains[gain0 + b][j] over the quiz's nRows rows at row0 (masses) and gain0
 //                      (gains): b ascending in one fma chain, a branch with a mass not > 0 left out, zeros where M is not > 0 or not
 //                      finite.  excl (optional): excl[i][exclWords] = the quiz's asked words | the bits of set[0 .. nSet).
 // All sums in a fixed order; no atomics.  K <= kTopBatchQuizzes; nRows <= kTopBatchQuizzes.
-constexpr int32_t kPagePickListed = -2;
+constexpr int32_t kPagePickListed = -2, kPageBlockGiven = -3;
 struct PageQuiz {
   const uint32_t *asked;         // the combine's exclusion bitmap starts from it
-  const RatedTargetDev *pick;    // kPagePickListed: where the listing left the question ...
+  union {
+    const RatedTargetDev *pick;  // kPagePickListed: where the listing left the question ...
+    const void *block;           // kPageBlockGiven: the question's block in a block package, 16-byte aligned
+  };
   const int64_t *nPick;          // ... and how many it listed
   int32_t *set;                  // the quiz's set so far, LOCAL ids in listed order (-1: a step without a pick)
   int32_t parent0, nParents, row0, nRows, gain0, question, nSet, pad;
@@ -849,7 +854,7 @@ struct PageQuiz {
 hipError_t LaunchPageRoots(const KbView &kb, const TopBatchPriors &priors, const PageQuiz *quizzes, int64_t nQuizzes, double *rows, int64_t pitch, double *masses,
                            hipStream_t stream);
 hipError_t LaunchPageExpand(const KbView &kb, const PageQuiz *quizzes, int64_t nQuizzes, int64_t maxParents, double *rows, int64_t pitch, double *masses,
-                            hipStream_t stream);
+                            int64_t blockLdT /* 0: no record of the list is kPageBlockGiven */, hipStream_t stream);
 hipError_t LaunchPageCombine(const KbView &kb, const PageQuiz *quizzes, int64_t nQuizzes, const double *gains, int64_t gainPitch, const double *masses,
                              double *combined, int64_t combPitch, uint32_t *excl, int64_t exclWords, hipStream_t stream);
 

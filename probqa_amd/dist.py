@@ -768,6 +768,139 @@ def list_informative_questions_batch(engine, quizzes, max_count: int, rank: int,
     return _gather_top(listed, max_count, group, device)
 
 
+# ---- question pages over the shards ----------------------------------------------------------------------------------------------
+# CG(q | S) needs the branch rows of S -- functions of the quiz's posterior, which every rank holds whole, and of the blocks of S's
+# questions, which their owners hold.  The owners pack those blocks into a zero-filled BLOCK PACKAGE (PqaHip_PackGivenBlocks: one writer
+# per slot), ONE all_reduce(SUM) hands every rank every block -- x + 0 == x, the owner's bits --, and every rank builds the same rows and
+# sweeps its own questions (the FromBlocks calls).  A page is a loop of such steps over a package that grows by the picks: only the
+# picked question's block crosses between two steps.  Each step rebuilds the branch rows from the root: the call is stateless and every
+# value is by construction the Eval form's bits.  Over a process group with a device per rank nothing here has been timed
+# (tools/question_page_ranks_bench.py times the engine calls with the shards on one device).
+
+
+def _distinct(sets, known=()) -> List[int]:
+    """The questions of the sets that are not in `known`, each once, in order of first appearance."""
+    seen, out = set(known), []
+    for s in sets:
+        for q in s:
+            if q not in seen:
+                seen.add(q)
+                out.append(q)
+    return out
+
+
+def _block_package(engine, n_slots: int, device: torch.device) -> torch.Tensor:
+    """A zero-filled block package of n_slots slots in the engine's element type."""
+    elem = 4 if engine.get_option("precision") == 1 else 8
+    return torch.zeros(max(n_slots, 1), engine.question_block_slot_bytes() // elem, dtype=torch.float32 if elem == 4 else torch.float64, device=device)
+
+
+def _given_sets(quizzes, given) -> Tuple[List[int], List[List[int]]]:
+    quizzes = [int(z) for z in quizzes]
+    sets = [[] for _ in quizzes] if given is None else [[int(q) for q in s] for s in given]
+    if len(sets) != len(quizzes):
+        raise ValueError("one given set per quiz")
+    return quizzes, sets
+
+
+def eval_conditional_gains_batch(engine, quizzes, given, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                                 device: Optional[torch.device] = None):
+    """PqaEngine_EvalConditionalGainsBatch on the shards of `world` ranks: a collective every rank calls with the same quizzes and
+    given sets (GLOBAL ids).  Returns THIS rank's columns, [n, local questions]: the ranks' arrays side by side are the whole
+    engine's bits.  The package's slots are the distinct given questions in order of first appearance.  All or none: a rank whose
+    pack or evaluation is refused still takes part in the all-reduce and the status words, after which every rank raises the first
+    failing rank's text.  The package is a snapshot of the cube: no rank may train between the pack and the evaluation."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    quizzes, sets = _given_sets(quizzes, given)
+    slots = _distinct(sets)
+    pkg = _block_package(engine, len(slots), ranks.device)
+    error = _summed_package(ranks, engine, pkg, lambda ptr: engine.pack_given_blocks(slots, ptr))
+    ranks.settle(error)
+    out = None
+    try:
+        out = engine.eval_conditional_gains_batch_from_blocks(quizzes, sets, slots, pkg.data_ptr())
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)
+    return out
+
+
+def merge_page_step(records_per_rank) -> List[Tuple[int, float]]:
+    """records_per_rank: [world][n] records (bits, GLOBAL question or -1), the ranks' PqaHip_SelectPageStepFromBlocks results of one
+    step.  Per quiz the pick (question, bits): the largest bits > 0, the lowest question among equals; (-1, 0.0) without a candidate
+    (a NaN is none).  Plain Python, no collective."""
+    arr = records_per_rank.cpu().numpy() if isinstance(records_per_rank, torch.Tensor) else records_per_rank
+    n = len(arr[0]) if len(arr) else 0
+    picks = []
+    for i in range(n):
+        best_q, best = -1, 0.0
+        for part in arr:
+            bits, q = float(part[i][0]), int(part[i][1])
+            if q < 0 or not bits > 0:
+                continue
+            if best_q < 0 or bits > best or (bits == best and q < best_q):
+                best_q, best = q, bits
+        picks.append((best_q, best))
+    return picks
+
+
+def list_question_page_batch(engine, quizzes, page_size: int, given, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                             device: Optional[torch.device] = None) -> List[List[Tuple[int, float]]]:
+    """PqaEngine_ListQuestionPageBatch on the shards of `world` ranks: a collective every rank calls with the same quizzes, page size
+    and given sets.  Every rank returns the same (GLOBAL question, bits) records in pick order, the whole engine's.  Per step: the
+    owners pack the questions the package does not hold yet (the first step the given ones, later the picks: fresh quizzes all pick
+    the same first question, which crosses once), ONE all_reduce over those slots and a status word, one
+    PqaHip_SelectPageStepFromBlocks per rank and a status word, ONE all-gather of 16 bytes a quiz, and merge_page_step.  A quiz without a pick is finished and leaves the later
+    steps.  nAnswers^(|given| + page_size - 1) <= 256 is checked before the first step: every rank raises the same text.  All or
+    none per step as eval_conditional_gains_batch."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    quizzes, sets = _given_sets(quizzes, given)
+    page_size = int(page_size)
+    if page_size < 0:
+        raise interop.PqaException("[The count is negative] count=%d |pageSize| must be non-negative." % page_size)
+    k = engine.copy_dims().n_answers
+    for i, s in enumerate(sets):
+        if k ** (len(s) + max(page_size, 1) - 1) > 256:
+            raise interop.PqaException("[Index is out of range] entry=%d branches=>256 A quiz's answer combinations must be at most 256." % i)
+    pages = [[] for _ in quizzes]
+    active = list(range(len(quizzes)))
+    slots: List[int] = []
+    # every slot the call can need: the distinct given questions, and a pick per quiz and step but the last
+    pkg = _block_package(engine, len(_distinct(sets)) + len(quizzes) * max(page_size - 1, 0), ranks.device)
+    for _ in range(page_size):
+        if not active:
+            break
+        new = _distinct([sets[i] for i in active], slots)
+        if new:   # (the same on every rank: the sets are)
+            ranks.settle(_summed_package(ranks, engine, pkg[len(slots):len(slots) + len(new)], lambda ptr: engine.pack_given_blocks(new, ptr)))
+            slots.extend(new)
+        error, records = None, None
+        try:
+            records = engine.select_page_step_from_blocks([quizzes[i] for i in active], [sets[i] for i in active], slots, pkg.data_ptr())
+        except interop.PqaException as e:
+            error = str(e)
+        ranks.settle(error)
+        merged = merge_page_step(ranks.gather(torch.as_tensor(records, dtype=torch.float64)))
+        still = []
+        for i, (q, bits) in zip(active, merged):
+            if q >= 0:
+                pages[i].append((q, bits))
+                sets[i].append(q)
+                still.append(i)
+        active = still
+    return pages
+
+
+def list_question_page(engine, quiz: int, page_size: int, given, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                       device: Optional[torch.device] = None) -> List[Tuple[int, float]]:
+    """list_question_page_batch for one quiz."""
+    return list_question_page_batch(engine, [quiz], page_size, [list(given or ())], rank, world, group, device)[0]
+
+
 # ---- .kb files in the process-per-GPU form ---------------------------------------------------------------------------------
 # Every rank loads its own window of one file (PqaEngineFactory_LoadHipEngineAs: a seek to its two blocks of rows) and writes it back in
 # place (PqaHip_SaveKBShard); the rank that holds question 0 writes everything that is not a row.  The ranks write disjoint byte ranges

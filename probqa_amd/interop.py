@@ -204,6 +204,9 @@ HIP_EXPORTS = {
     "PqaEngine_ListInformativeQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaEngine_EvalConditionalGainsBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _pdbl, _i64]),
     "PqaEngine_ListQuestionPageBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
+    "PqaHip_PackGivenBlocks": (_vp, [_vp, _i64, _pi64, _vp, _vp, ctypes.c_uint64]),
+    "PqaEngine_EvalConditionalGainsBatchFromBlocks": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _i64, _pi64, _vp, _i64, _pdbl, _i64]),
+    "PqaHip_SelectPageStepFromBlocks": (_vp, [_vp, _i64, _pi64, _pi64, _pi64, _i64, _pi64, _vp, _i64, ctypes.POINTER(CiHipSelection)]),
     "PqaEngine_ListTopQuestions": (_i64, [_vp, _pvp, _i64, _i64, ctypes.POINTER(CiRatedQuestion)]),
     "PqaEngine_ListTopQuestionsBatch": (_vp, [_vp, _i64, _pi64, _i64, ctypes.POINTER(CiRatedQuestion), _pi64]),
     "PqaHip_HostLogicProbe": (_i64, [ctypes.c_char_p, _pi64, _i64, _pi64, _i64]),
@@ -1380,6 +1383,43 @@ class PqaEngine:
 
     def list_question_page(self, quiz: int, page_size: int, given=()) -> List[Tuple[int, float]]:
         return self.list_question_page_batch([quiz], page_size, [list(given)])[0]
+
+    # ... and across shards that separate processes drive: the given questions' blocks travel as a block package (dist.py runs the exchange)
+    def pack_given_blocks(self, questions: List[int], dst: int, flag: int = 0, flag_value: int = 0) -> None:
+        """pack_question_blocks in REGULAR mode, for the given questions of the two calls below: enqueue (no synchronisation) the copy of
+        those of the questions (GLOBAL ids) this engine holds into their slots (question_block_slot_bytes each) of the package at
+        device-visible address `dst`; a gap is refused."""
+        arr = (ctypes.c_int64 * max(len(questions), 1))(*questions)
+        _check(_lib.PqaHip_PackGivenBlocks(self.c_engine, len(questions), arr, ctypes.c_void_p(dst or None), ctypes.c_void_p(flag or None), flag_value))
+
+    def _block_args(self, quizzes, given, block_questions, blocks_ptr):
+        qs = np.ascontiguousarray(quizzes, dtype=np.int64).reshape(-1)
+        counts, ids, keep = self._given_sets(len(qs), given)
+        named = np.ascontiguousarray(list(block_questions), dtype=np.int64).reshape(-1)
+        slot = self.question_block_slot_bytes() if (len(named) or blocks_ptr) else 0
+        args = (len(qs), qs.ctypes.data_as(_pi64), counts, ids, len(named), named.ctypes.data_as(_pi64) if len(named) else None, ctypes.c_void_p(blocks_ptr or None), slot)
+        return qs, args, (keep, named)
+
+    def eval_conditional_gains_batch_from_blocks(self, quizzes, given, block_questions=(), blocks_ptr: int = 0) -> np.ndarray:
+        """eval_conditional_gains_batch for the questions THIS engine holds, as an [n, local questions] array: a given question the
+        engine does not hold is read from the slot of the package at device-visible address `blocks_ptr` that block_questions (GLOBAL
+        ids, distinct) names.  The whole engine's bits; whole engines and shards."""
+        qs, args, keep = self._block_args(quizzes, given, block_questions, blocks_ptr)
+        q = self.get_option("local_questions")
+        out = np.zeros((len(qs), q), dtype=np.float64)
+        _check(_lib.PqaEngine_EvalConditionalGainsBatchFromBlocks(self.c_engine, *args, _dptr(out), q))
+        del keep
+        return out
+
+    def select_page_step_from_blocks(self, quizzes, given, block_questions=(), blocks_ptr: int = 0) -> np.ndarray:
+        """One step of a page for the questions THIS engine holds: array [n, 2] of (bits, GLOBAL question id or -1) -- the question that
+        tells quizzes[i] most given given[i] among those that are no gaps, not asked and not in the set; the bits are
+        eval_conditional_gains_batch_from_blocks'.  dist.merge_page_step merges the ranks' records."""
+        qs, args, keep = self._block_args(quizzes, given, block_questions, blocks_ptr)
+        out = (CiHipSelection * max(len(qs), 1))()
+        _check(_lib.PqaHip_SelectPageStepFromBlocks(self.c_engine, *args, out))
+        del keep
+        return np.array([(out[i].priority, out[i].iQuestion) for i in range(len(qs))], dtype=np.float64).reshape(len(qs), 2)
 
     def list_top_questions(self, i_quiz: int, max_count: int) -> List[Tuple[int, float]]:
         """The quiz's best next questions as (question, priority), by descending priority (ascending question among equal priorities):
