@@ -820,6 +820,51 @@ PQACORE_API int64_t PqaEngine_ResumeQuizFromRows(void *pvEngine, void **ppError,
                                                  const CiAnsweredQuestion *pAQs, const void *pRows);
 PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_t nQuizzes, const int64_t *pCounts,
                                                     const CiAnsweredQuestion *pAQs, const void *pRows, int64_t *pQuizzes);
+/* A PAGE of answers per quiz in one launch: the way back of PqaEngine_ListQuestionPageBatch.  Quiz pQuizzes[i] receives the pCounts[i]
+ * answers that start at pAQs[sum(pCounts[0..i))], in that order, with GLOBAL question ids; pLikelihood (may be NULL) runs parallel to
+ * pAQs.  Where a client today calls PqaEngine_SetActiveQuestion + PqaEngine_RecordAnswer once per answer -- one launch and one pass of
+ * the posterior through memory each -- one workgroup per quiz keeps the posterior on chip and walks the page.
+ *  (a) Posterior: bit for bit what SetActiveQuestion(q_j) + RecordAnswer(a_j), j = 0 .. count - 1, leave -- per answer the element
+ *      product, the reference-order sum over max(1, workers - 1) subtasks, the division, by the update kernels' own device code -- on
+ *      Double and Float engines, at every row length, under the engine's current option "workers"; the NaNs a dead answer (a total of
+ *      0) produces included, as the update kernels leave them (at a target gap too: 0 / NaN; the update fused into a speculative sweep,
+ *      option "fuse_update", writes 0.0 there instead -- the one element in which RecordAnswer's own two routes differ).
+ *  (b) Bookkeeping, as the calls would do it: the asked bits are set -- a question that is repeated within the page or was asked before
+ *      is recorded again --, the answers are appended in order (PqaHip_GetQuizAnswers), the active question becomes -1, the last use
+ *      is touched.
+ *  (c) A quiz with pCounts[i] == 0 is not changed at all: its active question stays.
+ *  (d) pLikelihood[j] = the total of step j, the predictive probability of the answer that was given: the bits
+ *      PqaEngine_PreviewAnswersBatch returns for the quiz in its state just before that step, at (q_j, a_j).
+ *  (e) All or none.  Refusals, all decided before any quiz changes and before anything is launched, in this order: negative nQuizzes or
+ *      a negative count (NegativeCount, "entry="); a needed buffer NULL (NullArgument); maintenance mode or shutdown, as
+ *      PqaEngine_RecordAnswerBatch answers them; a count above 4096 (IndexOutOfRange, "entry="; a fixed limit: a chunk's pointer table
+ *      stays within 16 MiB); an unknown quiz ("entry=", "quizId="); a quiz that appears twice in the call (IndexOutOfRange, "entry=");
+ *      a question outside [0, nQuestions of the whole knowledge base) or a gap (IndexOutOfRange, "entry=", "position=", "questionId=":
+ *      PqaEngine_PreviewAnswersBatch's code for a gap); an answer outside [0, nAnswers) (IndexOutOfRange, "entry=", "position=").
+ *  (f) A shard engine that meets a question another shard holds answers NotImplemented from the plain call, in PqaEngine_ResumeQuiz's
+ *      wording; the FromRows form reads such a question's rows from slot j of a row package (PqaHip_PackAnswerRows over the
+ *      flattened pages; this engine's own slots may be left unfilled), as PqaEngine_ResumeQuizBatchFromRows does; pRows is valid
+ *      until the call returns, so a call that reads the package synchronises before it does.  Every shard knows
+ *      the gaps of the whole question axis, so the FromRows form refuses the same calls on every rank (probqa_amd/dist.py:
+ *      record_answer_page_batch -- one exchange per page).
+ *  (g) Engine state: deferred answers are applied first; a resident sweep is quiesced as PqaEngine_RecordAnswer does it; a speculative
+ *      sweep that belongs to one of the quizzes is dropped and no new one is launched (as PqaEngine_ResumeQuizBatch); a NextQuestion that
+ *      follows returns what it returns after the consecutive calls.
+ *  (h) The kernel lists the last posterior's best targets ahead of PqaEngine_ListTopTargets, as PqaEngine_RecordAnswerBatch's kernel
+ *      does (option "top_cache"): the listing that follows returns the records it returns after the consecutive calls.
+ *  (i) Any number of quizzes, 256 per launch: per chunk one pinned block of tables, one copy, one launch; the likelihoods are copied
+ *      back behind it and the stream is synchronised once per chunk only when pLikelihood is given -- without it nothing waits for the
+ *      device, as in PqaEngine_RecordAnswerBatch.  Rows that fit 64 KB of LDS beside the sum's scratch (about 8000 targets) stay on chip
+ *      across the page; longer ones are updated in place in memory, still in the one launch.
+ *  (j) Read-only options "record_page_calls", "page_answers", "page_launches": the accepted calls, their answers and their launches;
+ *      with "time_sweeps", "record_page_device_ns".  ("page_calls" and "page_device_ns" count the question pages.)
+ * The one-process sharded engine (PQA_DEVICES) validates the whole call and then serves it position by position through its gathered
+ * answers -- the same bits, no kernel of its own, no speed claimed -- and answers NotImplemented when pLikelihood is given; its FromRows
+ * form ignores the package. */
+PQACORE_API void *PqaEngine_RecordAnswerPageBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                  const CiAnsweredQuestion *pAQs, double *pLikelihood);
+PQACORE_API void *PqaEngine_RecordAnswerPageBatchFromRows(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                          const CiAnsweredQuestion *pAQs, double *pLikelihood, const void *pRows);
 
 /* ---- The sampled selector (PqaEngine_NextQuestionSampled, the reference's PqaCore/CpuEngine.cpp:362-400) on shards that separate
  * processes drive.  The selector splits the GLOBAL question axis into eval_subtasks subtasks (CalcSplit) and runs one Kahan chain

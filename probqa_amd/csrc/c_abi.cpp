@@ -481,6 +481,17 @@ PQACORE_API void *PqaEngine_ResumeQuizBatchFromRows(void *pvEngine, const int64_
                                                     const void *pRows, int64_t *pQuizzes) {
   return ErrorOf(pvEngine, [&](IEngine &e) { return e.ResumeQuizBatchFromRows(nQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pRows, pQuizzes); });
 }
+// ---- a page of answers per quiz in one launch (hip_engine_record_page.cpp); FromRows: other shards' rows from a row package
+PQACORE_API void *PqaEngine_RecordAnswerPageBatch(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                  const CiAnsweredQuestion *pAQs, double *pLikelihood) {
+  return ErrorOf(pvEngine, [&](IEngine &e) { return e.RecordAnswerPageBatch(nQuizzes, pQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pLikelihood); });
+}
+PQACORE_API void *PqaEngine_RecordAnswerPageBatchFromRows(void *pvEngine, int64_t nQuizzes, const int64_t *pQuizzes, const int64_t *pCounts,
+                                                          const CiAnsweredQuestion *pAQs, double *pLikelihood, const void *pRows) {
+  return ErrorOf(pvEngine, [&](IEngine &e) {
+    return e.RecordAnswerPageBatchFromRows(nQuizzes, pQuizzes, pCounts, reinterpret_cast<const AQ *>(pAQs), pLikelihood, pRows);
+  });
+}
 // ---- the sampled selector on shards driven by processes of their own: every rank packs a selection part per quiz, picks from the
 // gathered parts of all ranks and takes the agreed pick (hip_engine_parts.cpp)
 PQACORE_API int64_t PqaHip_SampledPartBytes(void *pvEngine) {

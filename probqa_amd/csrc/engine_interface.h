@@ -114,6 +114,10 @@ class IEngine {
   virtual Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) = 0;
   virtual int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) = 0;
   virtual Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) = 0;
+  // a page of answers per quiz (include/PqaHipExt.h: PqaEngine_RecordAnswerPageBatch)
+  virtual Error RecordAnswerPageBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood) = 0;
+  virtual Error RecordAnswerPageBatchFromRows(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood,
+                                              const void *pRows) = 0;
   // Compact on a shard that a process of its own drives: question blocks travel as a package.  The one-process sharded engine moves
   // its blocks itself: it plans and packs nothing, and compacts from no package as Compact does.
   virtual Error CompactPlanOf(int64_t *, int64_t *, int64_t *, const int64_t **, uint8_t *) { return NoBlocks("CompactPlan"); }

@@ -330,6 +330,7 @@ HipEngine::~HipEngine() {
   }
   hipFree(_dTopExact);
   hipFree(_dRowStage);
+  FreeRecordPage();
   hipFree(_dPartsWords); hipFree(_dPartsRun); hipFree(_dPartsGrand); hipFree(_dPartsPickRun);
   hipFree(_dPostScratch);
   if (_hPack) hipHostFree(_hPack);
@@ -424,7 +425,11 @@ int64_t HipEngine::GetOption(const char *name) const {
       {"page_quizzes", &HipEngine::_pageQuizzes},                         // ... their quizzes ...
       {"page_device_ns", &HipEngine::_pageDeviceNs},                      // ... and, with time_sweeps, their chunks' kernels between events ...
       {"page_head_ns", &HipEngine::_pageHeadNs},                          // ... of which the roots and the given sets' expansions, before the first sweep
-      {"similarity_calls", &HipEngine::_simCalls},                       // target similarity calls that were accepted (hip_engine_sources.cpp) ...
+      {"record_page_calls", &HipEngine::_recPageCalls},                   // pages-of-answers calls that were accepted (hip_engine_record_page.cpp) ...
+      {"page_answers", &HipEngine::_recPageAnswers},                      // ... their answers ...
+      {"page_launches", &HipEngine::_recPageLaunches},                    // ... their launches (one per chunk of 256 quizzes) ...
+      {"record_page_device_ns", &HipEngine::_recPageDeviceNs},            // ... and, with time_sweeps, those launches between events
+      {"similarity_calls", &HipEngine::_simCalls},                      // target similarity calls that were accepted (hip_engine_sources.cpp) ...
       {"similarity_sources", &HipEngine::_simSources},                    // ... the sources swept for ...
       {"similarity_device_ns", &HipEngine::_simDeviceNs},                 // ... and, with time_sweeps, a whole engine's sweeps between events
       {"redundancy_calls", &HipEngine::_redCalls},                        // question redundancy calls that were accepted (hip_engine_sources.cpp) ...

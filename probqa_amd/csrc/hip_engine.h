@@ -305,6 +305,11 @@ class HipEngine : public IEngine {
   Error PackAnswerRows(int64_t n, const AQ *pAQs, void *pDst, void *pFlag, uint64_t flagValue) override;
   int64_t ResumeQuizFromRows(Error &err, int64_t nAnswered, const AQ *pAQs, const void *pRows) override;
   Error ResumeQuizBatchFromRows(int64_t n, const int64_t *pCounts, const AQ *pAQs, const void *pRows, int64_t *pQuizzes) override;
+  // ---- a page of answers per quiz in one launch (hip_engine_record_page.cpp): what SetActiveQuestion + RecordAnswer per answer
+  // leave, bit for bit, with each step's total; FromRows: the rows of other shards' questions from a row package, as above
+  Error RecordAnswerPageBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood) override;
+  Error RecordAnswerPageBatchFromRows(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood,
+                                      const void *pRows) override;
   // ---- the sampled selector across such shards (hip_engine_parts.cpp; layout: sampled_part.h): every rank packs a SELECTION PART per quiz
   // behind its batched sweep, the ranks all-gather the parts, every rank picks from all of them, the ranks agree on the one pick
   // that is not -1, and every rank takes it -- the fallback over the whole question axis, the active question, the count
@@ -468,6 +473,20 @@ class HipEngine : public IEngine {
   char *_dResume = nullptr, *_hResume = nullptr;
   size_t _dResumeBytes = 0, _hResumeBytes = 0;
   uint64_t _resumeBatches = 0, _resumesBatched = 0;   // options "resume_batches", "resumes_batched": drains that ran posted ResumeQuiz calls, and those calls
+  // ---- pages of answers (hip_engine_record_page.cpp): a chunk's tables -- slots | row pointers | local question indices, and behind
+  // them on the device the likelihoods -- with their pinned source and the event behind its copy (nothing else waits for a chunk
+  // without likelihoods), the pinned lines the likelihoods come back in, the events of option "time_sweeps".  They grow and stay.
+  struct RecordPageStage {
+    char *dTables = nullptr, *hTables = nullptr;
+    size_t dBytes = 0, hBytes = 0;
+    double *hLikelihood = nullptr;
+    size_t hLikelihoodCount = 0;
+    hipEvent_t evCopy = nullptr, ev[2] = {nullptr, nullptr};
+  } _recPage;
+  void FreeRecordPage();
+  Error RecordPages(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood, bool fromRows, const void *pRows);
+  // read-only "record_page_calls", "page_answers", "page_launches", "record_page_device_ns" ("page_calls" and "page_device_ns" are the question pages')
+  uint64_t _recPageCalls = 0, _recPageAnswers = 0, _recPageLaunches = 0, _recPageDeviceNs = 0;
   StartBatchInline *_startBatch = nullptr;   // StartQuizBatch: CreateQuiz queues the new quizzes' buffers here instead of launching
   // the steps of one training call in execution order, appended to `out`; scratch: the caller's, reused from call to call
   void AppendTrainSteps(int64_t n, const AQ *pAQs, bool fromQuiz, std::vector<TrainStep> &out, std::vector<int64_t> &scratch) const;

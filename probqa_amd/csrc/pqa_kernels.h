@@ -512,6 +512,23 @@ struct RecordBatchInline {
   RecordSlot s[kRecordInline];
 };
 hipError_t LaunchRecordAnswerBatch(const KbView &kb, const RecordBatchInline &batch, int64_t nWorkers, hipStream_t stream);
+// A PAGE of answers per quiz in ONE launch (grid.x = quiz): workgroup i gives quiz i its `count` answers one after another -- per
+// answer RecordAnswer's element step, reference-order sum and division, the same device functions in the same order as
+// LaunchRecordAnswer, so the posterior is bit-identical to `count` consecutive launches -- with the posterior read once and written
+// once where a row fits the LDS stage, and in place in memory where it does not.  Slot i lies in device memory.
+constexpr int kRecordPageChunk = 256;      // quizzes per launch
+constexpr int64_t kRecordPageMax = 4096;   // answers per quiz: a chunk's pointer table stays within 16 MiB
+struct RecordPageSlot {
+  double *prior;
+  uint32_t *asked;
+  void *pin;                      // as RecordSlot's (optional: no listing without)
+  uint64_t topFlagValue;
+  const void *const *rows;        // 2 count row pointers, {sA[q_j][a_j], mD[q_j]} per answer, as ResumeSlot's
+  const int32_t *qLocal;          // count local question indices; -1: another shard's question, no bit of `asked` to set
+  double *likelihood;             // count doubles: step j's total, the predictive probability of answer j (optional)
+  int64_t count;                  // >= 1
+};
+hipError_t LaunchRecordAnswerPage(const KbView &kb, const RecordPageSlot *slots, int64_t n, int64_t nWorkers, int64_t topCount, hipStream_t stream);
 // Several quizzes' StartQuiz in ONE launch (grid.x = quiz; every workgroup runs CESetPriorsSubtaskSum exactly as LaunchStartQuiz).
 constexpr int kStartInline = 256;
 struct StartBatchInline {

@@ -187,6 +187,41 @@ struct TopRequest {
 // sA[q][a][.] and mD[q][.] are read where they are (that shard's cube over peer access, or a staged copy) and there is no bit of
 // this shard's bitmap to set; every shard then computes the posterior itself, the same bits everywhere.
 struct RowPair { const void *a, *d; };
+
+// ---- RecordAnswer's three steps -- the element step (answer_products over the rows answer_rows finds), reference_order_sum, the
+// division (answer_divide) -- as the update kernels (record_answer_body) and the page of answers (prior_kernels.hip:
+// record_answer_page_kernel) both run them.  A thread owns the same elements t = threadIdx.x + i blockDim.x in the element step and in
+// the division, so a step may run in place (old == stage, stage == dst).
+
+// Where the element step reads the answered question's rows: their offsets in elements from a.cube -- the engine's cube, or
+// (rowsElsewhere) the A row itself, which then stands in for the cube's base.
+__device__ __forceinline__ void answer_rows(PriorArgs &a, int64_t iQuestion, int64_t iAnswer, RowPair rowsElsewhere, int64_t &rowA, int64_t &rowD) {
+  rowA = (iQuestion * (a.K + 1) + iAnswer) * a.ldT;  // CERecordAnswerSubtaskMul.cpp:25
+  rowD = (iQuestion * (a.K + 1) + a.K) * a.ldT;      // :26
+  if (rowsElsewhere.a != nullptr) {   // (wave-uniform)
+    a.cube = rowsElsewhere.a;
+    rowA = 0;
+    rowD = (int64_t)((static_cast<const char *>(rowsElsewhere.d) - static_cast<const char *>(rowsElsewhere.a)) / a.elem);
+  }
+}
+
+// dst[t] = stage[t] / total over the 4 nVects elements of the sum (CEDivTargPriorsSubtask.h:19); the row's padding behind them is
+// carried over as it is.
+template <bool SMALL>
+__device__ __forceinline__ void answer_divide(const double *stage, double *dst, double total, int64_t ldT, int64_t nVects) {
+  const int64_t step = blockDim.x;
+  int64_t t = threadIdx.x;
+  if constexpr (!SMALL)
+  for (; t + 3 * step < ldT; t += 4 * step) {
+    double x[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) x[e] = stage[t + e * step];
+#pragma unroll
+    for (int e = 0; e < 4; e++) dst[t + e * step] = t + e * step < 4 * nVects ? x[e] / total : x[e];
+  }
+  for (; t < ldT; t += step) dst[t] = t < 4 * nVects ? stage[t] / total : stage[t];
+}
+
 template <bool SMALL, bool COH>
 __device__ __forceinline__ void record_answer_body(PriorArgs a, int64_t iQuestion, int64_t iAnswer, uint32_t *asked, TopRequest top,
                                                    double *lds, TopScratch *topScratch, RowPair rowsElsewhere = RowPair{nullptr, nullptr}) {
@@ -197,27 +232,12 @@ __device__ __forceinline__ void record_answer_body(PriorArgs a, int64_t iQuestio
     asked[iQuestion >> 5] = w | (1u << (iQuestion & 31));
   }
   const int64_t nVects = (a.T + 3) >> 2;
-  int64_t rowA = (iQuestion * (a.K + 1) + iAnswer) * a.ldT;  // CERecordAnswerSubtaskMul.cpp:25
-  int64_t rowD = (iQuestion * (a.K + 1) + a.K) * a.ldT;      // :26
-  if (rowsElsewhere.a != nullptr) {   // (wave-uniform; offsets in elements from the A row, which stands in for the cube's base)
-    a.cube = rowsElsewhere.a;
-    rowA = 0;
-    rowD = (int64_t)((static_cast<const char *>(rowsElsewhere.d) - static_cast<const char *>(rowsElsewhere.a)) / a.elem);
-  }
+  int64_t rowA, rowD;
+  answer_rows(a, iQuestion, iAnswer, rowsElsewhere, rowA, rowD);
   double *stage = prior_stage(a, lds);
   answer_products<SMALL, COH>(a, rowA, rowD, a.prior, stage);
   const double total = reference_order_sum<!SMALL>(stage, nVects, a.nWorkers, lds);
-  const int64_t step = blockDim.x;
-  int64_t t = threadIdx.x;
-  if constexpr (!SMALL)
-  for (; t + 3 * step < a.ldT; t += 4 * step) {
-    double x[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) x[e] = stage[t + e * step];
-#pragma unroll
-    for (int e = 0; e < 4; e++) a.prior[t + e * step] = t + e * step < 4 * nVects ? x[e] / total : x[e];
-  }
-  for (; t < a.ldT; t += step) a.prior[t] = t < 4 * nVects ? stage[t] / total : stage[t];
+  answer_divide<SMALL>(stage, a.prior, total, a.ldT, nVects);
   if constexpr (COH) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // posterior and asked bit out of this XCD's L2
   if (top.count > 0) {
     __syncthreads();  // (a thread lists exactly the targets it has just written; the barrier is for the shared LDS rows)

@@ -78,6 +78,46 @@ __global__ __launch_bounds__(SMALL ? kSmallThreads : kThreads) void record_answe
   record_answer_body<SMALL, false>(a, s.iQuestion, s.iAnswer, s.asked, top, lds, &topScratch, RowPair{s.rowA, s.rowD});
 }
 
+// grid.x = quiz: workgroup i gives slot i's quiz the answers of its page, one after another.  Every step is RecordAnswer's three steps
+// (prior_device.h) on the rows the slot points to, so the posterior after step j carries the bits of j + 1 consecutive
+// record_answer_kernel launches.  Where the row fits the LDS stage the posterior is read from memory once, lives in the stage across
+// the steps (a thread owns the same elements in every step) and is written once, by the last step's division; where it does not, the
+// steps run in place on the posterior in memory.  Step j's total goes to likelihood[j].  The asked bits of the page's local questions
+// are set in stream order, the last posterior's best targets are listed as record_answer_batch_kernel lists them.
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? kSmallThreads : kThreads) void record_answer_page_kernel(PriorArgs a, const RecordPageSlot *__restrict__ slots, int topCount) {
+  extern __shared__ double lds[];
+  __shared__ TopScratch topScratch;
+  const RecordPageSlot s = slots[blockIdx.x];
+  a.prior = s.prior;
+  if (threadIdx.x == 0)   // CEQuiz::RecordAnswer, PqaCore/CEQuiz.h:92, for every answer of the page
+    for (int64_t j = 0; j < s.count; j++) {
+      const int32_t q = s.qLocal[j];
+      if (q >= 0) s.asked[q >> 5] |= 1u << (q & 31);
+    }
+  const int64_t nVects = (a.T + 3) >> 2;
+  double *stage = prior_stage(a, lds);
+  if (a.stage)
+    for (int64_t t = threadIdx.x; t < a.ldT; t += blockDim.x) stage[t] = a.prior[t];
+  for (int64_t j = 0; j < s.count; j++) {
+    PriorArgs r = a;
+    int64_t rowA, rowD;
+    answer_rows(r, 0, 0, RowPair{s.rows[2 * j], s.rows[2 * j + 1]}, rowA, rowD);
+    answer_products<SMALL, false>(r, rowA, rowD, stage, stage);
+    const double total = reference_order_sum<!SMALL>(stage, nVects, a.nWorkers, lds);
+    if (threadIdx.x == 0 && s.likelihood != nullptr) s.likelihood[j] = total;
+    const bool last = j + 1 == s.count;
+    answer_divide<SMALL>(stage, last ? a.prior : stage, total, a.ldT, nVects);
+    if (!last) __syncthreads();
+  }
+  if (topCount > 0 && s.pin != nullptr) {
+    TopOut *topOut = reinterpret_cast<TopOut *>(s.pin);
+    int64_t *topN = reinterpret_cast<int64_t *>(topOut + kQuizTopDev);
+    __syncthreads();  // (as record_answer_body: for the shared LDS rows)
+    top_targets_publish<SMALL>(a.prior, a.tgap, a.T, topCount, topOut, topN, reinterpret_cast<uint64_t *>(topN + 1), s.topFlagValue, &topScratch);
+  }
+}
+
 // rows: for answered question i the rows sA[q_i][a_i][.] (rows[2i]) and mD[q_i][.] (rows[2i + 1]) -- pointers instead of
 // indices, so that the rows of a question held by ANOTHER device of the process (a shard of the question axis,
 // sharded_engine.cpp) are read in place over xGMI peer access.
@@ -535,6 +575,19 @@ hipError_t LaunchRecordAnswerBatch(const KbView &kb, const RecordBatchInline &ba
   else
     hipLaunchKernelGGL(record_answer_batch_kernel<false>, dim3((unsigned)b.n), dim3(kThreads), staged_lds_bytes(kb, nWorkers), stream,
                        make_args(kb, nullptr, nWorkers, true), b);
+  return hipGetLastError();
+}
+
+hipError_t LaunchRecordAnswerPage(const KbView &kb, const RecordPageSlot *slots, int64_t n, int64_t nWorkers, int64_t topCount, hipStream_t stream) {
+  if (nWorkers < 1 || nWorkers > kMaxWorkers || n < 1 || n > kRecordPageChunk || slots == nullptr) return hipErrorInvalidValue;
+  const int top = kb.T <= 16384 ? (int)topCount : 0;
+  // the update kernels' two shapes (LaunchRecordAnswerBatch)
+  if (kb.T <= 4 * kSmallThreads)
+    hipLaunchKernelGGL(record_answer_page_kernel<true>, dim3((unsigned)n), dim3(kSmallThreads), staged_lds_bytes(kb, nWorkers), stream,
+                       make_args(kb, nullptr, nWorkers, true), slots, top);
+  else
+    hipLaunchKernelGGL(record_answer_page_kernel<false>, dim3((unsigned)n), dim3(kThreads), staged_lds_bytes(kb, nWorkers), stream,
+                       make_args(kb, nullptr, nWorkers, true), slots, top);
   return hipGetLastError();
 }
 

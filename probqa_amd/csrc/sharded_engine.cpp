@@ -32,6 +32,8 @@
 // shards (Rebuild below).  Not sharded (NotImplemented on this engine): SetStream and the stream-ordered single-shard entry points.
 #include "hip_engine_internal.h"
 
+#include <unordered_set>
+
 namespace pqa {
 
 namespace {
@@ -218,6 +220,12 @@ class ShardedEngine final : public IEngine {
     if (n > 0 && (!pQuizzes || !pAnswers)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
     for (int64_t i = 0; i < n; i++) { Error e = RecordAnswerDeferred(pQuizzes[i], pAnswers[i]); if (!e.ok()) return e; }
     return FlushNow();
+  }
+  // A page of answers per quiz: validated whole, in the one-device engine's order, then served position by position through the
+  // gathered answers (one hand-over to the shards per position: the bits of the consecutive calls; no kernel of its own, no speed claimed)
+  Error RecordAnswerPageBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood) override;
+  Error RecordAnswerPageBatchFromRows(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood, const void *) override {
+    return RecordAnswerPageBatch(n, pQuizzes, pCounts, pAQs, pLikelihood);   // (this engine holds every question: a package has nothing to add)
   }
   Error ListTopTargetsBatch(int64_t n, const int64_t *pQuizzes, int64_t maxCount, CiRatedTarget *pDest, int64_t *pCounts) override {
     // every shard holds every quiz's whole posterior: the gathered answers reach the shards, then one of them lists
@@ -961,6 +969,65 @@ Error ShardedEngine::RecordAnswer(int64_t iQuiz, int64_t iAnswer) {
   // Alone in the engine: the shards' kernels start now, under whatever the client does next.  Other clients inside: the answer
   // waits for the next call that needs a posterior -- which hands over all that have gathered by then, in one launch per shard.
   return Concurrent() ? Error() : FlushNow();
+}
+
+Error ShardedEngine::RecordAnswerPageBatch(int64_t n, const int64_t *pQuizzes, const int64_t *pCounts, const AQ *pAQs, double *pLikelihood) {
+  if (n < 0) return Error::MakeP(ErrCode::NegativeCount, "count=" + std::to_string(n), "|nQuizzes| must be non-negative.");
+  if (n > 0 && (!pQuizzes || !pCounts)) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of a batch buffer.");
+  int64_t total = 0, longest = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (pCounts[i] < 0)
+      return Error::MakeP(ErrCode::NegativeCount, "entry=" + std::to_string(i) + " count=" + std::to_string(pCounts[i]), "A page's number of answers must be non-negative.");
+    total += pCounts[i];
+    longest = std::max(longest, pCounts[i]);
+  }
+  if (total > 0 && pAQs == nullptr) return Error::Make(ErrCode::NullArgument, "Nullptr is passed in place of answered questions.");
+  if (pLikelihood != nullptr) return NotSharded("RecordAnswerPageBatch with likelihoods");
+  CallScope scope(_activeCallers);
+  if (!_sh[0]->IsRegularMode()) return QuizError(n > 0 ? pQuizzes[0] : -1);
+  for (int64_t i = 0; i < n; i++)
+    if (pCounts[i] > kRecordPageMax)
+      return Error::MakeP(ErrCode::IndexOutOfRange, "entry=" + std::to_string(i) + " " + RangeParams(pCounts[i], 0, kRecordPageMax), "A page holds at most 4096 answers.");
+  for (int64_t i = 0; i < n; i++) {
+    Error e = LiveRow(pQuizzes[i]) ? FailedQuiz(pQuizzes[i]) : QuizError(pQuizzes[i]);
+    if (e.ok() && !LiveRow(pQuizzes[i])) e = Error::Make(ErrCode::Internal, "The quiz tables have diverged.");
+    if (!e.ok()) {
+      e.params = "entry=" + std::to_string(i) + " quizId=" + std::to_string(pQuizzes[i]) + (e.hasParams ? " " + e.params : std::string());
+      e.hasParams = true;
+      return e;
+    }
+  }
+  {
+    std::unordered_set<int64_t> seen;
+    for (int64_t i = 0; i < n; i++)
+      if (!seen.insert(pQuizzes[i]).second)
+        return Error::MakeP(ErrCode::IndexOutOfRange, "entry=" + std::to_string(i) + " quizId=" + std::to_string(pQuizzes[i]), "A quiz appears twice in the call.");
+  }
+  for (int64_t i = 0, at = 0; i < n; i++)
+    for (int64_t j = 0; j < pCounts[i]; j++, at++) {
+      const int64_t id = pAQs[at].iQuestion;
+      const std::string where = "entry=" + std::to_string(i) + " position=" + std::to_string(j) + " questionId=" + std::to_string(id);
+      if (id < 0 || id >= _Q) return Error::MakeP(ErrCode::IndexOutOfRange, where + " " + RangeParams(id, 0, _Q - 1), "A page's question is out of range.");
+      if (_qGapBit[(size_t)id]) return Error::MakeP(ErrCode::IndexOutOfRange, where, "A page's question is a gap.");
+    }
+  for (int64_t i = 0, at = 0; i < n; i++)
+    for (int64_t j = 0; j < pCounts[i]; j++, at++)
+      if (pAQs[at].iAnswer < 0 || pAQs[at].iAnswer >= _K)
+        return Error::MakeP(ErrCode::IndexOutOfRange, "entry=" + std::to_string(i) + " position=" + std::to_string(j) + " " + RangeParams(pAQs[at].iAnswer, 0, _K - 1),
+                            "Answer index is not in the answer range.");
+  for (int64_t p = 0; p < longest; p++) {
+    for (int64_t i = 0, at = 0; i < n; at += pCounts[i], i++) {
+      if (pCounts[i] <= p) continue;
+      QuizRow *r = LiveRow(pQuizzes[i]);
+      if (!r) return QuizError(pQuizzes[i]);
+      r->active.store(pAQs[at + p].iQuestion, std::memory_order_relaxed);
+      Error e = RecordAnswerDeferred(pQuizzes[i], pAQs[at + p].iAnswer);
+      if (!e.ok()) return e;
+    }
+    Error e = FlushNow();
+    if (!e.ok()) return e;
+  }
+  return Error();
 }
 
 Error ShardedEngine::FlushAnswers() {

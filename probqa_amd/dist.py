@@ -662,6 +662,49 @@ def record_answer(engine, quiz: int, answer: int, rank: int, world: int, group: 
     record_answer_batch(engine, [quiz], [answer], rank, world, group, device)
 
 
+def record_answer_page_batch(engine, quizzes, pages, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                             device: Optional[torch.device] = None, likelihoods: bool = False):
+    """PqaEngine_RecordAnswerPageBatch on the shards of `world` ranks: a collective every rank calls with the same quizzes and the
+    same pages (lists of AnsweredQuestion, GLOBAL question ids).  The row package of resume_quiz_batch -- pack_answer_rows over the
+    flattened pages, ONE all_reduce -- and one recording per rank (PqaEngine_RecordAnswerPageBatchFromRows): one exchange per
+    page, where record_answer_batch per position costs a posterior package each.  A status word comes before the recording: if any
+    rank's pack or look-up of the quizzes is refused nobody records, and every rank raises the first failing rank's text.  The recording validates the whole
+    call before it changes anything, identically on every rank (every rank knows the gaps of the whole question axis); a second
+    status word covers it.  Returns None, or with `likelihoods` each quiz's list of its steps' totals, the same on every rank.  The
+    package is a snapshot of the cube: no rank may train between the pack and the recording inside this call."""
+    from . import interop
+
+    ranks = _Ranks(group, device, rank, world)
+    quizzes, pages = [int(q) for q in quizzes], [list(p) for p in pages]
+    flat = [aq for p in pages for aq in p]
+    pkg = _package(engine, len(flat), ranks.device)
+
+    def validate_and_pack(ptr):
+        for i, q in enumerate(quizzes):                       # what may differ between the ranks: the mode, the quiz registry
+            try:
+                engine.get_active_question_id(q)
+            except interop.PqaException as e:
+                raise interop.PqaException("entry=%d quizId=%d: %s" % (i, q, e))
+        engine.pack_answer_rows(flat, ptr)
+
+    error = _summed_package(ranks, engine, pkg, validate_and_pack)
+    ranks.settle(error)
+    result = None
+    try:
+        result = engine.record_answer_page_batch_from_rows(quizzes, pages, pkg.data_ptr(), likelihoods)
+    except interop.PqaException as e:
+        error = str(e)
+    ranks.settle(error)
+    return result
+
+
+def record_answer_page(engine, quiz: int, page, rank: int, world: int, group: Optional[dist.ProcessGroup] = None,
+                       device: Optional[torch.device] = None, likelihoods: bool = False):
+    """record_answer_page_batch for one quiz: None, or the list of its steps' likelihoods."""
+    result = record_answer_page_batch(engine, [quiz], [page], rank, world, group, device, likelihoods)
+    return result[0] if likelihoods else None
+
+
 def _list_from_summed_packages(engine, ranks: _Ranks, sources, pitch: int, pack, list_from, finish=None) -> list:
     """The source listings' exchange, 256 sources at a time: a zero-filled package of `pitch` doubles a source, pack(chunk, address)
     and the all-reduce (_summed_package), the status word, list_from(chunk, address), the status word; finish (optional): what turns a

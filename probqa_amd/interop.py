@@ -175,6 +175,8 @@ HIP_EXPORTS = {
     "PqaEngine_RecordAnswerBatchFromPosteriors": (_vp, [_vp, _i64, _pi64, _pi64, _vp]),
     "PqaEngine_ResumeQuizFromRows": (_i64, [_vp, _pvp, _i64, _pAQ, _vp]),
     "PqaEngine_ResumeQuizBatchFromRows": (_vp, [_vp, _i64, _pi64, _pAQ, _vp, _pi64]),
+    "PqaEngine_RecordAnswerPageBatch": (_vp, [_vp, _i64, _pi64, _pi64, _pAQ, _pdbl]),
+    "PqaEngine_RecordAnswerPageBatchFromRows": (_vp, [_vp, _i64, _pi64, _pi64, _pAQ, _pdbl, _vp]),
     "PqaEngine_RecordAnswerBatch": (_vp, [_vp, _i64, _pi64, _pi64]),
     "PqaEngine_StartQuizBatch": (_vp, [_vp, _i64, _pi64]),
     "PqaEngine_ResumeQuizBatch": (_vp, [_vp, _i64, _pi64, _pAQ, _pi64]),
@@ -976,6 +978,45 @@ class PqaEngine:
         out = (ctypes.c_int64 * max(n, 1))()
         _check(_lib.PqaEngine_ResumeQuizBatchFromRows(self.c_engine, n, counts, arr, ctypes.c_void_p(rows or None), out))
         return list(out[:n])
+
+    # ---- a page of answers per quiz in one launch (include/PqaHipExt.h: PqaEngine_RecordAnswerPageBatch) ------------------
+    def _record_pages(self, quizzes, pages, likelihoods: bool, rows: Optional[int]):
+        quizzes, pages = list(quizzes), [list(p) for p in pages]
+        if len(quizzes) != len(pages):
+            raise ValueError("one page per quiz")
+        n = len(quizzes)
+        qs = (ctypes.c_int64 * max(n, 1))(*quizzes)
+        counts = (ctypes.c_int64 * max(n, 1))(*[len(p) for p in pages])
+        arr, total = self.to_c_answered_questions([aq for p in pages for aq in p])
+        out = (ctypes.c_double * max(total, 1))() if likelihoods else None
+        if rows is None:
+            _check(_lib.PqaEngine_RecordAnswerPageBatch(self.c_engine, n, qs, counts, arr, out))
+        else:
+            _check(_lib.PqaEngine_RecordAnswerPageBatchFromRows(self.c_engine, n, qs, counts, arr, out, ctypes.c_void_p(rows or None)))
+        if not likelihoods:
+            return None
+        res, at = [], 0
+        for p in pages:
+            res.append(list(out[at:at + len(p)]))
+            at += len(p)
+        return res
+
+    def record_answer_page_batch(self, quizzes, pages, likelihoods: bool = False):
+        """Quiz quizzes[i] receives the answers of pages[i] (a list of AnsweredQuestion, GLOBAL question ids; given as
+        resume_quiz_batch takes its lists), in order, in one launch per 256 quizzes: what set_active_question + record_answer per
+        answer leave, bit for bit.  All or none.  likelihoods: returns, per quiz, each step's total -- the predictive probability of
+        the answer that was given -- instead of None."""
+        return self._record_pages(quizzes, pages, likelihoods, None)
+
+    def record_answer_page(self, i_quiz: int, page, likelihoods: bool = False):
+        """record_answer_page_batch for one quiz: None, or the list of its steps' likelihoods."""
+        res = self._record_pages([i_quiz], [page], likelihoods, None)
+        return res[0] if likelihoods else None
+
+    def record_answer_page_batch_from_rows(self, quizzes, pages, rows: int, likelihoods: bool = False):
+        """record_answer_page_batch on a shard, with the rows of the questions other shards hold read from the package at
+        device-visible address `rows`; its slots count through the answers of all pages, in order (pack_answer_rows)."""
+        return self._record_pages(quizzes, pages, likelihoods, rows or 0)
 
     # ---- selection parts: the sampled selector on a shard that a process of its own drives (include/PqaHipExt.h) ----------
     def sampled_part_bytes(self) -> int:
